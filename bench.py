@@ -6,7 +6,7 @@ Metric (BASELINE.json): Mrays/s at 1920x1080, 8 bounces, on the 1,000,000-triang
 one sample per pixel through PathTracer::path_trace (streaming mode).  1 ray = 1 closest-hit query,
 primary rays included.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|2|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|2|5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) starts its own N ranks: a child
@@ -24,7 +24,14 @@ cheap, terrain rows expensive, so contiguous bands would be unbalanced), one pro
 collective during tracing; the ranks' radiance is gathered to rank 0 over RCCL once, at present time, inside the
 timed region, and scattered back into frame order there.  Fixed total work -> "scaling": "strong".
 
-Prints ONE JSON line on rank 0 with the contract fields plus:
+A plain run sets up, warms up, times --steps frames and prints ONE JSON line on rank 0: the contract fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step) with the run's config and, N > 1, every rank's
+rays and time (ranks), and rccl_ranks (the sum of a device all-reduce of ones over the process group whose backend reports
+"nccl", asserted == N; 0 in a gloo rehearsal) and distinct_devices (distinct PCI identities among the ranks' GPUs, asserted
+== N outside a rehearsal).  --dump-outputs DIR then writes what the timed path handed over after its last step as
+DIR/<name>.npy (float32; config 3 and 2: color, plus normal and depth on one GPU; config 5: final, rgba), from the same
+inputs on every run with the same arguments.  Everything else is measured only with --full:
+
   roofline      dominant kernel = the closest-hit (trace) kernel k_traverse4.
                 achieved = SURVEY 8(d)'s ALGORITHMIC bytes of all its launches in the timed region / their summed
                 duration (HIP events on the kernel's stream, recorded inside libptcore around every launch).
@@ -42,15 +49,14 @@ Prints ONE JSON line on rank 0 with the contract fields plus:
                 cpu_baseline): mse, bit_exact, live counts and ray count equal.  N > 1 (and --share-of N): EVERY rank's
                 rows against the oracle's rendering of that rank (orc_render_streaming_interleaved: interleaved blocks,
                 per-rank numbering, slot_offset = rank * W * H), rank 0's first (timed: cpu_baseline), the others' after it.
-  rccl_ranks    N > 1: the sum of a device all-reduce of ones over the process group whose backend reports "nccl"
-                (asserted == N; 0 in a gloo rehearsal); distinct_devices = distinct PCI identities among the ranks' GPUs
-                (asserted == N outside a rehearsal).
+  gather        N > 1: the present-time gather on its own, over RCCL and over the library's inter-process pull.
   steady_state  the same workload with 32 frames per launch and 256 steps (the tuned schedule; the timed region
                 above runs exactly --steps frames, which the driver sets to 20).
   latency       ms per frame when frames are strictly serial (one frame in flight) and in the viewer pattern
                 (present after every iteration; eight one-frame slots).
   cpu_baseline  the CPU oracle (oracle/, kind "port": the reference has no CPU path) timed on this box's cores on
                 a bounded sample of the same workload (rank 0, N=1 only).
+  (N = 1)       rank_share, scaling_projection, reference_order_gpu and other_configs (see extra_legs).
 """
 import argparse
 import json
@@ -106,7 +112,35 @@ def parse():
     ap.add_argument("--cpu-frames", type=int, default=8, help="iterations the CPU oracle renders (cpu_baseline sample and parity frame): "
                                                                "8 full frames are about 15 s on 16 threads")
     ap.add_argument("--cpu-threads", type=int, default=16, help="oracle threads (the GPU box's CPU share for one GPU is 16)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the timed path handed over in its last step as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline (instrumented re-run), parity against "
+                         "and timing of the CPU oracle, steady state, latency, the gather on its own (N > 1) and the extra legs")
+    args = ap.parse_args()
+    if not args.full:   # a plain run does only what the headline needs
+        args.no_cpu_baseline = args.no_extras = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000   # all files of one --dump-outputs, .npy headers included
+NPY_HEADER_BYTES = 4096         # allowance per file (np.save writes 128 bytes for these arrays)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: arrays {name: [rows, w(, c)]} -> out_dir/<name>.npy in float32.  If the planes would take more than
+    DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of its pixels (in pixel order) instead."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - NPY_HEADER_BYTES * len(arrays)
+    for name, a in arrays.items():
+        if total > budget:
+            px = a.reshape(a.shape[0] * a.shape[1], -1)
+            keep = np.sort(np.random.default_rng(0).choice(len(px), len(px) * budget // total, replace=False))
+            a = px[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def pmc_record(name, frames_per_launch):
@@ -237,24 +271,27 @@ def _gather_floats(dist, group, world, value):
 _SCENES = {}
 
 
-def config3_scene(pkg, W, H, grid):
+def config3_scene(pkg, W, H, grid, host_bvh=True):
     """The benchmark scene, its flattened arrays and the host-built reference BVH (the tree the CPU oracle walks), built once
-    per process: the extra legs of a run (rank_share, reference_order_gpu, config 5) reuse them."""
+    per process: the extra legs of a run (rank_share, reference_order_gpu, config 5) reuse them.  host_bvh=False (a plain
+    run, whose tracer builds its own on the GPU) leaves flat.bvh and the depth None until a caller asks for them."""
     key = (W, H, grid)
     if key not in _SCENES:
         nx, nz = (int(v) for v in grid.split("x"))
         scene = pkg.scenes.heightfield_scene((W, H), nx=nx, nz=nz)
-        flat = scene.build_scene()
+        _SCENES[key] = [scene, scene.build_scene(), None, None]
+    scene, flat, bvh_depth, _ = entry = _SCENES[key]
+    if host_bvh and flat.bvh is None:
         mesh = list(scene.mesh_map_.values())[0]
         t0 = time.perf_counter()
-        flat.bvh, bvh_depth = pkg.bvh_from_mesh(mesh)       # host builder: the tree the CPU oracle walks (parity, cpu_baseline)
-        _SCENES[key] = (scene, flat, bvh_depth, time.perf_counter() - t0)
-    return _SCENES[key]
+        flat.bvh, entry[2] = pkg.bvh_from_mesh(mesh)       # host builder: the tree the CPU oracle walks (parity, cpu_baseline)
+        entry[3] = time.perf_counter() - t0
+    return tuple(entry)
 
 
 def run_config3(args, pkg, torch, dist, world, rank, local_rank, rehearse, ctl=None):
     W, H, MB = args.width or 1920, args.height or 1080, args.max_bounces
-    scene, flat, bvh_depth, bvh_build_s = config3_scene(pkg, W, H, args.grid)
+    scene, flat, bvh_depth, bvh_build_s = config3_scene(pkg, W, H, args.grid, host_bvh=args.full)
     import copy
     bare = copy.copy(flat)
     bare.bvh = None   # the tracer gets the scene as the reference's front end hands it over: the library builds BVH and layouts (on the GPU)
@@ -451,15 +488,27 @@ def run_config3(args, pkg, torch, dist, world, rank, local_rank, rehearse, ctl=N
         gather_fallback[0] = "RCCL unavailable (%s): the timed region uses --gather ipc, control messages over gloo" % rccl_error
 
     elapsed, rays, prof, first_iter = timed(pt, args.steps, args.warmup)
-    last_live = pt.stats()["last_live"]
+    timed_stats = pt.stats()
+    last_live = timed_stats["last_live"]
+    if flat.bvh is None:   # a plain run: the tree the timed tracer built on the GPU (the host builder's, node for node)
+        bvh_nodes, bvh_depth = timed_stats["bvh_node_count"], timed_stats["bvh_max_depth"]
+    else:
+        bvh_nodes = len(flat.bvh)
     ranks_detail = list(per_rank)
+    if args.dump_outputs and rank == 0:
+        # what a caller holds after the last timed step: the presented radiance (N > 1: the frame assembled on rank 0), and
+        # on one GPU the first-hit normal and depth planes of the same tracer
+        outputs = {"color": (frame if world > 1 else band_color).cpu().numpy()}
+        if world == 1:
+            outputs.update((k, pt.download(k)) for k in ("normal", "depth"))
+        dump_outputs(args.dump_outputs, outputs)
 
     # N > 1: the present-time gather on its own (SURVEY config 4: "RCCL gather time reported separately").  Both
     # transports, five presents each after the timed region: the torch.distributed gather (RCCL; gloo in a rehearsal)
     # timed with events on rank 0's stream from the first byte leaving to the frame being in row order, and the
     # library's one-kernel pull over mapped peer buffers (ptc_gather_frame, device time from ptc_gather_last_us).
     gather = None
-    if world > 1:
+    if world > 1 and args.full:
         gather = {"bytes_per_present": int(sum(len(rr) for rr in rank_rows[1:]) * W * 12),
                   "transport_in_timed_region": args.gather, "backend": "gloo (rehearsal)" if rehearse else "nccl (RCCL)",
                   "fallback": gather_fallback[0]}
@@ -537,7 +586,7 @@ def run_config3(args, pkg, torch, dist, world, rank, local_rank, rehearse, ctl=N
         else:
             gather["ipc_us"], gather["ipc_note"] = None, "library gather unavailable here: " + state[0]
         args.gather = saved
-    counted = count_tests(pt, first_iter, args.steps)
+    counted = count_tests(pt, first_iter, args.steps) if args.full else None
     # parity leg, GPU side: THE TRACER THAT WAS JUST TIMED (same context, slots, streams, launch plan) restarted and run
     # for the iterations the CPU oracle renders below; compared bit for bit there
     timed_frames = None
@@ -554,12 +603,14 @@ def run_config3(args, pkg, torch, dist, world, rank, local_rank, rehearse, ctl=N
         timed_frames["last_live"] = st["last_live"]
     # (the counter records under profiles/ were taken on the default workload with the default kernel)
     pmc_scene = args.grid == "1001x501" and (W, H, MB) == (1920, 1080, 8) and args.trace_variant in (-1, 3) and split == 1
-    roofline = trace_roofline(prof, counted, list(prof["paths"]), MB, elapsed, batch, pmc_scene=pmc_scene,
-                              pixels=W * H // split, frames=args.steps)
+    roofline = walked_total = None
+    if args.full:
+        roofline = trace_roofline(prof, counted, list(prof["paths"]), MB, elapsed, batch, pmc_scene=pmc_scene,
+                                  pixels=W * H // split, frames=args.steps)
+        walked_total = roofline["rays_walked_by_the_launches"]
+        if world > 1:   # every rank's traversal launches
+            walked_total = int(sum(_gather_floats(dist, ctl, world, walked_total)))
     slow_rays = sum(prof["slow_rays"])
-    walked_total = roofline["rays_walked_by_the_launches"]
-    if world > 1:   # every rank's traversal launches
-        walked_total = int(sum(_gather_floats(dist, ctl, world, walked_total)))
 
     # the tuned schedule on the same workload (only when the timed region above was too short to show it)
     steady = None
@@ -683,12 +734,13 @@ def run_config3(args, pkg, torch, dist, world, rank, local_rank, rehearse, ctl=N
     if rank != 0:
         return None
     value = rays / elapsed / 1e6
-    roofline["frame_level_frac"] = (roofline.get("frame_level") or {}).get("frac")
+    if roofline is not None:
+        roofline["frame_level_frac"] = (roofline.get("frame_level") or {}).get("frac")
     if steady is not None:
         roofline["steady_state_frame_level_frac"] = steady["frame_level_frac"]
     return {
         "metric": "Mrays/s at 1920×1080, 8 bounces", "value": round(value, 3), "unit": "Mrays/s",
-        "mrays_per_s_walked": round(walked_total / elapsed / 1e6, 3),
+        "mrays_per_s_walked": round(walked_total / elapsed / 1e6, 3) if walked_total is not None else None,
         "value_note": "value counts every closest-hit query (SURVEY 8d); mrays_per_s_walked counts only the rays the traversal launches "
                       "fetched: primary rays whose three world-box tests in k_raygen already say 'sky' are answered there "
                       "(roofline.rays_answered_by_the_list_builder) and never walk the tree",
@@ -697,7 +749,7 @@ def run_config3(args, pkg, torch, dist, world, rank, local_rank, rehearse, ctl=N
         "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"config 3: procedural {len(flat.indices) // 3}-triangle heightfield + 3 spheres, "
                                f"{W}x{H}, {MB} bounces, 1 spp/step, streaming mode",
-                   "triangles": len(flat.indices) // 3, "bvh_nodes": int(len(flat.bvh)), "bvh_depth": int(bvh_depth),
+                   "triangles": len(flat.indices) // 3, "bvh_nodes": int(bvh_nodes), "bvh_depth": int(bvh_depth),
                    "resolution": [W, H], "max_bounces": MB, "frames_in_flight": streams * batch,
                    "frames_per_launch": batch, "ray_sort": args.ray_sort,
                    "schedule_note": ("tuned schedule (32 frames per launch)" if batch == 32 else
@@ -710,7 +762,7 @@ def run_config3(args, pkg, torch, dist, world, rank, local_rank, rehearse, ctl=N
                    "partition": "full frame" if split == 1 else f"rows in blocks of {BLOCK_ROWS} dealt round-robin over {split} ranks; "
                                 f"present-time gather: {args.gather}",
                    "startup": {"scene_upload_ms": startup, "note": "ptc_upload_scene of the scene without BVH: reference BVH (bit-identical "
-                               "to the host builder's) and traversal layouts built on the GPU", "host_bvh_builder_s": round(bvh_build_s, 3)}},
+                               "to the host builder's) and traversal layouts built on the GPU", "host_bvh_builder_s": round(bvh_build_s, 3) if bvh_build_s is not None else None}},
         "roofline": roofline,
         "gather": gather,
         "ranks": ranks_detail or None,
@@ -759,20 +811,24 @@ def run_config2(args, pkg, torch, local_rank):
     rays = pt.stats()["rays_total"] - rays0
     prof = pt.profile()
     last_live = pt.stats()["last_live"]
-    pt.set_profiling(False, True)
-    pt.reset_profile()
-    pt.set_iteration(first_iter)
-    for _ in range(min(args.steps, 4)):
-        pt.path_trace(scene.camera)
-    counted = pt.profile()
-    pt.set_profiling(False, False)
-    # (counter records of this scene: profiles/pmc_*_c2_32.json, taken on the default workload with the default parameters)
-    pmc_scene = (W, H, MB) == (1280, 720, 8) and not args.param and args.trace_variant in (-1, 3)
-    roofline = trace_roofline(prof, counted, list(prof["paths"]), MB, elapsed, batch, pmc_scene=pmc_scene, pixels=W * H, frames=args.steps, pmc_tag="c2_")
-    roofline["kernel"] = roofline["kernel"].replace("k_traverse4 (", "k_traverse4m (both instances of the mesh in one launch per bounce; ")
-    roofline["note"] = ("%.1f node visits per ray: the fixed round trips of a ray (fetch, root, winner's parent box and normal, store) "
-                        "weigh more than its walk" % roofline["node_visits_per_ray"])
-    roofline["frame_level_frac"] = (roofline.get("frame_level") or {}).get("frac")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"color": out.cpu().numpy(), **{k: pt.download(k) for k in ("normal", "depth")}})
+    roofline = None
+    if args.full:
+        pt.set_profiling(False, True)
+        pt.reset_profile()
+        pt.set_iteration(first_iter)
+        for _ in range(min(args.steps, 4)):
+            pt.path_trace(scene.camera)
+        counted = pt.profile()
+        pt.set_profiling(False, False)
+        # (counter records of this scene: profiles/pmc_*_c2_32.json, taken on the default workload with the default parameters)
+        pmc_scene = (W, H, MB) == (1280, 720, 8) and not args.param and args.trace_variant in (-1, 3)
+        roofline = trace_roofline(prof, counted, list(prof["paths"]), MB, elapsed, batch, pmc_scene=pmc_scene, pixels=W * H, frames=args.steps, pmc_tag="c2_")
+        roofline["kernel"] = roofline["kernel"].replace("k_traverse4 (", "k_traverse4m (both instances of the mesh in one launch per bounce; ")
+        roofline["note"] = ("%.1f node visits per ray: the fixed round trips of a ray (fetch, root, winner's parent box and normal, store) "
+                            "weigh more than its walk" % roofline["node_visits_per_ray"])
+        roofline["frame_level_frac"] = (roofline.get("frame_level") or {}).get("frac")
     cpu_baseline = parity = None
     cpu_frames = max(1, min(args.cpu_frames, 4, args.steps))
     if not args.no_cpu_baseline:
@@ -855,7 +911,7 @@ def run_config5(args, pkg, torch, local_rank):
         el = time.perf_counter() - t0
         rays = pt.stats()["rays_total"] - rays0
         prof = pt.profile()
-        if keep:   # what the last timed frame left on the device: iteration 0, denoised -- compared with the oracle below
+        if keep:   # what the last timed frame left on the device: iteration 0, denoised -- compared with the oracle below, dumped
             pt.set_profiling(False, False)
             for k in ("color", "normal", "depth", "final"):
                 checked[k] = pt.download(k)
@@ -864,8 +920,10 @@ def run_config5(args, pkg, torch, local_rank):
         pt.close()
         return el, rays, prof
 
-    el, rays, prof = loop(True, args.steps, args.warmup, not args.no_events, keep=not args.no_cpu_baseline)
-    el_nd, _, _ = loop(False, args.steps, args.warmup, False)
+    el, rays, prof = loop(True, args.steps, args.warmup, not args.no_events, keep=not args.no_cpu_baseline or bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"final": checked["final"], "rgba": checked["rgba"]})
+    el_nd = loop(False, args.steps, args.warmup, False)[0] if args.full else None
     passes = max(prof["denoise_passes"], 1)
     den_ms_pass = prof["denoise_ms"] / passes
     # HBM-side algorithmic bytes of one pass: colour 16 + normal/depth 16 + position 16 read, 16 written per pixel
@@ -931,7 +989,7 @@ def run_config5(args, pkg, torch, local_rank):
         "config": {"workload": f"config 5: config 3's scene ({len(flat.indices) // 3} triangles), {W}x{H}, {MB} bounces, every frame = "
                                "restart + 1 spp + 4-pass A-Trous (filter_size 10, .45/.30/.25) + present; G-buffer in HBM",
                    "resolution": [W, H], "max_bounces": MB, "rays_per_step": round(rays / args.steps),
-                   "ms_per_frame_without_denoise": round(el_nd / args.steps * 1e3, 4),
+                   "ms_per_frame_without_denoise": round(el_nd / args.steps * 1e3, 4) if el_nd is not None else None,
                    "denoise_ms_per_frame_kernel_time": round(prof["denoise_ms"] / args.steps, 4),
                    "denoise_ms_per_pass": round(den_ms_pass, 4), "mrays_per_s": round(rays / el / 1e6, 1)},
         "roofline": roofline, "parity": parity, "cpu_baseline": cpu_baseline,
@@ -1010,6 +1068,7 @@ def extra_legs(args, pkg, torch, dist, local_rank, line):
     def sub(**over):
         a = copy.copy(args)
         a.param = list(args.param)
+        a.dump_outputs = ""   # --dump-outputs holds the headline's timed path only
         for k, v in over.items():
             setattr(a, k, v)
         return a

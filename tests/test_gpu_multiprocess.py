@@ -83,7 +83,7 @@ def test_band_handle_geometry_is_checked_on_import(pkg):
 
 
 def test_bench_starts_its_own_ranks():
-    """`python3 bench.py --gpus 2 --rehearse-on-one-gpu --steps 20 --warmup 5` with no launcher around it: bench.py
+    """`python3 bench.py --gpus 2 --rehearse-on-one-gpu --steps 20 --warmup 5 --full` with no launcher around it: bench.py
     spawns its two ranks itself (a child torch.distributed.run, before the parent touches the GPU) and rank 0 prints
     ONE line with n_gpus 2, the gather time on its own, and both ranks' rays.  Without --rehearse-on-one-gpu the same
     request on this one-GPU box must fail loudly instead of measuring one GPU."""
@@ -91,7 +91,7 @@ def test_bench_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "20", "--warmup", "5",
-           "--no-extras"]
+           "--full", "--no-extras"]
     proc = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith('{"metric"')]

@@ -1,8 +1,6 @@
 """The reference's OWN scene files through both front-ends (Python json_parser.py, C++ host/scene_description.cpp via
-hip_pt --dump-scene): /root/reference/assets/scenes/{bunny,ajax-white,three_balls}.json.
-
-They are read where they lie (this container only; the test skips where /root/reference does not exist, e.g. on the GPU
-box) and never copied into the repository.  Their meshes are git-LFS pointers, so `../models/*.obj` is served by this
+hip_pt --dump-scene): the reference's assets/scenes/{bunny,ajax-white,three_balls}.json, stored unchanged as test
+fixtures under tests/golden/reference_scenes/.  Their meshes are git-LFS pointers, so `../models/*.obj` is served by this
 repository's small stand-in OBJ; what is pinned is the GRAMMAR (assets/json_parser.cpp:40-95,174-224): a transform array
 applies its commands left to right as elem * mat, from/at/up builds the camera frame, vfov is in degrees, materials are
 indexed in name order, "background" / "accelerator" are ignored, and three_balls.json's camera key "o" is an error in
@@ -17,10 +15,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SCENES = "/root/reference/assets/scenes"
+REF_SCENES = os.path.join(ROOT, "tests", "golden", "reference_scenes")
 HIP_PT = os.path.join(ROOT, "cuda-path-tracer_amd", "host", "hip_pt")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SCENES), reason="the reference checkout is not on this machine")
 
 
 def T(v):

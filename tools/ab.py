@@ -80,7 +80,7 @@ def main():
     for rep in range(a.reps):
         for (label, args), combo, (tag, lib) in itertools.product(cases, itertools.product(*sweeps) if sweeps else [()], libs):
             extras = "--extras" in args
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-frames", "1"] + ([] if extras else ["--no-extras"])
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-frames", "1"] + ([] if extras else ["--no-extras"])
             cmd += [x for x in args if x != "--extras"]
             for name, v in combo:
                 cmd += ["--param", "%s=%s" % (name, v)]

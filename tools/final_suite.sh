@@ -4,11 +4,11 @@
 TAG=${1:?tag}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 timeout -k 10 600 python -m pytest tests -x -q -m gpu > $OUT/tests.log 2>&1 || { tail -5 $OUT/tests.log; exit 1; }
 tail -1 $OUT/tests.log
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_steps20.log 2>&1 || exit 1
-timeout -k 10 300 python bench.py > $OUT/bench_default.log 2>&1 || exit 1
-timeout -k 10 300 python bench.py --config 2 > $OUT/bench_config2.log 2>&1 || exit 1
-timeout -k 10 300 python bench.py --config 5 > $OUT/bench_config5.log 2>&1 || exit 1
-timeout -k 10 300 python bench.py --gpus 2 --rehearse-on-one-gpu --steps 20 --warmup 5 > $OUT/bench_rehearse2.log 2>&1 || exit 1
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_steps20.log 2>&1 || exit 1
+timeout -k 10 300 python bench.py --full > $OUT/bench_default.log 2>&1 || exit 1
+timeout -k 10 300 python bench.py --full --config 2 > $OUT/bench_config2.log 2>&1 || exit 1
+timeout -k 10 300 python bench.py --full --config 5 > $OUT/bench_config5.log 2>&1 || exit 1
+timeout -k 10 300 python bench.py --full --gpus 2 --rehearse-on-one-gpu --steps 20 --warmup 5 > $OUT/bench_rehearse2.log 2>&1 || exit 1
 SUMMARY_FLAGS="--timeline 20" tools/profile_bench.sh $TAG/prof20 --steps 20 --warmup 5 > /dev/null 2>&1
 tools/profile_bench.sh $TAG/profdef > /dev/null 2>&1
 tools/profile_bench.sh $TAG/profc2 --config 2 > /dev/null 2>&1

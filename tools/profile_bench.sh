@@ -7,7 +7,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-extras "$@" > "$OUT/bench.log" 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras "$@" > "$OUT/bench.log" 2>&1
 rc=$?
 cd "$ROOT"
 python3 tools/rocpd_summary.py "$(ls "$OUT"/prof/*.db | head -1)" $SUMMARY_FLAGS --tail "k_traverse4<false:8" > "$OUT/kernel_stats.txt" 2>&1
