@@ -1447,6 +1447,9 @@ int orc_denoise(const OCamera* cam, uint32_t w, uint32_t h, const float* color, 
  * ---------------------------------------------------------------------------------------------- */
 static inline uint8_t color_float_to_255(float v)
 {
+  /* NaN (a zero denoiser weight, the power of a negative value) passes the clamp unchanged, and converting it to an
+   * integer is undefined in C: it shows as 0, what the GPU's float-to-integer conversion gives for it */
+  if (v != v) return 0;
   const float cl = fmin_sel(fmax_sel(v, 0.f), 1.f); /* glm::clamp = min(max(x, lo), hi) */
   return (uint8_t)(cl * 255.99f);
 }

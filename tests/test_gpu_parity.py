@@ -175,8 +175,9 @@ def test_megakernel_against_oracle(pkg, orc, golden_dir):
 
 def test_denoise_and_preview_against_oracle(pkg, orc):
     """denoising_kernel x4 passes + preview_kernel.  expf/powf come from different math libraries on the
-    two sides, so these are tolerance checks: |d| <= 1e-5 on the denoised radiance, 1 LSB on RGBA8.
-    Pixels whose value depends on the reference's out-of-bounds row H are excluded (undefined there)."""
+    two sides, so these are tolerance checks: |d| <= 1e-5 on the denoised radiance, 1 LSB on RGBA8, on every pixel --
+    those whose value depends on the reference's out-of-bounds row H included: the port and the oracle define those taps
+    the same way.  The pixels that do not depend on them are also checked on their own."""
     scene = pkg.scenes.heightfield_scene((96, 64), nx=65, nz=33)
     flat = scene.build_scene()
     out = render(pkg, scene, flat, 96, 64, 2, 8, denoise=True)
@@ -190,6 +191,8 @@ def test_denoise_and_preview_against_oracle(pkg, orc):
     got = out["rgba"]
     assert np.max(np.abs(got[ok].astype(int) - want[ok].astype(int))) <= 1
     assert np.all(got[..., 3] == 255)
+    assert np.max(np.abs(out["final"] - den)) <= 1e-5                       # every pixel
+    assert np.max(np.abs(got.astype(int) - want.astype(int))) <= 1
     with pkg.PathTracer(max_bounces=8) as pt:
         pt.create_buffers((96, 64), flat)
         pt.path_trace(scene.camera)
@@ -206,8 +209,9 @@ def test_denoise_and_preview_against_oracle(pkg, orc):
 def test_denoise_kernels_against_oracle(pkg, orc, size):
     """Both A-Trous kernels (taps staged in LDS per sub-lattice = the default; taps through L1 / L2) against the oracle:
     config 5's size, and a size that is no multiple of any tile or step (partial sub-lattice tiles, the clamped taps of
-    every border).  Tolerance 1e-5 on the radiance (expf differs between the math libraries); pixels that depend on the
-    reference's out-of-bounds row H are excluded."""
+    every border).  Tolerance 1e-5 on the radiance (expf differs between the math libraries), on every pixel and, on
+    their own, on the pixels that do not depend on the reference's out-of-bounds row H.  The whole parameter range:
+    tests/test_gpu_denoise.py."""
     w, h = size
     scene = pkg.scenes.heightfield_scene((w, h), nx=257, nz=129)
     flat = scene.build_scene()
@@ -229,7 +233,9 @@ def test_denoise_kernels_against_oracle(pkg, orc, size):
     for variant, out in enumerate(outs):
         err = float(np.max(np.abs(out[ok] - den[ok])))
         assert err <= 1e-5, (variant, err)
-    assert float(np.max(np.abs(outs[0] - outs[1]))) <= 1e-5   # including the pixels the oracle leaves undefined
+        err = float(np.max(np.abs(out - den)))
+        assert err <= 1e-5, (variant, err)                     # every pixel
+    assert float(np.max(np.abs(outs[0] - outs[1]))) <= 1e-5
 
 
 def test_api_semantics(pkg, golden_dir):

@@ -25,6 +25,22 @@ SCRIPT = {"window": [64, 48], "iterations_per_frame": 2, "events": [
     {"frames": 2}]}
 
 
+# a third script: the filter size changed while denoising -- one pass, then steps 1..64 (k_denoise_lds<1..32> and the
+# L1 / L2 kernel at step 64) -- and back to the default; a camera move and a resize in between
+SCRIPT3 = {"window": [48, 36], "iterations_per_frame": 1, "events": [
+    {"denoise": True}, {"frames": 1}, {"filter_size": 1}, {"frames": 2}, {"filter_size": 64}, {"frames": 1},
+    {"key": "W"}, {"frames": 1}, {"resize": [33, 50]}, {"frames": 1}, {"filter_size": 10}, {"frames": 1},
+    {"filter_size": 64}, {"denoise": False}, {"frames": 1}]}
+
+
+def assert_denoised_frame(got, want, what):
+    """a denoised frame on every pixel, the bottom rows included: within 1 LSB of the oracle's, opaque"""
+    assert got.shape == want.shape, what
+    diff = np.abs(got.astype(np.int32) - want.astype(np.int32))
+    assert int(diff.max()) <= 1, (what, int(diff.max()))
+    assert np.all(got[..., 3] == 255), what
+
+
 def _ensure_cli():
     if not os.path.exists(HIP_PT):
         subprocess.run(["make"], cwd=os.path.dirname(HIP_PT), check=True, stdout=subprocess.DEVNULL)
@@ -130,8 +146,10 @@ def oracle_replay(pkg, orc, scene, script, max_bounces):
     while iteration_ < max_iterations and always re-points the result at the colour buffer (:391,:476); `denoise` filters
     the ACCUMULATED buffers and makes its output the result (:479-485); `restart` zeroes the counter (:522-525);
     `resize_image` reallocates and restarts (:527-545); `send_to_preview` shows the result, the normals or 1/depth
-    (:487-520).  Returns [(rgba, exact_mask)]: exact_mask marks the pixels whose value does not depend on the reference's
-    out-of-bounds A-Trous taps (all of them for an undenoised frame)."""
+    (:487-520); a `filter_size` event sets the denoiser's filter size (gui.cpp:87).  Returns [(rgba, exact_mask,
+    denoised)]: exact_mask marks the pixels whose value does not depend on the reference's out-of-bounds A-Trous taps
+    (all of them for an undenoised frame).  The oracle defines those taps as the port does, so a denoised frame is
+    compared on every pixel too."""
     import copy
     window = tuple(int(v) for v in script.get("window", (800, 800)))
     per_frame = int(script.get("iterations_per_frame", 1))
@@ -140,7 +158,7 @@ def oracle_replay(pkg, orc, scene, script, max_bounces):
     flat = scene.build_scene()
     sh = orc.SceneHandle(flat)
     st = {"iteration": 0, "max_iterations": scene.spp, "method": "streaming", "denoise": False, "display": "final",
-          "res": window, "fb": None, "result": None, "touched": None}
+          "res": window, "fb": None, "result": None, "touched": None, "filter_size": 10}
     shown = []
 
     def path_trace():
@@ -155,7 +173,7 @@ def oracle_replay(pkg, orc, scene, script, max_bounces):
     def denoise():
         w, h = st["res"]
         fb = st["fb"]
-        st["result"], st["touched"] = orc.denoise(camera, w, h, fb["color"], fb["normal"], fb["depth"])
+        st["result"], st["touched"] = orc.denoise(camera, w, h, fb["color"], fb["normal"], fb["depth"], st["filter_size"])
 
     def turn():
         for _ in range(per_frame):
@@ -198,6 +216,8 @@ def oracle_replay(pkg, orc, scene, script, max_bounces):
             st["method"] = ev["method"]
         elif "max_iterations" in ev:
             st["max_iterations"] = max(1, int(ev["max_iterations"]))
+        elif "filter_size" in ev:
+            st["filter_size"] = int(ev["filter_size"])
         elif "speed" in ev:
             controller.speed = np.float32(ev["speed"])
         elif "position" in ev:
@@ -215,8 +235,8 @@ def oracle_replay(pkg, orc, scene, script, max_bounces):
 @pytest.mark.gpu
 def test_replay_frames_against_the_oracle(pkg, orc):
     """Every frame the replayed viewer displays, against the CPU oracle driven through the same script: exact for
-    undenoised frames (final, normal view, megakernel), within 1 LSB for denoised ones on the pixels that do not
-    depend on the reference's out-of-bounds taps.  Round 3 compared the two front-ends with each
+    undenoised frames (final, normal view, megakernel), within 1 LSB for denoised ones on every pixel, and on the
+    pixels that do not depend on the reference's out-of-bounds taps also with few differing.  Round 3 compared the two front-ends with each
     other only -- the same HIP path twice."""
     scene = pkg.json_parser.scene_from_json(os.path.join(ROOT, "assets", "scenes", "cornell_mesh.json"))
     frames, _ = pkg.viewer.replay(scene, SCRIPT, max_bounces=6)
@@ -231,6 +251,7 @@ def test_replay_frames_against_the_oracle(pkg, orc):
             diff = np.abs(got.astype(np.int32) - rgba.astype(np.int32))[exact]
             assert int(diff.max()) <= 1, (i, int(diff.max()))
             assert float((diff > 0).mean()) < 0.02, i
+            assert_denoised_frame(got, rgba, i)
         else:
             assert np.array_equal(got, rgba), (i, int(np.sum(got != rgba)))
     assert denoised_frames == 4                      # three turns with max_iterations reached + the megakernel frame
@@ -276,3 +297,32 @@ def test_replay_frames_cpp_equals_python(pkg, tmp_path):
     # Space + megakernel: another image (another RNG stream per pixel, path_tracer.cu:239-243)
     assert not np.array_equal(frames[9], frames[8])
     assert np.all(frames[5][..., 3] == 255)   # the normal view is opaque
+
+
+@pytest.mark.gpu
+def test_replay_filter_size_changes(pkg, orc, tmp_path):
+    """SCRIPT3 (the `filter_size` event, mid-run): the C++ replay's PNG sequence equals the Python replay's frames, and
+    every frame equals the oracle's driven through the same script -- exact when undenoised, within 1 LSB on every pixel
+    when denoised"""
+    from PIL import Image
+    _ensure_cli()
+    script = tmp_path / "replay3.json"
+    script.write_text(json.dumps(SCRIPT3))
+    prefix = tmp_path / "view3"
+    r = subprocess.run([HIP_PT, "scenes/cornell_mesh.json", "--replay", str(script), "-o", str(prefix), "--max-bounces", "5"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout + r.stderr
+    scene = pkg.json_parser.scene_from_json(os.path.join(ROOT, "assets", "scenes", "cornell_mesh.json"))
+    frames, _ = pkg.viewer.replay(scene, SCRIPT3, max_bounces=5)
+    want = oracle_replay(pkg, orc, scene, SCRIPT3, 5)
+    shown = sum(ev.get("frames", 0) for ev in SCRIPT3["events"])
+    assert len(frames) == len(want) == shown == 8 and f"{shown} frames shown" in r.stdout
+    for i, got in enumerate(frames):
+        png = np.array(Image.open(f"{prefix}_{i:04d}.png"))
+        assert png.shape == got.shape and np.array_equal(png, got), i
+    assert [d for _, _, d in want] == [True] * 7 + [False]
+    for i, (got, (rgba, exact, denoised)) in enumerate(zip(frames, want)):
+        if denoised:
+            assert_denoised_frame(got, rgba, i)
+        else:
+            assert np.array_equal(got, rgba), (i, int(np.sum(got != rgba)))
