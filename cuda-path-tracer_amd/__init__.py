@@ -7,9 +7,9 @@ under the module name ``cuda_path_tracer_amd``.  All rendering happens in ``libp
 from . import _capi, bands, camera_controller, glmlite, json_parser, scenes, viewer
 from ._capi import LIB_PATH, PtcError, lib
 from .path_tracer import DisplayBufferType, EdgeAvoidingATrousDenoiser, GPUMethod, PathTracer
-from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, FlatScene, Mesh, MetalMaterial,
+from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, EmissiveMaterial, FlatScene, Mesh, MetalMaterial,
                                 SceneDescription, Sphere, bvh_from_mesh)
 
 __all__ = ["PathTracer", "GPUMethod", "DisplayBufferType", "EdgeAvoidingATrousDenoiser", "SceneDescription", "Camera",
-           "Sphere", "Mesh", "DiffuseMateral", "MetalMaterial", "DielectricMaterial", "FlatScene", "bvh_from_mesh",
+           "Sphere", "Mesh", "DiffuseMateral", "MetalMaterial", "DielectricMaterial", "EmissiveMaterial", "FlatScene", "bvh_from_mesh",
            "scenes", "bands", "glmlite", "json_parser", "lib", "LIB_PATH", "PtcError"]

@@ -377,13 +377,13 @@ void launch_sort_octant(hipStream_t s, const uint8_t* octs, uint32_t* order, uin
                         DeviceCounters* counters, const DBatchInfo& bi);
 void launch_tail_count(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths paths,
                        DHits hits, uint32_t max_paths, int bounce, uint32_t* chunk_counts, DeviceCounters* counters,
-                       const DBatchInfo& bi);
+                       const DBatchInfo& bi, bool emitters = false);
 void launch_scan(hipStream_t s, int bounce, bool last_bounce, const uint32_t* chunk_counts, uint32_t* chunk_offsets,
                  DeviceCounters* counters, const DBatchInfo& bi);
 void launch_shade(hipStream_t s, const DScene& scene, DPaths in, DPaths out, DHits hits, uint32_t max_paths,
                   bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                   const uint32_t* chunk_offsets, DFrame fb, DBand band, DeviceCounters* counters, uint8_t* octs,
-                  const DBatchInfo& bi);
+                  const DBatchInfo& bi, bool emitters = false);
 // the end of a bounce in one pass (k_shade_fused): trailing sphere run [obj_begin, obj_end) + material + stable compaction +
 // final gather.  tile_desc: shade_tiles_per_frame(max_paths) descriptors per frame of the batch (tile_stride apart), zero
 // at allocation and never cleared; epoch: a number no earlier launch on these descriptors has used (1 .. 2^30 - 1).
@@ -393,7 +393,7 @@ void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, 
                         DHits hits, uint32_t max_paths, bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                         unsigned long long* tile_desc, uint32_t tile_stride, uint32_t epoch, DFrame fb, DBand band,
                         DeviceCounters* counters, uint8_t* octs, const DBatchInfo& bi, const uint32_t* list = nullptr,
-                        const DNextRun* next = nullptr);
+                        const DNextRun* next = nullptr, bool emitters = false);
 // "prefold" at bounce 0: ray generation that also walks the sphere run in front of bounce 0's first mesh launch (next.hits: the
 // CURRENT bounce's records here) and leaves the bytes for launch_list_flags
 void launch_raygen_next(hipStream_t s, const DScene& scene, const DCameras& cams, const DBatchInfo& bi, DBand band, uint32_t pix_count, DPaths paths,
@@ -407,10 +407,10 @@ void launch_accumulate(hipStream_t s, DFrame stage, DFrame fb, uint32_t pix_coun
 // the bounce-spanning persistent launch (pt_kernels.hip, k_persist): state set-up (k_persist_init) + the launch, `waves` wavefronts;
 // spheres: the object list ends in a sphere run (pa.tail_begin / tail_end); listed0: bounce 0's shade pass walks pa.list0
 void launch_persist(hipStream_t s, const DScene& scene, uint32_t obj_index, DHits hits, DeviceCounters* counters, const DBatchInfo& bi,
-                    const DPersistArgs& pa, uint32_t waves, bool spheres, bool listed0);
+                    const DPersistArgs& pa, uint32_t waves, bool spheres, bool listed0, bool emitters = false);
 uint32_t persist_tiles_per_frame(uint32_t max_paths);
 void launch_megakernel(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band,
-                       uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters);
+                       uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters = false);
 void launch_preview(hipStream_t s, const float4* buf, uint32_t pix_count, int mode, uint32_t* rgba);
 void launch_pack(hipStream_t s, const float4* buf, uint32_t pix_count, int which, float* dst);
 // the bands of one multi-GPU gather launch (k_gather_bands): up to kGatherBands sources per launch

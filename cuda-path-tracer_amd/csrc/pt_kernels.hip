@@ -182,6 +182,8 @@ void k_traverse4(DScene sc, uint32_t obj_index, DPaths paths, DHits hits, int bo
 
 // path_tracing_mega_kernel, path_tracer.cu:227-269: the whole path in one thread, one RNG stream per
 // pixel (a different image from streaming mode at the same seed -- a property of the reference).
+// kEmit: the scene has an emissive material (the host's choice; without one the instance is the reference's loop as it was).
+template <bool kEmit>
 __global__ __launch_bounds__(kWave) void k_megakernel(DScene sc, DCamera cam, uint32_t iteration, DBand band,
                                                       uint32_t pix_count, int max_bounces, DFrame fb,
                                                       DeviceCounters* counters)
@@ -220,6 +222,10 @@ __global__ __launch_bounds__(kWave) void k_megakernel(DScene sc, DCamera cam, ui
         depth = rec.t;
       }
       bool tmin_flag = ray.tmin != 1e-4f;
+      if (kEmit && is_emitter(sc.materials[rec.mat])) {  // the path ends at the emitter: no draw
+        color = emit_color(color, sc.materials[rec.mat]);
+        break;
+      }
       evaluate_material(ray.o, ray.d, tmin_flag, rec.p, rec.n, rec.side, sc.materials[rec.mat], rng, color);
       ray.tmin = tmin_flag ? 1e-5f : 1e-4f;
     }
@@ -309,10 +315,14 @@ void launch_traverse(hipStream_t s, const DScene& scene, uint32_t obj_index, boo
   }
 }
 void launch_megakernel(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band,
-                       uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters)
+                       uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters)
 {
-  hipLaunchKernelGGL(k_megakernel, dim3(div_up(pix_count, kWave)), dim3(kWave), 0, s, scene, cam, iteration, band,
-                     pix_count, max_bounces, fb, counters);
+  if (emitters)
+    hipLaunchKernelGGL(k_megakernel<true>, dim3(div_up(pix_count, kWave)), dim3(kWave), 0, s, scene, cam, iteration, band,
+                       pix_count, max_bounces, fb, counters);
+  else
+    hipLaunchKernelGGL(k_megakernel<false>, dim3(div_up(pix_count, kWave)), dim3(kWave), 0, s, scene, cam, iteration, band,
+                       pix_count, max_bounces, fb, counters);
 }
 void launch_intersect(hipStream_t s, const DScene& scene, const float4* rays_o, const float4* rays_d, uint32_t n,
                       DHits hits, DeviceCounters* counters, int variant)

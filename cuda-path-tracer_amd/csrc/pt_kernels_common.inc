@@ -560,6 +560,11 @@ __device__ __forceinline__ float schlick(float cosine, float ref_idx)
   return r0 + (1.0f - r0) * (x4 * x);
 }
 
+// Emissive material (ptc_material type 3, an extension: the reference has no emitters).  A path whose closest hit is an
+// emitter ends there with throughput * emission, written as the miss's throughput * sky; no draw is made for it.
+__device__ __forceinline__ bool is_emitter(const DMaterial& m) { return m.type == 3; }
+__device__ __forceinline__ f3 emit_color(const f3 color, const DMaterial& m) { return color * mk3(m.p[0], m.p[1], m.p[2]); }
+
 // evaluate_material, path_tracer.cu:138-201.  tmin_flag: ray.t_min is 1e-5 from now on (dielectric).
 __device__ __forceinline__ void evaluate_material(f3& ro, f3& rd, bool& tmin_flag, const f3 hp, const f3 hn,
                                                   const uint32_t side, const DMaterial m, Minstd& rng, f3& color)
@@ -612,7 +617,11 @@ __device__ __forceinline__ void evaluate_material(f3& ro, f3& rd, bool& tmin_fla
 //     the kinds' own few operations
 // A lane executes exactly the operations of its kind's body in evaluate_material / background, on the same operands:
 // the same bits (the frames tests compare this kernel with k_shade's plain form and with the oracle).
-// kind: 0 diffuse, 1 metal, 2 dielectric (Material::type), 3 miss, anything else: nothing to do.
+// kind: 0 diffuse, 1 metal, 2 dielectric (Material::type), 3 miss, 4 emissive (kEmit instances only: material type 3, which
+// the caller maps to kKindEmit -- its material's type would read as "miss" here), anything else: nothing to do.  An emissive
+// hit makes no draw and touches neither ray nor tmin_flag: the path ends with color * emission (emit_color).
+constexpr uint32_t kKindMiss = 3u, kKindEmit = 4u;
+template <bool kEmit = false>
 __device__ __forceinline__ void shade_kinds(const uint32_t kind, f3& ro, f3& rd, bool& tmin_flag, const f3 hp, const f3 hn,
                                             const uint32_t side, const DMaterial m, const uint32_t slot, const uint32_t iteration,
                                             const uint32_t bounce, f3& color)
@@ -676,6 +685,8 @@ __device__ __forceinline__ void shade_kinds(const uint32_t kind, f3& ro, f3& rd,
   } else if (kind == 3u) {
     const float t = 0.5f * (unit.y + 1.0f);  // background(), path_tracer.cu:29-34
     color = color * (mk3(0.5f, 0.7f, 1.0f) * (1.0f - t) + mk3(1.0f, 1.0f, 1.0f) * t);
+  } else if (kEmit && kind == kKindEmit) {
+    color = emit_color(color, m);
   }
 }
 

@@ -37,7 +37,8 @@ namespace pt {
 #ifndef PT_SERVICE_TILES
 #define PT_SERVICE_TILES 1u
 #endif
-template <bool kSpheres>
+template <bool kSpheres, bool kEmit>
+// kEmit: the scene has an emissive material (shade_tile).
 // dedicated: a service wavefront proper (stays until every frame is done, sleeps when there is nothing to shade); else a walking
 // wavefront that found no rays to hand out: it shades up to `budget` tiles and goes back to look for rays.  Returns < 0 when
 // every frame is done (or the launch has given up), else the tiles it shaded.
@@ -147,7 +148,7 @@ __device__ __forceinline__ int persist_service(const DScene& sc, const uint32_t 
       const int last = (int)bounce == pa.max_bounces - 1 ? 1 : 0;
 #pragma unroll 1
       for (uint32_t tile = first; tile < end_tile; ++tile)
-        shade_tile<kSpheres, false, 1, true>(sc, pa.tail_begin, pa.tail_end, in, out, h, pa.staged, (int)bounce, last, pa.slot_base,
+        shade_tile<kSpheres, false, 1, true, false, kEmit>(sc, pa.tail_begin, pa.tail_end, in, out, h, pa.staged, (int)bounce, last, pa.slot_base,
                                              pa.tile_desc + (size_t)frame * pa.tile_stride, pa.epoch0 + bounce, fb, pa.band, ctr, nullptr, bi.iteration[frame],
                                              list ? list + fo : nullptr, fo, tile, tiles, n, n_all, s_cnt, &s_excl);
       // ---- sign the tiles off; the last sign-off of a pass opens the frame's next traversal phase ----
@@ -247,7 +248,7 @@ __device__ __forceinline__ int persist_service(const DScene& sc, const uint32_t 
   return -1;  // (gave up: the launch's error word is set)
 }
 
-template <bool kSpheres>
+template <bool kSpheres, bool kEmit = false>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PT_T4_WAVES, PT_T4_WAVES)))
 void k_persist(DScene sc, uint32_t obj_index, DHits hits, DeviceCounters* counters, DBatchInfo bi, DPersistArgs pa)
 {
@@ -255,7 +256,7 @@ void k_persist(DScene sc, uint32_t obj_index, DHits hits, DeviceCounters* counte
   if (threadIdx.x == 0u) arrival = __hip_atomic_fetch_add(&pa.st->started, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   arrival = (uint32_t)__builtin_amdgcn_readfirstlane((int)arrival);
   if (arrival % pa.service_every == pa.service_every - 1u) {
-    (void)persist_service<kSpheres>(sc, obj_index, pa, hits, counters, bi, arrival, true, 0u);
+    (void)persist_service<kSpheres, kEmit>(sc, obj_index, pa, hits, counters, bi, arrival, true, 0u);
     return;
   }
   // A walking wavefront: walk while there are rays to hand out; when there are none, shade a few tiles (the service
@@ -266,7 +267,7 @@ void k_persist(DScene sc, uint32_t obj_index, DHits hits, DeviceCounters* counte
   for (uint32_t spins = 0u;;) {
     const int walked = traverse4_walk<false, true, false, true>(sc, obj_index, unused, hits, 0, 0, counters, nullptr, nullptr, bi, false, &pa);
     if (walked < 0) break;
-    const int shaded = pa.help_tiles ? persist_service<kSpheres>(sc, obj_index, pa, hits, counters, bi, arrival, false, pa.help_tiles) : 0;
+    const int shaded = pa.help_tiles ? persist_service<kSpheres, kEmit>(sc, obj_index, pa, hits, counters, bi, arrival, false, pa.help_tiles) : 0;
     if (shaded < 0) break;
     if (shaded > 0) {
       spins = 0u;
@@ -329,12 +330,17 @@ __global__ __launch_bounds__(kWave) void k_persist_init(DPersist* st, DeviceCoun
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
 void launch_persist(hipStream_t s, const DScene& scene, uint32_t obj_index, DHits hits, DeviceCounters* counters, const DBatchInfo& bi,
-                    const DPersistArgs& pa, uint32_t waves, bool spheres, bool listed0)
+                    const DPersistArgs& pa, uint32_t waves, bool spheres, bool listed0, bool emitters)
 {
   hipLaunchKernelGGL(k_persist_init, dim3(1), dim3(kWave), 0, s, pa.st, counters, bi, listed0 ? 1 : 0);
   const dim3 grid(waves), block(kWave);
-  if (spheres) hipLaunchKernelGGL((k_persist<true>), grid, block, 0, s, scene, obj_index, hits, counters, bi, pa);
-  else hipLaunchKernelGGL((k_persist<false>), grid, block, 0, s, scene, obj_index, hits, counters, bi, pa);
+  if (emitters) {
+    if (spheres) hipLaunchKernelGGL((k_persist<true, true>), grid, block, 0, s, scene, obj_index, hits, counters, bi, pa);
+    else hipLaunchKernelGGL((k_persist<false, true>), grid, block, 0, s, scene, obj_index, hits, counters, bi, pa);
+  } else {
+    if (spheres) hipLaunchKernelGGL((k_persist<true>), grid, block, 0, s, scene, obj_index, hits, counters, bi, pa);
+    else hipLaunchKernelGGL((k_persist<false>), grid, block, 0, s, scene, obj_index, hits, counters, bi, pa);
+  }
 }
 uint32_t persist_tiles_per_frame(uint32_t max_paths) { return div_up(max_paths, kServiceTile); }
 }  // namespace pt

@@ -295,10 +295,11 @@ __global__ __launch_bounds__(256) void k_list_flags(const uint8_t* flags, int bo
 // The end of a bounce's closest-hit stage: the sphere run that ends the object list (if any) and the live count of
 // every 64-slot chunk (ballot / popcount of "the hit record holds a hit"), for the compaction scan.
 // kSpheres: objects [obj_begin, obj_end) are tested; kFirst: nothing has written the hit record in this bounce yet.
+// kEmit: the scene has an emissive material; a hit on one ends the path (k_shade) and is not counted live.
 // 256-thread workgroups: one wavefront per SIMD fits beside the other stream's persistent traversal wavefronts as soon
 // as one of those has left (1024-thread workgroups wait until four per SIMD have: measured 15 % slower end to end,
 // together with a scan fused in behind a "last workgroup" sign-off).
-template <bool kSpheres, bool kFirst>
+template <bool kSpheres, bool kFirst, bool kEmit = false>
 __global__ __launch_bounds__(256) void k_tail_count(DScene sc, uint32_t obj_begin, uint32_t obj_end, DPaths paths, DHits hits,
                                                     int bounce, uint32_t* chunk_counts, DeviceCounters* counters, DBatchInfo bi)
 {
@@ -328,12 +329,17 @@ __global__ __launch_bounds__(256) void k_tail_count(DScene sc, uint32_t obj_begi
       if (changed) {
         store_hit(hits, s, rec);
         hit = true;
+        if (kEmit && is_emitter(sc.materials[rec.mat])) hit = false;
       } else if (kFirst) {
         stnt(&hits.tp[s], make_float4(-1.0f, 0.f, 0.f, 0.f));
+      } else if (kEmit && hit) {
+        hit = !is_emitter(sc.materials[__float_as_uint(ldnt(&hits.nm[s]).w) & 0x7fffffffu]);
       }
+    } else if (kEmit && hit) {
+      hit = !is_emitter(sc.materials[__float_as_uint(ldnt(&hits.nm[s]).w) & 0x7fffffffu]);
     }
   }
-  const uint64_t live = __ballot(hit);
+  const uint64_t live = __ballot(hit);  // (kEmit: hits that go on)
   if ((threadIdx.x & 63u) == 0u) chunk_counts[s / kChunk] = (uint32_t)__popcll(live);
 }
 
@@ -384,7 +390,8 @@ __global__ __launch_bounds__(1024) void k_scan(int bounce, int last_bounce, cons
 // every path that ends at this bounce.
 // staged: `fb` is the slot's staging buffer (one sample per frame of the batch, plain stores); k_accumulate then
 // folds the staged samples into the real framebuffer in iteration order.  Otherwise the running mean goes
-// straight into `fb`.
+// straight into `fb`.  kEmit: as k_tail_count's (the chunk offsets count the paths that go on).
+template <bool kEmit = false>
 __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out, DHits hits, int staged, int bounce,
                                                int last_bounce, const uint32_t* slot_base, const uint32_t* chunk_offsets,
                                                DFrame fb, DBand band, DeviceCounters* counters, uint8_t* octs, DBatchInfo bi)
@@ -444,8 +451,10 @@ __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out,
       rng.seed(path_seed(slot, iteration));
       rng.discard((uint32_t)bounce);
       const f3 hp = mk3(tp.y, tp.z, tp.w);
-      evaluate_material(ro, rd, tmin_flag, hp, hn, ms >> 31, m, rng, color);
-      if (last_bounce) {
+      const bool emits = kEmit && is_emitter(m);
+      if (emits) color = emit_color(color, m);  // the path ends at the emitter: no draw
+      else evaluate_material(ro, rd, tmin_flag, hp, hn, ms >> 31, m, rng, color);
+      if (last_bounce || emits) {
         accumulate_color(fb.color4, local_pixel, acc_iteration, color);  // capped paths deposit raw throughput
       } else {
         survives = true;
@@ -492,7 +501,7 @@ __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out,
 #include "pt_shade_tile.inc"
 
 
-template <bool kSpheres, bool kFirst, bool kNext = false>
+template <bool kSpheres, bool kFirst, bool kNext = false, bool kEmit = false>
 // (occupancy bounds re-measured on the final build: at least 5 or 6 wavefronts per SIMD forces spills, -8 % / -13 % end
 // to end; 1 to 3 compile to the same 124 registers)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PT_SHADE_WAVES, 8))) void k_shade_fused(DScene sc, uint32_t obj_begin, uint32_t obj_end, DPaths in, DPaths out, DHits hits,
@@ -555,7 +564,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PT_SHADE_WA
     next.hits.nm += fo;
     next.flags += fo;
   }
-  shade_tile<kSpheres, kFirst, 4, false, kNext>(sc, obj_begin, obj_end, in, out, hits, staged, bounce, last_bounce, slot_base, tile_desc, epoch, fb, band,
+  shade_tile<kSpheres, kFirst, 4, false, kNext, kEmit>(sc, obj_begin, obj_end, in, out, hits, staged, bounce, last_bounce, slot_base, tile_desc, epoch, fb, band,
                                                 counters, octs, iteration, list, fo, tile, tiles, n, n_all, s_cnt, &s_excl, &next);
 }
 
@@ -709,16 +718,27 @@ void launch_list_flags(hipStream_t s, const uint8_t* flags, uint32_t max_paths, 
 }
 void launch_tail_count(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths paths,
                        DHits hits, uint32_t max_paths, int bounce, uint32_t* chunk_counts, DeviceCounters* counters,
-                       const DBatchInfo& bi)
+                       const DBatchInfo& bi, bool emitters)
 {
   const dim3 grid(div_up(max_paths, 256u), bi.count), block(256);
+#define PT_TAIL(SPH, FIRST, EMIT)                                                                                                  \
+  hipLaunchKernelGGL((k_tail_count<SPH, FIRST, EMIT>), grid, block, 0, s, scene, obj_begin < obj_end ? obj_begin : 0u,             \
+                     obj_begin < obj_end ? obj_end : 0u, paths, hits, bounce, chunk_counts, counters, bi)
   if (obj_begin < obj_end) {
-    if (first) hipLaunchKernelGGL((k_tail_count<true, true>), grid, block, 0, s, scene, obj_begin, obj_end, paths, hits, bounce, chunk_counts, counters, bi);
-    else hipLaunchKernelGGL((k_tail_count<true, false>), grid, block, 0, s, scene, obj_begin, obj_end, paths, hits, bounce, chunk_counts, counters, bi);
+    if (first) {
+      if (emitters) PT_TAIL(true, true, true);
+      else PT_TAIL(true, true, false);
+    } else {
+      if (emitters) PT_TAIL(true, false, true);
+      else PT_TAIL(true, false, false);
+    }
+  } else if (emitters) {
+    PT_TAIL(false, false, true);
   } else {
     // (nothing to test: some closest-hit launch has written every record of the bounce)
-    hipLaunchKernelGGL((k_tail_count<false, false>), grid, block, 0, s, scene, 0u, 0u, paths, hits, bounce, chunk_counts, counters, bi);
+    PT_TAIL(false, false, false);
   }
+#undef PT_TAIL
 }
 void launch_scan(hipStream_t s, int bounce, bool last_bounce, const uint32_t* chunk_counts, uint32_t* chunk_offsets,
                  DeviceCounters* counters, const DBatchInfo& bi)
@@ -729,21 +749,32 @@ void launch_scan(hipStream_t s, int bounce, bool last_bounce, const uint32_t* ch
 void launch_shade(hipStream_t s, const DScene& scene, DPaths in, DPaths out, DHits hits, uint32_t max_paths,
                   bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                   const uint32_t* chunk_offsets, DFrame fb, DBand band, DeviceCounters* counters, uint8_t* octs,
-                  const DBatchInfo& bi)
+                  const DBatchInfo& bi, bool emitters)
 {
-  hipLaunchKernelGGL(k_shade, dim3(div_up(max_paths, 256u), bi.count), dim3(256), 0, s, scene, in, out, hits,
-                     staged ? 1 : 0, bounce, last_bounce ? 1 : 0, slot_base, chunk_offsets, fb, band, counters, octs, bi);
+  if (emitters)
+    hipLaunchKernelGGL(k_shade<true>, dim3(div_up(max_paths, 256u), bi.count), dim3(256), 0, s, scene, in, out, hits,
+                       staged ? 1 : 0, bounce, last_bounce ? 1 : 0, slot_base, chunk_offsets, fb, band, counters, octs, bi);
+  else
+    hipLaunchKernelGGL(k_shade<false>, dim3(div_up(max_paths, 256u), bi.count), dim3(256), 0, s, scene, in, out, hits,
+                       staged ? 1 : 0, bounce, last_bounce ? 1 : 0, slot_base, chunk_offsets, fb, band, counters, octs, bi);
 }
 void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths in, DPaths out,
                         DHits hits, uint32_t max_paths, bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                         unsigned long long* tile_desc, uint32_t tile_stride, uint32_t epoch, DFrame fb, DBand band,
-                        DeviceCounters* counters, uint8_t* octs, const DBatchInfo& bi, const uint32_t* list, const DNextRun* next)
+                        DeviceCounters* counters, uint8_t* octs, const DBatchInfo& bi, const uint32_t* list, const DNextRun* next,
+                        bool emitters)
 {
   const dim3 grid(div_up(max_paths, kFuseTile) * bi.count), block(256);
   const DNextRun none{};
-#define PT_FUSED(SPH, FIRST, NEXT)                                                                                                 \
-  hipLaunchKernelGGL((k_shade_fused<SPH, FIRST, NEXT>), grid, block, 0, s, scene, obj_begin, obj_end, in, out, hits, staged ? 1 : 0, \
+#define PT_FUSED_E(SPH, FIRST, NEXT, EMIT)                                                                                                \
+  hipLaunchKernelGGL((k_shade_fused<SPH, FIRST, NEXT, EMIT>), grid, block, 0, s, scene, obj_begin, obj_end, in, out, hits, staged ? 1 : 0, \
                      bounce, last_bounce ? 1 : 0, slot_base, tile_desc, tile_stride, epoch, fb, band, counters, octs, bi, list, next ? *next : none)
+  // (scenes with an emissive material: the same five instances with kEmit)
+#define PT_FUSED(SPH, FIRST, NEXT)          \
+  do {                                      \
+    if (emitters) PT_FUSED_E(SPH, FIRST, NEXT, true);  \
+    else PT_FUSED_E(SPH, FIRST, NEXT, false); \
+  } while (0)
   if (next && !first && !last_bounce) {  // "prefold": the next bounce's leading sphere run rides along
     if (obj_begin < obj_end) PT_FUSED(true, false, true);
     else PT_FUSED(false, false, true);
@@ -756,6 +787,7 @@ void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, 
     PT_FUSED(false, false, false);  // (some closest-hit launch has written every record of the bounce)
   }
 #undef PT_FUSED
+#undef PT_FUSED_E
 }
 uint32_t shade_tiles_per_frame(uint32_t max_paths) { return div_up(max_paths, kFuseTile); }
 void launch_sort_octant(hipStream_t s, const uint8_t* octs, uint32_t* order, uint32_t max_paths, int bounce,

@@ -59,7 +59,11 @@ __device__ __forceinline__ void st_out(float4* base, uint32_t index, const float
 // Every pointer is the frame's own (frame offset applied by the caller); `fo` is that offset in slots (work-list entries are
 // batch-global); n_all = live[bounce] of the frame, n = what is walked (the list's length at bounce 0 of a finishing raygen,
 // else n_all), tiles = tiles of n; s_cnt: kFuseK * kGroupWaves words and s_excl: one word of the group's LDS.
-template <bool kSpheres, bool kFirst, int kGroupWaves, bool kCoherent, bool kNext = false>
+// kEmit: the scene has an emissive material (ptc_material type 3; the host picks the instance).  A path whose closest hit is
+// an emitter ends at this bounce, so the survivor ballot of phase 1 needs the hit's material: the hit record's nm is then
+// loaded in phase 1 (phase 2 finds it in registers) and the material's type read from the table.  Without emitters nm
+// waits for phase 2 as before, and the instance is the one that ran before emitters existed.
+template <bool kSpheres, bool kFirst, int kGroupWaves, bool kCoherent, bool kNext = false, bool kEmit = false>
 __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_begin, const uint32_t obj_end, const DPaths in, const DPaths out,
                                            const DHits hits, const int staged, const int bounce, const int last_bounce, const uint32_t* slot_base,
                                            unsigned long long* tile_desc, const uint32_t epoch, const DFrame fb, const DBand band,
@@ -122,7 +126,15 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
     }
     const bool hit = s < n_all && tp[j].x >= 0.0f;
     hit_mask |= hit ? 1u << j : 0u;
-    const uint64_t live = __ballot(hit && !last_bounce);
+    bool goes_on = hit;
+    if (kEmit && hit) {  // (kFirst: a hit is the sphere run's, its record is in registers)
+      if (!kFirst && !(have_nm >> j & 1u)) {
+        nm[j] = ld_in<kCoherent>(hits.nm, s);
+        have_nm |= 1u << j;
+      }
+      goes_on = !is_emitter(sc.materials[__float_as_uint(nm[j].w) & 0x7fffffffu]);
+    }
+    const uint64_t live = __ballot(goes_on && !last_bounce);
     if ((threadIdx.x & 63u) == 0u) s_cnt[j * kGroupWaves + (int)wave] = (uint32_t)__popcll(live);
   }
   // what phase 2 still needs from memory, requested before anybody waits for anything
@@ -160,16 +172,19 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
       const bool is_hit = (hit_mask >> j & 1u) != 0u;
       const f3 hn = xyz(nm[j]);
       const uint32_t ms = __float_as_uint(nm[j].w);
-      DMaterial m{3, {0.f, 0.f, 0.f, 0.f}};  // (types are 0..2: validate_scene)
+      DMaterial m{(int32_t)kKindMiss, {0.f, 0.f, 0.f, 0.f}};  // (a hit's type is 0..2, or 3 in a kEmit instance: validate_scene)
       if (is_hit) m = sc.materials[ms & 0x7fffffffu];
+      const bool emits = kEmit && is_hit && is_emitter(m);  // (phase 1 counted it out)
       if (bounce == 0) {
         if (is_hit) accumulate_nd(fb.nd4, local_pixel, acc_iteration, hn, tp[j].x);  // path_tracer.cu:308-311
         else accumulate_nd(fb.nd4, local_pixel, acc_iteration, -rd, 1e6f);           // raygen defaults, ray_gen.cu:26-28
       }
       const uint32_t slot = (slot_base ? *slot_base : 0u) + s;
-      shade_kinds((uint32_t)m.type, ro, rd, tmin_flag, mk3(tp[j].y, tp[j].z, tp[j].w), hn, ms >> 31, m, slot, iteration, (uint32_t)bounce, color);
-      if (!is_hit || last_bounce) {
-        // a miss ends the path with throughput * sky (path_tracer.cu:304-307, 283-289); capped paths deposit raw throughput
+      shade_kinds<kEmit>(emits ? kKindEmit : (uint32_t)m.type, ro, rd, tmin_flag, mk3(tp[j].y, tp[j].z, tp[j].w), hn, ms >> 31, m, slot,
+                         iteration, (uint32_t)bounce, color);
+      if (!is_hit || last_bounce || emits) {
+        // a miss ends the path with throughput * sky (path_tracer.cu:304-307, 283-289), an emitter with throughput * emission;
+        // capped paths deposit raw throughput
         accumulate_color(fb.color4, local_pixel, acc_iteration, color);
       } else {
         surv_mask |= 1u << j;
@@ -194,8 +209,10 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
         rng.seed(path_seed(slot, iteration));
         rng.discard((uint32_t)bounce);
         const f3 hp = mk3(tp[j].y, tp[j].z, tp[j].w);
-        evaluate_material(ro, rd, tmin_flag, hp, hn, ms >> 31, m, rng, color);
-        if (last_bounce) {
+        const bool emits = kEmit && is_emitter(m);
+        if (emits) color = emit_color(color, m);  // the path ends at the emitter: no draw
+        else evaluate_material(ro, rd, tmin_flag, hp, hn, ms >> 31, m, rng, color);
+        if (last_bounce || emits) {
           accumulate_color(fb.color4, local_pixel, acc_iteration, color);  // capped paths deposit raw throughput
         } else {
           surv_mask |= 1u << j;

@@ -44,6 +44,7 @@ struct ptc_ctx {
   std::vector<void*> scene_allocs;
   DScene scene{};
   bool has_scene = false;
+  bool has_emitters = false;  // the scene's material table holds an emissive material (type 3): the shade kernels' kEmit instances
   uint32_t bvh_nodes = 0, bvh_depth = 0, triangles = 0, bvh4_nodes = 0, bvh4_depth = 0;
   ptc_upload_times upload_times{};
   std::vector<DMeshView> mesh_views;   // host copy of DScene::mesh_views: a traversal launch gets its object's mesh as DScene::cur

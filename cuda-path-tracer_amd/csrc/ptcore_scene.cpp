@@ -2,6 +2,8 @@
 // BVH and the traversal layouts (host or device side), ptc_build_bvh*, ptc_make_object.  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
 
+#include <cmath>
+
 using namespace pt;
 using namespace ptcd;
 
@@ -135,8 +137,16 @@ int validate_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
     if (o.type == 1u && s->meshes && o.index >= s->mesh_count) return fail(ctx, PTC_ERR_INVALID, "mesh index out of range");
     if (s->object_material_indices[i] >= s->material_count) return fail(ctx, PTC_ERR_INVALID, "material index out of range");
   }
-  for (uint32_t i = 0; i < s->material_count; ++i)
-    if (s->materials[i].type < 0 || s->materials[i].type > 2) return fail(ctx, PTC_ERR_INVALID, "unknown material type");
+  for (uint32_t i = 0; i < s->material_count; ++i) {
+    const ptc_material& m = s->materials[i];
+    if (m.type < 0 || m.type > 3) return fail(ctx, PTC_ERR_INVALID, "unknown material type");
+    if (m.type == 3) {  // emissive (an extension): radiance rgb finite and >= 0, p[3] reserved
+      for (int k = 0; k < 3; ++k)
+        if (!(std::isfinite(m.p[k]) && m.p[k] >= 0.0f))
+          return fail(ctx, PTC_ERR_INVALID, "material " + std::to_string(i) + ": emission must be finite and >= 0");
+      if (m.p[3] != 0.0f) return fail(ctx, PTC_ERR_INVALID, "material " + std::to_string(i) + ": p[3] of an emissive material must be 0");
+    }
+  }
   return PTC_OK;
 }
 
@@ -331,6 +341,7 @@ int ptc_upload_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
   if (int rc = sync_frames(ctx)) return rc;
   free_pool(ctx->scene_allocs);
   ctx->has_scene = false;
+  ctx->has_emitters = false;
   ++ctx->scene_serial;
   DScene d{};
   const DObject* objects = nullptr;
@@ -341,6 +352,7 @@ int ptc_upload_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
   const DMaterial* mats = nullptr;
   if (int rc = upload(ctx, ctx->scene_allocs, &mats, reinterpret_cast<const DMaterial*>(s->materials), s->material_count)) return rc;
   d.materials = mats;
+  for (uint32_t i = 0; i < s->material_count; ++i) ctx->has_emitters |= s->materials[i].type == 3;
   {
     std::vector<float4> balls((size_t)s->object_count * kSphereTab);
     ctx->sphere_class.assign(s->object_count, 0u);

@@ -296,17 +296,18 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
     }
     launch_shade_fused(sl.stream, scene, tail ? ctx->tail_begin : 0u, tail ? ctx->tail_end : 0u, !wrote, in, out, sl.hits, ctx->pix_count,
                        ctx->staging(), bounce, last, slot_base_dev, sl.tile_desc, sl.tile_stride, sl.shade_epoch, sl.stage, ctx->band,
-                       sl.counters, octs, sl.bi, bounce == 0 && sl.primary_finished ? sl.worklist : nullptr, prefold ? &next : nullptr);
+                       sl.counters, octs, sl.bi, bounce == 0 && sl.primary_finished ? sl.worklist : nullptr, prefold ? &next : nullptr,
+                       ctx->has_emitters);
     if (prefold) {
       std::swap(sl.hits, sl.hits_other);
       sl.prefolded = true;
     }
   } else {
     launch_tail_count(sl.stream, scene, tail ? ctx->tail_begin : 0u, tail ? ctx->tail_end : 0u, !wrote, in, sl.hits, ctx->pix_count,
-                      bounce, sl.chunk_counts, sl.counters, sl.bi);
+                      bounce, sl.chunk_counts, sl.counters, sl.bi, ctx->has_emitters);
     launch_scan(sl.stream, bounce, last, sl.chunk_counts, sl.chunk_offsets, sl.counters, sl.bi);
     launch_shade(sl.stream, scene, in, out, sl.hits, ctx->pix_count, ctx->staging(), bounce, last, slot_base_dev,
-                 sl.chunk_offsets, sl.stage, ctx->band, sl.counters, octs, sl.bi);
+                 sl.chunk_offsets, sl.stage, ctx->band, sl.counters, octs, sl.bi, ctx->has_emitters);
   }
   sl.cur ^= 1;
   sl.bounces_done = bounce + 1;
@@ -401,7 +402,8 @@ int batch_persist(ptc_ctx* ctx, const uint32_t* slot_base_dev)
     }
     HIP_TRY(ctx, hipEventRecord(tp.start, sl.stream));
   }
-  launch_persist(sl.stream, scene, l.mesh, sl.hits, sl.counters, sl.bi, pa, ctx->traverse_waves, tail, pa.list0 != nullptr);
+  launch_persist(sl.stream, scene, l.mesh, sl.hits, sl.counters, sl.bi, pa, ctx->traverse_waves, tail, pa.list0 != nullptr,
+                 ctx->has_emitters);
   if (ctx->time_trace) {
     HIP_TRY(ctx, hipEventRecord(tp.stop, sl.stream));
     ctx->timed.push_back(tp);
@@ -611,7 +613,7 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
     ctx->cam = make_camera(*camera, ctx->width, ctx->height);
     ctx->have_cam = true;
     launch_megakernel(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
-                      ctx->max_bounces, ctx->fb, sl.counters);
+                      ctx->max_bounces, ctx->fb, sl.counters, ctx->has_emitters);
     if (int rc = check_last(ctx, "megakernel")) return rc;
     HIP_TRY(ctx, hipEventRecord(sl.done, sl.stream));
     if (ctx->staging()) {

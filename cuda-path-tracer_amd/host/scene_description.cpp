@@ -186,6 +186,9 @@ FlatScene SceneDescription::build_scene() const
       m.type = 1;
       std::memcpy(m.p, mt->albedo, sizeof mt->albedo);
       m.p[3] = mt->fuzz;
+    } else if (const auto* em = std::get_if<EmissiveMaterial>(&material)) {
+      m.type = 3;
+      std::memcpy(m.p, em->emission, sizeof em->emission);
     } else {
       m.type = 2;
       m.p[0] = std::get<DielectricMaterial>(material).refraction_index;
@@ -279,6 +282,15 @@ SceneDescription scene_from_json(const std::string& filename)
       vec3_from(m->at("albedo"), mt.albedo);
       mt.fuzz = m->at("fuzz").f();
       scene.add_material(name, mt);
+    } else if (type == "emissive") {  // an extension: the reference's grammar has no emitters
+      // "emission": three finite numbers >= 0 (json_parser.py, the same rule)
+      const Json* e = m->find("emission");
+      bool ok = e && e->kind == Json::Array && e->arr.size() == 3;
+      for (size_t i = 0; ok && i < 3; ++i) ok = e->arr[i]->kind == Json::Number && std::isfinite(e->arr[i]->num) && e->arr[i]->num >= 0.0;
+      if (!ok) throw std::runtime_error("Json Parser: emissive material " + name + " needs \"emission\": three finite numbers >= 0");
+      EmissiveMaterial em{};
+      vec3_from(*e, em.emission);
+      scene.add_material(name, em);
     } else {
       throw std::runtime_error("Json Parser: Unsupported material type " + type);
     }

@@ -27,7 +27,8 @@ Mat4 multiply(const Mat4& a, const Mat4& b);                       // glm mat4 *
 struct DiffuseMateral { float albedo[3]; };                 // (sic) material.hpp:6-8
 struct MetalMaterial { float albedo[3]; float fuzz; };      // material.hpp:10-13
 struct DielectricMaterial { float refraction_index; };      // material.hpp:15-17
-using Material = std::variant<DiffuseMateral, MetalMaterial, DielectricMaterial>;
+struct EmissiveMaterial { float emission[3]; };             // an extension (the reference has no emitters): ptc_material type 3
+using Material = std::variant<DiffuseMateral, MetalMaterial, DielectricMaterial, EmissiveMaterial>;
 
 struct Sphere { float center[3] = {0, 0, 0}; float radius = 0; };  // sphere.hpp:8-11
 

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from . import glmlite as glm
-from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, Mesh, MetalMaterial, SceneDescription,
+from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, EmissiveMaterial, Mesh, MetalMaterial, SceneDescription,
                                 Sphere)
 
 
@@ -73,6 +73,15 @@ def _transform(j):
     raise ValueError("Json Parser: Transform must be either an object or an array!")
 
 
+def _emission(m):
+    """An emissive material's "emission": an array of three finite numbers >= 0 (scene_description.cpp, the same rule)."""
+    e = m.get("emission")
+    if (not isinstance(e, list) or len(e) != 3 or
+            not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v >= 0 for v in e)):
+        raise ValueError(f"Json Parser: emissive material {m.get('name')!r} needs \"emission\": three finite numbers >= 0")
+    return tuple(e)
+
+
 def scene_from_json(filename):
     with open(filename) as f:
         root = json.load(f)
@@ -87,6 +96,8 @@ def scene_from_json(filename):
             scene.add_material(m["name"], DielectricMaterial(m["refraction_index"]))
         elif t == "metal":
             scene.add_material(m["name"], MetalMaterial(tuple(m["albedo"]), m["fuzz"]))
+        elif t == "emissive":  # an extension: the reference's grammar has no emitters
+            scene.add_material(m["name"], EmissiveMaterial(_emission(m)))
         else:
             raise ValueError(f"Json Parser: Unsupported material type {t}")
     for s in root["surfaces"]:

@@ -29,6 +29,11 @@ class DielectricMaterial:  # material.hpp:15-17
 
 
 @dataclass
+class EmissiveMaterial:  # an extension (the reference has no emitters): ptc_material type 3
+    emission: tuple  # radiance rgb, finite and >= 0
+
+
+@dataclass
 class Sphere:  # sphere.hpp:8-11
     center: tuple = (0.0, 0.0, 0.0)
     radius: float = 0.0
@@ -124,6 +129,9 @@ def material_record(material):
     elif isinstance(material, DielectricMaterial):
         rec["type"] = 2
         rec["p"][0] = material.refraction_index
+    elif isinstance(material, EmissiveMaterial):
+        rec["type"] = 3
+        rec["p"][:3] = material.emission
     else:
         raise TypeError(f"unsupported material {material!r}")
     return rec

@@ -7,8 +7,8 @@ import math
 import numpy as np
 
 from . import glmlite as glm
-from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, Mesh, MetalMaterial, SceneDescription,
-                                Sphere)
+from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, EmissiveMaterial, Mesh, MetalMaterial,
+                                SceneDescription, Sphere)
 
 
 def _hash_u32(a):
@@ -145,4 +145,31 @@ def heightfield_scene(resolution=(1920, 1080), nx=1001, nz=501):
     s.camera = _camera_from_look_at((0.0, 2.5, 5.0), (0.0, 0.0, 0.0), vfov_deg=50.0)
     s.resolution = tuple(resolution)
     s.spp = 1
+    return s
+
+
+def light_panel_mesh(x0=-0.5, x1=0.5, z0=-1.3, z1=-0.3, y=1.49):
+    """Two triangles: a horizontal quad at height y, facing down (the lamp of cornell_lit)."""
+    positions = np.array([[x0, y, z0], [x1, y, z0], [x1, y, z1], [x0, y, z1]], dtype=np.float32)
+    return Mesh(positions, np.array([0, 2, 1, 0, 3, 2], dtype=np.uint32))
+
+
+def cornell_lit(resolution=(256, 256), with_mesh=False):
+    """The box of cornell_spheres with a ceiling (open front) and lamps of its own -- emissive materials, an extension
+    (the reference has no emitters): a sphere lamp hanging from the ceiling, the last object of the list (the sphere run
+    that ends it), and with_mesh a two-triangle panel lamp under the ceiling (a mesh object: the traversal kernels)."""
+    s = SceneDescription()
+    _add_box_and_balls(s)
+    big = 1000.0
+    s.add_material("ceiling", DiffuseMateral((0.73, 0.73, 0.73)))
+    s.add_object(Sphere((0, 0, 0), big), glm.translate((0.0, big + 1.5, 0.0)), "ceiling")
+    s.add_material("lamp", EmissiveMaterial((4.0, 3.6, 3.0)))
+    if with_mesh:
+        s.add_material("panel", EmissiveMaterial((6.0, 6.0, 5.5)))
+        mesh = s.add_mesh("models/light_panel.obj", light_panel_mesh())
+        s.add_object(mesh, glm.identity(), "panel")
+    s.add_object(Sphere((0, 0, 0), 0.25), glm.translate((0.9, 1.5, -1.2)), "lamp")
+    s.camera = _camera_from_look_at((0.0, 0.0, 4.0), (0.0, -0.1, 0.0), vfov_deg=45.0)
+    s.resolution = tuple(resolution)
+    s.spp = 16
     return s

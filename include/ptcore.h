@@ -64,7 +64,15 @@ typedef struct ptc_object {
 typedef struct ptc_sphere { float center[3]; float radius; } ptc_sphere;
 
 /* Material, material.hpp:19-38 (20 bytes).  type 0 Diffuse {albedo rgb}, 1 Metal {albedo rgb, fuzz},
- * 2 Dielectric {refraction_index} */
+ * 2 Dielectric {refraction_index},
+ * 3 Emissive {emitted radiance rgb, p[3] reserved: 0} -- an extension (the reference has no emitters; parity unpinned by
+ *   construction, like ptc_mesh_range).  Each component finite and >= 0, else ptc_upload_scene fails with PTC_ERR_INVALID.
+ *   A path whose closest hit is emissive ends at that bounce with colour * emission (binary32, per component, as a miss
+ *   ends with colour * sky), makes no draw there and is not a survivor: it leaves the compaction like a miss, so the
+ *   slots -- and the random numbers -- of the paths behind it, live[] and ptc_stats.last_live count only the paths that
+ *   go on.  Two-sided (the side bit is ignored); at bounce 0 normal / depth are the hit's.  Streaming and megakernel
+ *   alike, every schedule parameter included (scenes whose table holds a type 3 run instances of the shade kernels built
+ *   for it; other scenes run exactly the code they ran before). */
 typedef struct ptc_material { int32_t type; float p[4]; } ptc_material;
 
 /* BVHNode, accelerators/bvh.hpp:17-28 (32 bytes).  leaf <=> primitive_count != 0; for a leaf
