@@ -117,6 +117,26 @@ struct Builder {
 
 }  // namespace
 
+int64_t first_non_finite_vertex(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count)
+{
+  auto not_finite = [](uint32_t bits) { return (bits & 0x7f800000u) == 0x7f800000u; };  // exponent all ones: infinite or NaN
+  if (index_count == 0u) return -1;  // no triangle uses any vertex
+  // the usual mesh has no such coordinate at all: one pass over the array in memory order says so
+  bool any = false;
+  for (size_t i = 0; i < 3u * (size_t)vertex_count; ++i) {
+    uint32_t bits;
+    std::memcpy(&bits, positions + i, sizeof bits);
+    any |= not_finite(bits);
+  }
+  if (!any) return -1;
+  for (uint32_t i = 0; i < index_count; ++i) {
+    uint32_t bits[3];
+    std::memcpy(bits, positions + 3u * (size_t)indices[i], sizeof bits);
+    if (not_finite(bits[0]) || not_finite(bits[1]) || not_finite(bits[2])) return (int64_t)indices[i];
+  }
+  return -1;
+}
+
 int build_bvh(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
               ptc_bvh_node* out, uint32_t* max_depth)
 {
@@ -124,6 +144,7 @@ int build_bvh(const float* positions, uint32_t vertex_count, const uint32_t* ind
   if (T == 0) return PTC_ERR_BVH;
   for (uint32_t i = 0; i < T * 3u; ++i)
     if (indices[i] >= vertex_count) return PTC_ERR_INVALID;
+  if (first_non_finite_vertex(positions, vertex_count, indices, T * 3u) >= 0) return PTC_ERR_INVALID;
 
   std::vector<Box> tri_box(T);
   std::vector<f3> tri_center(T);

@@ -12,6 +12,12 @@ namespace pt {
 int build_bvh(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
               ptc_bvh_node* out, uint32_t* max_depth);
 
+// The rule for vertices that are not finite: a mesh in which a triangle uses a vertex with a NaN or infinite coordinate is
+// refused (PTC_ERR_INVALID) by ptc_upload_scene, ptc_build_bvh and ptc_build_bvh_device before anything is built; a vertex
+// no triangle uses may hold anything.  Returns the first such vertex in the order of the index list, or -1.  The indices
+// are in range (checked by the caller).
+int64_t first_non_finite_vertex(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count);
+
 // glm::inverse(mat4) as Transform's constructor applies it (reference transform.hpp:16-19)
 m4 inverse(const m4& m);
 

@@ -319,6 +319,11 @@ int ptc_upload_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
   // ---- phase 1: the reference BVH of every mesh (scene_description.cpp:99-101), unless the caller brought it.  The
   // old scene is still intact: a failure here leaves the context as it was.
   uint32_t deepest = 0u, total_nodes = 0u, total_triangles = 0u;
+  for (uint32_t m = 0; m < mesh_count; ++m) {  // vertices a triangle uses are finite (the rule: pt_host.hpp)
+    const int64_t v = first_non_finite_vertex(meshes[m].positions, meshes[m].vertex_count, meshes[m].indices, meshes[m].index_count);
+    if (v >= 0)
+      return fail(ctx, PTC_ERR_INVALID, "mesh " + std::to_string(m) + ": vertex " + std::to_string(v) + " has a NaN or infinite coordinate");
+  }
   for (const MeshWork& w : meshes)  // every caller tree first, so that a refusal comes before any device work
     if (w.index_count != 0u && w.caller_bvh)
       if (int rc = validate_bvh(ctx, w.caller_bvh, w.caller_nodes, w.positions, w.indices, w.index_count)) return rc;
@@ -591,6 +596,10 @@ int ptc_build_bvh_device(ptc_ctx* ctx, const float* positions, uint32_t vertex_c
 {
   if (!ctx || !positions || !indices || !nodes || index_count % 3u != 0u) return fail(ctx, PTC_ERR_INVALID, "bad arguments");
   if (int rc = bind_device(ctx)) return rc;
+  for (uint32_t i = 0; i < index_count; ++i)
+    if (indices[i] >= vertex_count) return fail(ctx, PTC_ERR_INVALID, "vertex index out of range");
+  if (const int64_t v = first_non_finite_vertex(positions, vertex_count, indices, index_count); v >= 0)
+    return fail(ctx, PTC_ERR_INVALID, "vertex " + std::to_string(v) + " has a NaN or infinite coordinate");
   return bvh_on_device(ctx, positions, vertex_count, indices, index_count, nodes, max_depth, nullptr);
 }
 

@@ -105,7 +105,10 @@ typedef struct ptc_scene_desc {
   uint32_t sphere_count;
   const ptc_material* materials;
   uint32_t material_count;
-  const float* positions;                  /* 3 floats per vertex */
+  /* 3 floats per vertex.  Every vertex that a triangle uses must be finite: a NaN or infinite coordinate in one fails
+   * ptc_upload_scene with PTC_ERR_INVALID and a message that names the mesh and the vertex, before anything is built
+   * or uploaded (the scene uploaded before stays).  A vertex no triangle uses may hold anything. */
+  const float* positions;
   uint32_t vertex_count;
   const uint32_t* indices;                 /* 3 per triangle */
   uint32_t index_count;
@@ -436,12 +439,16 @@ int ptc_get_upload_times(const ptc_ctx* ctx, ptc_upload_times* out);
 int ptc_download_layout(ptc_ctx* ctx, int which, void* host, uint64_t capacity, uint64_t* bytes);
 
 /* bvh_from_mesh (accelerators/bvh.cpp:211-253), host-side, no GPU needed.  nodes must hold
- * index_count/3*2-1 entries.  Returns the node count (>0) or a negative ptc_status. */
+ * index_count/3*2-1 entries.  Returns the node count (>0) or a negative ptc_status: PTC_ERR_INVALID for an index out of
+ * range or a NaN or infinite coordinate in a vertex that a triangle uses (unused vertices may hold anything; the
+ * reference's builder indexes out of bounds or panics on such a mesh), PTC_ERR_BVH for a node of more than 4 coincident centroids. */
 int ptc_build_bvh(const float* positions, uint32_t vertex_count, const uint32_t* indices,
                   uint32_t index_count, ptc_bvh_node* nodes, uint32_t* max_depth);
 /* The same tree built by the context's GPU (pt_bvh_gpu.hip: all nodes of a depth split at once; the decisions are
  * the host builder's, from one source) -- node for node what ptc_build_bvh returns.  This is what ptc_upload_scene
- * runs when the scene brings no BVH (param "bvh_build_on_device", default 1; 0 = the host builder). */
+ * runs when the scene brings no BVH (param "bvh_build_on_device", default 1; 0 = the host builder).  The same
+ * refusals, too: a vertex in use that is not finite is PTC_ERR_INVALID here as well (the message names the vertex), checked
+ * on the host before anything goes to the device. */
 int ptc_build_bvh_device(ptc_ctx* ctx, const float* positions, uint32_t vertex_count, const uint32_t* indices,
                          uint32_t index_count, ptc_bvh_node* nodes, uint32_t* max_depth);
 

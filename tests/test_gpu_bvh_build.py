@@ -47,9 +47,8 @@ def test_device_builder_equals_host_builder_and_oracle(pkg, orc):
             assert len(got) == len(want) == 2 * mesh.triangle_count() - 1, name
             assert got_depth == want_depth, name
             assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), name
-            if mesh.triangle_count() <= 25_000:
-                ref, ref_depth = orc.build_bvh(mesh.positions, mesh.indices)
-                assert ref_depth == got_depth and np.array_equal(got.view(np.uint8), ref.view(np.uint8)), name
+            ref, ref_depth = orc.build_bvh(mesh.positions, mesh.indices)
+            assert ref_depth == got_depth and np.array_equal(got.view(np.uint8), ref.view(np.uint8)), name
 
 
 def test_device_builder_benchmark_mesh(pkg):
