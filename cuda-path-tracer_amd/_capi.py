@@ -96,6 +96,11 @@ class ptc_profile(C.Structure):
                 ("denoise_passes", C.c_uint32), ("persist_launches", C.c_uint32)]
 
 
+class ptc_occlusion_stats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("occluded", C.c_uint64), ("redone", C.c_uint64), ("kernel_ms", C.c_double),
+                ("launches", C.c_uint32)]
+
+
 class ptc_upload_times(C.Structure):
     _fields_ = [("bvh_build_ms", C.c_float), ("layout_ms", C.c_float), ("triangles_ms", C.c_float), ("copy_ms", C.c_float),
                 ("total_ms", C.c_float), ("bvh_on_device", C.c_uint32), ("layout_on_device", C.c_uint32)]
@@ -146,6 +151,8 @@ SIGNATURES = {
     "ptc_get_profile": (C.c_int, [_P, C.POINTER(ptc_profile)]),
     "ptc_intersect_rays": (C.c_int, [_P, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
+    "ptc_occluded_rays": (C.c_int, [_P, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint8)]),
+    "ptc_get_occlusion_stats": (C.c_int, [_P, C.POINTER(ptc_occlusion_stats)]),
     "ptc_get_upload_times": (C.c_int, [_P, C.POINTER(ptc_upload_times)]),
     "ptc_download_layout": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ptc_build_bvh_device": (C.c_int, [_P, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,

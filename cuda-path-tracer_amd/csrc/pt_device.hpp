@@ -451,6 +451,15 @@ void launch_denoise_pass(hipStream_t s, const DCamera& cam, uint32_t pix_count, 
                          const float4* pos, float4* out, int step_width, DDenoise params);
 void launch_intersect(hipStream_t s, const DScene& scene, const float4* rays_o, const float4* rays_d, uint32_t n,
                       DHits hits, DeviceCounters* counters, int variant);
+// occlusion queries (pt_occlude.hip): rays_o = origin.xyz, bits(t_min flag << 31); rays_d = direction.xyz, t_max; occluded = one byte
+// per ray, zeroed by the caller, set to 1 by the kernels and never read-modify-written.
+//   launch_occlude_spheres  the sphere objects of [obj_begin, obj_end) for every ray not flagged yet
+//   launch_occlude          one mesh object: k_traverse4's persistent wavefronts, stopping at the first accepted triangle; counters:
+//                           one block with live[0] = rays (the feed), its slow_rays[0] counts the rays redone exactly
+void launch_occlude_spheres(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, const float4* rays_o,
+                            const float4* rays_d, uint32_t n, uint8_t* occluded);
+void launch_occlude(hipStream_t s, const DScene& scene, uint32_t obj_index, const float4* rays_o, const float4* rays_d,
+                    uint8_t* occluded, int work_slot, DeviceCounters* counters, uint32_t waves, uint32_t* slow_list, const DBatchInfo& bi);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,
                      float* out_sin, float* out_cos);
 

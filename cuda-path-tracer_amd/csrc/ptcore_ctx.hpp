@@ -233,6 +233,7 @@ struct ptc_ctx {
   double denoise_ms = 0.0;               // A-Trous passes (TimedLaunch::bounce == -1)
   uint32_t denoise_passes = 0;
   uint32_t persist_launches = 0;         // batches traced through k_persist since ptc_reset_profile
+  ptc_occlusion_stats occlusion{};       // ptc_occluded_rays since ptc_reset_profile
 };
 
 

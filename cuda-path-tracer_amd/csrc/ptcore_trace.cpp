@@ -441,6 +441,54 @@ int batch_end(ptc_ctx* ctx)
 int batch_limit(const ptc_ctx* ctx) { return ctx->staged && ctx->trace_variant == 3 ? ctx->batch : 1; }
 
 
+// Occlusion queries on device arrays: rays_o4 = origin.xyz, bits(t_min flag << 31) as in the path state,
+// rays_d4 = direction.xyz, t_max; flags = one byte per ray, zeroed here and set to 1 by the kernels.  Every ray must be in the fast
+// domain (t_min 1e-4 or 1e-5, t_max >= 0) and the trace variant 3.  Spheres first (one group: any grouping of the object list
+// gives the same OR), then one any-hit launch per mesh object; a ray that is already flagged is skipped by every later launch.
+// Enqueues only.  The scratch is the caller's: ptc_occluded_rays allocates it per call, a bounce loop would lend its slot's.
+struct OccludeScratch {
+  uint32_t* slow_list;        // n entries
+  uint32_t* slow_stack;       // kStackDepth * kWave
+  uint2* spill;               // scene.spill_cap * scene.spill_stride
+  DeviceCounters* counters;   // one block; its slow_rays[0] and flags are the launches' results
+};
+int occlude_on_device(ptc_ctx* ctx, hipStream_t stream, const float4* rays_o4, const float4* rays_d4, uint32_t n, uint8_t* flags,
+                      const OccludeScratch& scr, uint32_t* launches)
+{
+  HIP_TRY(ctx, hipMemsetAsync(flags, 0, n, stream));
+  HIP_TRY(ctx, hipMemsetAsync(scr.counters, 0, sizeof(DeviceCounters), stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&scr.counters->live[0], &n, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  DScene scene = ctx->scene;
+  scene.spill = scr.spill;
+  scene.slow_stack = scr.slow_stack;
+  uint32_t sph_begin = 0xffffffffu, sph_end = 0u;
+  auto sphere_run = [&](uint32_t b, uint32_t e) {
+    if (b < e) {
+      sph_begin = std::min(sph_begin, b);
+      sph_end = std::max(sph_end, e);
+    }
+  };
+  for (const auto& l : ctx->launches) sphere_run(l.pre_begin, l.pre_end);
+  sphere_run(ctx->tail_begin, ctx->tail_end);
+  if (sph_begin < sph_end) {
+    launch_occlude_spheres(stream, scene, sph_begin, sph_end, rays_o4, rays_d4, n, flags);
+    ++*launches;
+  }
+  DBatchInfo bi{};
+  bi.stride = n;
+  bi.chunk_stride = n / kChunk + 1u;
+  bi.count = 1u;
+  // (ptc_intersect_rays' sizing: about four rays per lane, at most what is resident -- and what the overflow area is laid out for)
+  const uint32_t waves = std::min<uint32_t>(ctx->traverse_waves, std::max<uint32_t>(8u, ((n / (4u * kWave)) + 7u) & ~7u));
+  int work_slot = 0;
+  for (const auto& l : ctx->launches) {
+    scene.cur = ctx->mesh_views[ctx->object_mesh[l.mesh]];
+    launch_occlude(stream, scene, l.mesh, rays_o4, rays_d4, flags, work_slot++ % kWorkSlots, scr.counters, waves, scr.slow_list, bi);
+    ++*launches;
+  }
+  return check_last(ctx, "occlusion query");
+}
+
 }  // namespace
 
 namespace ptcd {
@@ -757,6 +805,118 @@ int ptc_intersect_rays(ptc_ctx* ctx, const float* rays, uint32_t n, float* hit_t
     hit_material[i] = miss ? 0u : (ms & 0x7fffffffu);
     hit_side[i] = miss ? (uint8_t)0 : (uint8_t)(ms >> 31);
   }
+  return PTC_OK;
+}
+
+int ptc_occluded_rays(ptc_ctx* ctx, const float* rays, uint32_t n, uint8_t* occluded)
+{
+  if (!ctx || !rays || !occluded) return PTC_ERR_INVALID;
+  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
+  if (n == 0) return PTC_OK;
+  if (n > 0x7fffffffu) return fail(ctx, PTC_ERR_INVALID, "too many rays");
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = flush_pending(ctx)) return rc;
+  // the fast domain: every shadow ray a renderer makes (path t_min values, a distance as t_max).  Anything else -- and the
+  // cross-check variants 0 / 1 -- takes the exact closest-hit kernel of ptc_intersect_rays, reduced to a flag on the host.
+  // (A NaN t_max: the reference's triangle test rejects on t > t_max, which a NaN never is -- it accepts; the culled walk of
+  // variant 1 compares the other way round, so such a call takes the reference-order kernel, variant 0.)
+  bool fast = ctx->trace_variant == 3, nan_tmax = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const float tmin = rays[8u * (size_t)i + 3u], tmax = rays[8u * (size_t)i + 7u];
+    fast = fast && (tmin == 1e-4f || tmin == 1e-5f) && tmax >= 0.0f;
+    nan_tmax = nan_tmax || tmax != tmax;
+  }
+  std::vector<void*> pool;
+  float4 *ro = nullptr, *rd = nullptr;
+  uint8_t* flags = nullptr;
+  DHits hits{};
+  OccludeScratch scr{};
+  int rc = dev_alloc(ctx, pool, &ro, n);
+  if (!rc) rc = dev_alloc(ctx, pool, &rd, n);
+  if (!rc && fast) {
+    rc = dev_alloc(ctx, pool, &flags, n);
+    if (!rc) rc = dev_alloc(ctx, pool, &scr.slow_list, n);
+    if (!rc) rc = dev_alloc(ctx, pool, &scr.slow_stack, (size_t)kStackDepth * kWave);
+    if (!rc) rc = dev_alloc(ctx, pool, &scr.spill, (size_t)ctx->scene.spill_cap * ctx->scene.spill_stride);
+    if (!rc) rc = dev_alloc(ctx, pool, &scr.counters, 1);
+  } else if (!rc) {
+    rc = dev_alloc(ctx, pool, &hits.tp, n);
+    if (!rc) rc = dev_alloc(ctx, pool, &hits.nm, n);
+  }
+  if (rc) {
+    free_pool(pool);
+    return rc;
+  }
+  std::vector<float4> ho(n), hd(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* r = rays + 8u * (size_t)i;
+    float w = r[3];
+    if (fast) {
+      const uint32_t flag = r[3] == 1e-5f ? 0x80000000u : 0u;
+      std::memcpy(&w, &flag, 4);
+    }
+    ho[i] = make_float4(r[0], r[1], r[2], w);
+    hd[i] = make_float4(r[4], r[5], r[6], r[7]);
+  }
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  const bool timed = ctx->time_trace;
+  uint32_t launches = 0u, dev_flags = 0u;
+  unsigned long long redone = 0ull;
+  std::vector<float4> tp;
+  auto run = [&]() -> int {
+    HIP_TRY(ctx, hipMemcpyAsync(ro, ho.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rd, hd.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    if (timed) {
+      HIP_TRY(ctx, hipEventCreate(&ev[0]));
+      HIP_TRY(ctx, hipEventCreate(&ev[1]));
+      HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
+    }
+    if (fast) {
+      if (int r2 = occlude_on_device(ctx, ctx->stream, ro, rd, n, flags, scr, &launches)) return r2;
+    } else {
+      launch_intersect(ctx->stream, ctx->scene, ro, rd, n, hits, ctx->misc_counters, ctx->trace_variant == 0 || nan_tmax ? 0 : 1);
+      ++launches;
+      if (int r2 = check_last(ctx, "occlusion query")) return r2;
+    }
+    if (timed) HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
+    if (fast) {
+      HIP_TRY(ctx, hipMemcpyAsync(occluded, flags, n, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(&redone, &scr.counters->slow_rays[0], sizeof redone, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(&dev_flags, &scr.counters->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+      tp.resize(n);
+      HIP_TRY(ctx, hipMemcpyAsync(tp.data(), hits.tp, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed) {
+      float ms = 0.0f;
+      HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
+      ctx->occlusion.kernel_ms += (double)ms;
+    }
+    return PTC_OK;
+  };
+  rc = run();
+  if (rc != PTC_OK) (void)hipStreamSynchronize(ctx->stream);  // nothing may still use the pool
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  free_pool(pool);
+  if (rc != PTC_OK) return rc;
+  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, "traversal stack overflow in ptc_occluded_rays");
+  uint64_t count = 0u;
+  if (!fast)
+    for (uint32_t i = 0; i < n; ++i) occluded[i] = tp[i].x >= 0.0f ? (uint8_t)1 : (uint8_t)0;
+  for (uint32_t i = 0; i < n; ++i) count += occluded[i];
+  ctx->occlusion.rays += n;
+  ctx->occlusion.occluded += count;
+  ctx->occlusion.redone += redone;
+  ctx->occlusion.launches += launches;
+  return PTC_OK;
+}
+
+int ptc_get_occlusion_stats(ptc_ctx* ctx, ptc_occlusion_stats* out)
+{
+  if (!ctx || !out) return PTC_ERR_INVALID;
+  *out = ctx->occlusion;
   return PTC_OK;
 }
 

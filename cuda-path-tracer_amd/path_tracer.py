@@ -300,6 +300,23 @@ class PathTracer:
             side.ctypes.data_as(C.POINTER(C.c_uint8))))
         return t, nrm, mat, side
 
+    def occluded_rays(self, rays):
+        """rays: [n, 8] float32 (origin, t_min, direction, t_max).  Returns uint8[n]: 1 where anything lies on the ray within
+        [t_min, t_max] (the reference's ray_scene_intersection_test reports a hit), else 0."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(rays)
+        occluded = np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.ptc_occluded_rays(
+            self._ctx, rays.ctypes.data_as(C.POINTER(C.c_float)), n, occluded.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return occluded
+
+    def occlusion_stats(self):
+        """Counters of occluded_rays since reset_profile / creation."""
+        s = _capi.ptc_occlusion_stats()
+        self._check(self._lib.ptc_get_occlusion_stats(self._ctx, C.byref(s)))
+        return {"rays": int(s.rays), "occluded": int(s.occluded), "redone": int(s.redone), "kernel_ms": float(s.kernel_ms),
+                "launches": int(s.launches)}
+
     def selftest_math(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)
         b = np.ascontiguousarray(b, dtype=np.float32)

@@ -421,6 +421,24 @@ int ptc_get_profile(ptc_ctx* ctx, ptc_profile* out);                /* synchroni
 int ptc_intersect_rays(ptc_ctx* ctx, const float* rays, uint32_t n, float* hit_t, float* hit_normal,
                        uint32_t* hit_material, uint8_t* hit_side);
 
+/* Occlusion queries (an extension: the reference has no any-hit query).  occluded[i] = 1 iff ray_scene_intersection_test
+ * (path_tracer.cu:110-128) reports a hit for ray i, else 0 -- the reference's own arithmetic and corners: world box by
+ * ray_aabb first, spheres in object space against the carried t_max, triangles accept t_min <= t <= t_max, a triangle counts
+ * only if every inner ancestor's box passes.  Emissive surfaces occlude like any other.  Rays as for ptc_intersect_rays (host,
+ * 8 floats each); occluded: n bytes (host).  Rays with t_min 1e-4f or 1e-5f and t_max >= 0 under trace variant 3 take the
+ * any-hit kernels (k_occlude_spheres, k_occlude4: the walk stops at the first hit); any other ray, or trace variant 0 / 1,
+ * sends the whole call through the exact closest-hit kernel of ptc_intersect_rays (the reference-order one when a t_max is
+ * NaN: the reference's test rejects on t > t_max, so it accepts).  Moves neither ptc_stats nor ptc_profile. */
+int ptc_occluded_rays(ptc_ctx* ctx, const float* rays, uint32_t n, uint8_t* occluded);
+/* Since ptc_reset_profile / create: rays asked, rays found occluded, rays the any-hit launches redid with exact box decisions,
+ * device time of the kernels (HIP events; only while ptc_set_profiling has timing on, else 0), kernel launches. */
+typedef struct ptc_occlusion_stats {
+  uint64_t rays, occluded, redone;
+  double kernel_ms;
+  uint32_t launches;
+} ptc_occlusion_stats;
+int ptc_get_occlusion_stats(ptc_ctx* ctx, ptc_occlusion_stats* out);
+
 /* Where the time of the last ptc_upload_scene went (milliseconds of host wall clock; the "Initialization" stage of
  * the reference's Stopwatch, cli.cpp): */
 typedef struct ptc_upload_times {
