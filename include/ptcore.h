@@ -65,6 +65,10 @@ typedef struct ptc_sphere { float center[3]; float radius; } ptc_sphere;
 
 /* Material, material.hpp:19-38 (20 bytes).  type 0 Diffuse {albedo rgb}, 1 Metal {albedo rgb, fuzz},
  * 2 Dielectric {refraction_index},
+ *   Defined behaviour -- the reference's bits, pinned by tests/test_gpu_materials.py -- for any finite albedo (0, above 1,
+ *   products that become denormal or overflow included) and fuzz (above 1 included) and any finite refraction index > 0;
+ *   nothing is clamped.  Other values of types 0-2 (index 0 or negative, NaN / inf in a record) are not refused: they give
+ *   the reference's NaN, in the same pixels, and no more is promised for them.
  * 3 Emissive {emitted radiance rgb, p[3] reserved: 0} -- an extension (the reference has no emitters; parity unpinned by
  *   construction, like ptc_mesh_range).  Each component finite and >= 0, else ptc_upload_scene fails with PTC_ERR_INVALID.
  *   A path whose closest hit is emissive ends at that bounce with colour * emission (binary32, per component, as a miss
