@@ -101,6 +101,21 @@ class ptc_occlusion_stats(C.Structure):
                 ("launches", C.c_uint32)]
 
 
+class ptc_light(C.Structure):
+    _fields_ = [("p0", C.c_float * 3), ("e1", C.c_float * 3), ("e2", C.c_float * 3), ("n", C.c_float * 3), ("cdf", C.c_float),
+                ("inv_pdf", C.c_float), ("object", C.c_uint32), ("kind_material", C.c_uint32)]
+
+
+class ptc_light_info(C.Structure):
+    _fields_ = [("lights", C.c_uint32), ("sphere_lights", C.c_uint32), ("triangle_lights", C.c_uint32),
+                ("emissive_objects", C.c_uint32), ("total_area", C.c_double), ("total_weight", C.c_double)]
+
+
+class ptc_direct_stats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("sampled", C.c_uint64), ("unoccluded", C.c_uint64), ("kernel_ms", C.c_double),
+                ("launches", C.c_uint32)]
+
+
 class ptc_upload_times(C.Structure):
     _fields_ = [("bvh_build_ms", C.c_float), ("layout_ms", C.c_float), ("triangles_ms", C.c_float), ("copy_ms", C.c_float),
                 ("total_ms", C.c_float), ("bvh_on_device", C.c_uint32), ("layout_on_device", C.c_uint32)]
@@ -153,6 +168,10 @@ SIGNATURES = {
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
     "ptc_occluded_rays": (C.c_int, [_P, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint8)]),
     "ptc_get_occlusion_stats": (C.c_int, [_P, C.POINTER(ptc_occlusion_stats)]),
+    "ptc_light_table": (C.c_int, [C.POINTER(ptc_scene_desc), C.POINTER(ptc_light), C.c_uint32, C.POINTER(ptc_light_info)]),
+    "ptc_get_light_info": (C.c_int, [_P, C.POINTER(ptc_light_info)]),
+    "ptc_direct_light": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_int]),
+    "ptc_get_direct_stats": (C.c_int, [_P, C.POINTER(ptc_direct_stats)]),
     "ptc_get_upload_times": (C.c_int, [_P, C.POINTER(ptc_upload_times)]),
     "ptc_download_layout": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ptc_build_bvh_device": (C.c_int, [_P, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,

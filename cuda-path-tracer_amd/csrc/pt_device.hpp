@@ -460,6 +460,28 @@ void launch_occlude_spheres(hipStream_t s, const DScene& scene, uint32_t obj_beg
                             const float4* rays_d, uint32_t n, uint8_t* occluded);
 void launch_occlude(hipStream_t s, const DScene& scene, uint32_t obj_index, const float4* rays_o, const float4* rays_d,
                     uint8_t* occluded, int work_slot, DeviceCounters* counters, uint32_t waves, uint32_t* slow_list, const DBatchInfo& bi);
+// direct-light queries (pt_light.hip).  The lamp table lives outside DScene (which every other kernel takes
+// by value): records = 4 float4 per lamp primitive (ptc_light), cdf = the records' cdf values as a dense array.
+struct DLights {
+  const float4* records;
+  const float* cdf;
+  uint32_t count, last;        // records; last record with a weight > 0
+  const DObject* objects;      // DScene's arrays: a sphere lamp reads its object's matrix and its sphere, every lamp its material
+  const float4* spheres;
+  const DMaterial* materials;
+};
+constexpr uint32_t kLightSeedXor = 0x4c495445u;  // xor-ed into path_seed(point, sample_index): no render path xors its seed
+constexpr uint32_t kLightStatLines = 64u;        // the resolve kernel's two counters, spread over this many 128-byte lines
+//   launch_light_sample   one thread per point: the shadow ray in the path-state layout occlude_on_device takes (o4 = p, tmin_word;
+//                         d4 = w, t_max) and contrib = {unshadowed contribution rgb, 1 if sampled else 0}; a culled sample: t_max 0
+//                         tmin_word: 0 (the any-hit kernels' flag word) or the bits of 1e-4f (launch_intersect's plain t_min)
+//   launch_light_resolve  radiance = sampled and not occluded ? contribution : 0; visible, rays (8 floats per point) may be null;
+//                         occluded: one byte per point, or (null) closest_tp: launch_intersect's records, hit iff .x >= 0;
+//                         stats: kLightStatLines lines of 32 words, word 0 += sampled, word 1 += visible
+void launch_light_sample(hipStream_t s, const DLights& lights, const float* points, const float* normals, uint32_t n, uint32_t sample_index,
+                         uint32_t tmin_word, float4* o4, float4* d4, float4* contrib);
+void launch_light_resolve(hipStream_t s, const float4* o4, const float4* d4, const float4* contrib, const uint8_t* occluded,
+                          const float4* closest_tp, uint32_t n, float* radiance, float* rays, uint8_t* visible, uint32_t* stats);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,
                      float* out_sin, float* out_cos);
 

@@ -770,6 +770,7 @@ int ptc_reset_profile(ptc_ctx* ctx)
   ctx->persist_launches = 0;
   ctx->intersect_redone = 0;
   ctx->occlusion = ptc_occlusion_stats{};
+  ctx->direct = ptc_direct_stats{};
   const size_t off = offsetof(DeviceCounters, paths), end = offsetof(DeviceCounters, work);
   for (auto& sl : ctx->slots)
     for (int k = 0; k < sl.capacity; ++k)

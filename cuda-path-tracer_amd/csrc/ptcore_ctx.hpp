@@ -234,6 +234,15 @@ struct ptc_ctx {
   uint32_t denoise_passes = 0;
   uint32_t persist_launches = 0;         // batches traced through k_persist since ptc_reset_profile
   ptc_occlusion_stats occlusion{};       // ptc_occluded_rays since ptc_reset_profile
+
+  // direct-light queries (ptc_direct_light): the lamp table of the uploaded scene.  Kept out of DScene, which
+  // every existing kernel takes by value.
+  ptc_light_info light_info{};
+  std::string light_error;               // not empty: an emissive sphere of the scene cannot be sampled (the query's refusal)
+  uint32_t light_last = 0;               // last record with a weight > 0
+  const float4* light_records = nullptr; // device: 4 float4 per record (ptc_light); null while there is nothing to sample
+  const float* light_cdf = nullptr;      // device: the records' cdf values, dense (the binary search)
+  ptc_direct_stats direct{};             // ptc_direct_light since ptc_reset_profile
 };
 
 
@@ -259,6 +268,9 @@ int flush_pending(ptc_ctx* ctx, bool from_trace = false);  // enqueue the iterat
 int sync_frames(ptc_ctx* ctx);
 void free_slots(ptc_ctx* ctx);
 int frame_ready(ptc_ctx* ctx);
+// The lamp table of a validated scene (ptcore_scene.cpp; include/ptcore.h: ptc_light).  *last = last record with a weight > 0.
+// Returns PTC_OK, or PTC_ERR_INVALID with `err` naming the emissive sphere whose matrix is no similarity.
+int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err);
 
 template <typename T>
 int dev_alloc(ptc_ctx* ctx, std::vector<void*>& pool, T** out, size_t count)

@@ -1,6 +1,7 @@
 // ptcore_scene.cpp -- ptc_upload_scene and what it needs: validation, the world-space balls of sphere objects, the reference
 // BVH and the traversal layouts (host or device side), ptc_build_bvh*, ptc_make_object.  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
+#include "pt_layout_rules.hpp"
 
 #include <cmath>
 
@@ -213,6 +214,119 @@ uint32_t bvh_depth_of(const ptc_bvh_node* nodes, uint32_t count, std::vector<uin
 
 }  // namespace
 
+namespace ptcd {
+
+// The lamp table (include/ptcore.h: ptc_light) from the caller's arrays -- not from DScene::tris, which is in
+// tree order and may exist only on the device.  Records in binary32 with the operations of the instance triangles
+// (layout_rules::instance_triangle); weights, their running sum and the cdf in binary64, from the records' own fields.
+int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err)
+{
+  out.clear();
+  ptc_light_info li{};
+  std::vector<double> weight;
+  std::vector<float> lum_of;
+  for (uint32_t i = 0; i < s->object_count; ++i) {
+    const ptc_object& o = s->objects[i];
+    const uint32_t mi = s->object_material_indices[i];
+    const ptc_material& mat = s->materials[mi];
+    if (mat.type != 3) continue;
+    ++li.emissive_objects;
+    const float lum = std::max(std::max(mat.p[0], mat.p[1]), mat.p[2]);
+    m4 m;
+    std::memcpy(&m, o.m, sizeof m);
+    auto push = [&](ptc_light& l, uint32_t kind, double area) {
+      l.cdf = 0.0f;
+      l.inv_pdf = 0.0f;
+      l.object = i;
+      l.kind_material = mi | kind << 31;
+      out.push_back(l);
+      weight.push_back(area * (double)lum);
+      lum_of.push_back(lum);
+      li.total_area += area;
+    };
+    if (o.type == 0u) {
+      // uniform on the object-space sphere is uniform in area on its image only under a similarity
+      double len[3], c[3][3];
+      for (int k = 0; k < 3; ++k) {
+        for (int r = 0; r < 3; ++r) c[k][r] = (double)o.m[4 * k + r];
+        len[k] = std::sqrt(c[k][0] * c[k][0] + c[k][1] * c[k][1] + c[k][2] * c[k][2]);
+      }
+      bool ok = o.m[3] == 0.0f && o.m[7] == 0.0f && o.m[11] == 0.0f && o.m[15] == 1.0f && std::isfinite(len[0] + len[1] + len[2]) && len[0] > 0.0;
+      for (int a = 0; a < 3 && ok; ++a)
+        for (int b = a + 1; b < 3; ++b) {
+          const double dt = c[a][0] * c[b][0] + c[a][1] * c[b][1] + c[a][2] * c[b][2];
+          ok = ok && std::fabs(dt) <= 1e-5 * len[a] * len[b] && std::fabs(len[a] - len[b]) <= 1e-5 * std::max(len[a], len[b]);
+        }
+      if (!ok) {
+        *err = "object " + std::to_string(i) + ": an emissive sphere whose matrix is not a similarity (rotation x uniform scale + translation) cannot be sampled";
+        out.clear();
+        return PTC_ERR_INVALID;
+      }
+      const ptc_sphere& sp = s->spheres[o.index];
+      const f3 centre = xform_point(m, mk3(sp.center[0], sp.center[1], sp.center[2]));
+      const float radius = length(mk3(o.m[0], o.m[1], o.m[2])) * sp.radius;
+      ptc_light l{};
+      l.p0[0] = centre.x, l.p0[1] = centre.y, l.p0[2] = centre.z;
+      l.e1[0] = radius;
+      push(l, 1u, 4.0 * 3.14159265358979323846 * (double)radius * (double)radius);
+      ++li.sphere_lights;
+    } else {
+      const float* positions = s->positions;
+      const uint32_t* indices = s->indices;
+      uint32_t index_count = s->index_count;
+      if (s->meshes) {
+        const ptc_mesh_range& r = s->meshes[o.index];
+        positions += 3u * (size_t)r.first_vertex;
+        indices += r.first_index;
+        index_count = r.index_count;
+      }
+      for (uint32_t t = 0; t + 2u < index_count; t += 3u) {
+        const float *q0 = positions + 3u * (size_t)indices[t], *q1 = positions + 3u * (size_t)indices[t + 1u],
+                    *q2 = positions + 3u * (size_t)indices[t + 2u];
+        float4 rec[kTriVec4];
+        layout_rules::instance_triangle(m, mk3(q0[0], q0[1], q0[2]), mk3(q1[0], q1[1], q1[2]), mk3(q2[0], q2[1], q2[2]), rec);
+        ptc_light l{};
+        std::memcpy(l.p0, rec, 12u * sizeof(float));
+        const double e1[3] = {l.e1[0], l.e1[1], l.e1[2]}, e2[3] = {l.e2[0], l.e2[1], l.e2[2]};
+        const double cx = e1[1] * e2[2] - e2[1] * e1[2], cy = e1[2] * e2[0] - e2[2] * e1[0], cz = e1[0] * e2[1] - e2[0] * e1[1];
+        push(l, 0u, 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz));
+        ++li.triangle_lights;
+      }
+    }
+    if (out.size() > 0x7fffffffu) {
+      *err = "more than 2^31 - 1 lamp primitives";
+      out.clear();
+      return PTC_ERR_INVALID;
+    }
+  }
+  li.lights = (uint32_t)out.size();
+  double W = 0.0;
+  uint32_t last_live = 0u;
+  for (size_t k = 0; k < out.size(); ++k) {
+    if (!std::isfinite(weight[k])) {
+      *err = "lamp primitive " + std::to_string(k) + " (object " + std::to_string(out[k].object) + ") has no finite area";
+      out.clear();
+      return PTC_ERR_INVALID;
+    }
+    W += weight[k];
+    if (weight[k] > 0.0) last_live = (uint32_t)k;
+  }
+  li.total_weight = W;
+  if (W > 0.0) {
+    double run = 0.0;
+    for (size_t k = 0; k < out.size(); ++k) {
+      run += weight[k];
+      out[k].cdf = k >= last_live ? 1.0f : (float)(run / W);
+      out[k].inv_pdf = lum_of[k] == 0.0f ? 0.0f : (float)(W / (double)lum_of[k]);
+    }
+  }
+  if (info) *info = li;
+  if (last) *last = last_live;
+  return PTC_OK;
+}
+
+}  // namespace ptcd
+
 namespace {
 // The reference BVH of a mesh built on the device.  nodes_host gets the 2T-1 nodes in the reference's layout;
 // *packed_out (when asked for) keeps the device copy in DScene::bvh's layout, owned by the caller.
@@ -366,11 +480,31 @@ int ptc_upload_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
     total_triangles += w.index_count / 3u;
   }
 
+  // the lamp table (direct-light queries), on the host from the caller's arrays.  An emissive sphere that
+  // cannot be sampled is no reason to refuse the scene: it renders as ever, only ptc_direct_light refuses
+  std::vector<ptc_light> lights;
+  ptc_light_info light_info{};
+  uint32_t light_last = 0u;
+  std::string light_error;
+  if (build_light_table(s, lights, &light_info, &light_last, &light_error) != PTC_OK) light_info = ptc_light_info{};
+
   // ---- phase 2: the old scene goes.  Iterations queued or in flight were asked for against it: trace them first
   if (int rc = sync_frames(ctx)) return rc;
   free_pool(ctx->scene_allocs);
   ctx->has_scene = false;
   ctx->has_emitters = false;
+  ctx->light_records = nullptr;
+  ctx->light_cdf = nullptr;
+  ctx->light_info = light_info;
+  ctx->light_last = light_last;
+  ctx->light_error = light_error;
+  if (!lights.empty() && light_info.total_weight > 0.0) {
+    std::vector<float> cdf(lights.size());
+    for (size_t k = 0; k < lights.size(); ++k) cdf[k] = lights[k].cdf;
+    static_assert(sizeof(ptc_light) == 4 * sizeof(float4), "a lamp record is four float4");
+    if (int rc = upload(ctx, ctx->scene_allocs, &ctx->light_records, reinterpret_cast<const float4*>(lights.data()), 4u * lights.size())) return rc;
+    if (int rc = upload(ctx, ctx->scene_allocs, &ctx->light_cdf, cdf.data(), cdf.size())) return rc;
+  }
   ++ctx->scene_serial;
   DScene d{};
   const DObject* objects = nullptr;
@@ -621,6 +755,29 @@ int ptc_get_upload_times(const ptc_ctx* ctx, ptc_upload_times* out)
 {
   if (!ctx || !out) return PTC_ERR_INVALID;
   *out = ctx->upload_times;
+  return PTC_OK;
+}
+
+int ptc_light_table(const ptc_scene_desc* scene, ptc_light* out, uint32_t capacity, ptc_light_info* info)
+{
+  if (!scene || !out) return fail(nullptr, PTC_ERR_INVALID, "scene or out is NULL");
+  if (int rc = validate_scene(nullptr, scene)) return rc;
+  std::vector<ptc_light> lights;
+  ptc_light_info li{};
+  std::string err;
+  if (int rc = build_light_table(scene, lights, &li, nullptr, &err)) return fail(nullptr, rc, err);
+  if (lights.size() > capacity)
+    return fail(nullptr, PTC_ERR_INVALID, "capacity " + std::to_string(capacity) + " is too small for " + std::to_string(lights.size()) + " lamp primitives");
+  if (!lights.empty()) std::memcpy(out, lights.data(), lights.size() * sizeof(ptc_light));
+  if (info) *info = li;
+  return (int)lights.size();
+}
+
+int ptc_get_light_info(ptc_ctx* ctx, ptc_light_info* out)
+{
+  if (!ctx || !out) return PTC_ERR_INVALID;
+  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
+  *out = ctx->light_info;
   return PTC_OK;
 }
 

@@ -452,6 +452,16 @@ struct OccludeScratch {
   uint2* spill;               // scene.spill_cap * scene.spill_stride
   DeviceCounters* counters;   // one block; its slow_rays[0] and flags are the launches' results
 };
+// the flags and the scratch of one query of n rays, into the caller's pool (ptc_occluded_rays, ptc_direct_light)
+int alloc_occlude_scratch(ptc_ctx* ctx, std::vector<void*>& pool, uint32_t n, uint8_t** flags, OccludeScratch* scr)
+{
+  int rc = dev_alloc(ctx, pool, flags, n);
+  if (!rc) rc = dev_alloc(ctx, pool, &scr->slow_list, n);
+  if (!rc) rc = dev_alloc(ctx, pool, &scr->slow_stack, (size_t)kStackDepth * kWave);
+  if (!rc) rc = dev_alloc(ctx, pool, &scr->spill, (size_t)ctx->scene.spill_cap * ctx->scene.spill_stride);
+  if (!rc) rc = dev_alloc(ctx, pool, &scr->counters, 1);
+  return rc;
+}
 int occlude_on_device(ptc_ctx* ctx, hipStream_t stream, const float4* rays_o4, const float4* rays_d4, uint32_t n, uint8_t* flags,
                       const OccludeScratch& scr, uint32_t* launches)
 {
@@ -834,11 +844,7 @@ int ptc_occluded_rays(ptc_ctx* ctx, const float* rays, uint32_t n, uint8_t* occl
   int rc = dev_alloc(ctx, pool, &ro, n);
   if (!rc) rc = dev_alloc(ctx, pool, &rd, n);
   if (!rc && fast) {
-    rc = dev_alloc(ctx, pool, &flags, n);
-    if (!rc) rc = dev_alloc(ctx, pool, &scr.slow_list, n);
-    if (!rc) rc = dev_alloc(ctx, pool, &scr.slow_stack, (size_t)kStackDepth * kWave);
-    if (!rc) rc = dev_alloc(ctx, pool, &scr.spill, (size_t)ctx->scene.spill_cap * ctx->scene.spill_stride);
-    if (!rc) rc = dev_alloc(ctx, pool, &scr.counters, 1);
+    rc = alloc_occlude_scratch(ctx, pool, n, &flags, &scr);
   } else if (!rc) {
     rc = dev_alloc(ctx, pool, &hits.tp, n);
     if (!rc) rc = dev_alloc(ctx, pool, &hits.nm, n);
@@ -917,6 +923,150 @@ int ptc_get_occlusion_stats(ptc_ctx* ctx, ptc_occlusion_stats* out)
 {
   if (!ctx || !out) return PTC_ERR_INVALID;
   *out = ctx->occlusion;
+  return PTC_OK;
+}
+
+// Direct-light queries: k_light_sample writes the shadow rays where occlude_on_device takes them -- its first
+// caller with rays that were never on the host -- and k_light_resolve combines its flags with the unshadowed contributions.
+int ptc_direct_light(ptc_ctx* ctx, const float* points, const float* normals, uint32_t n, uint32_t sample_index, float* radiance,
+                     float* shadow_rays, uint8_t* visible, int on_device)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
+  if (!ctx->light_error.empty()) return fail(ctx, PTC_ERR_INVALID, ctx->light_error);
+  if (n == 0) return PTC_OK;
+  if (!points || !normals || !radiance) return fail(ctx, PTC_ERR_INVALID, "points, normals or radiance is NULL");
+  if (n > 0x7fffffffu) return fail(ctx, PTC_ERR_INVALID, "too many points");
+  if (on_device && shadow_rays && ((uintptr_t)shadow_rays & 15u)) return fail(ctx, PTC_ERR_INVALID, "shadow_rays on the device must be 16-byte aligned");
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = flush_pending(ctx)) return rc;
+  const size_t n3 = 3u * (size_t)n;
+  if (!ctx->light_records) {
+    // no lamp, or lamps of total weight 0: zeros, the empty ray from every point, and no launch
+    std::vector<float> rays;
+    if (shadow_rays) {
+      std::vector<float> pts;
+      const float* src = points;
+      if (on_device) {
+        pts.resize(n3);
+        HIP_TRY(ctx, hipMemcpy(pts.data(), points, n3 * sizeof(float), hipMemcpyDeviceToHost));
+        src = pts.data();
+      }
+      rays.assign(8u * (size_t)n, 0.0f);
+      for (uint32_t i = 0; i < n; ++i) {
+        std::memcpy(&rays[8u * (size_t)i], src + 3u * (size_t)i, 3u * sizeof(float));
+        rays[8u * (size_t)i + 3u] = 1e-4f;
+      }
+    }
+    if (on_device) {
+      HIP_TRY(ctx, hipMemsetAsync(radiance, 0, n3 * sizeof(float), ctx->stream));
+      if (visible) HIP_TRY(ctx, hipMemsetAsync(visible, 0, n, ctx->stream));
+      if (shadow_rays) HIP_TRY(ctx, hipMemcpyAsync(shadow_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+      std::memset(radiance, 0, n3 * sizeof(float));
+      if (visible) std::memset(visible, 0, n);
+      if (shadow_rays) std::memcpy(shadow_rays, rays.data(), rays.size() * sizeof(float));
+    }
+    ctx->direct.points += n;
+    return PTC_OK;
+  }
+  // trace variants 0 / 1 stay cross-checks: the generated rays go through the exact closest-hit kernel, as in ptc_occluded_rays
+  // (there t_min travels as a float; a generated t_max is never NaN: d * 0.999f of a finite d, or 0)
+  const bool fast = ctx->trace_variant == 3;
+  std::vector<void*> pool;
+  float *d_pts = nullptr, *d_nrm = nullptr, *d_rad = radiance, *d_rays = shadow_rays;
+  uint8_t *d_vis = visible, *flags = nullptr;
+  float4 *o4 = nullptr, *d4 = nullptr, *contrib = nullptr;
+  uint32_t* stats = nullptr;
+  DHits hits{};
+  OccludeScratch scr{};
+  int rc = dev_alloc(ctx, pool, &o4, n);
+  if (!rc) rc = dev_alloc(ctx, pool, &d4, n);
+  if (!rc) rc = dev_alloc(ctx, pool, &contrib, n);
+  if (!rc) rc = dev_alloc(ctx, pool, &stats, (size_t)kLightStatLines * 32u);
+  if (!rc && !on_device) {
+    rc = dev_alloc(ctx, pool, &d_pts, n3);
+    if (!rc) rc = dev_alloc(ctx, pool, &d_nrm, n3);
+    if (!rc) rc = dev_alloc(ctx, pool, &d_rad, n3);
+    if (!rc && shadow_rays) rc = dev_alloc(ctx, pool, &d_rays, 8u * (size_t)n);
+    if (!rc && visible) rc = dev_alloc(ctx, pool, &d_vis, n);
+  }
+  if (!rc && fast) rc = alloc_occlude_scratch(ctx, pool, n, &flags, &scr);
+  else if (!rc) {
+    rc = dev_alloc(ctx, pool, &hits.tp, n);
+    if (!rc) rc = dev_alloc(ctx, pool, &hits.nm, n);
+  }
+  if (rc) {
+    free_pool(pool);
+    return rc;
+  }
+  DLights lights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres, ctx->scene.materials};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  const bool timed = ctx->time_trace;
+  uint32_t launches = 0u, dev_flags = 0u;
+  std::vector<uint32_t> host_stats((size_t)kLightStatLines * 32u, 0u);
+  auto run = [&]() -> int {
+    if (!on_device) {
+      HIP_TRY(ctx, hipMemcpyAsync(d_pts, points, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(d_nrm, normals, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(ctx, hipMemsetAsync(stats, 0, host_stats.size() * sizeof(uint32_t), ctx->stream));
+    if (timed) {
+      HIP_TRY(ctx, hipEventCreate(&ev[0]));
+      HIP_TRY(ctx, hipEventCreate(&ev[1]));
+      HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
+    }
+    const float tmin = 1e-4f;
+    uint32_t tmin_word = 0u;
+    if (!fast) std::memcpy(&tmin_word, &tmin, 4);
+    launch_light_sample(ctx->stream, lights, on_device ? points : d_pts, on_device ? normals : d_nrm, n, sample_index, tmin_word, o4, d4, contrib);
+    ++launches;
+    if (fast) {
+      if (int r2 = occlude_on_device(ctx, ctx->stream, o4, d4, n, flags, scr, &launches)) return r2;
+    } else {
+      launch_intersect(ctx->stream, ctx->scene, o4, d4, n, hits, ctx->misc_counters, ctx->trace_variant == 0 ? 0 : 1);
+      ++launches;
+    }
+    launch_light_resolve(ctx->stream, o4, d4, contrib, flags, hits.tp, n, d_rad, d_rays, d_vis, stats);
+    ++launches;
+    if (int r2 = check_last(ctx, "direct-light query")) return r2;
+    if (timed) HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
+    if (!on_device) {
+      HIP_TRY(ctx, hipMemcpyAsync(radiance, d_rad, n3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+      if (shadow_rays) HIP_TRY(ctx, hipMemcpyAsync(shadow_rays, d_rays, 8u * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+      if (visible) HIP_TRY(ctx, hipMemcpyAsync(visible, d_vis, n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(host_stats.data(), stats, host_stats.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (fast) HIP_TRY(ctx, hipMemcpyAsync(&dev_flags, &scr.counters->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed) {
+      float ms = 0.0f;
+      HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
+      ctx->direct.kernel_ms += (double)ms;
+    }
+    return PTC_OK;
+  };
+  rc = run();
+  if (rc != PTC_OK) (void)hipStreamSynchronize(ctx->stream);  // nothing may still use the pool
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  free_pool(pool);
+  if (rc != PTC_OK) return rc;
+  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, "traversal stack overflow in ptc_direct_light");
+  for (uint32_t l = 0; l < kLightStatLines; ++l) {
+    ctx->direct.sampled += host_stats[32u * l];
+    ctx->direct.unoccluded += host_stats[32u * l + 1u];
+  }
+  ctx->direct.points += n;
+  ctx->direct.launches += launches;
+  return PTC_OK;
+}
+
+int ptc_get_direct_stats(ptc_ctx* ctx, ptc_direct_stats* out)
+{
+  if (!ctx || !out) return PTC_ERR_INVALID;
+  *out = ctx->direct;
   return PTC_OK;
 }
 

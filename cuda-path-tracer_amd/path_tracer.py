@@ -33,6 +33,40 @@ class EdgeAvoidingATrousDenoiser:  # denoising/edge_avoiding_a_trous_denoiser.hp
     position_weight: float = 0.25
 
 
+LIGHT_DTYPE = np.dtype([("p0", "<f4", (3,)), ("e1", "<f4", (3,)), ("e2", "<f4", (3,)), ("n", "<f4", (3,)), ("cdf", "<f4"),
+                        ("inv_pdf", "<f4"), ("object", "<u4"), ("kind_material", "<u4")])
+assert LIGHT_DTYPE.itemsize == 64
+
+
+def _light_info_dict(info):
+    return {"lights": int(info.lights), "sphere_lights": int(info.sphere_lights), "triangle_lights": int(info.triangle_lights),
+            "emissive_objects": int(info.emissive_objects), "total_area": float(info.total_area),
+            "total_weight": float(info.total_weight)}
+
+
+def light_table(scene, capacity=None):
+    """The lamp table of a scene (ptc_light_table; host-side, no GPU needed): one 64-byte record per primitive of every
+    emissive object.  scene: a SceneDescription or a FlatScene.  -> (records [LIGHT_DTYPE], info dict).  capacity: records
+    the output may hold (default: every primitive of the scene)."""
+    flat = scene.build_scene() if isinstance(scene, SceneDescription) else scene
+    desc = flat.to_c()
+    if capacity is None:
+        capacity = 0
+        for obj, mat in zip(flat.objects, flat.object_material_indices):
+            if mat < len(flat.materials) and flat.materials["type"][mat] == 3:
+                if obj["type"] == 0:
+                    capacity += 1
+                elif flat.mesh_ranges is None:
+                    capacity += len(flat.indices) // 3
+                elif obj["index"] < len(flat.mesh_ranges):
+                    capacity += int(np.asarray(flat.mesh_ranges).reshape(-1, 6)[obj["index"], 3]) // 3
+    out = np.zeros(max(int(capacity), 1), dtype=LIGHT_DTYPE)
+    info = _capi.ptc_light_info()
+    rc = _capi.check(_capi.lib().ptc_light_table(C.byref(desc), out.ctypes.data_as(C.POINTER(_capi.ptc_light)), int(capacity),
+                                                 C.byref(info)))
+    return out[:rc].copy(), _light_info_dict(info)
+
+
 class PathTracer:
     def __init__(self, device=0, max_bounces=50):
         self._lib = _capi.lib()
@@ -316,6 +350,49 @@ class PathTracer:
         self._check(self._lib.ptc_get_occlusion_stats(self._ctx, C.byref(s)))
         return {"rays": int(s.rays), "occluded": int(s.occluded), "redone": int(s.redone), "kernel_ms": float(s.kernel_ms),
                 "launches": int(s.launches)}
+
+    @staticmethod
+    def light_table(scene, capacity=None):
+        """The module function light_table (ptc_light_table): the lamp table of a scene, on the host."""
+        return light_table(scene, capacity)
+
+    def light_info(self):
+        """Counts, total area and total weight of the uploaded scene's lamp table (ptc_get_light_info)."""
+        info = _capi.ptc_light_info()
+        self._check(self._lib.ptc_get_light_info(self._ctx, C.byref(info)))
+        return _light_info_dict(info)
+
+    def direct_light(self, points, normals, sample_index=0, want_rays=False):
+        """One light sample per surface point (ptc_direct_light).  points, normals: [n, 3] float32 (finite points, unit
+        normals).  Returns radiance [n, 3]: what the lamps send to a white Lambertian surface there by this sample; with
+        want_rays also the shadow rays [n, 8] (origin, t_min, direction, t_max) and visible uint8[n]."""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        n = len(points)
+        if len(normals) != n:
+            raise ValueError("points and normals differ in length")
+        radiance = np.zeros((n, 3), dtype=np.float32)
+        rays = np.zeros((n, 8), dtype=np.float32) if want_rays else None
+        visible = np.zeros(n, dtype=np.uint8) if want_rays else None
+        self._check(self._lib.ptc_direct_light(
+            self._ctx, points.ctypes.data, normals.ctypes.data, n, int(sample_index), radiance.ctypes.data,
+            rays.ctypes.data if want_rays else None, visible.ctypes.data if want_rays else None, 0))
+        return (radiance, rays, visible) if want_rays else radiance
+
+    def direct_light_dev(self, points_ptr, normals_ptr, n, sample_index, radiance_ptr, rays_ptr=None, visible_ptr=None):
+        """direct_light on device memory (torch tensors' data_ptr()): 3 floats per point in and out; optionally 8 floats
+        per point of shadow rays (16-byte aligned) and one byte of visibility.  Synchronises like download."""
+        self._check(self._lib.ptc_direct_light(
+            self._ctx, C.c_void_p(int(points_ptr)), C.c_void_p(int(normals_ptr)), int(n), int(sample_index),
+            C.c_void_p(int(radiance_ptr)), C.c_void_p(int(rays_ptr)) if rays_ptr else None,
+            C.c_void_p(int(visible_ptr)) if visible_ptr else None, 1))
+
+    def direct_stats(self):
+        """Counters of direct_light since reset_profile / creation."""
+        s = _capi.ptc_direct_stats()
+        self._check(self._lib.ptc_get_direct_stats(self._ctx, C.byref(s)))
+        return {"points": int(s.points), "sampled": int(s.sampled), "unoccluded": int(s.unoccluded),
+                "kernel_ms": float(s.kernel_ms), "launches": int(s.launches)}
 
     def selftest_math(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)

@@ -443,6 +443,64 @@ typedef struct ptc_occlusion_stats {
 } ptc_occlusion_stats;
 int ptc_get_occlusion_stats(ptc_ctx* ctx, ptc_occlusion_stats* out);
 
+/* Direct-light queries (an extension: the reference has no emitters).
+ * The lamp table of a scene: one record per primitive of every object whose material is emissive (type 3) -- emissive objects
+ * in object-list order, the triangles of a mesh object in index order, two instances of one mesh as two sets of records. */
+typedef struct ptc_light {           /* one lamp primitive, 64 bytes, world space */
+  float p0[3], e1[3], e2[3], n[3];   /* triangle: transform_point(M, v0), p1 - p0, p2 - p0, normalize(cross(e1, e2)) -- the operations of
+                                        DScene::tris;  sphere: p0 = transform_point(M, centre), e1[0] = world radius = length of M's
+                                        column 0 (binary32, glm order) * radius, the rest 0 */
+  float cdf;                         /* (float)(sum of the weights up to and including this record / W); the last record with a
+                                        weight > 0 and every record behind it: exactly 1.0f */
+  float inv_pdf;                     /* 1 / (area density of a sample on this primitive) = (float)(W / lum), 0 when lum == 0 */
+  uint32_t object;                   /* index into ptc_scene_desc::objects */
+  uint32_t kind_material;            /* material index | kind << 31  (kind 0 triangle, 1 sphere) */
+} ptc_light;
+/* weight of a record = area * lum in binary64 from the record's own binary32 fields: area = 0.5 |e1 x e2| or 4 pi R^2,
+ * lum = max(r, g, b) of the material's emission; W = the weights summed in table order.  A sample picks record
+ * k = min(#{j : cdf_j <= u0}, last record with a weight > 0) for u0 in [0, 1]: a record of weight 0 is never picked. */
+typedef struct ptc_light_info {
+  uint32_t lights, sphere_lights, triangle_lights, emissive_objects;
+  double total_area, total_weight;
+} ptc_light_info;
+/* Host-side, no GPU needed: the table of `scene` into out[capacity]; info may be NULL.  Returns the number of records (0: no
+ * lamps) or a negative ptc_status: PTC_ERR_INVALID for NULL arguments, a scene ptc_upload_scene would refuse, a capacity that
+ * is too small, and an emissive SPHERE whose matrix is no similarity -- a sphere lamp is sampled uniformly in object space,
+ * which is uniform in area only if the columns of the upper 3 x 3 are pairwise orthogonal and of equal length (both to 1e-5
+ * relative) and the bottom row is (0, 0, 0, 1); the message (ptc_last_error(NULL)) names the object.  Mesh lamps take any
+ * matrix.  Such a scene still uploads and renders; only this call and ptc_direct_light refuse it. */
+int ptc_light_table(const ptc_scene_desc* scene, ptc_light* out, uint32_t capacity, ptc_light_info* info);
+int ptc_get_light_info(ptc_ctx* ctx, ptc_light_info* out);    /* of the uploaded scene (zeros while its lamps cannot be sampled) */
+
+/* radiance[3i..] = radiance leaving a white Lambertian surface at points[i] with unit normal normals[i] by ONE light sample:
+ *   Le * cos_r * cos_l * inv_pdf / (pi * d^2) if the shadow ray is free, else 0
+ * with w = (q - p) / d, cos_r = dot(n, w) (<= 0: no sample), cos_l = |dot(n_l, w)| (lamps are two-sided, as in the path
+ * tracer; a sphere lamp's far side is hidden by the lamp itself -- the shadow ray decides, not a special case).
+ * Shadow ray: origin p, t_min 1e-4f, direction w, t_max = d * 0.999f (the any-hit walk's fast domain).
+ * Draws: Minstd seeded from path_seed(i, sample_index) xor 0x4c495445 (no render path xors its seed); u0 picks the lamp, u1, u2
+ * the point (triangle: b1 = 1 - sqrt(u1), b2 = u2 * sqrt(u1), q = p0 + b1 e1 + b2 e2; sphere: z = 1 - 2 u1,
+ * r = sqrt(max(0, 1 - z^2)), phi = 2 pi u2 through det_sincos, q = transform_point(M, c + R * dir), n_l = normalize(q - world
+ * centre)).  The binary32 operation order: DESIGN section 5f.
+ * A sample with cos_r <= 0, d == 0 (or not finite), a picked lamp of weight 0, or no lamps: radiance 0, visible 0,
+ * ray = {p, 1e-4f, 0, 0, 0, 0}.
+ * shadow_rays (8 floats per point, as ptc_intersect_rays takes them) and visible (1 byte per point) may be NULL.
+ * on_device != 0: every pointer is a device pointer (a torch tensor); the call synchronises like ptc_download.
+ * Under trace variant 0 / 1 the generated rays go through the exact closest-hit kernel, as in ptc_occluded_rays.
+ * A scene without lamps (or of total weight 0) gives zeros and launches nothing; a scene with an emissive sphere that cannot
+ * be sampled (ptc_light_table) fails with PTC_ERR_INVALID.
+ * Finite points and unit normals are the contract; moves neither ptc_stats nor ptc_profile nor ptc_occlusion_stats. */
+int ptc_direct_light(ptc_ctx* ctx, const float* points, const float* normals, uint32_t n, uint32_t sample_index,
+                     float* radiance, float* shadow_rays, uint8_t* visible, int on_device);
+/* Since ptc_reset_profile / create: points asked, samples that produced a shadow ray (points - culled), samples that arrived,
+ * device time of the kernels -- k_light_sample, the occlusion launches, k_light_resolve -- (HIP events; only while
+ * ptc_set_profiling has timing on, else 0), kernel launches. */
+typedef struct ptc_direct_stats {
+  uint64_t points, sampled, unoccluded;
+  double kernel_ms;
+  uint32_t launches;
+} ptc_direct_stats;
+int ptc_get_direct_stats(ptc_ctx* ctx, ptc_direct_stats* out);
+
 /* Where the time of the last ptc_upload_scene went (milliseconds of host wall clock; the "Initialization" stage of
  * the reference's Stopwatch, cli.cpp): */
 typedef struct ptc_upload_times {
