@@ -10,7 +10,8 @@
 //     being partitioned in place through a Thrust temporary.
 //
 // This unit: context, frame slots (ptc_resize), parameters, denoise / present / download, statistics.  Scene upload:
-// ptcore_scene.cpp; the launch plan of a batch: ptcore_trace.cpp; several GPUs: ptcore_bands.cpp; host-side checks: ptcore_checks.cpp.
+// ptcore_scene.cpp; the launch plan of a batch: ptcore_trace.cpp; the ray queries: ptcore_query.cpp; several GPUs: ptcore_bands.cpp;
+// host-side checks: ptcore_checks.cpp.
 #include "ptcore_ctx.hpp"
 
 using namespace pt;

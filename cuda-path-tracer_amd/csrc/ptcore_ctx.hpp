@@ -1,6 +1,7 @@
 // ptcore_ctx.hpp -- private to libptcore.so: the context behind include/ptcore.h and the helpers its translation units share
 // (ptcore.cpp: context, frame slots, parameters, views; ptcore_scene.cpp: scene upload; ptcore_trace.cpp: the launch plan of a
-// batch of frames; ptcore_bands.cpp: several GPUs; ptcore_checks.cpp: host-side checks of the schedule helpers).
+// batch of frames; ptcore_query.cpp: the ray queries outside the render loop; ptcore_bands.cpp: several GPUs; ptcore_checks.cpp:
+// host-side checks of the schedule helpers).
 #pragma once
 
 #include "../../include/ptcore.h"
@@ -141,7 +142,7 @@ struct ptc_ctx {
   const float4* result = nullptr;
   float* pack_buf = nullptr;     // 3 floats / pixel staging for downloads
   uint32_t* rgba_buf = nullptr;  // staging for host presents
-  DeviceCounters* misc_counters = nullptr;  // flags of kernels outside the frame loop (ptc_intersect_rays)
+  DeviceCounters* misc_counters = nullptr;  // flags of kernels outside the frame loop (ptcore_query.cpp: exact_closest_hit)
   uint32_t slot_offset = 0;                 // "slot_offset" (multi-GPU: distinct random streams per rank)
   uint32_t* slot_offset_dev = nullptr;
   hipEvent_t xstream_event = nullptr;       // orders the stepwise calls between a frame's stream and ctx->stream
@@ -265,12 +266,26 @@ int bind_device(ptc_ctx* ctx);
 void free_pool(std::vector<void*>& pool);
 DCamera make_camera(const ptc_camera& c, uint32_t w, uint32_t h);
 int flush_pending(ptc_ctx* ctx, bool from_trace = false);  // enqueue the iterations ptc_trace has queued (ptcore_trace.cpp)
+uint32_t fold_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end);  // may k_spheres take sphere_fold for this run? (ptcore_trace.cpp)
 int sync_frames(ptc_ctx* ctx);
 void free_slots(ptc_ctx* ctx);
 int frame_ready(ptc_ctx* ctx);
 // The lamp table of a validated scene (ptcore_scene.cpp; include/ptcore.h: ptc_light).  *last = last record with a weight > 0.
 // Returns PTC_OK, or PTC_ERR_INVALID with `err` naming the emissive sphere whose matrix is no similarity.
 int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err);
+
+// What a traversal launch over n rays needs besides its rays, outside a frame slot (ptcore_query.cpp).  The queries allocate it per
+// call (alloc_walk_scratch, into the call's pool); a bounce loop would fill it with its slot's buffers instead.
+struct WalkScratch {
+  uint32_t* slow_list = nullptr;       // n entries
+  uint32_t* slow_stack = nullptr;      // kStackDepth * kWave
+  uint2* spill = nullptr;              // scene.spill_cap * scene.spill_stride
+  DeviceCounters* counters = nullptr;  // one block; its slow_rays[0] and flags are the launches' results
+  uint32_t* chunk_counts = nullptr;    // n / kChunk + 1 entries, for launch_tail_count: the closest-hit query alone asks for it
+};
+int alloc_walk_scratch(ptc_ctx* ctx, std::vector<void*>& pool, uint32_t n, bool want_chunks, WalkScratch* scr);
+int occlude_on_device(ptc_ctx* ctx, hipStream_t stream, const float4* rays_o4, const float4* rays_d4, uint32_t n, uint8_t* flags,
+                      const WalkScratch& scr, uint32_t* launches);
 
 template <typename T>
 int dev_alloc(ptc_ctx* ctx, std::vector<void*>& pool, T** out, size_t count)

@@ -1,5 +1,5 @@
 // ptcore_trace.cpp -- the launch plan of a batch of frames (batch_begin / batch_bounce / batch_end), ptc_trace and its stepwise
-// form, the live counts, ptc_intersect_rays.  Part of libptcore.so (ptcore_ctx.hpp).
+// form, the live counts.  Part of libptcore.so (ptcore_ctx.hpp).  The ray queries outside the render loop: ptcore_query.cpp.
 #include "ptcore_ctx.hpp"
 
 using namespace pt;
@@ -68,15 +68,6 @@ static uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
   if (k == 0u) return 0u;
   for (uint32_t i = begin; i < end; ++i)
     if (ctx->sphere_class[i] != k) return 0u;
-  return 1u;
-}
-
-// may k_spheres take sphere_fold for the run [begin, end)?  Every object a "simple" sphere (sphere_ball_of)
-static uint32_t fold_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
-{
-  if (!ctx->sphere_fold || end <= begin || end > ctx->sphere_class.size()) return 0u;
-  for (uint32_t i = begin; i < end; ++i)
-    if (ctx->sphere_class[i] == 0u) return 0u;
   return 1u;
 }
 
@@ -440,68 +431,18 @@ int batch_end(ptc_ctx* ctx)
 // frames per batch ptc_trace may use right now (only the default traversal kernel reads DBatchInfo)
 int batch_limit(const ptc_ctx* ctx) { return ctx->staged && ctx->trace_variant == 3 ? ctx->batch : 1; }
 
-
-// Occlusion queries on device arrays: rays_o4 = origin.xyz, bits(t_min flag << 31) as in the path state,
-// rays_d4 = direction.xyz, t_max; flags = one byte per ray, zeroed here and set to 1 by the kernels.  Every ray must be in the fast
-// domain (t_min 1e-4 or 1e-5, t_max >= 0) and the trace variant 3.  Spheres first (one group: any grouping of the object list
-// gives the same OR), then one any-hit launch per mesh object; a ray that is already flagged is skipped by every later launch.
-// Enqueues only.  The scratch is the caller's: ptc_occluded_rays allocates it per call, a bounce loop would lend its slot's.
-struct OccludeScratch {
-  uint32_t* slow_list;        // n entries
-  uint32_t* slow_stack;       // kStackDepth * kWave
-  uint2* spill;               // scene.spill_cap * scene.spill_stride
-  DeviceCounters* counters;   // one block; its slow_rays[0] and flags are the launches' results
-};
-// the flags and the scratch of one query of n rays, into the caller's pool (ptc_occluded_rays, ptc_direct_light)
-int alloc_occlude_scratch(ptc_ctx* ctx, std::vector<void*>& pool, uint32_t n, uint8_t** flags, OccludeScratch* scr)
-{
-  int rc = dev_alloc(ctx, pool, flags, n);
-  if (!rc) rc = dev_alloc(ctx, pool, &scr->slow_list, n);
-  if (!rc) rc = dev_alloc(ctx, pool, &scr->slow_stack, (size_t)kStackDepth * kWave);
-  if (!rc) rc = dev_alloc(ctx, pool, &scr->spill, (size_t)ctx->scene.spill_cap * ctx->scene.spill_stride);
-  if (!rc) rc = dev_alloc(ctx, pool, &scr->counters, 1);
-  return rc;
-}
-int occlude_on_device(ptc_ctx* ctx, hipStream_t stream, const float4* rays_o4, const float4* rays_d4, uint32_t n, uint8_t* flags,
-                      const OccludeScratch& scr, uint32_t* launches)
-{
-  HIP_TRY(ctx, hipMemsetAsync(flags, 0, n, stream));
-  HIP_TRY(ctx, hipMemsetAsync(scr.counters, 0, sizeof(DeviceCounters), stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&scr.counters->live[0], &n, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-  DScene scene = ctx->scene;
-  scene.spill = scr.spill;
-  scene.slow_stack = scr.slow_stack;
-  uint32_t sph_begin = 0xffffffffu, sph_end = 0u;
-  auto sphere_run = [&](uint32_t b, uint32_t e) {
-    if (b < e) {
-      sph_begin = std::min(sph_begin, b);
-      sph_end = std::max(sph_end, e);
-    }
-  };
-  for (const auto& l : ctx->launches) sphere_run(l.pre_begin, l.pre_end);
-  sphere_run(ctx->tail_begin, ctx->tail_end);
-  if (sph_begin < sph_end) {
-    launch_occlude_spheres(stream, scene, sph_begin, sph_end, rays_o4, rays_d4, n, flags);
-    ++*launches;
-  }
-  DBatchInfo bi{};
-  bi.stride = n;
-  bi.chunk_stride = n / kChunk + 1u;
-  bi.count = 1u;
-  // (ptc_intersect_rays' sizing: about four rays per lane, at most what is resident -- and what the overflow area is laid out for)
-  const uint32_t waves = std::min<uint32_t>(ctx->traverse_waves, std::max<uint32_t>(8u, ((n / (4u * kWave)) + 7u) & ~7u));
-  int work_slot = 0;
-  for (const auto& l : ctx->launches) {
-    scene.cur = ctx->mesh_views[ctx->object_mesh[l.mesh]];
-    launch_occlude(stream, scene, l.mesh, rays_o4, rays_d4, flags, work_slot++ % kWorkSlots, scr.counters, waves, scr.slow_list, bi);
-    ++*launches;
-  }
-  return check_last(ctx, "occlusion query");
-}
-
 }  // namespace
 
 namespace ptcd {
+// may k_spheres take sphere_fold for the run [begin, end)?  Every object a "simple" sphere (sphere_ball_of)
+uint32_t fold_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
+{
+  if (!ctx->sphere_fold || end <= begin || end > ctx->sphere_class.size()) return 0u;
+  for (uint32_t i = begin; i < end; ++i)
+    if (ctx->sphere_class[i] == 0u) return 0u;
+  return 1u;
+}
+
 // one whole batch on the next slot: raygen, the bounces (per-bounce launches or the persistent launch), the fold
 static int enqueue_batch(ptc_ctx* ctx, std::vector<ptc_ctx::Pending>& items)
 {
@@ -693,380 +634,6 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
   ++ctx->frames;
   ctx->result = ctx->fb.color4;  // path_tracer.cu:476
   if ((int)ctx->pending.size() >= batch_limit(ctx)) return flush_pending(ctx, true);
-  return PTC_OK;
-}
-
-int ptc_intersect_rays(ptc_ctx* ctx, const float* rays, uint32_t n, float* hit_t, float* hit_normal, uint32_t* hit_material,
-                       uint8_t* hit_side)
-{
-  if (!ctx || !rays || !hit_t || !hit_normal || !hit_material || !hit_side) return PTC_ERR_INVALID;
-  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
-  if (n == 0) return PTC_OK;
-  if (n > 0x7fffffffu) return fail(ctx, PTC_ERR_INVALID, "too many rays");
-  if (int rc = bind_device(ctx)) return rc;
-  if (int rc = flush_pending(ctx)) return rc;
-  // The default schedule (variant 3) is the production closest-hit stage itself: the object list walked by the
-  // traversal launches (k_traverse4 with its sphere runs and its exact redo), fed with the caller's rays instead of
-  // path state.
-  // Path rays know two t_min values (1e-4, and 1e-5 after a dielectric: a flag bit) and start every bounce with
-  // t_max = FLT_MAX; a caller's t_max enters as the "closest hit so far" the segments carry in the hit record.
-  // Rays with another t_min take the one-wavefront-per-64-rays kernel with exact box decisions (variant 1).
-  bool path_like = ctx->trace_variant == 3;
-  for (uint32_t i = 0; i < n && path_like; ++i) {
-    const float tmin = rays[8u * (size_t)i + 3u], tmax = rays[8u * (size_t)i + 7u];
-    path_like = (tmin == 1e-4f || tmin == 1e-5f) && tmax >= 0.0f;
-  }
-  constexpr uint32_t kUntouched = 0x7fffffffu;  // material field of a record no segment has written: a miss
-  std::vector<void*> pool;
-  float4 *ro = nullptr, *rd = nullptr;
-  DHits hits{};
-  uint32_t *chunk_counts = nullptr, *slow_list = nullptr, *slow_stack = nullptr;
-  uint2* spill = nullptr;
-  DeviceCounters* counters = nullptr;
-  int rc = dev_alloc(ctx, pool, &ro, n);
-  if (!rc) rc = dev_alloc(ctx, pool, &rd, n);
-  if (!rc) rc = dev_alloc(ctx, pool, &hits.tp, n);
-  if (!rc) rc = dev_alloc(ctx, pool, &hits.nm, n);
-  if (!rc && path_like) {
-    rc = dev_alloc(ctx, pool, &chunk_counts, (size_t)n / kChunk + 1u);
-    if (!rc) rc = dev_alloc(ctx, pool, &slow_list, n);
-    if (!rc) rc = dev_alloc(ctx, pool, &slow_stack, (size_t)kStackDepth * kWave);
-    if (!rc) rc = dev_alloc(ctx, pool, &spill, (size_t)ctx->scene.spill_cap * ctx->scene.spill_stride);
-    if (!rc) rc = dev_alloc(ctx, pool, &counters, 1);
-  }
-  if (rc) {
-    free_pool(pool);
-    return rc;
-  }
-  std::vector<float4> ho(n), hd(n), tp(n), nm(n);
-  float untouched_bits;
-  std::memcpy(&untouched_bits, &kUntouched, 4);
-  for (uint32_t i = 0; i < n; ++i) {
-    const float* r = rays + 8u * (size_t)i;
-    if (path_like) {
-      const uint32_t flag = r[3] == 1e-5f ? 0x80000000u : 0u;
-      float fbits;
-      std::memcpy(&fbits, &flag, 4);
-      ho[i] = make_float4(r[0], r[1], r[2], fbits);
-      hd[i] = make_float4(r[4], r[5], r[6], 0.0f);
-      tp[i] = make_float4(r[7], 0.0f, 0.0f, 0.0f);
-      nm[i] = make_float4(0.0f, 0.0f, 0.0f, untouched_bits);
-    } else {
-      ho[i] = make_float4(r[0], r[1], r[2], r[3]);
-      hd[i] = make_float4(r[4], r[5], r[6], r[7]);
-    }
-  }
-  hipError_t e = hipMemcpyAsync(ro, ho.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(rd, hd.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && path_like) {
-    e = hipMemcpyAsync(hits.tp, tp.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hits.nm, nm.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(counters, 0, sizeof(DeviceCounters), ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&counters->live[0], &n, sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-      DScene scene = ctx->scene;
-      scene.spill = spill;
-      scene.slow_stack = slow_stack;
-      DPaths paths{ro, rd, nullptr};
-      DBatchInfo bi{};
-      bi.stride = n;
-      bi.chunk_stride = n / kChunk + 1u;
-      bi.count = 1u;
-      const uint32_t waves = std::min<uint32_t>(ctx->traverse_waves, std::max<uint32_t>(8u, ((n / (4u * kWave)) + 7u) & ~7u));
-      int work_slot = 0;
-      for (size_t k = 0; k < ctx->launches.size(); ++k) {
-        const auto& l = ctx->launches[k];
-        if (l.pre_begin < l.pre_end) {
-          scene.fold_run = fold_run_of(ctx, l.pre_begin, l.pre_end);
-          launch_spheres(ctx->stream, scene, l.pre_begin, l.pre_end, false, paths, hits, n, 0, counters, bi);
-        }
-        scene.cur = ctx->mesh_views[ctx->object_mesh[l.mesh]];
-        launch_traverse(ctx->stream, scene, l.mesh, false, paths, hits, 0, work_slot++ % kWorkSlots, counters, false, waves, slow_list,
-                        nullptr, ctx->trace_variant, bi);
-      }
-      launch_tail_count(ctx->stream, scene, ctx->tail_begin, ctx->tail_end, false, paths, hits, n, 0, chunk_counts, counters, bi);
-      e = hipGetLastError();
-    }
-  } else if (e == hipSuccess) {
-    launch_intersect(ctx->stream, ctx->scene, ro, rd, n, hits, ctx->misc_counters, ctx->trace_variant == 0 ? 0 : 1);
-    e = hipGetLastError();
-  }
-  uint32_t dev_flags = 0u;
-  unsigned long long redone = 0ull;
-  if (e == hipSuccess && path_like)
-    e = hipMemcpyAsync(&redone, &counters->slow_rays[0], sizeof redone, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(tp.data(), hits.tp, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(nm.data(), hits.nm, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && path_like)
-    e = hipMemcpyAsync(&dev_flags, &counters->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  free_pool(pool);
-  if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("intersect_rays: ") + hipGetErrorString(e));
-  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, "traversal stack overflow in ptc_intersect_rays");
-  ctx->intersect_redone += redone;
-  for (uint32_t i = 0; i < n; ++i) {
-    uint32_t ms;
-    std::memcpy(&ms, &nm[i].w, 4);
-    const bool miss = path_like ? (ms & 0x7fffffffu) == kUntouched : tp[i].x < 0.0f;
-    hit_t[i] = miss ? -1.0f : tp[i].x;
-    hit_normal[3u * i] = nm[i].x;
-    hit_normal[3u * i + 1u] = nm[i].y;
-    hit_normal[3u * i + 2u] = nm[i].z;
-    hit_material[i] = miss ? 0u : (ms & 0x7fffffffu);
-    hit_side[i] = miss ? (uint8_t)0 : (uint8_t)(ms >> 31);
-  }
-  return PTC_OK;
-}
-
-int ptc_occluded_rays(ptc_ctx* ctx, const float* rays, uint32_t n, uint8_t* occluded)
-{
-  if (!ctx || !rays || !occluded) return PTC_ERR_INVALID;
-  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
-  if (n == 0) return PTC_OK;
-  if (n > 0x7fffffffu) return fail(ctx, PTC_ERR_INVALID, "too many rays");
-  if (int rc = bind_device(ctx)) return rc;
-  if (int rc = flush_pending(ctx)) return rc;
-  // the fast domain: every shadow ray a renderer makes (path t_min values, a distance as t_max).  Anything else -- and the
-  // cross-check variants 0 / 1 -- takes the exact closest-hit kernel of ptc_intersect_rays, reduced to a flag on the host.
-  // (A NaN t_max: the reference's triangle test rejects on t > t_max, which a NaN never is -- it accepts; the culled walk of
-  // variant 1 compares the other way round, so such a call takes the reference-order kernel, variant 0.)
-  bool fast = ctx->trace_variant == 3, nan_tmax = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const float tmin = rays[8u * (size_t)i + 3u], tmax = rays[8u * (size_t)i + 7u];
-    fast = fast && (tmin == 1e-4f || tmin == 1e-5f) && tmax >= 0.0f;
-    nan_tmax = nan_tmax || tmax != tmax;
-  }
-  std::vector<void*> pool;
-  float4 *ro = nullptr, *rd = nullptr;
-  uint8_t* flags = nullptr;
-  DHits hits{};
-  OccludeScratch scr{};
-  int rc = dev_alloc(ctx, pool, &ro, n);
-  if (!rc) rc = dev_alloc(ctx, pool, &rd, n);
-  if (!rc && fast) {
-    rc = alloc_occlude_scratch(ctx, pool, n, &flags, &scr);
-  } else if (!rc) {
-    rc = dev_alloc(ctx, pool, &hits.tp, n);
-    if (!rc) rc = dev_alloc(ctx, pool, &hits.nm, n);
-  }
-  if (rc) {
-    free_pool(pool);
-    return rc;
-  }
-  std::vector<float4> ho(n), hd(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    const float* r = rays + 8u * (size_t)i;
-    float w = r[3];
-    if (fast) {
-      const uint32_t flag = r[3] == 1e-5f ? 0x80000000u : 0u;
-      std::memcpy(&w, &flag, 4);
-    }
-    ho[i] = make_float4(r[0], r[1], r[2], w);
-    hd[i] = make_float4(r[4], r[5], r[6], r[7]);
-  }
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  const bool timed = ctx->time_trace;
-  uint32_t launches = 0u, dev_flags = 0u;
-  unsigned long long redone = 0ull;
-  std::vector<float4> tp;
-  auto run = [&]() -> int {
-    HIP_TRY(ctx, hipMemcpyAsync(ro, ho.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(rd, hd.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    if (timed) {
-      HIP_TRY(ctx, hipEventCreate(&ev[0]));
-      HIP_TRY(ctx, hipEventCreate(&ev[1]));
-      HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
-    }
-    if (fast) {
-      if (int r2 = occlude_on_device(ctx, ctx->stream, ro, rd, n, flags, scr, &launches)) return r2;
-    } else {
-      launch_intersect(ctx->stream, ctx->scene, ro, rd, n, hits, ctx->misc_counters, ctx->trace_variant == 0 || nan_tmax ? 0 : 1);
-      ++launches;
-      if (int r2 = check_last(ctx, "occlusion query")) return r2;
-    }
-    if (timed) HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
-    if (fast) {
-      HIP_TRY(ctx, hipMemcpyAsync(occluded, flags, n, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(&redone, &scr.counters->slow_rays[0], sizeof redone, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(&dev_flags, &scr.counters->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-      tp.resize(n);
-      HIP_TRY(ctx, hipMemcpyAsync(tp.data(), hits.tp, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed) {
-      float ms = 0.0f;
-      HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-      ctx->occlusion.kernel_ms += (double)ms;
-    }
-    return PTC_OK;
-  };
-  rc = run();
-  if (rc != PTC_OK) (void)hipStreamSynchronize(ctx->stream);  // nothing may still use the pool
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  free_pool(pool);
-  if (rc != PTC_OK) return rc;
-  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, "traversal stack overflow in ptc_occluded_rays");
-  uint64_t count = 0u;
-  if (!fast)
-    for (uint32_t i = 0; i < n; ++i) occluded[i] = tp[i].x >= 0.0f ? (uint8_t)1 : (uint8_t)0;
-  for (uint32_t i = 0; i < n; ++i) count += occluded[i];
-  ctx->occlusion.rays += n;
-  ctx->occlusion.occluded += count;
-  ctx->occlusion.redone += redone;
-  ctx->occlusion.launches += launches;
-  return PTC_OK;
-}
-
-int ptc_get_occlusion_stats(ptc_ctx* ctx, ptc_occlusion_stats* out)
-{
-  if (!ctx || !out) return PTC_ERR_INVALID;
-  *out = ctx->occlusion;
-  return PTC_OK;
-}
-
-// Direct-light queries: k_light_sample writes the shadow rays where occlude_on_device takes them -- its first
-// caller with rays that were never on the host -- and k_light_resolve combines its flags with the unshadowed contributions.
-int ptc_direct_light(ptc_ctx* ctx, const float* points, const float* normals, uint32_t n, uint32_t sample_index, float* radiance,
-                     float* shadow_rays, uint8_t* visible, int on_device)
-{
-  if (!ctx) return PTC_ERR_INVALID;
-  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
-  if (!ctx->light_error.empty()) return fail(ctx, PTC_ERR_INVALID, ctx->light_error);
-  if (n == 0) return PTC_OK;
-  if (!points || !normals || !radiance) return fail(ctx, PTC_ERR_INVALID, "points, normals or radiance is NULL");
-  if (n > 0x7fffffffu) return fail(ctx, PTC_ERR_INVALID, "too many points");
-  if (on_device && shadow_rays && ((uintptr_t)shadow_rays & 15u)) return fail(ctx, PTC_ERR_INVALID, "shadow_rays on the device must be 16-byte aligned");
-  if (int rc = bind_device(ctx)) return rc;
-  if (int rc = flush_pending(ctx)) return rc;
-  const size_t n3 = 3u * (size_t)n;
-  if (!ctx->light_records) {
-    // no lamp, or lamps of total weight 0: zeros, the empty ray from every point, and no launch
-    std::vector<float> rays;
-    if (shadow_rays) {
-      std::vector<float> pts;
-      const float* src = points;
-      if (on_device) {
-        pts.resize(n3);
-        HIP_TRY(ctx, hipMemcpy(pts.data(), points, n3 * sizeof(float), hipMemcpyDeviceToHost));
-        src = pts.data();
-      }
-      rays.assign(8u * (size_t)n, 0.0f);
-      for (uint32_t i = 0; i < n; ++i) {
-        std::memcpy(&rays[8u * (size_t)i], src + 3u * (size_t)i, 3u * sizeof(float));
-        rays[8u * (size_t)i + 3u] = 1e-4f;
-      }
-    }
-    if (on_device) {
-      HIP_TRY(ctx, hipMemsetAsync(radiance, 0, n3 * sizeof(float), ctx->stream));
-      if (visible) HIP_TRY(ctx, hipMemsetAsync(visible, 0, n, ctx->stream));
-      if (shadow_rays) HIP_TRY(ctx, hipMemcpyAsync(shadow_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    } else {
-      std::memset(radiance, 0, n3 * sizeof(float));
-      if (visible) std::memset(visible, 0, n);
-      if (shadow_rays) std::memcpy(shadow_rays, rays.data(), rays.size() * sizeof(float));
-    }
-    ctx->direct.points += n;
-    return PTC_OK;
-  }
-  // trace variants 0 / 1 stay cross-checks: the generated rays go through the exact closest-hit kernel, as in ptc_occluded_rays
-  // (there t_min travels as a float; a generated t_max is never NaN: d * 0.999f of a finite d, or 0)
-  const bool fast = ctx->trace_variant == 3;
-  std::vector<void*> pool;
-  float *d_pts = nullptr, *d_nrm = nullptr, *d_rad = radiance, *d_rays = shadow_rays;
-  uint8_t *d_vis = visible, *flags = nullptr;
-  float4 *o4 = nullptr, *d4 = nullptr, *contrib = nullptr;
-  uint32_t* stats = nullptr;
-  DHits hits{};
-  OccludeScratch scr{};
-  int rc = dev_alloc(ctx, pool, &o4, n);
-  if (!rc) rc = dev_alloc(ctx, pool, &d4, n);
-  if (!rc) rc = dev_alloc(ctx, pool, &contrib, n);
-  if (!rc) rc = dev_alloc(ctx, pool, &stats, (size_t)kLightStatLines * 32u);
-  if (!rc && !on_device) {
-    rc = dev_alloc(ctx, pool, &d_pts, n3);
-    if (!rc) rc = dev_alloc(ctx, pool, &d_nrm, n3);
-    if (!rc) rc = dev_alloc(ctx, pool, &d_rad, n3);
-    if (!rc && shadow_rays) rc = dev_alloc(ctx, pool, &d_rays, 8u * (size_t)n);
-    if (!rc && visible) rc = dev_alloc(ctx, pool, &d_vis, n);
-  }
-  if (!rc && fast) rc = alloc_occlude_scratch(ctx, pool, n, &flags, &scr);
-  else if (!rc) {
-    rc = dev_alloc(ctx, pool, &hits.tp, n);
-    if (!rc) rc = dev_alloc(ctx, pool, &hits.nm, n);
-  }
-  if (rc) {
-    free_pool(pool);
-    return rc;
-  }
-  DLights lights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres, ctx->scene.materials};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  const bool timed = ctx->time_trace;
-  uint32_t launches = 0u, dev_flags = 0u;
-  std::vector<uint32_t> host_stats((size_t)kLightStatLines * 32u, 0u);
-  auto run = [&]() -> int {
-    if (!on_device) {
-      HIP_TRY(ctx, hipMemcpyAsync(d_pts, points, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(d_nrm, normals, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, hipMemsetAsync(stats, 0, host_stats.size() * sizeof(uint32_t), ctx->stream));
-    if (timed) {
-      HIP_TRY(ctx, hipEventCreate(&ev[0]));
-      HIP_TRY(ctx, hipEventCreate(&ev[1]));
-      HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
-    }
-    const float tmin = 1e-4f;
-    uint32_t tmin_word = 0u;
-    if (!fast) std::memcpy(&tmin_word, &tmin, 4);
-    launch_light_sample(ctx->stream, lights, on_device ? points : d_pts, on_device ? normals : d_nrm, n, sample_index, tmin_word, o4, d4, contrib);
-    ++launches;
-    if (fast) {
-      if (int r2 = occlude_on_device(ctx, ctx->stream, o4, d4, n, flags, scr, &launches)) return r2;
-    } else {
-      launch_intersect(ctx->stream, ctx->scene, o4, d4, n, hits, ctx->misc_counters, ctx->trace_variant == 0 ? 0 : 1);
-      ++launches;
-    }
-    launch_light_resolve(ctx->stream, o4, d4, contrib, flags, hits.tp, n, d_rad, d_rays, d_vis, stats);
-    ++launches;
-    if (int r2 = check_last(ctx, "direct-light query")) return r2;
-    if (timed) HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
-    if (!on_device) {
-      HIP_TRY(ctx, hipMemcpyAsync(radiance, d_rad, n3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-      if (shadow_rays) HIP_TRY(ctx, hipMemcpyAsync(shadow_rays, d_rays, 8u * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-      if (visible) HIP_TRY(ctx, hipMemcpyAsync(visible, d_vis, n, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(host_stats.data(), stats, host_stats.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (fast) HIP_TRY(ctx, hipMemcpyAsync(&dev_flags, &scr.counters->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed) {
-      float ms = 0.0f;
-      HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-      ctx->direct.kernel_ms += (double)ms;
-    }
-    return PTC_OK;
-  };
-  rc = run();
-  if (rc != PTC_OK) (void)hipStreamSynchronize(ctx->stream);  // nothing may still use the pool
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  free_pool(pool);
-  if (rc != PTC_OK) return rc;
-  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, "traversal stack overflow in ptc_direct_light");
-  for (uint32_t l = 0; l < kLightStatLines; ++l) {
-    ctx->direct.sampled += host_stats[32u * l];
-    ctx->direct.unoccluded += host_stats[32u * l + 1u];
-  }
-  ctx->direct.points += n;
-  ctx->direct.launches += launches;
-  return PTC_OK;
-}
-
-int ptc_get_direct_stats(ptc_ctx* ctx, ptc_direct_stats* out)
-{
-  if (!ctx || !out) return PTC_ERR_INVALID;
-  *out = ctx->direct;
   return PTC_OK;
 }
 

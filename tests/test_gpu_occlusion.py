@@ -3,13 +3,17 @@ oracle: occluded[i] == the oracle's hit flag of ray_scene_intersection_test, on 
 out.  Scenes: a room with two mesh instances, the 1,000,000-triangle heightfield with adversarial rays, coincident
 instances with t_max at / one ulp below the hit, several meshes, lamps, spheres at the edges of the sphere arithmetic;
 every schedule parameter the any-hit walk honours; the rays outside its fast domain; sizes; no side effects on a
-running accumulation; agreement with the library's own closest hit on 1,000,000 rays."""
+running accumulation; agreement with the library's own closest hit on 1,000,000 rays.  And what the three query calls share
+on the host (ptc_intersect_rays, ptc_occluded_rays, ptc_direct_light): the closest-hit call's sizes on both of its paths, the
+order of the refusals, a working context after a refused call."""
+import ctypes as C
 import importlib.util
 import os
 
 import numpy as np
 import pytest
 
+import direct_ref as D
 import occlusion_rays as R
 from test_gpu_schedules import _adversarial_rays
 
@@ -353,3 +357,99 @@ def test_agrees_with_the_closest_hit_on_a_million_rays(pkg):
     assert np.array_equal(occ, want), np.nonzero(occ != want)[0][:10]
     assert 0.02 < want[:500000].mean() < 0.98 and 0.02 < want[500000:].mean() < 0.98
     assert st["kernel_ms"] > 0.0 and st["launches"] == 2
+
+
+def _same_hits(got, recs, hit):
+    """The per-ray comparison of tests/test_gpu_parity.py: hit / miss, then t, normal, material and side of every hit, bit for bit."""
+    t, nrm, mat, side = got
+    m = hit.astype(bool)
+    assert t.shape == m.shape and nrm.shape == (len(m), 3) and mat.shape == m.shape and side.shape == m.shape
+    assert np.array_equal(t >= 0, m)
+    assert t[m].tobytes() == recs["t"][m].tobytes() and nrm[m].tobytes() == recs["normal"][m].tobytes()
+    assert np.array_equal(mat[m], recs["material_id"][m].astype(np.uint32)) and np.array_equal(side[m], recs["side"][m])
+    assert np.all(t[~m] == -1.0) and not mat[~m].any() and not side[~m].any()
+
+
+@pytest.mark.parametrize("kind", ["path_like", "exact", "force_slow"])
+def test_closest_hit_sizes(pkg, orc, kind):
+    """12: ptc_intersect_rays with n = 0, 1, 63, 64, 65 and 257 on the small room (spheres in front of a mesh launch, two instances,
+    a sphere run that ends the list) against the oracle's records.  path_like: the rays as generated, through the traversal
+    launches; exact: the call's last ray with t_min 0.25, which sends the whole call to the exact kernel; force_slow: the first
+    set with every ray handed to the exact redo, which profile()'s slow_rays count."""
+    flat = R.occlusion_scene(pkg, n_lat=24, n_lon=48).build_scene()
+    rays = R.shadow_rays(n=257, seed=12)
+    sh = orc.SceneHandle(flat)
+    with pkg.PathTracer() as pt:
+        if kind == "force_slow":
+            pt.set_param("debug_force_slow", 1)
+        pt.create_buffers((32, 32), flat)
+        slow_before = sum(pt.profile()["slow_rays"])
+        for n in (0, 1, 63, 64, 65, 257):
+            q = rays[:n].copy()
+            if kind == "exact" and n:
+                q[-1, 3] = 0.25
+            recs, hit = orc.intersect_rays(flat, q, scene_handle=sh)
+            got = pt.intersect_rays(q)
+            assert [len(a) for a in got] == [n] * 4
+            _same_hits(got, recs, hit)
+            if n == 257:
+                assert 0.2 < hit.mean() < 1.0
+        slow = sum(pt.profile()["slow_rays"]) - slow_before
+        print(kind, "rays redone exactly:", slow)
+        if kind != "path_like":
+            assert slow > 0 if kind == "force_slow" else slow == 0    # (the exact kernel sets no ray aside)
+
+
+@pytest.fixture(scope="module")
+def lit(pkg, orc):
+    """One lit scene for the three calls: 64 rays with the oracle's records, 64 points with the restatement's answer."""
+    flat = pkg.scenes.cornell_lit((64, 64), with_mesh=True).build_scene()
+    rays, _ = R.lamp_rays(n=64, seed=23)
+    pts, nrm = D.room_points(64, seed=17, lamp_points=D.cornell_lamp_points())
+    return flat, rays, orc.intersect_rays(flat, rays), pts, nrm, D.query(orc, flat, pts, nrm, 3)
+
+
+@pytest.mark.parametrize("which", ["intersect", "occluded", "direct_light"])
+def test_refusals_and_the_context_after_them(pkg, lit, which):
+    """13: the order of the checks the three calls open with -- no scene (PTC_ERR_NO_SCENE, "no scene uploaded"), a NULL context,
+    a NULL output with n = 1 (PTC_ERR_INVALID; ptc_direct_light names the arrays), ptc_direct_light's n = 0 with nothing else
+    -- and straight after every refusal a valid query with the oracle's answer."""
+    flat, rays, (recs, hit), pts, nrm, (want_rad, want_rays, want_vis, _) = lit
+    L, K = pkg.lib(), pkg._capi
+    fp, n = C.POINTER(C.c_float), 1
+    t, nr = np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+    mat, side, occ, rad = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros((n, 3), np.float32)
+
+    def call(ctx, null_output=False):
+        if which == "intersect":
+            return L.ptc_intersect_rays(ctx, rays.ctypes.data_as(fp), n, t.ctypes.data_as(fp), nr.ctypes.data_as(fp),
+                                        mat.ctypes.data_as(C.POINTER(C.c_uint32)), None if null_output else side.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if which == "occluded":
+            return L.ptc_occluded_rays(ctx, rays.ctypes.data_as(fp), n, None if null_output else occ.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return L.ptc_direct_light(ctx, pts.ctypes.data, nrm.ctypes.data, n, 3, None if null_output else rad.ctypes.data, None, None, 0)
+
+    def valid(pt):
+        if which == "intersect":
+            _same_hits(pt.intersect_rays(rays), recs, hit)
+        elif which == "occluded":
+            assert np.array_equal(pt.occluded_rays(rays), hit.astype(np.uint8))
+        else:
+            radiance, shadow, visible = pt.direct_light(pts, nrm, 3, want_rays=True)
+            assert shadow.tobytes() == want_rays.tobytes() and np.array_equal(visible, want_vis) and radiance.tobytes() == want_rad.tobytes()
+
+    assert 0 < hit.sum() < len(hit) and 0 < want_vis.sum() < len(want_vis)
+    with pkg.PathTracer() as pt:
+        assert call(pt._ctx) == K.PTC_ERR_NO_SCENE and L.ptc_last_error(pt._ctx) == b"no scene uploaded"
+        assert call(None) == K.PTC_ERR_INVALID
+        pt.create_buffers((32, 32), flat)
+        valid(pt)
+        assert call(None) == K.PTC_ERR_INVALID
+        valid(pt)
+        assert call(pt._ctx, null_output=True) == K.PTC_ERR_INVALID
+        if which == "direct_light":
+            assert L.ptc_last_error(pt._ctx) == b"points, normals or radiance is NULL"
+        valid(pt)
+        assert call(pt._ctx) == K.PTC_OK
+        if which == "direct_light":
+            assert L.ptc_direct_light(pt._ctx, None, None, 0, 0, None, None, None, 0) == K.PTC_OK
+            valid(pt)
