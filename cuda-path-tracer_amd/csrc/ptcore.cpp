@@ -45,6 +45,32 @@ int check_last(ptc_ctx* ctx, const char* what)
   return PTC_OK;
 }
 
+// HIP events around one launch of a timed kernel, on the stream it runs on.  The events come from free_events, where drain_timed
+// puts them back when it has read the pair that timed_end left in ctx->timed.
+int timed_begin(ptc_ctx* ctx, hipStream_t stream, int bounce, ptc_ctx::TimedLaunch* tl)
+{
+  *tl = ptc_ctx::TimedLaunch{nullptr, nullptr, bounce};
+  if (!ctx->time_trace) return PTC_OK;
+  for (hipEvent_t* e : {&tl->start, &tl->stop}) {
+    if (!ctx->free_events.empty()) {
+      *e = ctx->free_events.back();
+      ctx->free_events.pop_back();
+    } else {
+      HIP_TRY(ctx, hipEventCreate(e));
+    }
+  }
+  HIP_TRY(ctx, hipEventRecord(tl->start, stream));
+  return PTC_OK;
+}
+
+int timed_end(ptc_ctx* ctx, hipStream_t stream, const ptc_ctx::TimedLaunch& tl)
+{
+  if (!ctx->time_trace) return PTC_OK;
+  HIP_TRY(ctx, hipEventRecord(tl.stop, stream));
+  ctx->timed.push_back(tl);
+  return PTC_OK;
+}
+
 int bind_device(ptc_ctx* ctx)
 {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -111,6 +137,73 @@ int frame_ready(ptc_ctx* ctx)
 }
 
 }  // namespace ptcd
+
+namespace {
+
+// ptc_set_param (documented in include/ptcore.h): one row per parameter that stores a checked value -- the inclusive range and what
+// follows the name in the refusal of a value outside it, whether it must be set before ptc_resize (it sizes the frame slots) or
+// before ptc_upload_scene (it sizes the scene), and where the value goes.  The range is checked before the gate.
+enum ParamGate { kAnyTime, kBeforeResize, kBeforeUpload };
+struct ParamRow {
+  const char* name;
+  int lo, hi;
+  const char* complaint;
+  ParamGate gate;
+  void (*store)(ptc_ctx* c, int v);
+};
+#define PT_STR2(x) #x
+#define PT_STR(x) PT_STR2(x)
+constexpr const char* k01 = " must be 0 or 1";
+constexpr const char* kRange = " out of range";
+const ParamRow kParams[] = {
+    {"batch_frames", 1, kMaxBatch, " must be in [1,32]", kBeforeResize, [](ptc_ctx* c, int v) { c->batch_frames = v; }},
+    {"traverse_waves", 8, 65536, kRange, kBeforeUpload, [](ptc_ctx* c, int v) { c->traverse_waves = (uint32_t)v; }},
+    {"debug_lds_entries", 1, kLds4, " must be in [1," PT_STR(PT_T4_LDS) "]", kBeforeUpload,
+     [](ptc_ctx* c, int v) { c->lds_entries = (uint32_t)v; }},
+    {"layout_on_device", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->layout_on_device = v != 0; }},
+    {"filter_rays", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->filter_rays = v != 0; }},
+    {"fused_shade", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->fused_shade = v != 0; }},
+    {"merge_instances", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->merge_instances = v != 0; }},
+    {"bvh_build_on_device", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->bvh_on_device = v != 0; }},
+    {"static_eighths", 0, 8, " must be in [0,8]", kAnyTime,
+     [](ptc_ctx* c, int v) { c->scene.static_eighths = c->static_eighths = (uint32_t)v; }},
+    {"small_waves", 8, 65536, kRange, kAnyTime, [](ptc_ctx* c, int v) { c->small_waves = (uint32_t)v; }},
+    {"small_rays_per_lane", 0, 1024, kRange, kAnyTime, [](ptc_ctx* c, int v) { c->small_rays_per_lane = (uint32_t)v; }},
+    {"run_waves", 8, 65536, kRange, kAnyTime, [](ptc_ctx* c, int v) { c->run_waves = (uint32_t)v; }},
+    {"min_waves", 8, 65536, kRange, kAnyTime, [](ptc_ctx* c, int v) { c->min_waves = (uint32_t)v; }},
+    {"beam", 0, 1, k01, kBeforeResize, [](ptc_ctx* c, int v) { c->beam = v != 0; }},
+    {"persist", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->persist = v; }},
+    {"persist_service_every", 2, 64, " must be in [2, 64]", kAnyTime,
+     [](ptc_ctx* c, int v) { c->persist_service_every = (uint32_t)v; }},
+    {"prefold", 0, 1, k01, kBeforeResize, [](ptc_ctx* c, int v) { c->prefold = v != 0; }},
+    {"pair_batches", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->pair_batches = v; }},
+    {"persist_help_tiles", 0, 4096, " must be in [0, 4096]", kAnyTime, [](ptc_ctx* c, int v) { c->persist_help_tiles = (uint32_t)v; }},
+    {"persist_min_frames", 1, kMaxBatch, " must be in [1, 32]", kAnyTime, [](ptc_ctx* c, int v) { c->persist_min_frames = (uint32_t)v; }},
+    {"sphere_fold", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->sphere_fold = v != 0; }},
+    {"sphere_lanes", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->sphere_lanes = v != 0; }},
+    {"split_idle", 0, 64, " must be in [0,64]", kAnyTime, [](ptc_ctx* c, int v) { c->scene.split_idle = c->split_idle = (uint32_t)v; }},
+    {"refill_lanes", 1, 64, " must be in [1,64]", kAnyTime,
+     [](ptc_ctx* c, int v) { c->scene.refill_lanes = c->refill_lanes = (uint32_t)v; }},
+    {"ray_sort", 0, 1, k01, kBeforeResize, [](ptc_ctx* c, int v) { c->ray_sort = v; }},
+    {"denoise_variant", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_variant = v; }},
+    {"frames_in_flight", 1, 256, " must be in [1,256]", kBeforeResize, [](ptc_ctx* c, int v) { c->frames_in_flight = v; }},
+};
+#undef PT_STR
+#undef PT_STR2
+static_assert(kMaxBatch == 32, "the range messages of batch_frames and persist_min_frames spell the bound out");
+
+// "slot_offset", the one parameter that lives on the device
+int set_slot_offset(ptc_ctx* ctx, int value)
+{
+  if (value < 0) return fail(ctx, PTC_ERR_INVALID, "slot_offset must not be negative");
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;  // frames in flight read the offset when they execute
+  ctx->slot_offset = (uint32_t)value;
+  HIP_TRY(ctx, hipMemcpy(ctx->slot_offset_dev, &ctx->slot_offset, sizeof(uint32_t), hipMemcpyHostToDevice));
+  return PTC_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -417,168 +510,21 @@ int ptc_set_param(ptc_ctx* ctx, const char* name, int value)
 {
   if (!ctx || !name) return PTC_ERR_INVALID;
   if (int rc = flush_pending(ctx)) return rc;
-  if (std::strcmp(name, "batch_frames") == 0) {
-    if (value < 1 || value > kMaxBatch) return fail(ctx, PTC_ERR_INVALID, "batch_frames must be in [1,32]");
-    if (ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "set batch_frames before ptc_resize");
-    ctx->batch_frames = value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "traverse_waves") == 0) {
-    if (value < 8 || value > 65536) return fail(ctx, PTC_ERR_INVALID, "traverse_waves out of range");
-    if (ctx->has_scene) return fail(ctx, PTC_ERR_INVALID, "set traverse_waves before ptc_upload_scene");
-    ctx->traverse_waves = (uint32_t)value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "debug_lds_entries") == 0) {
-    if (value < 1 || value > kLds4) return fail(ctx, PTC_ERR_INVALID, "debug_lds_entries must be in [1," + std::to_string(kLds4) + "]");
-    if (ctx->has_scene) return fail(ctx, PTC_ERR_INVALID, "set debug_lds_entries before ptc_upload_scene");
-    ctx->lds_entries = (uint32_t)value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "debug_force_slow") == 0) {
-    ctx->scene.force_slow = (uint32_t)value;  // 1: every ray at fetch time, 2: every winner at verification time
+  // the parameters that do more than store a checked value
+  if (std::strcmp(name, "slot_offset") == 0) return set_slot_offset(ctx, value);
+  if (std::strcmp(name, "debug_force_slow") == 0) {  // any value; 1: every ray at fetch time, 2: every winner at verification time
+    ctx->scene.force_slow = (uint32_t)value;
     ctx->force_slow = value;
     return PTC_OK;
   }
-  if (std::strcmp(name, "layout_on_device") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "layout_on_device must be 0 or 1");
-    ctx->layout_on_device = value != 0;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "filter_rays") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "filter_rays must be 0 or 1");
-    ctx->filter_rays = value != 0;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "fused_shade") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "fused_shade must be 0 or 1");
-    ctx->fused_shade = value != 0;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "merge_instances") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "merge_instances must be 0 or 1");
-    ctx->merge_instances = value != 0;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "bvh_build_on_device") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "bvh_build_on_device must be 0 or 1");
-    ctx->bvh_on_device = value != 0;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "static_eighths") == 0) {
-    if (value < 0 || value > 8) return fail(ctx, PTC_ERR_INVALID, "static_eighths must be in [0,8]");
-    ctx->static_eighths = (uint32_t)value;
-    ctx->scene.static_eighths = ctx->static_eighths;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "small_waves") == 0) {
-    if (value < 8 || value > 65536) return fail(ctx, PTC_ERR_INVALID, "small_waves out of range");
-    ctx->small_waves = (uint32_t)value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "small_rays_per_lane") == 0) {
-    if (value < 0 || value > 1024) return fail(ctx, PTC_ERR_INVALID, "small_rays_per_lane out of range");
-    ctx->small_rays_per_lane = (uint32_t)value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "run_waves") == 0) {
-    if (value < 8 || value > 65536) return fail(ctx, PTC_ERR_INVALID, "run_waves out of range");
-    ctx->run_waves = (uint32_t)value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "min_waves") == 0) {
-    if (value < 8 || value > 65536) return fail(ctx, PTC_ERR_INVALID, "min_waves out of range");
-    ctx->min_waves = (uint32_t)value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "beam") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "beam must be 0 or 1");
-    if (ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "set beam before ptc_resize");
-    ctx->beam = value != 0;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "persist") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "persist must be 0 or 1");
-    if (int rc = flush_pending(ctx)) return rc;
-    ctx->persist = value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "persist_service_every") == 0) {
-    if (value < 2 || value > 64) return fail(ctx, PTC_ERR_INVALID, "persist_service_every must be in [2, 64]");
-    if (int rc = flush_pending(ctx)) return rc;
-    ctx->persist_service_every = (uint32_t)value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "prefold") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "prefold must be 0 or 1");
-    if (ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "set prefold before ptc_resize");
-    ctx->prefold = value != 0;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "pair_batches") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "pair_batches must be 0 or 1");
-    if (int rc = flush_pending(ctx)) return rc;
-    ctx->pair_batches = value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "persist_help_tiles") == 0) {
-    if (value < 0 || value > 4096) return fail(ctx, PTC_ERR_INVALID, "persist_help_tiles must be in [0, 4096]");
-    if (int rc = flush_pending(ctx)) return rc;
-    ctx->persist_help_tiles = (uint32_t)value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "persist_min_frames") == 0) {
-    if (value < 1 || value > kMaxBatch) return fail(ctx, PTC_ERR_INVALID, "persist_min_frames must be in [1, 32]");
-    if (int rc = flush_pending(ctx)) return rc;
-    ctx->persist_min_frames = (uint32_t)value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "sphere_fold") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "sphere_fold must be 0 or 1");
-    ctx->sphere_fold = value != 0;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "sphere_lanes") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "sphere_lanes must be 0 or 1");
-    ctx->sphere_lanes = value != 0;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "split_idle") == 0) {
-    if (value < 0 || value > 64) return fail(ctx, PTC_ERR_INVALID, "split_idle must be in [0,64]");
-    ctx->split_idle = (uint32_t)value;
-    ctx->scene.split_idle = ctx->split_idle;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "refill_lanes") == 0) {
-    if (value < 1 || value > 64) return fail(ctx, PTC_ERR_INVALID, "refill_lanes must be in [1,64]");
-    ctx->refill_lanes = (uint32_t)value;
-    ctx->scene.refill_lanes = ctx->refill_lanes;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "ray_sort") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "ray_sort must be 0 or 1");
-    if (ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "set ray_sort before ptc_resize");
-    ctx->ray_sort = value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "denoise_variant") == 0) {
-    if (value != 0 && value != 1) return fail(ctx, PTC_ERR_INVALID, "denoise_variant must be 0 or 1");
-    ctx->denoise_variant = value;
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "slot_offset") == 0) {
-    if (value < 0) return fail(ctx, PTC_ERR_INVALID, "slot_offset must not be negative");
-    if (int rc = bind_device(ctx)) return rc;
-    if (int rc = sync_frames(ctx)) return rc;  // frames in flight read the offset when they execute
-    ctx->slot_offset = (uint32_t)value;
-    HIP_TRY(ctx, hipMemcpy(ctx->slot_offset_dev, &ctx->slot_offset, sizeof(uint32_t), hipMemcpyHostToDevice));
-    return PTC_OK;
-  }
-  if (std::strcmp(name, "frames_in_flight") == 0) {
-    if (value < 1 || value > 256) return fail(ctx, PTC_ERR_INVALID, "frames_in_flight must be in [1,256]");
-    if (ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "set frames_in_flight before ptc_resize");
-    ctx->frames_in_flight = value;
-    ctx->frames_auto = false;
+  for (const ParamRow& row : kParams) {
+    if (std::strcmp(name, row.name) != 0) continue;
+    if (value < row.lo || value > row.hi) return fail(ctx, PTC_ERR_INVALID, std::string(row.name) + row.complaint);
+    if (row.gate == kBeforeResize && ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, std::string("set ") + row.name + " before ptc_resize");
+    if (row.gate == kBeforeUpload && ctx->has_scene) return fail(ctx, PTC_ERR_INVALID, std::string("set ") + row.name + " before ptc_upload_scene");
+    row.store(ctx, value);
+    // (a caller that has chosen the frames in flight gets them: ptc_resize no longer caps the count)
+    if (std::strcmp(name, "frames_in_flight") == 0) ctx->frames_auto = false;
     return PTC_OK;
   }
   return fail(ctx, PTC_ERR_INVALID, std::string("unknown parameter ") + name);
@@ -608,23 +554,10 @@ int ptc_denoise(ptc_ctx* ctx)
   float4* front = ctx->den_b;
   if (ctx->den.filter_size >= 1) launch_denoise_positions(ctx->stream, ctx->cam, ctx->pix_count, ctx->fb.nd4, ctx->den_pos);
   for (int step = 1; step <= ctx->den.filter_size; step *= 2) {
-    ptc_ctx::TimedLaunch tl{nullptr, nullptr, -1};
-    if (ctx->time_trace) {
-      for (hipEvent_t* e : {&tl.start, &tl.stop}) {
-        if (!ctx->free_events.empty()) {
-          *e = ctx->free_events.back();
-          ctx->free_events.pop_back();
-        } else {
-          HIP_TRY(ctx, hipEventCreate(e));
-        }
-      }
-      HIP_TRY(ctx, hipEventRecord(tl.start, ctx->stream));
-    }
+    ptc_ctx::TimedLaunch tl;
+    if (int rc = timed_begin(ctx, ctx->stream, -1, &tl)) return rc;
     launch_denoise_pass(ctx->stream, ctx->cam, ctx->pix_count, color, ctx->fb.nd4, ctx->den_pos, back, step, prm);
-    if (ctx->time_trace) {
-      HIP_TRY(ctx, hipEventRecord(tl.stop, ctx->stream));
-      ctx->timed.push_back(tl);
-    }
+    if (int rc = timed_end(ctx, ctx->stream, tl)) return rc;
     const float4* new_color = back;
     float4* new_back = front;
     float4* new_front = back;

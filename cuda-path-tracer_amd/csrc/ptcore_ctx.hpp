@@ -1,5 +1,5 @@
 // ptcore_ctx.hpp -- private to libptcore.so: the context behind include/ptcore.h and the helpers its translation units share
-// (ptcore.cpp: context, frame slots, parameters, views; ptcore_scene.cpp: scene upload; ptcore_trace.cpp: the launch plan of a
+// (ptcore.cpp: context, frame slots, the parameter table, timed launches, views; ptcore_scene.cpp: scene upload; ptcore_trace.cpp: the launch plan of a
 // batch of frames; ptcore_query.cpp: the ray queries outside the render loop; ptcore_bands.cpp: several GPUs; ptcore_checks.cpp:
 // host-side checks of the schedule helpers).
 #pragma once
@@ -262,6 +262,10 @@ int fail(ptc_ctx* ctx, int code, const std::string& msg);
   } while (0)
 
 int check_last(ptc_ctx* ctx, const char* what);
+// HIP events around one launch of a timed kernel, on the stream it runs on (ptcore.cpp; a closest-hit launch of `bounce`, an
+// A-Trous pass with bounce -1).  Nothing while ctx->time_trace is off.
+int timed_begin(ptc_ctx* ctx, hipStream_t stream, int bounce, ptc_ctx::TimedLaunch* tl);
+int timed_end(ptc_ctx* ctx, hipStream_t stream, const ptc_ctx::TimedLaunch& tl);
 int bind_device(ptc_ctx* ctx);
 void free_pool(std::vector<void*>& pool);
 DCamera make_camera(const ptc_camera& c, uint32_t w, uint32_t h);

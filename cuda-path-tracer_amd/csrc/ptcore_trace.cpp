@@ -45,7 +45,6 @@ uint32_t traverse_waves_for(ptc_ctx* ctx, uint32_t frames, int bounce, bool list
   return (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(std::min<uint32_t>(ctx->min_waves, ctx->traverse_waves), want));
 }
 
-// Enqueue raygen for `count` consecutive iterations on the next slot (round robin) and make it the active batch.
 // launches [k, k + run) of the plan are one traversal launch: consecutive objects that instantiate the same mesh, with
 // nothing between them (k_traverse4m; "merge_instances")
 size_t launch_run(const ptc_ctx* ctx, size_t k)
@@ -61,7 +60,7 @@ size_t launch_run(const ptc_ctx* ctx, size_t k)
 }
 
 // may the sphere run [begin, end) take the per-lane path (sphere_run_lanes)?
-static uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
+uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
 {
   if (!ctx->sphere_lanes || end <= begin || end - begin > 8u || end > ctx->sphere_class.size()) return 0u;
   const uint32_t k = ctx->sphere_class[begin];
@@ -71,6 +70,81 @@ static uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
   return 1u;
 }
 
+// ---- the decisions of the launch plan (ptc_ctx::TraceLaunch), each in one place -------------------------------------------
+
+// What opens the object list: a traversal launch with nothing in front of it, a sphere run in front of the first traversal
+// launch, or -- a scene without a mesh launch -- nothing (the tail run is all there is).  The first traversal launch walks the
+// objects [launches[0].mesh, launches[0].mesh + launch_run(ctx, 0)).
+enum class Opens { nothing, launch, spheres };
+Opens plan_opens(const ptc_ctx* ctx)
+{
+  if (ctx->launches.empty()) return Opens::nothing;
+  return ctx->launches[0].pre_begin < ctx->launches[0].pre_end ? Opens::spheres : Opens::launch;
+}
+
+// "prefold": may a kernel that has a bounce's new rays in registers walk that bounce's leading sphere run for them (k_raygen_next
+// for bounce 0, k_shade_fused for the bounce after its own) and leave k_list_flags to open the bounce?  The object list opens
+// with a sphere run that would list the rays of the launch behind it -- k_spheres' own conditions: the listing is on, no ray
+// sorting -- and the slot has the second set of hit records.  A caller adds what only it knows.
+bool may_prefold(const ptc_ctx* ctx, const ptc_ctx::FrameSlot& sl)
+{
+  return ctx->prefold && ctx->trace_variant == 3 && ctx->fused_shade && ctx->filter_rays && !ctx->ray_sort && sl.next_flags &&
+         plan_opens(ctx) == Opens::spheres;
+}
+
+// ... and what that kernel gets: the leading sphere run, the objects of the launch behind it, where the hit records and the
+// list bytes go
+DNextRun next_run(const ptc_ctx* ctx, DHits hits, uint8_t* flags)
+{
+  const auto& l0 = ctx->launches[0];
+  DNextRun next{};
+  next.begin = l0.pre_begin;
+  next.end = l0.pre_end;
+  next.filt_begin = l0.mesh;
+  next.filt_end = l0.mesh + (uint32_t)launch_run(ctx, 0);
+  next.fold_run = fold_run_of(ctx, l0.pre_begin, l0.pre_end);
+  next.hits = hits;
+  next.flags = flags;
+  return next;
+}
+
+// The sphere run that ends the object list, as the kernel that ends a bounce takes it (k_shade_fused, k_persist; k_tail_count
+// reads the range alone): the objects [begin, end) -- (0, 0) without such a run, and under the variants 0 / 1, whose trace
+// kernel walks the whole list -- and scene.lanes_run / scene.fold_run set for it.
+struct ObjectRange {
+  uint32_t begin, end;
+};
+ObjectRange tail_run(const ptc_ctx* ctx, DScene& scene)
+{
+  const bool tail = ctx->trace_variant == 3 && ctx->tail_begin < ctx->tail_end;
+  scene.lanes_run = tail ? lanes_run_of(ctx, ctx->tail_begin, ctx->tail_end) : 0u;
+  scene.fold_run = tail && !scene.lanes_run ? fold_run_of(ctx, ctx->tail_begin, ctx->tail_end) : 0u;
+  return tail ? ObjectRange{ctx->tail_begin, ctx->tail_end} : ObjectRange{0u, 0u};
+}
+
+// Enqueue the traversal launch over launch k of the plan, for the rays in sl.paths[sl.cur]: a run of `run` instances of one mesh
+// (k_traverse4m) or one object (k_traverse4; bounce 0's first launch gets the batch's entry points, if batch_begin has made
+// any), timed when launches are.  It sets scene.cur and scene.beam.  first: no launch of this bounce has written the hit
+// records yet.  pick: the list the lanes fetch their rays through -- sl.worklist (a listed launch), sl.order, or null.
+int enqueue_traversal(ptc_ctx* ctx, ptc_ctx::FrameSlot& sl, DScene& scene, size_t k, size_t run, int bounce, bool first, const uint32_t* pick)
+{
+  const auto& l = ctx->launches[k];
+  const bool listed = pick != nullptr && pick == sl.worklist;
+  ptc_ctx::TimedLaunch tl;
+  if (int rc = timed_begin(ctx, sl.stream, bounce, &tl)) return rc;
+  const uint32_t waves = traverse_waves_for(ctx, sl.bi.count, bounce, listed, run > 1);
+  scene.cur = ctx->mesh_views[ctx->object_mesh[l.mesh]];  // this object's mesh
+  scene.beam = (bounce == 0 && k == 0) ? sl.beam : DBeam{};
+  if (run > 1)
+    launch_traverse_run(sl.stream, scene, l.mesh, l.mesh + (uint32_t)run, first, sl.paths[sl.cur], sl.hits, bounce, sl.work_slot++ % kWorkSlots,
+                        sl.counters, ctx->count_tests, waves, sl.slow_list, pick, sl.bi, listed);
+  else
+    launch_traverse(sl.stream, scene, l.mesh, first, sl.paths[sl.cur], sl.hits, bounce, sl.work_slot++ % kWorkSlots, sl.counters,
+                    ctx->count_tests, waves, sl.slow_list, pick, ctx->trace_variant, sl.bi, listed);
+  return timed_end(ctx, sl.stream, tl);
+}
+
+// Enqueue raygen for `count` consecutive iterations on the next slot (round robin) and make it the active batch.
 int batch_begin(ptc_ctx* ctx, const ptc_ctx::Pending* items, int count)
 {
   const int single_slots = (int)ctx->slots.size() - ctx->big_slots;
@@ -102,46 +176,37 @@ int batch_begin(ptc_ctx* ctx, const ptc_ctx::Pending* items, int count)
     cams.c[k] = items[k].cam;
     sl.bi.iteration[k] = items[k].iteration;
   }
+  const Opens opens = plan_opens(ctx);
+  const uint32_t run0 = opens == Opens::nothing ? 0u : (uint32_t)launch_run(ctx, 0);  // the first traversal launch: this many objects
   // "filter_rays" at bounce 0: when the bounce opens with a traversal launch (no sphere run in front of the first mesh),
   // raygen lists the rays that may hit that launch's world boxes and writes the others' miss records itself
-  sl.first_listed = ctx->filter_rays && ctx->trace_variant == 3 && !ctx->launches.empty() &&
-                    ctx->launches[0].pre_begin == ctx->launches[0].pre_end;
+  sl.first_listed = ctx->filter_rays && ctx->trace_variant == 3 && opens == Opens::launch;
   const uint32_t first_mesh = sl.first_listed ? ctx->launches[0].mesh : 0u;
-  uint32_t filt_end = sl.first_listed ? first_mesh + (uint32_t)launch_run(ctx, 0) : 0u;
+  uint32_t filt_end = sl.first_listed ? first_mesh + run0 : 0u;
   // ... and when that launch is the scene's whole mesh part -- only the sphere run that ends the object list, if any,
   // follows it -- the filter also takes the world boxes of those spheres (the reference tests a sphere's box before the
   // sphere, path_tracer.cu:84): a ray it does not list then hits nothing at all, raygen ends its path, and bounce 0's
   // k_shade_fused walks the list.  (The few rays listed for a sphere's box alone leave the traversal launch at its root.)
   const bool tail = ctx->tail_begin < ctx->tail_end;
-  sl.primary_finished = sl.first_listed && ctx->fused_shade && launch_run(ctx, 0) == ctx->launches.size() &&
-                        (!tail || ctx->tail_begin == filt_end);
+  sl.primary_finished = sl.first_listed && ctx->fused_shade && run0 == ctx->launches.size() && (!tail || ctx->tail_begin == filt_end);
   if (sl.primary_finished && tail) filt_end = ctx->tail_end;
-  // "prefold": the object list opens with a sphere run in front of a mesh launch that lists its rays -- ray generation walks
-  // the run for the primary rays itself, and bounce 0 starts with k_list_flags (batch_bounce) instead of k_spheres
-  const bool raygen_folds = ctx->prefold && ctx->trace_variant == 3 && ctx->fused_shade && ctx->filter_rays && !ctx->ray_sort && sl.next_flags &&
-                            !ctx->launches.empty() && ctx->launches[0].pre_begin < ctx->launches[0].pre_end;
-  if (raygen_folds) {
-    const auto& l0 = ctx->launches[0];
-    DNextRun next{};
-    next.begin = l0.pre_begin;
-    next.end = l0.pre_end;
-    next.filt_begin = l0.mesh;
-    next.filt_end = l0.mesh + (uint32_t)launch_run(ctx, 0);
-    next.fold_run = fold_run_of(ctx, l0.pre_begin, l0.pre_end);
-    next.hits = sl.hits;
-    next.flags = sl.next_flags;
-    launch_raygen_next(sl.stream, ctx->scene, cams, sl.bi, ctx->band, ctx->pix_count, sl.paths[0], sl.counters, next);
+  if (may_prefold(ctx, sl)) {
+    // "prefold": ray generation walks the leading sphere run for the primary rays itself, and bounce 0 starts with k_list_flags
+    // (batch_bounce) instead of k_spheres
+    launch_raygen_next(sl.stream, ctx->scene, cams, sl.bi, ctx->band, ctx->pix_count, sl.paths[0], sl.counters,
+                       next_run(ctx, sl.hits, sl.next_flags));
     sl.prefolded = true;
-  } else
-  launch_raygen(sl.stream, cams, sl.bi, ctx->band, ctx->pix_count, sl.paths[0], sl.counters, ctx->scene.objects, first_mesh, filt_end,
-                sl.first_listed ? sl.worklist : nullptr, sl.hits, sl.tile_desc, sl.tile_stride, next_epoch(sl), sl.primary_finished,
-                sl.stage, ctx->staging());
+  } else {
+    launch_raygen(sl.stream, cams, sl.bi, ctx->band, ctx->pix_count, sl.paths[0], sl.counters, ctx->scene.objects, first_mesh, filt_end,
+                  sl.first_listed ? sl.worklist : nullptr, sl.hits, sl.tile_desc, sl.tile_stride, next_epoch(sl), sl.primary_finished,
+                  sl.stage, ctx->staging());
+  }
   if (int rc = check_last(ctx, "raygen")) return rc;
   // "beam": when bounce 0 opens with a launch over ONE mesh object (k_traverse4), its primary rays start at entry points
   // computed per tile and distinct camera of the batch
   sl.beam = DBeam{};
-  if (ctx->beam && sl.beam_entries && ctx->trace_variant == 3 && !ctx->launches.empty() && ctx->launches[0].pre_begin == ctx->launches[0].pre_end &&
-      launch_run(ctx, 0) == 1 && ctx->width >= 2u && ctx->height >= 2u) {
+  if (ctx->beam && sl.beam_entries && ctx->trace_variant == 3 && opens == Opens::launch && run0 == 1u && ctx->width >= 2u &&
+      ctx->height >= 2u) {
     uint8_t cam_of_beam[kMaxBatch];
     uint32_t nbeam = 0;
     for (int k = 0; k < count; ++k) {
@@ -174,6 +239,7 @@ int batch_begin(ptc_ctx* ctx, const ptc_ctx::Pending* items, int count)
   return PTC_OK;
 }
 
+// One bounce of the active batch: the optional sort, the closest hit launch by launch of the plan, the end of the bounce.
 int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
 {
   auto& sl = ctx->slots[(size_t)ctx->active_slot];
@@ -182,48 +248,32 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
   DScene scene = ctx->scene;
   scene.spill = sl.spill;
   scene.slow_stack = sl.slow_stack;
-  // HIP events around each launch of the dominant (closest-hit) kernel, on the stream it runs on
-  auto timed_begin = [&](ptc_ctx::TimedLaunch& tl) -> int {
-    if (!ctx->time_trace) return PTC_OK;
-    for (hipEvent_t* e : {&tl.start, &tl.stop}) {
-      if (!ctx->free_events.empty()) {
-        *e = ctx->free_events.back();
-        ctx->free_events.pop_back();
-      } else {
-        HIP_TRY(ctx, hipEventCreate(e));
-      }
-    }
-    HIP_TRY(ctx, hipEventRecord(tl.start, sl.stream));
-    return PTC_OK;
-  };
-  auto timed_end = [&](ptc_ctx::TimedLaunch& tl) -> int {
-    if (!ctx->time_trace) return PTC_OK;
-    HIP_TRY(ctx, hipEventRecord(tl.stop, sl.stream));
-    ctx->timed.push_back(tl);
-    return PTC_OK;
-  };
+  const bool persistent = ctx->trace_variant == 3;
   bool wrote = false;  // some launch of this bounce has written the hit records
   const bool prefolded = sl.prefolded;  // ... the previous bounce's shade kernel has, for the leading sphere run ("prefold")
   sl.prefolded = false;
+
   // ray sorting: the shade kernel of the previous bounce has tagged its surviving rays with their direction octant
-  const bool persistent = ctx->trace_variant == 3;
-  const bool sorted = ctx->ray_sort && ctx->trace_variant == 3 && bounce >= 1 && sl.order && !ctx->launches.empty();
+  const bool sorted = ctx->ray_sort && persistent && bounce >= 1 && sl.order && !ctx->launches.empty();
   if (sorted) launch_sort_octant(sl.stream, sl.octs, sl.order, ctx->pix_count, bounce, sl.counters, sl.bi);
+
   if (persistent) {
-    // closest hit = the object list walked by the launches of TraceLaunch
-    for (size_t k = 0; k < ctx->launches.size(); ++k) {
+    // closest hit = the object list walked by the launches of TraceLaunch: per launch of the plan the sphere run in front of it,
+    // if there is one (or, behind "prefold", the list that run would have made), then the traversal launch
+    for (size_t k = 0; k < ctx->launches.size();) {
       const auto& l = ctx->launches[k];
       const size_t run = launch_run(ctx, k);
       // a sphere run in front of the launch reads every ray anyway: it also lists the rays that may hit one of the launch's
       // objects at all ("filter_rays"), and the launch fetches through that list
-      const bool by_spheres = ctx->filter_rays && l.pre_begin < l.pre_end && !sorted && ctx->trace_variant == 3;
+      const bool spheres = l.pre_begin < l.pre_end;
+      const bool by_spheres = ctx->filter_rays && spheres && !sorted;
       const bool listed = by_spheres || (bounce == 0 && k == 0 && sl.first_listed);  // (bounce 0's first launch: listed by k_raygen)
-      if (l.pre_begin < l.pre_end && k == 0 && prefolded) {
+      if (spheres && k == 0 && prefolded) {
         // "prefold": the shade kernel of the bounce before has walked this run for every survivor and left the hit records
         // (in what is now sl.hits) and one byte per ray; all that is left of k_spheres is its work list
         launch_list_flags(sl.stream, sl.next_flags, ctx->pix_count, bounce, sl.counters, sl.bi, sl.worklist, sl.tile_desc, sl.tile_stride, next_epoch(sl));
         wrote = true;
-      } else if (l.pre_begin < l.pre_end) {
+      } else if (spheres) {
         scene.lanes_run = lanes_run_of(ctx, l.pre_begin, l.pre_end);
         scene.fold_run = fold_run_of(ctx, l.pre_begin, l.pre_end);
         launch_spheres(sl.stream, scene, l.pre_begin, l.pre_end, !wrote, in, sl.hits, ctx->pix_count, bounce, sl.counters, sl.bi,
@@ -233,69 +283,43 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
       }
       // ("pair_batches": this batch's traversal launches wait for the partner's previous one, and say when they are done)
       if (ctx->turn_mine >= 0 && ctx->turn_wait >= 0) HIP_TRY(ctx, hipStreamWaitEvent(sl.stream, ctx->turn_event[ctx->turn_wait], 0));
-      ptc_ctx::TimedLaunch tl{nullptr, nullptr, bounce};
-      if (int rc = timed_begin(tl)) return rc;
-      const uint32_t waves = traverse_waves_for(ctx, sl.bi.count, bounce, listed, run > 1);
-      scene.cur = ctx->mesh_views[ctx->object_mesh[l.mesh]];  // this object's mesh
-      const uint32_t* pick = listed ? sl.worklist : (sorted ? sl.order : nullptr);
-      if (run > 1) {
-        launch_traverse_run(sl.stream, scene, l.mesh, l.mesh + (uint32_t)run, !wrote, in, sl.hits, bounce, sl.work_slot++ % kWorkSlots, sl.counters,
-                            ctx->count_tests, waves, sl.slow_list, pick, sl.bi, listed);
-        k += run - 1;
-      } else {
-        const int kernel = ctx->trace_variant;
-        scene.beam = (bounce == 0 && k == 0) ? sl.beam : DBeam{};
-        launch_traverse(sl.stream, scene, l.mesh, !wrote, in, sl.hits, bounce, sl.work_slot++ % kWorkSlots, sl.counters, ctx->count_tests, waves,
-                        sl.slow_list, pick, kernel, sl.bi, listed);
-      }
+      if (int rc = enqueue_traversal(ctx, sl, scene, k, run, bounce, !wrote, listed ? sl.worklist : (sorted ? sl.order : nullptr))) return rc;
       wrote = true;
-      if (int rc = timed_end(tl)) return rc;
       if (ctx->turn_mine >= 0) {
         HIP_TRY(ctx, hipEventRecord(ctx->turn_event[ctx->turn_mine], sl.stream));
         ctx->turn_wait = ctx->turn_mine;
       }
+      k += run;
     }
   } else {
-    ptc_ctx::TimedLaunch tl{nullptr, nullptr, bounce};
-    if (int rc = timed_begin(tl)) return rc;
+    // the variants 0 / 1: one kernel walks the whole object list
+    ptc_ctx::TimedLaunch tl;
+    if (int rc = timed_begin(ctx, sl.stream, bounce, &tl)) return rc;
     launch_trace(sl.stream, scene, in, sl.hits, ctx->pix_count, bounce, sl.counters, ctx->count_tests, ctx->trace_variant);
     wrote = true;
-    if (int rc = timed_end(tl)) return rc;
+    if (int rc = timed_end(ctx, sl.stream, tl)) return rc;
   }
-  // the sphere run that ends the object list (variant 3 only) + the live counts; their scan
-  const bool tail = persistent && ctx->tail_begin < ctx->tail_end;
+
+  // the end of the bounce: the sphere run that ends the object list + the live counts and their scan + the materials
+  const ObjectRange tail = tail_run(ctx, scene);
   uint8_t* octs = ctx->ray_sort && !last ? sl.octs : nullptr;
   if (ctx->fused_shade) {
     // one pass: trailing spheres + material + stable compaction (decoupled look-back) + final gather
     next_epoch(sl);
-    scene.lanes_run = tail ? lanes_run_of(ctx, ctx->tail_begin, ctx->tail_end) : 0u;
-    scene.fold_run = tail && !scene.lanes_run ? fold_run_of(ctx, ctx->tail_begin, ctx->tail_end) : 0u;
     // "prefold": the next bounce opens with a sphere run in front of its first traversal launch, which lists its rays -- this
-    // kernel walks that run for every survivor (DNextRun).  By k_spheres' own conditions: the listing is on, no ray sorting.
-    DNextRun next{};
-    const bool prefold = ctx->prefold && persistent && !last && wrote && ctx->filter_rays && !ctx->ray_sort && sl.next_flags && !ctx->launches.empty() &&
-                         ctx->launches[0].pre_begin < ctx->launches[0].pre_end;
-    if (prefold) {
-      const auto& l0 = ctx->launches[0];
-      next.begin = l0.pre_begin;
-      next.end = l0.pre_end;
-      next.filt_begin = l0.mesh;
-      next.filt_end = l0.mesh + (uint32_t)launch_run(ctx, 0);
-      next.fold_run = fold_run_of(ctx, l0.pre_begin, l0.pre_end);
-      next.hits = sl.hits_other;
-      next.flags = sl.next_flags;
-    }
-    launch_shade_fused(sl.stream, scene, tail ? ctx->tail_begin : 0u, tail ? ctx->tail_end : 0u, !wrote, in, out, sl.hits, ctx->pix_count,
-                       ctx->staging(), bounce, last, slot_base_dev, sl.tile_desc, sl.tile_stride, sl.shade_epoch, sl.stage, ctx->band,
-                       sl.counters, octs, sl.bi, bounce == 0 && sl.primary_finished ? sl.worklist : nullptr, prefold ? &next : nullptr,
-                       ctx->has_emitters);
+    // kernel walks that run for every survivor (DNextRun)
+    const bool prefold = may_prefold(ctx, sl) && !last && wrote;
+    const DNextRun next = prefold ? next_run(ctx, sl.hits_other, sl.next_flags) : DNextRun{};
+    launch_shade_fused(sl.stream, scene, tail.begin, tail.end, !wrote, in, out, sl.hits, ctx->pix_count, ctx->staging(), bounce, last,
+                       slot_base_dev, sl.tile_desc, sl.tile_stride, sl.shade_epoch, sl.stage, ctx->band, sl.counters, octs, sl.bi,
+                       bounce == 0 && sl.primary_finished ? sl.worklist : nullptr, prefold ? &next : nullptr, ctx->has_emitters);
     if (prefold) {
       std::swap(sl.hits, sl.hits_other);
       sl.prefolded = true;
     }
   } else {
-    launch_tail_count(sl.stream, scene, tail ? ctx->tail_begin : 0u, tail ? ctx->tail_end : 0u, !wrote, in, sl.hits, ctx->pix_count,
-                      bounce, sl.chunk_counts, sl.counters, sl.bi, ctx->has_emitters);
+    launch_tail_count(sl.stream, scene, tail.begin, tail.end, !wrote, in, sl.hits, ctx->pix_count, bounce, sl.chunk_counts, sl.counters,
+                      sl.bi, ctx->has_emitters);
     launch_scan(sl.stream, bounce, last, sl.chunk_counts, sl.chunk_offsets, sl.counters, sl.bi);
     launch_shade(sl.stream, scene, in, out, sl.hits, ctx->pix_count, ctx->staging(), bounce, last, slot_base_dev,
                  sl.chunk_offsets, sl.stage, ctx->band, sl.counters, octs, sl.bi, ctx->has_emitters);
@@ -314,7 +338,7 @@ bool persist_ok(const ptc_ctx* ctx, int count)
 {
   if (!ctx->persist || ctx->trace_variant != 3 || !ctx->fused_shade || ctx->ray_sort || !ctx->staging()) return false;
   if (ctx->count_tests || ctx->max_bounces < 2 || count < (int)ctx->persist_min_frames) return false;
-  if (ctx->launches.size() != 1u || ctx->launches[0].pre_begin != ctx->launches[0].pre_end || launch_run(ctx, 0) != 1u) return false;
+  if (ctx->launches.size() != 1u || plan_opens(ctx) != Opens::launch || launch_run(ctx, 0) != 1u) return false;
   const auto& sl = ctx->slots[(size_t)ctx->active_slot];
   if (!sl.persist || (uint64_t)sl.bi.stride * (uint64_t)count >= (1ull << kPersistSlotBits)) return false;
   return true;
@@ -329,34 +353,13 @@ int batch_persist(ptc_ctx* ctx, const uint32_t* slot_base_dev)
   DScene scene = ctx->scene;
   scene.spill = sl.spill;
   scene.slow_stack = sl.slow_stack;
+  // bounce 0's closest hit: launch 0 of the plan, one object, the first launch of its bounce, listed if ray generation has listed
+  // its rays (persist_ok: the default kernel, no counting run; never one of a pair of batches)
+  if (int rc = enqueue_traversal(ctx, sl, scene, /*k*/ 0, /*run*/ 1, /*bounce*/ 0, /*first*/ true, sl.first_listed ? sl.worklist : nullptr)) return rc;
+  // everything else (scene.cur stays this object's mesh)
   const auto& l = ctx->launches[0];
-  scene.cur = ctx->mesh_views[ctx->object_mesh[l.mesh]];
-  // ---- bounce 0's closest hit: batch_bounce's traversal part ----
-  ptc_ctx::TimedLaunch tl{nullptr, nullptr, 0};
-  if (ctx->time_trace) {
-    for (hipEvent_t* e : {&tl.start, &tl.stop}) {
-      if (!ctx->free_events.empty()) {
-        *e = ctx->free_events.back();
-        ctx->free_events.pop_back();
-      } else {
-        HIP_TRY(ctx, hipEventCreate(e));
-      }
-    }
-    HIP_TRY(ctx, hipEventRecord(tl.start, sl.stream));
-  }
-  const bool listed = sl.first_listed;
-  scene.beam = sl.beam;
-  launch_traverse(sl.stream, scene, l.mesh, true, sl.paths[0], sl.hits, 0, sl.work_slot++ % kWorkSlots, sl.counters, false,
-                  traverse_waves_for(ctx, sl.bi.count, 0, listed), sl.slow_list, listed ? sl.worklist : nullptr, 3, sl.bi, listed);
-  if (ctx->time_trace) {
-    HIP_TRY(ctx, hipEventRecord(tl.stop, sl.stream));
-    ctx->timed.push_back(tl);
-  }
-  // ---- everything else ----
   scene.beam = DBeam{};
-  const bool tail = ctx->tail_begin < ctx->tail_end;
-  scene.lanes_run = tail ? lanes_run_of(ctx, ctx->tail_begin, ctx->tail_end) : 0u;
-  scene.fold_run = tail && !scene.lanes_run ? fold_run_of(ctx, ctx->tail_begin, ctx->tail_end) : 0u;
+  const ObjectRange tail = tail_run(ctx, scene);
   DPersistArgs pa{};
   pa.st = sl.persist;
   pa.paths[0] = sl.paths[0];
@@ -364,8 +367,8 @@ int batch_persist(ptc_ctx* ctx, const uint32_t* slot_base_dev)
   pa.max_bounces = MB;
   pa.service_every = ctx->persist_service_every;
   pa.help_tiles = ctx->persist_help_tiles;
-  pa.tail_begin = tail ? ctx->tail_begin : 0u;
-  pa.tail_end = tail ? ctx->tail_end : 0u;
+  pa.tail_begin = tail.begin;
+  pa.tail_end = tail.end;
   pa.staged = ctx->staging() ? 1 : 0;
   pa.slot_base = slot_base_dev;
   pa.tile_desc = sl.tile_desc;
@@ -381,24 +384,11 @@ int batch_persist(ptc_ctx* ctx, const uint32_t* slot_base_dev)
   pa.band = ctx->band;
   pa.list0 = sl.primary_finished ? sl.worklist : nullptr;
   pa.slow_list = sl.slow_list;
-  ptc_ctx::TimedLaunch tp{nullptr, nullptr, 1};
-  if (ctx->time_trace) {
-    for (hipEvent_t* e : {&tp.start, &tp.stop}) {
-      if (!ctx->free_events.empty()) {
-        *e = ctx->free_events.back();
-        ctx->free_events.pop_back();
-      } else {
-        HIP_TRY(ctx, hipEventCreate(e));
-      }
-    }
-    HIP_TRY(ctx, hipEventRecord(tp.start, sl.stream));
-  }
-  launch_persist(sl.stream, scene, l.mesh, sl.hits, sl.counters, sl.bi, pa, ctx->traverse_waves, tail, pa.list0 != nullptr,
+  ptc_ctx::TimedLaunch tp;  // (reported with bounce 1's launches: bounce 0's traversal launch above has tag 0)
+  if (int rc = timed_begin(ctx, sl.stream, 1, &tp)) return rc;
+  launch_persist(sl.stream, scene, l.mesh, sl.hits, sl.counters, sl.bi, pa, ctx->traverse_waves, tail.begin < tail.end, pa.list0 != nullptr,
                  ctx->has_emitters);
-  if (ctx->time_trace) {
-    HIP_TRY(ctx, hipEventRecord(tp.stop, sl.stream));
-    ctx->timed.push_back(tp);
-  }
+  if (int rc = timed_end(ctx, sl.stream, tp)) return rc;
   sl.cur = MB & 1;
   sl.bounces_done = MB;
   ++ctx->persist_launches;
@@ -471,7 +461,10 @@ static int enqueue_pair(ptc_ctx* ctx, std::vector<ptc_ctx::Pending>& a, std::vec
   const uint32_t* slot_base = ctx->slot_offset ? ctx->slot_offset_dev : nullptr;
   if (int rc = batch_begin(ctx, a.data(), (int)a.size())) return rc;
   const int slot_a = ctx->active_slot;
-  if (int rc = batch_begin(ctx, b.data(), (int)b.size())) return rc;
+  if (int rc = batch_begin(ctx, b.data(), (int)b.size())) {
+    ctx->active_slot = -1;  // (not the first batch's slot: no failure leaves a batch open)
+    return rc;
+  }
   const int slot_b = ctx->active_slot;
   ctx->turn_wait = -1;
   int rc = PTC_OK;
