@@ -1,5 +1,6 @@
 // ptcore_ctx.hpp -- private to libptcore.so: the context behind include/ptcore.h and the helpers its translation units share
-// (ptcore.cpp: context, frame slots, the parameter table, timed launches, views; ptcore_scene.cpp: scene upload; ptcore_trace.cpp: the launch plan of a
+// (ptcore.cpp: context, frame slots, the parameter table, timed launches, views; ptcore_scene.cpp: scene upload in stages -- refusals and
+// host preparation while the old scene stands, its release, device work, one assignment of ptc_scene_state; ptcore_trace.cpp: the launch plan of a
 // batch of frames; ptcore_query.cpp: the ray queries outside the render loop; ptcore_bands.cpp: several GPUs; ptcore_checks.cpp:
 // host-side checks of the schedule helpers).
 #pragma once
@@ -32,25 +33,48 @@ static_assert(sizeof(ptc_material) == sizeof(DMaterial), "ptc_material must matc
 static_assert(sizeof(ptc_bvh_node) == 32, "BVH node is 32 bytes (bvh.hpp:30)");
 static_assert(PTC_MAX_BOUNCES_CAP == kMaxBounces, "bounce cap mismatch");
 
-// in-flight path state a context allocates when the caller has not chosen frames_in_flight
-constexpr uint64_t kAutoFrameBytes = 24ull << 30;
-
-struct ptc_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  std::string err;
-
-  // scene
-  std::vector<void*> scene_allocs;
+// Everything of a context that describes the uploaded scene.  ptc_upload_scene (ptcore_scene.cpp) builds one of these beside the
+// context and assigns it as a whole, after the last step that can fail; a value-initialised one is the state "no scene".  A
+// field that depends on the scene belongs here.
+struct ptc_scene_state {
+  std::vector<void*> scene_allocs;  // every device array of the scene
   DScene scene{};
   bool has_scene = false;
   bool has_emitters = false;  // the scene's material table holds an emissive material (type 3): the shade kernels' kEmit instances
-  uint32_t bvh_nodes = 0, bvh_depth = 0, triangles = 0, bvh4_nodes = 0, bvh4_depth = 0;
+  uint32_t bvh_nodes = 0, bvh_depth = 0, triangles = 0;  // over all meshes (ptc_get_stats)
   ptc_upload_times upload_times{};
   std::vector<DMeshView> mesh_views;   // host copy of DScene::mesh_views: a traversal launch gets its object's mesh as DScene::cur
   std::vector<uint32_t> object_mesh;
   std::vector<uint32_t> mesh_nodes4;   // four-wide nodes of every mesh (k_beam's range check)
+  // The closest-hit stage of the default variant, in object order: per mesh object a k_spheres launch for the run of
+  // spheres in front of it ([pre_begin, pre_end), if it holds any) and a persistent traversal launch; the run that
+  // ends the object list ([tail_begin, tail_end): everything, in a scene without a mesh) is tested by the kernel that ends the bounce (k_shade_fused; k_tail_count in the three-kernel form).
+  struct TraceLaunch {
+    uint32_t mesh, pre_begin, pre_end;
+  };
+  std::vector<TraceLaunch> launches;
+  uint32_t tail_begin = 0, tail_end = 0;
+  // per object: 0, or the class of a "simple" sphere object (sphere_ball_of) -- objects of one class have the same
+  // matrix entries outside the translation columns; a run of one class (at most eight objects) takes sphere_run_lanes
+  std::vector<uint32_t> sphere_class;
+  uint64_t layout_counts[5] = {0, 0, 0, 0, 0};  // bytes of bvh4q, leaf_parent, tris, wide, bvh (ptc_download_layout)
+  // direct-light queries (ptc_direct_light, DESIGN section 5f): the lamp table of the uploaded scene.  Kept out of DScene, which
+  // every existing kernel takes by value.
+  ptc_light_info light_info{};
+  std::string light_error;               // not empty: an emissive sphere of the scene cannot be sampled (the query's refusal)
+  uint32_t light_last = 0;               // last record with a weight > 0
+  const float4* light_records = nullptr; // device: 4 float4 per record (ptc_light); null while there is nothing to sample
+  const float* light_cdf = nullptr;      // device: the records' cdf values, dense (the binary search)
+};
+
+// in-flight path state a context allocates when the caller has not chosen frames_in_flight
+constexpr uint64_t kAutoFrameBytes = 24ull << 30;
+
+struct ptc_ctx : ptc_scene_state {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  std::string err;
 
   // frame
   uint32_t width = 0, height = 0;
@@ -169,17 +193,6 @@ struct ptc_ctx {
   uint64_t frames = 0;
 
   int trace_variant = 3;  // 3: persistent lanes over the four-wide collapse, conservative FMA slabs, exact check of the winner (default); 0: reference-order traversal; 1: culled near-first traversal with exact box decisions
-  // The closest-hit stage of the default variant, in object order: per mesh object a k_spheres launch for the run of
-  // spheres in front of it ([pre_begin, pre_end), if it holds any) and a persistent traversal launch; the run that
-  // ends the object list ([tail_begin, tail_end): everything, in a scene without a mesh) is tested by the kernel that ends the bounce (k_shade_fused; k_tail_count in the three-kernel form).
-  struct TraceLaunch {
-    uint32_t mesh, pre_begin, pre_end;
-  };
-  std::vector<TraceLaunch> launches;
-  uint32_t tail_begin = 0, tail_end = 0;
-  // per object: 0, or the class of a "simple" sphere object (sphere_ball_of) -- objects of one class have the same
-  // matrix entries outside the translation columns; a run of one class (at most eight objects) takes sphere_run_lanes
-  std::vector<uint32_t> sphere_class;
   bool sphere_lanes = true;   // "sphere_lanes"
   bool sphere_fold = true;    // "sphere_fold"
   bool beam = true;           // "beam": primary rays start at their tile's entry points (k_beam)
@@ -197,7 +210,6 @@ struct ptc_ctx {
   bool merge_instances = true;  // "merge_instances": consecutive instances of one mesh walked by one launch (k_traverse4m)
   bool bvh_on_device = true;  // "bvh_build_on_device": the reference BVH of ptc_upload_scene from pt_bvh_gpu.hip
   bool layout_on_device = true;  // "layout_on_device": the traversal layouts derived from it, too
-  uint64_t layout_counts[5] = {0, 0, 0, 0, 0};  // bytes of bvh4q, leaf_parent, tris, wide, bvh (ptc_download_layout)
   uint32_t split_idle = 8;    // "split_idle"
   uint32_t min_waves = 1024;  // "min_waves": fewest persistent wavefronts of a traversal launch
   uint32_t small_waves = 3072;        // "small_waves": ... of a launch with fewer than small_rays_per_lane rays per lane of a full one
@@ -236,14 +248,7 @@ struct ptc_ctx {
   uint32_t persist_launches = 0;         // batches traced through k_persist since ptc_reset_profile
   ptc_occlusion_stats occlusion{};       // ptc_occluded_rays since ptc_reset_profile
 
-  // direct-light queries (ptc_direct_light, DESIGN section 5f): the lamp table of the uploaded scene.  Kept out of DScene, which
-  // every existing kernel takes by value.
-  ptc_light_info light_info{};
-  std::string light_error;               // not empty: an emissive sphere of the scene cannot be sampled (the query's refusal)
-  uint32_t light_last = 0;               // last record with a weight > 0
-  const float4* light_records = nullptr; // device: 4 float4 per record (ptc_light); null while there is nothing to sample
-  const float* light_cdf = nullptr;      // device: the records' cdf values, dense (the binary search)
-  ptc_direct_stats direct{};             // ptc_direct_light since ptc_reset_profile
+  ptc_direct_stats direct{};             // ptc_direct_light (DESIGN section 5f) since ptc_reset_profile
 };
 
 

@@ -1,5 +1,9 @@
-// ptcore_scene.cpp -- ptc_upload_scene and what it needs: validation, the world-space balls of sphere objects, the reference
-// BVH and the traversal layouts (host or device side), ptc_build_bvh*, ptc_make_object.  Part of libptcore.so (ptcore_ctx.hpp).
+// ptcore_scene.cpp -- ptc_upload_scene as a sequence of stages: validation and the other refusals that
+// need the caller's arrays alone; per mesh the reference BVH (reference_bvh: caller's, device-built or host-built); everything
+// else the host can work out (stage_host: lamp table, sphere table, object -> mesh, triangle bases, launch table); the
+// release of the old scene; uploads and per mesh the traversal layouts (mesh_layouts: device or host side); the instance
+// triangles; and ONE commit (one assignment of the context's ptc_scene_state), after the last step that can fail.  Also
+// ptc_build_bvh*, ptc_light_table, ptc_make_object.  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
 #include "pt_layout_rules.hpp"
 
@@ -10,6 +14,69 @@ using namespace ptcd;
 
 namespace {
 
+// One mesh of a scene description: the caller's arrays as bvh_from_mesh would see that mesh on its own.
+struct MeshSlice {
+  const float* positions = nullptr;
+  uint32_t vertex_count = 0;
+  const uint32_t* indices = nullptr;
+  uint32_t index_count = 0;
+  const ptc_bvh_node* caller_bvh = nullptr;
+  uint32_t caller_nodes = 0;
+};
+
+// The meshes of a scene.  The reference keeps ONE mesh whatever the scene file says (scene_description.cpp:42,95), which is
+// what a description without a mesh table means here; with a table (ptc_mesh_range) every mesh object instantiates the
+// mesh its `index` names.
+uint32_t mesh_count_of(const ptc_scene_desc* s) { return s->meshes ? s->mesh_count : (s->index_count ? 1u : 0u); }
+uint32_t mesh_of_object(const ptc_scene_desc* s, const ptc_object& o) { return s->meshes ? o.index : 0u; }
+MeshSlice mesh_slice(const ptc_scene_desc* s, uint32_t m)
+{
+  if (!s->meshes) return {s->positions, s->vertex_count, s->indices, s->index_count, s->bvh, s->bvh ? s->bvh_node_count : 0u};
+  const ptc_mesh_range& r = s->meshes[m];
+  const ptc_bvh_node* bvh = s->bvh && r.bvh_node_count ? s->bvh + r.first_bvh_node : nullptr;
+  return {s->positions + 3u * (size_t)r.first_vertex, r.vertex_count, s->indices + r.first_index, r.index_count, bvh, bvh ? r.bvh_node_count : 0u};
+}
+
+// position of the first index that names no vertex, or -1
+int64_t first_index_out_of_range(const uint32_t* indices, uint32_t index_count, uint32_t vertex_count)
+{
+  for (uint32_t i = 0; i < index_count; ++i)
+    if (indices[i] >= vertex_count) return i;
+  return -1;
+}
+
+// Matrices are column-major: m[4 * col + row].  is_affine: the last row is (0, 0, 0, 1).  all_linear: does `pred(entry, on
+// the diagonal)` hold for every entry outside the translation column?
+bool is_affine(const float* m) { return m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f; }
+template <typename Pred>
+bool all_linear(Pred pred)
+{
+  for (int c = 0; c < 4; ++c)
+    for (int r = 0; r < 4; ++r)
+      if (!(c == 3 && r < 3) && !pred(4 * c + r, c == r)) return false;
+  return true;
+}
+// "simple": both matrices are a pure translation -- diagonal 1.0f, everything else outside the translation column a
+// zero of either sign (a cofactor inverse leaves -0.0f in a checkerboard).  The reference's matrix arithmetic then has
+// the same operands for every such object of a run except the translation, and a lane can fetch what differs for
+// itself (sphere_run_lanes): box, inverse translation, sphere, translation, material
+bool is_simple(const ptc_object& o)
+{
+  auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
+  bool simple = all_linear([&](int k, bool diagonal) {
+    for (const float* mat : {o.m, o.inv_m})
+      if (diagonal ? bits(mat[k]) != 0x3f800000u : (bits(mat[k]) & 0x7fffffffu) != 0u) return false;
+    return true;
+  });
+  for (int r = 0; r < 3; ++r) simple = simple && std::isfinite(o.m[12 + r]) && std::isfinite(o.inv_m[12 + r]);
+  return simple;
+}
+// one sphere class: the same bits in both matrices outside the translation columns
+bool same_linear(const ptc_object& a, const ptc_object& b)
+{
+  return all_linear([&](int k, bool) { return std::memcmp(&a.m[k], &b.m[k], 4) == 0 && std::memcmp(&a.inv_m[k], &b.inv_m[k], 4) == 0; });
+}
+
 // The world-space ball around a sphere object (DScene::sphere_ball), in double precision with the roundings of the
 // float copies charged to the radius: centre = M (c, 1), radius = r * (largest singular value of M's 3 x 3 part).
 // A matrix whose last row is not (0, 0, 0, 1), anything non-finite, a mesh object: radius -1 (no ball, never skipped).
@@ -18,8 +85,8 @@ static void sphere_ball_of(const ptc_object& o, const ptc_sphere* spheres, uint3
   out[0] = make_float4(0.f, 0.f, 0.f, -1.0f);
   for (uint32_t k = 1; k < kSphereTab; ++k) out[k] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (o.type != 0u || o.index >= sphere_count) return;
-  const float* m = o.m;  // column-major: m[4 * col + row]
-  if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return;
+  const float* m = o.m;
+  if (!is_affine(m)) return;
   const ptc_sphere& sp = spheres[o.index];
   double a[3][3];  // a[row][col]
   for (int r = 0; r < 3; ++r)
@@ -82,21 +149,7 @@ static void sphere_ball_of(const ptc_object& o, const ptc_sphere* spheres, uint3
   float inv_sigma = (float)((1.0 / sigma) * (1.0 - 1e-6));
   inv_sigma = std::nextafter(inv_sigma, 0.0f);
   out[0] = make_float4(fx, fy, fz, fr);
-  // "simple": both matrices are a pure translation -- diagonal 1.0f, everything else outside the translation column a
-  // zero of either sign (a cofactor inverse leaves -0.0f in a checkerboard).  The reference's matrix arithmetic then has
-  // the same operands for every such object of a run except the translation, and a lane can fetch what differs for
-  // itself (sphere_run_lanes): box, inverse translation, sphere, translation, material
-  auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
-  bool simple = true;
-  for (int c = 0; c < 4; ++c)
-    for (int r = 0; r < 4; ++r) {
-      if (c == 3 && r < 3) continue;  // the translation column
-      for (const float* mat : {o.m, o.inv_m}) {
-        const uint32_t u = bits(mat[4 * c + r]);
-        simple = simple && (c == r ? u == 0x3f800000u : (u & 0x7fffffffu) == 0u);
-      }
-    }
-  for (int r = 0; r < 3; ++r) simple = simple && std::isfinite(o.m[12 + r]) && std::isfinite(o.inv_m[12 + r]);
+  const bool simple = is_simple(o);
   out[1] = make_float4(inv_sigma, simple ? 1.0f : 0.0f, simple ? fin : 0.0f, 0.f);  // (.z: a simple object does not stretch)
   float mat_f;
   std::memcpy(&mat_f, &material, 4);
@@ -107,6 +160,23 @@ static void sphere_ball_of(const ptc_object& o, const ptc_sphere* spheres, uint3
   out[6] = make_float4(mat_f, 0.f, 0.f, 0.f);
 }
 
+// DScene::sphere_ball of every object, and per object 0 or the class of a simple sphere object (ptc_ctx::sphere_class):
+// classes are numbered from 1 in the order of their first object
+void sphere_table(const ptc_scene_desc* s, std::vector<float4>& balls, std::vector<uint32_t>& sphere_class)
+{
+  balls.resize((size_t)s->object_count * kSphereTab);
+  sphere_class.assign(s->object_count, 0u);
+  std::vector<uint32_t> class_first;  // first object of every class
+  for (uint32_t i = 0; i < s->object_count; ++i) {
+    sphere_ball_of(s->objects[i], s->spheres, s->sphere_count, s->object_material_indices[i], &balls[(size_t)kSphereTab * i]);
+    if (balls[(size_t)kSphereTab * i + 1u].y == 0.0f) continue;
+    uint32_t k = 0;
+    while (k < class_first.size() && !same_linear(s->objects[class_first[k]], s->objects[i])) ++k;
+    if (k == class_first.size()) class_first.push_back(i);
+    sphere_class[i] = k + 1u;
+  }
+}
+
 int validate_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
 {
   if (s->object_count && (!s->objects || !s->object_material_indices)) return fail(ctx, PTC_ERR_INVALID, "objects missing");
@@ -115,21 +185,19 @@ int validate_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
   if (s->index_count % 3u) return fail(ctx, PTC_ERR_INVALID, "index_count is not a multiple of 3");
   if (s->object_count > 0xffffu) return fail(ctx, PTC_ERR_INVALID, "more than 65535 objects");
   if (s->index_count && (!s->indices || !s->positions)) return fail(ctx, PTC_ERR_INVALID, "mesh arrays missing");
-  if (!s->meshes) {
-    for (uint32_t i = 0; i < s->index_count; ++i)
-      if (s->indices[i] >= s->vertex_count) return fail(ctx, PTC_ERR_INVALID, "vertex index out of range");
-  } else {
-    if (s->mesh_count > 0xffffu) return fail(ctx, PTC_ERR_INVALID, "more than 65535 meshes");
-    for (uint32_t m = 0; m < s->mesh_count; ++m) {
+  if (s->meshes && s->mesh_count > 0xffffu) return fail(ctx, PTC_ERR_INVALID, "more than 65535 meshes");
+  for (uint32_t m = 0; m < mesh_count_of(s); ++m) {
+    if (s->meshes) {
       const ptc_mesh_range& r = s->meshes[m];
       if ((uint64_t)r.first_vertex + r.vertex_count > s->vertex_count || (uint64_t)r.first_index + r.index_count > s->index_count ||
           r.index_count % 3u)
         return fail(ctx, PTC_ERR_INVALID, "mesh range outside the vertex / index arrays");
       if (r.bvh_node_count && (!s->bvh || (uint64_t)r.first_bvh_node + r.bvh_node_count > s->bvh_node_count))
         return fail(ctx, PTC_ERR_INVALID, "mesh range outside the BVH array");
-      for (uint32_t i = 0; i < r.index_count; ++i)
-        if (s->indices[r.first_index + i] >= r.vertex_count) return fail(ctx, PTC_ERR_INVALID, "vertex index out of range");
     }
+    const MeshSlice mesh = mesh_slice(s, m);
+    if (first_index_out_of_range(mesh.indices, mesh.index_count, mesh.vertex_count) >= 0)
+      return fail(ctx, PTC_ERR_INVALID, "vertex index out of range");
   }
   for (uint32_t i = 0; i < s->object_count; ++i) {
     const ptc_object& o = s->objects[i];
@@ -155,9 +223,10 @@ int validate_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
 // walk never needs (include/ptcore.h): every node but the root is the child of exactly one node, a
 // leaf's offset is a multiple of 3, a leaf's box holds its triangle's vertices, a child's box lies inside its parent's.
 // Exact float comparisons, O(count); the indices were checked against the vertex count before (validate_scene).
-int validate_bvh(ptc_ctx* ctx, const ptc_bvh_node* nodes, uint32_t count, const float* positions, const uint32_t* indices,
-                 uint32_t index_count)
+int validate_bvh(ptc_ctx* ctx, const MeshSlice& mesh)
 {
+  const ptc_bvh_node* nodes = mesh.caller_bvh;
+  const uint32_t count = mesh.caller_nodes, index_count = mesh.index_count;
   auto bad = [&](uint32_t i, const std::string& what) { return fail(ctx, PTC_ERR_INVALID, "BVH node " + std::to_string(i) + ": " + what); };
   std::vector<uint8_t> parents(count, 0u);
   for (uint32_t i = 0; i < count; ++i) {
@@ -169,7 +238,7 @@ int validate_bvh(ptc_ctx* ctx, const ptc_bvh_node* nodes, uint32_t count, const 
       if ((uint64_t)f + 2u >= index_count) return bad(i, "leaf out of range");
       if (f % 3u) return bad(i, "leaf offset is not a multiple of 3");
       for (uint32_t v = 0; v < 3u; ++v) {
-        const float* p = positions + 3u * (size_t)indices[f + v];
+        const float* p = mesh.positions + 3u * (size_t)mesh.indices[f + v];
         for (int k = 0; k < 3; ++k)
           if (!(n.aabb_min[k] <= p[k] && p[k] <= n.aabb_max[k])) return bad(i, "leaf box does not contain its triangle");
       }
@@ -251,7 +320,7 @@ int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_
         for (int r = 0; r < 3; ++r) c[k][r] = (double)o.m[4 * k + r];
         len[k] = std::sqrt(c[k][0] * c[k][0] + c[k][1] * c[k][1] + c[k][2] * c[k][2]);
       }
-      bool ok = o.m[3] == 0.0f && o.m[7] == 0.0f && o.m[11] == 0.0f && o.m[15] == 1.0f && std::isfinite(len[0] + len[1] + len[2]) && len[0] > 0.0;
+      bool ok = is_affine(o.m) && std::isfinite(len[0] + len[1] + len[2]) && len[0] > 0.0;
       for (int a = 0; a < 3 && ok; ++a)
         for (int b = a + 1; b < 3; ++b) {
           const double dt = c[a][0] * c[b][0] + c[a][1] * c[b][1] + c[a][2] * c[b][2];
@@ -271,18 +340,10 @@ int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_
       push(l, 1u, 4.0 * 3.14159265358979323846 * (double)radius * (double)radius);
       ++li.sphere_lights;
     } else {
-      const float* positions = s->positions;
-      const uint32_t* indices = s->indices;
-      uint32_t index_count = s->index_count;
-      if (s->meshes) {
-        const ptc_mesh_range& r = s->meshes[o.index];
-        positions += 3u * (size_t)r.first_vertex;
-        indices += r.first_index;
-        index_count = r.index_count;
-      }
-      for (uint32_t t = 0; t + 2u < index_count; t += 3u) {
-        const float *q0 = positions + 3u * (size_t)indices[t], *q1 = positions + 3u * (size_t)indices[t + 1u],
-                    *q2 = positions + 3u * (size_t)indices[t + 2u];
+      const MeshSlice mesh = mesh_slice(s, mesh_of_object(s, o));
+      for (uint32_t t = 0; t + 2u < mesh.index_count; t += 3u) {
+        const float *q0 = mesh.positions + 3u * (size_t)mesh.indices[t], *q1 = mesh.positions + 3u * (size_t)mesh.indices[t + 1u],
+                    *q2 = mesh.positions + 3u * (size_t)mesh.indices[t + 2u];
         float4 rec[kTriVec4];
         layout_rules::instance_triangle(m, mk3(q0[0], q0[1], q0[2]), mk3(q1[0], q1[1], q1[2]), mk3(q2[0], q2[1], q2[2]), rec);
         ptc_light l{};
@@ -328,29 +389,31 @@ int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_
 }  // namespace ptcd
 
 namespace {
-// The reference BVH of a mesh built on the device.  nodes_host gets the 2T-1 nodes in the reference's layout;
-// *packed_out (when asked for) keeps the device copy in DScene::bvh's layout, owned by the caller.
-int bvh_on_device(ptc_ctx* ctx, const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
-                  ptc_bvh_node* nodes_host, uint32_t* max_depth, float4** packed_out, std::vector<uint32_t>* level_base = nullptr)
+
+const char kBvhFailed[] = "BVH build failed (empty SAH side: coincident centroids?)";
+
+// The reference BVH of a mesh built on the device; the caller has checked the indices and the vertices in use.  nodes_host
+// gets the 2T-1 nodes in the reference's layout; *packed_out (when asked for) keeps the device copy in DScene::bvh's layout,
+// owned by the caller.
+int bvh_on_device(ptc_ctx* ctx, const MeshSlice& mesh, ptc_bvh_node* nodes_host, uint32_t* max_depth, float4** packed_out,
+                  std::vector<uint32_t>* level_base = nullptr)
 {
-  const uint32_t T = index_count / 3u;
+  const uint32_t T = mesh.index_count / 3u;
   if (T == 0u) return fail(ctx, PTC_ERR_BVH, "empty mesh");
-  for (uint32_t i = 0; i < T * 3u; ++i)
-    if (indices[i] >= vertex_count) return fail(ctx, PTC_ERR_INVALID, "vertex index out of range");
   std::vector<void*> pool;
   const float* d_pos = nullptr;
   const uint32_t* d_idx = nullptr;
   float4* d_packed = nullptr;
   ptc_bvh_node* d_nodes = nullptr;
   const size_t count = 2u * (size_t)T - 1u;
-  int rc = upload(ctx, pool, &d_pos, positions, (size_t)vertex_count * 3u);
-  if (!rc) rc = upload(ctx, pool, &d_idx, indices, (size_t)T * 3u);
+  int rc = upload(ctx, pool, &d_pos, mesh.positions, (size_t)mesh.vertex_count * 3u);
+  if (!rc) rc = upload(ctx, pool, &d_idx, mesh.indices, (size_t)T * 3u);
   if (!rc) rc = dev_alloc(ctx, pool, &d_packed, 2u * count);
   if (!rc && nodes_host) rc = dev_alloc(ctx, pool, &d_nodes, count);
   uint32_t built = 0u;
   if (!rc) {
     rc = build_bvh_device(ctx->stream, d_pos, d_idx, T * 3u, d_packed, d_nodes, &built, max_depth, level_base);
-    if (rc) fail(ctx, rc, rc == PTC_ERR_BVH ? "BVH build failed (empty SAH side: coincident centroids?)" : "device BVH build failed");
+    if (rc) fail(ctx, rc, rc == PTC_ERR_BVH ? kBvhFailed : "device BVH build failed");
   }
   if (!rc && nodes_host && hipMemcpy(nodes_host, d_nodes, count * sizeof(ptc_bvh_node), hipMemcpyDeviceToHost) != hipSuccess)
     rc = fail(ctx, PTC_ERR_HIP, "device BVH download failed");
@@ -359,33 +422,297 @@ int bvh_on_device(ptc_ctx* ctx, const float* positions, uint32_t vertex_count, c
   if (!rc && packed_out) *packed_out = d_packed;
   return rc ? rc : (int)built;
 }
-}  // namespace
-
-namespace {
 
 // one mesh of the scene on its way to the device
 struct MeshWork {
-  // input slice
-  const float* positions = nullptr;
-  uint32_t vertex_count = 0;
-  const uint32_t* indices = nullptr;
-  uint32_t index_count = 0;
-  const ptc_bvh_node* caller_bvh = nullptr;
-  uint32_t caller_nodes = 0;
-  // reference BVH
+  MeshSlice in;
+  // reference BVH (reference_bvh)
   std::vector<ptc_bvh_node> built;   // host copy of a BVH built here (only when something on the host needs it)
-  const ptc_bvh_node* nodes = nullptr;
+  const ptc_bvh_node* nodes = nullptr;  // the host's copy, the caller's or `built`; null when only the device holds the tree
   std::vector<uint32_t> level_base;  // first node of every depth + the node count, when the nodes are stored depth by depth
   float4* dev_packed = nullptr;      // the device builder's output, already in DMeshView::bvh's layout
-  uint32_t node_count = 0, depth = 0;
-  // layouts
-  DMeshView view{};
-  const uint32_t* tri_order_dev = nullptr;  // depth-first rank -> triangle (device layouts)
-  std::vector<uint32_t> tri_order_host;     // ... (host layouts)
-  uint32_t triangles = 0, w4_depth = 0, w4_nodes = 0;
+  uint32_t node_count = 0, depth = 0, triangles = 0;
   bool layouts_on_device = false;
+  // traversal layouts (mesh_layouts), whichever side built them
+  DMeshView view{};
+  const uint32_t* tri_order_dev = nullptr;  // depth-first rank -> triangle: on the device ...
+  std::vector<uint32_t> tri_order_host;     // ... or on the host
+  uint32_t w4_depth = 0, w4_nodes = 0;
   ~MeshWork() { if (dev_packed) (void)hipFree(dev_packed); }
 };
+
+// An upload in progress: the scene state it builds beside the context (ptc_scene_state: assigned to the context as a whole,
+// at the end; freed with this struct if it never gets there), the host's staging of arrays that go to the device only
+// (stage_host), and the clock behind upload_times: lap(field) charges the time since the last lap to that field.
+struct NewScene : ptc_scene_state {
+  std::vector<ptc_light> lights;
+  std::vector<float> cdf;          // the records' cdf values; empty: nothing to sample
+  std::vector<float4> balls;       // DScene::sphere_ball
+  std::vector<uint32_t> tri_base;  // DScene::object_tri_base
+  size_t tri_records = 0;          // records of DScene::tris
+  std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now(), last = start;
+  void lap(float& into)
+  {
+    const auto now = std::chrono::steady_clock::now();
+    into += std::chrono::duration<float, std::milli>(now - last).count();
+    last = now;
+  }
+  ~NewScene() { free_pool(scene_allocs); }
+};
+
+// The reference BVH of one mesh (scene_description.cpp:99-101): the caller's tree, else the device builder's, else the host
+// builder's -- and with it which side derives the layouts.
+int reference_bvh(ptc_ctx* ctx, MeshWork& w, NewScene& n)
+{
+  if (w.in.index_count == 0u) return PTC_OK;  // (the reference panics on an empty mesh, bvh.cpp:200; here: a mesh nobody can hit)
+  if (w.in.caller_bvh) {
+    w.nodes = w.in.caller_bvh;
+    w.node_count = w.in.caller_nodes;
+    w.depth = bvh_depth_of(w.nodes, w.node_count, &w.level_base);
+    n.lap(n.upload_times.copy_ms);
+  } else {
+    const bool host_copy = !ctx->bvh_on_device || !ctx->layout_on_device;
+    if (host_copy) w.built.resize((size_t)w.in.index_count / 3u * 2u);
+    int rc;
+    if (ctx->bvh_on_device) {
+      rc = bvh_on_device(ctx, w.in, host_copy ? w.built.data() : nullptr, &w.depth, &w.dev_packed, &w.level_base);
+      if (rc < 0) return rc;
+      n.upload_times.bvh_on_device = 1u;
+    } else {
+      rc = build_bvh(w.in.positions, w.in.vertex_count, w.in.indices, w.in.index_count, w.built.data(), &w.depth);
+      if (rc < 0) return fail(ctx, rc, kBvhFailed);
+      (void)bvh_depth_of(w.built.data(), (uint32_t)rc, &w.level_base);
+    }
+    w.nodes = host_copy ? w.built.data() : nullptr;
+    w.node_count = (uint32_t)rc;
+    n.lap(n.upload_times.bvh_build_ms);
+  }
+  w.triangles = w.node_count ? (w.node_count + 1u) / 2u : 0u;
+  // depth-first traversal pushes two children per inner node popped: stack need = depth + 1
+  if (w.node_count && w.depth + 2u > (uint32_t)kStackDepth)
+    return fail(ctx, PTC_ERR_STACK, "BVH depth " + std::to_string(w.depth) + " exceeds the traversal stack");
+  // the layouts come from the device when the nodes are stored depth by depth (the reference's breadth-first order:
+  // always, unless the caller brought a tree numbered some other way)
+  w.layouts_on_device = ctx->layout_on_device && w.node_count != 0u && !w.level_base.empty();
+  if (!w.layouts_on_device && w.node_count != 0u && !w.nodes) return fail(ctx, PTC_ERR_INVALID, "internal: no host copy of the BVH");
+  return PTC_OK;
+}
+
+// Launches of the persistent pipeline (ptc_ctx::TraceLaunch) from the objects' types and, per object, the nodes of the mesh
+// it instantiates.  A mesh object without nodes (empty mesh) is no launch; the sphere code skips non-sphere objects, so
+// the runs on both sides of it merge.
+std::vector<ptc_ctx::TraceLaunch> launch_table(const ptc_object* objects, const std::vector<uint32_t>& object_nodes,
+                                               uint32_t* tail_begin, uint32_t* tail_end)
+{
+  std::vector<ptc_ctx::TraceLaunch> launches;
+  const uint32_t count = (uint32_t)object_nodes.size();
+  uint32_t run_begin = 0;  // objects [run_begin, i) come after the last mesh launch ...
+  bool any = false;        // ... and hold a sphere
+  for (uint32_t i = 0; i < count; ++i)
+    if (objects[i].type == 0u) {
+      any = true;
+    } else if (object_nodes[i]) {
+      launches.push_back({i, any ? run_begin : 0u, any ? i : 0u});
+      run_begin = i + 1u;
+      any = false;
+    }
+  *tail_begin = any ? run_begin : 0u;
+  *tail_end = any ? count : 0u;
+  return launches;
+}
+
+// Everything of the new scene that the host works out alone, from the description and the meshes' node counts; the old
+// scene is still in place, and the one refusal here leaves it there.
+int stage_host(ptc_ctx* ctx, const ptc_scene_desc* s, const std::vector<MeshWork>& meshes, NewScene& n)
+{
+  // the lamp table (direct-light queries).  An emissive sphere that cannot be sampled is no reason to
+  // refuse the scene: it renders as ever, only ptc_direct_light refuses
+  if (build_light_table(s, n.lights, &n.light_info, &n.light_last, &n.light_error) != PTC_OK) n.light_info = ptc_light_info{};
+  if (n.light_info.total_weight > 0.0)
+    for (const ptc_light& l : n.lights) n.cdf.push_back(l.cdf);
+  for (uint32_t i = 0; i < s->material_count; ++i) n.has_emitters |= s->materials[i].type == 3;
+  sphere_table(s, n.balls, n.sphere_class);
+  // per mesh OBJECT (instance): its mesh and the first of its world-space triangle records, which end with one all-zero
+  // record (the dummy triangle of the four-wide tree's unused slots)
+  n.object_mesh.assign(s->object_count, 0u);
+  n.tri_base.assign(s->object_count, 0u);
+  std::vector<uint32_t> object_nodes(s->object_count, 0u);
+  for (uint32_t i = 0; i < s->object_count; ++i) {
+    if (s->objects[i].type != 1u) continue;
+    const uint32_t m = mesh_of_object(s, s->objects[i]);
+    n.object_mesh[i] = m;
+    n.tri_base[i] = (uint32_t)n.tri_records;
+    if (m < meshes.size()) {
+      n.tri_records += (size_t)meshes[m].triangles + 1u;
+      object_nodes[i] = meshes[m].node_count;
+    }
+    if (n.tri_records > 0x7fffffffull) return fail(ctx, PTC_ERR_OOM, "too many instance triangles");
+  }
+  n.launches = launch_table(s->objects, object_nodes, &n.tail_begin, &n.tail_end);
+  for (const MeshWork& w : meshes) {
+    n.bvh_nodes += w.node_count;
+    n.bvh_depth = std::max(n.bvh_depth, w.depth);
+    n.triangles += w.in.index_count / 3u;
+  }
+  DScene& d = n.scene;
+  d.object_count = s->object_count;
+  d.refill_lanes = ctx->refill_lanes;
+  d.split_idle = ctx->split_idle;
+  d.static_eighths = ctx->static_eighths;
+  d.force_slow = (uint32_t)ctx->force_slow;
+  d.spill_stride = ctx->traverse_waves * kWave;  // (the overflow areas themselves belong to the frame slots, batch_begin)
+  d.lds_cap = std::min<uint32_t>(ctx->lds_entries, (uint32_t)kLds4);
+  return PTC_OK;
+}
+
+// the arrays every scene has: lamp records, the reference's four tables, the sphere table
+int upload_tables(ptc_ctx* ctx, const ptc_scene_desc* s, NewScene& n)
+{
+  std::vector<void*>& pool = n.scene_allocs;
+  DScene& d = n.scene;
+  if (!n.cdf.empty()) {
+    static_assert(sizeof(ptc_light) == 4 * sizeof(float4), "a lamp record is four float4");
+    if (int rc = upload(ctx, pool, &n.light_records, reinterpret_cast<const float4*>(n.lights.data()), 4u * n.lights.size())) return rc;
+    if (int rc = upload(ctx, pool, &n.light_cdf, n.cdf.data(), n.cdf.size())) return rc;
+  }
+  const DObject* objects = nullptr;
+  if (int rc = upload(ctx, pool, &objects, reinterpret_cast<const DObject*>(s->objects), s->object_count)) return rc;
+  d.objects = objects;
+  if (int rc = upload(ctx, pool, &d.object_material, s->object_material_indices, s->object_count)) return rc;
+  if (int rc = upload(ctx, pool, &d.spheres, reinterpret_cast<const float4*>(s->spheres), s->sphere_count)) return rc;
+  const DMaterial* mats = nullptr;
+  if (int rc = upload(ctx, pool, &mats, reinterpret_cast<const DMaterial*>(s->materials), s->material_count)) return rc;
+  d.materials = mats;
+  return upload(ctx, pool, &d.sphere_ball, n.balls.data(), n.balls.size());
+}
+
+// the arrays of the reference layout of one mesh: positions, indices, nodes as two float4 {min.xyz, first}, {max.xyz, count}
+int mesh_arrays(ptc_ctx* ctx, NewScene& n, MeshWork& w)
+{
+  std::vector<void*>& pool = n.scene_allocs;
+  DMeshView& v = w.view;
+  if (int rc = upload(ctx, pool, &v.positions, w.in.positions, (size_t)w.in.vertex_count * 3u)) return rc;
+  if (int rc = upload(ctx, pool, &v.indices, w.in.indices, w.in.index_count)) return rc;
+  v.bvh_node_count = w.node_count;
+  if (w.dev_packed) {
+    pool.push_back(w.dev_packed);
+    v.bvh = w.dev_packed;
+    w.dev_packed = nullptr;
+    return PTC_OK;
+  }
+  std::vector<float4> packed((size_t)w.node_count * 2u);
+  for (uint32_t i = 0; i < w.node_count; ++i) {
+    const ptc_bvh_node& node = w.nodes[i];
+    float fbits, cbits;
+    std::memcpy(&fbits, &node.first_child_or_primitive, 4);
+    std::memcpy(&cbits, &node.primitive_count, 4);
+    packed[2u * i] = make_float4(node.aabb_min[0], node.aabb_min[1], node.aabb_min[2], fbits);
+    packed[2u * i + 1u] = make_float4(node.aabb_max[0], node.aabb_max[1], node.aabb_max[2], cbits);
+  }
+  return upload(ctx, pool, &v.bvh, packed.data(), packed.size());
+}
+
+// The layouts of one mesh for the fast traversals (wide inner records, the four-wide quantised tree, the depth-first leaf
+// order), derived on the device or on the host and uploaded -- the same bytes; the leaf order stays where it was made.
+// Either side leaves the arrays in the mesh's view and the numbers in one DeviceLayouts.
+int mesh_layouts(ptc_ctx* ctx, NewScene& n, MeshWork& w)
+{
+  std::vector<void*>& pool = n.scene_allocs;
+  DeviceLayouts lay;
+  DMeshView& v = w.view;
+  if (w.layouts_on_device) {
+    const int rc = build_layouts_device(ctx->stream, w.view.bvh, w.node_count, w.level_base, &lay);
+    for (void* q : {(void*)lay.nodes_q, (void*)lay.leaf_parent, (void*)lay.tri_order, (void*)lay.wide})
+      if (q) pool.push_back(q);
+    if (rc) return fail(ctx, rc, "traversal layouts failed on the device");
+    v.wide = lay.wide;
+    v.leaf_parent = lay.leaf_parent;
+    v.bvh4q = reinterpret_cast<const uint4*>(lay.nodes_q);
+    w.tri_order_dev = lay.tri_order;
+    n.upload_times.layout_on_device = 1u;
+    n.lap(n.upload_times.layout_ms);
+  } else {
+    WideAccel wa;
+    if (int rc = build_wide(w.nodes, w.node_count, wa)) return fail(ctx, rc, "wide BVH layout failed");
+    Wide4Accel w4;
+    if (int rc = build_wide4(w.nodes, w.node_count, w4)) return fail(ctx, rc, "four-wide BVH layout failed");
+    n.lap(n.upload_times.layout_ms);
+    const uint32_t* nodes_q = nullptr;
+    if (int rc = upload(ctx, pool, &v.wide, wa.wide.data(), wa.wide.size())) return rc;
+    if (int rc = upload(ctx, pool, &v.leaf_parent, w4.leaf_parent.data(), w4.leaf_parent.size())) return rc;
+    if (int rc = upload(ctx, pool, &nodes_q, w4.nodes_q.data(), w4.nodes_q.size())) return rc;
+    v.bvh4q = reinterpret_cast<const uint4*>(nodes_q);
+    lay.root_ref4 = w4.root_ref, lay.dummy_ref = w4.dummy_ref, lay.root_ref2 = wa.root_ref;
+    std::memcpy(lay.root_min, wa.root_min, sizeof lay.root_min);
+    std::memcpy(lay.root_max, wa.root_max, sizeof lay.root_max);
+    lay.wide4_depth = w4.depth, lay.wide4_nodes = w4.node_count;
+    w.tri_order_host = std::move(wa.tri_order);
+    n.lap(n.upload_times.copy_ms);
+  }
+  v.bvh4_root = lay.root_ref4;
+  v.dummy_ref = lay.dummy_ref;
+  v.root_ref = lay.root_ref2;
+  std::memcpy(v.root_min, lay.root_min, sizeof v.root_min);
+  std::memcpy(v.root_max, lay.root_max, sizeof v.root_max);
+  w.w4_depth = lay.wide4_depth;
+  w.w4_nodes = lay.wide4_nodes;
+  return PTC_OK;
+}
+
+// DScene::tris: per mesh object the world-space triangle records of its instance in depth-first order, from the side that
+// holds the leaf order; and DScene::object_tri_base
+int instance_triangles(ptc_ctx* ctx, const ptc_scene_desc* s, const std::vector<MeshWork>& meshes, NewScene& n)
+{
+  float4* tris = nullptr;
+  if (int rc = dev_alloc(ctx, n.scene_allocs, &tris, n.tri_records * kTriVec4)) return rc;
+  if (n.tri_records) HIP_TRY(ctx, hipMemsetAsync(tris, 0, n.tri_records * kTriVec4 * sizeof(float4), ctx->stream));
+  std::vector<float4> host_tris;
+  for (uint32_t i = 0; i < s->object_count; ++i) {
+    if (s->objects[i].type != 1u || n.object_mesh[i] >= meshes.size()) continue;
+    const MeshWork& w = meshes[n.object_mesh[i]];
+    if (w.triangles == 0u) continue;
+    m4 m;
+    std::memcpy(&m, s->objects[i].m, sizeof m);
+    float4* dst = tris + (size_t)n.tri_base[i] * kTriVec4;
+    if (w.tri_order_dev) {
+      launch_instance_triangles(ctx->stream, m, w.view.positions, w.view.indices, w.tri_order_dev, w.triangles, dst);
+    } else {
+      host_tris.assign((size_t)w.triangles * kTriVec4, make_float4(0.f, 0.f, 0.f, 0.f));
+      build_instance_triangles(m, w.in.positions, w.in.indices, w.tri_order_host, host_tris.data());
+      HIP_TRY(ctx, hipMemcpyAsync(dst, host_tris.data(), host_tris.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  n.scene.tris = tris;
+  n.layout_counts[2] = (uint64_t)n.tri_records * 16u * kTriVec4;  // bytes of tris, all instances (ptc_download_layout)
+  return upload(ctx, n.scene_allocs, &n.scene.object_tri_base, n.tri_base.data(), n.tri_base.size());
+}
+
+// what the scene holds over all its meshes: their views (host and device), the object -> mesh table, the sizes of mesh 0's
+// arrays (ptc_download_layout) and the stack need of the four-wide walk
+int mesh_tables(ptc_ctx* ctx, const std::vector<MeshWork>& meshes, NewScene& n)
+{
+  DScene& d = n.scene;
+  for (const MeshWork& w : meshes) {
+    n.mesh_views.push_back(w.view);
+    n.mesh_nodes4.push_back(w.w4_nodes);
+    if (!w.node_count) continue;
+    // up to three entries per level; whatever exceeds the LDS part goes to the per-thread overflow area (DScene::spill)
+    const uint32_t need4 = 3u * w.w4_depth + 2u > d.lds_cap ? 3u * w.w4_depth + 2u - d.lds_cap : 0u;
+    d.spill_cap = std::max(d.spill_cap, need4);
+  }
+  if (int rc = upload(ctx, n.scene_allocs, &d.mesh_views, n.mesh_views.data(), n.mesh_views.size())) return rc;
+  if (int rc = upload(ctx, n.scene_allocs, &d.object_mesh, n.object_mesh.data(), n.object_mesh.size())) return rc;
+  if (meshes.empty()) return PTC_OK;
+  d.cur = n.mesh_views[0];
+  const uint64_t t0 = meshes[0].triangles, n0 = meshes[0].node_count;
+  n.layout_counts[0] = (uint64_t)meshes[0].w4_nodes * 64u;  // bvh4q
+  n.layout_counts[1] = n0 ? (t0 + 1u) * 32u : 0u;           // leaf_parent
+  n.layout_counts[3] = n0 ? (t0 - 1u) * 64u : 0u;           // wide
+  n.layout_counts[4] = n0 * 32u;                            // bvh
+  return PTC_OK;
+}
 
 }  // namespace
 
@@ -396,332 +723,49 @@ int ptc_upload_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
   if (!ctx || !s) return PTC_ERR_INVALID;
   if (int rc = bind_device(ctx)) return rc;
   if (int rc = validate_scene(ctx, s)) return rc;
+  NewScene n;
+  std::vector<MeshWork> meshes(mesh_count_of(s));
+  for (uint32_t m = 0; m < meshes.size(); ++m) meshes[m].in = mesh_slice(s, m);
 
-  ptc_upload_times times{};
-  auto t_start = std::chrono::steady_clock::now(), t_lap = t_start;
-  auto lap = [&](float& into) {
-    const auto now = std::chrono::steady_clock::now();
-    into += std::chrono::duration<float, std::milli>(now - t_lap).count();
-    t_lap = now;
-  };
-
-  // The meshes of the scene.  The reference keeps ONE mesh whatever the scene file says (scene_description.cpp:42,95),
-  // which is what a description without a mesh table means here; with a table (ptc_mesh_range) every mesh object
-  // instantiates the mesh its `index` names.
-  const uint32_t mesh_count = s->meshes ? s->mesh_count : (s->index_count ? 1u : 0u);
-  std::vector<MeshWork> meshes(mesh_count);
-  for (uint32_t m = 0; m < mesh_count; ++m) {
-    MeshWork& w = meshes[m];
-    if (s->meshes) {
-      const ptc_mesh_range& r = s->meshes[m];
-      w.positions = s->positions + 3u * (size_t)r.first_vertex;
-      w.vertex_count = r.vertex_count;
-      w.indices = s->indices + r.first_index;
-      w.index_count = r.index_count;
-      w.caller_bvh = s->bvh && r.bvh_node_count ? s->bvh + r.first_bvh_node : nullptr;
-      w.caller_nodes = w.caller_bvh ? r.bvh_node_count : 0u;
-    } else {
-      w.positions = s->positions;
-      w.vertex_count = s->vertex_count;
-      w.indices = s->indices;
-      w.index_count = s->index_count;
-      w.caller_bvh = s->bvh;
-      w.caller_nodes = s->bvh ? s->bvh_node_count : 0u;
-    }
-  }
-
-  // ---- phase 1: the reference BVH of every mesh (scene_description.cpp:99-101), unless the caller brought it.  The
-  // old scene is still intact: a failure here leaves the context as it was.
-  uint32_t deepest = 0u, total_nodes = 0u, total_triangles = 0u;
-  for (uint32_t m = 0; m < mesh_count; ++m) {  // vertices a triangle uses are finite (the rule: pt_host.hpp)
-    const int64_t v = first_non_finite_vertex(meshes[m].positions, meshes[m].vertex_count, meshes[m].indices, meshes[m].index_count);
+  // ---- what can refuse the scene while the old one is intact, in this order: a vertex in use that is not finite (the rule:
+  // pt_host.hpp); every caller tree, before any device work; per mesh its reference BVH; the host's own preparation
+  for (uint32_t m = 0; m < meshes.size(); ++m) {
+    const MeshSlice& in = meshes[m].in;
+    const int64_t v = first_non_finite_vertex(in.positions, in.vertex_count, in.indices, in.index_count);
     if (v >= 0)
       return fail(ctx, PTC_ERR_INVALID, "mesh " + std::to_string(m) + ": vertex " + std::to_string(v) + " has a NaN or infinite coordinate");
   }
-  for (const MeshWork& w : meshes)  // every caller tree first, so that a refusal comes before any device work
-    if (w.index_count != 0u && w.caller_bvh)
-      if (int rc = validate_bvh(ctx, w.caller_bvh, w.caller_nodes, w.positions, w.indices, w.index_count)) return rc;
-  for (MeshWork& w : meshes) {
-    if (w.index_count == 0u) continue;  // (the reference panics on an empty mesh, bvh.cpp:200; here: a mesh nobody can hit)
-    if (!w.caller_bvh) {
-      int rc;
-      if (ctx->bvh_on_device) {
-        const bool host_copy = !ctx->layout_on_device;
-        if (host_copy) w.built.resize((size_t)w.index_count / 3u * 2u);
-        rc = bvh_on_device(ctx, w.positions, w.vertex_count, w.indices, w.index_count, host_copy ? w.built.data() : nullptr,
-                           &w.depth, &w.dev_packed, &w.level_base);
-        if (rc < 0) return rc;
-        times.bvh_on_device = 1u;
-        w.nodes = host_copy ? w.built.data() : nullptr;
-      } else {
-        w.built.resize((size_t)w.index_count / 3u * 2u);
-        rc = build_bvh(w.positions, w.vertex_count, w.indices, w.index_count, w.built.data(), &w.depth);
-        if (rc < 0) return fail(ctx, rc, "BVH build failed (empty SAH side: coincident centroids?)");
-        w.nodes = w.built.data();
-        (void)bvh_depth_of(w.nodes, (uint32_t)rc, &w.level_base);
-      }
-      w.node_count = (uint32_t)rc;
-      lap(times.bvh_build_ms);
-    } else {
-      w.nodes = w.caller_bvh;
-      w.node_count = w.caller_nodes;
-      w.depth = bvh_depth_of(w.nodes, w.node_count, &w.level_base);
-      lap(times.copy_ms);
-    }
-    // depth-first traversal pushes two children per inner node popped: stack need = depth + 1
-    if (w.node_count && w.depth + 2u > (uint32_t)kStackDepth)
-      return fail(ctx, PTC_ERR_STACK, "BVH depth " + std::to_string(w.depth) + " exceeds the traversal stack");
-    // the layouts come from the device when the nodes are stored depth by depth (the reference's breadth-first order:
-    // always, unless the caller brought a tree numbered some other way)
-    w.layouts_on_device = ctx->layout_on_device && w.node_count != 0u && !w.level_base.empty();
-    if (!w.layouts_on_device && w.node_count != 0u && !w.nodes) return fail(ctx, PTC_ERR_INVALID, "internal: no host copy of the BVH");
-    deepest = std::max(deepest, w.depth);
-    total_nodes += w.node_count;
-    total_triangles += w.index_count / 3u;
-  }
+  for (const MeshWork& w : meshes)
+    if (w.in.index_count != 0u && w.in.caller_bvh)
+      if (int rc = validate_bvh(ctx, w.in)) return rc;
+  for (MeshWork& w : meshes)
+    if (int rc = reference_bvh(ctx, w, n)) return rc;
+  if (int rc = stage_host(ctx, s, meshes, n)) return rc;
 
-  // the lamp table (direct-light queries), on the host from the caller's arrays.  An emissive sphere that
-  // cannot be sampled is no reason to refuse the scene: it renders as ever, only ptc_direct_light refuses
-  std::vector<ptc_light> lights;
-  ptc_light_info light_info{};
-  uint32_t light_last = 0u;
-  std::string light_error;
-  if (build_light_table(s, lights, &light_info, &light_last, &light_error) != PTC_OK) light_info = ptc_light_info{};
-
-  // ---- phase 2: the old scene goes.  Iterations queued or in flight were asked for against it: trace them first
+  // ---- the old scene goes, before the new one's allocations.  Iterations queued or in flight were asked for against it:
+  // trace them first.  From here to the commit the context holds no scene, and a failure leaves it so (~NewScene)
   if (int rc = sync_frames(ctx)) return rc;
   free_pool(ctx->scene_allocs);
-  ctx->has_scene = false;
-  ctx->has_emitters = false;
-  ctx->light_records = nullptr;
-  ctx->light_cdf = nullptr;
-  ctx->light_info = light_info;
-  ctx->light_last = light_last;
-  ctx->light_error = light_error;
-  if (!lights.empty() && light_info.total_weight > 0.0) {
-    std::vector<float> cdf(lights.size());
-    for (size_t k = 0; k < lights.size(); ++k) cdf[k] = lights[k].cdf;
-    static_assert(sizeof(ptc_light) == 4 * sizeof(float4), "a lamp record is four float4");
-    if (int rc = upload(ctx, ctx->scene_allocs, &ctx->light_records, reinterpret_cast<const float4*>(lights.data()), 4u * lights.size())) return rc;
-    if (int rc = upload(ctx, ctx->scene_allocs, &ctx->light_cdf, cdf.data(), cdf.size())) return rc;
-  }
+  static_cast<ptc_scene_state&>(*ctx) = ptc_scene_state{};
   ++ctx->scene_serial;
-  DScene d{};
-  const DObject* objects = nullptr;
-  if (int rc = upload(ctx, ctx->scene_allocs, &objects, reinterpret_cast<const DObject*>(s->objects), s->object_count)) return rc;
-  d.objects = objects;
-  if (int rc = upload(ctx, ctx->scene_allocs, &d.object_material, s->object_material_indices, s->object_count)) return rc;
-  if (int rc = upload(ctx, ctx->scene_allocs, &d.spheres, reinterpret_cast<const float4*>(s->spheres), s->sphere_count)) return rc;
-  const DMaterial* mats = nullptr;
-  if (int rc = upload(ctx, ctx->scene_allocs, &mats, reinterpret_cast<const DMaterial*>(s->materials), s->material_count)) return rc;
-  d.materials = mats;
-  for (uint32_t i = 0; i < s->material_count; ++i) ctx->has_emitters |= s->materials[i].type == 3;
-  {
-    std::vector<float4> balls((size_t)s->object_count * kSphereTab);
-    ctx->sphere_class.assign(s->object_count, 0u);
-    std::vector<uint32_t> class_first;  // first object of every class
-    for (uint32_t i = 0; i < s->object_count; ++i) {
-      sphere_ball_of(s->objects[i], s->spheres, s->sphere_count, s->object_material_indices[i], &balls[(size_t)kSphereTab * i]);
-      if (balls[(size_t)kSphereTab * i + 1u].y == 0.0f) continue;
-      auto same = [&](const ptc_object& a, const ptc_object& b) {
-        for (int c = 0; c < 4; ++c)
-          for (int r = 0; r < 4; ++r) {
-            if (c == 3 && r < 3) continue;
-            if (std::memcmp(&a.m[4 * c + r], &b.m[4 * c + r], 4) != 0 || std::memcmp(&a.inv_m[4 * c + r], &b.inv_m[4 * c + r], 4) != 0) return false;
-          }
-        return true;
-      };
-      uint32_t k = 0;
-      while (k < class_first.size() && !same(s->objects[class_first[k]], s->objects[i])) ++k;
-      if (k == class_first.size()) class_first.push_back(i);
-      ctx->sphere_class[i] = k + 1u;
-    }
-    if (int rc = upload(ctx, ctx->scene_allocs, &d.sphere_ball, balls.data(), balls.size())) return rc;
-  }
-  lap(times.copy_ms);
 
-  // ---- phase 3: per mesh, the arrays of the reference layout and the layouts for the fast traversals (wide inner
-  // records, the four-wide quantised tree, the depth-first leaf order)
+  if (int rc = upload_tables(ctx, s, n)) return rc;
+  n.lap(n.upload_times.copy_ms);
   for (MeshWork& w : meshes) {
-    DMeshView& v = w.view;
-    w.triangles = w.node_count ? (w.node_count + 1u) / 2u : 0u;
-    if (int rc = upload(ctx, ctx->scene_allocs, &v.positions, w.positions, (size_t)w.vertex_count * 3u)) return rc;
-    if (int rc = upload(ctx, ctx->scene_allocs, &v.indices, w.indices, w.index_count)) return rc;
-    if (w.dev_packed) {
-      ctx->scene_allocs.push_back(w.dev_packed);
-      v.bvh = w.dev_packed;
-      w.dev_packed = nullptr;
-    } else {
-      // node -> two float4: {min.xyz, first}, {max.xyz, count}
-      std::vector<float4> packed((size_t)w.node_count * 2u);
-      for (uint32_t i = 0; i < w.node_count; ++i) {
-        const ptc_bvh_node& n = w.nodes[i];
-        float fbits, cbits;
-        std::memcpy(&fbits, &n.first_child_or_primitive, 4);
-        std::memcpy(&cbits, &n.primitive_count, 4);
-        packed[2u * i] = make_float4(n.aabb_min[0], n.aabb_min[1], n.aabb_min[2], fbits);
-        packed[2u * i + 1u] = make_float4(n.aabb_max[0], n.aabb_max[1], n.aabb_max[2], cbits);
-      }
-      if (int rc = upload(ctx, ctx->scene_allocs, &v.bvh, packed.data(), packed.size())) return rc;
-    }
-    v.bvh_node_count = w.node_count;
-    lap(times.copy_ms);
-    if (w.layouts_on_device) {
-      DeviceLayouts lay;
-      const int rc = build_layouts_device(ctx->stream, v.bvh, w.node_count, w.level_base, &lay);
-      for (void* q : {(void*)lay.nodes_q, (void*)lay.leaf_parent, (void*)lay.tri_order, (void*)lay.wide})
-        if (q) ctx->scene_allocs.push_back(q);
-      if (rc) return fail(ctx, rc, "traversal layouts failed on the device");
-      v.wide = lay.wide;
-      v.leaf_parent = lay.leaf_parent;
-      v.bvh4q = reinterpret_cast<const uint4*>(lay.nodes_q);
-      v.bvh4_root = lay.root_ref4;
-      v.dummy_ref = lay.dummy_ref;
-      v.root_ref = lay.root_ref2;
-      std::memcpy(v.root_min, lay.root_min, sizeof v.root_min);
-      std::memcpy(v.root_max, lay.root_max, sizeof v.root_max);
-      w.tri_order_dev = lay.tri_order;
-      w.w4_depth = lay.wide4_depth;
-      w.w4_nodes = lay.wide4_nodes;
-      times.layout_on_device = 1u;
-      lap(times.layout_ms);
-    } else {
-      WideAccel wa;
-      if (int rc = build_wide(w.nodes, w.node_count, wa)) return fail(ctx, rc, "wide BVH layout failed");
-      Wide4Accel w4;
-      if (int rc = build_wide4(w.nodes, w.node_count, w4)) return fail(ctx, rc, "four-wide BVH layout failed");
-      lap(times.layout_ms);
-      if (int rc = upload(ctx, ctx->scene_allocs, &v.wide, wa.wide.data(), wa.wide.size())) return rc;
-      if (int rc = upload(ctx, ctx->scene_allocs, &v.leaf_parent, w4.leaf_parent.data(), w4.leaf_parent.size())) return rc;
-      {
-        const uint32_t* q = nullptr;
-        if (int rc = upload(ctx, ctx->scene_allocs, &q, w4.nodes_q.data(), w4.nodes_q.size())) return rc;
-        v.bvh4q = reinterpret_cast<const uint4*>(q);
-      }
-      v.bvh4_root = w4.root_ref;
-      v.dummy_ref = w4.dummy_ref;
-      v.root_ref = wa.root_ref;
-      std::memcpy(v.root_min, wa.root_min, sizeof v.root_min);
-      std::memcpy(v.root_max, wa.root_max, sizeof v.root_max);
-      w.tri_order_host = std::move(wa.tri_order);
-      w.w4_depth = w4.depth;
-      w.w4_nodes = w4.node_count;
-      lap(times.copy_ms);
-    }
+    if (int rc = mesh_arrays(ctx, n, w)) return rc;
+    n.lap(n.upload_times.copy_ms);
+    if (int rc = mesh_layouts(ctx, n, w)) return rc;
   }
-
-  // ---- phase 4: per mesh OBJECT (instance), its world-space triangle records in depth-first order (+ one all-zero
-  // record: the dummy triangle of the four-wide tree's unused slots), and the object -> mesh table
-  std::vector<uint32_t> object_mesh(s->object_count, 0u), tri_base(s->object_count, 0u);
-  size_t tri_records = 0;
-  for (uint32_t i = 0; i < s->object_count; ++i) {
-    if (s->objects[i].type != 1u) continue;
-    const uint32_t m = s->meshes ? s->objects[i].index : 0u;
-    object_mesh[i] = m;
-    tri_base[i] = (uint32_t)tri_records;
-    if (m < mesh_count) tri_records += (size_t)meshes[m].triangles + 1u;
-    if (tri_records > 0x7fffffffull) return fail(ctx, PTC_ERR_OOM, "too many instance triangles");
-  }
-  {
-    float4* tris = nullptr;
-    if (int rc = dev_alloc(ctx, ctx->scene_allocs, &tris, tri_records * kTriVec4)) return rc;
-    if (tri_records) HIP_TRY(ctx, hipMemsetAsync(tris, 0, tri_records * kTriVec4 * sizeof(float4), ctx->stream));
-    std::vector<float4> host_tris;
-    for (uint32_t i = 0; i < s->object_count; ++i) {
-      if (s->objects[i].type != 1u || object_mesh[i] >= mesh_count) continue;
-      const MeshWork& w = meshes[object_mesh[i]];
-      if (w.triangles == 0u) continue;
-      m4 m;
-      std::memcpy(&m, s->objects[i].m, sizeof m);
-      float4* dst = tris + (size_t)tri_base[i] * kTriVec4;
-      if (w.tri_order_dev) {
-        launch_instance_triangles(ctx->stream, m, w.view.positions, w.view.indices, w.tri_order_dev, w.triangles, dst);
-      } else {
-        host_tris.assign((size_t)w.triangles * kTriVec4, make_float4(0.f, 0.f, 0.f, 0.f));
-        build_instance_triangles(m, w.positions, w.indices, w.tri_order_host, host_tris.data());
-        HIP_TRY(ctx, hipMemcpyAsync(dst, host_tris.data(), host_tris.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      }
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    d.tris = tris;
-    if (int rc = upload(ctx, ctx->scene_allocs, &d.object_tri_base, tri_base.data(), tri_base.size())) return rc;
-    lap(times.triangles_ms);
-  }
-  ctx->mesh_views.clear();
-  ctx->mesh_nodes4.clear();
-  for (const MeshWork& w : meshes) {
-    ctx->mesh_views.push_back(w.view);
-    ctx->mesh_nodes4.push_back(w.w4_nodes);
-  }
-  ctx->object_mesh = object_mesh;
-  if (int rc = upload(ctx, ctx->scene_allocs, &d.mesh_views, ctx->mesh_views.data(), ctx->mesh_views.size())) return rc;
-  if (int rc = upload(ctx, ctx->scene_allocs, &d.object_mesh, object_mesh.data(), object_mesh.size())) return rc;
-  if (!ctx->mesh_views.empty()) d.cur = ctx->mesh_views[0];
-  lap(times.copy_ms);
-
-  // sizes of mesh 0's arrays (ptc_download_layout)
-  {
-    const MeshWork* w0 = meshes.empty() ? nullptr : &meshes[0];
-    const uint64_t t0 = w0 ? w0->triangles : 0u, n0 = w0 ? w0->node_count : 0u;
-    ctx->layout_counts[0] = (uint64_t)(w0 ? w0->w4_nodes : 0u) * 64u;         // bvh4q
-    ctx->layout_counts[1] = n0 ? (t0 + 1u) * 32u : 0u;                          // leaf_parent
-    ctx->layout_counts[2] = (uint64_t)tri_records * 16u * kTriVec4;            // tris (all instances)
-    ctx->layout_counts[3] = n0 ? (t0 - 1u) * 64u : 0u;                          // wide
-    ctx->layout_counts[4] = n0 * 32u;                                           // bvh
-  }
-  d.refill_lanes = ctx->refill_lanes;
-  d.split_idle = ctx->split_idle;
-  d.static_eighths = ctx->static_eighths;
-  d.force_slow = (uint32_t)ctx->force_slow;
-  d.spill = nullptr;
-  d.spill_stride = ctx->traverse_waves * kWave;
-  // stack need of the four-wide walk: up to three entries per level; whatever exceeds the LDS part (24 entries)
-  // goes to this per-thread overflow area (the areas themselves belong to the frame slots, batch_begin)
-  d.spill_cap = 0;
-  d.lds_cap = std::min<uint32_t>(ctx->lds_entries, (uint32_t)kLds4);
-  uint32_t w4_depth = 0u, w4_nodes = 0u;
-  for (const MeshWork& w : meshes) {
-    if (!w.node_count) continue;
-    // four-wide walk: up to three refs per level
-    const uint32_t need4 = 3u * w.w4_depth + 2u > d.lds_cap ? 3u * w.w4_depth + 2u - d.lds_cap : 0u;
-    d.spill_cap = std::max(d.spill_cap, need4);
-    w4_depth = std::max(w4_depth, w.w4_depth);
-    w4_nodes += w.w4_nodes;
-  }
-  ctx->bvh4_nodes = w4_nodes;
-  ctx->bvh4_depth = w4_depth;
-  d.object_count = s->object_count;
-  // launches of the persistent pipeline (TraceLaunch).  A mesh object without nodes (empty mesh) is no launch; the
-  // sphere code skips non-sphere objects, so the runs on both sides of it merge.
-  ctx->launches.clear();
-  {
-    auto has_sphere = [&](uint32_t b, uint32_t e) {
-      for (uint32_t i = b; i < e; ++i)
-        if (s->objects[i].type == 0u) return true;
-      return false;
-    };
-    auto mesh_nodes = [&](uint32_t i) { return object_mesh[i] < mesh_count ? meshes[object_mesh[i]].node_count : 0u; };
-    uint32_t run_begin = 0;  // objects [run_begin, i) hold the spheres seen since the last mesh launch
-    for (uint32_t i = 0; i < s->object_count; ++i)
-      if (s->objects[i].type == 1u && mesh_nodes(i)) {
-        const bool any = has_sphere(run_begin, i);
-        ctx->launches.push_back({i, any ? run_begin : 0u, any ? i : 0u});
-        run_begin = i + 1u;
-      }
-    const bool any = has_sphere(run_begin, s->object_count);
-    ctx->tail_begin = any ? run_begin : 0u;
-    ctx->tail_end = any ? s->object_count : 0u;
-  }
-  ctx->scene = d;
-  ctx->has_scene = true;
-  ctx->bvh_nodes = total_nodes;
-  ctx->bvh_depth = deepest;
-  ctx->triangles = total_triangles;
+  if (int rc = instance_triangles(ctx, s, meshes, n)) return rc;
+  n.lap(n.upload_times.triangles_ms);
+  if (int rc = mesh_tables(ctx, meshes, n)) return rc;
   if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, PTC_ERR_HIP, "scene upload failed");
-  lap(times.copy_ms);
-  times.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-  ctx->upload_times = times;
+  n.lap(n.upload_times.copy_ms);
+
+  // ---- the commit: nothing above assigned a scene-describing field of the context, nothing below can fail
+  n.upload_times.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - n.start).count();
+  n.has_scene = true;
+  std::swap(static_cast<ptc_scene_state&>(*ctx), static_cast<ptc_scene_state&>(n));
   return PTC_OK;
 }
 
@@ -730,11 +774,10 @@ int ptc_build_bvh_device(ptc_ctx* ctx, const float* positions, uint32_t vertex_c
 {
   if (!ctx || !positions || !indices || !nodes || index_count % 3u != 0u) return fail(ctx, PTC_ERR_INVALID, "bad arguments");
   if (int rc = bind_device(ctx)) return rc;
-  for (uint32_t i = 0; i < index_count; ++i)
-    if (indices[i] >= vertex_count) return fail(ctx, PTC_ERR_INVALID, "vertex index out of range");
+  if (first_index_out_of_range(indices, index_count, vertex_count) >= 0) return fail(ctx, PTC_ERR_INVALID, "vertex index out of range");
   if (const int64_t v = first_non_finite_vertex(positions, vertex_count, indices, index_count); v >= 0)
     return fail(ctx, PTC_ERR_INVALID, "vertex " + std::to_string(v) + " has a NaN or infinite coordinate");
-  return bvh_on_device(ctx, positions, vertex_count, indices, index_count, nodes, max_depth, nullptr);
+  return bvh_on_device(ctx, {positions, vertex_count, indices, index_count, nullptr, 0u}, nodes, max_depth, nullptr);
 }
 
 int ptc_download_layout(ptc_ctx* ctx, int which, void* host, uint64_t capacity, uint64_t* bytes)

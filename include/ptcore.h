@@ -203,7 +203,8 @@ int ptc_set_stream(ptc_ctx* ctx, void* hip_stream);
 
 /* ---- scene + buffers ---- */
 /* Upload half of PathTracer::create_buffers (path_tracer.cu:559-564) = SceneDescription::build_scene's
- * device uploads.  An empty mesh (index_count == 0) is accepted (the reference panics, bvh.cpp:200). */
+ * device uploads.  An empty mesh (index_count == 0) is accepted (the reference panics, bvh.cpp:200).  Every refusal that
+ * depends on the caller's arrays alone leaves the previously uploaded scene in place. */
 int ptc_upload_scene(ptc_ctx* ctx, const ptc_scene_desc* scene);
 /* PathTracer::resize_image (path_tracer.cu:527-545): (re)allocates all per-pixel buffers, restarts. */
 int ptc_resize(ptc_ctx* ctx, uint32_t width, uint32_t height);
