@@ -188,6 +188,8 @@ SIGNATURES = {
     "ptc_check_feed": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "ptc_selftest_math": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ptc_selftest_rng": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ptc_check_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
 }
 
 _lib = None

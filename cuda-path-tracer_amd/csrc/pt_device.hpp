@@ -407,7 +407,7 @@ void launch_shade(hipStream_t s, const DScene& scene, DPaths in, DPaths out, DHi
                   const DBatchInfo& bi, bool emitters = false);
 // the end of a bounce in one pass (k_shade_fused): trailing sphere run [obj_begin, obj_end) + material + stable compaction +
 // final gather.  tile_desc: shade_tiles_per_frame(max_paths) descriptors per frame of the batch (tile_stride apart), zero
-// at allocation and never cleared; epoch: a number no earlier launch on these descriptors has used (1 .. 2^30 - 1).
+// at allocation, cleared again only when the epochs start over; epoch: a number no earlier launch of this lap has used (1 .. 2^30 - 1).
 // list: bounce 0 after launch_raygen(finish_misses): the work list of the bounce's one traversal launch -- the kernel
 // walks it (DeviceCounters::list_count entries per frame) instead of all slots
 void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths in, DPaths out,
@@ -484,5 +484,6 @@ void launch_light_resolve(hipStream_t s, const float4* o4, const float4* d4, con
                           const float4* closest_tp, uint32_t n, float* radiance, float* rays, uint8_t* visible, uint32_t* stats);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,
                      float* out_sin, float* out_cos);
+void launch_selftest_rng(hipStream_t s, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);
 
 }  // namespace pt

@@ -1,5 +1,5 @@
 // pt_post.hip -- what follows the path: k_preview*, k_pack, k_gather_bands (multi-GPU present), the A-Trous denoiser
-// (k_denoise_positions, k_denoise, k_denoise_lds<step>), k_selftest.
+// (k_denoise_positions, k_denoise, k_denoise_lds<step>), k_selftest, k_selftest_rng.
 
 #include "pt_device.hpp"
 #include "pt_rng.hpp"
@@ -317,6 +317,16 @@ __global__ void k_selftest(const float* a, const float* b, uint32_t n, float* ou
   out_cos[i] = c;
 }
 
+// pt_rng.hpp per element, as the render kernels run it: seed, discard, two raw values, two uniform draws.  out[6 i ..]: the
+// state after the seed, the state after the discard, the raw values, the bit patterns of the draws (ptc_check_rng: the host twin).
+__global__ void k_selftest_rng(const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t r[6];
+  selftest_rng_one(seeds[i], discards[i], r);
+  for (int k = 0; k < 6; ++k) out[6u * (size_t)i + (uint32_t)k] = r[k];
+}
 
 // ------------------------------------------------------------------------------------------------
 // launchers
@@ -373,6 +383,10 @@ void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, 
                      float* out_sin, float* out_cos)
 {
   hipLaunchKernelGGL(k_selftest, dim3(div_up(n, 256u)), dim3(256), 0, s, a, b, n, out_div, out_sqrt, out_sin, out_cos);
+}
+void launch_selftest_rng(hipStream_t s, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out)
+{
+  hipLaunchKernelGGL(k_selftest_rng, dim3(div_up(n, 256u)), dim3(256), 0, s, seeds, discards, n, out);
 }
 
 }  // namespace pt

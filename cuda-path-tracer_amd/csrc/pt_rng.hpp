@@ -66,4 +66,21 @@ struct Minstd {
 
 PT_HD uint32_t path_seed(uint32_t index, uint32_t iteration) { return hash32(hash32(index) ^ iteration); }
 
+// One element of the generator's self-test (k_selftest_rng on the device, ptc_check_rng on the host): r = the state after
+// seed(s), the state after discard(z), two raw values, the bit patterns of the two uniform draws that follow them.
+PT_HD void selftest_rng_one(uint32_t s, uint32_t z, uint32_t r[6])
+{
+  Minstd g;
+  g.seed(s);
+  r[0] = g.x;
+  g.discard(z);
+  r[1] = g.x;
+  r[2] = g.next();
+  r[3] = g.next();
+  for (int k = 4; k < 6; ++k) {
+    const float u = g.uniform();
+    __builtin_memcpy(&r[k], &u, 4);
+  }
+}
+
 }  // namespace pt

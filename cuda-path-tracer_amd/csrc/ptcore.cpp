@@ -203,6 +203,21 @@ int set_slot_offset(ptc_ctx* ctx, int value)
   return PTC_OK;
 }
 
+// "debug_shade_epoch": every slot as if it had seen `value` look-back launches and none of them had left a descriptor
+int set_shade_epoch(ptc_ctx* ctx, int value)
+{
+  if (value < 0 || (uint32_t)value > kMaxEpoch) return fail(ctx, PTC_ERR_INVALID, "debug_shade_epoch must be in [0,1073741823]");
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;  // frames in flight carry the epochs they were enqueued with
+  for (auto& sl : ctx->slots) {
+    // (a descriptor of an earlier launch may carry an epoch above `value`, which a launch to come would take again)
+    HIP_TRY(ctx, hipMemset(sl.tile_desc, 0, sizeof(unsigned long long) * (size_t)sl.capacity * sl.tile_stride));
+    sl.shade_epoch = (uint32_t)value;
+  }
+  return PTC_OK;
+}
+static_assert(kMaxEpoch == 1073741823u, "the range message of debug_shade_epoch spells the bound out");
+
 }  // namespace
 
 extern "C" {
@@ -512,6 +527,7 @@ int ptc_set_param(ptc_ctx* ctx, const char* name, int value)
   if (int rc = flush_pending(ctx)) return rc;
   // the parameters that do more than store a checked value
   if (std::strcmp(name, "slot_offset") == 0) return set_slot_offset(ctx, value);
+  if (std::strcmp(name, "debug_shade_epoch") == 0) return set_shade_epoch(ctx, value);
   if (std::strcmp(name, "debug_force_slow") == 0) {  // any value; 1: every ray at fetch time, 2: every winner at verification time
     ctx->scene.force_slow = (uint32_t)value;
     ctx->force_slow = value;

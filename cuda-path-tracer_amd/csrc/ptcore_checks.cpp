@@ -1,6 +1,7 @@
 // ptcore_checks.cpp -- host-side checks of the rules the kernels share with the host (ptc_check_beam, ptc_check_feed,
-// ptc_check_traversal_layout), ptc_debug_beam_entries, ptc_selftest_math.  Part of libptcore.so (ptcore_ctx.hpp).
+// ptc_check_traversal_layout, ptc_check_rng), ptc_debug_beam_entries, ptc_selftest_math, ptc_selftest_rng.  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
+#include "pt_rng.hpp"
 
 using namespace pt;
 using namespace ptcd;
@@ -368,6 +369,43 @@ int ptc_selftest_math(ptc_ctx* ctx, const float* a, const float* b, uint32_t n, 
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   free_pool(pool);
   if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("selftest: ") + hipGetErrorString(e));
+  return PTC_OK;
+}
+
+// The per-path generator (pt_rng.hpp) on the host: out[6 i ..] as k_selftest_rng writes it
+int ptc_check_rng(const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out)
+{
+  if (n == 0) return PTC_OK;
+  if (!seeds || !discards || !out) return PTC_ERR_INVALID;
+  for (uint32_t i = 0; i < n; ++i) selftest_rng_one(seeds[i], discards[i], out + 6u * (size_t)i);
+  return PTC_OK;
+}
+
+// ... and on the device
+int ptc_selftest_rng(ptc_ctx* ctx, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out)
+{
+  if (!ctx || !seeds || !discards || !out) return PTC_ERR_INVALID;
+  if (n == 0) return PTC_OK;
+  if (int rc = bind_device(ctx)) return rc;
+  std::vector<void*> pool;
+  uint32_t *d_seeds = nullptr, *d_discards = nullptr, *d_out = nullptr;
+  int rc = dev_alloc(ctx, pool, &d_seeds, n);
+  if (!rc) rc = dev_alloc(ctx, pool, &d_discards, n);
+  if (!rc) rc = dev_alloc(ctx, pool, &d_out, (size_t)n * 6u);
+  if (rc) {
+    free_pool(pool);
+    return rc;
+  }
+  hipError_t e = hipMemcpyAsync(d_seeds, seeds, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_discards, discards, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    launch_selftest_rng(ctx->stream, d_seeds, d_discards, n, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 6u * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  free_pool(pool);
+  if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("selftest_rng: ") + hipGetErrorString(e));
   return PTC_OK;
 }
 

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -67,6 +68,9 @@ struct ptc_scene_state {
   const float* light_cdf = nullptr;      // device: the records' cdf values, dense (the binary search)
 };
 
+// the last epoch of a lap of look-back launches on a slot's tile descriptors (30 bits: pt_shade_tile.inc; ptcore_trace.cpp, next_epoch)
+constexpr uint32_t kMaxEpoch = 0x3fffffffu;
+
 // in-flight path state a context allocates when the caller has not chosen frames_in_flight
 constexpr uint64_t kAutoFrameBytes = 24ull << 30;
 
@@ -97,7 +101,7 @@ struct ptc_ctx : ptc_scene_state {
     uint32_t* chunk_offsets = nullptr;
     unsigned long long* tile_desc = nullptr;  // k_shade_fused: look-back descriptors, tile_stride per frame of the batch
     uint32_t tile_stride = 0;
-    uint32_t shade_epoch = 0;           // look-back launches on these descriptors so far (1 .. 2^30 - 1, then round again)
+    uint32_t shade_epoch = 0;           // look-back launches on these descriptors so far (1 .. kMaxEpoch, then round again; "debug_shade_epoch")
     float4* beam_entries = nullptr; // "beam": entry points of the batch's cameras (DBeam), capacity x tiles x 8 float4
     DBeam beam{};                   // ... as bounce 0's first traversal launch gets them (entries null: off for this batch)
     DCameras beam_cams{};           // the cameras (of the beams) the entries in beam_entries were computed for ...

@@ -7,11 +7,17 @@ using namespace ptcd;
 
 namespace {
 
-// the epoch of the next look-back launch on a slot's tile descriptors (k_shade_fused, the listing k_raygen / k_spheres)
+// the epoch of the next look-back launch on a slot's tile descriptors (k_shade_fused, the listing k_raygen / k_spheres).  After
+// kMaxEpoch the epochs start at 1 again, and a descriptor that no launch of the finished lap has overwritten (a tile above a band
+// that ptc_set_rows shrank) would pass for one of the new lap: the descriptors are cleared on the slot's stream, behind the last
+// launch of the old lap and in front of the launch that takes epoch 1.  (A failure of the clear is the caller's next check_last.)
 uint32_t next_epoch(ptc_ctx::FrameSlot& sl)
 {
-  sl.shade_epoch = sl.shade_epoch >= 0x3fffffffu ? 1u : sl.shade_epoch + 1u;
-  return sl.shade_epoch;
+  if (sl.shade_epoch >= kMaxEpoch) {
+    (void)hipMemsetAsync(sl.tile_desc, 0, sizeof(unsigned long long) * (size_t)sl.capacity * sl.tile_stride, sl.stream);
+    sl.shade_epoch = 0u;
+  }
+  return ++sl.shade_epoch;
 }
 
 // Persistent wavefronts of a traversal launch.  A launch ends with its longest ray (about 100 us however few rays it
@@ -373,13 +379,10 @@ int batch_persist(ptc_ctx* ctx, const uint32_t* slot_base_dev)
   pa.slot_base = slot_base_dev;
   pa.tile_desc = sl.tile_desc;
   pa.tile_stride = sl.tile_stride;
-  pa.epoch0 = next_epoch(sl);  // bounce b's pass: epoch0 + b
+  // bounce b's pass: epoch0 + b.  A run that would pass kMaxEpoch starts the new lap early, at 1 (next_epoch clears the descriptors)
+  if (sl.shade_epoch + (uint32_t)MB > kMaxEpoch) sl.shade_epoch = kMaxEpoch;
+  pa.epoch0 = next_epoch(sl);
   for (int b = 1; b < MB; ++b) next_epoch(sl);
-  if (sl.shade_epoch < pa.epoch0) {  // the epochs wrapped inside this batch: start the batch's run at 1 again
-    sl.shade_epoch = 0;
-    pa.epoch0 = next_epoch(sl);
-    for (int b = 1; b < MB; ++b) next_epoch(sl);
-  }
   pa.stage = sl.stage;
   pa.band = ctx->band;
   pa.list0 = sl.primary_finished ? sl.worklist : nullptr;
@@ -517,6 +520,8 @@ int ptc_trace_begin(ptc_ctx* ctx, const ptc_camera* camera)
   if (int rc = frame_ready(ctx)) return rc;
   if (!camera) return fail(ctx, PTC_ERR_INVALID, "camera is NULL");
   if (ctx->active_slot >= 0) return fail(ctx, PTC_ERR_INVALID, "ptc_trace_end missing");
+  // (ptc_trace stops at max_iterations; nothing else stands between the stepwise calls and ptc_trace_end's ++iteration)
+  if (ctx->iteration == INT_MAX) return fail(ctx, PTC_ERR_INVALID, "the iteration counter is at INT_MAX: ptc_restart or ptc_set_iteration first");
   if (int rc = flush_pending(ctx)) return rc;
   ctx->cam = make_camera(*camera, ctx->width, ctx->height);
   ctx->have_cam = true;

@@ -402,3 +402,13 @@ class PathTracer:
         self._check(self._lib.ptc_selftest_math(self._ctx, a.ctypes.data_as(fp), b.ctypes.data_as(fp), len(a),
                                                 *[o.ctypes.data_as(fp) for o in outs]))
         return outs
+
+    def selftest_rng(self, seeds, discards):
+        """The per-path generator on the device (ptc_selftest_rng) -> uint32 [n, 6]: state after the seed, state after the
+        discard, two raw values, the bit patterns of the two uniform draws behind them."""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+        discards = np.ascontiguousarray(discards, dtype=np.uint32)
+        assert seeds.shape == discards.shape and seeds.ndim == 1
+        out = np.zeros((len(seeds), 6), dtype=np.uint32)
+        self._check(self._lib.ptc_selftest_rng(self._ctx, seeds.ctypes.data, discards.ctypes.data, len(seeds), out.ctypes.data))
+        return out

@@ -244,7 +244,7 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *            each other, defaults may move with the hardware, a name may go when its alternative goes
  *              fused_shade, filter_rays, merge_instances, sphere_lanes, sphere_fold, beam, ray_sort, denoise_variant, bvh_build_on_device,
  *              layout_on_device, split_idle, refill_lanes, static_eighths, small_waves, small_rays_per_lane, min_waves
- *   TEST     hooks for the parity tests only: debug_lds_entries, debug_force_slow
+ *   TEST     hooks for the parity tests only: debug_lds_entries, debug_force_slow, debug_shade_epoch
  * None of them changes a result, with one exception that is the point of it: slot_offset keys the material RNG
  * (multi-GPU).  Unknown names return PTC_ERR_INVALID.  Known names:
  *   "frames_in_flight" consecutive iterations in flight at once, folded into the framebuffer in iteration order
@@ -332,6 +332,10 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *                      Bit-identical, measured 6-7 % slower than the default (profiles/r05_pair_batches.txt): off.  Any time
  *   "debug_lds_entries" test hook: keep only this many of the 24 per-lane traversal stack entries in LDS, so that small
  *                      scenes exercise the global overflow area (1..24; before ptc_upload_scene)
+ *   "debug_shade_epoch" test hook: the look-back launches on every frame slot's tile descriptors count on from this value
+ *                      (0..2^30 - 1; the next launch takes value + 1, and after 2^30 - 1 the epochs start at 1 again, behind a
+ *                      clear of the descriptors), so that a test reaches the wrap without 2^30 launches.  Any time, also after
+ *                      ptc_resize; synchronises the frames in flight, as slot_offset does, and clears the descriptors
  *   "debug_force_slow" test hook: route every ray through the exact redo at the end of the traversal launch */
 int ptc_set_param(ptc_ctx* ctx, const char* name, int value);
 
@@ -347,6 +351,7 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera);
  *                       (path_tracer.cu:423-457); slot_base_dev (device pointer to ONE uint32, or
  *                       NULL for 0) is added to every local slot index before RNG seeding
  *   ptc_trace_end     = final_gathering_kernel (path_tracer.cu:460-470) + ++iteration
+ * (ptc_trace_begin at iteration() == INT_MAX fails with PTC_ERR_INVALID: the counter is an int, and ptc_trace_end would overflow it)
  * ptc_live_count_dev returns the device address of the uint32 holding the number of live paths
  * entering bounce b of the current frame (valid after bounce b-1 was enqueued). */
 int ptc_trace_begin(ptc_ctx* ctx, const ptc_camera* camera);
@@ -569,6 +574,13 @@ int ptc_debug_persist(ptc_ctx* ctx, int slot, void* dst, uint64_t bytes);
  * sqrt and the deterministic sin/cos on the GPU for n inputs (host arrays in, host arrays out). */
 int ptc_selftest_math(ptc_ctx* ctx, const float* a, const float* b, uint32_t n, float* out_div,
                       float* out_sqrt, float* out_sin, float* out_cos);
+/* Device self-test of the per-path generator (csrc/pt_rng.hpp: thrust::default_random_engine + uniform_real_distribution<float>,
+ * whose bits every frame depends on).  Per element i (host arrays in and out): seed(seeds[i]), discard(discards[i]), two raw values,
+ * then two uniform draws; out[6 i ..] = the state after the seed, the state after the discard, the raw values, the bit
+ * patterns of the draws. */
+int ptc_selftest_rng(ptc_ctx* ctx, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);
+/* The same header run on the host (no GPU; test hook): the same six words per element. */
+int ptc_check_rng(const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);
 
 #ifdef __cplusplus
 }

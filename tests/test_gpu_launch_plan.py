@@ -150,6 +150,7 @@ PARAMS = {
     "traverse_waves": (8, 65536, "traverse_waves out of range", UPLOAD),
     "debug_lds_entries": (1, 24, "debug_lds_entries must be in [1,24]", UPLOAD),
     "debug_force_slow": (INT_MIN, INT_MAX, None, None),
+    "debug_shade_epoch": (0, 0x3FFFFFFF, "debug_shade_epoch must be in [0,1073741823]", None),
     "layout_on_device": (0, 1, "layout_on_device must be 0 or 1", None),
     "filter_rays": (0, 1, "filter_rays must be 0 or 1", None),
     "fused_shade": (0, 1, "fused_shade must be 0 or 1", None),
@@ -190,7 +191,7 @@ def _outside(lo, hi):
 
 
 def test_every_parameter_at_the_ends_of_its_range(pkg):
-    assert len(PARAMS) == 29
+    assert len(PARAMS) == 30
     invalid = pkg._capi.PTC_ERR_INVALID
     with pkg.PathTracer(device=0, max_bounces=MB) as pt:   # no scene, no frame: every gate is open
         for name, (lo, hi, refusal, _) in PARAMS.items():
@@ -225,7 +226,7 @@ def test_refusals_leave_a_working_context(pkg):
             if gate:
                 refusals += [(name, v, f"set {name} before {gate}") for v in (lo, hi)]
         refusals.append(("no_such_knob", 0, "unknown parameter no_such_knob"))
-        assert len(refusals) == 2 * 27 + 1 + 2 * 7 + 1
+        assert len(refusals) == 2 * 28 + 1 + 2 * 7 + 1
         for name, v, refusal in refusals:
             assert _set(pkg, pt, name, v) == (invalid, refusal.encode()), (name, v)
             assert np.array_equal(frame(), first), (name, v)
