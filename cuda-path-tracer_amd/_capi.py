@@ -121,6 +121,11 @@ class ptc_upload_times(C.Structure):
                 ("total_ms", C.c_float), ("bvh_on_device", C.c_uint32), ("layout_on_device", C.c_uint32)]
 
 
+class ptc_frame_plan(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("batch", C.c_int32), ("big_slots", C.c_int32), ("single_slots", C.c_int32),
+                ("staged", C.c_int32)]
+
+
 # every symbol include/ptcore.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -186,6 +191,7 @@ SIGNATURES = {
     "ptc_debug_beam_entries": (C.c_int, [_P, C.POINTER(ptc_camera), C.c_void_p, C.c_uint64]),
     "ptc_debug_persist": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint64]),
     "ptc_check_feed": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "ptc_check_frame_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ptc_frame_plan)]),
     "ptc_selftest_math": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ptc_selftest_rng": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -9,8 +9,9 @@
 //   - path state is ping-ponged between two buffers by the fused shade+compaction kernel instead of
 //     being partitioned in place through a Thrust temporary.
 //
-// This unit: context, frame slots (ptc_resize), parameters, denoise / present / download, statistics.  Scene upload:
-// ptcore_scene.cpp; the launch plan of a batch: ptcore_trace.cpp; the ray queries: ptcore_query.cpp; several GPUs: ptcore_bands.cpp;
+// This unit: context; ptc_resize in stages (refusals, frame_plan, release of the old frame, a ptc_frame_state built beside the
+// context, ONE assignment) and release_frame, the one release path; parameters; denoise; the views (buffer_view / display_view);
+// statistics (each_counter_block).  Scene upload: ptcore_scene.cpp; the launch plan of a batch: ptcore_trace.cpp; the ray queries: ptcore_query.cpp; several GPUs: ptcore_bands.cpp;
 // host-side checks: ptcore_checks.cpp.
 #include "ptcore_ctx.hpp"
 
@@ -113,19 +114,22 @@ int sync_frames(ptc_ctx* ctx)
   return PTC_OK;
 }
 
-void free_slots(ptc_ctx* ctx)
+// The one release path of a frame state (ptc_resize: the old frame, and a new one that did not get to the commit; ptc_destroy).
+// Events that outlive a frame -- gather_ev, the timed launches' -- are the context's and stay.
+void release_frame(ptc_frame_state& f)
 {
-  for (auto& sl : ctx->slots) {
+  for (auto& sl : f.slots) {
     if (sl.own_stream && sl.stream) (void)hipStreamDestroy(sl.stream);
     if (sl.done) (void)hipEventDestroy(sl.done);
     if (sl.live_host) (void)hipHostFree(sl.live_host);
     if (sl.spill) (void)hipFree(sl.spill);
   }
-  ctx->slots.clear();
-  ctx->pending.clear();
-  ctx->held.clear();
-  ctx->active_slot = -1;
-  ctx->est_valid = false;
+  free_pool(f.frame_allocs);
+  for (auto& peer : f.peers)
+    if (peer.opened && peer.mapped) (void)hipIpcCloseMemHandle(peer.mapped);
+  for (void* q : {(void*)f.band_buf, (void*)f.gather_frame, (void*)f.gather_rgba})
+    if (q) (void)hipFree(q);
+  f = ptc_frame_state{};
 }
 
 int frame_ready(ptc_ctx* ctx)
@@ -134,6 +138,32 @@ int frame_ready(ptc_ctx* ctx)
   if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
   if (!ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "ptc_resize first");
   return bind_device(ctx);
+}
+
+int view_ready(ptc_ctx* ctx, const void* arg)
+{
+  if (!ctx || !arg) return PTC_ERR_INVALID;
+  if (!ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "ptc_resize first");
+  return bind_device(ctx);
+}
+
+// the two tables of the views, by ptc_buffer (colour, normal, depth, final) and by ptc_display (final, colour, normal, depth)
+static_assert(PTC_BUF_COLOR == 0 && PTC_BUF_FINAL == 3 && PTC_DISPLAY_FINAL == 0 && PTC_DISPLAY_DEPTH == 3, "the view tables' order");
+int buffer_view(ptc_ctx* ctx, int which, BufferView* out)
+{
+  if (which < PTC_BUF_COLOR || which > PTC_BUF_FINAL) return fail(ctx, PTC_ERR_INVALID, "unknown buffer");
+  const BufferView views[] = {{ctx->fb.color4, 0, 3u}, {ctx->fb.nd4, 0, 3u}, {ctx->fb.nd4, 1, 1u}, {ctx->result, 0, 3u}};
+  *out = views[which];
+  return PTC_OK;
+}
+
+int display_view(ptc_ctx* ctx, int display_type, bool gathered, DisplayView* out)
+{
+  if (display_type < PTC_DISPLAY_FINAL || display_type > PTC_DISPLAY_DEPTH) return fail(ctx, PTC_ERR_INVALID, "unknown display type");
+  // a gathered FINAL shows the accumulated colour: a denoised buffer exists only for a context that owns the whole frame
+  const DisplayView views[] = {{gathered ? PTC_BUF_COLOR : PTC_BUF_FINAL, 0}, {PTC_BUF_COLOR, 0}, {PTC_BUF_NORMAL, 1}, {PTC_BUF_DEPTH, 2}};
+  *out = views[display_type];
+  return PTC_OK;
 }
 
 }  // namespace ptcd
@@ -218,6 +248,122 @@ int set_shade_epoch(ptc_ctx* ctx, int value)
 }
 static_assert(kMaxEpoch == 1073741823u, "the range message of debug_shade_epoch spells the bound out");
 
+// ---- the counter blocks: one DeviceCounters per slot and frame of its batch; their head is everything but the fetch cursors
+constexpr size_t kCountersHead = offsetof(DeviceCounters, work);
+// visit(slot, frame of the slot's batch, the block on the device) for every block, in slot order; stops at the first failure
+template <typename Visit>
+int each_counter_block(ptc_ctx* ctx, Visit visit)
+{
+  for (size_t f = 0; f < ctx->slots.size(); ++f)
+    for (int k = 0; k < ctx->slots[f].capacity; ++k)
+      if (int rc = visit(f, k, ctx->slots[f].counters + k)) return rc;
+  return PTC_OK;
+}
+
+// ... with the block's head on the host: one copy per block
+template <typename Visit>
+int each_counter_head(ptc_ctx* ctx, Visit visit)
+{
+  std::vector<char> buf(sizeof(DeviceCounters));
+  return each_counter_block(ctx, [&](size_t f, int k, const DeviceCounters* dev) -> int {
+    HIP_TRY(ctx, hipMemcpy(buf.data(), dev, kCountersHead, hipMemcpyDeviceToHost));
+    visit(f, k, *reinterpret_cast<const DeviceCounters*>(buf.data()));
+    return PTC_OK;
+  });
+}
+
+// ---- ptc_resize: a frame state in the making, assigned to the context as a whole; released with this struct if it never gets there
+struct NewFrame : ptc_frame_state {
+  ~NewFrame() { release_frame(*this); }
+};
+
+// One slot of `capacity` frames of P pixels: its stream and event, path state, hit records, lists, counters and staging.
+int build_slot(ptc_ctx* ctx, NewFrame& n, ptc_ctx::FrameSlot& sl, int capacity, size_t P)
+{
+  auto& pool = n.frame_allocs;
+  const size_t chunks = (P + kChunk - 1) / kChunk;
+  sl.capacity = capacity;
+  sl.stream = ctx->stream;  // one frame in flight: trace on the context's stream (ptc_set_stream keeps it so)
+  if (n.staged) {
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
+    sl.own_stream = true;
+  }
+  HIP_TRY(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+  HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&sl.live_host), sizeof(uint32_t) * 2 * (kMaxBounces + 1), hipHostMallocDefault));
+  const size_t BP = (size_t)capacity * P;  // frame f of the batch at element offset f * P (DBatchInfo::stride)
+  for (int k = 0; k < 2; ++k) {
+    if (int rc = dev_alloc(ctx, pool, &sl.paths[k].o4, BP)) return rc;
+    if (int rc = dev_alloc(ctx, pool, &sl.paths[k].d4, BP)) return rc;
+    if (int rc = dev_alloc(ctx, pool, &sl.paths[k].t2, BP)) return rc;
+  }
+  if (int rc = dev_alloc(ctx, pool, &sl.hits.tp, BP)) return rc;
+  if (int rc = dev_alloc(ctx, pool, &sl.hits.nm, BP)) return rc;
+  if (ctx->prefold) {
+    if (int rc = dev_alloc(ctx, pool, &sl.hits_other.tp, BP)) return rc;
+    if (int rc = dev_alloc(ctx, pool, &sl.hits_other.nm, BP)) return rc;
+    if (int rc = dev_alloc(ctx, pool, &sl.next_flags, BP)) return rc;
+  }
+  if (int rc = dev_alloc(ctx, pool, &sl.chunk_counts, (size_t)capacity * chunks)) return rc;
+  if (int rc = dev_alloc(ctx, pool, &sl.chunk_offsets, (size_t)capacity * chunks)) return rc;
+  // (tile descriptors: k_shade_fused's 512-slot tiles, or the persistent launch's 128-slot ones)
+  sl.tile_stride = std::max(shade_tiles_per_frame((uint32_t)P), persist_tiles_per_frame((uint32_t)P));
+  if (int rc = dev_alloc(ctx, pool, &sl.tile_desc, (size_t)capacity * sl.tile_stride)) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(sl.tile_desc, 0, sizeof(unsigned long long) * (size_t)capacity * sl.tile_stride, ctx->stream));
+  if (int rc = dev_alloc(ctx, pool, &sl.slow_list, BP)) return rc;
+  if (n.staged) {
+    if (int rc = dev_alloc(ctx, pool, &sl.persist, 1)) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(sl.persist, 0, sizeof(DPersist), ctx->stream));
+  }
+  if (int rc = dev_alloc(ctx, pool, &sl.slow_stack, (size_t)kStackDepth * kWave)) return rc;
+  if (ctx->beam)
+    if (int rc = dev_alloc(ctx, pool, &sl.beam_entries, (size_t)capacity * n.beam_tiles_x * n.beam_tiles_y * 2u * kBeamEntries)) return rc;
+  if (int rc = dev_alloc(ctx, pool, &sl.worklist, BP)) return rc;
+  if (ctx->ray_sort) {
+    if (int rc = dev_alloc(ctx, pool, &sl.octs, BP)) return rc;
+    if (int rc = dev_alloc(ctx, pool, &sl.order, BP)) return rc;
+  }
+  if (int rc = dev_alloc(ctx, pool, &sl.counters, (size_t)capacity)) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(sl.counters, 0, sizeof(DeviceCounters) * (size_t)capacity, ctx->stream));
+  sl.bi.stride = (uint32_t)P;
+  sl.bi.chunk_stride = (uint32_t)chunks;
+  sl.bi.count = 1u;
+  sl.stage = n.fb;  // one frame in flight: shade accumulates straight into the framebuffers
+  if (n.staged) {
+    if (int rc = dev_alloc(ctx, pool, &sl.stage.color4, BP)) return rc;
+    if (int rc = dev_alloc(ctx, pool, &sl.stage.nd4, BP)) return rc;
+  }
+  return PTC_OK;
+}
+
+// The frame state of a width x height frame under `plan`, into n: nothing of the context is assigned here.
+int build_frame(ptc_ctx* ctx, uint32_t width, uint32_t height, const ptc_frame_plan& plan, NewFrame& n)
+{
+  const size_t P = (size_t)width * height;
+  auto& pool = n.frame_allocs;
+  n.batch = plan.batch;
+  n.staged = plan.staged != 0;
+  n.big_slots = plan.big_slots;
+  n.beam_tiles_x = (width + kBeamTile - 1u) / kBeamTile;  // ("beam": the slots' entry points)
+  n.beam_tiles_y = (height + kBeamTile - 1u) / kBeamTile;
+  if (int rc = dev_alloc(ctx, pool, &n.fb.color4, P)) return rc;
+  if (int rc = dev_alloc(ctx, pool, &n.fb.nd4, P)) return rc;
+  n.slots.resize((size_t)(plan.big_slots + plan.single_slots));
+  for (int f = 0; f < (int)n.slots.size(); ++f)
+    if (int rc = build_slot(ctx, n, n.slots[(size_t)f], f < plan.big_slots ? plan.batch : 1, P)) return rc;
+  for (float4** q : {&n.den_a, &n.den_b, &n.den_pos})
+    if (int rc = dev_alloc(ctx, pool, q, P)) return rc;
+  if (int rc = dev_alloc(ctx, pool, &n.pack_buf, P * 3u)) return rc;
+  if (int rc = dev_alloc(ctx, pool, &n.rgba_buf, P)) return rc;
+  for (float4* q : {n.fb.color4, n.fb.nd4, n.den_a, n.den_b}) HIP_TRY(ctx, hipMemsetAsync(q, 0, P * sizeof(float4), ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  n.width = width;
+  n.height = height;
+  n.band = DBand{0u, width, 0u, 1u, 0u};
+  n.pix_count = n.pix_capacity = (uint32_t)P;
+  n.result = n.fb.color4;
+  return PTC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -296,9 +442,8 @@ void ptc_destroy(ptc_ctx* ctx)
   for (auto& sl : ctx->slots)
     if (sl.stream) (void)hipStreamSynchronize(sl.stream);
   if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
-  free_slots(ctx);
+  release_frame(*ctx);
   free_pool(ctx->scene_allocs);
-  free_pool(ctx->frame_allocs);
   for (auto& tl : ctx->timed) {
     (void)hipEventDestroy(tl.start);
     (void)hipEventDestroy(tl.stop);
@@ -309,10 +454,7 @@ void ptc_destroy(ptc_ctx* ctx)
   if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
   if (ctx->main_event) (void)hipEventDestroy(ctx->main_event);
   if (ctx->xstream_event) (void)hipEventDestroy(ctx->xstream_event);
-  for (auto& peer : ctx->peers)
-    if (peer.opened && peer.mapped) (void)hipIpcCloseMemHandle(peer.mapped);
-  for (void* q : {(void*)ctx->band_buf, (void*)ctx->gather_frame, (void*)ctx->gather_rgba, (void*)ctx->slot_offset_dev})
-    if (q) (void)hipFree(q);
+  if (ctx->slot_offset_dev) (void)hipFree(ctx->slot_offset_dev);
   for (hipEvent_t e : ctx->gather_ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->misc_counters) (void)hipFree(ctx->misc_counters);
@@ -332,135 +474,21 @@ int ptc_set_stream(ptc_ctx* ctx, void* hip_stream)
 
 int ptc_resize(ptc_ctx* ctx, uint32_t width, uint32_t height)
 {
+  // ---- refusals: the frame the context has stays as it is
   if (!ctx || width < 2u || height < 2u) return fail(ctx, PTC_ERR_INVALID, "resolution must be at least 2x2");
   if ((uint64_t)width * height > 0x7fffffffull) return fail(ctx, PTC_ERR_INVALID, "too many pixels");
   if (int rc = bind_device(ctx)) return rc;
+  // ---- the plan
+  const ptc_frame_plan plan = frame_plan(width, height, ctx->frames_in_flight, ctx->frames_auto, ctx->batch_frames, ctx->prefold);
+  // ---- the old frame goes before the new one's allocations: its memory is needed.  Iterations queued or in flight were asked
+  // for at its size: trace them first.  From here to the commit the context holds no frame, and a failure leaves it so (~NewFrame)
   if (int rc = sync_frames(ctx)) return rc;
-  free_slots(ctx);
-  free_pool(ctx->frame_allocs);
-  // nothing below is usable until this call has succeeded (frame_ready / ptc_download / ptc_present check these)
-  ctx->pix_capacity = ctx->pix_count = 0;
-  ctx->width = ctx->height = 0;
-  ctx->fb = DFrame{};
-  ctx->den_a = ctx->den_b = ctx->den_pos = nullptr;
-  ctx->result = nullptr;
-  ctx->pack_buf = nullptr;
-  ctx->rgba_buf = nullptr;
-  ctx->have_cam = false;
-  // band / gather buffers belong to the old frame size (an exported handle dies with its buffer: export again)
-  for (auto& peer : ctx->peers)
-    if (peer.opened && peer.mapped) (void)hipIpcCloseMemHandle(peer.mapped);
-  ctx->peers.clear();
-  for (float** q : {&ctx->band_buf, &ctx->gather_frame}) {
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-  }
-  if (ctx->gather_rgba) (void)hipFree(ctx->gather_rgba);
-  ctx->gather_rgba = nullptr;
-  ctx->gather_timed = false;
-  const size_t P = (size_t)width * height;
-  auto& pool = ctx->frame_allocs;
-  const size_t chunks = (P + kChunk - 1) / kChunk;
-  int frames = std::max(1, ctx->frames_in_flight);
-  if (ctx->frames_auto) {
-    // path state, hit records (two sets with "prefold"), staging: 148 (181) bytes per pixel and frame in flight
-    const uint64_t per_frame = (ctx->prefold ? 181ull : 148ull) * P;
-    frames = (int)std::min<uint64_t>((uint64_t)frames, std::max<uint64_t>(1ull, kAutoFrameBytes / per_frame));
-  }
-  const int B = std::min({std::max(1, ctx->batch_frames), frames, kMaxBatch});
-  if (ctx->frames_auto) frames -= frames % B;
-  const int F = (frames + B - 1) / B;  // slots (streams); each holds a batch of B frames
-  ctx->batch = B;
-  ctx->staged = frames > 1;
-  ctx->batches_issued = 0;
-  ctx->singles_issued = 0;
-  ctx->big_slots = F;
-  const int singles = (ctx->staged && B > 1) ? 8 : 0;
-  ctx->slots.resize((size_t)(F + singles));
-  if (int rc = dev_alloc(ctx, pool, &ctx->fb.color4, P)) return rc;
-  if (int rc = dev_alloc(ctx, pool, &ctx->fb.nd4, P)) return rc;
-  for (int f = 0; f < F + singles; ++f) {
-    auto& sl = ctx->slots[(size_t)f];
-    const int B = f < F ? ctx->batch : 1;  // this slot's capacity (shadows the batch size above)
-    sl.capacity = B;
-    if (!ctx->staged) {
-      sl.stream = ctx->stream;
-      sl.own_stream = false;
-    } else {
-      HIP_TRY(ctx, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-      sl.own_stream = true;
-    }
-    HIP_TRY(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&sl.live_host), sizeof(uint32_t) * 2 * (kMaxBounces + 1), hipHostMallocDefault));
-    const size_t BP = (size_t)B * P;  // frame f of the batch at element offset f * P (DBatchInfo::stride)
-    for (int k = 0; k < 2; ++k) {
-      if (int rc = dev_alloc(ctx, pool, &sl.paths[k].o4, BP)) return rc;
-      if (int rc = dev_alloc(ctx, pool, &sl.paths[k].d4, BP)) return rc;
-      if (int rc = dev_alloc(ctx, pool, &sl.paths[k].t2, BP)) return rc;
-    }
-    if (int rc = dev_alloc(ctx, pool, &sl.hits.tp, BP)) return rc;
-    if (int rc = dev_alloc(ctx, pool, &sl.hits.nm, BP)) return rc;
-    if (ctx->prefold) {
-      if (int rc = dev_alloc(ctx, pool, &sl.hits_other.tp, BP)) return rc;
-      if (int rc = dev_alloc(ctx, pool, &sl.hits_other.nm, BP)) return rc;
-      if (int rc = dev_alloc(ctx, pool, &sl.next_flags, BP)) return rc;
-    }
-    sl.prefolded = false;
-    if (int rc = dev_alloc(ctx, pool, &sl.chunk_counts, (size_t)B * chunks)) return rc;
-    if (int rc = dev_alloc(ctx, pool, &sl.chunk_offsets, (size_t)B * chunks)) return rc;
-    // (tile descriptors: k_shade_fused's 512-slot tiles, or the persistent launch's 128-slot ones)
-    sl.tile_stride = std::max(shade_tiles_per_frame((uint32_t)P), persist_tiles_per_frame((uint32_t)P));
-    if (int rc = dev_alloc(ctx, pool, &sl.tile_desc, (size_t)B * sl.tile_stride)) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(sl.tile_desc, 0, sizeof(unsigned long long) * (size_t)B * sl.tile_stride, ctx->stream));
-    sl.shade_epoch = 0;
-    if (int rc = dev_alloc(ctx, pool, &sl.slow_list, BP)) return rc;
-    if (ctx->staged) {
-      if (int rc = dev_alloc(ctx, pool, &sl.persist, 1)) return rc;
-      HIP_TRY(ctx, hipMemsetAsync(sl.persist, 0, sizeof(DPersist), ctx->stream));
-    }
-    if (int rc = dev_alloc(ctx, pool, &sl.slow_stack, (size_t)kStackDepth * kWave)) return rc;
-    if (ctx->beam) {
-      ctx->beam_tiles_x = (width + kBeamTile - 1u) / kBeamTile;    // (ctx->width is set when everything has been allocated)
-      ctx->beam_tiles_y = (height + kBeamTile - 1u) / kBeamTile;
-      if (int rc = dev_alloc(ctx, pool, &sl.beam_entries, (size_t)B * ctx->beam_tiles_x * ctx->beam_tiles_y * 2u * kBeamEntries)) return rc;
-    }
-    if (int rc = dev_alloc(ctx, pool, &sl.worklist, BP)) return rc;
-    if (ctx->ray_sort) {
-      if (int rc = dev_alloc(ctx, pool, &sl.octs, BP)) return rc;
-      if (int rc = dev_alloc(ctx, pool, &sl.order, BP)) return rc;
-    }
-    if (int rc = dev_alloc(ctx, pool, &sl.counters, (size_t)B)) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(sl.counters, 0, sizeof(DeviceCounters) * (size_t)B, ctx->stream));
-    sl.bi = DBatchInfo{};
-    sl.bi.stride = (uint32_t)P;
-    sl.bi.chunk_stride = (uint32_t)chunks;
-    sl.bi.count = 1u;
-    if (!ctx->staged) {
-      sl.stage = ctx->fb;  // shade accumulates straight into the framebuffers
-    } else {
-      if (int rc = dev_alloc(ctx, pool, &sl.stage.color4, BP)) return rc;
-      if (int rc = dev_alloc(ctx, pool, &sl.stage.nd4, BP)) return rc;
-    }
-  }
-  if (int rc = dev_alloc(ctx, pool, &ctx->den_a, P)) return rc;
-  if (int rc = dev_alloc(ctx, pool, &ctx->den_b, P)) return rc;
-  if (int rc = dev_alloc(ctx, pool, &ctx->den_pos, P)) return rc;
-  if (int rc = dev_alloc(ctx, pool, &ctx->pack_buf, P * 3u)) return rc;
-  if (int rc = dev_alloc(ctx, pool, &ctx->rgba_buf, P)) return rc;
-  HIP_TRY(ctx, hipMemsetAsync(ctx->fb.color4, 0, P * sizeof(float4), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->fb.nd4, 0, P * sizeof(float4), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->den_a, 0, P * sizeof(float4), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->den_b, 0, P * sizeof(float4), ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->width = width;
-  ctx->height = height;
-  ctx->pix_begin = 0;
-  ctx->band = DBand{0u, width, 0u, 1u, 0u};
-  ctx->pix_count = (uint32_t)P;
-  ctx->pix_capacity = (uint32_t)P;
-  ctx->result = ctx->fb.color4;
-  ctx->have_cam = false;
-  ctx->last_slot = 0;
+  release_frame(*ctx);
+  // ---- the new frame, beside the context
+  NewFrame n;
+  if (int rc = build_frame(ctx, width, height, plan, n)) return rc;
+  // ---- the commit: nothing above assigned a frame field of the context, nothing below can fail
+  std::swap(static_cast<ptc_frame_state&>(*ctx), static_cast<ptc_frame_state&>(n));
   return ptc_restart(ctx);
 }
 
@@ -590,22 +618,15 @@ int ptc_denoise(ptc_ctx* ctx)
 
 int ptc_present_rgba8(ptc_ctx* ctx, void* dst, int dst_is_device, int display_type)
 {
-  if (!ctx || !dst) return PTC_ERR_INVALID;
-  if (!ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "ptc_resize first");
-  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = view_ready(ctx, dst)) return rc;
   if (int rc = flush_pending(ctx)) return rc;
-  const float4* src = nullptr;
-  int mode = 0;
-  switch (display_type) {
-  case PTC_DISPLAY_FINAL: src = ctx->result; break;
-  case PTC_DISPLAY_COLOR: src = ctx->fb.color4; break;
-  case PTC_DISPLAY_NORMAL: src = ctx->fb.nd4; mode = 1; break;
-  case PTC_DISPLAY_DEPTH: src = ctx->fb.nd4; mode = 2; break;
-  default: return fail(ctx, PTC_ERR_INVALID, "unknown display type");
-  }
+  DisplayView show;
+  BufferView view;
+  if (int rc = display_view(ctx, display_type, false, &show)) return rc;
+  if (int rc = buffer_view(ctx, show.which, &view)) return rc;
   if (int rc = sync_frames(ctx)) return rc;
   uint32_t* out = dst_is_device ? static_cast<uint32_t*>(dst) : ctx->rgba_buf;
-  launch_preview(ctx->stream, src, ctx->pix_count, mode, out);
+  launch_preview(ctx->stream, view.src, ctx->pix_count, show.mode, out);
   if (int rc = check_last(ctx, "preview")) return rc;
   if (!dst_is_device)
     HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rgba_buf, (size_t)ctx->pix_count * 4u, hipMemcpyDeviceToHost, ctx->stream));
@@ -615,24 +636,15 @@ int ptc_present_rgba8(ptc_ctx* ctx, void* dst, int dst_is_device, int display_ty
 
 int ptc_download(ptc_ctx* ctx, int which, void* dst, int dst_is_device)
 {
-  if (!ctx || !dst) return PTC_ERR_INVALID;
-  if (!ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "ptc_resize first");
-  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = view_ready(ctx, dst)) return rc;
   if (int rc = flush_pending(ctx)) return rc;
-  const float4* src = nullptr;
-  int sel = 0;
-  size_t floats = (size_t)ctx->pix_count * 3u;
-  switch (which) {
-  case PTC_BUF_COLOR: src = ctx->fb.color4; break;
-  case PTC_BUF_NORMAL: src = ctx->fb.nd4; break;
-  case PTC_BUF_DEPTH: src = ctx->fb.nd4; sel = 1; floats = ctx->pix_count; break;
-  case PTC_BUF_FINAL: src = ctx->result; break;
-  default: return fail(ctx, PTC_ERR_INVALID, "unknown buffer");
-  }
+  BufferView view;
+  if (int rc = buffer_view(ctx, which, &view)) return rc;
   if (int rc = sync_frames(ctx)) return rc;
   float* out = dst_is_device ? static_cast<float*>(dst) : ctx->pack_buf;
-  launch_pack(ctx->stream, src, ctx->pix_count, sel, out);
+  launch_pack(ctx->stream, view.src, ctx->pix_count, view.sel, out);
   if (int rc = check_last(ctx, "pack")) return rc;
+  const size_t floats = (size_t)ctx->pix_count * view.floats_per_pixel;
   if (!dst_is_device) HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->pack_buf, floats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return PTC_OK;
@@ -652,18 +664,15 @@ int ptc_get_stats(ptc_ctx* ctx, ptc_stats* out)
   if (int rc = sync_frames(ctx)) return rc;
   std::memset(out, 0, sizeof *out);
   uint32_t flags = 0;
-  const size_t head = offsetof(DeviceCounters, work);  // everything but the fetch cursors
+  if (int rc = each_counter_head(ctx, [&](size_t f, int k, const DeviceCounters& host) {
+        out->rays_total += host.rays_total;
+        flags |= host.flags;
+        if ((int)f == ctx->last_slot && k + 1 == (int)ctx->slots[f].bi.count)
+          for (int i = 0; i < PTC_MAX_BOUNCES_CAP; ++i) out->last_live[i] = i < ctx->max_bounces ? host.live[i] : 0u;
+      }))
+    return rc;
   std::vector<char> buf(sizeof(DeviceCounters));
-  for (size_t f = 0; f < ctx->slots.size(); ++f)
-    for (int k = 0; k < ctx->slots[f].capacity; ++k) {
-      HIP_TRY(ctx, hipMemcpy(buf.data(), ctx->slots[f].counters + k, head, hipMemcpyDeviceToHost));
-      const DeviceCounters& host = *reinterpret_cast<const DeviceCounters*>(buf.data());
-      out->rays_total += host.rays_total;
-      flags |= host.flags;
-      if ((int)f == ctx->last_slot && k + 1 == (int)ctx->slots[f].bi.count)
-        for (int i = 0; i < PTC_MAX_BOUNCES_CAP; ++i) out->last_live[i] = i < ctx->max_bounces ? host.live[i] : 0u;
-    }
-  HIP_TRY(ctx, hipMemcpy(buf.data(), ctx->misc_counters, head, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(buf.data(), ctx->misc_counters, kCountersHead, hipMemcpyDeviceToHost));
   flags |= reinterpret_cast<const DeviceCounters*>(buf.data())->flags;
   out->frames = ctx->frames;
   out->bvh_node_count = ctx->bvh_nodes;
@@ -721,11 +730,11 @@ int ptc_reset_profile(ptc_ctx* ctx)
   ctx->intersect_redone = 0;
   ctx->occlusion = ptc_occlusion_stats{};
   ctx->direct = ptc_direct_stats{};
-  const size_t off = offsetof(DeviceCounters, paths), end = offsetof(DeviceCounters, work);
-  for (auto& sl : ctx->slots)
-    for (int k = 0; k < sl.capacity; ++k)
-      HIP_TRY(ctx, hipMemset(reinterpret_cast<char*>(sl.counters + k) + off, 0, end - off));
-  return PTC_OK;
+  const size_t off = offsetof(DeviceCounters, paths);  // the profile counters: from `paths` to the end of the head
+  return each_counter_block(ctx, [&](size_t, int, DeviceCounters* dev) -> int {
+    HIP_TRY(ctx, hipMemset(reinterpret_cast<char*>(dev) + off, 0, kCountersHead - off));
+    return PTC_OK;
+  });
 }
 
 int ptc_get_profile(ptc_ctx* ctx, ptc_profile* out)
@@ -735,22 +744,18 @@ int ptc_get_profile(ptc_ctx* ctx, ptc_profile* out)
   if (int rc = sync_frames(ctx)) return rc;
   if (int rc = drain_timed(ctx)) return rc;
   std::memset(out, 0, sizeof *out);
-  const size_t head = offsetof(DeviceCounters, work);
-  std::vector<char> buf(sizeof(DeviceCounters));
-  for (auto& sl : ctx->slots)
-    for (int k = 0; k < sl.capacity; ++k) {
-    HIP_TRY(ctx, hipMemcpy(buf.data(), sl.counters + k, head, hipMemcpyDeviceToHost));
-    const DeviceCounters& host = *reinterpret_cast<const DeviceCounters*>(buf.data());
-    for (int b = 0; b < PTC_MAX_BOUNCES_CAP; ++b) {
-      out->paths[b] += host.paths[b];
-      out->box_tests[b] += host.box_tests[b];
-      out->tri_tests[b] += host.tri_tests[b];
-      out->max_box_tests[b] = std::max(out->max_box_tests[b], host.max_box_tests[b]);
-      out->listed_rays[b] += host.listed_rays[b];
-      out->slow_rays[b] += host.slow_rays[b];
-      out->node_visits[b] += host.node_visits[b];
-    }
-  }
+  if (int rc = each_counter_head(ctx, [&](size_t, int, const DeviceCounters& host) {
+        for (int b = 0; b < PTC_MAX_BOUNCES_CAP; ++b) {
+          out->paths[b] += host.paths[b];
+          out->box_tests[b] += host.box_tests[b];
+          out->tri_tests[b] += host.tri_tests[b];
+          out->max_box_tests[b] = std::max(out->max_box_tests[b], host.max_box_tests[b]);
+          out->listed_rays[b] += host.listed_rays[b];
+          out->slow_rays[b] += host.slow_rays[b];
+          out->node_visits[b] += host.node_visits[b];
+        }
+      }))
+    return rc;
   for (int b = 0; b < PTC_MAX_BOUNCES_CAP; ++b) {
     out->trace_ms[b] = ctx->trace_ms[b];
     out->trace_launches[b] = ctx->trace_launches[b];

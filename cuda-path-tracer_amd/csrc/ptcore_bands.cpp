@@ -36,28 +36,16 @@ int ptc_set_interleave(ptc_ctx* ctx, uint32_t rank, uint32_t nranks, uint32_t bl
 }
 
 // ---- several GPUs: bands over HIP inter-process memory (include/ptcore.h) -------------------------------------------
-static int band_pack(ptc_ctx* ctx, int which, float* dst, size_t* floats)
+static int band_pack(ptc_ctx* ctx, const BufferView& view, float* dst)
 {
-  const float4* src = nullptr;
-  int sel = 0;
-  *floats = (size_t)ctx->pix_count * 3u;
-  switch (which) {
-  case PTC_BUF_COLOR: src = ctx->fb.color4; break;
-  case PTC_BUF_NORMAL: src = ctx->fb.nd4; break;
-  case PTC_BUF_DEPTH: src = ctx->fb.nd4; sel = 1; *floats = ctx->pix_count; break;
-  case PTC_BUF_FINAL: src = ctx->result; break;
-  default: return fail(ctx, PTC_ERR_INVALID, "unknown buffer");
-  }
   if (int rc = sync_frames(ctx)) return rc;
-  launch_pack(ctx->stream, src, ctx->pix_count, sel, dst);
+  launch_pack(ctx->stream, view.src, ctx->pix_count, view.sel, dst);
   return check_last(ctx, "pack");
 }
 
 int ptc_band_export(ptc_ctx* ctx, ptc_band_handle* out)
 {
-  if (!ctx || !out) return PTC_ERR_INVALID;
-  if (!ctx->pix_capacity) return fail(ctx, PTC_ERR_INVALID, "ptc_resize first");
-  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = view_ready(ctx, out)) return rc;
   if (!ctx->band_buf) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->band_buf), (size_t)ctx->pix_capacity * 3u * sizeof(float)));
   std::memset(out, 0, sizeof *out);
   hipIpcMemHandle_t h;
@@ -112,13 +100,14 @@ int ptc_band_publish(ptc_ctx* ctx, int which)
   if (!ctx) return PTC_ERR_INVALID;
   if (!ctx->band_buf) return fail(ctx, PTC_ERR_INVALID, "ptc_band_export first");
   if (int rc = bind_device(ctx)) return rc;
-  size_t floats = 0;
-  if (int rc = band_pack(ctx, which, ctx->band_buf, &floats)) return rc;
+  BufferView view;
+  if (int rc = buffer_view(ctx, which, &view)) return rc;
+  if (int rc = band_pack(ctx, view, ctx->band_buf)) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the rows are in the exported buffer when this returns
   return PTC_OK;
 }
 
-static int gather_rows(ptc_ctx* root, int which, int channels)
+static int gather_rows(ptc_ctx* root, const BufferView& view)
 {
   const size_t P = (size_t)root->width * root->height;
   if (!root->gather_frame) HIP_TRY(root, hipMalloc(reinterpret_cast<void**>(&root->gather_frame), P * 3u * sizeof(float)));
@@ -128,15 +117,14 @@ static int gather_rows(ptc_ctx* root, int which, int channels)
     HIP_TRY(root, hipEventCreate(&root->gather_ev[1]));
   }
   // the root's own rows, packed like a peer's
-  size_t floats = 0;
-  if (int rc = band_pack(root, which, root->band_buf, &floats)) return rc;
+  if (int rc = band_pack(root, view, root->band_buf)) return rc;
   // One launch pulls every band -- the root's own and every imported rank's, straight out of the peers' mapped
   // buffers -- into row order: all peer -> root xGMI links carry their band at the same time, nothing is staged.
   HIP_TRY(root, hipEventRecord(root->gather_ev[0], root->stream));
   DGatherBands bands{};
   uint32_t n = 0, max_pix = 0;
   auto flush = [&]() {
-    if (n) launch_gather_bands(root->stream, bands, n, max_pix, channels, (uint32_t)P, root->gather_frame);
+    if (n) launch_gather_bands(root->stream, bands, n, max_pix, (int)view.floats_per_pixel, (uint32_t)P, root->gather_frame);
     n = 0;
     max_pix = 0;
   };
@@ -175,13 +163,11 @@ int ptc_gather_last_us(ptc_ctx* root, float* microseconds)
 
 int ptc_gather_frame(ptc_ctx* root, int which, void* dst, int dst_is_device)
 {
-  if (!root || !dst) return PTC_ERR_INVALID;
-  if (!root->pix_capacity) return fail(root, PTC_ERR_INVALID, "ptc_resize first");
-  if (which < PTC_BUF_COLOR || which > PTC_BUF_FINAL) return fail(root, PTC_ERR_INVALID, "unknown buffer");
-  if (int rc = bind_device(root)) return rc;
-  const int channels = which == PTC_BUF_DEPTH ? 1 : 3;
-  if (int rc = gather_rows(root, which, channels)) return rc;
-  const size_t bytes = (size_t)root->width * root->height * (size_t)channels * sizeof(float);
+  if (int rc = view_ready(root, dst)) return rc;
+  BufferView view;
+  if (int rc = buffer_view(root, which, &view)) return rc;
+  if (int rc = gather_rows(root, view)) return rc;
+  const size_t bytes = (size_t)root->width * root->height * view.floats_per_pixel * sizeof(float);
   HIP_TRY(root, hipMemcpyAsync(dst, root->gather_frame, bytes, dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, root->stream));
   HIP_TRY(root, hipStreamSynchronize(root->stream));
   return PTC_OK;
@@ -189,23 +175,16 @@ int ptc_gather_frame(ptc_ctx* root, int which, void* dst, int dst_is_device)
 
 int ptc_gather_present_rgba8(ptc_ctx* root, void* dst, int dst_is_device, int display_type)
 {
-  if (!root || !dst) return PTC_ERR_INVALID;
-  if (!root->pix_capacity) return fail(root, PTC_ERR_INVALID, "ptc_resize first");
-  if (int rc = bind_device(root)) return rc;
-  int which = PTC_BUF_COLOR, mode = 0;
-  switch (display_type) {
-  case PTC_DISPLAY_FINAL:
-  case PTC_DISPLAY_COLOR: break;
-  case PTC_DISPLAY_NORMAL: which = PTC_BUF_NORMAL; mode = 1; break;
-  case PTC_DISPLAY_DEPTH: which = PTC_BUF_DEPTH; mode = 2; break;
-  default: return fail(root, PTC_ERR_INVALID, "unknown display type");
-  }
-  const int channels = which == PTC_BUF_DEPTH ? 1 : 3;
-  if (int rc = gather_rows(root, which, channels)) return rc;
+  if (int rc = view_ready(root, dst)) return rc;
+  DisplayView show;
+  BufferView view;
+  if (int rc = display_view(root, display_type, true, &show)) return rc;
+  if (int rc = buffer_view(root, show.which, &view)) return rc;
+  if (int rc = gather_rows(root, view)) return rc;
   const uint32_t P = root->width * root->height;
   if (!root->gather_rgba) HIP_TRY(root, hipMalloc(reinterpret_cast<void**>(&root->gather_rgba), (size_t)P * 4u));
   uint32_t* out = dst_is_device ? static_cast<uint32_t*>(dst) : root->gather_rgba;
-  launch_preview_packed(root->stream, root->gather_frame, P, channels, mode, out);
+  launch_preview_packed(root->stream, root->gather_frame, P, (int)view.floats_per_pixel, show.mode, out);
   if (int rc = check_last(root, "preview")) return rc;
   if (!dst_is_device) HIP_TRY(root, hipMemcpyAsync(dst, root->gather_rgba, (size_t)P * 4u, hipMemcpyDeviceToHost, root->stream));
   HIP_TRY(root, hipStreamSynchronize(root->stream));

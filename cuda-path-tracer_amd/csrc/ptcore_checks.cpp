@@ -197,6 +197,15 @@ int ptc_check_feed(uint32_t n, uint32_t static_eighths, uint32_t dyn_batch)
   return bad;
 }
 
+// frame_plan (ptcore_ctx.hpp), the sizing rule ptc_resize follows, for the resolutions ptc_resize accepts.
+int ptc_check_frame_plan(uint32_t width, uint32_t height, int frames_in_flight, int frames_auto, int batch_frames, int prefold,
+                         ptc_frame_plan* out)
+{
+  if (!out || width < 2u || height < 2u || (uint64_t)width * height > 0x7fffffffull) return PTC_ERR_INVALID;
+  *out = frame_plan(width, height, frames_in_flight, frames_auto != 0, batch_frames, prefold != 0);
+  return PTC_OK;
+}
+
 // Test hook: the entries k_beam computes on the GPU for the uploaded scene's first traversal launch (its mesh object) and
 // `camera` at the context's resolution, [tiles][4][8 floats] as ptc_check_beam lays them out.
 int ptc_debug_beam_entries(ptc_ctx* ctx, const ptc_camera* camera, float* entries_out, uint64_t capacity_floats)

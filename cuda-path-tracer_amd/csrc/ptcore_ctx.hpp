@@ -1,5 +1,6 @@
 // ptcore_ctx.hpp -- private to libptcore.so: the context behind include/ptcore.h and the helpers its translation units share
-// (ptcore.cpp: context, frame slots, the parameter table, timed launches, views; ptcore_scene.cpp: scene upload in stages -- refusals and
+// (ptcore.cpp: context, ptc_resize in stages -- refusals, the sizing plan, the old frame's release, a ptc_frame_state built beside the
+// context, one assignment --, the parameter table, timed launches, views; ptcore_scene.cpp: scene upload in stages -- refusals and
 // host preparation while the old scene stands, its release, device work, one assignment of ptc_scene_state; ptcore_trace.cpp: the launch plan of a
 // batch of frames; ptcore_query.cpp: the ray queries outside the render loop; ptcore_bands.cpp: several GPUs; ptcore_checks.cpp:
 // host-side checks of the schedule helpers).
@@ -26,6 +27,7 @@
 #include "pt_host.hpp"
 #include "pt_beam_rules.hpp"
 #include "pt_feed_rules.hpp"
+#include "pt_frame_rules.hpp"
 
 using namespace pt;
 
@@ -71,20 +73,15 @@ struct ptc_scene_state {
 // the last epoch of a lap of look-back launches on a slot's tile descriptors (30 bits: pt_shade_tile.inc; ptcore_trace.cpp, next_epoch)
 constexpr uint32_t kMaxEpoch = 0x3fffffffu;
 
-// in-flight path state a context allocates when the caller has not chosen frames_in_flight
-constexpr uint64_t kAutoFrameBytes = 24ull << 30;
-
-struct ptc_ctx : ptc_scene_state {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  std::string err;
-
-  // frame
+// Everything of a context that a ptc_resize decides or that dies with it.  ptc_resize (ptcore.cpp) builds one of these beside the
+// context and assigns it as a whole, after the last step that can fail; a value-initialised one is the state "no frame"
+// (pix_capacity 0: "ptc_resize first" from every entry point); release_frame gives back what one owns.  A field that depends on
+// the frame size belongs here.
+struct ptc_frame_state {
   uint32_t width = 0, height = 0;
   uint32_t pix_begin = 0, pix_count = 0, pix_capacity = 0;
   DBand band{0, 0, 0, 1, 0};
-  std::vector<void*> frame_allocs;
+  std::vector<void*> frame_allocs;  // every device array of the frame but the slots' spill areas and the band / gather buffers
   // Frames in flight: consecutive iterations are independent until they are folded into the framebuffer, and
   // the tail of every bounce is a handful of long rays (latency-bound), so iteration i runs on stream i % F
   // with its own path state and staging buffers; k_accumulate folds the staged samples in iteration order.
@@ -116,7 +113,7 @@ struct ptc_ctx : ptc_scene_state {
     bool primary_finished = false;  // ... and finished the others itself: bounce 0's shade walks the list (launch_raygen)
     bool first_listed = false;      // ... k_raygen has listed the rays of bounce 0's first traversal launch (this batch)
     uint32_t* worklist = nullptr;   // "filter_rays": the rays of the next traversal launch that may hit one of its objects (k_spheres)
-    uint2* spill = nullptr;         // traversal stack overflow area of this slot's launches (DScene::spill)
+    uint2* spill = nullptr;         // traversal stack overflow area of this slot's launches (DScene::spill); grown by batch_begin, not in the pool
     size_t spill_elems = 0;
     DFrame stage{};
     DeviceCounters* counters = nullptr;  // one per frame of the batch
@@ -129,14 +126,60 @@ struct ptc_ctx : ptc_scene_state {
     DBatchInfo bi{};            // the batch being traced / traced last
     int capacity = 1;           // frames the slot's arrays hold
   };
+  // Slots [0, big_slots) hold `batch` frames each; slots [big_slots, slots.size()) hold ONE frame: a batch of a
+  // single iteration (a viewer that presents after every iteration, the stepwise calls) goes to one of those, so
+  // that many such launches can be in flight on their own streams without the memory of full-size slots.
   std::vector<FrameSlot> slots;
-  int frames_in_flight = 64;
-  bool frames_auto = true;  // not set by the caller: ptc_resize caps it so that the in-flight state stays under kAutoFrameBytes
   // Batches: up to `batch` consecutive iterations share the launches of a slot (DBatchInfo).  ptc_trace only
   // queues the iteration; the batch is enqueued when it is full or when anything else looks at the context.
-  int batch_frames = 32;  // requested (ptc_set_param, before ptc_resize)
-  int batch = 1;          // allocated per slot
+  int batch = 1;          // allocated per big slot (frame_plan)
   bool staged = false;    // samples go through staging buffers and k_accumulate
+  int big_slots = 0;
+  uint32_t beam_tiles_x = 0, beam_tiles_y = 0;
+  uint64_t batches_issued = 0, singles_issued = 0;  // round robin over the big and the single-frame slots
+  int active_slot = -1;          // slot of the frame being built by ptc_trace_begin/bounce/end
+  int last_slot = 0;             // slot of the most recent finished frame
+  // live paths entering each bounce of one recent frame (what a frame of this scene / camera looks like): the host
+  // never waits for them, they only size the traversal launches
+  uint32_t est_live[2 * (kMaxBounces + 1)] = {};  // live[], then listed_now[] (DeviceCounters) of a recent batch's first frame
+  bool est_valid = false;
+  DFrame fb{};
+  float4* den_a = nullptr;
+  float4* den_b = nullptr;
+  float4* den_pos = nullptr;     // per-pixel view-space hit position of the accumulated depth (denoiser)
+  const float4* result = nullptr;
+  float* pack_buf = nullptr;     // 3 floats / pixel staging for downloads
+  uint32_t* rgba_buf = nullptr;  // staging for host presents
+  DCamera cam{};                 // of the last traced frame, made for this width and height (ptc_denoise reuses it)
+  bool have_cam = false;
+  // several GPUs (ptc_band_*): this rank's exported band buffer (its handle dies with it: export again after a resize), and on
+  // the root the peers' mapped buffers
+  float* band_buf = nullptr;                // 3 floats per pixel of pix_capacity
+  struct Peer {
+    void* mapped = nullptr;                 // hipIpcOpenMemHandle of the peer process's band buffer
+    bool opened = false;
+    ptc_band_handle h{};
+  };
+  std::vector<Peer> peers;                  // by rank
+  float* gather_frame = nullptr;            // root: the whole frame, 3 floats per pixel
+  uint32_t* gather_rgba = nullptr;
+  bool gather_timed = false;                // a gather of this frame has run (the events around it are the context's: gather_ev)
+};
+
+// What serves the frames and still stays here: the queue (pending, held) -- sync_frames traces what is queued, so it is empty
+// whenever a frame state is released or assigned; active_slot indexes `slots` and est_live counts paths of a frame of this size,
+// so those two are frame state -- and every event (order / main / xstream, turn_event, gather_ev, the timed launches'): created
+// once, reused across resizes.  order_valid / main_valid are cleared by sync_frames.
+struct ptc_ctx : ptc_scene_state, ptc_frame_state {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  std::string err;
+
+  // what the caller asked for (ptc_set_param, before ptc_resize): frame_plan turns it into ptc_frame_state's batch / slots
+  int frames_in_flight = 64;
+  bool frames_auto = true;  // not set by the caller: frame_plan caps it so that the in-flight state stays under kAutoFrameBytes
+  int batch_frames = 32;
   struct Pending {
     DCamera cam;
     uint32_t iteration;
@@ -151,49 +194,21 @@ struct ptc_ctx : ptc_scene_state {
   hipEvent_t turn_event[2] = {nullptr, nullptr};  // recorded behind the traversal launches of a pair's two batches
   int turn_wait = -1;                             // which of them the next traversal launch of the pair waits for (-1: none)
   int turn_mine = -1;                             // which one the batch being enqueued records (-1: not a pair)
-  uint64_t batches_issued = 0;
-  // Slots [0, big_slots) hold `batch` frames each; slots [big_slots, slots.size()) hold ONE frame: a batch of a
-  // single iteration (a viewer that presents after every iteration, the stepwise calls) goes to one of those, so
-  // that many such launches can be in flight on their own streams without the memory of full-size slots.
-  int big_slots = 0;
-  uint64_t singles_issued = 0;
-  int active_slot = -1;          // slot of the frame being built by ptc_trace_begin/bounce/end
-  int last_slot = 0;             // slot of the most recent finished frame
   hipEvent_t order_event = nullptr;  // last accumulate enqueued (accumulates run in iteration order)
   bool order_valid = false;
   hipEvent_t main_event = nullptr;   // last main-stream consumer that read the framebuffers asynchronously
   bool main_valid = false;
-  DFrame fb{};
-  float4* den_a = nullptr;
-  float4* den_b = nullptr;
-  float4* den_pos = nullptr;     // per-pixel view-space hit position of the accumulated depth (denoiser)
-  const float4* result = nullptr;
-  float* pack_buf = nullptr;     // 3 floats / pixel staging for downloads
-  uint32_t* rgba_buf = nullptr;  // staging for host presents
   DeviceCounters* misc_counters = nullptr;  // flags of kernels outside the frame loop (ptcore_query.cpp: exact_closest_hit)
   uint32_t slot_offset = 0;                 // "slot_offset" (multi-GPU: distinct random streams per rank)
   uint32_t* slot_offset_dev = nullptr;
   hipEvent_t xstream_event = nullptr;       // orders the stepwise calls between a frame's stream and ctx->stream
-  // several GPUs (ptc_band_*): this rank's exported band buffer, and on the root the peers' mapped buffers
-  float* band_buf = nullptr;                // 3 floats per pixel of pix_capacity
-  struct Peer {
-    void* mapped = nullptr;                 // hipIpcOpenMemHandle of the peer process's band buffer
-    bool opened = false;
-    ptc_band_handle h{};
-  };
-  std::vector<Peer> peers;                  // by rank
-  float* gather_frame = nullptr;            // root: the whole frame, 3 floats per pixel
-  uint32_t* gather_rgba = nullptr;
   hipEvent_t gather_ev[2] = {nullptr, nullptr};  // around the most recent gather launch (ptc_gather_last_us)
-  bool gather_timed = false;
 
   int iteration = 0;
   int max_iterations = 1;
   int method = PTC_METHOD_STREAMING;
   int max_bounces = 50;
   ptc_denoiser_params den{10, 0.45f, 0.30f, 0.25f};
-  DCamera cam{};
-  bool have_cam = false;
   uint64_t frames = 0;
 
   int trace_variant = 3;  // 3: persistent lanes over the four-wide collapse, conservative FMA slabs, exact check of the winner (default); 0: reference-order traversal; 1: culled near-first traversal with exact box decisions
@@ -207,7 +222,6 @@ struct ptc_ctx : ptc_scene_state {
   uint32_t persist_help_tiles = 8;     // "persist_help_tiles": tiles a walking wavefront without rays shades before it looks for rays again (0: it sleeps)
   uint32_t persist_min_frames = 2;     // "persist_min_frames": batches of fewer frames keep the per-bounce launches
   uint64_t scene_serial = 0;  // counts ptc_upload_scene calls (entry points computed for another scene are stale)
-  uint32_t beam_tiles_x = 0, beam_tiles_y = 0;
   uint32_t traverse_waves = 5120;
   uint32_t refill_lanes = 32;   // (20 until round 4: re-swept on its final code, profiles/r04_schedules.txt)
   uint32_t static_eighths = 4;  // (3 until round 4)
@@ -222,10 +236,6 @@ struct ptc_ctx : ptc_scene_state {
   uint32_t run_waves = 3072;          // "run_waves" (round 5): most persistent wavefronts of a launch that walks a run of instances (k_traverse4m).
                                       // Config 2 -- 4.5 M listed rays per launch, two batches in flight -- 14.0 -> 14.8 Grays/s on 1536 ... 3584
                                       // wavefronts against 5120: the other batch's HBM-bound kernels get on the chip (profiles/r05_run_waves.txt)
-  // live paths entering each bounce of one recent frame (what a frame of this scene / camera looks like): the host
-  // never waits for them, they only size the traversal launches
-  uint32_t est_live[2 * (kMaxBounces + 1)] = {};  // live[], then listed_now[] (DeviceCounters) of a recent batch's first frame
-  bool est_valid = false;
   bool filter_rays = true;    // "filter_rays": a sphere run in front of a mesh launch also lists the rays that launch has to walk
   bool prefold = true;        // "prefold": the kernel that ends a bounce also walks the NEXT bounce's leading sphere run for its survivors (config 2's shape)
   bool fused_shade = true;    // "fused_shade": the end of a bounce in one pass (k_shade_fused); 0: k_tail_count -> k_scan -> k_shade
@@ -241,7 +251,6 @@ struct ptc_ctx : ptc_scene_state {
     hipEvent_t start, stop;
     int bounce;
   };
-  bool staging() const { return staged; }
   std::vector<TimedLaunch> timed;        // recorded, not yet read
   std::vector<hipEvent_t> free_events;
   double trace_ms[kMaxBounces] = {};
@@ -254,7 +263,6 @@ struct ptc_ctx : ptc_scene_state {
 
   ptc_direct_stats direct{};             // ptc_direct_light since ptc_reset_profile
 };
-
 
 namespace ptcd {
 
@@ -281,8 +289,16 @@ DCamera make_camera(const ptc_camera& c, uint32_t w, uint32_t h);
 int flush_pending(ptc_ctx* ctx, bool from_trace = false);  // enqueue the iterations ptc_trace has queued (ptcore_trace.cpp)
 uint32_t fold_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end);  // may k_spheres take sphere_fold for this run? (ptcore_trace.cpp)
 int sync_frames(ptc_ctx* ctx);
-void free_slots(ptc_ctx* ctx);
+// gives back everything a frame state owns and leaves it "no frame" (ptcore.cpp); its streams must be idle (sync_frames)
+void release_frame(ptc_frame_state& f);
 int frame_ready(ptc_ctx* ctx);
+// The views (ptcore.cpp).  view_ready: the opening their entry points share -- NULL is PTC_ERR_INVALID, "ptc_resize first", the device.
+// buffer_view: the one reading of a ptc_buffer ("unknown buffer"); display_view: of a ptc_display ("unknown display type").
+struct BufferView { const float4* src; int sel; uint32_t floats_per_pixel; };  // framebuffer, launch_pack's selector, floats of a packed pixel
+struct DisplayView { int which, mode; };                                       // the ptc_buffer shown, launch_preview's mode
+int view_ready(ptc_ctx* ctx, const void* arg);
+int buffer_view(ptc_ctx* ctx, int which, BufferView* out);
+int display_view(ptc_ctx* ctx, int display_type, bool gathered, DisplayView* out);
 // The lamp table of a validated scene (ptcore_scene.cpp; include/ptcore.h: ptc_light).  *last = last record with a weight > 0.
 // Returns PTC_OK, or PTC_ERR_INVALID with `err` naming the emissive sphere whose matrix is no similarity.
 int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err);

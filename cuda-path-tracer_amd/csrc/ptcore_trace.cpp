@@ -161,7 +161,7 @@ int batch_begin(ptc_ctx* ctx, const ptc_ctx::Pending* items, int count)
   // A main-stream consumer that still reads the framebuffers (denoise) must finish before anything is folded
   // in: with staging that is only the accumulate at the end of the batch (so tracing overlaps the denoise of
   // the previous frame); without staging the shade kernels write the framebuffers directly.
-  if (ctx->main_valid && !ctx->staging()) HIP_TRY(ctx, hipStreamWaitEvent(sl.stream, ctx->main_event, 0));
+  if (ctx->main_valid && !ctx->staged) HIP_TRY(ctx, hipStreamWaitEvent(sl.stream, ctx->main_event, 0));
   // launches of different slots run at the same time: each slot has its own stack overflow area
   const size_t spill_need = (size_t)ctx->scene.spill_cap * ctx->scene.spill_stride;
   if (spill_need > sl.spill_elems) {
@@ -205,7 +205,7 @@ int batch_begin(ptc_ctx* ctx, const ptc_ctx::Pending* items, int count)
   } else {
     launch_raygen(sl.stream, cams, sl.bi, ctx->band, ctx->pix_count, sl.paths[0], sl.counters, ctx->scene.objects, first_mesh, filt_end,
                   sl.first_listed ? sl.worklist : nullptr, sl.hits, sl.tile_desc, sl.tile_stride, next_epoch(sl), sl.primary_finished,
-                  sl.stage, ctx->staging());
+                  sl.stage, ctx->staged);
   }
   if (int rc = check_last(ctx, "raygen")) return rc;
   // "beam": when bounce 0 opens with a launch over ONE mesh object (k_traverse4), its primary rays start at entry points
@@ -316,7 +316,7 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
     // kernel walks that run for every survivor (DNextRun)
     const bool prefold = may_prefold(ctx, sl) && !last && wrote;
     const DNextRun next = prefold ? next_run(ctx, sl.hits_other, sl.next_flags) : DNextRun{};
-    launch_shade_fused(sl.stream, scene, tail.begin, tail.end, !wrote, in, out, sl.hits, ctx->pix_count, ctx->staging(), bounce, last,
+    launch_shade_fused(sl.stream, scene, tail.begin, tail.end, !wrote, in, out, sl.hits, ctx->pix_count, ctx->staged, bounce, last,
                        slot_base_dev, sl.tile_desc, sl.tile_stride, sl.shade_epoch, sl.stage, ctx->band, sl.counters, octs, sl.bi,
                        bounce == 0 && sl.primary_finished ? sl.worklist : nullptr, prefold ? &next : nullptr, ctx->has_emitters);
     if (prefold) {
@@ -327,7 +327,7 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
     launch_tail_count(sl.stream, scene, tail.begin, tail.end, !wrote, in, sl.hits, ctx->pix_count, bounce, sl.chunk_counts, sl.counters,
                       sl.bi, ctx->has_emitters);
     launch_scan(sl.stream, bounce, last, sl.chunk_counts, sl.chunk_offsets, sl.counters, sl.bi);
-    launch_shade(sl.stream, scene, in, out, sl.hits, ctx->pix_count, ctx->staging(), bounce, last, slot_base_dev,
+    launch_shade(sl.stream, scene, in, out, sl.hits, ctx->pix_count, ctx->staged, bounce, last, slot_base_dev,
                  sl.chunk_offsets, sl.stage, ctx->band, sl.counters, octs, sl.bi, ctx->has_emitters);
   }
   sl.cur ^= 1;
@@ -342,7 +342,7 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
 // same results), and slots must fit the 26 bits a lane keeps them in.
 bool persist_ok(const ptc_ctx* ctx, int count)
 {
-  if (!ctx->persist || ctx->trace_variant != 3 || !ctx->fused_shade || ctx->ray_sort || !ctx->staging()) return false;
+  if (!ctx->persist || ctx->trace_variant != 3 || !ctx->fused_shade || ctx->ray_sort || !ctx->staged) return false;
   if (ctx->count_tests || ctx->max_bounces < 2 || count < (int)ctx->persist_min_frames) return false;
   if (ctx->launches.size() != 1u || plan_opens(ctx) != Opens::launch || launch_run(ctx, 0) != 1u) return false;
   const auto& sl = ctx->slots[(size_t)ctx->active_slot];
@@ -375,7 +375,7 @@ int batch_persist(ptc_ctx* ctx, const uint32_t* slot_base_dev)
   pa.help_tiles = ctx->persist_help_tiles;
   pa.tail_begin = tail.begin;
   pa.tail_end = tail.end;
-  pa.staged = ctx->staging() ? 1 : 0;
+  pa.staged = ctx->staged ? 1 : 0;
   pa.slot_base = slot_base_dev;
   pa.tile_desc = sl.tile_desc;
   pa.tile_stride = sl.tile_stride;
@@ -401,7 +401,7 @@ int batch_persist(ptc_ctx* ctx, const uint32_t* slot_base_dev)
 int batch_end(ptc_ctx* ctx)
 {
   auto& sl = ctx->slots[(size_t)ctx->active_slot];
-  if (ctx->staging()) {
+  if (ctx->staged) {
     // fold these samples in after the previous iteration's fold (running means do not commute)
     if (ctx->order_valid) HIP_TRY(ctx, hipStreamWaitEvent(sl.stream, ctx->order_event, 0));
     if (ctx->main_valid) HIP_TRY(ctx, hipStreamWaitEvent(sl.stream, ctx->main_event, 0));
@@ -497,7 +497,7 @@ int flush_pending(ptc_ctx* ctx, bool from_trace)
   if (ctx->pending.empty() && ctx->held.empty()) return PTC_OK;
   if (int rc = bind_device(ctx)) return rc;
   // "pair_batches": a batch that ptc_trace has just filled waits for its partner
-  const bool pairing = ctx->pair_batches && ctx->big_slots >= 2 && ctx->staging() && ctx->trace_variant == 3 && !ctx->persist;
+  const bool pairing = ctx->pair_batches && ctx->big_slots >= 2 && ctx->staged && ctx->trace_variant == 3 && !ctx->persist;
   if (pairing && from_trace && ctx->held.empty() && (int)ctx->pending.size() >= batch_limit(ctx) && batch_limit(ctx) > 1) {
     ctx->held.swap(ctx->pending);
     return PTC_OK;
@@ -601,7 +601,7 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
   }
   if (ctx->method == PTC_METHOD_MEGAKERNEL) {
     // one kernel per sample, accumulating in place: frames are serialised on slot 0's stream
-    if (ctx->staging()) {
+    if (ctx->staged) {
       if (int rc = sync_frames(ctx)) return rc;
     } else if (int rc = flush_pending(ctx)) {
       return rc;
@@ -613,7 +613,7 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
                       ctx->max_bounces, ctx->fb, sl.counters, ctx->has_emitters);
     if (int rc = check_last(ctx, "megakernel")) return rc;
     HIP_TRY(ctx, hipEventRecord(sl.done, sl.stream));
-    if (ctx->staging()) {
+    if (ctx->staged) {
       HIP_TRY(ctx, hipEventRecord(ctx->order_event, sl.stream));
       ctx->order_valid = true;
     }

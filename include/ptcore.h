@@ -555,6 +555,16 @@ int ptc_check_traversal_layout(const ptc_bvh_node* nodes, uint32_t node_count, u
  * or 128) rays, with the region geometry the kernels use (csrc/pt_feed_rules.hpp).  Returns the number of rays handed out
  * twice or never and of batches that are not contiguous or leave the frame (0 = sound), or a negative ptc_status. */
 int ptc_check_feed(uint32_t n, uint32_t static_eighths, uint32_t dyn_batch);
+/* The sizing rule of ptc_resize, on the host (no GPU, no context; test hook): what a context whose parameters are
+ * frames_in_flight (frames_auto != 0: the caller has not set it, and the in-flight state is capped at 24 GiB), batch_frames and
+ * prefold would allocate for a width x height frame -- frames in flight, frames per batch, batch slots, single-frame slots, and
+ * whether samples are staged (0: one frame in flight, shaded straight into the framebuffers).  PTC_ERR_INVALID for a NULL out
+ * and for a resolution ptc_resize refuses. */
+typedef struct ptc_frame_plan {
+  int32_t frames, batch, big_slots, single_slots, staged;
+} ptc_frame_plan;
+int ptc_check_frame_plan(uint32_t width, uint32_t height, int frames_in_flight, int frames_auto, int batch_frames, int prefold,
+                         ptc_frame_plan* out);
 /* Entry points for primary rays ("beam"), checked on the host (no GPU): for every 8 x 8-pixel tile of a width x height
  * frame of `camera`, the entries k_beam computes for the mesh under the object matrix object_m16 (NULL: identity;
  * column-major), and for sample rays of the tile (corners and centre of the jitter range of every stride-th pixel) the
