@@ -116,6 +116,10 @@ class ptc_direct_stats(C.Structure):
                 ("launches", C.c_uint32)]
 
 
+class ptc_direct_loop_stats(C.Structure):
+    _fields_ = [("diffuse_hits", C.c_uint64), ("shadow_rays", C.c_uint64), ("unoccluded", C.c_uint64)]
+
+
 class ptc_upload_times(C.Structure):
     _fields_ = [("bvh_build_ms", C.c_float), ("layout_ms", C.c_float), ("triangles_ms", C.c_float), ("copy_ms", C.c_float),
                 ("total_ms", C.c_float), ("bvh_on_device", C.c_uint32), ("layout_on_device", C.c_uint32)]
@@ -177,6 +181,7 @@ SIGNATURES = {
     "ptc_get_light_info": (C.c_int, [_P, C.POINTER(ptc_light_info)]),
     "ptc_direct_light": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_int]),
     "ptc_get_direct_stats": (C.c_int, [_P, C.POINTER(ptc_direct_stats)]),
+    "ptc_get_direct_loop_stats": (C.c_int, [_P, C.POINTER(ptc_direct_loop_stats)]),
     "ptc_get_upload_times": (C.c_int, [_P, C.POINTER(ptc_upload_times)]),
     "ptc_download_layout": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ptc_build_bvh_device": (C.c_int, [_P, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,

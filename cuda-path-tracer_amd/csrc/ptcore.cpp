@@ -215,6 +215,7 @@ const ParamRow kParams[] = {
     {"refill_lanes", 1, 64, " must be in [1,64]", kAnyTime,
      [](ptc_ctx* c, int v) { c->scene.refill_lanes = c->refill_lanes = (uint32_t)v; }},
     {"ray_sort", 0, 1, k01, kBeforeResize, [](ptc_ctx* c, int v) { c->ray_sort = v; }},
+    {"direct_light", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->direct_light = v != 0; }},
     {"denoise_variant", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_variant = v; }},
     {"frames_in_flight", 1, 256, " must be in [1,256]", kBeforeResize, [](ptc_ctx* c, int v) { c->frames_in_flight = v; }},
 };
@@ -431,6 +432,8 @@ int ptc_create(const ptc_config* config, ptc_ctx** out)
   if (hipMalloc(&p, 256) != hipSuccess) return bail(fail(ctx, PTC_ERR_OOM, "hipMalloc(slot offset) failed"));
   ctx->slot_offset_dev = static_cast<uint32_t*>(p);
   if (hipMemset(ctx->slot_offset_dev, 0, 256) != hipSuccess) return bail(fail(ctx, PTC_ERR_HIP, "hipMemset failed"));
+  if (hipMalloc(&p, kLoopStatBytes) != hipSuccess) return bail(fail(ctx, PTC_ERR_OOM, "hipMalloc(direct-light loop counters) failed"));
+  ctx->loop_stats = static_cast<unsigned long long*>(p);
   *out = ctx;
   return PTC_OK;
 }
@@ -458,6 +461,7 @@ void ptc_destroy(ptc_ctx* ctx)
   for (hipEvent_t e : ctx->gather_ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->misc_counters) (void)hipFree(ctx->misc_counters);
+  if (ctx->loop_stats) (void)hipFree(ctx->loop_stats);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -501,6 +505,7 @@ int ptc_restart(ptc_ctx* ctx)
   if (!ctx->pending.empty() || !ctx->held.empty())
     if (int rc = flush_pending(ctx)) return rc;
   ctx->iteration = 0;
+  ctx->loop_stats_clear = true;  // ptc_get_direct_loop_stats counts from here
   return PTC_OK;
 }
 
@@ -685,6 +690,23 @@ int ptc_get_stats(ptc_ctx* ctx, ptc_stats* out)
   if (flags & kFlagDispatchOrder)
     return fail(ctx, PTC_ERR_HIP, "k_shade_fused gave up waiting for a predecessor tile's survivor count: the image is invalid "
                                   "(set the parameter \"fused_shade\" to 0 to use the three-kernel path)");
+  return PTC_OK;
+}
+
+int ptc_get_direct_loop_stats(ptc_ctx* ctx, ptc_direct_loop_stats* out)
+{
+  if (!ctx || !out) return PTC_ERR_INVALID;
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;
+  *out = ptc_direct_loop_stats{};
+  if (ctx->loop_stats_clear) return PTC_OK;  // nothing direct-lit has been launched since ptc_restart
+  std::vector<unsigned long long> host((size_t)kLightStatLines * kLoopStatWords);
+  HIP_TRY(ctx, hipMemcpy(host.data(), ctx->loop_stats, kLoopStatBytes, hipMemcpyDeviceToHost));
+  for (uint32_t l = 0; l < kLightStatLines; ++l) {
+    out->diffuse_hits += host[(size_t)kLoopStatWords * l];
+    out->shadow_rays += host[(size_t)kLoopStatWords * l + 1u];
+    out->unoccluded += host[(size_t)kLoopStatWords * l + 2u];
+  }
   return PTC_OK;
 }
 

@@ -72,6 +72,8 @@ struct ptc_scene_state {
 
 // the last epoch of a lap of look-back launches on a slot's tile descriptors (30 bits: pt_shade_tile.inc; ptcore_trace.cpp, next_epoch)
 constexpr uint32_t kMaxEpoch = 0x3fffffffu;
+// the counter block of the direct-lit megakernel (ptc_ctx::loop_stats)
+constexpr size_t kLoopStatBytes = (size_t)kLightStatLines * kLoopStatWords * sizeof(unsigned long long);
 
 // Everything of a context that a ptc_resize decides or that dies with it.  ptc_resize (ptcore.cpp) builds one of these beside the
 // context and assigns it as a whole, after the last step that can fail; a value-initialised one is the state "no frame"
@@ -262,6 +264,11 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   ptc_occlusion_stats occlusion{};       // ptc_occluded_rays since ptc_reset_profile
 
   ptc_direct_stats direct{};             // ptc_direct_light since ptc_reset_profile
+
+  // "direct_light" (DESIGN section 5g): the megakernel draws a light sample at every diffuse hit (k_megakernel_direct)
+  bool direct_light = false;
+  unsigned long long* loop_stats = nullptr;  // device: kLightStatLines lines of kLoopStatWords words (diffuse hits, shadow rays, unoccluded)
+  bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
 };
 
 namespace ptcd {

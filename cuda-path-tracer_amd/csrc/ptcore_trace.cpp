@@ -7,6 +7,10 @@ using namespace ptcd;
 
 namespace {
 
+// "direct_light" 1 outside the megakernel method: the refusal of ptc_trace and ptc_trace_begin
+constexpr const char* kDirectNeedsMegakernel =
+    "direct_light is rendered by the megakernel method only (ptc_set_method(PTC_METHOD_MEGAKERNEL)); the streaming loop has no direct lighting";
+
 // the epoch of the next look-back launch on a slot's tile descriptors (k_shade_fused, the listing k_raygen / k_spheres).  After
 // kMaxEpoch the epochs start at 1 again, and a descriptor that no launch of the finished lap has overwritten (a tile above a band
 // that ptc_set_rows shrank) would pass for one of the new lap: the descriptors are cleared on the slot's stream, behind the last
@@ -520,6 +524,7 @@ int ptc_trace_begin(ptc_ctx* ctx, const ptc_camera* camera)
   if (int rc = frame_ready(ctx)) return rc;
   if (!camera) return fail(ctx, PTC_ERR_INVALID, "camera is NULL");
   if (ctx->active_slot >= 0) return fail(ctx, PTC_ERR_INVALID, "ptc_trace_end missing");
+  if (ctx->direct_light) return fail(ctx, PTC_ERR_INVALID, kDirectNeedsMegakernel);  // (the stepwise calls are the streaming loop)
   // (ptc_trace stops at max_iterations; nothing else stands between the stepwise calls and ptc_trace_end's ++iteration)
   if (ctx->iteration == INT_MAX) return fail(ctx, PTC_ERR_INVALID, "the iteration counter is at INT_MAX: ptc_restart or ptc_set_iteration first");
   if (int rc = flush_pending(ctx)) return rc;
@@ -595,6 +600,9 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
   if (int rc = frame_ready(ctx)) return rc;
   if (!camera) return fail(ctx, PTC_ERR_INVALID, "camera is NULL");
   if (ctx->active_slot >= 0) return fail(ctx, PTC_ERR_INVALID, "ptc_trace_end missing");
+  // "direct_light" is rendered by the megakernel alone: refused before anything is queued or launched
+  if (ctx->direct_light && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kDirectNeedsMegakernel);
+  if (ctx->direct_light && !ctx->light_error.empty()) return fail(ctx, PTC_ERR_INVALID, ctx->light_error);  // as ptc_direct_light
   if (ctx->iteration >= ctx->max_iterations) {  // path_tracer.cu:391
     ctx->result = ctx->fb.color4;
     return PTC_OK;
@@ -609,8 +617,19 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
     auto& sl = ctx->slots[0];
     ctx->cam = make_camera(*camera, ctx->width, ctx->height);
     ctx->have_cam = true;
-    launch_megakernel(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
-                      ctx->max_bounces, ctx->fb, sl.counters, ctx->has_emitters);
+    if (ctx->direct_light && ctx->light_records) {  // a lamp table of total weight > 0; without one: the plain instances, the same bits
+      if (ctx->loop_stats_clear) {
+        HIP_TRY(ctx, hipMemsetAsync(ctx->loop_stats, 0, kLoopStatBytes, sl.stream));
+        ctx->loop_stats_clear = false;
+      }
+      const DLights lights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
+                           ctx->scene.materials};
+      launch_megakernel_direct(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
+                               ctx->max_bounces, ctx->fb, sl.counters, ctx->loop_stats);
+    } else {
+      launch_megakernel(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
+                        ctx->max_bounces, ctx->fb, sl.counters, ctx->has_emitters);
+    }
     if (int rc = check_last(ctx, "megakernel")) return rc;
     HIP_TRY(ctx, hipEventRecord(sl.done, sl.stream));
     if (ctx->staged) {

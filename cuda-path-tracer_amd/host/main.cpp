@@ -48,6 +48,7 @@ struct CliConfigurations {  // configurations.hpp:11-15
   int max_bounces = 50;
   bool denoise = false;
   bool megakernel = false;
+  bool direct_light = false;
   int gpu = 0;
   int gpus = 1;
   std::optional<std::string> dump_scene;
@@ -67,6 +68,7 @@ void usage()
                "      --max-bounces N  bounce cap (default 50)\n"
                "      --denoise        run the A-Trous denoiser before writing the image\n"
                "      --method M       streaming (default) | megakernel\n"
+               "      --direct-light   a light sample with a shadow ray at every diffuse hit (needs --method megakernel)\n"
                "      --gpu N          HIP device ordinal\n"
                "      --gpus N         split the frame's rows over N processes / GPUs (rank r on device r %% device count)\n"
                "      --dump-scene F   write the flattened scene to F and exit (no GPU needed)\n"
@@ -98,6 +100,7 @@ CliConfigurations parse_cli_args(int argc, char** argv)
     else if (a == "--max-bounces") c.max_bounces = std::stoi(need("max-bounces"));
     else if (a == "--denoise") c.denoise = true;
     else if (a == "--method") c.megakernel = need("method") == "megakernel";
+    else if (a == "--direct-light") c.direct_light = true;
     else if (a == "--gpu") c.gpu = std::stoi(need("gpu"));
     else if (a == "--gpus") c.gpus = std::stoi(need("gpus"));
     else if (a == "--dump-scene") c.dump_scene = need("dump-scene");
@@ -119,6 +122,10 @@ CliConfigurations parse_cli_args(int argc, char** argv)
       std::fprintf(stderr, "Option '%s' does not exist\n", a.c_str());
       std::exit(1);
     } else c.filename = a;
+  }
+  if (c.direct_light && !c.megakernel) {  // before any GPU is touched: the streaming loop would render without it
+    std::fprintf(stderr, "hip_pt: --direct-light needs --method megakernel (the streaming method renders no direct light)\n");
+    std::exit(1);
   }
   if (c.filename.empty()) {
     std::fprintf(stderr, "Usage: hip_pt [options] <filename>\nRun 'hip_pt --help' for more information");
@@ -252,6 +259,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   bool enable_denoising = configs.denoise;
   DisplayBufferType display = configs.display;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
+  path_tracer.direct_light = configs.direct_light;
 
   int shown = 0;
   std::vector<uchar4> buffer;
@@ -354,6 +362,8 @@ try {
   Stopwatch stopwatch;
   PathTracer path_tracer{rank % devices};
   path_tracer.max_bounces = configs.max_bounces;
+  if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
+  path_tracer.direct_light = configs.direct_light;
   path_tracer.create_buffers(resolution, scene_desc);
   auto check = [&](int rc, const char* what) {
     if (rc < 0) throw std::runtime_error(std::string(what) + ": " + ptc_last_error(path_tracer.handle()));
@@ -433,7 +443,9 @@ int run_ranks(const CliConfigurations& configs, const SceneDescription& scene_de
     std::fprintf(stderr, "hip_pt: at most %d ranks\n", kMaxRanks);
     return 1;
   }
-  if (configs.denoise || configs.megakernel) {
+  // (the megakernel seeds by frame pixel, so its ranks render the single-GPU image; it is let through for --direct-light, which
+  // the streaming method cannot render)
+  if (configs.denoise || (configs.megakernel && !configs.direct_light)) {
     std::fprintf(stderr, "hip_pt: --gpus N renders in streaming mode without the denoiser (it needs the whole frame in one context)\n");
     return 1;
   }
@@ -526,6 +538,7 @@ try {
   PathTracer path_tracer{configs.gpu};
   path_tracer.max_bounces = configs.max_bounces;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
+  path_tracer.direct_light = configs.direct_light;
   path_tracer.create_buffers(resolution, scene_desc);
   path_tracer.synchronize();
   std::printf("Start path tracing\nspp: %d\nwidth: %u, height: %u\n", spp, resolution.width, resolution.height);

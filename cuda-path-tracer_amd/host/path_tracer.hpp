@@ -38,6 +38,7 @@ class PathTracer {
 public:
   int max_iterations = 1;
   GPUMethod current_gpu_method = GPUMethod::streaming;
+  bool direct_light = false;  // a light sample at every diffuse hit (megakernel method only; ptc_set_param "direct_light")
   EdgeAvoidingATrousDenoiser atrous_denoiser{};
   int max_bounces = 50;  // reference: compile-time constant, path_tracer.cu:27
 
@@ -104,6 +105,10 @@ private:
   {
     check(ptc_set_max_iterations(ctx_, max_iterations), "max_iterations");
     check(ptc_set_method(ctx_, current_gpu_method == GPUMethod::megakernel ? PTC_METHOD_MEGAKERNEL : PTC_METHOD_STREAMING), "method");
+    if (direct_light != direct_light_pushed_) {  // (ptc_set_param flushes queued frames: only on a change)
+      check(ptc_set_param(ctx_, "direct_light", direct_light ? 1 : 0), "direct_light");
+      direct_light_pushed_ = direct_light;
+    }
     check(ptc_set_max_bounces(ctx_, max_bounces), "max_bounces");
     const ptc_denoiser_params p{atrous_denoiser.filter_size, atrous_denoiser.color_weight, atrous_denoiser.normal_weight,
                                 atrous_denoiser.position_weight};
@@ -114,6 +119,7 @@ private:
     if (rc < 0) throw std::runtime_error(std::string(what) + ": " + ptc_last_error(ctx_));
   }
   ptc_ctx* ctx_ = nullptr;
+  bool direct_light_pushed_ = false;
 };
 
 }  // namespace hip_pt

@@ -67,11 +67,27 @@ def light_table(scene, capacity=None):
     return out[:rc].copy(), _light_info_dict(info)
 
 
+class _DirectLight:
+    """What PathTracer.direct_light is.  The name was the direct-light QUERY's (ptc_direct_light) before it became the render
+    loop's switch as well (the field the C++ PathTracer has), so it is both: its truth value is the switch -- assign True or False
+    to PathTracer.direct_light --, and called it is the query, as before."""
+
+    def __init__(self, tracer):
+        self._tracer = tracer
+
+    def __bool__(self):
+        return self._tracer._direct_light
+
+    def __call__(self, points, normals, sample_index=0, want_rays=False):
+        return self._tracer._direct_light_query(points, normals, sample_index, want_rays)
+
+
 class PathTracer:
     def __init__(self, device=0, max_bounces=50):
         self._lib = _capi.lib()
         self.max_iterations = 1
         self.current_gpu_method = GPUMethod.streaming
+        self._direct_light = False  # PathTracer.direct_light = True: a light sample at every diffuse hit (megakernel method only)
         self.atrous_denoiser = EdgeAvoidingATrousDenoiser()
         self.max_bounces = max_bounces  # reference: compile-time 50 (path_tracer.cu:27)
         cfg = _capi.ptc_config(device=device, max_bounces=max_bounces, method=int(self.current_gpu_method), reserved=0)
@@ -80,6 +96,7 @@ class PathTracer:
         self._ctx = handle
         self._resolution = None
         self._rows = None
+        self._direct_light_pushed = False
 
     # -- lifetime -------------------------------------------------------------------------------
     def close(self):
@@ -102,9 +119,22 @@ class PathTracer:
     def _check(self, rc):
         return _capi.check(rc, self._ctx)
 
+    @property
+    def direct_light(self):
+        """The switch of direct lighting in the megakernel (ptc_set_param "direct_light"; assign True / False, read with bool())
+        and, called with points and normals, the direct-light query (ptc_direct_light)."""
+        return _DirectLight(self)
+
+    @direct_light.setter
+    def direct_light(self, on):
+        self._direct_light = bool(on)
+
     def _push_fields(self):
         self._check(self._lib.ptc_set_max_iterations(self._ctx, int(self.max_iterations)))
         self._check(self._lib.ptc_set_method(self._ctx, int(self.current_gpu_method)))
+        if self._direct_light != self._direct_light_pushed:  # (ptc_set_param flushes queued frames: only on a change)
+            self._check(self._lib.ptc_set_param(self._ctx, b"direct_light", 1 if self._direct_light else 0))
+            self._direct_light_pushed = self._direct_light
         self._check(self._lib.ptc_set_max_bounces(self._ctx, int(self.max_bounces)))
         d = self.atrous_denoiser
         p = _capi.ptc_denoiser_params(int(d.filter_size), float(d.color_weight), float(d.normal_weight),
@@ -362,7 +392,7 @@ class PathTracer:
         self._check(self._lib.ptc_get_light_info(self._ctx, C.byref(info)))
         return _light_info_dict(info)
 
-    def direct_light(self, points, normals, sample_index=0, want_rays=False):
+    def _direct_light_query(self, points, normals, sample_index=0, want_rays=False):
         """One light sample per surface point (ptc_direct_light).  points, normals: [n, 3] float32 (finite points, unit
         normals).  Returns radiance [n, 3]: what the lamps send to a white Lambertian surface there by this sample; with
         want_rays also the shadow rays [n, 8] (origin, t_min, direction, t_max) and visible uint8[n]."""
@@ -393,6 +423,13 @@ class PathTracer:
         self._check(self._lib.ptc_get_direct_stats(self._ctx, C.byref(s)))
         return {"points": int(s.points), "sampled": int(s.sampled), "unoccluded": int(s.unoccluded),
                 "kernel_ms": float(s.kernel_ms), "launches": int(s.launches)}
+
+    def direct_loop_stats(self):
+        """Counters of the direct-lit megakernel (direct_light = True) since restart: hits on a diffuse material, shadow rays
+        traced, shadow rays that arrived."""
+        s = _capi.ptc_direct_loop_stats()
+        self._check(self._lib.ptc_get_direct_loop_stats(self._ctx, C.byref(s)))
+        return {"diffuse_hits": int(s.diffuse_hits), "shadow_rays": int(s.shadow_rays), "unoccluded": int(s.unoccluded)}
 
     def selftest_math(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)

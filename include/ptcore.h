@@ -327,6 +327,15 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *                      the primary rays -- into a second set of hit records, and the bounce starts with the work list (k_list_flags)
  *                      instead of k_spheres.  Bit-identical; config 2 +8-9 %.  0: every bounce runs k_spheres.  Before ptc_resize
  *                      (33 more bytes per pixel and frame in flight)
+ *   "direct_light"     RENDERING (default 0; an extension): 1 = ptc_trace under PTC_METHOD_MEGAKERNEL draws one light
+ *                      sample (ptc_direct_light's, from a random stream of its own) with a shadow ray at every diffuse hit, sums the
+ *                      samples' radiance along the path, and counts an emissive hit only when the vertex before it drew no sample
+ *                      (the camera, metal, glass).  The expectation of every pixel is unchanged, its variance is lower wherever a lamp is
+ *                      small; normal, depth and ptc_stats.rays_total (closest-hit queries) are bit for bit those of 0.  A scene without
+ *                      lamps, or of total lamp weight 0, renders bit for bit as with 0; a scene with an emissive sphere that cannot be
+ *                      sampled (ptc_light_table) makes ptc_trace fail with PTC_ERR_INVALID, naming the object.  Under
+ *                      PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is 1, before anything is
+ *                      queued: the streaming loop does not render direct light.  Counters: ptc_get_direct_loop_stats.  Any time
  *   "pair_batches"     SCHEDULE (round 5; default 0): 1 = a full batch is held until the next one is full (or anything else looks at
  *                      the context); the two are enqueued bounce by bounce on two slots and their traversal launches take turns.
  *                      Bit-identical, measured 6-7 % slower than the default (profiles/r05_pair_batches.txt): off.  Any time
@@ -506,6 +515,15 @@ typedef struct ptc_direct_stats {
   uint32_t launches;
 } ptc_direct_stats;
 int ptc_get_direct_stats(ptc_ctx* ctx, ptc_direct_stats* out);
+
+/* The direct-lit megakernel ("direct_light" 1) since ptc_restart: hits on a diffuse material (each one draws a
+ * light sample), shadow rays traced (the samples that were not culled) and the shadow rays that arrived (their contribution was
+ * added).  Synchronises.  Zeros while nothing direct-lit has been traced since ptc_restart.  Moves none of ptc_stats, ptc_profile,
+ * ptc_occlusion_stats and ptc_direct_stats, and nothing moves it but ptc_trace and ptc_restart. */
+typedef struct ptc_direct_loop_stats {
+  uint64_t diffuse_hits, shadow_rays, unoccluded;
+} ptc_direct_loop_stats;
+int ptc_get_direct_loop_stats(ptc_ctx* ctx, ptc_direct_loop_stats* out);
 
 /* Where the time of the last ptc_upload_scene went (milliseconds of host wall clock; the "Initialization" stage of
  * the reference's Stopwatch, cli.cpp): */
