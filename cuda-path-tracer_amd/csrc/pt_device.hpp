@@ -398,13 +398,15 @@ void launch_sort_octant(hipStream_t s, const uint8_t* octs, uint32_t* order, uin
                         DeviceCounters* counters, const DBatchInfo& bi);
 void launch_tail_count(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths paths,
                        DHits hits, uint32_t max_paths, int bounce, uint32_t* chunk_counts, DeviceCounters* counters,
-                       const DBatchInfo& bi, bool emitters = false);
+                       const DBatchInfo& bi, bool emitters = false, bool roulette = false, const uint32_t* slot_base = nullptr);
 void launch_scan(hipStream_t s, int bounce, bool last_bounce, const uint32_t* chunk_counts, uint32_t* chunk_offsets,
                  DeviceCounters* counters, const DBatchInfo& bi);
+// roulette (launch_tail_count, launch_shade, launch_shade_fused): the bounce plays Russian roulette; the caller
+// decides that and never asks for it at the last bounce -- the kRoulette instances do not look at last_bounce for it
 void launch_shade(hipStream_t s, const DScene& scene, DPaths in, DPaths out, DHits hits, uint32_t max_paths,
                   bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                   const uint32_t* chunk_offsets, DFrame fb, DBand band, DeviceCounters* counters, uint8_t* octs,
-                  const DBatchInfo& bi, bool emitters = false);
+                  const DBatchInfo& bi, bool emitters = false, bool roulette = false);
 // the end of a bounce in one pass (k_shade_fused): trailing sphere run [obj_begin, obj_end) + material + stable compaction +
 // final gather.  tile_desc: shade_tiles_per_frame(max_paths) descriptors per frame of the batch (tile_stride apart), zero
 // at allocation, cleared again only when the epochs start over; epoch: a number no earlier launch of this lap has used (1 .. 2^30 - 1).
@@ -414,7 +416,7 @@ void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, 
                         DHits hits, uint32_t max_paths, bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                         unsigned long long* tile_desc, uint32_t tile_stride, uint32_t epoch, DFrame fb, DBand band,
                         DeviceCounters* counters, uint8_t* octs, const DBatchInfo& bi, const uint32_t* list = nullptr,
-                        const DNextRun* next = nullptr, bool emitters = false);
+                        const DNextRun* next = nullptr, bool emitters = false, bool roulette = false);
 // "prefold" at bounce 0: ray generation that also walks the sphere run in front of bounce 0's first mesh launch (next.hits: the
 // CURRENT bounce's records here) and leaves the bytes for launch_list_flags
 void launch_raygen_next(hipStream_t s, const DScene& scene, const DCameras& cams, const DBatchInfo& bi, DBand band, uint32_t pix_count, DPaths paths,
@@ -432,6 +434,9 @@ void launch_persist(hipStream_t s, const DScene& scene, uint32_t obj_index, DHit
 uint32_t persist_tiles_per_frame(uint32_t max_paths);
 void launch_megakernel(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band,
                        uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters = false);
+// ... for a frame with a bounce that plays Russian roulette (1 <= roulette < max_bounces - 1, the caller's check)
+void launch_megakernel_roulette(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
+                                int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette);
 void launch_preview(hipStream_t s, const float4* buf, uint32_t pix_count, int mode, uint32_t* rgba);
 void launch_pack(hipStream_t s, const float4* buf, uint32_t pix_count, int which, float* dst);
 // the bands of one multi-GPU gather launch (k_gather_bands): up to kGatherBands sources per launch
@@ -471,6 +476,8 @@ struct DLights {
   const DMaterial* materials;
 };
 constexpr uint32_t kLightSeedXor = 0x4c495445u;  // xor-ed into path_seed(point, sample_index): no render path xors its seed
+// Russian roulette (ptc_set_param "roulette"): xor-ed into path_seed(slot or pixel, iteration); discard(bounce), one draw
+constexpr uint32_t kRouletteSeedXor = 0x52524c54u;
 constexpr uint32_t kLightStatLines = 64u;        // the resolve kernel's two counters, spread over this many 128-byte lines
 //   launch_light_sample   one thread per point: the shadow ray in the path-state layout occlude_on_device takes (o4 = p, tmin_word;
 //                         d4 = w, t_max) and contrib = {unshadowed contribution rgb, 1 if sampled else 0}; a culled sample: t_max 0
@@ -488,7 +495,8 @@ void launch_light_resolve(hipStream_t s, const float4* o4, const float4* d4, con
 // feed depends on.
 constexpr uint32_t kLoopStatWords = 16u;
 void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats);
+                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats,
+                              int roulette = 0);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,
                      float* out_sin, float* out_cos);
 void launch_selftest_rng(hipStream_t s, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);

@@ -569,6 +569,24 @@ __device__ __forceinline__ float schlick(float cosine, float ref_idx)
 __device__ __forceinline__ bool is_emitter(const DMaterial& m) { return m.type == 3; }
 __device__ __forceinline__ f3 emit_color(const f3 color, const DMaterial& m) { return color * mk3(m.p[0], m.p[1], m.p[2]); }
 
+// Russian roulette (ptc_set_param "roulette", an extension; DESIGN section 5h) for a path that would go on: c is the throughput
+// that came INTO the bounce (before evaluate_material), index the path's slot (streaming) or pixel (megakernel).  True: the path
+// ends here with the sample (0, 0, 0) and makes no material draw.  False: it goes on, c divided by q when q < 1 (the largest
+// component becomes exactly 1); q >= 1 draws nothing and divides nothing.  The draw is the roulette stream's alone:
+// seed(path_seed(index, iteration) ^ kRouletteSeedXor), discard(bounce), one uniform().  One binary32 operation per line item.
+__device__ __forceinline__ bool roulette_ends(f3& c, const uint32_t index, const uint32_t iteration, const uint32_t bounce)
+{
+  const float q = sel_max(sel_max(c.x, c.y), c.z);
+  if (q >= 1.0f) return false;
+  Minstd rng;
+  rng.seed(path_seed(index, iteration) ^ kRouletteSeedXor);
+  rng.discard(bounce);
+  const float u = rng.uniform();
+  if (!(u < q)) return true;  // (q == 0 as well)
+  c = mk3(c.x / q, c.y / q, c.z / q);
+  return false;
+}
+
 // evaluate_material, path_tracer.cu:138-201.  tmin_flag: ray.t_min is 1e-5 from now on (dielectric).
 __device__ __forceinline__ void evaluate_material(f3& ro, f3& rd, bool& tmin_flag, const f3 hp, const f3 hn,
                                                   const uint32_t side, const DMaterial m, Minstd& rng, f3& color)
@@ -624,7 +642,7 @@ __device__ __forceinline__ void evaluate_material(f3& ro, f3& rd, bool& tmin_fla
 // kind: 0 diffuse, 1 metal, 2 dielectric (Material::type), 3 miss, 4 emissive (kEmit instances only: material type 3, which
 // the caller maps to kKindEmit -- its material's type would read as "miss" here), anything else: nothing to do.  An emissive
 // hit makes no draw and touches neither ray nor tmin_flag: the path ends with color * emission (emit_color).
-constexpr uint32_t kKindMiss = 3u, kKindEmit = 4u;
+constexpr uint32_t kKindMiss = 3u, kKindEmit = 4u, kKindNone = 5u;  // (kKindNone: a path roulette has ended, section 5h)
 template <bool kEmit = false>
 __device__ __forceinline__ void shade_kinds(const uint32_t kind, f3& ro, f3& rd, bool& tmin_flag, const f3 hp, const f3 hn,
                                             const uint32_t side, const DMaterial m, const uint32_t slot, const uint32_t iteration,
@@ -852,6 +870,20 @@ __device__ __forceinline__ Ray load_ray(const DPaths& paths, uint32_t s)
   r.d = xyz(d);
   r.tmin = (__float_as_uint(o.w) >> 31) ? 1e-5f : 1e-4f;
   r.tmax = FLT_MAX;
+  return r;
+}
+
+// ... and the first throughput component, which rides in the direction's fourth word (DPaths): one load of d4 for both
+__device__ __forceinline__ Ray load_ray(const DPaths& paths, uint32_t s, float& through_x)
+{
+  const float4 o = ldnt(&paths.o4[s]);
+  const float4 d = ldnt(&paths.d4[s]);
+  Ray r;
+  r.o = xyz(o);
+  r.d = xyz(d);
+  r.tmin = (__float_as_uint(o.w) >> 31) ? 1e-5f : 1e-4f;
+  r.tmax = FLT_MAX;
+  through_x = d.w;
   return r;
 }
 

@@ -160,9 +160,13 @@ __device__ __forceinline__ bool scene_occluded(const Ray& ray, const DScene& sc,
 // path_tracing_mega_kernel (path_tracer.cu:227-269) with DESIGN section 5g's rule.  One thread per pixel of the band; launched only
 // for a scene with a lamp table of total weight > 0 (so the scene has an emissive material: this is k_megakernel<true>'s loop).
 // stats: kLightStatLines lines of kLoopStatWords 64-bit words; word 0 += diffuse hits, word 1 += shadow rays traced, word 2 += unoccluded ones.
+// kRoulette: Russian roulette from bounce `roulette` on, the last bounce excepted, as k_megakernel's: a path that
+// ends there leaves colour 0, takes no light sample at that hit and adds nothing to the three loop counters; a survivor's light
+// sample is weighted with the divided colour.
+template <bool kRoulette>
 __global__ __launch_bounds__(kWave) void k_megakernel_direct(DScene sc, DLights lt, DCamera cam, uint32_t iteration, DBand band,
                                                              uint32_t pix_count, int max_bounces, DFrame fb,
-                                                             DeviceCounters* counters, unsigned long long* stats)
+                                                             DeviceCounters* counters, unsigned long long* stats, int roulette)
 {
   __shared__ uint32_t s_stack[kStackDepth * kWave];
   const uint32_t s = blockIdx.x * kWave + threadIdx.x;
@@ -204,6 +208,10 @@ __global__ __launch_bounds__(kWave) void k_megakernel_direct(DScene sc, DLights 
       const DMaterial mat = sc.materials[rec.mat];
       if (is_emitter(mat)) {  // the path ends at the emitter: no draw; after a diffuse vertex its light sample has counted the lamp
         color = count_emission ? emit_color(color, mat) : mk3(0.0f, 0.0f, 0.0f);
+        break;
+      }
+      if (kRoulette && i >= roulette && i != max_bounces - 1 && roulette_ends(color, pixel, iteration, (uint32_t)i)) {
+        color = mk3(0.0f, 0.0f, 0.0f);  // the path ends by chance: radiance + 0 is deposited, no draw, no light sample
         break;
       }
       evaluate_material(ray.o, ray.d, tmin_flag, rec.p, rec.n, rec.side, mat, rng, color);
@@ -248,10 +256,29 @@ __global__ __launch_bounds__(kWave) void k_megakernel_direct(DScene sc, DLights 
   }
 }
 
-void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats)
+// the plain megakernel's instances that play roulette (pt_megakernel.inc; the plain ones: pt_kernels.hip)
+#include "pt_megakernel.inc"
+
+void launch_megakernel_roulette(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
+                                int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette)
 {
-  hipLaunchKernelGGL(k_megakernel_direct, dim3((pix_count + kWave - 1u) / kWave), dim3(kWave), 0, s, scene, lights, cam, iteration, band,
-                     pix_count, max_bounces, fb, counters, stats);
+  const dim3 grid((pix_count + kWave - 1u) / kWave), block(kWave);
+  if (emitters)
+    hipLaunchKernelGGL((k_megakernel<true, true>), grid, block, 0, s, scene, cam, iteration, band, pix_count, max_bounces, fb, counters, roulette);
+  else
+    hipLaunchKernelGGL((k_megakernel<false, true>), grid, block, 0, s, scene, cam, iteration, band, pix_count, max_bounces, fb, counters, roulette);
+}
+
+void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
+                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats,
+                              int roulette)
+{
+  const dim3 grid((pix_count + kWave - 1u) / kWave), block(kWave);
+  if (roulette >= 1 && roulette < max_bounces - 1)  // some bounce plays roulette
+    hipLaunchKernelGGL(k_megakernel_direct<true>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters,
+                       stats, roulette);
+  else
+    hipLaunchKernelGGL(k_megakernel_direct<false>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters,
+                       stats, roulette);
 }
 }  // namespace pt

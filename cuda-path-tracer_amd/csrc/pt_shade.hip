@@ -296,18 +296,23 @@ __global__ __launch_bounds__(256) void k_list_flags(const uint8_t* flags, int bo
 // every 64-slot chunk (ballot / popcount of "the hit record holds a hit"), for the compaction scan.
 // kSpheres: objects [obj_begin, obj_end) are tested; kFirst: nothing has written the hit record in this bounce yet.
 // kEmit: the scene has an emissive material; a hit on one ends the path (k_shade) and is not counted live.
+// kRoulette: the bounce plays Russian roulette: a hit that would go on makes the roulette decision here, from
+// the throughput that came into the bounce, and is not counted live when it ends; k_shade<.., true> makes the same decision from
+// the same operands (roulette_ends).
 // 256-thread workgroups: one wavefront per SIMD fits beside the other stream's persistent traversal wavefronts as soon
 // as one of those has left (1024-thread workgroups wait until four per SIMD have: measured 15 % slower end to end,
 // together with a scan fused in behind a "last workgroup" sign-off).
-template <bool kSpheres, bool kFirst, bool kEmit = false>
+template <bool kSpheres, bool kFirst, bool kEmit = false, bool kRoulette = false>
 __global__ __launch_bounds__(256) void k_tail_count(DScene sc, uint32_t obj_begin, uint32_t obj_end, DPaths paths, DHits hits,
-                                                    int bounce, uint32_t* chunk_counts, DeviceCounters* counters, DBatchInfo bi)
+                                                    int bounce, uint32_t* chunk_counts, DeviceCounters* counters, DBatchInfo bi,
+                                                    const uint32_t* slot_base)
 {
   const uint32_t frame = blockIdx.y;  // see DBatchInfo
   paths.o4 += (size_t)frame * bi.stride;
   paths.d4 += (size_t)frame * bi.stride;
   hits.tp += (size_t)frame * bi.stride;
   hits.nm += (size_t)frame * bi.stride;
+  if (kRoulette) paths.t2 += (size_t)frame * bi.stride;
   chunk_counts += (size_t)frame * bi.chunk_stride;
   counters += frame;
   const uint32_t n = counters->live[bounce];
@@ -320,8 +325,9 @@ __global__ __launch_bounds__(256) void k_tail_count(DScene sc, uint32_t obj_begi
     float t_so_far = -1.0f;
     if (!kFirst) t_so_far = ldnt(&hits.tp[s]).x;
     hit = t_so_far >= 0.0f;
+    float through_x = 1.0f;  // (kRoulette: d4.w, from the sphere run's own load of the ray when there is one)
     if (kSpheres) {
-      Ray ray = load_ray(paths, s);
+      Ray ray = kRoulette ? load_ray(paths, s, through_x) : load_ray(paths, s);
       if (hit) ray.tmax = t_so_far;
       Hit rec;
       bool changed = false;
@@ -338,8 +344,14 @@ __global__ __launch_bounds__(256) void k_tail_count(DScene sc, uint32_t obj_begi
     } else if (kEmit && hit) {
       hit = !is_emitter(sc.materials[__float_as_uint(ldnt(&hits.nm[s]).w) & 0x7fffffffu]);
     }
+    if (kRoulette && hit) {  // (the host picks a kRoulette instance for no last bounce: every hit that goes on plays)
+      const float2 t2 = bounce == 0 ? make_float2(1.0f, 1.0f) : ldnt(&paths.t2[s]);
+      if (!kSpheres) through_x = ldnt(&paths.d4[s]).w;
+      f3 c = mk3(bounce == 0 ? 1.0f : through_x, t2.x, t2.y);
+      hit = !roulette_ends(c, (slot_base ? *slot_base : 0u) + s, bi.iteration[frame], (uint32_t)bounce);
+    }
   }
-  const uint64_t live = __ballot(hit);  // (kEmit: hits that go on)
+  const uint64_t live = __ballot(hit);  // (kEmit, kRoulette: hits that go on)
   if ((threadIdx.x & 63u) == 0u) chunk_counts[s / kChunk] = (uint32_t)__popcll(live);
 }
 
@@ -390,8 +402,8 @@ __global__ __launch_bounds__(1024) void k_scan(int bounce, int last_bounce, cons
 // every path that ends at this bounce.
 // staged: `fb` is the slot's staging buffer (one sample per frame of the batch, plain stores); k_accumulate then
 // folds the staged samples into the real framebuffer in iteration order.  Otherwise the running mean goes
-// straight into `fb`.  kEmit: as k_tail_count's (the chunk offsets count the paths that go on).
-template <bool kEmit = false>
+// straight into `fb`.  kEmit, kRoulette: as k_tail_count's (the chunk offsets count the paths that go on).
+template <bool kEmit = false, bool kRoulette = false>
 __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out, DHits hits, int staged, int bounce,
                                                int last_bounce, const uint32_t* slot_base, const uint32_t* chunk_offsets,
                                                DFrame fb, DBand band, DeviceCounters* counters, uint8_t* octs, DBatchInfo bi)
@@ -452,9 +464,13 @@ __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out,
       rng.discard((uint32_t)bounce);
       const f3 hp = mk3(tp.y, tp.z, tp.w);
       const bool emits = kEmit && is_emitter(m);
+      // roulette: the path ends with the sample (0, 0, 0) and no draw, or goes on with its throughput divided (section 5h)
+      // (the host picks a kRoulette instance for no last bounce)
+      const bool ended = kRoulette && !emits && roulette_ends(color, slot, iteration, (uint32_t)bounce);
       if (emits) color = emit_color(color, m);  // the path ends at the emitter: no draw
+      else if (ended) color = mk3(0.0f, 0.0f, 0.0f);
       else evaluate_material(ro, rd, tmin_flag, hp, hn, ms >> 31, m, rng, color);
-      if (last_bounce || emits) {
+      if (last_bounce || emits || ended) {
         accumulate_color(fb.color4, local_pixel, acc_iteration, color);  // capped paths deposit raw throughput
       } else {
         survives = true;
@@ -501,7 +517,7 @@ __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out,
 #include "pt_shade_tile.inc"
 
 
-template <bool kSpheres, bool kFirst, bool kNext = false, bool kEmit = false>
+template <bool kSpheres, bool kFirst, bool kNext = false, bool kEmit = false, bool kRoulette = false>
 // (occupancy bounds re-measured on the final build: at least 5 or 6 wavefronts per SIMD forces spills, -8 % / -13 % end
 // to end; 1 to 3 compile to the same 124 registers)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PT_SHADE_WAVES, 8))) void k_shade_fused(DScene sc, uint32_t obj_begin, uint32_t obj_end, DPaths in, DPaths out, DHits hits,
@@ -564,7 +580,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PT_SHADE_WA
     next.hits.nm += fo;
     next.flags += fo;
   }
-  shade_tile<kSpheres, kFirst, 4, false, kNext, kEmit>(sc, obj_begin, obj_end, in, out, hits, staged, bounce, last_bounce, slot_base, tile_desc, epoch, fb, band,
+  shade_tile<kSpheres, kFirst, 4, false, kNext, kEmit, kRoulette>(sc, obj_begin, obj_end, in, out, hits, staged, bounce, last_bounce, slot_base, tile_desc, epoch, fb, band,
                                                 counters, octs, iteration, list, fo, tile, tiles, n, n_all, s_cnt, &s_excl, &next);
 }
 
@@ -718,12 +734,18 @@ void launch_list_flags(hipStream_t s, const uint8_t* flags, uint32_t max_paths, 
 }
 void launch_tail_count(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths paths,
                        DHits hits, uint32_t max_paths, int bounce, uint32_t* chunk_counts, DeviceCounters* counters,
-                       const DBatchInfo& bi, bool emitters)
+                       const DBatchInfo& bi, bool emitters, bool roulette, const uint32_t* slot_base)
 {
   const dim3 grid(div_up(max_paths, 256u), bi.count), block(256);
-#define PT_TAIL(SPH, FIRST, EMIT)                                                                                                  \
-  hipLaunchKernelGGL((k_tail_count<SPH, FIRST, EMIT>), grid, block, 0, s, scene, obj_begin < obj_end ? obj_begin : 0u,             \
-                     obj_begin < obj_end ? obj_end : 0u, paths, hits, bounce, chunk_counts, counters, bi)
+#define PT_TAIL_R(SPH, FIRST, EMIT, ROUL)                                                                                          \
+  hipLaunchKernelGGL((k_tail_count<SPH, FIRST, EMIT, ROUL>), grid, block, 0, s, scene, obj_begin < obj_end ? obj_begin : 0u,       \
+                     obj_begin < obj_end ? obj_end : 0u, paths, hits, bounce, chunk_counts, counters, bi, slot_base)
+  // (a bounce that plays roulette: the same six instances with kRoulette)
+#define PT_TAIL(SPH, FIRST, EMIT)                  \
+  do {                                             \
+    if (roulette) PT_TAIL_R(SPH, FIRST, EMIT, true); \
+    else PT_TAIL_R(SPH, FIRST, EMIT, false);       \
+  } while (0)
   if (obj_begin < obj_end) {
     if (first) {
       if (emitters) PT_TAIL(true, true, true);
@@ -739,6 +761,7 @@ void launch_tail_count(hipStream_t s, const DScene& scene, uint32_t obj_begin, u
     PT_TAIL(false, false, false);
   }
 #undef PT_TAIL
+#undef PT_TAIL_R
 }
 void launch_scan(hipStream_t s, int bounce, bool last_bounce, const uint32_t* chunk_counts, uint32_t* chunk_offsets,
                  DeviceCounters* counters, const DBatchInfo& bi)
@@ -749,26 +772,38 @@ void launch_scan(hipStream_t s, int bounce, bool last_bounce, const uint32_t* ch
 void launch_shade(hipStream_t s, const DScene& scene, DPaths in, DPaths out, DHits hits, uint32_t max_paths,
                   bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                   const uint32_t* chunk_offsets, DFrame fb, DBand band, DeviceCounters* counters, uint8_t* octs,
-                  const DBatchInfo& bi, bool emitters)
+                  const DBatchInfo& bi, bool emitters, bool roulette)
 {
-  if (emitters)
-    hipLaunchKernelGGL(k_shade<true>, dim3(div_up(max_paths, 256u), bi.count), dim3(256), 0, s, scene, in, out, hits,
-                       staged ? 1 : 0, bounce, last_bounce ? 1 : 0, slot_base, chunk_offsets, fb, band, counters, octs, bi);
-  else
-    hipLaunchKernelGGL(k_shade<false>, dim3(div_up(max_paths, 256u), bi.count), dim3(256), 0, s, scene, in, out, hits,
-                       staged ? 1 : 0, bounce, last_bounce ? 1 : 0, slot_base, chunk_offsets, fb, band, counters, octs, bi);
+#define PT_SHADE(EMIT, ROUL)                                                                                                  \
+  hipLaunchKernelGGL((k_shade<EMIT, ROUL>), dim3(div_up(max_paths, 256u), bi.count), dim3(256), 0, s, scene, in, out, hits, \
+                     staged ? 1 : 0, bounce, last_bounce ? 1 : 0, slot_base, chunk_offsets, fb, band, counters, octs, bi)
+  if (roulette) {  // (a bounce that plays roulette)
+    if (emitters) PT_SHADE(true, true);
+    else PT_SHADE(false, true);
+  } else if (emitters) {
+    PT_SHADE(true, false);
+  } else {
+    PT_SHADE(false, false);
+  }
+#undef PT_SHADE
 }
 void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths in, DPaths out,
                         DHits hits, uint32_t max_paths, bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                         unsigned long long* tile_desc, uint32_t tile_stride, uint32_t epoch, DFrame fb, DBand band,
                         DeviceCounters* counters, uint8_t* octs, const DBatchInfo& bi, const uint32_t* list, const DNextRun* next,
-                        bool emitters)
+                        bool emitters, bool roulette)
 {
   const dim3 grid(div_up(max_paths, kFuseTile) * bi.count), block(256);
   const DNextRun none{};
-#define PT_FUSED_E(SPH, FIRST, NEXT, EMIT)                                                                                                \
-  hipLaunchKernelGGL((k_shade_fused<SPH, FIRST, NEXT, EMIT>), grid, block, 0, s, scene, obj_begin, obj_end, in, out, hits, staged ? 1 : 0, \
+#define PT_FUSED_R(SPH, FIRST, NEXT, EMIT, ROUL)                                                                                                \
+  hipLaunchKernelGGL((k_shade_fused<SPH, FIRST, NEXT, EMIT, ROUL>), grid, block, 0, s, scene, obj_begin, obj_end, in, out, hits, staged ? 1 : 0, \
                      bounce, last_bounce ? 1 : 0, slot_base, tile_desc, tile_stride, epoch, fb, band, counters, octs, bi, list, next ? *next : none)
+  // (a bounce that plays roulette, DESIGN section 5h: the same instances with kRoulette; the caller asks for none at the last bounce)
+#define PT_FUSED_E(SPH, FIRST, NEXT, EMIT)                  \
+  do {                                                      \
+    if (roulette) PT_FUSED_R(SPH, FIRST, NEXT, EMIT, true); \
+    else PT_FUSED_R(SPH, FIRST, NEXT, EMIT, false);         \
+  } while (0)
   // (scenes with an emissive material: the same five instances with kEmit)
 #define PT_FUSED(SPH, FIRST, NEXT)          \
   do {                                      \
@@ -788,6 +823,7 @@ void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, 
   }
 #undef PT_FUSED
 #undef PT_FUSED_E
+#undef PT_FUSED_R
 }
 uint32_t shade_tiles_per_frame(uint32_t max_paths) { return div_up(max_paths, kFuseTile); }
 void launch_sort_octant(hipStream_t s, const uint8_t* octs, uint32_t* order, uint32_t max_paths, int bounce,

@@ -63,7 +63,12 @@ __device__ __forceinline__ void st_out(float4* base, uint32_t index, const float
 // an emitter ends at this bounce, so the survivor ballot of phase 1 needs the hit's material: the hit record's nm is then
 // loaded in phase 1 (phase 2 finds it in registers) and the material's type read from the table.  Without emitters nm
 // waits for phase 2 as before, and the instance is the one that ran before emitters existed.
-template <bool kSpheres, bool kFirst, int kGroupWaves, bool kCoherent, bool kNext = false, bool kEmit = false>
+// kRoulette: the bounce plays Russian roulette ("roulette", DESIGN section 5h; the host picks the instance for the bounces that
+// play, never the last one).  A path that would go on may end by chance, so the survivor ballot of phase 1 needs the decision:
+// the throughput that came into the bounce (d4.w, t2) is loaded with the ray, the roulette stream's draw is made in phase 1 and
+// a survivor's division is applied to the registers phase 2 reads its throughput from; a path that ends is remembered for phase
+// 2, which gives it no material draw and the sample (0, 0, 0).  The count still goes out after one round trip.
+template <bool kSpheres, bool kFirst, int kGroupWaves, bool kCoherent, bool kNext = false, bool kEmit = false, bool kRoulette = false>
 __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_begin, const uint32_t obj_end, const DPaths in, const DPaths out,
                                            const DHits hits, const int staged, const int bounce, const int last_bounce, const uint32_t* slot_base,
                                            unsigned long long* tile_desc, const uint32_t epoch, const DFrame fb, const DBand band,
@@ -72,12 +77,14 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
                                            uint32_t* s_excl, const DNextRun* next = nullptr)
 {
   static_assert(!kNext || (!kCoherent && !kFirst), "prefold: the per-bounce launches, behind a bounce that had a closest-hit launch");
+  static_assert(!kRoulette || !kCoherent, "roulette: the per-bounce launches (k_persist is not taught it)");
   constexpr uint32_t kThreads = 64u * (uint32_t)kGroupWaves, kTile = kThreads * (uint32_t)kFuseK;
   const uint32_t acc_iteration = staged ? 0u : iteration;
   const uint32_t wave = threadIdx.x >> 6;
   // ---- phase 1: rays and hits of the tile; the closest hit is final after the trailing sphere run ----
   float4 o4[kFuseK], d4[kFuseK], tp[kFuseK], nm[kFuseK];
-  uint32_t have_nm = 0u, hit_mask = 0u;
+  float2 t2[kFuseK];  // (throughput: d4.w, t2.x, t2.y -- DPaths)
+  uint32_t have_nm = 0u, hit_mask = 0u, ended_mask = 0u;
   uint32_t slot_of[kFuseK];  // position tile * kFuseTile + j * 256 + thread of the walk -> slot (the same unless `list`)
 #pragma unroll
   for (int j = 0; j < kFuseK; ++j) {
@@ -89,10 +96,12 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
     const uint32_t s = slot_of[j];
     tp[j] = make_float4(-1.0f, 0.f, 0.f, 0.f);
     nm[j] = o4[j] = d4[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (kRoulette) t2[j] = make_float2(0.f, 0.f);
     if (s < n_all) {
       o4[j] = ld_in<kCoherent>(in.o4, s);
       d4[j] = ld_in<kCoherent>(in.d4, s);
       if (!kFirst) tp[j] = ld_in<kCoherent>(hits.tp, s);
+      if (kRoulette) t2[j] = bounce != 0 ? ld_in<kCoherent>(in.t2, s) : make_float2(1.0f, 1.0f);
     }
   }
   // the sphere run that ends the object list: every lane with its own candidates, all its slots at once, when the run
@@ -134,16 +143,27 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
       }
       goes_on = !is_emitter(sc.materials[__float_as_uint(nm[j].w) & 0x7fffffffu]);
     }
+    if (kRoulette && goes_on) {  // (exactly the paths the ballot below counts: the host picks a kRoulette instance for no last bounce)
+      f3 c = mk3(bounce == 0 ? 1.0f : d4[j].w, t2[j].x, t2[j].y);
+      if (roulette_ends(c, (slot_base ? *slot_base : 0u) + s, iteration, (uint32_t)bounce)) {
+        goes_on = false;
+        ended_mask |= 1u << j;
+      } else {  // (q >= 1: the same bits)
+        d4[j].w = c.x;
+        t2[j] = make_float2(c.y, c.z);
+      }
+    }
     const uint64_t live = __ballot(goes_on && !last_bounce);
     if ((threadIdx.x & 63u) == 0u) s_cnt[j * kGroupWaves + (int)wave] = (uint32_t)__popcll(live);
   }
   // what phase 2 still needs from memory, requested before anybody waits for anything
-  float2 t2[kFuseK];  // (throughput: d4.w, t2.x, t2.y -- DPaths)
 #pragma unroll
   for (int j = 0; j < kFuseK; ++j) {
     const uint32_t s = slot_of[j];
-    t2[j] = make_float2(0.f, 0.f);
-    if (s < n_all && bounce != 0) t2[j] = ld_in<kCoherent>(in.t2, s);  // (bounce 0: throughput 1, k_raygen does not write it)
+    if (!kRoulette) {  // (a roulette instance has it already)
+      t2[j] = make_float2(0.f, 0.f);
+      if (s < n_all && bounce != 0) t2[j] = ld_in<kCoherent>(in.t2, s);  // (bounce 0: throughput 1, k_raygen does not write it)
+    }
     if (!kFirst && (hit_mask >> j & 1u) && !(have_nm >> j & 1u)) nm[j] = ld_in<kCoherent>(hits.nm, s);
   }
   if (kGroupWaves > 1) __syncthreads();
@@ -175,14 +195,16 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
       DMaterial m{(int32_t)kKindMiss, {0.f, 0.f, 0.f, 0.f}};  // (a hit's type is 0..2, or 3 in a kEmit instance: validate_scene)
       if (is_hit) m = sc.materials[ms & 0x7fffffffu];
       const bool emits = kEmit && is_hit && is_emitter(m);  // (phase 1 counted it out)
+      const bool ended = kRoulette && (ended_mask >> j & 1u) != 0u;  // (roulette, phase 1: no draw, the sample is 0)
       if (bounce == 0) {
         if (is_hit) accumulate_nd(fb.nd4, local_pixel, acc_iteration, hn, tp[j].x);  // path_tracer.cu:308-311
         else accumulate_nd(fb.nd4, local_pixel, acc_iteration, -rd, 1e6f);           // raygen defaults, ray_gen.cu:26-28
       }
       const uint32_t slot = (slot_base ? *slot_base : 0u) + s;
-      shade_kinds<kEmit>(emits ? kKindEmit : (uint32_t)m.type, ro, rd, tmin_flag, mk3(tp[j].y, tp[j].z, tp[j].w), hn, ms >> 31, m, slot,
+      shade_kinds<kEmit>(ended ? kKindNone : emits ? kKindEmit : (uint32_t)m.type, ro, rd, tmin_flag, mk3(tp[j].y, tp[j].z, tp[j].w), hn, ms >> 31, m, slot,
                          iteration, (uint32_t)bounce, color);
-      if (!is_hit || last_bounce || emits) {
+      if (ended) color = mk3(0.0f, 0.0f, 0.0f);
+      if (!is_hit || last_bounce || emits || ended) {
         // a miss ends the path with throughput * sky (path_tracer.cu:304-307, 283-289), an emitter with throughput * emission;
         // capped paths deposit raw throughput
         accumulate_color(fb.color4, local_pixel, acc_iteration, color);
@@ -210,9 +232,11 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
         rng.discard((uint32_t)bounce);
         const f3 hp = mk3(tp[j].y, tp[j].z, tp[j].w);
         const bool emits = kEmit && is_emitter(m);
+        const bool ended = kRoulette && (ended_mask >> j & 1u) != 0u;  // (roulette, phase 1: no draw, the sample is 0)
         if (emits) color = emit_color(color, m);  // the path ends at the emitter: no draw
+        else if (ended) color = mk3(0.0f, 0.0f, 0.0f);
         else evaluate_material(ro, rd, tmin_flag, hp, hn, ms >> 31, m, rng, color);
-        if (last_bounce || emits) {
+        if (last_bounce || emits || ended) {
           accumulate_color(fb.color4, local_pixel, acc_iteration, color);  // capped paths deposit raw throughput
         } else {
           surv_mask |= 1u << j;

@@ -216,6 +216,7 @@ const ParamRow kParams[] = {
      [](ptc_ctx* c, int v) { c->scene.refill_lanes = c->refill_lanes = (uint32_t)v; }},
     {"ray_sort", 0, 1, k01, kBeforeResize, [](ptc_ctx* c, int v) { c->ray_sort = v; }},
     {"direct_light", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->direct_light = v != 0; }},
+    {"roulette", 0, 64, " must be in [0,64]", kAnyTime, [](ptc_ctx* c, int v) { c->roulette = v; }},
     {"denoise_variant", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_variant = v; }},
     {"frames_in_flight", 1, 256, " must be in [1,256]", kBeforeResize, [](ptc_ctx* c, int v) { c->frames_in_flight = v; }},
 };

@@ -267,6 +267,8 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
 
   // "direct_light" (DESIGN section 5g): the megakernel draws a light sample at every diffuse hit (k_megakernel_direct)
   bool direct_light = false;
+  // "roulette" (DESIGN section 5h): Russian roulette at every bounce >= this, the last bounce excepted; 0 = off
+  int roulette = 0;
   unsigned long long* loop_stats = nullptr;  // device: kLightStatLines lines of kLoopStatWords words (diffuse hits, shadow rays, unoccluded)
   bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
 };

@@ -80,6 +80,13 @@ uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
   return 1u;
 }
 
+// "roulette" (DESIGN section 5h): does bounce `bounce` of a frame play Russian roulette?  From bounce `roulette` on, never the last
+// bounce (capped paths deposit raw throughput as ever); 0 is off.  The kernels that end such a bounce are the roulette instances,
+// every other bounce launches what it launched before the parameter existed.
+bool roulette_bounce(const ptc_ctx* ctx, int bounce) { return ctx->roulette >= 1 && bounce >= ctx->roulette && bounce < ctx->max_bounces - 1; }
+// ... does any bounce of a frame?
+bool roulette_frame(const ptc_ctx* ctx) { return ctx->roulette >= 1 && ctx->roulette < ctx->max_bounces - 1; }
+
 // ---- the decisions of the launch plan (ptc_ctx::TraceLaunch), each in one place -------------------------------------------
 
 // What opens the object list: a traversal launch with nothing in front of it, a sphere run in front of the first traversal
@@ -313,6 +320,7 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
   // the end of the bounce: the sphere run that ends the object list + the live counts and their scan + the materials
   const ObjectRange tail = tail_run(ctx, scene);
   uint8_t* octs = ctx->ray_sort && !last ? sl.octs : nullptr;
+  const bool roulette = roulette_bounce(ctx, bounce);
   if (ctx->fused_shade) {
     // one pass: trailing spheres + material + stable compaction (decoupled look-back) + final gather
     next_epoch(sl);
@@ -322,17 +330,17 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
     const DNextRun next = prefold ? next_run(ctx, sl.hits_other, sl.next_flags) : DNextRun{};
     launch_shade_fused(sl.stream, scene, tail.begin, tail.end, !wrote, in, out, sl.hits, ctx->pix_count, ctx->staged, bounce, last,
                        slot_base_dev, sl.tile_desc, sl.tile_stride, sl.shade_epoch, sl.stage, ctx->band, sl.counters, octs, sl.bi,
-                       bounce == 0 && sl.primary_finished ? sl.worklist : nullptr, prefold ? &next : nullptr, ctx->has_emitters);
+                       bounce == 0 && sl.primary_finished ? sl.worklist : nullptr, prefold ? &next : nullptr, ctx->has_emitters, roulette);
     if (prefold) {
       std::swap(sl.hits, sl.hits_other);
       sl.prefolded = true;
     }
   } else {
     launch_tail_count(sl.stream, scene, tail.begin, tail.end, !wrote, in, sl.hits, ctx->pix_count, bounce, sl.chunk_counts, sl.counters,
-                      sl.bi, ctx->has_emitters);
+                      sl.bi, ctx->has_emitters, roulette, slot_base_dev);
     launch_scan(sl.stream, bounce, last, sl.chunk_counts, sl.chunk_offsets, sl.counters, sl.bi);
     launch_shade(sl.stream, scene, in, out, sl.hits, ctx->pix_count, ctx->staged, bounce, last, slot_base_dev,
-                 sl.chunk_offsets, sl.stage, ctx->band, sl.counters, octs, sl.bi, ctx->has_emitters);
+                 sl.chunk_offsets, sl.stage, ctx->band, sl.counters, octs, sl.bi, ctx->has_emitters, roulette);
   }
   sl.cur ^= 1;
   sl.bounces_done = bounce + 1;
@@ -343,10 +351,11 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
 // The launch plan must be the simplest one -- every bounce is one traversal launch over one mesh object with nothing in front
 // of it, then the kernel that ends the bounce (a sphere run may end the object list) --, the shade pass the fused one, no ray
 // sorting, staged samples, no instrumentation (the counting runs and the per-launch events keep the per-bounce launches:
-// same results), and slots must fit the 26 bits a lane keeps them in.
+// same results), no bounce that plays roulette (k_persist is not taught it, section 5h: the per-bounce launches render such a
+// frame, with the same bits), and slots must fit the 26 bits a lane keeps them in.
 bool persist_ok(const ptc_ctx* ctx, int count)
 {
-  if (!ctx->persist || ctx->trace_variant != 3 || !ctx->fused_shade || ctx->ray_sort || !ctx->staged) return false;
+  if (!ctx->persist || ctx->trace_variant != 3 || !ctx->fused_shade || ctx->ray_sort || !ctx->staged || roulette_frame(ctx)) return false;
   if (ctx->count_tests || ctx->max_bounces < 2 || count < (int)ctx->persist_min_frames) return false;
   if (ctx->launches.size() != 1u || plan_opens(ctx) != Opens::launch || launch_run(ctx, 0) != 1u) return false;
   const auto& sl = ctx->slots[(size_t)ctx->active_slot];
@@ -625,7 +634,10 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
       const DLights lights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
                            ctx->scene.materials};
       launch_megakernel_direct(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
-                               ctx->max_bounces, ctx->fb, sl.counters, ctx->loop_stats);
+                               ctx->max_bounces, ctx->fb, sl.counters, ctx->loop_stats, ctx->roulette);
+    } else if (roulette_frame(ctx)) {  // some bounce plays roulette
+      launch_megakernel_roulette(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces,
+                                 ctx->fb, sl.counters, ctx->has_emitters, ctx->roulette);
     } else {
       launch_megakernel(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
                         ctx->max_bounces, ctx->fb, sl.counters, ctx->has_emitters);

@@ -49,6 +49,7 @@ struct CliConfigurations {  // configurations.hpp:11-15
   bool denoise = false;
   bool megakernel = false;
   bool direct_light = false;
+  int roulette = 0;
   int gpu = 0;
   int gpus = 1;
   std::optional<std::string> dump_scene;
@@ -69,6 +70,7 @@ void usage()
                "      --denoise        run the A-Trous denoiser before writing the image\n"
                "      --method M       streaming (default) | megakernel\n"
                "      --direct-light   a light sample with a shadow ray at every diffuse hit (needs --method megakernel)\n"
+               "      --roulette K     Russian roulette at every bounce >= K but the last, unbiased (0 = off, the default; K in [0,64])\n"
                "      --gpu N          HIP device ordinal\n"
                "      --gpus N         split the frame's rows over N processes / GPUs (rank r on device r %% device count)\n"
                "      --dump-scene F   write the flattened scene to F and exit (no GPU needed)\n"
@@ -101,6 +103,17 @@ CliConfigurations parse_cli_args(int argc, char** argv)
     else if (a == "--denoise") c.denoise = true;
     else if (a == "--method") c.megakernel = need("method") == "megakernel";
     else if (a == "--direct-light") c.direct_light = true;
+    else if (a == "--roulette") {
+      // a whole decimal number in [0, 64] (ptc_set_param's range), refused here: before the scene is read or a GPU touched
+      const std::string v = need("roulette");
+      int k = -1;
+      if (!v.empty() && v.size() <= 2 && v.find_first_not_of("0123456789") == std::string::npos) k = std::stoi(v);
+      if (k < 0 || k > 64) {
+        std::fprintf(stderr, "Option '--roulette': '%s' is not a number in [0,64]\n", v.c_str());
+        std::exit(1);
+      }
+      c.roulette = k;
+    }
     else if (a == "--gpu") c.gpu = std::stoi(need("gpu"));
     else if (a == "--gpus") c.gpus = std::stoi(need("gpus"));
     else if (a == "--dump-scene") c.dump_scene = need("dump-scene");
@@ -260,6 +273,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   DisplayBufferType display = configs.display;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
+  path_tracer.roulette = configs.roulette;
 
   int shown = 0;
   std::vector<uchar4> buffer;
@@ -364,6 +378,7 @@ try {
   path_tracer.max_bounces = configs.max_bounces;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
+  path_tracer.roulette = configs.roulette;
   path_tracer.create_buffers(resolution, scene_desc);
   auto check = [&](int rc, const char* what) {
     if (rc < 0) throw std::runtime_error(std::string(what) + ": " + ptc_last_error(path_tracer.handle()));
@@ -539,6 +554,7 @@ try {
   path_tracer.max_bounces = configs.max_bounces;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
+  path_tracer.roulette = configs.roulette;
   path_tracer.create_buffers(resolution, scene_desc);
   path_tracer.synchronize();
   std::printf("Start path tracing\nspp: %d\nwidth: %u, height: %u\n", spp, resolution.width, resolution.height);

@@ -39,6 +39,7 @@ public:
   int max_iterations = 1;
   GPUMethod current_gpu_method = GPUMethod::streaming;
   bool direct_light = false;  // a light sample at every diffuse hit (megakernel method only; ptc_set_param "direct_light")
+  int roulette = 0;  // Russian roulette at every bounce >= this but the last, 0 = off (both methods; ptc_set_param "roulette", [0, 64])
   EdgeAvoidingATrousDenoiser atrous_denoiser{};
   int max_bounces = 50;  // reference: compile-time constant, path_tracer.cu:27
 
@@ -109,6 +110,10 @@ private:
       check(ptc_set_param(ctx_, "direct_light", direct_light ? 1 : 0), "direct_light");
       direct_light_pushed_ = direct_light;
     }
+    if (roulette != roulette_pushed_) {
+      check(ptc_set_param(ctx_, "roulette", roulette), "roulette");
+      roulette_pushed_ = roulette;
+    }
     check(ptc_set_max_bounces(ctx_, max_bounces), "max_bounces");
     const ptc_denoiser_params p{atrous_denoiser.filter_size, atrous_denoiser.color_weight, atrous_denoiser.normal_weight,
                                 atrous_denoiser.position_weight};
@@ -120,6 +125,7 @@ private:
   }
   ptc_ctx* ctx_ = nullptr;
   bool direct_light_pushed_ = false;
+  int roulette_pushed_ = 0;
 };
 
 }  // namespace hip_pt

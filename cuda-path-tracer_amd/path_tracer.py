@@ -88,6 +88,7 @@ class PathTracer:
         self.max_iterations = 1
         self.current_gpu_method = GPUMethod.streaming
         self._direct_light = False  # PathTracer.direct_light = True: a light sample at every diffuse hit (megakernel method only)
+        self._roulette = 0  # PathTracer.roulette = k: Russian roulette at every bounce >= k but the last (0 = off)
         self.atrous_denoiser = EdgeAvoidingATrousDenoiser()
         self.max_bounces = max_bounces  # reference: compile-time 50 (path_tracer.cu:27)
         cfg = _capi.ptc_config(device=device, max_bounces=max_bounces, method=int(self.current_gpu_method), reserved=0)
@@ -97,6 +98,7 @@ class PathTracer:
         self._resolution = None
         self._rows = None
         self._direct_light_pushed = False
+        self._roulette_pushed = 0
 
     # -- lifetime -------------------------------------------------------------------------------
     def close(self):
@@ -129,12 +131,28 @@ class PathTracer:
     def direct_light(self, on):
         self._direct_light = bool(on)
 
+    @property
+    def roulette(self):
+        """Russian roulette (ptc_set_param "roulette"): 0 = off (the default); k >= 1 = a path may end by chance at
+        every bounce >= k except the last, unbiased, in both render methods.  An int in [0, 64]."""
+        return self._roulette
+
+    @roulette.setter
+    def roulette(self, k):
+        k = int(k)
+        if not 0 <= k <= 64:
+            raise ValueError("roulette must be in [0,64]")
+        self._roulette = k
+
     def _push_fields(self):
         self._check(self._lib.ptc_set_max_iterations(self._ctx, int(self.max_iterations)))
         self._check(self._lib.ptc_set_method(self._ctx, int(self.current_gpu_method)))
         if self._direct_light != self._direct_light_pushed:  # (ptc_set_param flushes queued frames: only on a change)
             self._check(self._lib.ptc_set_param(self._ctx, b"direct_light", 1 if self._direct_light else 0))
             self._direct_light_pushed = self._direct_light
+        if self._roulette != self._roulette_pushed:
+            self._check(self._lib.ptc_set_param(self._ctx, b"roulette", self._roulette))
+            self._roulette_pushed = self._roulette
         self._check(self._lib.ptc_set_max_bounces(self._ctx, int(self.max_bounces)))
         d = self.atrous_denoiser
         p = _capi.ptc_denoiser_params(int(d.filter_size), float(d.color_weight), float(d.normal_weight),

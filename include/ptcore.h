@@ -336,6 +336,16 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *                      sampled (ptc_light_table) makes ptc_trace fail with PTC_ERR_INVALID, naming the object.  Under
  *                      PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is 1, before anything is
  *                      queued: the streaming loop does not render direct light.  Counters: ptc_get_direct_loop_stats.  Any time
+ *   "roulette"         RENDERING (default 0 = off; an extension): k in [1, 64] = Russian roulette at every bounce b >= k
+ *                      except the last one, under both methods (and "direct_light").  A path whose closest hit exists and is no emitter
+ *                      takes q = the largest component of the throughput that came into the bounce; q >= 1 changes nothing (no draw); else
+ *                      one draw u from a random stream of its own (path_seed(slot or pixel, iteration) ^ 0x52524c54, discard(b)): u < q
+ *                      divides the throughput by q and the bounce goes on as ever, otherwise the path ends with the sample (0, 0, 0) and
+ *                      no material draw.  The expectation of every pixel is unchanged (the variance may rise); bounce 0 never plays, so
+ *                      normal and depth are bit for bit those of 0; ptc_stats.rays_total and the live counts fall.  0, and any
+ *                      k >= max_bounces - 1, launch exactly what was launched before the parameter existed.  A frame with a bounce that
+ *                      plays is not eligible for "persist" (k_persist is not taught roulette): it renders through the per-bounce
+ *                      launches, with the same bits.  Any time (queued frames are flushed first)
  *   "pair_batches"     SCHEDULE (round 5; default 0): 1 = a full batch is held until the next one is full (or anything else looks at
  *                      the context); the two are enqueued bounce by bounce on two slots and their traversal launches take turns.
  *                      Bit-identical, measured 6-7 % slower than the default (profiles/r05_pair_batches.txt): off.  Any time
