@@ -3,52 +3,26 @@ manner of lit_ref.py.  Three things, none of them the thing under test:
 
   (a) light_table: the lamp table in numpy -- the records in binary32 with the operations of the library's instance triangles
       (transform_point, edge differences, normalize(cross)), weights / running sum / cdf in binary64 from the records' fields;
-  (b) sample / query: one light sample per point in numpy binary32, one numpy operation per source operation of k_light_sample
-      in the order DESIGN section 5f writes down (numpy does not contract into FMA); its pinned pieces are the oracle's
-      orc_path_seed, orc_rng_seed / orc_rng_uniform (the draws), orc_sincos and intersect_rays (the shadow rays);
+  (b) light_sample / sample / query: one light sample per point in numpy binary32, one numpy operation per source operation of
+      light_sample_point in the order DESIGN section 5f writes down (numpy does not contract into FMA); its pinned pieces are the
+      oracle's orc_path_seed, orc_rng_seed / orc_rng_uniform (the draws: ref_f32.stream_draws), orc_sincos and intersect_rays (the
+      shadow rays).  light_sample takes its draws from the caller: the query (sample) and the render loop (lit_ref.render_megakernel,
+      section 5g) key their light streams differently and share everything else;
   (c) estimate_f64 and the truths: a float64 Monte-Carlo estimator written from the formula
           Le cos_r cos_l / (pi d^2 pdf_area) * visibility
       with numpy's own generator and analytic visibility, a closed form (sphere lamp) and a midpoint quadrature (panel lamp).
       Nothing in (c) calls (b).
 
 Also the scenes and seeded points the CPU and GPU tests share."""
-import ctypes as C
-
 import numpy as np
 
-F = np.float32
-PI = F(3.14159265358979323846264338327950288)   # pi_f, the constant of lit_ref.py
-PI2 = F(2.0) * PI
+from ref_f32 import PI, PI2, F, _cross, _dot, _normalize, _sincos, _xform_point, stream_draws
+
 SEED_XOR = 0x4C495445                            # kLightSeedXor (pt_device.hpp)
 T_MIN = F(1e-4)
 LIGHT_DTYPE = np.dtype([("p0", "<f4", (3,)), ("e1", "<f4", (3,)), ("e2", "<f4", (3,)), ("n", "<f4", (3,)), ("cdf", "<f4"),
                         ("inv_pdf", "<f4"), ("object", "<u4"), ("kind_material", "<u4")])
 EMISSIVE = 3
-
-
-# ---- binary32 pieces (glm order, as pt_math.hpp) -------------------------------------------------------------------------
-def _dot(a, b):
-    t = a * b
-    return (t[..., 0] + t[..., 1]) + t[..., 2]
-
-
-def _cross(a, b):
-    return np.stack([a[..., 1] * b[..., 2] - b[..., 1] * a[..., 2], a[..., 2] * b[..., 0] - b[..., 2] * a[..., 0],
-                     a[..., 0] * b[..., 1] - b[..., 0] * a[..., 1]], axis=-1)
-
-
-def _normalize(v):
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return v * (F(1.0) / np.sqrt(_dot(v, v)))[..., None]
-
-
-def _xform_point(m16, p):
-    """transform_point: (M * (p, 1)).xyz / w with mat4 * vec4 = (c0 x + c1 y) + (c2 z + c3 w); m16 column-major."""
-    m = np.asarray(m16, dtype=np.float32)
-    p = np.asarray(p, dtype=np.float32)
-    x, y, z = p[..., 0], p[..., 1], p[..., 2]
-    row = [(m[0 + r] * x + m[4 + r] * y) + (m[8 + r] * z + m[12 + r] * F(1.0)) for r in range(4)]
-    return np.stack([row[0] / row[3], row[1] / row[3], row[2] / row[3]], axis=-1)
 
 
 # ---- (a) the table -------------------------------------------------------------------------------------------------------
@@ -127,41 +101,17 @@ def select(cdf, last, u0):
 
 
 # ---- (b) the sample, binary32 ---------------------------------------------------------------------------------------------
-def _draws(orc, n, sample_index, first=0):
-    h = orc.lib()
-    u = np.empty((n, 3), dtype=np.float32)
-    st = C.c_uint32()
-    for i in range(n):
-        st.value = h.orc_rng_seed(h.orc_path_seed(first + i, sample_index) ^ SEED_XOR)
-        u[i, 0] = h.orc_rng_uniform(C.byref(st))
-        u[i, 1] = h.orc_rng_uniform(C.byref(st))
-        u[i, 2] = h.orc_rng_uniform(C.byref(st))
-    return u
-
-
-def _sincos(orc, phi):
-    s, c = np.empty_like(phi), np.empty_like(phi)
-    fs, fc = C.c_float(), C.c_float()
-    h = orc.lib()
-    for k, x in enumerate(phi):
-        h.orc_sincos(float(x), C.byref(fs), C.byref(fc))
-        s[k], c[k] = fs.value, fc.value
-    return s, c
-
-
-def sample(orc, flat, points, normals, sample_index, table=None):
-    """k_light_sample: -> dict(rays [n, 8] as ptc_direct_light returns them, contribution [n, 3] (unshadowed), sampled bool[n],
-    lamp int[n]).  Point i draws from the generator of index i."""
-    recs, _, weights, last = table if table is not None else light_table(flat)
-    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
-    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+def light_sample(orc, flat, table, p, nrm, u):
+    """light_sample_point for points p [n, 3] with normals nrm and draws u [n, 3] (item 1: whose they
+    are is the caller's business): -> dict(rays [n, 8] as ptc_direct_light returns them, contribution [n, 3] (unshadowed), sampled
+    bool[n], lamp int[n]).  table = light_table(flat), total weight > 0."""
+    recs, _, _, last = table
     n = len(p)
     rays = np.zeros((n, 8), dtype=np.float32)
     rays[:, 0:3], rays[:, 3] = p, T_MIN
     contribution = np.zeros((n, 3), dtype=np.float32)
-    if len(recs) == 0 or not float(np.sum(weights)) > 0.0:
-        return {"rays": rays, "contribution": contribution, "sampled": np.zeros(n, dtype=bool), "lamp": np.zeros(n, dtype=np.int64)}
-    u = _draws(orc, n, sample_index)
+    if n == 0:
+        return {"rays": rays, "contribution": contribution, "sampled": np.zeros(0, dtype=bool), "lamp": np.zeros(0, dtype=np.int64)}
     u0, u1, u2 = u[:, 0], u[:, 1], u[:, 2]
     k = select(recs["cdf"], last, u0)
     r = recs[k]
@@ -209,6 +159,21 @@ def sample(orc, flat, points, normals, sample_index, table=None):
     rays[sampled, 4:7] = w[sampled]
     rays[sampled, 7] = tmax[sampled]
     return {"rays": rays, "contribution": contribution, "sampled": sampled, "lamp": k}
+
+
+def sample(orc, flat, points, normals, sample_index, table=None):
+    """k_light_sample: light_sample for every point, point i with the first three draws of the generator of index i.  A scene
+    without a lamp of weight > 0 samples nothing."""
+    table = table if table is not None else light_table(flat)
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    n = len(p)
+    if len(table[0]) == 0 or not float(np.sum(table[2])) > 0.0:
+        rays = np.zeros((n, 8), dtype=np.float32)
+        rays[:, 0:3], rays[:, 3] = p, T_MIN
+        return {"rays": rays, "contribution": np.zeros((n, 3), dtype=np.float32), "sampled": np.zeros(n, dtype=bool),
+                "lamp": np.zeros(n, dtype=np.int64)}
+    return light_sample(orc, flat, table, p, nrm, stream_draws(orc, range(n), sample_index, SEED_XOR, 0, 3))
 
 
 def query(orc, flat, points, normals, sample_index, table=None, scene_handle=None):

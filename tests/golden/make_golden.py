@@ -14,6 +14,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+if os.path.dirname(HERE) not in sys.path:
+    sys.path.insert(1, os.path.dirname(HERE))  # tests/: loop_ref_cases imports the restatements
 import __graft_entry__ as graft  # noqa: E402
 
 pkg = graft.load_package()
@@ -123,6 +125,83 @@ def main_interleaved():
     print("wrote", os.path.join(HERE, "interleaved.npz"))
 
 
+LOOP_REF = dict(w=16, h=12, iterations=2, max_bounces=6, block_rows=2, far_iteration=1000003, points=256, points_seed=11)
+LOOP_REF_STREAMING = ("color", "normal", "depth", "live", "rays", "played", "ended", "skipped")
+LOOP_REF_MEGAKERNEL = ("color", "normal", "depth", "rays", "diffuse_hits", "shadow_rays", "unoccluded", "played", "ended", "skipped")
+
+
+def loop_ref_cases():
+    """The arrays of tests/golden/loop_ref.npz: what the numpy restatements of the render loops (tests/lit_ref.py) and of the
+    light sample (tests/direct_ref.py) return, at the CPU tests' shape -- every option of either loop, a rank of an interleaved
+    pair, a continuation from a frame, a far iteration, scenes with metal and glass, a lamp behind glass and no lamp.  The file
+    was written by the restatements as they stood when each loop still had a copy per feature; it pins the CHECKER's bits (the
+    oracle cannot: it has no emitters, light samples or roulette), and tests/test_loop_ref_golden_cpu.py holds today's to it."""
+    import direct_loop_scenes as scenes
+    import direct_ref as dr
+    import lit_ref as lr
+    c = LOOP_REF
+    w, h, n, mb = c["w"], c["h"], c["iterations"], c["max_bounces"]
+    out = {}
+
+    def streaming(name, scene, flat, sh, roulette, iter_begin=0, iter_count=n, **kw):
+        r = lr.render_streaming(orc, flat, scene.camera, w, h, iter_begin, iter_count, mb, roulette=roulette, scene_handle=sh, **kw)
+        assert roulette == 0 or r["ended"].sum() > 0, name
+        out.update({f"{name}_{k}": np.asarray(r[k]) for k in LOOP_REF_STREAMING})
+        return r
+
+    def megakernel(name, scene, flat, sh, direct, roulette, iter_begin=0, iter_count=n, **kw):
+        r = lr.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iter_count, mb, direct=direct, roulette=roulette,
+                                 scene_handle=sh, **kw)
+        assert roulette == 0 or r["ended"].sum() > 0, name
+        out.update({f"{name}_{k}": np.asarray(r[k]) for k in LOOP_REF_MEGAKERNEL})
+        return r
+
+    lit = pkg.scenes.cornell_lit(resolution=(w, h), with_mesh=True)
+    flat = lit.build_scene()
+    sh = orc.SceneHandle(flat)
+    for roulette in (0, 1, 3):
+        s = streaming(f"lit_streaming_r{roulette}", lit, flat, sh, roulette)
+        if roulette == 1:
+            streaming("lit_streaming_r1_continued", lit, flat, sh, 1, iter_begin=n, iter_count=1, prev=s)
+        for direct in (False, True):
+            m = megakernel(f"lit_megakernel_d{int(direct)}_r{roulette}", lit, flat, sh, direct, roulette)
+            if direct:
+                assert m["shadow_rays"] > m["unoccluded"] > 0, roulette
+                if roulette == 1:
+                    megakernel("lit_megakernel_d1_r1_continued", lit, flat, sh, True, 1, iter_begin=n, iter_count=1, prev=m)
+    pixels = lr.interleaved_pixels(w, h, 1, 2, c["block_rows"])
+    for roulette in (0, 1):
+        streaming(f"lit_rank1of2_r{roulette}", lit, flat, sh, roulette, pixels=pixels, slot_offset=w * h)
+    m = megakernel("lit_megakernel_d1_r1_far", lit, flat, sh, True, 1, iter_begin=c["far_iteration"])
+    assert m["shadow_rays"] > m["unoccluded"] > 0
+
+    both = scenes.metal_glass_scene(pkg)
+    flat_b = both.build_scene()
+    sh_b = orc.SceneHandle(flat_b)
+    for roulette in (0, 1):
+        megakernel(f"metal_glass_megakernel_d1_r{roulette}", both, flat_b, sh_b, True, roulette)
+    glass = scenes.glass_lamp_scene(pkg)
+    flat_g = glass.build_scene()
+    m = megakernel("glass_lamp_megakernel_d1_r0", glass, flat_g, orc.SceneHandle(flat_g), True, 0)
+    assert m["shadow_rays"] > 0 and m["unoccluded"] == 0
+    dark = pkg.scenes.cornell_spheres((w, h))
+    flat_d = dark.build_scene()
+    sh_d = orc.SceneHandle(flat_d)
+    streaming("no_lamp_streaming_r0", dark, flat_d, sh_d, 0)
+    megakernel("no_lamp_megakernel_d1_r0", dark, flat_d, sh_d, True, 0)
+
+    points, normals = dr.room_points(c["points"], c["points_seed"])
+    s = dr.sample(orc, flat, points, normals, dr.SAMPLE_INDEX)
+    assert s["sampled"].any() and not s["sampled"].all()
+    out.update({f"sample_{k}": np.asarray(s[k]) for k in ("rays", "contribution", "sampled", "lamp")})
+    return out
+
+
+def main_loop_ref():
+    np.savez_compressed(os.path.join(HERE, "loop_ref.npz"), **loop_ref_cases())
+    print("wrote", os.path.join(HERE, "loop_ref.npz"))
+
+
 def main():
     out = {}
     for name, (scene, w, h) in golden_scenes().items():
@@ -183,7 +262,10 @@ if __name__ == "__main__":
         main_multimesh()
     elif sys.argv[1:] == ["interleaved"]:
         main_interleaved()
+    elif sys.argv[1:] == ["loop_ref"]:
+        main_loop_ref()
     else:
         main()
         main_multimesh()
         main_interleaved()
+        main_loop_ref()

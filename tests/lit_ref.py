@@ -1,68 +1,35 @@
-"""CPU restatement of the render loops WITH emissive materials (ptc_material type 3), in numpy binary32.
+"""CPU restatement of the render loops WITH the library's extensions -- emissive materials (ptc_material type 3), direct lighting in
+the megakernel (ptc_set_param "direct_light") and Russian roulette (ptc_set_param "roulette", section 5h) -- in
+numpy binary32.  TEST INFRASTRUCTURE: the checker of tests/test_gpu_emissive.py, test_gpu_direct_loop.py and test_gpu_roulette.py,
+not the thing under test.  Each loop and each rule stands here once; a feature is an option of its loop.
 
-The reference has no emitters, so the oracle (oracle/oracle.c) cannot check them and stays as it is.  This file restates
+The reference has none of the three, so the oracle (oracle/oracle.c) cannot check them and stays as it is.  This file restates
 the oracle's streaming loop (oracle.c:1055-1125, and its interleaved-rows variant) and its megakernel loop (oracle.c:
-1283-1305) with the emissive rule added, built from the oracle's pinned pieces:
-  - orc_generate_ray (primary rays), orc_intersect_rays (closest hits, each bounce), orc_path_seed / orc_rng_* (every draw),
-    orc_sincos (random_in_unit_sphere);
+1283-1305) with the rules added, built from the oracle's pinned pieces:
+  - orc_generate_ray (primary rays), orc_intersect_rays (closest hits, each bounce; the HIT FLAG of the shadow rays),
+    orc_path_seed / orc_rng_* (every draw), orc_sincos (random_in_unit_sphere);
   - restated operation by operation: evaluate_material and random_in_unit_sphere (oracle.c:825-916), the sky, the stable
     partition on bounces_left, the cap (paths alive after the last bounce keep the colour the last bounce left) and the
-    running-mean gather.
+    running-mean gather; direct_ref.light_table / light_sample (the lamp table and section 5f's light sample).
 The emissive rule: a path whose closest hit has an emissive material ends at that bounce with colour * emission (a
 binary32 multiply per component, like the miss's colour * sky), makes no draw there, and drops out of the partition like a
-miss; at bounce 0 it records the hit's normal and t.  On scenes without emitters every result equals the oracle's bit for
-bit (tests/test_lit_ref_cpu.py): the restatement is the checker of tests/test_gpu_emissive.py, not the thing under test.
+miss; at bounce 0 it records the hit's normal and t.  The direct-light rule stands at render_megakernel, the roulette rule at
+play.  On scenes without emitters, with both options off, every result equals the oracle's bit for bit
+(tests/test_lit_ref_cpu.py); tests/golden/loop_ref.npz pins the bits of every option (tests/test_loop_ref_golden_cpu.py).
 Every numpy operation below is one binary32 operation of the C source, in its order (numpy does not contract into FMA)."""
 import ctypes as C
 
 import numpy as np
 
-F = np.float32
-PI2 = F(2.0) * F(3.14159265358979323846264338327950288)  # 2.f * pi_f, as the C expression folds it
+import direct_ref
+from ref_f32 import PI2, Draws, F, _dot, _normalize, _sign, _sincos, stream_draws, stream_states
+
 FLT_MAX = F(np.finfo(np.float32).max)
 SKY_X = np.array([0.5, 0.7, 1.0], dtype=np.float32)
 SKY_Y = np.array([1.0, 1.0, 1.0], dtype=np.float32)
 EMISSIVE = 3
-
-
-def _dot(a, b):
-    t = a * b  # glm::dot: tmp = a * b; tmp.x + tmp.y + tmp.z
-    return (t[:, 0] + t[:, 1]) + t[:, 2]
-
-
-def _normalize(v):
-    return v * (F(1.0) / np.sqrt(_dot(v, v)))[:, None]  # v * (1 / sqrt(dot(v, v)))
-
-
-def _sign(x):
-    return ((F(0.0) < x).astype(np.float32) - (x < F(0.0)).astype(np.float32)).astype(np.float32)
-
-
-class Draws:
-    """thrust::minstd_rand states, one per path, advanced through the oracle (orc_rng_uniform)."""
-
-    def __init__(self, orc, states):
-        self.h = orc.lib()
-        self.states = np.asarray(states, dtype=np.uint32).copy()
-
-    def uniform(self, idx):
-        out = np.empty(len(idx), dtype=np.float32)
-        st = C.c_uint32()
-        for k, i in enumerate(idx):
-            st.value = int(self.states[i])
-            out[k] = self.h.orc_rng_uniform(C.byref(st))
-            self.states[i] = st.value
-        return out
-
-
-def _sincos(orc, phi):
-    s, c = np.empty_like(phi), np.empty_like(phi)
-    fs, fc = C.c_float(), C.c_float()
-    h = orc.lib()
-    for k, x in enumerate(phi):
-        h.orc_sincos(float(x), C.byref(fs), C.byref(fc))
-        s[k], c[k] = fs.value, fc.value
-    return s, c
+ROULETTE_XOR = 0x52524C54                       # kRouletteSeedXor (pt_device.hpp)
+TABLES = ("played", "ended", "skipped")
 
 
 def sky(d):
@@ -183,6 +150,24 @@ def _fold(fb, local, iteration, value):
         fb[local] = (fb[local] * (sc - F(1.0)) + value) / sc
 
 
+def _frame(prev, P):
+    """The running means a render folds its samples into, (colour [P, 3], normal [P, 3], depth [P]): zeros, or an earlier
+    result's planes (copied: the result handed in stays as it is)."""
+    if prev is None:
+        return np.zeros((P, 3), np.float32), np.zeros((P, 3), np.float32), np.zeros(P, np.float32)
+    return tuple(np.array(prev[k], dtype=np.float32).reshape(shape) for k, shape in (("color", (P, 3)), ("normal", (P, 3)), ("depth", P)))
+
+
+def _deposit(frame, local, iteration, color, normal, depth):
+    """One iteration's samples into the three planes; path i belongs to the frame's place local[i]."""
+    for fb, value in zip(frame, (color, normal, depth)):
+        _fold(fb, local, iteration, value)
+
+
+def _planes(frame, rows, w):
+    return {"color": frame[0].reshape(rows, w, 3), "normal": frame[1].reshape(rows, w, 3), "depth": frame[2].reshape(rows, w)}
+
+
 def interleaved_pixels(w, h, rank, nranks, block_rows):
     """The rank's slots -> frame pixels (band_slot_to_pixel, oracle.c:996-1004), in the rank's order."""
     rows = []
@@ -191,11 +176,74 @@ def interleaved_pixels(w, h, rank, nranks, block_rows):
     return (np.asarray(rows, dtype=np.int64)[:, None] * w + np.arange(w)[None, :]).reshape(-1)
 
 
-def render_streaming(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, prev=None, pixels=None,
-                     slot_offset=None, scene_handle=None):
+def _closest_hits(orc, flat, sh, materials, o, d, tmin, at, bounce, color, normal, depth):
+    """The bounce's closest hits of the paths in rows `at`, and what a bounce does before any draw: a miss takes colour * sky,
+    a hit at bounce 0 records its normal and t, an emitter is told from the rest.
+    -> (records [len(o)], rows on an emitter, their emission [.., 3], rows on another material, those materials' types)."""
+    recs_at, hit_at = orc.intersect_rays(flat, _rays(o[at], tmin[at], d[at]), scene_handle=sh)
+    recs = np.zeros(len(o), dtype=recs_at.dtype)
+    recs[at] = recs_at
+    hit_at = hit_at.astype(bool)
+    miss, hi = at[~hit_at], at[hit_at]
+    color[miss] = color[miss] * sky(d[miss])
+    if bounce == 0:
+        depth[hi] = recs["t"][hi]
+        normal[hi] = recs["normal"][hi]
+    mat = recs["material_id"][hi].astype(np.int64)
+    typ = materials["type"][mat]
+    lamp = typ == EMISSIVE
+    return recs, hi[lamp], materials["p"][mat[lamp], :3].astype(np.float32), hi[~lamp], typ[~lamp]
+
+
+def plays_at(roulette, bounce, max_bounces):
+    """Does bounce `bounce` play roulette?  (The host's launch selection, restated.)"""
+    return roulette >= 1 and bounce >= roulette and bounce != max_bounces - 1
+
+
+def play(orc, color, idx, indices, iteration, bounce, record=None):
+    """The roulette rule, one binary32 operation per line item.  With k = roulette >= 1, a path plays at
+    bounce b iff plays_at(k, b, max_bounces) -- b >= k and b is not the last bounce --, its closest hit exists and the hit's
+    material is not emissive; both loops play after the emitter check and before evaluate_material.  c = the throughput that
+    came into the bounce:
+      1. q = max(max(c.r, c.g), c.b), by compare and select ((a < b) ? b : a);
+      2. q >= 1: nothing happens (no draw, no division);
+      3. else u = one uniform() of a generator seeded path_seed(index, iteration) ^ 0x52524c54, after discard(b); index =
+         slot_base + slot (streaming) or the pixel (megakernel);
+      4. !(u < q): the path ends, its sample is (0, 0, 0), it makes no material draw (and takes no light sample);
+      5. else c = (c.r / q, c.g / q, c.b / q), and the bounce goes on as without roulette.
+    Here: for the paths `idx` (rows of color; all of them play), whose generators' indices are `indices`, in place on color.
+    -> (bool[len(idx)]: the path ends, bool[len(idx)]: it skipped with q >= 1); who did neither survived with the division."""
+    c = color[idx]
+    m = np.where(c[:, 0] < c[:, 1], c[:, 1], c[:, 0])  # sel_max(c.r, c.g)
+    q = np.where(m < c[:, 2], c[:, 2], m)              # sel_max(.., c.b)
+    skip = q >= F(1.0)
+    drawn = np.nonzero(~skip)[0]
+    u = stream_draws(orc, np.asarray(indices)[drawn], iteration, ROULETTE_XOR, bounce, 1)[:, 0]
+    with np.errstate(invalid="ignore"):
+        goes = u < q[drawn]
+    ended = np.zeros(len(idx), dtype=bool)
+    ended[drawn[~goes]] = True
+    div = drawn[goes]
+    c[div] = c[div] / q[div][:, None]
+    c[ended] = F(0.0)
+    color[idx] = c
+    if record is not None:
+        record.append({"kind": "roulette", "iteration": iteration, "bounce": bounce, "q": q, "skipped": skip, "ended": ended,
+                       "after": c[div].copy(), "indices": np.asarray(indices).copy()})
+    return ended, skip
+
+
+def _tally(tables, it, bounce, ended, skip):
+    tables["played"][it, bounce], tables["ended"][it, bounce], tables["skipped"][it, bounce] = len(ended), ended.sum(), skip.sum()
+
+
+def render_streaming(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, roulette=0, prev=None, pixels=None,
+                     slot_offset=None, scene_handle=None, record=None):
     """orc_render_streaming (pixels None) or orc_render_streaming_interleaved (pixels = interleaved_pixels(..),
-    slot_offset = the rank's first global slot, added at every bounce) with emitters.  Returns the oracle's dict:
-    color / normal / depth over the frame's (or the rank's) pixels in order, live [iter, bounce], rays."""
+    slot_offset = the rank's first global slot, added at every bounce) with emitters and, with roulette >= 1, the rule of
+    play on the stream of slot_base + slot.  Returns the oracle's dict -- color / normal / depth over the frame's (or the
+    rank's) pixels in order, live [iter, bounce], rays -- and played / ended / skipped, each [iter, bounce] (0 where no bounce
+    plays).  record: a list that gets play's entries."""
     sh = scene_handle or orc.SceneHandle(flat)
     materials = np.asarray(flat.materials)
     if pixels is None:
@@ -204,15 +252,9 @@ def render_streaming(orc, flat, camera, w, h, iter_begin, iter_count, max_bounce
     else:
         slot_base = int(slot_offset)
     P = len(pixels)
-    rows = P // w
-    if prev is None:
-        fc, fn, fd = np.zeros((P, 3), np.float32), np.zeros((P, 3), np.float32), np.zeros(P, np.float32)
-    else:
-        fc = np.array(prev["color"], dtype=np.float32).reshape(P, 3)
-        fn = np.array(prev["normal"], dtype=np.float32).reshape(P, 3)
-        fd = np.array(prev["depth"], dtype=np.float32).reshape(P)
-    lib = orc.lib()
+    frame = _frame(prev, P)
     live = np.zeros((iter_count, max_bounces), dtype=np.uint32)
+    tables = {k: np.zeros((iter_count, max_bounces), dtype=np.int64) for k in TABLES}
     rays = 0
     for it in range(iter_count):
         iteration = iter_begin + it
@@ -227,61 +269,62 @@ def render_streaming(orc, flat, camera, w, h, iter_begin, iter_count, max_bounce
                 break
             live[it, b] = n
             rays += n
-            recs, hit = orc.intersect_rays(flat, _rays(o[:n], tmin[:n], d[:n]), scene_handle=sh)
-            hit = hit.astype(bool)
-            goes_on = hit.copy()  # bounces_left > 0
-            miss = np.nonzero(~hit)[0]
-            color[miss] = color[miss] * sky(d[miss])
-            hi = np.nonzero(hit)[0]
-            if b == 0:
-                depth[hi] = recs["t"][hi]
-                normal[hi] = recs["normal"][hi]
-            mat_type = np.full(n, -1, dtype=np.int64)
-            mat_type[hi] = materials["type"][recs["material_id"][hi].astype(np.int64)]
-            em = np.nonzero(mat_type == EMISSIVE)[0]
-            if len(em):  # the emissive rule: colour * emission, no draw, the path ends
-                color[em] = color[em] * materials["p"][recs["material_id"][em].astype(np.int64), :3].astype(np.float32)
-                goes_on[em] = False
-            sc = np.nonzero(hit & (mat_type != EMISSIVE))[0]
-            states = np.zeros(n, dtype=np.uint32)
-            st = C.c_uint32()
-            for i in sc:
-                st.value = lib.orc_rng_seed(lib.orc_path_seed(slot_base + int(i), iteration))
-                lib.orc_rng_discard(C.byref(st), b)
-                states[i] = st.value
+            recs, em, emission, sc, _ = _closest_hits(orc, flat, sh, materials, o, d, tmin, np.arange(n), b, color, normal, depth)
+            color[em] = color[em] * emission  # the emissive rule: colour * emission, no draw, the path ends
+            if plays_at(roulette, b, max_bounces):  # before any material draw of the bounce
+                ended, skip = play(orc, color, sc, slot_base + sc, iteration, b, record)
+                _tally(tables, it, b, ended, skip)
+                sc = sc[~ended]
+            states = np.zeros(P, dtype=np.uint32)
+            states[sc] = stream_states(orc, slot_base + sc, iteration, 0, b)  # the material stream: keyed on the SLOT, per bounce
             shade(orc, materials, o, d, tmin, recs, sc, Draws(orc, states), color)
             # stable partition on bounces_left > 0 (oracle.c:1082-1104): live first, then the rest, both in order
+            goes_on = np.zeros(n, dtype=bool)
+            goes_on[sc] = True
             order = np.concatenate([np.nonzero(goes_on)[0], np.nonzero(~goes_on)[0], np.arange(n, P)])
             o, d, tmin, color, normal, depth, local = (a[order] for a in (o, d, tmin, color, normal, depth, local))
-            n = int(goes_on.sum())
-        for fb, val in ((fc, color), (fn, normal)):
-            for k in range(3):
-                col = fb[:, k].copy()
-                _fold(col, local, iteration, val[:, k])
-                fb[:, k] = col
-        _fold(fd, local, iteration, depth)
-    return {"color": fc.reshape(rows, w, 3), "normal": fn.reshape(rows, w, 3), "depth": fd.reshape(rows, w),
-            "live": live, "rays": rays}
+            n = len(sc)
+        _deposit(frame, local, iteration, color, normal, depth)
+    return {**_planes(frame, P // w, w), "live": live, "rays": rays, **tables}
 
 
-def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, prev=None, scene_handle=None):
+def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, direct=False, roulette=0, prev=None,
+                      scene_handle=None, record=None):
     """orc_render_megakernel (oracle.c:1280-1330) with emitters: one generator per pixel for the whole path; an emissive
-    hit records normal / depth if it is the first hit, then colour *= emission and the path ends, with no draw."""
+    hit records normal / depth if it is the first hit, then colour *= emission and the path ends, with no draw.
+
+    direct: the rule of DESIGN section 5g (ptc_set_param "direct_light" 1).  A per-path radiance sum, deposited as radiance +
+    colour; at every hit on a diffuse material, after evaluate_material (colour = throughput x albedo), one light sample
+    (direct_ref.light_sample: section 5f, items 2-5) at the hit point about the hit's normal from the stream
+    seed(path_seed(pixel, iteration) ^ kLightSeedXor), discard(3 * bounce); a sampled sample traces {p, 1e-4, w, d * 0.999} and,
+    if the oracle reports no hit, radiance += colour * contribution; an emissive hit ends the path with colour * emission if
+    the vertex before drew no light sample (the camera, metal, glass), else with 0.  A scene whose lamp table is empty or has no
+    weight renders as without the option.
+
+    roulette >= 1: the rule of play, on the roulette stream of the PIXEL.  A path that ends leaves colour 0, draws nothing, takes
+    no light sample and adds nothing to the three loop counters; a survivor's light sample is weighted with the divided colour.
+
+    -> dict(color, normal, depth, rays, diffuse_hits, shadow_rays, unoccluded, played, ended, skipped); the counters are 0
+    without direct, the tables ([iter, bounce]) where no bounce plays.  record: a list that gets play's entries and, per
+    (iteration, bounce) with light samples, a "kind": "light" entry with the diffuse hits' pixels, points, normals, the sample
+    drawn there and which shadow rays came through."""
     sh = scene_handle or orc.SceneHandle(flat)
     materials = np.asarray(flat.materials)
+    lit = False
+    if direct:
+        lamps = direct_ref.light_table(flat)
+        lit = len(lamps[0]) > 0 and float(lamps[1]["total_weight"]) > 0.0
     P = w * h
-    if prev is None:
-        fc, fn, fd = np.zeros((P, 3), np.float32), np.zeros((P, 3), np.float32), np.zeros(P, np.float32)
-    else:
-        fc = np.array(prev["color"], dtype=np.float32).reshape(P, 3)
-        fn = np.array(prev["normal"], dtype=np.float32).reshape(P, 3)
-        fd = np.array(prev["depth"], dtype=np.float32).reshape(P)
-    rays = 0
+    frame = _frame(prev, P)
+    tables = {k: np.zeros((iter_count, max_bounces), dtype=np.int64) for k in TABLES}
+    rays = diffuse_hits = shadow_rays = unoccluded = 0
     for it in range(iter_count):
         iteration = iter_begin + it
         o, d, tmin, states = _primary(orc, camera, w, h, np.arange(P), iteration)
         draws = Draws(orc, states)
         color = np.ones((P, 3), dtype=np.float32)
+        radiance = np.zeros((P, 3), dtype=np.float32)
+        count_emission = np.ones(P, dtype=bool)  # (stays all True unless lit)
         normal = -d
         depth = np.full(P, F(1e6), dtype=np.float32)
         active = np.arange(P)
@@ -289,27 +332,35 @@ def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounc
             if len(active) == 0:
                 break
             rays += len(active)
-            recs_a, hit_a = orc.intersect_rays(flat, _rays(o[active], tmin[active], d[active]), scene_handle=sh)
-            recs = np.zeros(P, dtype=recs_a.dtype)
-            recs[active] = recs_a
-            hit = np.zeros(P, dtype=bool)
-            hit[active] = hit_a.astype(bool)
-            miss = active[~hit[active]]
-            color[miss] = color[miss] * sky(d[miss])
-            hi = active[hit[active]]
-            if b == 0:
-                depth[hi] = recs["t"][hi]
-                normal[hi] = recs["normal"][hi]
-            mt = materials["type"][recs["material_id"][hi].astype(np.int64)]
-            em = hi[mt == EMISSIVE]
-            color[em] = color[em] * materials["p"][recs["material_id"][em].astype(np.int64), :3].astype(np.float32)
-            sc = hi[mt != EMISSIVE]
+            recs, em, emission, sc, typ = _closest_hits(orc, flat, sh, materials, o, d, tmin, active, b, color, normal, depth)
+            color[em] = np.where(count_emission[em][:, None], color[em] * emission, F(0.0))
+            if plays_at(roulette, b, max_bounces):
+                ended, skip = play(orc, color, sc, sc, iteration, b, record)
+                _tally(tables, it, b, ended, skip)
+                sc, typ = sc[~ended], typ[~ended]
             shade(orc, materials, o, d, tmin, recs, sc, draws, color)
+            if lit:
+                count_emission[sc] = typ != 0
+                df = sc[typ == 0]
+                diffuse_hits += len(df)
+                pts = recs["point"][df].astype(np.float32)
+                nrm = recs["normal"][df].astype(np.float32)
+                u = stream_draws(orc, df, iteration, direct_ref.SEED_XOR, 3 * b, 3)
+                smp = direct_ref.light_sample(orc, flat, lamps, pts, nrm, u)
+                sel = np.nonzero(smp["sampled"])[0]
+                shadow_rays += len(sel)
+                clear = np.zeros(len(df), dtype=bool)
+                if len(sel):
+                    _, blocked = orc.intersect_rays(flat, smp["rays"][sel], scene_handle=sh)
+                    clear[sel] = blocked == 0
+                unoccluded += int(clear.sum())
+                got = df[clear]
+                radiance[got] = radiance[got] + color[got] * smp["contribution"][clear]
+                if record is not None:
+                    record.append({"kind": "light", "iteration": iteration, "bounce": b, "pixels": df, "points": pts, "normals": nrm,
+                                   "sample": smp, "clear": clear})
             active = sc
-        for fb, val in ((fc, color), (fn, normal)):
-            for k in range(3):
-                col = fb[:, k].copy()
-                _fold(col, np.arange(P), iteration, val[:, k])
-                fb[:, k] = col
-        _fold(fd, np.arange(P), iteration, depth)
-    return {"color": fc.reshape(h, w, 3), "normal": fn.reshape(h, w, 3), "depth": fd.reshape(h, w), "rays": rays}
+        total = radiance + color if lit else color   # (no lamp table: the plain kernel deposits colour itself)
+        _deposit(frame, np.arange(P), iteration, total, normal, depth)
+    return {**_planes(frame, h, w), "rays": rays, "diffuse_hits": diffuse_hits, "shadow_rays": shadow_rays,
+            "unoccluded": unoccluded, **tables}

@@ -3,29 +3,19 @@ pixel -- the out-of-bounds taps of the bottom row and right column included -- o
 reference's GUI reaches (filter size 1-100, each weight 0-1) and one filter size past it.  Two independent statements of
 the reference agreeing within 2e-6 is what lets tests/test_gpu_denoise.py hold the HIP kernels to both of them."""
 import ctypes as C
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import denoise_ref as dr
+
 TOL = 2e-6
 # Past the GUI's filter sizes: the eighth pass (step 128) at the ill-conditioned end of the weights (all at 0.01, every
 # exponent scaled by 100) carries the binary32 rounding of seven passes before it -- 2.1e-6 at one pixel of 3x130,
 # against 1.9e-6 after seven passes.  That is the reference's own arithmetic, not a disagreement of substance: a
 # misplaced tap or weight moves a pixel by 1e-3 and more (tests/test_gpu_denoise.py).
 TOL_PAST_GUI = 3e-6
-
-
-def _ref():
-    spec = importlib.util.spec_from_file_location("denoise_ref", os.path.join(ROOT, "tests", "denoise_ref.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-dr = _ref()
 
 # (camera, w, h): oracle-rendered G-buffers of the heightfield scene (2 iterations, 4 bounces); "golden" is the
 # 64x64 input of tests/golden/frames.npz.  2x2 is the smallest frame; 3x130 and 130x3 are thinner than one step.

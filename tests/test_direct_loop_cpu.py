@@ -1,25 +1,20 @@
 """Direct lighting in the megakernel without a GPU: the binding, and the CPU restatement
-(tests/direct_loop_ref.py) against the pieces it is built from -- lit_ref.render_megakernel for everything but the colour, the
-no-lamp and glass-fronted-lamp scenes for the emission gate, direct_ref's sample for the light stream at bounce 0."""
+(lit_ref.render_megakernel with direct=True) against the same loop without the option for everything but the colour, on the
+no-lamp and glass-fronted-lamp scenes for the emission gate, and against direct_ref's sample for the light stream at bounce 0."""
 import ctypes as C
-import importlib.util
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import direct_loop_scenes as scenes
+import direct_ref as dr
+import lit_ref as lr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-dl = _load("direct_loop_ref")
 W, H = 16, 12
 _cache = {}
 
@@ -29,8 +24,8 @@ def _both(orc, key, scene, mb, iters=2):
         flat = scene.build_scene()
         sh = orc.SceneHandle(flat)
         record = []
-        lit = dl.render_megakernel_direct(orc, flat, scene.camera, W, H, 0, iters, mb, scene_handle=sh, record=record)
-        plain = dl.lr.render_megakernel(orc, flat, scene.camera, W, H, 0, iters, mb, scene_handle=sh)
+        lit = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, iters, mb, direct=True, scene_handle=sh, record=record)
+        plain = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, iters, mb, scene_handle=sh)
         _cache[(key, mb)] = (flat, lit, plain, record)
     return _cache[(key, mb)]
 
@@ -79,7 +74,7 @@ def test_a_scene_without_lamps_is_untouched(pkg, orc):
 def test_a_lamp_behind_glass_keeps_its_emission(pkg, orc):
     """Every shadow ray is blocked by the glass, and the lamp is only ever hit after a dielectric vertex or from the camera: the
     gate must let every such hit count, so the colour is the plain render's (radiance stays 0; 0 + colour == colour)."""
-    scene = dl.glass_lamp_scene(pkg)
+    scene = scenes.glass_lamp_scene(pkg)
     _, lit, plain, _ = _both(orc, "glass_lamp", scene, 5)
     assert lit["shadow_rays"] > 0 and lit["unoccluded"] == 0
     seen = plain["color"].max(axis=-1) > 1.0
@@ -93,14 +88,14 @@ def test_bounce_0_is_the_query_sample(pkg, orc):
     restatement's own first-hit points (points without a diffuse first hit get a dummy and are left out of the comparison)."""
     scene = pkg.scenes.cornell_lit(resolution=(W, H), with_mesh=True)
     flat, _, _, record = _both(orc, "cornell_lit", scene, 2)
-    table = dl.dr.light_table(flat)
-    first = [r for r in record if r["bounce"] == 0]
+    table = dr.light_table(flat)
+    first = [r for r in record if r["kind"] == "light" and r["bounce"] == 0]
     assert len(first) == 2
     for r in first:
         pts = np.zeros((W * H, 3), dtype=np.float32)
         nrm = np.tile(np.array([0.0, 1.0, 0.0], dtype=np.float32), (W * H, 1))
         pts[r["pixels"]], nrm[r["pixels"]] = r["points"], r["normals"]
-        want = dl.dr.sample(orc, flat, pts, nrm, r["iteration"], table=table)
+        want = dr.sample(orc, flat, pts, nrm, r["iteration"], table=table)
         assert len(r["pixels"]) > W * H // 2
         assert np.array_equal(want["rays"][r["pixels"]], r["sample"]["rays"])
         assert np.array_equal(want["contribution"][r["pixels"]], r["sample"]["contribution"])

@@ -9,26 +9,14 @@ Per case: |GPU - oracle| <= 1e-5 and |GPU - float64| <= 1e-5 on the radiance, bo
 each other within 1e-5; NaN exactly where the oracle has it (every pixel for a zero weight: -0/0 at the centre tap);
 the display of the result within 1 LSB of orc_preview with NaN shown as black; ptc_denoise running floor(log2 N) + 1
 passes per call and none for filter_size < 1; parameters applied per call."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
+import denoise_ref as dr
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-5
-
-
-def _ref():
-    spec = importlib.util.spec_from_file_location("denoise_ref", os.path.join(ROOT, "tests", "denoise_ref.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-dr = _ref()
 
 
 def _camera(pkg, scene, cam):

@@ -1,29 +1,19 @@
 """Direct lighting in the megakernel (ptc_set_param "direct_light" 1) on the GPU against its CPU restatement
-(tests/direct_loop_ref.py), bit for bit: colour, first-hit normal and depth, ptc_stats.rays_total and the three loop counters
+(tests/lit_ref.py, render_megakernel with direct=True), bit for bit: colour, first-hit normal and depth, ptc_stats.rays_total and the three loop counters
 (diffuse hits, shadow rays traced, unoccluded).  Then what the rule promises beside the bits: normal / depth / rays_total equal to
 the plain megakernel's, a lamp-less scene untouched, interleaved ranks assembling to the one-context frame, the refusals, and a
 paired statistical test of the estimator (same expectation as the plain render, lower spread)."""
-import importlib.util
 import math
-import os
 
 import numpy as np
 import pytest
 
+import direct_loop_scenes as scenes
+import direct_ref as D
+import lit_ref as lr
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-dl = _load("direct_loop_ref")
-D = dl.dr
 PLANES = ("color", "normal", "depth")
 COUNTERS = ("diffuse_hits", "shadow_rays", "unoccluded")
 
@@ -59,7 +49,7 @@ def _same(got, ref, what, planes=PLANES, counters=COUNTERS):
 
 def _against_restatement(pkg, orc, scene, w, h, mb, iters, what, iter_begin=0):
     flat = scene.build_scene()
-    ref = dl.render_megakernel_direct(orc, flat, scene.camera, w, h, iter_begin, iters, mb)
+    ref = lr.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iters, mb, direct=True)
     got = _render(pkg, scene, flat, w, h, mb, iters, True, iter_begin)
     _same(got, ref, what)
     return flat, got, ref
@@ -102,8 +92,8 @@ SCENES = {
     "dark_lamps": lambda pkg: D.dark_lamp_scene(pkg),
     "area_0_triangles": lambda pkg: _floor_and_camera(pkg, D.degenerate_scene(pkg), True),
     "big_emitter": lambda pkg: _floor_and_camera(pkg, D.big_emitter_scene(pkg), False),  # 16,384 triangles: the cdf search runs 14 steps
-    "metal_and_glass": lambda pkg: dl.metal_glass_scene(pkg),
-    "lamp_behind_glass": lambda pkg: dl.glass_lamp_scene(pkg),
+    "metal_and_glass": lambda pkg: scenes.metal_glass_scene(pkg),
+    "lamp_behind_glass": lambda pkg: scenes.glass_lamp_scene(pkg),
 }
 
 
@@ -211,14 +201,14 @@ def stat_blocks(pkg, blocks=16, per_block=256, w=32, h=24, room=None):
     """Per mode (direct_light 0, 1) and block b the image mean per channel of iterations [per_block b, per_block (b + 1)), and
     whether normal and depth agreed.  Each block starts from framebuffers that ptc_resize has cleared, at iteration per_block * b:
     the running mean then holds (sum of the block's samples) / (per_block (b + 1)), so the block's own mean is that times (b + 1)."""
-    scene = (room or dl.small_lamp_room)(pkg)
+    scene = (room or scenes.small_lamp_room)(pkg)
     flat = scene.build_scene()
     means = np.zeros((2, blocks, 3))
     geometry = []
     tracers = []
     try:
         for mode in (0, 1):
-            pt = pkg.PathTracer(device=0, max_bounces=dl.STAT_BOUNCES)
+            pt = pkg.PathTracer(device=0, max_bounces=scenes.STAT_BOUNCES)
             tracers.append(pt)
             pt.current_gpu_method = pkg.GPUMethod.megakernel
             pt.direct_light = bool(mode)
@@ -245,7 +235,7 @@ def test_same_expectation_lower_spread(pkg):
     """Paired over B = 16 blocks of 256 iterations (fixed seeds: deterministic).  D_b = image mean of block b with direct light
     minus without.  |mean(D)| <= 4.073 sd(D) / sqrt(16) per channel (the two-sided 0.1 % point of Student's t, 15 degrees of
     freedom), and the spread of the direct-lit block means is below the plain ones'.
-    The room's walls are triangles (direct_loop_ref.small_lamp_room says why).  The same room from the stock scenes' radius-1000 wall
+    The room's walls are triangles (direct_loop_scenes.small_lamp_room says why).  The same room from the stock scenes' radius-1000 wall
     spheres MISSES the first bound -- mean(D) -1.885e-3 / -1.596e-3 / -1.173e-3 against bounds 1.844e-3 / 1.661e-3 / 1.372e-3 (r, g,
     b; image mean 0.21, variance ratios 3.1 / 2.5 / 2.9) -- because 7 % of its shadow rays, carrying 6 % of the unshadowed direct light, hit the wall they start
     on: section 5f's shadow epsilon (origin at the hit point, t_min 1e-4) is too small for a sphere of radius 1000 in binary32.  A

@@ -5,12 +5,13 @@ survivor's slot, and with it its random numbers, moves.  The scenes put the emit
 from: the sphere run that ends the object list (k_shade_fused's tail), a mesh (the traversal kernels), the sphere run in
 front of the first mesh (k_spheres / "prefold") and a run between two meshes; the schedules cover every form of the kernel
 that ends a bounce (fused and three-kernel, prefold, the persistent launch, the megakernel, interleaved ranks)."""
-import importlib.util
 import os
 import subprocess
 
 import numpy as np
 import pytest
+
+import lit_ref as lr
 
 pytestmark = pytest.mark.gpu
 
@@ -21,14 +22,6 @@ KNOBS = [(("fused_shade", 0),), (("prefold", 0),), (("sphere_fold", 0),), (("sph
          (("ray_sort", 1),), (("pair_batches", 1), ("frames_in_flight", 4), ("batch_frames", 2))]
 
 
-def _ref():
-    spec = importlib.util.spec_from_file_location("lit_ref", os.path.join(ROOT, "tests", "lit_ref.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-lr = _ref()
 _cache = {}
 
 

@@ -1,29 +1,18 @@
-"""Russian roulette (ptc_set_param "roulette") on the GPU against its CPU restatement (tests/roulette_ref.py), bit
+"""Russian roulette (ptc_set_param "roulette") on the GPU against its CPU restatement (tests/lit_ref.py with roulette >= 1), bit
 for bit: colour, first-hit normal and depth, ptc_stats.rays_total and the per-bounce live counts, under the streaming method (every
 schedule that ends a bounce differently, interleaved ranks, the stepwise calls, high sample indices) and under the megakernel (plain
 and with "direct_light" 1: the three loop counters too).  Then what the rule promises beside the bits: a parameter that lets no
 bounce play renders as 0 does, fewer rays, and a paired statistical test of the estimator in both methods."""
-import importlib.util
 import math
-import os
 
 import numpy as np
 import pytest
 
+import direct_loop_scenes as scenes
+import lit_ref as lr
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-rr = _load("roulette_ref")
-dl = rr.dl
 PLANES = ("color", "normal", "depth")
 COUNTERS = ("diffuse_hits", "shadow_rays", "unoccluded")
 W, H, MB, ITERS = 65, 33, 8, 3  # 2145 slots: five 512-slot tiles, the last one partly filled
@@ -40,7 +29,7 @@ def _lit(pkg):
 def _ref_streaming(orc, key, flat, camera, w, h, mb, iters, k, **kw):
     key = ("s", key, w, h, mb, iters, k, tuple(sorted((a, str(b)[:40]) for a, b in kw.items() if a != "pixels")))
     if key not in _cache:
-        _cache[key] = rr.render_streaming_roulette(orc, flat, camera, w, h, kw.pop("iter_begin", 0), iters, mb, k, **kw)
+        _cache[key] = lr.render_streaming(orc, flat, camera, w, h, kw.pop("iter_begin", 0), iters, mb, roulette=k, **kw)
     return _cache[key]
 
 
@@ -189,7 +178,7 @@ def test_every_class_of_path(pkg, orc, name):
     """metal_glass_scene: a mesh lamp, metal, glass (throughput 1: q >= 1).  cornell_spheres: no mesh, every hit comes from the sphere
     run that ends the object list (the kFirst instances).  The restatement must show every class, so the test cannot pass vacuously."""
     if name == "metal_glass":
-        scene, w, h, iters = dl.metal_glass_scene(pkg), 48, 32, 3
+        scene, w, h, iters = scenes.metal_glass_scene(pkg), 48, 32, 3
     else:
         scene, w, h, iters = pkg.scenes.cornell_spheres((96, 96)), 96, 96, 2
     flat = scene.build_scene()
@@ -199,7 +188,7 @@ def test_every_class_of_path(pkg, orc, name):
         assert ended > 0 and divided > 0 and skipped > 0, (name, k, ended, divided, skipped)
         _same(_render(pkg, scene, flat, w, h, MB, iters, k), ref, (name, k))
         _same(_render(pkg, scene, flat, w, h, MB, iters, k, params=(("fused_shade", 0),)), ref, (name, k, "three kernels"))
-    mk = rr.render_megakernel_roulette(orc, flat, scene.camera, w, h, 0, iters, MB, 1)
+    mk = lr.render_megakernel(orc, flat, scene.camera, w, h, 0, iters, MB, roulette=1)
     assert all(n > 0 for n in _classes(mk)), _classes(mk)
     _same(_render(pkg, scene, flat, w, h, MB, iters, 1, method=pkg.GPUMethod.megakernel), mk, (name, "megakernel"), live=False)
 
@@ -224,10 +213,10 @@ def test_high_sample_indices(pkg, orc):
     scene = pkg.scenes.cornell_lit(resolution=(32, 24), with_mesh=True)
     flat = scene.build_scene()
     begin = 2 ** 31 - 6
-    ref = rr.render_streaming_roulette(orc, flat, scene.camera, 32, 24, begin, 3, 6, 1)
+    ref = lr.render_streaming(orc, flat, scene.camera, 32, 24, begin, 3, 6, roulette=1)
     assert all(n > 0 for n in _classes(ref))
     _same(_render(pkg, scene, flat, 32, 24, 6, 3, 1, iter_begin=begin), ref, "2^31 - 6")
-    mk = rr.render_megakernel_roulette(orc, flat, scene.camera, 32, 24, begin, 3, 6, 1, direct=True)
+    mk = lr.render_megakernel(orc, flat, scene.camera, 32, 24, begin, 3, 6, direct=True, roulette=1)
     _same(_render(pkg, scene, flat, 32, 24, 6, 3, 1, iter_begin=begin, method=pkg.GPUMethod.megakernel, direct=True), mk, "2^31 - 6, direct",
           live=False, counters=COUNTERS)
 
@@ -240,9 +229,9 @@ def test_two_interleaved_ranks(pkg, orc):
     flat = scene.build_scene()
     sh = orc.SceneHandle(flat)
     for rank in (0, 1):
-        pixels = rr.lr.interleaved_pixels(w, h, rank, 2, block)
-        ref = rr.render_streaming_roulette(orc, flat, scene.camera, w, h, 0, ITERS, mb, 1, pixels=pixels, slot_offset=rank * w * h,
-                                           scene_handle=sh)
+        pixels = lr.interleaved_pixels(w, h, rank, 2, block)
+        ref = lr.render_streaming(orc, flat, scene.camera, w, h, 0, ITERS, mb, roulette=1, pixels=pixels, slot_offset=rank * w * h,
+                                  scene_handle=sh)
         assert all(n > 0 for n in _classes(ref))
         _same(_render(pkg, scene, flat, w, h, mb, ITERS, 1, interleave=(rank, 2, block)), ref, ("interleaved", rank))
 
@@ -253,7 +242,7 @@ def test_megakernel_against_the_restatement(pkg, orc, mb, direct):
     """Plain and with "direct_light" 1.  At 2 bounces bounce 1 is the last one: nothing plays."""
     scene, flat = _lit(pkg)
     k = 1
-    ref = rr.render_megakernel_roulette(orc, flat, scene.camera, W, H, 0, ITERS, mb, k, direct=direct)
+    ref = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, mb, direct=direct, roulette=k)
     got = _render(pkg, scene, flat, W, H, mb, ITERS, k, method=pkg.GPUMethod.megakernel, direct=direct)
     _same(got, ref, ("megakernel", mb, direct), live=False, counters=COUNTERS)
     off = _render(pkg, scene, flat, W, H, mb, ITERS, 0, method=pkg.GPUMethod.megakernel, direct=direct)
@@ -299,14 +288,14 @@ def stat_blocks(pkg, method, w=32, h=24):
     """Per mode (roulette 0, STAT_K) and block b the image mean per channel of iterations [256 b, 256 (b + 1)) and the rays traced.
     Each block starts from framebuffers that ptc_resize has cleared, at iteration 256 b: the running mean then holds (sum of the
     block's samples) / (256 (b + 1)), so the block's own mean is that times (b + 1)  (tests/test_gpu_direct_loop.py)."""
-    scene = dl.small_lamp_room(pkg)
+    scene = scenes.small_lamp_room(pkg)
     flat = scene.build_scene()
     means = np.zeros((2, STAT_BLOCKS, 3))
     rays = [0, 0]
     tracers = []
     try:
         for mode in (0, 1):
-            pt = pkg.PathTracer(device=0, max_bounces=dl.STAT_BOUNCES)
+            pt = pkg.PathTracer(device=0, max_bounces=scenes.STAT_BOUNCES)
             tracers.append(pt)
             pt.current_gpu_method = method
             if method == pkg.GPUMethod.streaming:  # (few launches: 32 iterations per batch)

@@ -3,7 +3,6 @@ can speak (scenes without emitters: every bit of colour, normal, depth, live cou
 interleaved rows), the emissive rule's own properties where it cannot, and the "emissive" entry of the scene grammar in both
 readers (json_parser.py and hip_pt --dump-scene).  Emitters are an extension: the reference has none, so what is checked
 here is the rule of include/ptcore.h, not the reference."""
-import importlib.util
 import json
 import os
 import subprocess
@@ -11,18 +10,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import lit_ref as lr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIP_PT = os.path.join(ROOT, "cuda-path-tracer_amd", "host", "hip_pt")
 
 
-def _ref():
-    spec = importlib.util.spec_from_file_location("lit_ref", os.path.join(ROOT, "tests", "lit_ref.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-lr = _ref()
 KEYS = ("color", "normal", "depth")
 
 

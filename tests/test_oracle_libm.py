@@ -1,24 +1,12 @@
 """The three libm substitutions (sinf / cosf, pow(x, 5), tan) measured at image level on the CPU:
 the oracle built with the platform's libm (oracle/liboracle_libm.so) against the oracle with the fixed sequences.
 INTEGRATION.md section 5 quotes the figures of tests/libm_sensitivity.py; this test holds them to bounds."""
-import importlib.util
-import os
-
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _module():
-    spec = importlib.util.spec_from_file_location("libm_sensitivity", os.path.join(ROOT, "tests", "libm_sensitivity.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @pytest.mark.parametrize("index", [0, 1, 2])
 def test_substitutions_do_not_change_the_image(index):
-    mod = _module()
+    import libm_sensitivity as mod
     name, (scene, w, h, mb) = list(mod.scenes().items())[index]
     r = mod.measure(scene, w, h, mb, spp=32)
     one, many = r["one_spp"], r["many_spp"]

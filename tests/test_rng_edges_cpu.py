@@ -14,6 +14,7 @@ import pytest
 
 import direct_ref as D
 import seed_cases as sc
+from ref_f32 import stream_draws
 
 
 @pytest.fixture(scope="module")
@@ -93,7 +94,7 @@ def test_every_direct_light_case_meets_its_target(orc):
     cases = sc.light_cases(orc)
     assert len(cases) == 4 + 3 * 4
     for c in cases:
-        u = D._draws(orc, c["point"] + 1, c["sample_index"])[c["point"]]
+        u = stream_draws(orc, [c["point"]], c["sample_index"], D.SEED_XOR, 0, 3)[0]
         seed = orc.lib().orc_path_seed(c["point"], c["sample_index"]) ^ D.SEED_XOR
         assert seed == c["seed"] and 0 <= c["sample_index"] < 2**32, c
         if c["draw"]:

@@ -23,6 +23,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))  # the test module below imports its helpers from there
 
 
 def main():
@@ -38,7 +39,7 @@ def main():
     t = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(t)
     if args.self_shadow:
-        return self_shadow(pkg, graft.load_oracle(), t.dl)
+        return self_shadow(pkg, graft.load_oracle())
     w, h, mb, n = 1280, 720, 8, args.iterations
     scene = pkg.scenes.cornell_lit(resolution=(w, h), with_mesh=True)
     flat = scene.build_scene()
@@ -83,14 +84,14 @@ def main():
     print(f"  time ratio (1 / 0): {time_ratio:.3f}")
     if args.no_variance:
         return
-    for room in (t.dl.small_lamp_room, t.dl.small_lamp_sphere_room):
+    for room in (t.scenes.small_lamp_room, t.scenes.small_lamp_sphere_room):
         variance(pkg, t, room, time_ratio)
 
 
 def variance(pkg, t, room, time_ratio):
     t0 = time.perf_counter()
     means, geometry = t.stat_blocks(pkg, room=room)
-    print(f"{room.__name__} 32 x 24, {t.dl.STAT_BOUNCES} bounces, 16 blocks of 256 iterations per mode ({time.perf_counter() - t0:.1f} s); "
+    print(f"{room.__name__} 32 x 24, {t.scenes.STAT_BOUNCES} bounces, 16 blocks of 256 iterations per mode ({time.perf_counter() - t0:.1f} s); "
           f"normal / depth equal in every block: {all(geometry)}")
     for c, name in enumerate("rgb"):
         v0, v1 = means[0, :, c].var(ddof=1), means[1, :, c].var(ddof=1)
@@ -100,20 +101,23 @@ def variance(pkg, t, room, time_ratio):
               f"per unit of time {v0 / v1 / time_ratio:.1f}")
 
 
-def self_shadow(pkg, orc, dl):
+def self_shadow(pkg, orc):
     """Per room: 4 iterations of the restatement at 32 x 24, every sampled shadow ray once more through the oracle's closest hit;
     a hit within 0.05 of the origin is the wall the ray starts on (the rooms are convex: nothing else is that near on the way to
     the lamp)."""
     import numpy as np
-    for room in (dl.small_lamp_room, dl.small_lamp_sphere_room):
+
+    import direct_loop_scenes as scenes
+    import lit_ref
+    for room in (scenes.small_lamp_room, scenes.small_lamp_sphere_room):
         scene = room(pkg)
         flat = scene.build_scene()
         sh = orc.SceneHandle(flat)
         record = []
-        dl.render_megakernel_direct(orc, flat, scene.camera, 32, 24, 0, 4, dl.STAT_BOUNCES, scene_handle=sh, record=record)
+        lit_ref.render_megakernel(orc, flat, scene.camera, 32, 24, 0, 4, scenes.STAT_BOUNCES, direct=True, scene_handle=sh, record=record)
         rays = near = 0
         light = lost = 0.0
-        for e in record:
+        for e in (e for e in record if e["kind"] == "light"):
             sel = np.nonzero(e["sample"]["sampled"])[0]
             if len(sel) == 0:
                 continue

@@ -21,6 +21,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))  # the test module below imports its helpers from there
 
 
 def main():
@@ -96,7 +97,7 @@ def variance(pkg, t, method):
     t0 = time.perf_counter()
     means, rays = t.stat_blocks(pkg, getattr(pkg.GPUMethod, method))
     ray_ratio = rays[1] / rays[0]
-    print(f"small_lamp_room 32 x 24, {t.dl.STAT_BOUNCES} bounces, {method}, roulette 0 / {t.STAT_K}, {t.STAT_BLOCKS} blocks of {t.STAT_PER_BLOCK} "
+    print(f"small_lamp_room 32 x 24, {t.scenes.STAT_BOUNCES} bounces, {method}, roulette 0 / {t.STAT_K}, {t.STAT_BLOCKS} blocks of {t.STAT_PER_BLOCK} "
           f"iterations per mode ({time.perf_counter() - t0:.1f} s); rays {rays[0]} / {rays[1]}: ratio {ray_ratio:.3f}")
     for c, name in enumerate("rgb"):
         v0, v1 = means[0, :, c].var(ddof=1), means[1, :, c].var(ddof=1)
