@@ -489,8 +489,8 @@ void launch_light_sample(hipStream_t s, const DLights& lights, const float* poin
                          uint32_t tmin_word, float4* o4, float4* d4, float4* contrib);
 void launch_light_resolve(hipStream_t s, const float4* o4, const float4* d4, const float4* contrib, const uint8_t* occluded,
                           const float4* closest_tp, uint32_t n, float* radiance, float* rays, uint8_t* visible, uint32_t* stats);
-// direct lighting in the megakernel (pt_mega_direct.hip): k_megakernel<true>'s loop with a light sample and a shadow
-// ray at every diffuse hit.  stats: kLightStatLines lines of kLoopStatWords 64-bit words (a 128-byte line each), word 0 += diffuse
+// direct lighting in the megakernel: k_megakernel_direct (pt_mega_direct.hip) wraps the one loop, mega_path with
+// kDirect (pt_megakernel.inc) -- a light sample and a shadow ray (scene_occluded, pt_kernels_common.inc) at every diffuse hit.  stats: kLightStatLines lines of kLoopStatWords 64-bit words (a 128-byte line each), word 0 += diffuse
 // hits, word 1 += shadow rays traced, word 2 += unoccluded ones; one add per wavefront.  Not part of DeviceCounters, whose layout the
 // feed depends on.
 constexpr uint32_t kLoopStatWords = 16u;

@@ -1,5 +1,6 @@
 // pt_kernels_common.inc -- device functions shared by the kernel translation units (pt_kernels.hip: closest hit;
-// pt_shade.hip: ray generation and the end of a bounce; pt_post.hip: views, gather, denoiser).  Included inside namespace pt;
+// pt_shade.hip: ray generation and the end of a bounce; pt_mega_direct.hip: the megakernel's shadow ray, scene_occluded over the
+// any-hit option of the one two-wide walk; pt_post.hip: views, gather, denoiser).  Included inside namespace pt;
 // everything here is __device__ __forceinline__ or a constant, so every unit gets its own copy of what it uses.
 #pragma once
 
@@ -359,7 +360,10 @@ __device__ __forceinline__ bool box_culled(const float t_near, const float t_far
   return (t_near - pad_t > limit * 1.001f + 1e-3f * (t_far - t_near)) || (t_far + pad_t < -1e-3f * fabsf(t_near));
 }
 
-template <bool kCount>
+// kAny: the any-hit form (scene_occluded below).  The limit stays at scale * best_t (the caller's t_max) for the whole walk, a
+// triangle is accepted for !(t < t_min) && !(t > t_max), and the first accepted triangle ends the walk: best_k names it,
+// best_t is left alone.
+template <bool kCount, bool kAny = false>
 __device__ __forceinline__ void mesh_closest_wide(const Ray& ray, const DScene& sc, const DMeshView& mv, const DObject* obj,
                                                   const uint32_t tri_base, float& best_t, int& best_k, uint32_t* stack,
                                                   uint32_t& flags, Tally& tally)
@@ -405,7 +409,12 @@ __device__ __forceinline__ void mesh_closest_wide(const Ray& ray, const DScene& 
           const float w = f * dot(ray.d, q);
           if (!(w < 0.0f || u + w > 1.0f)) {
             const float t = f * dot(e2, q);
-            if (!(t < ray.tmin) && (t < best_t || (t == best_t && (int)k > best_k))) {
+            if (kAny) {
+              if (!(t < ray.tmin) && !(t > best_t)) {
+                best_k = (int)k;
+                return;
+              }
+            } else if (!(t < ray.tmin) && (t < best_t || (t == best_t && (int)k > best_k))) {
               best_t = t;
               best_k = (int)k;
               limit = scale * t;
@@ -532,6 +541,36 @@ __device__ __forceinline__ bool ray_scene_wide(Ray ray, const DScene& sc, Hit& r
     rec.n = rec.side == 0u ? outward : -outward;
   }
   return hit;
+}
+
+// occluded(ray) := the reference's ray_scene_intersection_test (path_tracer.cu:110-128) reports a hit (DESIGN section 5e).
+// Objects in list order, each one from the caller's t_max (the OR-over-groups argument: every object is a group of its own):
+// the world box by ray_aabb first, a sphere in object space against the world-space t_max, a mesh by mesh_closest_wide's any-hit
+// form.  The first object that reports a hit ends the walk.  The closest-hit form started at best_t = t_max, best_k = -1 accepts
+// the same set of triangles (t < best_t, or t == best_t and k > -1) and culls MORE (its limit shrinks), so "the any-hit walk names
+// a triangle" == "the closest-hit walk finds one" == the reference's answer for the object (section 5e: no order appears in it).
+__device__ __forceinline__ bool scene_occluded(const Ray& ray, const DScene& sc, uint32_t* stack, uint32_t& flags)
+{
+  for (uint32_t i = 0; i < sc.object_count; ++i) {
+    const DObject* obj = sc.objects + i;
+    if (!ray_aabb(ray.o, ray.d, ld3(obj->bmin), ld3(obj->bmax))) continue;
+    if (obj->type == 0u) {
+      Ray tr;
+      inverse_transform_ray(obj->inv_m, ray, tr.o, tr.d);
+      tr.tmin = ray.tmin;
+      tr.tmax = ray.tmax;
+      const float4 sp = sc.spheres[obj->index];
+      Hit unused;
+      if (ray_sphere(tr, xyz(sp), sp.w, unused)) return true;
+    } else {
+      float t = ray.tmax;
+      int k = -1;
+      Tally tally;
+      mesh_closest_wide<false, true>(ray, sc, sc.mesh_views[sc.object_mesh[i]], obj, sc.object_tri_base[i], t, k, stack, flags, tally);
+      if (k >= 0) return true;
+    }
+  }
+  return false;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -746,6 +785,38 @@ __device__ __forceinline__ void generate_ray(const DCamera& cam, float fx, float
   const float dy = cam.lly + cam.vh * v;
   o = cam.origin;
   d = normalize(xform_vector(cam.cam, mk3(dx, dy, -1.0f)));
+}
+
+// The primary sample of a pixel (raygen_kernel, ray_gen.cu:11-32; path_tracing_mega_kernel, path_tracer.cu:233-240): the path's
+// stream seeded, its first two draws jitter the pixel, the ray through that point with a primary ray's range.  rng is left behind
+// the two draws (the megakernel goes on drawing from it).
+__device__ __forceinline__ void primary_ray(const DCamera& cam, const uint32_t pixel, const uint32_t iteration, Minstd& rng, Ray& ray)
+{
+  const uint32_t x = pixel % cam.width, y = pixel / cam.width;
+  rng.seed(path_seed(pixel, iteration));
+  const float fx = (float)x + rng.uniform();
+  const float fy = (float)y + rng.uniform();
+  generate_ray(cam, fx, fy, ray.o, ray.d);
+  ray.tmin = 1e-4f;
+  ray.tmax = FLT_MAX;
+}
+
+// A batch kernel's view of ONE frame of the batch (DBatchInfo): the frame's part of every per-slot array, `offset` slots in.
+__device__ __forceinline__ void offset_frame(DPaths& p, const size_t offset)
+{
+  p.o4 += offset;
+  p.d4 += offset;
+  p.t2 += offset;
+}
+__device__ __forceinline__ void offset_frame(DHits& h, const size_t offset)
+{
+  h.tp += offset;
+  h.nm += offset;
+}
+__device__ __forceinline__ void offset_frame(DFrame& f, const size_t offset)
+{
+  f.color4 += offset;
+  f.nd4 += offset;
 }
 
 // ------------------------------------------------------------------------------------------------

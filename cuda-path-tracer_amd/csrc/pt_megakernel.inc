@@ -1,31 +1,39 @@
-// pt_megakernel.inc -- k_megakernel, the whole path in one thread.  Included (inside namespace pt, after pt_kernels_common.inc) by
-// pt_kernels.hip, which instantiates the plain instances beside the closest-hit kernels as ever, and by pt_mega_direct.hip, which
-// instantiates the kRoulette ones: the code object that holds the traversal kernels stays the one it was (DESIGN section 5h).
+// pt_megakernel.inc -- the megakernel's loop, the whole path in one thread: mega_path, and k_megakernel around it.  Included (inside
+// namespace pt, after pt_kernels_common.inc and with pt_light_sample.hpp in front) by pt_kernels.hip, which instantiates the plain
+// instances beside the closest-hit kernels as ever, and by pt_mega_direct.hip, which instantiates the kRoulette ones and
+// k_megakernel_direct: the code object that holds the traversal kernels stays the one it was (DESIGN section 5h).
 // path_tracing_mega_kernel, path_tracer.cu:227-269: the whole path in one thread, one RNG stream per
 // pixel (a different image from streaming mode at the same seed -- a property of the reference).
 // kEmit: the scene has an emissive material (the host's choice; without one the instance is the reference's loop as it was).
 // kRoulette: Russian roulette from bounce `roulette` on, the last bounce excepted (DESIGN section 5h; the host picks the instance
-// when some bounce plays): after the emitter check and before evaluate_material, on the roulette stream of the pixel.
-template <bool kEmit, bool kRoulette = false>
-__global__ __launch_bounds__(kWave) void k_megakernel(DScene sc, DCamera cam, uint32_t iteration, DBand band,
-                                                      uint32_t pix_count, int max_bounces, DFrame fb,
-                                                      DeviceCounters* counters, int roulette)
+// when some bounce plays): after the emitter check and before evaluate_material, on the roulette stream of the pixel.  A path that
+// ends there leaves colour 0 and makes no draw.
+// kDirect (with kEmit; DESIGN section 5g): one light sample (section 5f, pt_light_sample.hpp) and one shadow ray at every diffuse
+// hit, a per-path radiance sum and the emission gate that keeps a lamp from being counted twice -- and nothing else.  The shadow
+// ray takes the per-thread any-hit walk (scene_occluded) on the thread's own LDS stack, which is free while it runs.  The light
+// samples draw from a stream of their own (path_seed(pixel, iteration) ^ kLightSeedXor, draws 3b .. 3b + 2 at bounce b), so every
+// material draw, every closest hit, the normal and depth planes and rays_total are those of the plain loop at the same iteration:
+// only the colour differs.  A path roulette ends takes no light sample at that hit and adds nothing to the three loop counters; a
+// survivor's light sample is weighted with the divided colour.  tests/direct_loop_ref.py restates the loop in numpy.
+// stats (kDirect): kLightStatLines lines of kLoopStatWords 64-bit words; word 0 += diffuse hits, word 1 += shadow rays traced,
+// word 2 += unoccluded ones.  stack: the calling thread's column of the workgroup's LDS stack.
+template <bool kEmit, bool kRoulette, bool kDirect>
+__device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, const DCamera& cam, const uint32_t iteration, const DBand band,
+                                          const uint32_t pix_count, const int max_bounces, const DFrame fb, DeviceCounters* counters,
+                                          unsigned long long* stats, const int roulette, uint32_t* stack)
 {
-  __shared__ uint32_t s_stack[kStackDepth * kWave];
+  static_assert(kEmit || !kDirect, "direct lighting: launched only for a scene with a lamp table, so with an emissive material");
   const uint32_t s = blockIdx.x * kWave + threadIdx.x;
   uint32_t rays = 0u, flags = 0u;
+  uint32_t n_diffuse = 0u, n_shadow = 0u, n_clear = 0u;
   if (s < pix_count) {
     const uint32_t pixel = band_pixel(band, s);
-    const uint32_t x = pixel % cam.width, y = pixel / cam.width;
     Minstd rng;
-    rng.seed(path_seed(pixel, iteration));
-    const float fx = (float)x + rng.uniform();
-    const float fy = (float)y + rng.uniform();
     Ray ray;
-    generate_ray(cam, fx, fy, ray.o, ray.d);
-    ray.tmin = 1e-4f;
-    ray.tmax = FLT_MAX;
+    primary_ray(cam, pixel, iteration, rng, ray);
     f3 color = mk3(1.0f, 1.0f, 1.0f);
+    f3 radiance = mk3(0.0f, 0.0f, 0.0f);
+    bool count_emission = true;  // the last vertex drew no light sample (the camera, metal, glass): a lamp hit from it counts
     f3 normal = -ray.d;
     float depth = 1e6f;
     for (int i = 0; i < max_bounces; ++i) {
@@ -36,7 +44,7 @@ __global__ __launch_bounds__(kWave) void k_megakernel(DScene sc, DCamera cam, ui
       rec.side = 0u;
       ++rays;
       Tally tally;
-      if (!ray_scene<false>(ray, sc, rec, s_stack + threadIdx.x, flags, tally)) {
+      if (!ray_scene<false>(ray, sc, rec, stack, flags, tally)) {
         color = color * background(ray.d);
         break;
       }
@@ -45,24 +53,70 @@ __global__ __launch_bounds__(kWave) void k_megakernel(DScene sc, DCamera cam, ui
         depth = rec.t;
       }
       bool tmin_flag = ray.tmin != 1e-4f;
-      if (kEmit && is_emitter(sc.materials[rec.mat])) {  // the path ends at the emitter: no draw
-        color = emit_color(color, sc.materials[rec.mat]);
+      const DMaterial& mat = sc.materials[rec.mat];
+      if (kEmit && is_emitter(mat)) {  // the path ends at the emitter: no draw; after a diffuse vertex its light sample has counted the lamp
+        color = !kDirect || count_emission ? emit_color(color, mat) : mk3(0.0f, 0.0f, 0.0f);
         break;
       }
       if (kRoulette && i >= roulette && i != max_bounces - 1 && roulette_ends(color, pixel, iteration, (uint32_t)i)) {
-        color = mk3(0.0f, 0.0f, 0.0f);  // the path ends by chance: the sample is 0, no draw
+        color = mk3(0.0f, 0.0f, 0.0f);  // the path ends by chance: the sample is (radiance +) 0, no draw, no light sample
         break;
       }
-      evaluate_material(ray.o, ray.d, tmin_flag, rec.p, rec.n, rec.side, sc.materials[rec.mat], rng, color);
+      evaluate_material(ray.o, ray.d, tmin_flag, rec.p, rec.n, rec.side, mat, rng, color);
       ray.tmin = tmin_flag ? 1e-5f : 1e-4f;
+      if constexpr (kDirect) {
+        count_emission = mat.type != 0;
+        if (mat.type == 0) {  // diffuse: colour is throughput x albedo now; one light sample at the hit, about the unflipped normal
+          ++n_diffuse;
+          const LightSample ls = light_sample_point(lt, rec.p, rec.n, pixel, iteration, 3u * (uint32_t)i);
+          if (ls.sampled) {
+            ++n_shadow;
+            Ray shadow;
+            shadow.o = rec.p;
+            shadow.tmin = 1e-4f;
+            shadow.d = ls.w;
+            shadow.tmax = ls.tmax;
+            if (!scene_occluded(shadow, sc, stack, flags)) {
+              ++n_clear;
+              radiance = radiance + color * ls.contrib;
+            }
+          }
+        }
+      }
     }
-    accumulate_color(fb.color4, s, iteration, color);
+    accumulate_color(fb.color4, s, iteration, kDirect ? radiance + color : color);
     accumulate_nd(fb.nd4, s, iteration, normal, depth);
     if (flags) atomicOr(&counters->flags, flags);
   }
-  // one ray-counter atomic per wavefront
-  uint32_t sum = rays;
+  // one atomic per counter and wavefront; the three loop counters spread over lines (adds to one line serialise in L2)
+  uint32_t sum = rays, sd = n_diffuse, ss = n_shadow, sv = n_clear;
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
-  if (threadIdx.x == 0u && sum) atomicAdd(&counters->rays_total, (unsigned long long)sum);
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_down(sum, off, 64);
+    if constexpr (kDirect) {
+      sd += __shfl_down(sd, off, 64);
+      ss += __shfl_down(ss, off, 64);
+      sv += __shfl_down(sv, off, 64);
+    }
+  }
+  if (threadIdx.x == 0u) {
+    if (sum) atomicAdd(&counters->rays_total, (unsigned long long)sum);
+    if constexpr (kDirect) {
+      unsigned long long* line = stats + kLoopStatWords * (blockIdx.x % kLightStatLines);
+      if (sd) atomicAdd(&line[0], (unsigned long long)sd);
+      if (ss) atomicAdd(&line[1], (unsigned long long)ss);
+      if (sv) atomicAdd(&line[2], (unsigned long long)sv);
+    }
+  }
+}
+
+// the plain loop (instances: pt_kernels.hip; the ones that play roulette: pt_mega_direct.hip)
+template <bool kEmit, bool kRoulette = false>
+__global__ __launch_bounds__(kWave) void k_megakernel(DScene sc, DCamera cam, uint32_t iteration, DBand band,
+                                                      uint32_t pix_count, int max_bounces, DFrame fb,
+                                                      DeviceCounters* counters, int roulette)
+{
+  __shared__ uint32_t s_stack[kStackDepth * kWave];
+  mega_path<kEmit, kRoulette, false>(sc, DLights{}, cam, iteration, band, pix_count, max_bounces, fb, counters, nullptr, roulette,
+                                     s_stack + threadIdx.x);
 }

@@ -131,20 +131,12 @@ __device__ __forceinline__ int persist_service(const DScene& sc, const uint32_t 
       DeviceCounters* ctr = counters + frame;
       const uint32_t* list = bounce == 0u ? pa.list0 : nullptr;
       DPaths in = pa.paths[bounce & 1u], out = pa.paths[(bounce & 1u) ^ 1u];
-      in.o4 += fo;
-      in.d4 += fo;
-      in.t2 += fo;
-      out.o4 += fo;
-      out.d4 += fo;
-      out.t2 += fo;
+      offset_frame(in, fo);
+      offset_frame(out, fo);
       DHits h = hits;
-      h.tp += fo;
-      h.nm += fo;
+      offset_frame(h, fo);
       DFrame fb = pa.stage;
-      if (pa.staged) {
-        fb.color4 += fo;
-        fb.nd4 += fo;
-      }
+      if (pa.staged) offset_frame(fb, fo);
       const int last = (int)bounce == pa.max_bounces - 1 ? 1 : 0;
 #pragma unroll 1
       for (uint32_t tile = first; tile < end_tile; ++tile)

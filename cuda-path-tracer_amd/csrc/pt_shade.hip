@@ -9,10 +9,12 @@ static_assert(pt::beam_rules::kLeaf == pt::kLeafBit, "pt_beam_rules.hpp restates
 static_assert((uint32_t)pt::beam_rules::kEntries == pt::kBeamEntries, "pt_beam_rules.hpp restates the entries per tile (pt_device.hpp)");
 static_assert(pt::feed_rules::kBatch == (uint32_t)pt::kWave, "a feed batch is one wavefront's worth of rays");
 #include <float.h>
+#include <type_traits>
 
 namespace pt {
 
 #include "pt_kernels_common.inc"
+#include "pt_shade_tile.inc"  // the end of a bounce per path (goes_on, bounce_outcome, pack_survivor) and per tile (shade_tile)
 
 // raygen_kernel, ray_gen.cu:11-32.  Slot s of this context holds pixel band_pixel(band, s).
 // kFilter ("filter_rays"): the bounce's first launch is a traversal launch over the mesh objects [filt_begin, filt_end)
@@ -33,7 +35,7 @@ __global__ __launch_bounds__(256) void k_raygen(DCameras cams, DBatchInfo bi, DB
   const uint32_t frame = blockIdx.x % bi.count;  // see DBatchInfo; frame-fastest: neighbouring workgroups take their tickets on different lines
   const DCamera& cam = cams.c[frame];
   const uint32_t iteration = bi.iteration[frame];
-  paths.o4 += (size_t)frame * bi.stride;
+  paths.o4 += (size_t)frame * bi.stride;  // (written out, not offset_frame: with it k_raygen<true, true> orders its scalar adds differently)
   paths.d4 += (size_t)frame * bi.stride;
   counters += frame;
   scan.desc += (size_t)frame * tile_stride;
@@ -56,13 +58,10 @@ __global__ __launch_bounds__(256) void k_raygen(DCameras cams, DBatchInfo bi, DB
     const uint32_t s = block_first + (uint32_t)j * 256u + threadIdx.x;
     if (s >= pix_count) continue;
     const uint32_t pixel = band_pixel(band, s);
-    const uint32_t x = pixel % cam.width, y = pixel / cam.width;
     Minstd rng;
-    rng.seed(path_seed(pixel, iteration));
-    const float fx = (float)x + rng.uniform();
-    const float fy = (float)y + rng.uniform();
-    f3 o, d;
-    generate_ray(cam, fx, fy, o, d);
+    Ray ray;
+    primary_ray(cam, pixel, iteration, rng, ray);
+    const f3 o = ray.o, d = ray.d;
     bool may_hit = true;
     if (kFilter) {
       may_hit = may_hit_boxes(objects, filt_begin, filt_end, o, d, FLT_MAX);
@@ -95,10 +94,8 @@ __global__ __launch_bounds__(256) void k_raygen_next(DScene sc, DCameras cams, D
   const DCamera& cam = cams.c[frame];
   const uint32_t iteration = bi.iteration[frame];
   const size_t fo = (size_t)frame * bi.stride;
-  paths.o4 += fo;
-  paths.d4 += fo;
-  next.hits.tp += fo;
-  next.hits.nm += fo;
+  offset_frame(paths, fo);
+  offset_frame(next.hits, fo);
   next.flags += fo;
   counters += frame;
   const uint32_t tile = blockIdx.x / bi.count;
@@ -112,17 +109,11 @@ __global__ __launch_bounds__(256) void k_raygen_next(DScene sc, DCameras cams, D
     const uint32_t s = block_first + (uint32_t)j * 256u + threadIdx.x;
     if (s >= pix_count) continue;
     const uint32_t pixel = band_pixel(band, s);
-    const uint32_t x = pixel % cam.width, y = pixel / cam.width;
     Minstd rng;
-    rng.seed(path_seed(pixel, iteration));
-    const float fx = (float)x + rng.uniform();
-    const float fy = (float)y + rng.uniform();
     Ray ray;
-    generate_ray(cam, fx, fy, ray.o, ray.d);
+    primary_ray(cam, pixel, iteration, rng, ray);  // (t_min as load_ray reads it: the sign bit of a primary ray's pixel word is clear)
     stnt(&paths.o4[s], make_float4(ray.o.x, ray.o.y, ray.o.z, __uint_as_float(pixel)));
     stnt(&paths.d4[s], make_float4(ray.d.x, ray.d.y, ray.d.z, 0.0f));
-    ray.tmin = 1e-4f;  // (load_ray: the sign bit of a primary ray's pixel word is clear)
-    ray.tmax = FLT_MAX;
     Hit rec;
     bool changed = false;
     if (next.fold_run != 0u) sphere_fold(sc, next.begin, next.end, ray, rec, changed);
@@ -154,10 +145,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PT_SPHERES_
                                                  uint32_t filt_end, uint32_t* worklist, DTileScan scan, uint32_t tile_stride)
 {
   const uint32_t frame = blockIdx.x % bi.count;  // see DBatchInfo; frame-fastest as in k_raygen
-  paths.o4 += (size_t)frame * bi.stride;
-  paths.d4 += (size_t)frame * bi.stride;
-  hits.tp += (size_t)frame * bi.stride;
-  hits.nm += (size_t)frame * bi.stride;
+  offset_frame(paths, (size_t)frame * bi.stride);
+  offset_frame(hits, (size_t)frame * bi.stride);
   counters += frame;
   scan.desc += (size_t)frame * tile_stride;
   const uint32_t n = counters->live[bounce];
@@ -297,8 +286,8 @@ __global__ __launch_bounds__(256) void k_list_flags(const uint8_t* flags, int bo
 // kSpheres: objects [obj_begin, obj_end) are tested; kFirst: nothing has written the hit record in this bounce yet.
 // kEmit: the scene has an emissive material; a hit on one ends the path (k_shade) and is not counted live.
 // kRoulette: the bounce plays Russian roulette: a hit that would go on makes the roulette decision here, from
-// the throughput that came into the bounce, and is not counted live when it ends; k_shade<.., true> makes the same decision from
-// the same operands (roulette_ends).
+// the throughput that came into the bounce, and is not counted live when it ends.  Both are goes_on (pt_shade_tile.inc), which
+// k_shade asks as well.
 // 256-thread workgroups: one wavefront per SIMD fits beside the other stream's persistent traversal wavefronts as soon
 // as one of those has left (1024-thread workgroups wait until four per SIMD have: measured 15 % slower end to end,
 // together with a scan fused in behind a "last workgroup" sign-off).
@@ -308,11 +297,8 @@ __global__ __launch_bounds__(256) void k_tail_count(DScene sc, uint32_t obj_begi
                                                     const uint32_t* slot_base)
 {
   const uint32_t frame = blockIdx.y;  // see DBatchInfo
-  paths.o4 += (size_t)frame * bi.stride;
-  paths.d4 += (size_t)frame * bi.stride;
-  hits.tp += (size_t)frame * bi.stride;
-  hits.nm += (size_t)frame * bi.stride;
-  if (kRoulette) paths.t2 += (size_t)frame * bi.stride;
+  offset_frame(paths, (size_t)frame * bi.stride);
+  offset_frame(hits, (size_t)frame * bi.stride);
   chunk_counts += (size_t)frame * bi.chunk_stride;
   counters += frame;
   const uint32_t n = counters->live[bounce];
@@ -326,6 +312,8 @@ __global__ __launch_bounds__(256) void k_tail_count(DScene sc, uint32_t obj_begi
     if (!kFirst) t_so_far = ldnt(&hits.tp[s]).x;
     hit = t_so_far >= 0.0f;
     float through_x = 1.0f;  // (kRoulette: d4.w, from the sphere run's own load of the ray when there is one)
+    uint32_t mat_word = 0u;
+    bool have_word = false;  // the hit is the sphere run's: its material is at hand
     if (kSpheres) {
       Ray ray = kRoulette ? load_ray(paths, s, through_x) : load_ray(paths, s);
       if (hit) ray.tmax = t_so_far;
@@ -334,21 +322,22 @@ __global__ __launch_bounds__(256) void k_tail_count(DScene sc, uint32_t obj_begi
       sphere_segment(sc, obj_begin, obj_end, ray, rec, changed);
       if (changed) {
         store_hit(hits, s, rec);
-        hit = true;
-        if (kEmit && is_emitter(sc.materials[rec.mat])) hit = false;
+        hit = have_word = true;
+        mat_word = rec.mat;
       } else if (kFirst) {
         stnt(&hits.tp[s], make_float4(-1.0f, 0.f, 0.f, 0.f));
-      } else if (kEmit && hit) {
-        hit = !is_emitter(sc.materials[__float_as_uint(ldnt(&hits.nm[s]).w) & 0x7fffffffu]);
       }
-    } else if (kEmit && hit) {
-      hit = !is_emitter(sc.materials[__float_as_uint(ldnt(&hits.nm[s]).w) & 0x7fffffffu]);
     }
-    if (kRoulette && hit) {  // (the host picks a kRoulette instance for no last bounce: every hit that goes on plays)
-      const float2 t2 = bounce == 0 ? make_float2(1.0f, 1.0f) : ldnt(&paths.t2[s]);
-      if (!kSpheres) through_x = ldnt(&paths.d4[s]).w;
-      f3 c = mk3(bounce == 0 ? 1.0f : through_x, t2.x, t2.y);
-      hit = !roulette_ends(c, (slot_base ? *slot_base : 0u) + s, bi.iteration[frame], (uint32_t)bounce);
+    if ((kEmit || kRoulette) && hit) {  // (the host picks a kRoulette instance for no last bounce: every hit that goes on plays)
+      if (kEmit && !have_word) mat_word = __float_as_uint(ldnt(&hits.nm[s]).w);
+      const auto through = [&]() -> f3 {  // (loaded for a hit that plays only)
+        const float2 t2 = bounce == 0 ? make_float2(1.0f, 1.0f) : ldnt(&paths.t2[s]);
+        if (!kSpheres) through_x = ldnt(&paths.d4[s]).w;
+        return mk3(bounce == 0 ? 1.0f : through_x, t2.x, t2.y);
+      };
+      f3 c;
+      bool ended;
+      hit = goes_on<kEmit, kRoulette>(sc, mat_word, through, c, (slot_base ? *slot_base : 0u) + s, bi.iteration[frame], (uint32_t)bounce, ended);
     }
   }
   const uint64_t live = __ballot(hit);  // (kEmit, kRoulette: hits that go on)
@@ -412,19 +401,11 @@ __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out,
   const uint32_t iteration = bi.iteration[frame];
   const uint32_t acc_iteration = staged ? 0u : iteration;
   if (octs) octs += (size_t)frame * bi.stride;
-  in.o4 += (size_t)frame * bi.stride;
-  in.d4 += (size_t)frame * bi.stride;
-  in.t2 += (size_t)frame * bi.stride;
-  out.o4 += (size_t)frame * bi.stride;
-  out.d4 += (size_t)frame * bi.stride;
-  out.t2 += (size_t)frame * bi.stride;
-  hits.tp += (size_t)frame * bi.stride;
-  hits.nm += (size_t)frame * bi.stride;
+  offset_frame(in, (size_t)frame * bi.stride);
+  offset_frame(out, (size_t)frame * bi.stride);
+  offset_frame(hits, (size_t)frame * bi.stride);
   chunk_offsets += (size_t)frame * bi.chunk_stride;
-  if (staged) {
-    fb.color4 += (size_t)frame * bi.stride;
-    fb.nd4 += (size_t)frame * bi.stride;
-  }
+  if (staged) offset_frame(fb, (size_t)frame * bi.stride);
   counters += frame;
   const uint32_t n = counters->live[bounce];
   const uint32_t s = blockIdx.x * 256u + threadIdx.x;
@@ -432,7 +413,8 @@ __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out,
   const bool active = s < n;
   bool survives = false;
   f3 ro = mk3(0, 0, 0), rd = mk3(0, 0, 0), color = mk3(0, 0, 0);
-  uint32_t pixbits = 0u;
+  uint32_t pixel = 0u;
+  bool tmin_flag = false;
   if (active) {
     const float4 o4 = ldnt(&in.o4[s]);
     const float4 d4 = ldnt(&in.d4[s]);
@@ -441,49 +423,31 @@ __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out,
     ro = xyz(o4);
     rd = xyz(d4);
     color = mk3(bounce == 0 ? 1.0f : d4.w, t2.x, t2.y);
-    pixbits = __float_as_uint(o4.w);
-    const uint32_t pixel = pixbits & 0x7fffffffu;
-    const uint32_t local_pixel = band_local(band, pixel);
-    bool tmin_flag = (pixbits >> 31) != 0u;
-
-    if (tp.x < 0.0f) {
-      // miss: throughput *= sky; the path ends (path_tracer.cu:304-307, 283-289)
-      color = color * background(rd);
-      if (bounce == 0) accumulate_nd(fb.nd4, local_pixel, acc_iteration, -rd, 1e6f);  // raygen defaults, ray_gen.cu:26-28
-      accumulate_color(fb.color4, local_pixel, acc_iteration, color);
-    } else {
-      const float4 nm = ldnt(&hits.nm[s]);
-      const f3 hn = xyz(nm);
-      if (bounce == 0) accumulate_nd(fb.nd4, local_pixel, acc_iteration, hn, tp.x);  // path_tracer.cu:308-311
-      const uint32_t ms = __float_as_uint(nm.w);
-      const DMaterial m = sc.materials[ms & 0x7fffffffu];
-      // RNG re-seeded from the global slot index, then discard(bounce) (path_tracer.cu:300-301)
-      const uint32_t slot = (slot_base ? *slot_base : 0u) + s;
-      Minstd rng;
-      rng.seed(path_seed(slot, iteration));
-      rng.discard((uint32_t)bounce);
-      const f3 hp = mk3(tp.y, tp.z, tp.w);
-      const bool emits = kEmit && is_emitter(m);
-      // roulette: the path ends with the sample (0, 0, 0) and no draw, or goes on with its throughput divided (section 5h)
-      // (the host picks a kRoulette instance for no last bounce)
-      const bool ended = kRoulette && !emits && roulette_ends(color, slot, iteration, (uint32_t)bounce);
-      if (emits) color = emit_color(color, m);  // the path ends at the emitter: no draw
-      else if (ended) color = mk3(0.0f, 0.0f, 0.0f);
-      else evaluate_material(ro, rd, tmin_flag, hp, hn, ms >> 31, m, rng, color);
-      if (last_bounce || emits || ended) {
-        accumulate_color(fb.color4, local_pixel, acc_iteration, color);  // capped paths deposit raw throughput
-      } else {
-        survives = true;
-        pixbits = pixel | (tmin_flag ? 0x80000000u : 0u);
-      }
+    pixel = __float_as_uint(o4.w) & 0x7fffffffu;
+    tmin_flag = (__float_as_uint(o4.w) >> 31) != 0u;
+    const uint32_t slot = (slot_base ? *slot_base : 0u) + s;
+    const bool hit = !(tp.x < 0.0f);
+    float4 nm = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool emits = false, ended = false;
+    if (hit) {
+      nm = ldnt(&hits.nm[s]);
+      // the decision k_tail_count has counted by: an emitter ends the path; roulette ends it with the sample (0, 0, 0) and no draw,
+      // or lets it go on with its throughput divided (section 5h; the host picks a kRoulette instance for no last bounce)
+      const bool on = goes_on<kEmit, kRoulette>(sc, __float_as_uint(nm.w), [&] { return color; }, color, slot, iteration, (uint32_t)bounce, ended);
+      emits = !on && !ended;
     }
+    survives = bounce_outcome(sc, fb, band_local(band, pixel), acc_iteration, bounce, last_bounce, slot, iteration, hit, tp, nm, emits, ended,
+                              ro, rd, tmin_flag, color);
   }
   const uint64_t live = __ballot(survives);
   if (survives) {
     const uint32_t dst = chunk_offsets[s / kChunk] + rank_below(live);
-    stnt(&out.o4[dst], make_float4(ro.x, ro.y, ro.z, __uint_as_float(pixbits)));
-    stnt(&out.d4[dst], make_float4(rd.x, rd.y, rd.z, color.x));
-    stnt(&out.t2[dst], make_float2(color.y, color.z));
+    float4 o4, d4;
+    float2 t2;
+    pack_survivor(ro, rd, color, pixel, tmin_flag, o4, d4, t2);
+    stnt(&out.o4[dst], o4);
+    stnt(&out.d4[dst], d4);
+    stnt(&out.t2[dst], t2);
     // direction octant of the new ray, for the coherence sort of the next bounce (k_sort_octant)
     if (octs) octs[dst] = (uint8_t)((rd.x < 0.0f ? 1u : 0u) | (rd.y < 0.0f ? 2u : 0u) | (rd.z < 0.0f ? 4u : 0u));
   }
@@ -514,9 +478,6 @@ __global__ __launch_bounds__(256) void k_shade(DScene sc, DPaths in, DPaths out,
 // Slots per thread: 2 (round 4; 4 until then).  With four the kernel needs 128 registers and spills 18 of them at four
 // wavefronts per SIMD; with two it needs 88, spills nothing and runs five: config 2 +2.2 %, config 3 +0.6 ... 1.2 %;
 // one slot (eight wavefronts): -4 ... -6 % (profiles/r04_config2_counters.txt).  Six wavefronts (80 registers) spill 53.
-#include "pt_shade_tile.inc"
-
-
 template <bool kSpheres, bool kFirst, bool kNext = false, bool kEmit = false, bool kRoulette = false>
 // (occupancy bounds re-measured on the final build: at least 5 or 6 wavefronts per SIMD forces spills, -8 % / -13 % end
 // to end; 1 to 3 compile to the same 124 registers)
@@ -532,7 +493,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PT_SHADE_WA
   const uint32_t iteration = bi.iteration[frame];
   const size_t fo = (size_t)frame * bi.stride;
   if (octs) octs += fo;
-  in.o4 += fo;
+  in.o4 += fo;  // (written out, not offset_frame: with it the kFirst instances order two scalar adds differently)
   in.d4 += fo;
   in.t2 += fo;
   out.o4 += fo;
@@ -576,8 +537,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PT_SHADE_WA
 
   // (the tile itself: pt_shade_tile.inc, shared with the persistent launch's service wavefronts)
   if (kNext) {  // (the next bounce's records and bytes of this frame)
-    next.hits.tp += fo;
-    next.hits.nm += fo;
+    offset_frame(next.hits, fo);
     next.flags += fo;
   }
   shade_tile<kSpheres, kFirst, 4, false, kNext, kEmit, kRoulette>(sc, obj_begin, obj_end, in, out, hits, staged, bounce, last_bounce, slot_base, tile_desc, epoch, fb, band,
@@ -682,6 +642,21 @@ __global__ __launch_bounds__(256) void k_accumulate(DFrame stage, DFrame fb, uin
 // ------------------------------------------------------------------------------------------------
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
 
+// Run-time booleans to template arguments: with_flags(f, a, b, ...) calls f(A{}, B{}, ...) with std::true_type or std::false_type
+// in each flag's place, so f (a generic lambda) names its kernel instance as k<decltype(a)::value, ...>.  Every combination is
+// compiled: f leaves out, by `if constexpr`, the ones its caller never asks for (they would be kernels nobody launches).
+template <class F>
+static inline void with_flags(F&& f)
+{
+  f();
+}
+template <class F, class... Rest>
+static inline void with_flags(F&& f, bool flag, Rest... rest)
+{
+  if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
 void launch_raygen(hipStream_t s, const DCameras& cams, const DBatchInfo& bi, DBand band, uint32_t pix_count,
                    DPaths paths, DeviceCounters* counters, const DObject* objects, uint32_t filt_begin, uint32_t filt_end,
                    uint32_t* worklist, DHits hits, unsigned long long* tile_desc, uint32_t tile_stride, uint32_t epoch,
@@ -713,17 +688,12 @@ void launch_spheres(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint
 {
   const dim3 grid(div_up(max_paths, 256u * kListPer) * bi.count), block(256);
   const DTileScan scan{tile_desc, epoch};
-#define PT_SPHERES(FIRST, FILTER)                                                                                              \
-  hipLaunchKernelGGL((k_spheres<FIRST, FILTER>), grid, block, 0, s, scene, obj_begin, obj_end, paths, hits, bounce, counters, bi, \
-                     filt_begin, filt_end, worklist, scan, tile_stride)
-  if (worklist && filt_begin < filt_end && tile_desc) {
-    if (first) PT_SPHERES(true, true);
-    else PT_SPHERES(false, true);
-  } else {
-    if (first) PT_SPHERES(true, false);
-    else PT_SPHERES(false, false);
-  }
-#undef PT_SPHERES
+  with_flags(
+      [&](auto kFirst, auto kFilter) {
+        hipLaunchKernelGGL((k_spheres<decltype(kFirst)::value, decltype(kFilter)::value>), grid, block, 0, s, scene, obj_begin, obj_end, paths, hits,
+                           bounce, counters, bi, filt_begin, filt_end, worklist, scan, tile_stride);
+      },
+      first, worklist && filt_begin < filt_end && tile_desc);
 }
 void launch_list_flags(hipStream_t s, const uint8_t* flags, uint32_t max_paths, int bounce, DeviceCounters* counters, const DBatchInfo& bi,
                        uint32_t* worklist, unsigned long long* tile_desc, uint32_t tile_stride, uint32_t epoch)
@@ -737,31 +707,16 @@ void launch_tail_count(hipStream_t s, const DScene& scene, uint32_t obj_begin, u
                        const DBatchInfo& bi, bool emitters, bool roulette, const uint32_t* slot_base)
 {
   const dim3 grid(div_up(max_paths, 256u), bi.count), block(256);
-#define PT_TAIL_R(SPH, FIRST, EMIT, ROUL)                                                                                          \
-  hipLaunchKernelGGL((k_tail_count<SPH, FIRST, EMIT, ROUL>), grid, block, 0, s, scene, obj_begin < obj_end ? obj_begin : 0u,       \
-                     obj_begin < obj_end ? obj_end : 0u, paths, hits, bounce, chunk_counts, counters, bi, slot_base)
-  // (a bounce that plays roulette: the same six instances with kRoulette)
-#define PT_TAIL(SPH, FIRST, EMIT)                  \
-  do {                                             \
-    if (roulette) PT_TAIL_R(SPH, FIRST, EMIT, true); \
-    else PT_TAIL_R(SPH, FIRST, EMIT, false);       \
-  } while (0)
-  if (obj_begin < obj_end) {
-    if (first) {
-      if (emitters) PT_TAIL(true, true, true);
-      else PT_TAIL(true, true, false);
-    } else {
-      if (emitters) PT_TAIL(true, false, true);
-      else PT_TAIL(true, false, false);
-    }
-  } else if (emitters) {
-    PT_TAIL(false, false, true);
-  } else {
-    // (nothing to test: some closest-hit launch has written every record of the bounce)
-    PT_TAIL(false, false, false);
-  }
-#undef PT_TAIL
-#undef PT_TAIL_R
+  // spheres: there is a run to test; without one some closest-hit launch has written every record of the bounce (so: not first)
+  const bool spheres = obj_begin < obj_end;
+  with_flags(
+      [&](auto kSpheres, auto kFirst, auto kEmit, auto kRoulette) {
+        if constexpr (decltype(kSpheres)::value || !decltype(kFirst)::value)
+          hipLaunchKernelGGL((k_tail_count<decltype(kSpheres)::value, decltype(kFirst)::value, decltype(kEmit)::value, decltype(kRoulette)::value>),
+                             grid, block, 0, s, scene, spheres ? obj_begin : 0u, spheres ? obj_end : 0u, paths, hits, bounce, chunk_counts,
+                             counters, bi, slot_base);
+      },
+      spheres, spheres && first, emitters, roulette);  // (roulette: a bounce that plays)
 }
 void launch_scan(hipStream_t s, int bounce, bool last_bounce, const uint32_t* chunk_counts, uint32_t* chunk_offsets,
                  DeviceCounters* counters, const DBatchInfo& bi)
@@ -774,18 +729,12 @@ void launch_shade(hipStream_t s, const DScene& scene, DPaths in, DPaths out, DHi
                   const uint32_t* chunk_offsets, DFrame fb, DBand band, DeviceCounters* counters, uint8_t* octs,
                   const DBatchInfo& bi, bool emitters, bool roulette)
 {
-#define PT_SHADE(EMIT, ROUL)                                                                                                  \
-  hipLaunchKernelGGL((k_shade<EMIT, ROUL>), dim3(div_up(max_paths, 256u), bi.count), dim3(256), 0, s, scene, in, out, hits, \
-                     staged ? 1 : 0, bounce, last_bounce ? 1 : 0, slot_base, chunk_offsets, fb, band, counters, octs, bi)
-  if (roulette) {  // (a bounce that plays roulette)
-    if (emitters) PT_SHADE(true, true);
-    else PT_SHADE(false, true);
-  } else if (emitters) {
-    PT_SHADE(true, false);
-  } else {
-    PT_SHADE(false, false);
-  }
-#undef PT_SHADE
+  with_flags(
+      [&](auto kEmit, auto kRoulette) {
+        hipLaunchKernelGGL((k_shade<decltype(kEmit)::value, decltype(kRoulette)::value>), dim3(div_up(max_paths, 256u), bi.count), dim3(256), 0, s,
+                           scene, in, out, hits, staged ? 1 : 0, bounce, last_bounce ? 1 : 0, slot_base, chunk_offsets, fb, band, counters, octs, bi);
+      },
+      emitters, roulette);  // (roulette: a bounce that plays)
 }
 void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths in, DPaths out,
                         DHits hits, uint32_t max_paths, bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
@@ -795,35 +744,20 @@ void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, 
 {
   const dim3 grid(div_up(max_paths, kFuseTile) * bi.count), block(256);
   const DNextRun none{};
-#define PT_FUSED_R(SPH, FIRST, NEXT, EMIT, ROUL)                                                                                                \
-  hipLaunchKernelGGL((k_shade_fused<SPH, FIRST, NEXT, EMIT, ROUL>), grid, block, 0, s, scene, obj_begin, obj_end, in, out, hits, staged ? 1 : 0, \
-                     bounce, last_bounce ? 1 : 0, slot_base, tile_desc, tile_stride, epoch, fb, band, counters, octs, bi, list, next ? *next : none)
-  // (a bounce that plays roulette, DESIGN section 5h: the same instances with kRoulette; the caller asks for none at the last bounce)
-#define PT_FUSED_E(SPH, FIRST, NEXT, EMIT)                  \
-  do {                                                      \
-    if (roulette) PT_FUSED_R(SPH, FIRST, NEXT, EMIT, true); \
-    else PT_FUSED_R(SPH, FIRST, NEXT, EMIT, false);         \
-  } while (0)
-  // (scenes with an emissive material: the same five instances with kEmit)
-#define PT_FUSED(SPH, FIRST, NEXT)          \
-  do {                                      \
-    if (emitters) PT_FUSED_E(SPH, FIRST, NEXT, true);  \
-    else PT_FUSED_E(SPH, FIRST, NEXT, false); \
-  } while (0)
-  if (next && !first && !last_bounce) {  // "prefold": the next bounce's leading sphere run rides along
-    if (obj_begin < obj_end) PT_FUSED(true, false, true);
-    else PT_FUSED(false, false, true);
-  } else if (obj_begin < obj_end) {
-    if (first) PT_FUSED(true, true, false);
-    else PT_FUSED(true, false, false);
-  } else if (first) {
-    PT_FUSED(false, true, false);   // a scene without objects: every ray misses
-  } else {
-    PT_FUSED(false, false, false);  // (some closest-hit launch has written every record of the bounce)
-  }
-#undef PT_FUSED
-#undef PT_FUSED_E
-#undef PT_FUSED_R
+  // prefold: the next bounce's leading sphere run rides along; spheres: a run ends the object list (without one, and first: a
+  // scene without objects, every ray misses; not first: some closest-hit launch has written every record of the bounce).
+  // emitters: the scene has an emissive material; roulette: a bounce that plays (the caller asks for none at
+  // the last bounce) -- the same six instances again with kEmit, and those twelve with kRoulette.
+  const bool prefold = next && !first && !last_bounce;
+  with_flags(
+      [&](auto kSpheres, auto kFirst, auto kNext, auto kEmit, auto kRoulette) {
+        if constexpr (!(decltype(kFirst)::value && decltype(kNext)::value))
+          hipLaunchKernelGGL((k_shade_fused<decltype(kSpheres)::value, decltype(kFirst)::value, decltype(kNext)::value, decltype(kEmit)::value,
+                                            decltype(kRoulette)::value>),
+                             grid, block, 0, s, scene, obj_begin, obj_end, in, out, hits, staged ? 1 : 0, bounce, last_bounce ? 1 : 0, slot_base,
+                             tile_desc, tile_stride, epoch, fb, band, counters, octs, bi, list, next ? *next : none);
+      },
+      obj_begin < obj_end, first && !prefold, prefold, emitters, roulette);
 }
 uint32_t shade_tiles_per_frame(uint32_t max_paths) { return div_up(max_paths, kFuseTile); }
 void launch_sort_octant(hipStream_t s, const uint8_t* octs, uint32_t* order, uint32_t max_paths, int bounce,

@@ -1,7 +1,8 @@
 // pt_shade_tile.inc -- one TILE of the kernel that ends a bounce (k_shade_fused, pt_shade.hip): trailing sphere run +
 // material + stable compaction + final gather for kFuseK x 64 x kGroupWaves consecutive slots of one frame.  Included (inside
 // namespace pt, after pt_kernels_common.inc) by pt_shade.hip, whose kernel gives a 256-thread workgroup a tile, and by
-// pt_kernels.hip, whose persistent launch (k_persist, round 5) gives one to a single SERVICE wavefront.
+// pt_persist.hip, whose persistent launch (k_persist, round 5) gives one to a single SERVICE wavefront.  In front of the tile: the
+// end of a bounce for ONE path (goes_on, bounce_outcome, pack_survivor), which k_tail_count and k_shade (pt_shade.hip) share with it.
 //   kGroupWaves  wavefronts of the group that owns the tile: 4 (blockDim 256) or 1 (blockDim 64)
 //   kCoherent    the tile's inputs were written, and its outputs are read, by OTHER wavefronts of the SAME launch (k_persist):
 //                every handed-over byte is then stored write-through (sc1) and loaded past the L1, the per-frame counters are updated by agent-scope atomics, and the caller drains its
@@ -54,6 +55,78 @@ __device__ __forceinline__ void st_out(float4* base, uint32_t index, const float
   } else {
     stnt(&base[index], v);
   }
+}
+
+// ---- the end of a bounce for one path, stated once for the streaming forms (k_tail_count, k_shade, shade_tile) ----
+// "This hit goes on": the path's closest hit is not an emitter (kEmit; mat_word: the hit record's material word, the side bit
+// ignored), and roulette (kRoulette: a bounce that plays; index: the path's global slot) does not end it.  through(): the
+// throughput that came into the bounce, asked for only when roulette plays (a caller that has to load it loads it then); c: that
+// throughput, divided for a path that goes on (roulette_ends).  `ended`: roulette ended it; false with a false result: an emitter
+// did.  What the compaction counts (k_tail_count) and what the material step does (k_shade, which hands both answers to
+// bounce_outcome) must agree: both ask here, with or without roulette.  (shade_tile's phase 1 makes the same two checks in
+// place, as it did: asked here, every form tried gave its roulette instances of k_shade_fused other instructions --
+// profiles/loops_refactor.txt, A.)
+template <bool kEmit, bool kRoulette, class Through>
+__device__ __forceinline__ bool goes_on(const DScene& sc, const uint32_t mat_word, Through&& through, f3& c, const uint32_t index,
+                                        const uint32_t iteration, const uint32_t bounce, bool& ended)
+{
+  ended = false;
+  if (kEmit && is_emitter(sc.materials[mat_word & 0x7fffffffu])) return false;
+  if (kRoulette) {
+    c = through();
+    ended = roulette_ends(c, index, iteration, bounce);
+  }
+  return !ended;
+}
+
+// material_kernel (path_tracer.cu:292-315) and the final gather of a path that ends here, for one slot, in the plain form (one
+// `if` per outcome; shade_tile's default is shade_kinds, the same operations for a wavefront of mixed outcomes).  hit, tp, nm: the
+// closest hit; emits: it is an emitter; ended: roulette has ended the path (both: goes_on's answers); color: the throughput,
+// already divided for a roulette survivor.
+// True: the path survives with its new ray in ro, rd, tmin_flag and its throughput in color.  False: it ended and its sample is
+// in `fb` (staged: acc_iteration 0) -- miss: throughput * sky; emitter: throughput * emission, no draw; roulette: 0, no draw;
+// the last bounce: the raw throughput.
+__device__ __forceinline__ bool bounce_outcome(const DScene& sc, const DFrame& fb, const uint32_t local_pixel, const uint32_t acc_iteration,
+                                               const int bounce, const int last_bounce, const uint32_t slot, const uint32_t iteration,
+                                               const bool hit, const float4 tp, const float4 nm, const bool emits, const bool ended,
+                                               f3& ro, f3& rd, bool& tmin_flag, f3& color)
+{
+  if (!hit) {
+    // miss: throughput *= sky; the path ends (path_tracer.cu:304-307, 283-289)
+    color = color * background(rd);
+    if (bounce == 0) accumulate_nd(fb.nd4, local_pixel, acc_iteration, -rd, 1e6f);  // raygen defaults, ray_gen.cu:26-28
+    accumulate_color(fb.color4, local_pixel, acc_iteration, color);
+    return false;
+  }
+  const f3 hn = xyz(nm);
+  if (bounce == 0) accumulate_nd(fb.nd4, local_pixel, acc_iteration, hn, tp.x);  // path_tracer.cu:308-311
+  const uint32_t ms = __float_as_uint(nm.w);
+  const DMaterial m = sc.materials[ms & 0x7fffffffu];
+  if (emits) {
+    color = emit_color(color, m);  // the path ends at the emitter: no draw
+  } else if (ended) {
+    color = mk3(0.0f, 0.0f, 0.0f);
+  } else {
+    // RNG re-seeded from the global slot index, then discard(bounce) (path_tracer.cu:300-301)
+    Minstd rng;
+    rng.seed(path_seed(slot, iteration));
+    rng.discard((uint32_t)bounce);
+    evaluate_material(ro, rd, tmin_flag, mk3(tp.y, tp.z, tp.w), hn, ms >> 31, m, rng, color);
+  }
+  if (last_bounce || emits || ended) {
+    accumulate_color(fb.color4, local_pixel, acc_iteration, color);  // capped paths deposit raw throughput
+    return false;
+  }
+  return true;
+}
+
+// a survivor as the path arrays hold it (DPaths): o4 = origin, pixel | tmin_flag << 31; d4 = direction, throughput.x; t2 = throughput.yz
+__device__ __forceinline__ void pack_survivor(const f3 ro, const f3 rd, const f3 color, const uint32_t pixel, const bool tmin_flag, float4& o4,
+                                              float4& d4, float2& t2)
+{
+  o4 = make_float4(ro.x, ro.y, ro.z, __uint_as_float(pixel | (tmin_flag ? 0x80000000u : 0u)));
+  d4 = make_float4(rd.x, rd.y, rd.z, color.x);
+  t2 = make_float2(color.y, color.z);
 }
 
 // Every pointer is the frame's own (frame offset applied by the caller); `fo` is that offset in slots (work-list entries are
@@ -135,7 +208,7 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
     }
     const bool hit = s < n_all && tp[j].x >= 0.0f;
     hit_mask |= hit ? 1u << j : 0u;
-    bool goes_on = hit;
+    bool goes_on = hit;  // (goes_on()'s two checks, in place: see there)
     if (kEmit && hit) {  // (kFirst: a hit is the sphere run's, its record is in registers)
       if (!kFirst && !(have_nm >> j & 1u)) {
         nm[j] = ld_in<kCoherent>(hits.nm, s);
@@ -209,41 +282,18 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
         // capped paths deposit raw throughput
         accumulate_color(fb.color4, local_pixel, acc_iteration, color);
       } else {
-        surv_mask |= 1u << j;
+        surv_mask |= 1u << j;  // (pack_survivor, in place: called here it costs every instance 18 instructions and more)
         o4[j] = make_float4(ro.x, ro.y, ro.z, __uint_as_float(pixel | (tmin_flag ? 0x80000000u : 0u)));
         d4[j] = make_float4(rd.x, rd.y, rd.z, color.x);
         t2[j] = make_float2(color.y, color.z);
       }
 #else
-      if (!(hit_mask >> j & 1u)) {
-        // miss: throughput *= sky; the path ends (path_tracer.cu:304-307, 283-289)
-        color = color * background(rd);
-        if (bounce == 0) accumulate_nd(fb.nd4, local_pixel, acc_iteration, -rd, 1e6f);  // raygen defaults, ray_gen.cu:26-28
-        accumulate_color(fb.color4, local_pixel, acc_iteration, color);
-      } else {
-        const f3 hn = xyz(nm[j]);
-        if (bounce == 0) accumulate_nd(fb.nd4, local_pixel, acc_iteration, hn, tp[j].x);  // path_tracer.cu:308-311
-        const uint32_t ms = __float_as_uint(nm[j].w);
-        const DMaterial m = sc.materials[ms & 0x7fffffffu];
-        // RNG re-seeded from the global slot index, then discard(bounce) (path_tracer.cu:300-301)
-        const uint32_t slot = (slot_base ? *slot_base : 0u) + s;
-        Minstd rng;
-        rng.seed(path_seed(slot, iteration));
-        rng.discard((uint32_t)bounce);
-        const f3 hp = mk3(tp[j].y, tp[j].z, tp[j].w);
-        const bool emits = kEmit && is_emitter(m);
-        const bool ended = kRoulette && (ended_mask >> j & 1u) != 0u;  // (roulette, phase 1: no draw, the sample is 0)
-        if (emits) color = emit_color(color, m);  // the path ends at the emitter: no draw
-        else if (ended) color = mk3(0.0f, 0.0f, 0.0f);
-        else evaluate_material(ro, rd, tmin_flag, hp, hn, ms >> 31, m, rng, color);
-        if (last_bounce || emits || ended) {
-          accumulate_color(fb.color4, local_pixel, acc_iteration, color);  // capped paths deposit raw throughput
-        } else {
-          surv_mask |= 1u << j;
-          o4[j] = make_float4(ro.x, ro.y, ro.z, __uint_as_float(pixel | (tmin_flag ? 0x80000000u : 0u)));
-          d4[j] = make_float4(rd.x, rd.y, rd.z, color.x);
-          t2[j] = make_float2(color.y, color.z);
-        }
+      const bool is_hit = (hit_mask >> j & 1u) != 0u;  // (emits, ended: what phase 1 counted by)
+      const bool emits = kEmit && is_hit && is_emitter(sc.materials[__float_as_uint(nm[j].w) & 0x7fffffffu]);
+      if (bounce_outcome(sc, fb, local_pixel, acc_iteration, bounce, last_bounce, (slot_base ? *slot_base : 0u) + s, iteration, is_hit, tp[j], nm[j],
+                         emits, kRoulette && (ended_mask >> j & 1u) != 0u, ro, rd, tmin_flag, color)) {
+        surv_mask |= 1u << j;
+        pack_survivor(ro, rd, color, pixel, tmin_flag, o4[j], d4[j], t2[j]);
       }
 #endif
     }

@@ -260,6 +260,24 @@ def test_megakernel_against_the_restatement(pkg, orc, mb, direct):
             assert (got["diffuse_hits"], got["shadow_rays"], got["unoccluded"]) == (0, 0, 0)
 
 
+def test_the_forms_of_the_end_of_a_bounce_agree(pkg, orc):
+    """64 x 48, 6 bounces, 2 iterations, roulette 1: the fused, three-kernel and persistent forms of the end of a bounce give byte-equal
+    colour (and the restatement's), and the megakernel with "direct_light" 1 -- the one loop with its direct part -- the restatement's."""
+    w, h, mb, iters, k = 64, 48, 6, 2, 1
+    scene = pkg.scenes.cornell_lit(resolution=(w, h), with_mesh=True)
+    flat = scene.build_scene()
+    ref = lr.render_streaming(orc, flat, scene.camera, w, h, 0, iters, mb, roulette=k)
+    assert all(n > 0 for n in _classes(ref)), _classes(ref)
+    forms = {name: _render(pkg, scene, flat, w, h, mb, iters, k, params=params)
+             for name, params in (("fused", ()), ("three_kernels", (("fused_shade", 0),)), ("persist", (("persist", 1),)))}
+    for name, got in forms.items():
+        assert got["color"].tobytes() == forms["fused"]["color"].tobytes(), name
+        _same(got, ref, name)
+    mk = lr.render_megakernel(orc, flat, scene.camera, w, h, 0, iters, mb, direct=True, roulette=k)
+    _same(_render(pkg, scene, flat, w, h, mb, iters, k, method=pkg.GPUMethod.megakernel, direct=True), mk, "megakernel, direct", live=False,
+          counters=COUNTERS)
+
+
 def test_the_refusals(pkg):
     scene, flat = _lit(pkg)
     invalid = pkg._capi.PTC_ERR_INVALID
