@@ -500,5 +500,9 @@ void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights&
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,
                      float* out_sin, float* out_cos);
 void launch_selftest_rng(hipStream_t s, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);
+// test hook (ptc_debug_sphere_lanes): sphere_run_lanes<slots> on the run [obj_begin, obj_end), rays and records in the path-state
+// layout, cand (may be null) one byte per ray; false (nothing launched): slots is neither 1 nor the fused kernel's slots per lane
+bool launch_debug_sphere_lanes(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, int slots, const float4* rays_o4,
+                               const float4* rays_d4, float4* hit_tp, float4* hit_nm, uint32_t n, uint8_t* cand);
 
 }  // namespace pt

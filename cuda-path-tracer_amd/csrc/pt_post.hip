@@ -1,5 +1,5 @@
 // pt_post.hip -- what follows the path: k_preview*, k_pack, k_gather_bands (multi-GPU present), the A-Trous denoiser
-// (k_denoise_positions, k_denoise, k_denoise_lds<step>), k_selftest, k_selftest_rng.
+// (k_denoise_positions, k_denoise, k_denoise_lds<step>), k_selftest, k_selftest_rng, k_debug_sphere_lanes.
 
 #include "pt_device.hpp"
 #include "pt_rng.hpp"
@@ -328,6 +328,43 @@ __global__ void k_selftest_rng(const uint32_t* seeds, const uint32_t* discards, 
   for (int k = 0; k < 6; ++k) out[6u * (size_t)i + (uint32_t)k] = r[k];
 }
 
+// Test hook (ptc_debug_sphere_lanes): sphere_run_lanes<kSlots> on the run [obj_begin, obj_end) for n rays and hit records in
+// the path-state layout (o4 = origin, t_min flag; d4 = direction; tp.x = the closest hit carried in, < 0: none), laid into the
+// slots of a lane as shade_tile lays a tile's: slot j of thread t of workgroup g is ray g * 256 * kSlots + j * 256 + t.  A
+// record is stored only where the run changed it.  cand (may be null): per ray the mask sphere_candidates returned.
+template <int kSlots>
+__global__ __launch_bounds__(256) void k_debug_sphere_lanes(DScene sc, uint32_t obj_begin, uint32_t obj_end, const float4* rays_o4,
+                                                            const float4* rays_d4, float4* hit_tp, float4* hit_nm, uint32_t n,
+                                                            uint8_t* cand)
+{
+  float4 o4[kSlots], d4[kSlots], tp[kSlots], nm[kSlots];
+  uint32_t at[kSlots], valid = 0u;
+#pragma unroll
+  for (int j = 0; j < kSlots; ++j) {
+    at[j] = blockIdx.x * (256u * (uint32_t)kSlots) + (uint32_t)j * 256u + threadIdx.x;
+    tp[j] = make_float4(-1.0f, 0.f, 0.f, 0.f);
+    nm[j] = o4[j] = d4[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (at[j] < n) {
+      valid |= 1u << j;
+      o4[j] = rays_o4[at[j]];
+      d4[j] = rays_d4[at[j]];
+      tp[j] = hit_tp[at[j]];
+    }
+  }
+  if (cand) {
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j)
+      if (at[j] < n) cand[at[j]] = (uint8_t)sphere_candidates<kSlots == 1>(sc, obj_begin, obj_end, o4[j], d4[j], tp[j].x);
+  }
+  const uint32_t changed = sphere_run_lanes<kSlots>(sc, obj_begin, obj_end, o4, d4, tp, nm, valid);
+#pragma unroll
+  for (int j = 0; j < kSlots; ++j)
+    if (at[j] < n && ((changed >> j) & 1u) != 0u) {
+      hit_tp[at[j]] = tp[j];
+      hit_nm[at[j]] = nm[j];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
@@ -387,6 +424,19 @@ void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, 
 void launch_selftest_rng(hipStream_t s, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out)
 {
   hipLaunchKernelGGL(k_selftest_rng, dim3(div_up(n, 256u)), dim3(256), 0, s, seeds, discards, n, out);
+}
+bool launch_debug_sphere_lanes(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, int slots, const float4* rays_o4,
+                               const float4* rays_d4, float4* hit_tp, float4* hit_nm, uint32_t n, uint8_t* cand)
+{
+  if (slots != 1 && slots != kFuseK) return false;
+  if (n == 0u) return true;  // (an empty grid is no launch)
+  if (slots == 1)
+    hipLaunchKernelGGL(k_debug_sphere_lanes<1>, dim3(div_up(n, 256u)), dim3(256), 0, s, scene, obj_begin, obj_end, rays_o4, rays_d4,
+                       hit_tp, hit_nm, n, cand);
+  else
+    hipLaunchKernelGGL(k_debug_sphere_lanes<kFuseK>, dim3(div_up(n, 256u * (uint32_t)kFuseK)), dim3(256), 0, s, scene, obj_begin, obj_end,
+                       rays_o4, rays_d4, hit_tp, hit_nm, n, cand);
+  return true;
 }
 
 }  // namespace pt

@@ -1,5 +1,5 @@
 // ptcore_checks.cpp -- host-side checks of the rules the kernels share with the host (ptc_check_beam, ptc_check_feed,
-// ptc_check_traversal_layout, ptc_check_rng), ptc_debug_beam_entries, ptc_selftest_math, ptc_selftest_rng.  Part of libptcore.so (ptcore_ctx.hpp).
+// ptc_check_traversal_layout, ptc_check_rng), ptc_debug_beam_entries, ptc_debug_sphere_lanes, ptc_selftest_math, ptc_selftest_rng.  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
 #include "pt_rng.hpp"
 
@@ -231,6 +231,90 @@ int ptc_debug_beam_entries(ptc_ctx* ctx, const ptc_camera* camera, float* entrie
   if (e == hipSuccess) e = hipMemcpy(entries_out, dev, floats * sizeof(float), hipMemcpyDeviceToHost);
   (void)hipFree(dev);
   if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("beam entries: ") + hipGetErrorString(e));
+  return PTC_OK;
+}
+
+// Test hook: the per-lane form of a sphere run (sphere_run_lanes<slots>) on the uploaded scene's trailing run, fed with the caller's
+// rays the way ptc_intersect_rays feeds the traversal launches -- t_min as the path state's flag, t_max as the closest hit carried
+// in, a record nothing has written yet a miss.
+int ptc_debug_sphere_lanes(ptc_ctx* ctx, const float* rays, uint32_t n, int slots, float* hit_t, float* hit_normal, uint32_t* hit_material,
+                           uint8_t* hit_side, uint8_t* candidates)
+{
+  if (!ctx || !rays || !hit_t || !hit_normal || !hit_material || !hit_side) return PTC_ERR_INVALID;
+  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
+  if (!lanes_run_of(ctx, ctx->tail_begin, ctx->tail_end))
+    return fail(ctx, PTC_ERR_INVALID, "the trailing sphere run does not take the per-lane form");
+  if (n > 0x7fffffffu) return fail(ctx, PTC_ERR_INVALID, "too many rays");
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* r = rays + 8u * (size_t)i;
+    if (!((r[3] == 1e-4f || r[3] == 1e-5f) && r[7] >= 0.0f)) return fail(ctx, PTC_ERR_INVALID, "t_min must be 1e-4 or 1e-5, t_max >= 0");
+    if (!std::isfinite(r[0] + r[1] + r[2]) || !std::isfinite(r[4] + r[5] + r[6])) return fail(ctx, PTC_ERR_INVALID, "origin and direction must be finite");
+  }
+  constexpr uint32_t kUntouched = 0x7fffffffu;  // material field of a record the run has not written: a miss
+  float untouched_bits;
+  std::memcpy(&untouched_bits, &kUntouched, 4);
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;
+  std::vector<void*> pool;
+  float4 *ro = nullptr, *rd = nullptr, *d_tp = nullptr, *d_nm = nullptr;
+  uint8_t* d_cand = nullptr;
+  const size_t cap = n ? n : 1u;
+  int rc = dev_alloc(ctx, pool, &ro, cap);
+  if (!rc) rc = dev_alloc(ctx, pool, &rd, cap);
+  if (!rc) rc = dev_alloc(ctx, pool, &d_tp, cap);
+  if (!rc) rc = dev_alloc(ctx, pool, &d_nm, cap);
+  if (!rc && candidates) rc = dev_alloc(ctx, pool, &d_cand, cap);
+  if (rc) {
+    free_pool(pool);
+    return rc;
+  }
+  std::vector<float4> ho(n), hd(n), tp(n), nm(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* r = rays + 8u * (size_t)i;
+    const uint32_t flag = r[3] == 1e-5f ? 0x80000000u : 0u;
+    float w;
+    std::memcpy(&w, &flag, 4);
+    ho[i] = make_float4(r[0], r[1], r[2], w);
+    hd[i] = make_float4(r[4], r[5], r[6], 0.0f);
+    // "none yet" as the kernels that call the per-lane form say it (a negative t).  With one ray per lane a cap of +inf -- a closest
+    // hit of FLT_MAX times the form's 1.0001 -- would admit the unset bounds of the slots BEYOND the run as candidates, objects
+    // that are not there: no distance comes near that, and the hook keeps it out
+    tp[i] = make_float4(r[7] < 3.0e38f ? r[7] : -1.0f, 0.0f, 0.0f, 0.0f);
+    nm[i] = make_float4(0.0f, 0.0f, 0.0f, untouched_bits);
+  }
+  hipError_t e = hipSuccess;
+  bool known = true;
+  if (n) {
+    e = hipMemcpyAsync(ro, ho.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rd, hd.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tp, tp.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_nm, nm.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+      known = launch_debug_sphere_lanes(ctx->stream, ctx->scene, ctx->tail_begin, ctx->tail_end, slots, ro, rd, d_tp, d_nm, n, d_cand);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess && known) e = hipMemcpyAsync(tp.data(), d_tp, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && known) e = hipMemcpyAsync(nm.data(), d_nm, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && known && candidates) e = hipMemcpyAsync(candidates, d_cand, n, hipMemcpyDeviceToHost, ctx->stream);
+  } else {
+    known = launch_debug_sphere_lanes(ctx->stream, ctx->scene, 0u, 0u, slots, nullptr, nullptr, nullptr, nullptr, 0u, nullptr);
+  }
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = es;
+  free_pool(pool);
+  if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("sphere lanes: ") + hipGetErrorString(e));
+  if (!known) return fail(ctx, PTC_ERR_INVALID, "slots must be 1 or the fused kernel's slots per lane");
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t ms;
+    std::memcpy(&ms, &nm[i].w, 4);
+    const bool miss = (ms & 0x7fffffffu) == kUntouched;
+    hit_t[i] = miss ? -1.0f : tp[i].x;
+    hit_normal[3u * i] = nm[i].x;
+    hit_normal[3u * i + 1u] = nm[i].y;
+    hit_normal[3u * i + 2u] = nm[i].z;
+    hit_material[i] = miss ? 0u : (ms & 0x7fffffffu);
+    hit_side[i] = miss ? (uint8_t)0 : (uint8_t)(ms >> 31);
+  }
   return PTC_OK;
 }
 

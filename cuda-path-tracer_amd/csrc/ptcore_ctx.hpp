@@ -297,6 +297,7 @@ void free_pool(std::vector<void*>& pool);
 DCamera make_camera(const ptc_camera& c, uint32_t w, uint32_t h);
 int flush_pending(ptc_ctx* ctx, bool from_trace = false);  // enqueue the iterations ptc_trace has queued (ptcore_trace.cpp)
 uint32_t fold_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end);  // may k_spheres take sphere_fold for this run? (ptcore_trace.cpp)
+uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end);  // ... the per-lane form, sphere_run_lanes? (ptcore_trace.cpp)
 int sync_frames(ptc_ctx* ctx);
 // gives back everything a frame state owns and leaves it "no frame" (ptcore.cpp); its streams must be idle (sync_frames)
 void release_frame(ptc_frame_state& f);

@@ -145,6 +145,17 @@ static void sphere_ball_of(const ptc_object& o, const ptc_sphere* spheres, uint3
   float fr = (float)((rad + cerr) * (1.0 + 1e-6));
   fr = std::nextafter(fr, INFINITY);
   float fin = (float)(std::max(0.0, std::fabs((double)sp.radius) * (1.0 - 1e-6) - cerr) * (1.0 - 1e-6));
+  // "Surely hit" also means that the reference's test of the object's STORED box passes first (path_tracer.cu:84), and the C ABI
+  // takes that box as given: the inner ball must lie inside it.  No inner ball for a radius that is not positive (the reference's
+  // own box of a negative radius has min > max: the object is never hit) or a box that is empty on an axis; otherwise no larger
+  // than the distance from the centre to the nearest face (a caller's clipped box).  Before this bound a ray through such an
+  // object was a "sure hit" that capped the list, and a sphere behind it, later in the list, was never tested.
+  double face = (double)INFINITY;
+  const double centre[3] = {cx, cy, cz};
+  for (int ax = 0; ax < 3; ++ax)
+    face = std::min(face, std::min(centre[ax] - (double)o.aabb_min[ax], (double)o.aabb_max[ax] - centre[ax]));
+  if (!(sp.radius > 0.0f) || !(face > 0.0)) fin = 0.0f;  // (a NaN bound: none)
+  else fin = std::min(fin, (float)std::max(0.0, face * (1.0 - 1e-6) - cerr));
   fin = fin > 0.0f ? std::nextafter(fin, 0.0f) : 0.0f;
   float inv_sigma = (float)((1.0 / sigma) * (1.0 - 1e-6));
   inv_sigma = std::nextafter(inv_sigma, 0.0f);

@@ -69,17 +69,6 @@ size_t launch_run(const ptc_ctx* ctx, size_t k)
   return run;
 }
 
-// may the sphere run [begin, end) take the per-lane path (sphere_run_lanes)?
-uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
-{
-  if (!ctx->sphere_lanes || end <= begin || end - begin > 8u || end > ctx->sphere_class.size()) return 0u;
-  const uint32_t k = ctx->sphere_class[begin];
-  if (k == 0u) return 0u;
-  for (uint32_t i = begin; i < end; ++i)
-    if (ctx->sphere_class[i] != k) return 0u;
-  return 1u;
-}
-
 // "roulette" (DESIGN section 5h): does bounce `bounce` of a frame play Russian roulette?  From bounce `roulette` on, never the last
 // bounce (capped paths deposit raw throughput as ever); 0 is off.  The kernels that end such a bounce are the roulette instances,
 // every other bounce launches what it launched before the parameter existed.
@@ -446,6 +435,17 @@ uint32_t fold_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
   if (!ctx->sphere_fold || end <= begin || end > ctx->sphere_class.size()) return 0u;
   for (uint32_t i = begin; i < end; ++i)
     if (ctx->sphere_class[i] == 0u) return 0u;
+  return 1u;
+}
+
+// may the sphere run [begin, end) take the per-lane path (sphere_run_lanes)?
+uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
+{
+  if (!ctx->sphere_lanes || end <= begin || end - begin > 8u || end > ctx->sphere_class.size()) return 0u;
+  const uint32_t k = ctx->sphere_class[begin];
+  if (k == 0u) return 0u;
+  for (uint32_t i = begin; i < end; ++i)
+    if (ctx->sphere_class[i] != k) return 0u;
   return 1u;
 }
 

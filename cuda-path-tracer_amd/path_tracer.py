@@ -392,6 +392,21 @@ class PathTracer:
             self._ctx, rays.ctypes.data_as(C.POINTER(C.c_float)), n, occluded.ctypes.data_as(C.POINTER(C.c_uint8))))
         return occluded
 
+    def debug_sphere_lanes(self, rays, slots, want_candidates=False):
+        """The per-lane form of the trailing sphere run on the device (ptc_debug_sphere_lanes; test hook).  rays as for
+        intersect_rays with t_min 1e-4 or 1e-5 and t_max >= 0; slots: 1 or the fused kernel's rays per lane.  Returns t, normal,
+        material, side, and with want_candidates the candidate mask uint8[n] (bit k: object k of the run)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(rays)
+        t = np.empty(n, dtype=np.float32)
+        nrm = np.empty((n, 3), dtype=np.float32)
+        mat = np.empty(n, dtype=np.uint32)
+        side = np.empty(n, dtype=np.uint8)
+        cand = np.zeros(n, dtype=np.uint8) if want_candidates else None
+        self._check(self._lib.ptc_debug_sphere_lanes(self._ctx, rays.ctypes.data, n, int(slots), t.ctypes.data, nrm.ctypes.data,
+                                                     mat.ctypes.data, side.ctypes.data, cand.ctypes.data if want_candidates else None))
+        return (t, nrm, mat, side, cand) if want_candidates else (t, nrm, mat, side)
+
     def occlusion_stats(self):
         """Counters of occluded_rays since reset_profile / creation."""
         s = _capi.ptc_occlusion_stats()

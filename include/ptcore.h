@@ -603,6 +603,17 @@ int ptc_check_beam(const float* positions, uint32_t vertex_count, const uint32_t
                    const ptc_camera* camera, uint32_t width, uint32_t height, uint32_t stride, uint64_t* stats5, float* entries_out);
 /* Test hook: the same entries as k_beam computes them on the GPU for the uploaded scene's first traversal launch. */
 int ptc_debug_beam_entries(ptc_ctx* ctx, const ptc_camera* camera, float* entries_out, uint64_t capacity_floats);
+/* Test hook: the per-lane form of a sphere run (csrc/pt_kernels_common.inc: sphere_run_lanes, what the kernels that end a bounce
+ * run for a trailing run of up to eight translated spheres) on the uploaded scene's trailing sphere run, for the caller's rays.
+ * rays, n and the four outputs as for ptc_intersect_rays, except that origins and directions must be finite, every t_min 1e-4 or
+ * 1e-5 and every t_max >= 0 (the closest hit carried in; 3e38 and more: none).  slots: 1 (every bound of the run held against the smallest cap) or the number of rays a lane of the
+ * fused shade kernel holds (2; an object is held against the caps of the objects before it) -- consecutive rays are laid into a
+ * lane's slots as that kernel lays a tile's: ray g * 256 * slots + j * 256 + t is slot j of thread t of workgroup g.  candidates
+ * (may be NULL): one byte per ray, bit k set when object k of the run is a candidate of that ray (sphere_candidates).
+ * PTC_ERR_INVALID when the scene's trailing run does not take the per-lane form (none, more than eight objects, two classes of
+ * matrices, a member that is no translated sphere, "sphere_lanes" 0), for another slots and for a ray outside that domain. */
+int ptc_debug_sphere_lanes(ptc_ctx* ctx, const float* rays, uint32_t n, int slots, float* hit_t, float* hit_normal, uint32_t* hit_material,
+                           uint8_t* hit_side, uint8_t* candidates);
 /* TEST / diagnostic: the state block (DPersist, pt_device.hpp) of slot `slot`'s persistent launch ("persist"), copied after a
  * device synchronisation; its per-phase counters are filled in by -DPT_PERSIST_DEBUG builds only (tools/debug/persist_diff.py).
  * No reference equivalent. */

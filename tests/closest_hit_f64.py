@@ -4,7 +4,8 @@ Test infrastructure only.
 It reads the same float32 scene arrays (ptc_scene_desc as scene_description.FlatScene holds them) and rays (8 floats:
 origin, t_min, direction, t_max) as the library and the oracle, widens them to float64 and then follows the reference's
 geometry (intersections.cuh, path_tracer.cu:36-128): an object's triangles are moved to world space by its matrix and
-met by Moeller-Trumbore there (|det| < 1e-7 is parallel, t in [t_min, t_max]); a sphere is met in object space along the
+met by Moeller-Trumbore there (|det| < 1e-7 is parallel, t in [t_min, t_max]); a sphere object is met only by a ray whose line
+meets the object's stored world box (which need not contain it), then in object space along the
 re-normalised direction (t_min / t_max in those units, the near root unless it is out of range), its t is the world
 distance and its normal transpose(inverse) * n, not re-normalised; a triangle's normal is the unit geometric normal.
 Both face the ray.  Nothing here shares the BVH, the split rules or the binary32 arithmetic with the library or the
@@ -42,7 +43,9 @@ def _mat(o, key):
 def closest_hits(flat, rays, chunk=256):
     """-> dict of arrays over the rays: hit (bool), t, normal [n,3], obj (object index, -1 on a miss), edge (edge or
     silhouette margin of the winner), gap (relative gap to the next hit of another primitive, inf if none), near_limit
-    (some candidate lies at t_min or at the parallel cutoff), robust (bool)"""
+    (some candidate lies at t_min or at the parallel cutoff; for a sphere object also: at t_max or at the closest hit so far, within
+    MARGIN of its silhouette from outside, or on a line whose slab gap at the stored box is within MARGIN of the two extremes),
+    robust (bool)"""
     rays = np.asarray(rays, dtype=np.float32).reshape(-1, 8).astype(np.float64)
     n = len(rays)
     o, tmin, d, tmax = rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7]
@@ -58,11 +61,12 @@ def closest_hits(flat, rays, chunk=256):
     meshes = _mesh_slices(flat)
     spheres = np.asarray(flat.spheres, dtype=np.float32).reshape(-1, 4).astype(np.float64)
 
-    def offer(sel, t, nrm, margin, k, cond=0.0, ncond=0.0):
-        """candidate hits t[sel] (nan = none) of object k; keeps the nearest and the second nearest"""
+    def offer(sel, t, nrm, margin, k, cond=0.0, ncond=0.0, take=None):
+        """candidate hits t[sel] (nan = none) of object k; keeps the nearest and the second nearest.  take (a sphere object):
+        the candidates that replace the record -- the nearest otherwise"""
         t = np.where(np.isnan(t), np.inf, t)
         cond = np.broadcast_to(cond, t.shape)
-        first = t < best_t[sel]
+        first = t < best_t[sel] if take is None else take
         # (a hit at exactly the same t as the best one of another primitive is a gap of 0: not robust)
         runner = np.where(first, best_t[sel], np.minimum(second_t[sel], t))
         second_cond[sel] = np.where(first, t_cond[sel], np.where(t < second_t[sel], cond, second_cond[sel]))
@@ -142,12 +146,45 @@ def closest_hits(flat, rays, chunk=256):
             disc = b * b - cc
             sq = np.sqrt(np.maximum(disc, 0.0))
             t1, t2 = -b - sq, -b + sq
-            in1 = (t1 >= tmin) & (t1 <= tmax)
-            in2 = (t2 >= tmin) & (t2 <= tmax)
-            ts = np.where(in1, t1, np.where(in2, t2, np.nan))
-            ts = np.where(disc >= 0.0, ts, np.nan)
-            near_limit |= (disc >= 0.0) & ((np.abs(t1 - tmin) <= MARGIN * np.maximum(1.0, np.abs(t1))) |
-                                           (np.abs(t2 - tmin) <= MARGIN * np.maximum(1.0, np.abs(t2))))
+            # The reference walks the objects in order and hands the closest hit so far -- a WORLD distance -- to the object-space
+            # test as t_max, unscaled (transform.hpp:51-58); an accepted hit replaces the record whatever its own world distance.
+            # Under a translation or a rotation that is "the nearest wins"; under a scale it is not: `take` says which rays the
+            # walk accepts here, the candidate by the ray's own t_max stays in the books as a runner-up.
+            tcur = np.minimum(tmax, best_t)
+
+            def root_in(limit):
+                r1, r2 = (t1 >= tmin) & (t1 <= limit), (t2 >= tmin) & (t2 <= limit)
+                return np.where(disc >= 0.0, np.where(r1, t1, np.where(r2, t2, np.nan)), np.nan)
+
+            ts, ts_walk = root_in(tmax), root_in(tcur)
+            # the object's stored world box comes first (path_tracer.cu:84; ray_aabb_intersection_test, intersections.cuh:87-103:
+            # the LINE against the slabs, min(far) >= max(near), an empty box misses).  The reference's box of a sphere object
+            # takes the stretch of the x axis alone (scene_description.cpp:29-36), so it cuts an ellipsoid and a caller may
+            # store any box: the gate decides hits, it is not a bound
+            bmin = np.asarray(ob["aabb_min"], dtype=np.float32).astype(np.float64)
+            bmax = np.asarray(ob["aabb_max"], dtype=np.float32).astype(np.float64)
+            if np.any(bmin > bmax):
+                continue
+            with np.errstate(divide="ignore", invalid="ignore"):
+                s0, s1 = (bmin - o) / d, (bmax - o) / d
+                minmax, maxmin = np.maximum(s0, s1).min(axis=1), np.minimum(s0, s1).max(axis=1)   # (a nan, 0 / 0, stays one)
+                slab_gap = minmax - maxmin
+                box_close = ~(np.abs(slab_gap) > MARGIN * (np.abs(minmax) + np.abs(maxmin)))   # (nan, inf - inf: close)
+            near_limit |= box_close & ~np.isnan(ts)
+            ts = np.where(slab_gap >= 0.0, ts, np.nan)
+            take = ~np.isnan(ts) & (ts_walk == ts)
+            size = np.einsum("rk,rk->r", oc, oc) + r * r + b * b
+            u = 2.0 ** -24
+            in_box = slab_gap >= 0.0
+            with np.errstate(invalid="ignore"):
+                for root in (t1, t2):    # a root at t_min, at the ray's t_max or at the closest hit so far
+                    for limit in (tmin, tmax, tcur):
+                        near_limit |= in_box & (disc >= 0.0) & (np.abs(root - limit) <= MARGIN * np.maximum(1.0, np.abs(root)))
+                # a line that passes the sphere by less than the silhouette margin of a hit (below)
+                near_limit |= in_box & (disc < 0.0) & (-b + np.sqrt(np.maximum(-disc, 0.0)) >= tmin) & \
+                    (np.sqrt(np.maximum(-disc, 0.0)) <= MARGIN * abs(r) + np.sqrt(16 * u * size))
+            if r == 0.0:
+                continue     # (a point: met by no line that the float grid holds; what is near it is flagged above)
             p_obj = oo + ts[:, None] * dn
             out = (p_obj - c) / r
             side = np.einsum("rk,rk->r", dn, out) < 0.0
@@ -158,12 +195,21 @@ def closest_hits(flat, rays, chunk=256):
             # The quadratic's terms are large next to its roots for a big sphere seen from near its surface (a room's
             # wall): binary32 rounding of |oc|^2 - r^2 moves the root by about u * (|oc|^2 + r^2 + b^2) / sqrt(disc)
             # (u = 2^-24), and decides hit or miss only where disc exceeds that size.  The silhouette margin counts from
-            # there; the root's own uncertainty widens the t tolerance.
-            size = np.einsum("rk,rk->r", oc, oc) + r * r + b * b
-            u = 2.0 ** -24
+            # there; the root's own uncertainty widens the t tolerance -- and so do, as for a triangle, the roundings of the
+            # coordinates: of the origin on its way into object space (8 u of the terms of M^-1 o + t), of the hit point on its
+            # way back and of the world coordinates the recorded distance is taken between.
             sil = (np.sqrt(np.maximum(disc, 0.0)) - np.sqrt(16 * u * size)) / abs(r)
-            cond = 8 * u * size / np.maximum(sq, 1e-300) * (t_world / np.maximum(np.abs(ts), 1e-300))
-            offer(slice(None), np.where(np.isnan(ts), np.nan, t_world), n_world, sil, k, np.nan_to_num(cond, nan=0.0, posinf=0.0))
+            coord_obj = 8 * u * (np.abs(o) @ np.abs(inv[:3, :3]).T + np.abs(inv[:3, 3])).max(axis=1) + 8 * u * np.abs(c).max()
+            stretch = np.linalg.norm(m[:3, :3], 2)
+            with np.errstate(invalid="ignore", over="ignore"):
+                root_err = 8 * u * size / np.maximum(sq, 1e-300) + coord_obj * np.sqrt(size) / np.maximum(sq, 1e-300)
+                coord_world = 8 * u * (np.linalg.norm(o, axis=1) + np.linalg.norm(np.nan_to_num(p_world), axis=1))
+                cond = root_err * (t_world / np.maximum(np.abs(ts), 1e-300)) + coord_world + coord_obj * stretch
+                # the normal moves with the hit point in object space, by its error over the radius; transpose(inverse) can
+                # stretch that by the matrix' condition
+                ncond = (root_err + coord_obj) / abs(r) * stretch * np.linalg.norm(inv[:3, :3], 2)
+            offer(slice(None), np.where(np.isnan(ts), np.nan, t_world), n_world, sil, k, np.nan_to_num(cond, nan=0.0, posinf=0.0),
+                  np.nan_to_num(ncond, nan=0.0, posinf=0.0), take=take)
     hit = np.isfinite(best_t)
     with np.errstate(invalid="ignore", divide="ignore"):
         gap = np.where(hit, (second_t - best_t) / best_t, np.inf)
