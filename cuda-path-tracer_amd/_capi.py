@@ -151,6 +151,9 @@ SIGNATURES = {
     "ptc_set_max_bounces": (C.c_int, [_P, C.c_int]),
     "ptc_set_trace_variant": (C.c_int, [_P, C.c_int]),
     "ptc_set_param": (C.c_int, [_P, C.c_char_p, C.c_int]),
+    "ptc_set_lens": (C.c_int, [_P, C.c_float, C.c_float]),
+    "ptc_get_lens": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ptc_generate_rays": (C.c_int, [_P, C.POINTER(ptc_camera), C.c_uint32, C.c_void_p, C.c_uint64]),
     "ptc_set_denoiser_params": (C.c_int, [_P, C.POINTER(ptc_denoiser_params)]),
     "ptc_trace": (C.c_int, [_P, C.POINTER(ptc_camera)]),
     "ptc_trace_begin": (C.c_int, [_P, C.POINTER(ptc_camera)]),

@@ -202,6 +202,13 @@ struct DCamera {
   uint32_t width, height;
 };
 
+// The thin lens (ptc_set_lens): aperture radius and focus distance in world units, context-wide.  radius 0 is the
+// pinhole: the host launches the pinhole instances and nothing reads this.  Not part of DCamera: DCameras is kMaxBatch cameras by
+// value and the kernel-argument block has no room for 32 copies of a frame-wide constant.
+struct DLens {
+  float radius, focus;
+};
+
 // Live-path state, 40 B/path in three arrays (round 5; 48 until then: a float4 of its own for the throughput, two words unused --
 // the kernels that end a bounce are HBM-bound and read and write every word of it):
 //   o4 = origin.xyz, bits(pixel | tmin_flag<<31)   tmin_flag: t_min is 1e-5 (after a dielectric) instead of 1e-4
@@ -361,7 +368,7 @@ void launch_raygen(hipStream_t s, const DCameras& cams, const DBatchInfo& bi, DB
                    DPaths paths, DeviceCounters* counters, const DObject* objects = nullptr, uint32_t filt_begin = 0u,
                    uint32_t filt_end = 0u, uint32_t* worklist = nullptr, DHits hits = DHits{nullptr, nullptr},
                    unsigned long long* tile_desc = nullptr, uint32_t tile_stride = 0u, uint32_t epoch = 0u,
-                   bool finish_misses = false, DFrame fb = DFrame{nullptr, nullptr}, bool staged = false);
+                   bool finish_misses = false, DFrame fb = DFrame{nullptr, nullptr}, bool staged = false, DLens lens = DLens{0.0f, 0.0f});
 // variant 0: reference-order traversal (k_trace); 1: culled near-first traversal over the wide layout (k_trace_wide)
 void launch_trace(hipStream_t s, const DScene& scene, DPaths paths, DHits hits, uint32_t max_paths, int bounce,
                   DeviceCounters* counters, bool count_tests, int variant);
@@ -420,7 +427,10 @@ void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, 
 // "prefold" at bounce 0: ray generation that also walks the sphere run in front of bounce 0's first mesh launch (next.hits: the
 // CURRENT bounce's records here) and leaves the bytes for launch_list_flags
 void launch_raygen_next(hipStream_t s, const DScene& scene, const DCameras& cams, const DBatchInfo& bi, DBand band, uint32_t pix_count, DPaths paths,
-                        DeviceCounters* counters, const DNextRun& next);
+                        DeviceCounters* counters, const DNextRun& next, DLens lens = DLens{0.0f, 0.0f});
+// the primary rays of one iteration for every slot of the band, 8 floats per slot (origin, t_min, direction, t_max): primary_ray and
+// nothing else (ptc_generate_rays; k_generate_rays, pt_shade.hip)
+void launch_generate_rays(hipStream_t s, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count, DLens lens, float4* rays);
 // "prefold": the work list of a bounce whose leading sphere run the previous bounce's shade kernel has already walked, from the
 // bytes it left (k_list_flags; tile_desc / epoch as for launch_spheres)
 void launch_list_flags(hipStream_t s, const uint8_t* flags, uint32_t max_paths, int bounce, DeviceCounters* counters, const DBatchInfo& bi,
@@ -437,6 +447,10 @@ void launch_megakernel(hipStream_t s, const DScene& scene, const DCamera& cam, u
 // ... for a frame with a bounce that plays Russian roulette (1 <= roulette < max_bounces - 1, the caller's check)
 void launch_megakernel_roulette(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
                                 int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette);
+// ... for a frame under a thin lens (lens.radius > 0, the caller's check): the plain loop or, when some bounce
+// plays (roulette: the context's parameter; 1 <= roulette < max_bounces - 1 is decided here), the roulette one, with primary_ray<true>
+void launch_megakernel_lens(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
+                            int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette, DLens lens);
 void launch_preview(hipStream_t s, const float4* buf, uint32_t pix_count, int mode, uint32_t* rgba);
 void launch_pack(hipStream_t s, const float4* buf, uint32_t pix_count, int which, float* dst);
 // the bands of one multi-GPU gather launch (k_gather_bands): up to kGatherBands sources per launch
@@ -478,6 +492,8 @@ struct DLights {
 constexpr uint32_t kLightSeedXor = 0x4c495445u;  // xor-ed into path_seed(point, sample_index): no render path xors its seed
 // Russian roulette (ptc_set_param "roulette"): xor-ed into path_seed(slot or pixel, iteration); discard(bounce), one draw
 constexpr uint32_t kRouletteSeedXor = 0x52524c54u;
+// the thin lens (ptc_set_lens): xor-ed into path_seed(pixel, iteration); two draws, the point on the lens disk
+constexpr uint32_t kLensSeedXor = 0x4c454e53u;
 constexpr uint32_t kLightStatLines = 64u;        // the resolve kernel's two counters, spread over this many 128-byte lines
 //   launch_light_sample   one thread per point: the shadow ray in the path-state layout occlude_on_device takes (o4 = p, tmin_word;
 //                         d4 = w, t_max) and contrib = {unshadowed contribution rgb, 1 if sampled else 0}; a culled sample: t_max 0
@@ -496,7 +512,7 @@ void launch_light_resolve(hipStream_t s, const float4* o4, const float4* d4, con
 constexpr uint32_t kLoopStatWords = 16u;
 void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
                               uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats,
-                              int roulette = 0);
+                              int roulette = 0, DLens lens = DLens{0.0f, 0.0f});
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,
                      float* out_sin, float* out_cos);
 void launch_selftest_rng(hipStream_t s, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);

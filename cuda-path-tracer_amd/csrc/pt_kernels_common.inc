@@ -790,13 +790,41 @@ __device__ __forceinline__ void generate_ray(const DCamera& cam, float fx, float
 // The primary sample of a pixel (raygen_kernel, ray_gen.cu:11-32; path_tracing_mega_kernel, path_tracer.cu:233-240): the path's
 // stream seeded, its first two draws jitter the pixel, the ray through that point with a primary ray's range.  rng is left behind
 // the two draws (the megakernel goes on drawing from it).
-__device__ __forceinline__ void primary_ray(const DCamera& cam, const uint32_t pixel, const uint32_t iteration, Minstd& rng, Ray& ray)
+// kLens (ptc_set_lens with a radius > 0, an extension: the reference's camera is a pinhole; DESIGN section 5i): the thin lens.  The
+// path stream and the jitter are the pinhole's; a point on the lens disk comes from a stream of its own, seed(path_seed(pixel,
+// iteration) ^ kLensSeedXor), two draws; the ray leaves that point towards the point the pinhole ray has at camera-space depth
+// `focus`.  One binary32 operation per line item, in section 5i's order.  Without kLens nothing of it is compiled and `lens` is
+// not read: the pinhole instances are what they were.
+template <bool kLens = false>
+__device__ __forceinline__ void primary_ray(const DCamera& cam, const uint32_t pixel, const uint32_t iteration, Minstd& rng, Ray& ray,
+                                            const DLens lens = DLens{0.0f, 0.0f})
 {
   const uint32_t x = pixel % cam.width, y = pixel / cam.width;
   rng.seed(path_seed(pixel, iteration));
   const float fx = (float)x + rng.uniform();
   const float fy = (float)y + rng.uniform();
-  generate_ray(cam, fx, fy, ray.o, ray.d);
+  if constexpr (kLens) {
+    const float u = fx / (float)(cam.width - 1u);  // generate_ray's dx, dy
+    const float v = ((float)cam.height - fy) / (float)(cam.height - 1u);
+    const float dx = cam.llx + cam.vw * u;
+    const float dy = cam.lly + cam.vh * v;
+    Minstd lens_rng;
+    lens_rng.seed(path_seed(pixel, iteration) ^ kLensSeedXor);
+    const float u1 = lens_rng.uniform();
+    const float u2 = lens_rng.uniform();
+    const float rho = lens.radius * ieee_sqrt(u1);
+    const float phi = 2.f * 3.14159265358979323846264338327950288f * u2;
+    float sn, cs;
+    det_sincos(phi, sn, cs);
+    const float lx = rho * cs;
+    const float ly = rho * sn;
+    const float px = dx * lens.focus;  // the point in focus: (px, py, -focus)
+    const float py = dy * lens.focus;
+    ray.o = xform_point(cam.cam, mk3(lx, ly, 0.0f));
+    ray.d = normalize(xform_vector(cam.cam, mk3(px - lx, py - ly, -lens.focus)));
+  } else {
+    generate_ray(cam, fx, fy, ray.o, ray.d);
+  }
   ray.tmin = 1e-4f;
   ray.tmax = FLT_MAX;
 }

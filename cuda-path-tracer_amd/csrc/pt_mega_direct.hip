@@ -1,5 +1,6 @@
-// pt_mega_direct.hip -- the megakernel's instances off the plain path: k_megakernel_direct (direct lighting) and
-// k_megakernel<.., true> (Russian roulette, section 5h), with their launchers.  The loop itself, with what kDirect and kRoulette add
+// pt_mega_direct.hip -- the megakernel's instances off the plain path: k_megakernel_direct (direct lighting),
+// k_megakernel<.., true> (Russian roulette, section 5h) and the thin lens's k_megakernel_lens / k_megakernel_direct_lens (section 5i),
+// with their launchers.  The loop itself, with what kDirect and kRoulette add
 // to it, is mega_path (pt_megakernel.inc); the shadow ray's any-hit walk is scene_occluded (pt_kernels_common.inc).  Part of
 // libptcore.so.
 #include "pt_device.hpp"
@@ -27,6 +28,17 @@ __global__ __launch_bounds__(kWave) void k_megakernel_direct(DScene sc, DLights 
                                    s_stack + threadIdx.x);
 }
 
+// ... under a thin lens
+template <bool kRoulette>
+__global__ __launch_bounds__(kWave) void k_megakernel_direct_lens(DScene sc, DLights lt, DCamera cam, uint32_t iteration, DBand band,
+                                                                  uint32_t pix_count, int max_bounces, DFrame fb,
+                                                                  DeviceCounters* counters, unsigned long long* stats, int roulette, DLens lens)
+{
+  __shared__ uint32_t s_stack[kStackDepth * kWave];
+  mega_path<true, kRoulette, true, true>(sc, lt, cam, iteration, band, pix_count, max_bounces, fb, counters, stats, roulette,
+                                         s_stack + threadIdx.x, lens);
+}
+
 // the plain megakernel's instances that play roulette (the plain ones: pt_kernels.hip)
 void launch_megakernel_roulette(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
                                 int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette)
@@ -38,11 +50,36 @@ void launch_megakernel_roulette(hipStream_t s, const DScene& scene, const DCamer
     hipLaunchKernelGGL((k_megakernel<false, true>), grid, block, 0, s, scene, cam, iteration, band, pix_count, max_bounces, fb, counters, roulette);
 }
 
-void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats,
-                              int roulette)
+// the plain loop under a thin lens: all four instances, the plain ones too -- pt_kernels.hip stays the code object it was
+void launch_megakernel_lens(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
+                            int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette, DLens lens)
 {
   const dim3 grid((pix_count + kWave - 1u) / kWave), block(kWave);
+  const bool plays = roulette >= 1 && roulette < max_bounces - 1;  // some bounce plays roulette
+  if (emitters && plays)
+    hipLaunchKernelGGL((k_megakernel_lens<true, true>), grid, block, 0, s, scene, cam, iteration, band, pix_count, max_bounces, fb, counters, roulette, lens);
+  else if (emitters)
+    hipLaunchKernelGGL((k_megakernel_lens<true, false>), grid, block, 0, s, scene, cam, iteration, band, pix_count, max_bounces, fb, counters, 0, lens);
+  else if (plays)
+    hipLaunchKernelGGL((k_megakernel_lens<false, true>), grid, block, 0, s, scene, cam, iteration, band, pix_count, max_bounces, fb, counters, roulette, lens);
+  else
+    hipLaunchKernelGGL((k_megakernel_lens<false, false>), grid, block, 0, s, scene, cam, iteration, band, pix_count, max_bounces, fb, counters, 0, lens);
+}
+
+void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
+                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats,
+                              int roulette, DLens lens)
+{
+  const dim3 grid((pix_count + kWave - 1u) / kWave), block(kWave);
+  if (lens.radius > 0.0f) {  // the thin lens: the same choice, the lens instances
+    if (roulette >= 1 && roulette < max_bounces - 1)
+      hipLaunchKernelGGL(k_megakernel_direct_lens<true>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters,
+                         stats, roulette, lens);
+    else
+      hipLaunchKernelGGL(k_megakernel_direct_lens<false>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters,
+                         stats, roulette, lens);
+    return;
+  }
   if (roulette >= 1 && roulette < max_bounces - 1)  // some bounce plays roulette
     hipLaunchKernelGGL(k_megakernel_direct<true>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters,
                        stats, roulette);

@@ -17,10 +17,14 @@
 // survivor's light sample is weighted with the divided colour.  tests/direct_loop_ref.py restates the loop in numpy.
 // stats (kDirect): kLightStatLines lines of kLoopStatWords 64-bit words; word 0 += diffuse hits, word 1 += shadow rays traced,
 // word 2 += unoccluded ones.  stack: the calling thread's column of the workgroup's LDS stack.
-template <bool kEmit, bool kRoulette, bool kDirect>
+// kLens (DESIGN section 5i): the primary ray is the thin lens's, primary_ray<true> with `lens`; rng is left where the pinhole leaves it,
+// so every material draw is the pinhole render's.  The lens instances (k_megakernel_lens, k_megakernel_direct_lens) live in
+// pt_mega_direct.hip.
+template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false>
 __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, const DCamera& cam, const uint32_t iteration, const DBand band,
                                           const uint32_t pix_count, const int max_bounces, const DFrame fb, DeviceCounters* counters,
-                                          unsigned long long* stats, const int roulette, uint32_t* stack)
+                                          unsigned long long* stats, const int roulette, uint32_t* stack,
+                                          const DLens lens = DLens{0.0f, 0.0f})
 {
   static_assert(kEmit || !kDirect, "direct lighting: launched only for a scene with a lamp table, so with an emissive material");
   const uint32_t s = blockIdx.x * kWave + threadIdx.x;
@@ -30,7 +34,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
     const uint32_t pixel = band_pixel(band, s);
     Minstd rng;
     Ray ray;
-    primary_ray(cam, pixel, iteration, rng, ray);
+    primary_ray<kLens>(cam, pixel, iteration, rng, ray, lens);
     f3 color = mk3(1.0f, 1.0f, 1.0f);
     f3 radiance = mk3(0.0f, 0.0f, 0.0f);
     bool count_emission = true;  // the last vertex drew no light sample (the camera, metal, glass): a lamp hit from it counts
@@ -119,4 +123,15 @@ __global__ __launch_bounds__(kWave) void k_megakernel(DScene sc, DCamera cam, ui
   __shared__ uint32_t s_stack[kStackDepth * kWave];
   mega_path<kEmit, kRoulette, false>(sc, DLights{}, cam, iteration, band, pix_count, max_bounces, fb, counters, nullptr, roulette,
                                      s_stack + threadIdx.x);
+}
+
+// ... under a thin lens (DESIGN section 5i; instances: pt_mega_direct.hip)
+template <bool kEmit, bool kRoulette>
+__global__ __launch_bounds__(kWave) void k_megakernel_lens(DScene sc, DCamera cam, uint32_t iteration, DBand band,
+                                                           uint32_t pix_count, int max_bounces, DFrame fb,
+                                                           DeviceCounters* counters, int roulette, DLens lens)
+{
+  __shared__ uint32_t s_stack[kStackDepth * kWave];
+  mega_path<kEmit, kRoulette, false, true>(sc, DLights{}, cam, iteration, band, pix_count, max_bounces, fb, counters, nullptr, roulette,
+                                           s_stack + threadIdx.x, lens);
 }

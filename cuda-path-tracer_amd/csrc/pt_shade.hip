@@ -16,112 +16,27 @@ namespace pt {
 #include "pt_kernels_common.inc"
 #include "pt_shade_tile.inc"  // the end of a bounce per path (goes_on, bounce_outcome, pack_survivor) and per tile (shade_tile)
 
-// raygen_kernel, ray_gen.cu:11-32.  Slot s of this context holds pixel band_pixel(band, s).
-// kFilter ("filter_rays"): the bounce's first launch is a traversal launch over the mesh objects [filt_begin, filt_end)
-// (no sphere run in front of it): the rays that may hit one of their world boxes go on its work list, the others get
-// their miss record here (what that launch would have written for them) -- the sky pixels of an outdoor scene never
-// reach the traversal kernel.
-// kFinish (with kFilter, when that launch walks the scene's WHOLE object list): a ray that is not listed hits nothing at
-// all, so its path ends here -- throughput (1, 1, 1) times the sky into the frame, exactly what the shade kernel does
-// for a miss at bounce 0 (path_tracer.cu:304-307, ray_gen.cu:26-28) -- and neither its ray nor a miss record is written;
-// bounce 0's k_shade_fused then walks the work list instead of all slots.  Per sky pixel and frame: 32 bytes written
-// here instead of 48, and 48 bytes the shade kernel no longer reads.
-template <bool kFilter, bool kFinish>
-__global__ __launch_bounds__(256) void k_raygen(DCameras cams, DBatchInfo bi, DBand band, uint32_t pix_count,
-                                                DPaths paths, DeviceCounters* counters, const DObject* objects, uint32_t filt_begin,
-                                                uint32_t filt_end, uint32_t* worklist, DHits hits, DTileScan scan, uint32_t tile_stride,
-                                                DFrame fb, int staged)
-{
-  const uint32_t frame = blockIdx.x % bi.count;  // see DBatchInfo; frame-fastest: neighbouring workgroups take their tickets on different lines
-  const DCamera& cam = cams.c[frame];
-  const uint32_t iteration = bi.iteration[frame];
-  paths.o4 += (size_t)frame * bi.stride;  // (written out, not offset_frame: with it k_raygen<true, true> orders its scalar adds differently)
-  paths.d4 += (size_t)frame * bi.stride;
-  counters += frame;
-  scan.desc += (size_t)frame * tile_stride;
-  if (kFinish && staged) {
-    fb.color4 += (size_t)frame * bi.stride;
-    fb.nd4 += (size_t)frame * bi.stride;
-  }
-  const uint32_t acc_iteration = staged ? 0u : iteration;
-  const uint32_t tiles = gridDim.x / bi.count;
-  const uint32_t tile = kFilter ? list_tile(counters, tiles) : blockIdx.x / bi.count;
-  const uint32_t block_first = tile * (256u * kListPer);  // a workgroup generates kListPer x 256 consecutive slots
-  if (tile == 0u) {
-    if (threadIdx.x == 0u) counters->live[0] = pix_count;
-    // fetch cursors of this frame's persistent traversal launches
-    for (uint32_t i = threadIdx.x; i < (uint32_t)kWorkSlots * 8u; i += 256u) (&counters->work[0][0][0])[i * 32u] = 0u;
-  }
-  uint32_t may_mask = 0u;
-#pragma unroll
-  for (int j = 0; j < kListPer; ++j) {
-    const uint32_t s = block_first + (uint32_t)j * 256u + threadIdx.x;
-    if (s >= pix_count) continue;
-    const uint32_t pixel = band_pixel(band, s);
-    Minstd rng;
-    Ray ray;
-    primary_ray(cam, pixel, iteration, rng, ray);
-    const f3 o = ray.o, d = ray.d;
-    bool may_hit = true;
-    if (kFilter) {
-      may_hit = may_hit_boxes(objects, filt_begin, filt_end, o, d, FLT_MAX);
-      may_mask |= may_hit ? 1u << j : 0u;
-    }
-    if (kFinish && !may_hit) {
-      const uint32_t local_pixel = band_local(band, pixel);
-      const f3 color = mk3(1.0f, 1.0f, 1.0f) * background(d);
-      accumulate_nd(fb.nd4, local_pixel, acc_iteration, -d, 1e6f);
-      accumulate_color(fb.color4, local_pixel, acc_iteration, color);
-      continue;
-    }
-    stnt(&paths.o4[s], make_float4(o.x, o.y, o.z, __uint_as_float(pixel)));
-    stnt(&paths.d4[s], make_float4(d.x, d.y, d.z, 0.0f));
-    // (the throughput of a primary ray is (1, 1, 1), ray_gen.cu:25: the shade kernels know that at bounce 0 and neither
-    // is it written here nor read there -- 32 bytes per pixel and frame less)
-    if (kFilter && !may_hit) stnt(&hits.tp[(size_t)frame * bi.stride + s], make_float4(-1.0f, 0.f, 0.f, 0.f));
-  }
-  if (kFilter) list_rays(may_mask, worklist, counters, (size_t)frame * bi.stride, tile, tiles, scan);
-}
+// k_raygen<kFilter, kFinish>, k_raygen_next and their thin-lens forms k_raygen_lens<kFilter, kFinish>, k_raygen_next_lens:
+// pt_raygen.inc, one text for both
+#define PT_RAYGEN_LENS 0
+#include "pt_raygen.inc"
+#undef PT_RAYGEN_LENS
+#define PT_RAYGEN_LENS 1
+#include "pt_raygen.inc"
+#undef PT_RAYGEN_LENS
 
-// "prefold" at bounce 0: ray generation for a scene whose object list opens with a sphere run in front of a mesh (config 2).  The
-// primary ray is in registers: k_spheres<first, filter>'s work for it -- the run, the hit or miss record, the byte that says
-// whether it goes on the mesh launch's work list (shade_tile<.., kNext> does the same for the later bounces) -- is done here, and
-// bounce 0 starts with k_list_flags.
-__global__ __launch_bounds__(256) void k_raygen_next(DScene sc, DCameras cams, DBatchInfo bi, DBand band, uint32_t pix_count, DPaths paths,
-                                                     DeviceCounters* counters, DNextRun next)
+// ptc_generate_rays: the primary ray of every slot of the band at one iteration, as the frame's ray generation builds it (primary_ray
+// and nothing else), 8 floats per slot: origin, t_min, direction, t_max -- the layout ptc_intersect_rays takes.
+template <bool kLens>
+__global__ __launch_bounds__(256) void k_generate_rays(DCamera cam, uint32_t iteration, DBand band, uint32_t pix_count, DLens lens, float4* rays)
 {
-  const uint32_t frame = blockIdx.x % bi.count;
-  const DCamera& cam = cams.c[frame];
-  const uint32_t iteration = bi.iteration[frame];
-  const size_t fo = (size_t)frame * bi.stride;
-  offset_frame(paths, fo);
-  offset_frame(next.hits, fo);
-  next.flags += fo;
-  counters += frame;
-  const uint32_t tile = blockIdx.x / bi.count;
-  const uint32_t block_first = tile * (256u * kListPer);
-  if (tile == 0u) {
-    if (threadIdx.x == 0u) counters->live[0] = pix_count;
-    for (uint32_t i = threadIdx.x; i < (uint32_t)kWorkSlots * 8u; i += 256u) (&counters->work[0][0][0])[i * 32u] = 0u;
-  }
-#pragma unroll 1
-  for (int j = 0; j < kListPer; ++j) {
-    const uint32_t s = block_first + (uint32_t)j * 256u + threadIdx.x;
-    if (s >= pix_count) continue;
-    const uint32_t pixel = band_pixel(band, s);
-    Minstd rng;
-    Ray ray;
-    primary_ray(cam, pixel, iteration, rng, ray);  // (t_min as load_ray reads it: the sign bit of a primary ray's pixel word is clear)
-    stnt(&paths.o4[s], make_float4(ray.o.x, ray.o.y, ray.o.z, __uint_as_float(pixel)));
-    stnt(&paths.d4[s], make_float4(ray.d.x, ray.d.y, ray.d.z, 0.0f));
-    Hit rec;
-    bool changed = false;
-    if (next.fold_run != 0u) sphere_fold(sc, next.begin, next.end, ray, rec, changed);
-    else sphere_segment<true>(sc, next.begin, next.end, ray, rec, changed);
-    if (changed) store_hit(next.hits, s, rec);
-    else stnt(&next.hits.tp[s], make_float4(-1.0f, 0.f, 0.f, 0.f));
-    next.flags[s] = may_hit_boxes(sc.objects, next.filt_begin, next.filt_end, ray.o, ray.d, ray.tmax) ? (uint8_t)1 : (uint8_t)0;
-  }
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= pix_count) return;
+  Minstd rng;
+  Ray ray;
+  primary_ray<kLens>(cam, band_pixel(band, s), iteration, rng, ray, lens);
+  rays[2u * (size_t)s] = make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tmin);
+  rays[2u * (size_t)s + 1u] = make_float4(ray.d.x, ray.d.y, ray.d.z, ray.tmax);
 }
 
 // A run of sphere objects that does not end the object list (the spheres in front of a mesh), continuing from /
@@ -660,10 +575,22 @@ static inline void with_flags(F&& f, bool flag, Rest... rest)
 void launch_raygen(hipStream_t s, const DCameras& cams, const DBatchInfo& bi, DBand band, uint32_t pix_count,
                    DPaths paths, DeviceCounters* counters, const DObject* objects, uint32_t filt_begin, uint32_t filt_end,
                    uint32_t* worklist, DHits hits, unsigned long long* tile_desc, uint32_t tile_stride, uint32_t epoch,
-                   bool finish_misses, DFrame fb, bool staged)
+                   bool finish_misses, DFrame fb, bool staged, DLens lens)
 {
   const dim3 grid(div_up(pix_count, 256u * kListPer) * bi.count), block(256);
   const DTileScan scan{tile_desc, epoch};
+  if (lens.radius > 0.0f) {  // the thin lens: the same three choices, the lens instances
+    const bool filter = worklist && filt_begin < filt_end && tile_desc;
+    with_flags(
+        [&](auto kFilter, auto kFinish) {
+          if constexpr (decltype(kFilter)::value || !decltype(kFinish)::value)
+            hipLaunchKernelGGL((k_raygen_lens<decltype(kFilter)::value, decltype(kFinish)::value>), grid, block, 0, s, cams, bi, band, pix_count, paths,
+                               counters, objects, filter ? filt_begin : 0u, filter ? filt_end : 0u, worklist, hits, scan, tile_stride, fb,
+                               decltype(kFinish)::value && staged ? 1 : 0, lens);
+        },
+        filter, filter && finish_misses);
+    return;
+  }
   if (worklist && filt_begin < filt_end && tile_desc) {
     if (finish_misses)
       hipLaunchKernelGGL((k_raygen<true, true>), grid, block, 0, s, cams, bi, band, pix_count, paths, counters, objects, filt_begin,
@@ -677,10 +604,17 @@ void launch_raygen(hipStream_t s, const DCameras& cams, const DBatchInfo& bi, DB
   }
 }
 void launch_raygen_next(hipStream_t s, const DScene& scene, const DCameras& cams, const DBatchInfo& bi, DBand band, uint32_t pix_count, DPaths paths,
-                        DeviceCounters* counters, const DNextRun& next)
+                        DeviceCounters* counters, const DNextRun& next, DLens lens)
 {
   const dim3 grid(div_up(pix_count, 256u * kListPer) * bi.count), block(256);
-  hipLaunchKernelGGL(k_raygen_next, grid, block, 0, s, scene, cams, bi, band, pix_count, paths, counters, next);
+  if (lens.radius > 0.0f) hipLaunchKernelGGL(k_raygen_next_lens, grid, block, 0, s, scene, cams, bi, band, pix_count, paths, counters, next, lens);
+  else hipLaunchKernelGGL(k_raygen_next, grid, block, 0, s, scene, cams, bi, band, pix_count, paths, counters, next);
+}
+void launch_generate_rays(hipStream_t s, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count, DLens lens, float4* rays)
+{
+  const dim3 grid(div_up(pix_count, 256u)), block(256);
+  if (lens.radius > 0.0f) hipLaunchKernelGGL(k_generate_rays<true>, grid, block, 0, s, cam, iteration, band, pix_count, lens, rays);
+  else hipLaunchKernelGGL(k_generate_rays<false>, grid, block, 0, s, cam, iteration, band, pix_count, lens, rays);
 }
 void launch_spheres(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths paths, DHits hits,
                     uint32_t max_paths, int bounce, DeviceCounters* counters, const DBatchInfo& bi, uint32_t filt_begin,

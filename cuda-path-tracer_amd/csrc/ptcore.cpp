@@ -580,6 +580,28 @@ int ptc_set_param(ptc_ctx* ctx, const char* name, int value)
   return fail(ctx, PTC_ERR_INVALID, std::string("unknown parameter ") + name);
 }
 
+// The thin lens.  Checked values only: a refusal leaves the context's lens as it was.
+int ptc_set_lens(ptc_ctx* ctx, float lens_radius, float focus_distance)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (int rc = flush_pending(ctx)) return rc;  // a batch renders with one lens
+  if (!std::isfinite(lens_radius)) return fail(ctx, PTC_ERR_INVALID, "lens_radius must be finite, got " + std::to_string(lens_radius));
+  if (!std::isfinite(focus_distance)) return fail(ctx, PTC_ERR_INVALID, "focus_distance must be finite, got " + std::to_string(focus_distance));
+  if (lens_radius < 0.0f) return fail(ctx, PTC_ERR_INVALID, "lens_radius must not be negative, got " + std::to_string(lens_radius));
+  if (lens_radius > 0.0f && !(focus_distance > 0.0f))
+    return fail(ctx, PTC_ERR_INVALID, "focus_distance must be positive under a lens_radius > 0, got " + std::to_string(focus_distance));
+  ctx->lens = DLens{lens_radius, focus_distance};
+  return PTC_OK;
+}
+
+int ptc_get_lens(ptc_ctx* ctx, float* lens_radius, float* focus_distance)
+{
+  if (!ctx || !lens_radius || !focus_distance) return PTC_ERR_INVALID;
+  *lens_radius = ctx->lens.radius;
+  *focus_distance = ctx->lens.focus;
+  return PTC_OK;
+}
+
 int ptc_set_denoiser_params(ptc_ctx* ctx, const ptc_denoiser_params* p)
 {
   if (!ctx || !p) return PTC_ERR_INVALID;

@@ -1,5 +1,6 @@
 // ptcore_checks.cpp -- host-side checks of the rules the kernels share with the host (ptc_check_beam, ptc_check_feed,
-// ptc_check_traversal_layout, ptc_check_rng), ptc_debug_beam_entries, ptc_debug_sphere_lanes, ptc_selftest_math, ptc_selftest_rng.  Part of libptcore.so (ptcore_ctx.hpp).
+// ptc_check_traversal_layout, ptc_check_rng), ptc_debug_beam_entries, ptc_debug_sphere_lanes, ptc_selftest_math, ptc_selftest_rng, and
+// ptc_generate_rays (the frame's primary rays as ray generation builds them).  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
 #include "pt_rng.hpp"
 
@@ -514,3 +515,27 @@ int ptc_debug_persist(ptc_ctx* ctx, int slot, void* dst, uint64_t bytes)
 
 }  // extern "C"
 
+
+extern "C" {
+// The primary rays of `iteration` for every slot of the context, in slot order, under the context's lens: the
+// device function the frame's ray generation runs, and nothing else.  Moves neither ptc_stats nor the iteration counter.
+int ptc_generate_rays(ptc_ctx* ctx, const ptc_camera* camera, uint32_t iteration, float* rays_out, uint64_t capacity_floats)
+{
+  if (!ctx || !camera || !rays_out) return PTC_ERR_INVALID;
+  if (!ctx->pix_capacity || !ctx->pix_count) return fail(ctx, PTC_ERR_INVALID, "ptc_resize first");
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;
+  const size_t floats = (size_t)ctx->pix_count * 8u;
+  if (capacity_floats < floats) return fail(ctx, PTC_ERR_INVALID, "rays_out too small: " + std::to_string(floats) + " floats needed");
+  float4* dev = nullptr;
+  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&dev), floats * sizeof(float)));
+  launch_generate_rays(ctx->stream, make_camera(*camera, ctx->width, ctx->height), iteration, ctx->band, ctx->pix_count,
+                       ctx->lens.radius > 0.0f ? ctx->lens : DLens{0.0f, 0.0f}, dev);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(rays_out, dev, floats * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(dev);
+  if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("generate rays: ") + hipGetErrorString(e));
+  return PTC_OK;
+}
+}  // extern "C"

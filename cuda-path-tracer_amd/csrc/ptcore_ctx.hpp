@@ -269,6 +269,8 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   bool direct_light = false;
   // "roulette" (DESIGN section 5h): Russian roulette at every bounce >= this, the last bounce excepted; 0 = off
   int roulette = 0;
+  // the thin lens (ptc_set_lens): radius 0 = the pinhole; every frame of a batch renders with one lens
+  DLens lens{0.0f, 1.0f};
   unsigned long long* loop_stats = nullptr;  // device: kLightStatLines lines of kLoopStatWords words (diffuse hits, shadow rays, unoccluded)
   bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
 };

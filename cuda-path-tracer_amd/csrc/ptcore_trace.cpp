@@ -76,6 +76,14 @@ bool roulette_bounce(const ptc_ctx* ctx, int bounce) { return ctx->roulette >= 1
 // ... does any bounce of a frame?
 bool roulette_frame(const ptc_ctx* ctx) { return ctx->roulette >= 1 && ctx->roulette < ctx->max_bounces - 1; }
 
+// The thin lens (ptc_set_lens): is a frame rendered now a lens frame?  Such a frame launches the lens instances of
+// ray generation (of the megakernel), and gets no entry points ("beam"): k_beam builds a tile's frustum from the pinhole origin, and
+// a lens ray leaves it.  Everything behind the primary ray is per ray and stays as it is.  Radius 0 launches what was launched
+// before the lens existed.
+bool lens_frame(const ptc_ctx* ctx) { return ctx->lens.radius > 0.0f; }
+// ... what the launchers of ray generation get: the context's lens, or the pinhole's "no lens"
+DLens frame_lens(const ptc_ctx* ctx) { return lens_frame(ctx) ? ctx->lens : DLens{0.0f, 0.0f}; }
+
 // ---- the decisions of the launch plan (ptc_ctx::TraceLaunch), each in one place -------------------------------------------
 
 // What opens the object list: a traversal launch with nothing in front of it, a sphere run in front of the first traversal
@@ -200,18 +208,18 @@ int batch_begin(ptc_ctx* ctx, const ptc_ctx::Pending* items, int count)
     // "prefold": ray generation walks the leading sphere run for the primary rays itself, and bounce 0 starts with k_list_flags
     // (batch_bounce) instead of k_spheres
     launch_raygen_next(sl.stream, ctx->scene, cams, sl.bi, ctx->band, ctx->pix_count, sl.paths[0], sl.counters,
-                       next_run(ctx, sl.hits, sl.next_flags));
+                       next_run(ctx, sl.hits, sl.next_flags), frame_lens(ctx));
     sl.prefolded = true;
   } else {
     launch_raygen(sl.stream, cams, sl.bi, ctx->band, ctx->pix_count, sl.paths[0], sl.counters, ctx->scene.objects, first_mesh, filt_end,
                   sl.first_listed ? sl.worklist : nullptr, sl.hits, sl.tile_desc, sl.tile_stride, next_epoch(sl), sl.primary_finished,
-                  sl.stage, ctx->staged);
+                  sl.stage, ctx->staged, frame_lens(ctx));
   }
   if (int rc = check_last(ctx, "raygen")) return rc;
   // "beam": when bounce 0 opens with a launch over ONE mesh object (k_traverse4), its primary rays start at entry points
-  // computed per tile and distinct camera of the batch
+  // computed per tile and distinct camera of the batch (a pinhole batch: lens_frame)
   sl.beam = DBeam{};
-  if (ctx->beam && sl.beam_entries && ctx->trace_variant == 3 && opens == Opens::launch && run0 == 1u && ctx->width >= 2u &&
+  if (ctx->beam && !lens_frame(ctx) && sl.beam_entries && ctx->trace_variant == 3 && opens == Opens::launch && run0 == 1u && ctx->width >= 2u &&
       ctx->height >= 2u) {
     uint8_t cam_of_beam[kMaxBatch];
     uint32_t nbeam = 0;
@@ -634,7 +642,10 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
       const DLights lights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
                            ctx->scene.materials};
       launch_megakernel_direct(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
-                               ctx->max_bounces, ctx->fb, sl.counters, ctx->loop_stats, ctx->roulette);
+                               ctx->max_bounces, ctx->fb, sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx));
+    } else if (lens_frame(ctx)) {  // the thin lens: the lens instance of the plain or the roulette loop
+      launch_megakernel_lens(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces,
+                             ctx->fb, sl.counters, ctx->has_emitters, ctx->roulette, ctx->lens);
     } else if (roulette_frame(ctx)) {  // some bounce plays roulette
       launch_megakernel_roulette(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces,
                                  ctx->fb, sl.counters, ctx->has_emitters, ctx->roulette);

@@ -3,7 +3,7 @@
 // following the call sequence of execute_cli_version (src/cli/cli.cpp:62-116): read scene, create_buffers,
 // max_iterations = spp, spp x path_trace, synchronize, send_to_preview, write PNG, stage timings.
 // Extra flags: --max-bounces N (the reference's cap is a compile-time 50), --denoise, --method, --gpu,
-// --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
+// --lens-radius R / --focus-distance F (the thin lens), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
 // (DisplayBufferType of send_to_preview, path_tracer.cu:487-520: which buffer the PNG shows), --dump-raw FILE (the
 // accumulated float framebuffers as they are: "PTRF", width, height, 7 as uint32, then colour rgb, normal xyz and
 // depth planes as float32).  Without -o the reference opens its GLFW viewer; this build is headless and says so.
@@ -22,6 +22,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <filesystem>
@@ -50,6 +51,7 @@ struct CliConfigurations {  // configurations.hpp:11-15
   bool megakernel = false;
   bool direct_light = false;
   int roulette = 0;
+  std::optional<float> lens_radius, focus_distance;  // the thin lens (override the scene file's camera keys)
   int gpu = 0;
   int gpus = 1;
   std::optional<std::string> dump_scene;
@@ -71,6 +73,8 @@ void usage()
                "      --method M       streaming (default) | megakernel\n"
                "      --direct-light   a light sample with a shadow ray at every diffuse hit (needs --method megakernel)\n"
                "      --roulette K     Russian roulette at every bounce >= K but the last, unbiased (0 = off, the default; K in [0,64])\n"
+               "      --lens-radius R  thin lens: aperture radius in world units (0 = pinhole; overrides the scene's \"lens_radius\")\n"
+               "      --focus-distance F  thin lens: distance of the plane in focus, > 0 (overrides the scene's \"focus_distance\")\n"
                "      --gpu N          HIP device ordinal\n"
                "      --gpus N         split the frame's rows over N processes / GPUs (rank r on device r %% device count)\n"
                "      --dump-scene F   write the flattened scene to F and exit (no GPU needed)\n"
@@ -113,6 +117,18 @@ CliConfigurations parse_cli_args(int argc, char** argv)
         std::exit(1);
       }
       c.roulette = k;
+    }
+    else if (a == "--lens-radius" || a == "--focus-distance") {
+      // a finite decimal number, >= 0 (radius) or > 0 (focus distance), refused here: before the scene is read or a GPU touched
+      const bool radius = a == "--lens-radius";
+      const std::string v = need(a.c_str() + 2);
+      char* end = nullptr;
+      const float x = std::strtof(v.c_str(), &end);
+      if (v.empty() || *end != '\0' || !std::isfinite(x) || x < 0.0f || (!radius && x == 0.0f)) {
+        std::fprintf(stderr, "Option '%s': '%s' is not a finite number %s\n", a.c_str(), v.c_str(), radius ? ">= 0" : "> 0");
+        std::exit(1);
+      }
+      (radius ? c.lens_radius : c.focus_distance) = x;
     }
     else if (a == "--gpu") c.gpu = std::stoi(need("gpu"));
     else if (a == "--gpus") c.gpus = std::stoi(need("gpus"));
@@ -274,6 +290,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
   path_tracer.roulette = configs.roulette;
+  if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
 
   int shown = 0;
   std::vector<uchar4> buffer;
@@ -379,6 +396,7 @@ try {
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
   path_tracer.roulette = configs.roulette;
+  if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.create_buffers(resolution, scene_desc);
   auto check = [&](int rc, const char* what) {
     if (rc < 0) throw std::runtime_error(std::string(what) + ": " + ptc_last_error(path_tracer.handle()));
@@ -522,6 +540,13 @@ try {
   SceneDescription scene_desc = scene_from_json(path.string());
   scene_desc.filename = configs.filename;
   if (configs.spp) scene_desc.spp = *configs.spp;
+  // the thin lens: the command line over the scene file; a radius > 0 needs a focus distance from one of them (before any GPU is touched)
+  if (configs.lens_radius) scene_desc.camera.lens_radius = *configs.lens_radius;
+  if (configs.focus_distance) scene_desc.camera.focus_distance = *configs.focus_distance;
+  if (scene_desc.camera.lens_radius > 0.0f && !(scene_desc.camera.focus_distance > 0.0f)) {
+    std::fprintf(stderr, "hip_pt: a lens radius > 0 needs a focus distance (--focus-distance F, or \"focus_distance\" in the scene's camera)\n");
+    return 1;
+  }
   stopwatch.end_stage("Scene loading");
 
   if (configs.dump_scene) {
@@ -537,6 +562,10 @@ try {
     out.write(reinterpret_cast<const char*>(&cam), sizeof cam);
     const int32_t tail[3] = {scene_desc.resolution[0], scene_desc.resolution[1], scene_desc.spp};
     out.write(reinterpret_cast<const char*>(tail), sizeof tail);
+    if (scene_desc.camera.lens_radius != 0.0f || scene_desc.camera.focus_distance != 0.0f) {  // (a scene without a lens: the dump as ever)
+      const float lens[2] = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
+      out.write(reinterpret_cast<const char*>(lens), sizeof lens);
+    }
     return 0;
   }
   if (configs.replay && configs.dry_run) return run_replay(configs, scene_desc);
@@ -555,6 +584,7 @@ try {
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
   path_tracer.roulette = configs.roulette;
+  if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.create_buffers(resolution, scene_desc);
   path_tracer.synchronize();
   std::printf("Start path tracing\nspp: %d\nwidth: %u, height: %u\n", spp, resolution.width, resolution.height);

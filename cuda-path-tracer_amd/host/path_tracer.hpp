@@ -40,6 +40,12 @@ public:
   GPUMethod current_gpu_method = GPUMethod::streaming;
   bool direct_light = false;  // a light sample at every diffuse hit (megakernel method only; ptc_set_param "direct_light")
   int roulette = 0;  // Russian roulette at every bounce >= this but the last, 0 = off (both methods; ptc_set_param "roulette", [0, 64])
+  // the thin lens (ptc_set_lens): aperture radius (0 = the pinhole, the default) and the distance of the plane in
+  // focus, world units; both methods
+  struct Lens {
+    float radius = 0.0f, focus_distance = 1.0f;
+    bool operator!=(const Lens& o) const { return radius != o.radius || focus_distance != o.focus_distance; }
+  } lens;
   EdgeAvoidingATrousDenoiser atrous_denoiser{};
   int max_bounces = 50;  // reference: compile-time constant, path_tracer.cu:27
 
@@ -114,6 +120,10 @@ private:
       check(ptc_set_param(ctx_, "roulette", roulette), "roulette");
       roulette_pushed_ = roulette;
     }
+    if (lens != lens_pushed_) {  // (ptc_set_lens flushes queued frames too)
+      check(ptc_set_lens(ctx_, lens.radius, lens.focus_distance), "lens");
+      lens_pushed_ = lens;
+    }
     check(ptc_set_max_bounces(ctx_, max_bounces), "max_bounces");
     const ptc_denoiser_params p{atrous_denoiser.filter_size, atrous_denoiser.color_weight, atrous_denoiser.normal_weight,
                                 atrous_denoiser.position_weight};
@@ -126,6 +136,7 @@ private:
   ptc_ctx* ctx_ = nullptr;
   bool direct_light_pushed_ = false;
   int roulette_pushed_ = 0;
+  Lens lens_pushed_{};
 };
 
 }  // namespace hip_pt

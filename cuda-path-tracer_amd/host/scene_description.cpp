@@ -320,6 +320,16 @@ SceneDescription scene_from_json(const std::string& filename)
     quat_from_matrix(m, scene.camera.rotation_wxyz);
   }
   scene.camera.vfov = camera.at("vfov").f() * 0.01745329251994329576923690768489f;
+  // the thin lens (an extension; json_parser.py, the same rule): optional, a finite number each, >= 0 / > 0
+  auto lens_value = [&](const char* key, bool positive) -> float {
+    const Json* j = camera.find(key);
+    if (!j) return 0.0f;
+    if (j->kind != Json::Number || !std::isfinite(j->num) || j->num < 0.0 || (positive && j->num == 0.0))
+      throw std::runtime_error(std::string("Json Parser: camera \"") + key + "\" must be a finite number " + (positive ? "> 0" : ">= 0"));
+    return (float)j->num;
+  };
+  scene.camera.lens_radius = lens_value("lens_radius", false);
+  scene.camera.focus_distance = lens_value("focus_distance", true);
   if (const Json* r = camera.find("resolution")) {
     if (r->kind != Json::Array || r->arr.size() != 2) throw std::runtime_error("Json Parser: resolution need to be 2d");
     scene.resolution[0] = (int)r->arr[0]->num;

@@ -43,6 +43,10 @@ struct Camera {  // camera.hpp:17-23
   float position[3] = {0, 0, 0};
   float rotation_wxyz[4] = {1, 0, 0, 0};
   float vfov = 1.57079632679f;
+  // the thin lens (an extension: the reference's camera is a pinhole), PathTracer::lens's two values.  Not part
+  // of ptc_camera: the lens is the context's (ptc_set_lens).  0 / 0: no lens, none given
+  float lens_radius = 0.0f;
+  float focus_distance = 0.0f;
   [[nodiscard]] ptc_camera to_c() const
   {
     return ptc_camera{{position[0], position[1], position[2]},

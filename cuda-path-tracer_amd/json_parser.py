@@ -82,6 +82,17 @@ def _emission(m):
     return tuple(e)
 
 
+def _lens_value(cam, key, positive):
+    """An optional camera key of the thin lens (an extension; scene_description.cpp, the same rule): a finite number, >= 0
+    ("lens_radius") or > 0 ("focus_distance").  Absent: 0."""
+    if key not in cam:
+        return 0.0
+    v = cam[key]
+    if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v) or v < 0 or (positive and v == 0):
+        raise ValueError(f"Json Parser: camera \"{key}\" must be a finite number {'> 0' if positive else '>= 0'}, got {v!r}")
+    return float(np.float32(v))
+
+
 def scene_from_json(filename):
     with open(filename) as f:
         root = json.load(f)
@@ -117,6 +128,8 @@ def scene_from_json(filename):
         camera.position = tuple(float(v) for v in m[3, 0:3])
         camera.rotation = tuple(float(v) for v in glm.quat_from_matrix(m))
     camera.vfov = float(np.float32(np.float32(cam["vfov"]) * np.float32(0.01745329251994329576923690768489)))
+    camera.lens_radius = _lens_value(cam, "lens_radius", False)
+    camera.focus_distance = _lens_value(cam, "focus_distance", True)
     scene.camera = camera
     if "resolution" in cam:
         scene.resolution = (int(cam["resolution"][0]), int(cam["resolution"][1]))

@@ -89,6 +89,7 @@ class PathTracer:
         self.current_gpu_method = GPUMethod.streaming
         self._direct_light = False  # PathTracer.direct_light = True: a light sample at every diffuse hit (megakernel method only)
         self._roulette = 0  # PathTracer.roulette = k: Russian roulette at every bounce >= k but the last (0 = off)
+        self._lens = (0.0, 1.0)  # PathTracer.lens = (radius, focus_distance): the thin lens (radius 0 = the pinhole)
         self.atrous_denoiser = EdgeAvoidingATrousDenoiser()
         self.max_bounces = max_bounces  # reference: compile-time 50 (path_tracer.cu:27)
         cfg = _capi.ptc_config(device=device, max_bounces=max_bounces, method=int(self.current_gpu_method), reserved=0)
@@ -99,6 +100,7 @@ class PathTracer:
         self._rows = None
         self._direct_light_pushed = False
         self._roulette_pushed = 0
+        self._lens_pushed = (0.0, 1.0)
 
     # -- lifetime -------------------------------------------------------------------------------
     def close(self):
@@ -144,6 +146,22 @@ class PathTracer:
             raise ValueError("roulette must be in [0,64]")
         self._roulette = k
 
+    @property
+    def lens(self):
+        """The thin lens (ptc_set_lens): (lens_radius, focus_distance) in world units.  Radius 0 (the default) is the
+        pinhole; under a radius > 0 the plane at camera-space depth focus_distance is sharp and everything else blurs with the radius,
+        in both render methods."""
+        return self._lens
+
+    @lens.setter
+    def lens(self, value):
+        radius, focus = (float(np.float32(v)) for v in value)
+        if not np.isfinite(radius) or radius < 0.0:
+            raise ValueError(f"lens radius must be finite and not negative, got {radius}")
+        if not np.isfinite(focus) or (radius > 0.0 and not focus > 0.0):
+            raise ValueError(f"focus distance must be finite, and positive under a lens radius > 0, got {focus}")
+        self._lens = (radius, focus)
+
     def _push_fields(self):
         self._check(self._lib.ptc_set_max_iterations(self._ctx, int(self.max_iterations)))
         self._check(self._lib.ptc_set_method(self._ctx, int(self.current_gpu_method)))
@@ -153,6 +171,9 @@ class PathTracer:
         if self._roulette != self._roulette_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"roulette", self._roulette))
             self._roulette_pushed = self._roulette
+        if self._lens != self._lens_pushed:
+            self._check(self._lib.ptc_set_lens(self._ctx, self._lens[0], self._lens[1]))
+            self._lens_pushed = self._lens
         self._check(self._lib.ptc_set_max_bounces(self._ctx, int(self.max_bounces)))
         d = self.atrous_denoiser
         p = _capi.ptc_denoiser_params(int(d.filter_size), float(d.color_weight), float(d.normal_weight),
@@ -381,6 +402,15 @@ class PathTracer:
             nrm.ctypes.data_as(C.POINTER(C.c_float)), mat.ctypes.data_as(C.POINTER(C.c_uint32)),
             side.ctypes.data_as(C.POINTER(C.c_uint8))))
         return t, nrm, mat, side
+
+    def generate_rays(self, camera, iteration=0):
+        """The primary rays of `iteration` for every pixel of this context in slot order, under the current lens: [n, 8] float32
+        (origin, t_min, direction, t_max), what intersect_rays and occluded_rays take.  Moves neither stats nor the iteration."""
+        self._push_fields()
+        cam = camera.to_c() if isinstance(camera, Camera) else camera
+        rays = np.empty((self.pixel_count(), 8), dtype=np.float32)
+        self._check(self._lib.ptc_generate_rays(self._ctx, C.byref(cam), int(iteration), rays.ctypes.data_as(C.c_void_p), rays.size))
+        return rays
 
     def occluded_rays(self, rays):
         """rays: [n, 8] float32 (origin, t_min, direction, t_max).  Returns uint8[n]: 1 where anything lies on the ray within

@@ -60,6 +60,10 @@ class Camera:  # camera.hpp:17-23
     position: tuple = (0.0, 0.0, 0.0)
     rotation: tuple = (1.0, 0.0, 0.0, 0.0)  # w x y z
     vfov: float = float(np.pi / 2)
+    # the thin lens (an extension: the reference's camera is a pinhole), PathTracer.lens's two values.  Not part
+    # of ptc_camera: the lens is the context's (ptc_set_lens).  0 / 0: no lens, none given
+    lens_radius: float = 0.0
+    focus_distance: float = 0.0
 
     def to_c(self):
         c = _capi.ptc_camera()

@@ -358,6 +358,18 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *   "debug_force_slow" test hook: route every ray through the exact redo at the end of the traversal launch */
 int ptc_set_param(ptc_ctx* ctx, const char* name, int value);
 
+/* The thin lens (an extension: the reference's camera is a pinhole).  Two context-wide values in world units: the
+ * aperture radius (default 0 = the pinhole: exactly what was launched before the lens existed) and the distance of the plane in
+ * focus (default 1; read only under a radius > 0).  Under a radius > 0 the primary ray of a pixel leaves a point of the lens disk
+ * -- uniform on the disk, two draws of a random stream of its own (path_seed(pixel, iteration) ^ 0x4c454e53) -- towards the point
+ * the pinhole ray has at camera-space depth focus_distance; the jitter and every material draw are the pinhole render's.  Both render
+ * methods and every parameter that renders a pinhole frame ("direct_light", "roulette", emitters, rows / interleave); a lens frame
+ * gets no entry points ("beam"), and ptc_denoise's positions stay the pinhole ray's x depth (approximate under a lens).
+ * PTC_ERR_INVALID, with the offending value in ptc_last_error and the lens left as it was: a NaN or infinite value, a negative
+ * radius, a radius > 0 with focus_distance <= 0.  Any time (queued frames are flushed first: a batch renders with one lens). */
+int ptc_set_lens(ptc_ctx* ctx, float lens_radius, float focus_distance);
+int ptc_get_lens(ptc_ctx* ctx, float* lens_radius, float* focus_distance);
+
 /* ---- the hot path ---- */
 /* PathTracer::path_trace (path_tracer.cu:389-477): one sample per pixel, accumulated as a running
  * mean; no-op once iteration() >= max_iterations.  Asynchronous on the context's stream. */
@@ -449,6 +461,13 @@ int ptc_get_profile(ptc_ctx* ctx, ptc_profile* out);                /* synchroni
  * hit_t[n] (t, or -1 on miss), hit_normal[3n], hit_material[n], hit_side[n]. */
 int ptc_intersect_rays(ptc_ctx* ctx, const float* rays, uint32_t n, float* hit_t, float* hit_normal,
                        uint32_t* hit_material, uint8_t* hit_side);
+
+/* The primary rays of `iteration` for every slot of the context in slot order -- all pixels, or this context's under ptc_set_rows /
+ * ptc_set_interleave -- as the frame's ray generation builds them for `camera` under the context's lens (ptc_set_lens): the same
+ * device function.  rays_out (host): 8 floats per ray, origin, t_min, direction, t_max -- what ptc_intersect_rays,
+ * ptc_occluded_rays and ptc_direct_light's shadow rays take; capacity_floats >= 8 x the context's pixels.  After ptc_resize;
+ * synchronises; moves neither ptc_stats nor the iteration counter. */
+int ptc_generate_rays(ptc_ctx* ctx, const ptc_camera* camera, uint32_t iteration, float* rays_out, uint64_t capacity_floats);
 
 /* Occlusion queries (an extension: the reference has no any-hit query).  occluded[i] = 1 iff ray_scene_intersection_test
  * (path_tracer.cu:110-128) reports a hit for ray i, else 0 -- the reference's own arithmetic and corners: world box by

@@ -1,0 +1,333 @@
+"""The thin lens (ptc_set_lens) on the GPU against its CPU restatement (tests/lens_ref.py: lit_ref's loops with the lens's
+primary rays), bit for bit: colour, first-hit normal and depth, ptc_stats.rays_total and the per-bounce live counts.  The primary
+rays themselves through ptc_generate_rays; one streaming frame per ray-generation instance the host can pick; the megakernel (plain,
+"roulette", "direct_light": the three loop counters too); interleaved ranks; lens changes between calls; the refusals; denoise and
+present of a lens frame.  Frames are 64 x 48, 4 bounces, 3 accumulated iterations unless a case says otherwise."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import lens_ref
+import lit_ref
+
+pytestmark = pytest.mark.gpu
+
+PLANES = ("color", "normal", "depth")
+COUNTERS = ("diffuse_hits", "shadow_rays", "unoccluded")
+W, H, MB, ITERS = 64, 48, 4, 3
+LENS = (0.25, 3.5)
+_cache = {}
+
+
+def _scene(pkg, name):
+    """name -> (scene, flat), built once"""
+    if name not in _cache:
+        if name == "room":       # the sphere room in front of two instances of one mesh: bounce 0 opens with a sphere run
+            scene = pkg.scenes.cornell_bunny(resolution=(W, H), n_lat=6, n_lon=12)
+        elif name == "lit":      # ... with lamps: a mesh panel and a sphere (emitters, "direct_light")
+            scene = pkg.scenes.cornell_lit(resolution=(W, H), with_mesh=True)
+        elif name == "spheres":
+            scene = pkg.scenes.cornell_spheres((W, H))
+        else:                    # a heightfield alone under the sky ("terrain"), or with a sphere behind it in the object list
+            scene = _terrain(pkg, name == "terrain_sphere")
+        _cache[name] = (scene, scene.build_scene())
+    return _cache[name]
+
+
+def _terrain(pkg, sphere):
+    """tests/test_gpu_primary_misses.py's terrain, looked at from above: one mesh object opens the object list -- ray generation lists the rays of its launch
+    and finishes the others (k_raygen<true, true>), and a pinhole frame would get entry points ("beam")."""
+    glm = pkg.glmlite
+    s = pkg.SceneDescription()
+    s.add_material("ground", pkg.DiffuseMateral((0.7, 0.6, 0.5)))
+    s.add_material("glass", pkg.DielectricMaterial(1.5))
+    s.add_object(s.add_mesh("terrain", pkg.scenes.heightfield_mesh(49, 33, 3.0, 2.0, seed=11)), glm.identity(), "ground")
+    if sphere:
+        s.add_object(pkg.Sphere((0, 0, 0), 0.4), glm.translate((0.3, 0.6, 0.2)), "glass")
+    s.camera = pkg.scenes._camera_from_look_at((0.0, 3.0, 2.5), (0.0, 0.0, 0.0), vfov_deg=40.0)   # (the terrain and a band of sky)
+    return s
+
+
+def _tracer(pkg, flat, w=W, h=H, mb=MB, params=(), method=None, direct=False, roulette=0, interleave=None):
+    pt = pkg.PathTracer(device=0, max_bounces=mb)
+    for name, v in params:
+        pt.set_param(name, v)
+    if method is not None:
+        pt.current_gpu_method = method
+    pt.direct_light = direct
+    pt.roulette = roulette
+    pt.create_buffers((w, h), flat)
+    if interleave is not None:
+        rank, world, block = interleave
+        pt.set_interleave(rank, world, block)
+        pt.set_param("slot_offset", rank * w * h)
+    return pt
+
+
+def _result(pt):
+    out = {p: pt.download(p) for p in PLANES}
+    st = pt.stats()
+    out["rays"], out["last_live"] = st["rays_total"], st["last_live"]
+    out["persist_launches"] = pt.profile()["persist_launches"]
+    out.update(pt.direct_loop_stats())
+    return out
+
+
+def _render(pkg, flat, cameras, lens, iters=ITERS, iter_begin=0, **kw):
+    """iteration i of the run with cameras[i % len(cameras)]"""
+    with _tracer(pkg, flat, **kw) as pt:
+        pt.lens = lens
+        pt.restart()
+        if iter_begin:
+            pt.set_iteration(iter_begin)
+        pt.max_iterations = iter_begin + iters
+        pt.reset_profile()
+        for i in range(iters):
+            pt.path_trace(cameras[i % len(cameras)])
+        return _result(pt)
+
+
+def _ref_streaming(orc, flat, cameras, lens, iters=ITERS, w=W, h=H, mb=MB, **kw):
+    """the restatement, iteration by iteration (each folds into the one before: `prev`), with the camera and the lens of each;
+    lens: one for all iterations, or a list with one per iteration"""
+    lenses = lens if isinstance(lens, list) else [lens] * iters
+    prev, rays = None, 0
+    for i in range(iters):
+        prev = lens_ref.render_streaming(orc, flat, cameras[i % len(cameras)], w, h, i, 1, mb, lens=lenses[i], prev=prev, **kw)
+        rays += prev["rays"]
+    return {**prev, "rays": rays}
+
+
+def _same(got, ref, what, live=True, counters=()):
+    for p in PLANES:
+        a = np.ascontiguousarray(got[p]).view(np.uint32)
+        b = np.ascontiguousarray(ref[p], dtype=np.float32).reshape(got[p].shape).view(np.uint32)
+        assert np.array_equal(a, b), (what, p, int(np.sum(a != b)), np.argwhere(a != b)[:4].tolist())
+    assert got["rays"] == ref["rays"], (what, got["rays"], ref["rays"])
+    if live:
+        want = [int(x) for x in ref["live"][-1]]
+        assert got["last_live"][:len(want)] == want, (what, got["last_live"], want)
+    for c in counters:
+        assert got[c] == ref[c], (what, c, got[c], ref[c])
+
+
+# ---- 1. the primary rays ----------------------------------------------------------------------------------------------------
+def _check_rays(rays, o, d):
+    assert rays.shape == (len(o), 8) and rays.dtype == np.float32
+    assert np.array_equal(rays[:, 0:3].view(np.uint32), o.view(np.uint32))
+    assert np.array_equal(rays[:, 4:7].view(np.uint32), d.view(np.uint32))
+    assert np.all(rays[:, 3] == np.float32(1e-4)) and np.all(rays[:, 7] == np.finfo(np.float32).max)
+
+
+@pytest.mark.parametrize("w,h", [(64, 48), (65, 33)])
+@pytest.mark.parametrize("iteration", [0, 2 ** 31 - 6])
+def test_generate_rays_against_the_restatement(pkg, orc, w, h, iteration):
+    """ptc_generate_rays, lens off and on, bit for bit; with the lens off the rays are the parent's (lit_ref._primary); the query moves
+    neither the iteration counter nor ptc_stats."""
+    scene, flat = _scene(pkg, "spheres")
+    pixels = np.arange(w * h)
+    with _tracer(pkg, flat, w, h) as pt:
+        for lens in ((0.0, 1.0), LENS, (5.0, 0.1), (0.0, 7.0)):
+            pt.lens = lens
+            rays = pt.generate_rays(scene.camera, iteration)
+            o, d, _, _ = lens_ref.primary(orc, scene.camera, w, h, pixels, iteration, lens)
+            _check_rays(rays, o, d)
+            if lens[0] == 0.0:
+                po, pd, _, _ = lit_ref._primary(orc, scene.camera, w, h, pixels, iteration)
+                _check_rays(rays, po, pd)
+            else:
+                assert not np.array_equal(rays[:, 0:3], np.broadcast_to(rays[0, 0:3], (w * h, 3)))   # (origins spread over the lens)
+        assert pt.iteration() == 0 and pt.stats()["rays_total"] == 0
+
+
+def test_generate_rays_of_an_interleaved_rank(pkg, orc):
+    """rank 1 of 2, blocks of 8 rows: the rank's slots in slot order, keyed by frame pixel"""
+    scene, flat = _scene(pkg, "spheres")
+    pixels = lit_ref.interleaved_pixels(W, H, 1, 2, 8)
+    with _tracer(pkg, flat, interleave=(1, 2, 8)) as pt:
+        for lens in ((0.0, 1.0), LENS):
+            pt.lens = lens
+            rays = pt.generate_rays(scene.camera, 5)
+            assert len(rays) == len(pixels) == W * H // 2
+            o, d, _, _ = lens_ref.primary(orc, scene.camera, W, H, pixels, 5, lens)
+            _check_rays(rays, o, d)
+
+
+# ---- 2. one streaming frame per ray-generation instance -------------------------------------------------------------------------
+TERRAIN_LENS = (0.5, 2.0)  # the terrain lies about 3.9 from the camera: out of focus by about the lens radius, an 8 x 8 tile's footprint there
+
+STREAMING = {
+    # (scene, lens, parameters): which ray generation the host picks
+    "room_raygen_next": ("room", LENS, ()),                                       # k_raygen_next_lens ("prefold")
+    "room_no_prefold": ("room", LENS, (("prefold", 0),)),                        # k_raygen_lens<false, false>, k_spheres opens bounce 0
+    "terrain": ("terrain", TERRAIN_LENS, ()),                                     # k_raygen_lens<true, true>; where "beam" would be on
+    "terrain_sphere": ("terrain_sphere", TERRAIN_LENS, ()),                       # ... the trailing sphere's box joins the filter
+    "terrain_no_filter": ("terrain", TERRAIN_LENS, (("filter_rays", 0),)),        # k_raygen_lens<false, false>
+    "terrain_three_kernels": ("terrain_sphere", TERRAIN_LENS, (("fused_shade", 0),)),  # k_raygen_lens<true, false>
+    "terrain_persist": ("terrain_sphere", TERRAIN_LENS, (("persist", 1), ("frames_in_flight", 12), ("batch_frames", 12))),
+    "terrain_unstaged": ("terrain", TERRAIN_LENS, (("frames_in_flight", 1),)),    # kFinish folds the sky into the framebuffers themselves
+    "room_unstaged": ("room", LENS, (("frames_in_flight", 1),)),
+}
+
+
+@pytest.mark.parametrize("name", list(STREAMING))
+def test_streaming_frame_per_ray_generation_instance(pkg, orc, name):
+    scene_name, lens, params = STREAMING[name]
+    scene, flat = _scene(pkg, scene_name)
+    key = ("stream", scene_name, lens)
+    if key not in _cache:
+        _cache[key] = _ref_streaming(orc, flat, [scene.camera], lens)
+    got = _render(pkg, flat, [scene.camera], lens, params=params)
+    _same(got, _cache[key], name)
+    if name == "terrain_persist":
+        assert got["persist_launches"] >= 1
+    pin = ("stream", scene_name, None)
+    if pin not in _cache:
+        _cache[pin] = _ref_streaming(orc, flat, [scene.camera], None)
+    assert not np.array_equal(_cache[key]["depth"], _cache[pin]["depth"])   # (the lens does change the frame)
+
+
+def test_terrain_lens_rays_leave_their_tile_s_pinhole_frustum(pkg, orc):
+    """Why a lens frame gets no entry points ("beam"): k_beam computes a tile's entries for the frustum from the PINHOLE origin through
+    the tile's 8 x 8 pixels, and a lens ray's hit need not lie in it.  Of the restatement's 3072 primary rays of the terrain frame at
+    iteration 0 under TERRAIN_LENS, 1305 hit the mesh, and 869 of those at a point that the pinhole projects into ANOTHER tile (checked
+    here on the CPU; with the entries of their own tile such rays could start below the subtree that holds their hit).  The GPU frame
+    of this very case is test_streaming_frame_per_ray_generation_instance[terrain]; profiles/lens.txt records it failing with the
+    decision taken out."""
+    scene, flat = _scene(pkg, "terrain")
+    pixels = np.arange(W * H)
+    o, d, tmin, _ = lens_ref.primary(orc, scene.camera, W, H, pixels, 0, TERRAIN_LENS)
+    recs, hit = orc.intersect_rays(flat, lit_ref._rays(o, tmin, d))
+    hit = hit.astype(bool)
+    p = o[hit].astype(np.float64) + d[hit].astype(np.float64) * recs["t"][hit].astype(np.float64)[:, None]
+    m = lens_ref.camera_matrix(orc, scene.camera, W, H).astype(np.float64).reshape(4, 4).T
+    pc = (np.concatenate([p, np.ones((len(p), 1))], axis=1) @ np.linalg.inv(m).T)[:, :3]
+    llx, lly, vw, vh = (float(v) for v in lens_ref.viewport(scene.camera, W, H))
+    fx = (pc[:, 0] / -pc[:, 2] - llx) / vw * (W - 1)
+    fy = H - (pc[:, 1] / -pc[:, 2] - lly) / vh * (H - 1)
+    own = pixels[hit]
+    left = (np.floor(fx / 8) != (own % W) // 8) | (np.floor(fy / 8) != (own // W) // 8)
+    print(f"{int(hit.sum())} of {W * H} rays hit the mesh, {int(left.sum())} outside their tile's pinhole frustum")
+    assert (int(hit.sum()), int(left.sum())) == TERRAIN_COUNTS
+    assert left.sum() > 0
+
+
+TERRAIN_COUNTS = (1305, 869)
+
+
+def test_a_batch_of_four_iterations_with_two_cameras(pkg, orc):
+    """one launch of ray generation for four frames: the cameras alternate, the lens is the batch's"""
+    scene, flat = _scene(pkg, "room")
+    other = pkg.scenes._camera_from_look_at((0.6, 0.4, 3.6), (0.0, -0.4, 0.0), vfov_deg=50.0)
+    cameras = [scene.camera, other]
+    ref = _ref_streaming(orc, flat, cameras, LENS, iters=4)
+    got = _render(pkg, flat, cameras, LENS, iters=4, params=(("frames_in_flight", 8), ("batch_frames", 4)))
+    _same(got, ref, "batch of 4, two cameras")
+    scene, flat = _scene(pkg, "terrain_sphere")
+    cameras = [scene.camera, pkg.scenes._camera_from_look_at((0.5, 2.6, 2.2), (0.0, 0.0, 0.0), vfov_deg=45.0)]
+    ref = _ref_streaming(orc, flat, cameras, TERRAIN_LENS, iters=4)
+    got = _render(pkg, flat, cameras, TERRAIN_LENS, iters=4, params=(("frames_in_flight", 8), ("batch_frames", 4)))
+    _same(got, ref, "batch of 4, two cameras, terrain")
+
+
+# ---- 3. the megakernel ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,direct,roulette", [("plain", False, 0), ("roulette", False, 2), ("direct", True, 0), ("direct_roulette", True, 2)])
+def test_megakernel_against_the_restatement(pkg, orc, name, direct, roulette):
+    """cornell_lit (emitters: the kEmit instances) and, plain, the room without lamps; with "direct_light" the three loop counters too"""
+    for scene_name in ("lit",) + (("room",) if not direct else ()):
+        scene, flat = _scene(pkg, scene_name)
+        ref = lens_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, lens=LENS, direct=direct, roulette=roulette)
+        got = _render(pkg, flat, [scene.camera], LENS, method=pkg.GPUMethod.megakernel, direct=direct, roulette=roulette)
+        _same(got, ref, (name, scene_name), live=False, counters=COUNTERS)
+        if roulette:
+            assert ref["played"].sum() > 0 and ref["ended"].sum() > 0
+        if direct:
+            assert ref["shadow_rays"] > 0
+        pin = lit_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, roulette=roulette)
+        assert not np.array_equal(ref["depth"], pin["depth"])
+
+
+# ---- 4., 5. roulette and interleaved ranks in the streaming loop ---------------------------------------------------------------------
+def test_roulette_in_the_streaming_loop_with_a_lens(pkg, orc):
+    scene, flat = _scene(pkg, "lit")
+    ref = _ref_streaming(orc, flat, [scene.camera], LENS, roulette=2)
+    assert ref["played"].sum() > 0
+    _same(_render(pkg, flat, [scene.camera], LENS, roulette=2), ref, "roulette 2")
+    _same(_render(pkg, flat, [scene.camera], LENS, roulette=2, params=(("fused_shade", 0),)), ref, "roulette 2, three kernels")
+
+
+def test_two_interleaved_ranks(pkg, orc):
+    """rows dealt in blocks of 8, paths numbered per rank, slot_offset = rank * W * H (tests/test_gpu_interleaved.py): the lens stream
+    is keyed by FRAME pixel, the material stream by slot_offset + slot"""
+    scene, flat = _scene(pkg, "room")
+    sh = orc.SceneHandle(flat)
+    for rank in (0, 1):
+        pixels = lit_ref.interleaved_pixels(W, H, rank, 2, 8)
+        ref = _ref_streaming(orc, flat, [scene.camera], LENS, pixels=pixels, slot_offset=rank * W * H, scene_handle=sh)
+        _same(_render(pkg, flat, [scene.camera], LENS, interleave=(rank, 2, 8)), ref, ("interleaved", rank))
+
+
+# ---- 6. lens changes between calls ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("method", ["streaming", "megakernel"])
+def test_lens_changes_between_calls(pkg, orc, method):
+    """off, on, another lens, off again: every iteration has the restatement's bits and the running mean folds them in order; radius 0
+    after a lens frame gives back the pinhole's primary rays for the next iteration"""
+    scene, flat = _scene(pkg, "room")
+    lenses = [(0.0, 1.0), LENS, (0.05, 6.0), (0.0, 3.0)]
+    mega = method == "megakernel"
+    render = lens_ref.render_megakernel if mega else lens_ref.render_streaming
+    with _tracer(pkg, flat, method=pkg.GPUMethod.megakernel if mega else None) as pt:
+        pt.max_iterations = len(lenses)
+        prev, rays = None, 0
+        for i, lens in enumerate(lenses):
+            pt.lens = lens
+            pt.path_trace(scene.camera)
+            prev = render(orc, flat, scene.camera, W, H, i, 1, MB, lens=lens, prev=prev)
+            rays += prev["rays"]
+            _same(_result(pt), {**prev, "rays": rays}, (method, i, lens), live=not mega)
+            r, f = C.c_float(), C.c_float()
+            assert pt._lib.ptc_get_lens(pt._ctx, C.byref(r), C.byref(f)) == 0
+            assert (r.value, f.value) == (np.float32(lens[0]), np.float32(lens[1]))
+
+
+# ---- 7. the refusals -------------------------------------------------------------------------------------------------------------
+def test_the_refusals(pkg, orc):
+    scene, flat = _scene(pkg, "room")
+    invalid = pkg._capi.PTC_ERR_INVALID
+    with _tracer(pkg, flat) as pt:
+        pt.lens = LENS
+        pt.max_iterations = 2
+        pt.path_trace(scene.camera)
+        for r, f, says in ((float("nan"), 1.0, "nan"), (0.5, float("nan"), "nan"), (float("inf"), 1.0, "inf"), (0.5, float("inf"), "inf"),
+                           (-0.25, 1.0, "-0.25"), (0.5, 0.0, "0.0"), (0.5, -3.0, "-3.0")):
+            assert pt._lib.ptc_set_lens(pt._ctx, r, f) == invalid, (r, f)
+            text = pt._lib.ptc_last_error(pt._ctx).decode()
+            assert says in text and ("lens_radius" in text or "focus_distance" in text), (r, f, text)
+        assert pt._lib.ptc_set_lens(pt._ctx, 0.0, -1.0) == 0   # the pinhole asks nothing of the focus distance but a finite value ...
+        assert pt._lib.ptc_set_lens(pt._ctx, *LENS) == 0       # ... (and back, behind the mirror's back: the same lens)
+        pt.path_trace(scene.camera)                            # the context still renders, with the lens it had
+        _same(_result(pt), _ref_streaming(orc, flat, [scene.camera], LENS, iters=2), "after the refusals")
+
+
+# ---- 8. denoise and present ----------------------------------------------------------------------------------------------------------
+def test_denoise_and_present_of_a_lens_frame(pkg, orc):
+    """ptc_denoise and send_to_preview on a lens frame run and agree with orc_denoise / orc_preview applied to the same planes within the
+    tolerances of tests/test_gpu_denoise.py (1e-5, 1 LSB).  (Both rebuild positions from the PINHOLE ray x the accumulated depth: under
+    a lens those are approximate, DESIGN section 5i -- the same approximation on both sides.)"""
+    scene, flat = _scene(pkg, "room")
+    with _tracer(pkg, flat) as pt:
+        pt.lens = LENS
+        pt.max_iterations = 2
+        for _ in range(2):
+            pt.path_trace(scene.camera)
+        g = {k: pt.download(k) for k in PLANES}
+        pt.denoise()
+        out = pt.download("final")
+        rgba = pt.send_to_preview()
+    want, _ = orc.denoise(scene.camera, W, H, g["color"], g["normal"], g["depth"], 10)
+    assert np.isfinite(want).all() and np.isfinite(out).all()
+    assert float(np.max(np.abs(out.astype(np.float64) - want.astype(np.float64)))) <= 1e-5
+    want_rgba = orc.preview(want, W, H, 0)
+    assert np.all(rgba[..., 3] == 255)
+    assert int(np.abs(rgba[..., :3].astype(np.int32) - want_rgba[..., :3].astype(np.int32)).max()) <= 1
