@@ -196,6 +196,7 @@ SIGNATURES = {
     "ptc_check_traversal_layout": (C.c_int, [C.POINTER(ptc_bvh_node), C.c_uint32, C.POINTER(C.c_uint64)]),
     "ptc_check_beam": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                  C.POINTER(C.c_uint64), C.c_void_p]),
+    "ptc_check_beam_frustum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "ptc_debug_beam_entries": (C.c_int, [_P, C.POINTER(ptc_camera), C.c_void_p, C.c_uint64]),
     "ptc_debug_sphere_lanes": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptc_debug_persist": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint64]),

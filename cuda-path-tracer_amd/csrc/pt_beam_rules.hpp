@@ -15,24 +15,40 @@ constexpr int kEntries = 4;              // == pt::kBeamEntries
 PT_HD float as_float(uint32_t u) { return __builtin_bit_cast(float, u); }
 PT_HD bool finite1(float x) { return __builtin_fabsf(x) < __builtin_inff(); }
 
-// Four planes through `eye`, each spanned by two neighbouring corner directions of the tile's pixel rectangle and turned
-// so that the centre direction `dc` lies inside (n . dc >= 0).  Inside = the forward pyramid only.
+// Four planes through `eye` around the pixel rectangle [x0, x1] x [y0, y1] of a camera (DCamera's constants, generate_ray's
+// operations for the rectangle's sides), in the space of an object with inverse matrix inv_m.  Inside = the forward pyramid.
+//
+// A side of the rectangle is a line of camera space, dx = const or dy = const, and the plane through the eye and that line is
+// spanned by two vectors a right angle apart: (dx, 0, -1) and the camera's y axis for a vertical side, (0, dy, -1) and the
+// camera's x axis for a horizontal one.  Each is taken through cam and inv_m (linear maps: the images span the image of the
+// plane) before the cross product, and the normal is turned towards the image of the axis that points into the rectangle.
+// Neither the length of the normal nor its sign depends on how narrow the rectangle is: two NEIGHBOURING CORNER directions, an
+// angle theta apart, give a normal of length theta whose rounding tilts the plane by about 5e-8 / theta -- beyond the allowance of
+// outside() below theta = 5e-4, a telephoto view.  Here the tilt is a few ulp at any theta (the beam section).
 struct Frustum {
   f3 eye;
-  f3 n[4];
+  f3 n[4];      // left (x0), right (x1), top (y0), bottom (y1)
   bool usable;  // false (a degenerate camera): nothing is ever out of reach
 };
-PT_HD Frustum make_frustum(const f3 eye, const f3 d00, const f3 d10, const f3 d01, const f3 d11, const f3 dc)
+PT_HD Frustum tile_frustum(const m4& cam, const f3 origin, float llx, float lly, float vw, float vh, uint32_t width, uint32_t height,
+                           const m4& inv_m, float x0, float x1, float y0, float y1)
 {
+  const float dx0 = llx + vw * (x0 / (float)(width - 1u)), dx1 = llx + vw * (x1 / (float)(width - 1u));
+  const float dy0 = lly + vh * (((float)height - y0) / (float)(height - 1u)), dy1 = lly + vh * (((float)height - y1) / (float)(height - 1u));
+  const f3 ex = xform_vector(inv_m, xform_vector(cam, mk3(1.0f, 0.0f, 0.0f)));
+  const f3 ey = xform_vector(inv_m, xform_vector(cam, mk3(0.0f, 1.0f, 0.0f)));
   Frustum f;
-  f.eye = eye;
-  f.n[0] = cross(d00, d10);
-  f.n[1] = cross(d10, d11);
-  f.n[2] = cross(d11, d01);
-  f.n[3] = cross(d01, d00);
-  f.usable = finite1(eye.x + eye.y + eye.z);
+  f.eye = xform_point(inv_m, origin);
+  f.n[0] = cross(xform_vector(inv_m, xform_vector(cam, mk3(dx0, 0.0f, -1.0f))), ey);
+  f.n[1] = cross(xform_vector(inv_m, xform_vector(cam, mk3(dx1, 0.0f, -1.0f))), ey);
+  f.n[2] = cross(xform_vector(inv_m, xform_vector(cam, mk3(0.0f, dy0, -1.0f))), ex);
+  f.n[3] = cross(xform_vector(inv_m, xform_vector(cam, mk3(0.0f, dy1, -1.0f))), ex);
+  f.usable = finite1(f.eye.x + f.eye.y + f.eye.z);
   for (int k = 0; k < 4; ++k) {
-    if (dot(f.n[k], dc) < 0.0f) f.n[k] = -f.n[k];
+    // the inside of side k lies towards +axis when the other side of the pair has the larger coordinate
+    const bool up = k == 0 ? dx1 > dx0 : k == 1 ? dx0 > dx1 : k == 2 ? dy1 > dy0 : dy0 > dy1;
+    const float s = dot(f.n[k], k < 2 ? ex : ey);
+    if (up ? s < 0.0f : s > 0.0f) f.n[k] = -f.n[k];
     f.usable = f.usable && finite1(f.n[k].x + f.n[k].y + f.n[k].z) && dot(f.n[k], f.n[k]) > 0.0f;
   }
   return f;

@@ -114,9 +114,10 @@ extern "C" int ptc_debug_tailprof(void* dst, size_t bytes)
 #include "pt_walk.inc"
 
 // Entry points for primary rays (DBeam), one thread per tile and camera.  The tile's frustum: four planes through the
-// camera, each spanned by two neighbouring corner rays of the tile's pixel rectangle (generate_ray at the rectangle's
-// corners, a twentieth of a pixel outside: the jitter keeps a ray of pixel x inside [x, x + 1]); everything in the space
-// of the launch's object (the walk's space).  A box is out when its corner farthest along a plane's normal is still
+// camera around the tile's pixel rectangle (a twentieth of a pixel outside: the jitter keeps a ray of pixel x inside
+// [x, x + 1]), each spanned by two vectors a right angle apart so that a narrow tile conditions it no worse than a wide
+// one (beam_rules::tile_frustum, the rule the host checks share); everything in the space of the launch's object (the
+// walk's space).  A box is out when its corner farthest along a plane's normal is still
 // outside that plane by more than the margin; the pyramid is the forward one only, so what lies behind the camera is out
 // -- the reference's line-without-range box test would pass such boxes, but no triangle in them can be hit at t >= t_min.
 // Frontier: the root; as long as there is room for them, the largest inner entry is replaced by those of its (quantised)
@@ -132,14 +133,7 @@ __global__ __launch_bounds__(64) void k_beam(DScene sc, uint32_t obj_index, DCam
   const DObject* obj = sc.objects + obj_index;
   const float x0 = (float)(tx * kBeamTile) - 0.05f, x1 = (float)((tx + 1u) * kBeamTile) + 0.05f;
   const float y0 = (float)(ty * kBeamTile) - 0.05f, y1 = (float)((ty + 1u) * kBeamTile) + 0.05f;
-  f3 o, d00, d10, d01, d11, dc;
-  generate_ray(cam, x0, y0, o, d00);
-  generate_ray(cam, x1, y0, o, d10);
-  generate_ray(cam, x0, y1, o, d01);
-  generate_ray(cam, x1, y1, o, d11);
-  generate_ray(cam, 0.5f * (x0 + x1), 0.5f * (y0 + y1), o, dc);
-  const beam_rules::Frustum fr = beam_rules::make_frustum(xform_point(obj->inv_m, o), xform_vector(obj->inv_m, d00), xform_vector(obj->inv_m, d10),
-                                                          xform_vector(obj->inv_m, d01), xform_vector(obj->inv_m, d11), xform_vector(obj->inv_m, dc));
+  const beam_rules::Frustum fr = beam_rules::tile_frustum(cam.cam, cam.origin, cam.llx, cam.lly, cam.vw, cam.vh, cam.width, cam.height, obj->inv_m, x0, x1, y0, y1);
   f3 lo4[4], hi4[4];
   uint32_t ref4[4];
   int n = 0;

@@ -1,4 +1,4 @@
-// ptcore_checks.cpp -- host-side checks of the rules the kernels share with the host (ptc_check_beam, ptc_check_feed,
+// ptcore_checks.cpp -- host-side checks of the rules the kernels share with the host (ptc_check_beam, ptc_check_beam_frustum, ptc_check_feed,
 // ptc_check_traversal_layout, ptc_check_rng), ptc_debug_beam_entries, ptc_debug_sphere_lanes, ptc_selftest_math, ptc_selftest_rng, and
 // ptc_generate_rays (the frame's primary rays as ray generation builds them).  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
@@ -104,14 +104,7 @@ int ptc_check_beam(const float* positions, uint32_t vertex_count, const uint32_t
     for (uint32_t tx = 0; tx < tiles_x; ++tx) {
       const float x0 = (float)(tx * kBeamTile) - 0.05f, x1 = (float)((tx + 1u) * kBeamTile) + 0.05f;
       const float y0 = (float)(ty * kBeamTile) - 0.05f, y1 = (float)((ty + 1u) * kBeamTile) + 0.05f;
-      f3 o, d00, d10, d01, d11, dc;
-      gen(x0, y0, o, d00);
-      gen(x1, y0, o, d10);
-      gen(x0, y1, o, d01);
-      gen(x1, y1, o, d11);
-      gen(0.5f * (x0 + x1), 0.5f * (y0 + y1), o, dc);
-      const beam_rules::Frustum fr = beam_rules::make_frustum(xform_point(inv_m, o), xform_vector(inv_m, d00), xform_vector(inv_m, d10),
-                                                              xform_vector(inv_m, d01), xform_vector(inv_m, d11), xform_vector(inv_m, dc));
+      const beam_rules::Frustum fr = beam_rules::tile_frustum(cam.cam, cam.origin, cam.llx, cam.lly, cam.vw, cam.vh, cam.width, cam.height, inv_m, x0, x1, y0, y1);
       f3 lo4[4], hi4[4];
       uint32_t ref4[4];
       const int n = beam_rules::tile_entries(nq, n4, w4.root_ref, root_lo, root_hi, fr, lo4, hi4, ref4);
@@ -155,6 +148,40 @@ int ptc_check_beam(const float* positions, uint32_t vertex_count, const uint32_t
     stats5[4] = hits;
   }
   return bad;
+}
+
+// The tile frustums of ptc_check_beam / k_beam by themselves (pt_beam_rules.hpp: tile_frustum, the same call), without a mesh: per
+// tile 16 floats {eye.xyz, usable (1 or 0), n[0].xyz, n[1].xyz, n[2].xyz, n[3].xyz} into frusta_out [tiles][16], and the binary32
+// constants the rule read into consts39 (may be NULL): the camera matrix (16, column-major), its origin (3), vw, vh, llx, lly, and the
+// object's inverse matrix (16).  Returns the number of tiles or a negative status.
+int ptc_check_beam_frustum(const float* object_m16, const ptc_camera* camera, uint32_t width, uint32_t height, float* frusta_out,
+                           uint64_t capacity_floats, float* consts39)
+{
+  if (!camera || !frusta_out || width < 2u || height < 2u) return PTC_ERR_INVALID;
+  const uint32_t tiles_x = (width + kBeamTile - 1u) / kBeamTile, tiles_y = (height + kBeamTile - 1u) / kBeamTile;
+  if ((uint64_t)tiles_x * tiles_y > 0x7fffffffull || capacity_floats < (uint64_t)tiles_x * tiles_y * 16u) return PTC_ERR_INVALID;
+  m4 m{};
+  for (int c = 0; c < 4; ++c)
+    for (int r = 0; r < 4; ++r) m.c[c][r] = object_m16 ? object_m16[4 * c + r] : (c == r ? 1.0f : 0.0f);
+  const m4 inv_m = inverse(m);
+  const DCamera cam = make_camera(*camera, width, height);
+  if (consts39) {
+    std::memcpy(consts39, cam.cam.c, 16 * sizeof(float));
+    const float rest[7] = {cam.origin.x, cam.origin.y, cam.origin.z, cam.vw, cam.vh, cam.llx, cam.lly};
+    std::memcpy(consts39 + 16, rest, sizeof rest);
+    std::memcpy(consts39 + 23, inv_m.c, 16 * sizeof(float));
+  }
+  for (uint32_t ty = 0; ty < tiles_y; ++ty)
+    for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+      const float x0 = (float)(tx * kBeamTile) - 0.05f, x1 = (float)((tx + 1u) * kBeamTile) + 0.05f;
+      const float y0 = (float)(ty * kBeamTile) - 0.05f, y1 = (float)((ty + 1u) * kBeamTile) + 0.05f;
+      const beam_rules::Frustum fr = beam_rules::tile_frustum(cam.cam, cam.origin, cam.llx, cam.lly, cam.vw, cam.vh, cam.width, cam.height, inv_m, x0, x1, y0, y1);
+      float* e = frusta_out + ((size_t)ty * tiles_x + tx) * 16u;
+      const float rec[16] = {fr.eye.x, fr.eye.y, fr.eye.z, fr.usable ? 1.0f : 0.0f, fr.n[0].x, fr.n[0].y, fr.n[0].z, fr.n[1].x, fr.n[1].y, fr.n[1].z,
+                             fr.n[2].x, fr.n[2].y, fr.n[2].z, fr.n[3].x, fr.n[3].y, fr.n[3].z};
+      std::memcpy(e, rec, sizeof rec);
+    }
+  return (int)(tiles_x * tiles_y);
 }
 
 // The ray feed of the persistent traversal launches (BatchFeed; pt_feed_rules.hpp) checked on the host: a frame of n rays,

@@ -620,6 +620,12 @@ int ptc_check_frame_plan(uint32_t width, uint32_t height, int frames_in_flight, 
  * entries_out (may be NULL): the entries themselves, [tiles][4][8 floats] = {box min, reference bits} {box max, 0}. */
 int ptc_check_beam(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count, const float* object_m16,
                    const ptc_camera* camera, uint32_t width, uint32_t height, uint32_t stride, uint64_t* stats5, float* entries_out);
+/* Host only, no GPU: the tile frustums ptc_check_beam and k_beam cull with, by themselves (the same shared rule, no mesh).  Per tile
+ * 16 floats into frusta_out [tiles][16]: eye.xyz, usable (1 or 0), then the normals of the left, right, top and bottom plane; into
+ * consts39 (may be NULL) the binary32 constants the rule read: camera matrix (16, column-major), its origin (3), viewport width and
+ * height, lower-left x and y, the object's inverse matrix (16).  Returns the number of tiles or a negative status. */
+int ptc_check_beam_frustum(const float* object_m16, const ptc_camera* camera, uint32_t width, uint32_t height, float* frusta_out,
+                           uint64_t capacity_floats, float* consts39);
 /* Test hook: the same entries as k_beam computes them on the GPU for the uploaded scene's first traversal launch. */
 int ptc_debug_beam_entries(ptc_ctx* ctx, const ptc_camera* camera, float* entries_out, uint64_t capacity_floats);
 /* Test hook: the per-lane form of a sphere run (csrc/pt_kernels_common.inc: sphere_run_lanes, what the kernels that end a bounce

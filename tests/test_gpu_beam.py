@@ -3,7 +3,9 @@ nodes of the launch's tree its frustum overlaps, and they start there instead of
 changes, so every frame must stay the oracle's bits -- checked here where the pre-pass has something to get wrong: the
 entries themselves against the host's (pt_beam_rules.hpp runs on both sides: same bits), a mesh under a rotation and a
 non-uniform scale, a camera inside the mesh, frames of one batch with different cameras (one set of entries per distinct
-camera), frame sizes that are no multiple of the tile, the interleaved multi-GPU rows (a slot is another pixel there)."""
+camera), frame sizes that are no multiple of the tile, the interleaved multi-GPU rows (a slot is another pixel there).  The cameras
+here are ordinary ones; the camera's range -- telephoto views, degenerate vertical fields, scaled quaternions, far eyes, hostile object
+matrices -- and the entry cache are tests/test_gpu_camera_range.py's."""
 import ctypes as C
 
 import numpy as np
