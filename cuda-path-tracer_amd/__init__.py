@@ -4,7 +4,7 @@ The directory name contains a hyphen, so it is imported through ``__graft_entry_
 under the module name ``cuda_path_tracer_amd``.  All rendering happens in ``libptcore.so``
 (``csrc/``, C ABI in ``include/ptcore.h``); the Python files are the host-side mirror of the reference's
 ``PathTracer`` / ``SceneDescription`` interface used by the tests and by bench.py."""
-from . import _capi, bands, camera_controller, glmlite, json_parser, scenes, viewer
+from . import _capi, bands, camera_controller, glmlite, hdr, json_parser, scenes, viewer
 from ._capi import LIB_PATH, PtcError, lib
 from .path_tracer import LIGHT_DTYPE, DisplayBufferType, EdgeAvoidingATrousDenoiser, GPUMethod, PathTracer, light_table
 from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, EmissiveMaterial, FlatScene, Mesh, MetalMaterial,
@@ -12,4 +12,4 @@ from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, Emis
 
 __all__ = ["PathTracer", "GPUMethod", "DisplayBufferType", "EdgeAvoidingATrousDenoiser", "SceneDescription", "Camera",
            "Sphere", "Mesh", "DiffuseMateral", "MetalMaterial", "DielectricMaterial", "EmissiveMaterial", "FlatScene", "bvh_from_mesh",
-           "light_table", "LIGHT_DTYPE", "scenes", "bands", "glmlite", "json_parser", "lib", "LIB_PATH", "PtcError"]
+           "light_table", "LIGHT_DTYPE", "scenes", "bands", "glmlite", "hdr", "json_parser", "lib", "LIB_PATH", "PtcError"]

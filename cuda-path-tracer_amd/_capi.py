@@ -206,6 +206,12 @@ SIGNATURES = {
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ptc_selftest_rng": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptc_check_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ptc_set_environment": (C.c_int, [_P, C.c_void_p, C.c_uint32]),
+    "ptc_get_environment": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "ptc_sample_environment": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ptc_environment_from_equirect": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]),
+    "ptc_check_environment": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ptc_check_environment_apron": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
 }
 
 _lib = None

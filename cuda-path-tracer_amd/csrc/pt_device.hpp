@@ -9,6 +9,7 @@
 
 #include "../../include/ptcore.h"
 #include "pt_math.hpp"
+#include "pt_env.hpp"
 
 namespace pt {
 
@@ -209,6 +210,14 @@ struct DLens {
   float radius, focus;
 };
 
+// The environment (ptc_set_environment): the context's octahedral HDR map with its apron, (n + 2) x (n + 2) texels
+// {r, g, b, 0}, row-major (pt_env.hpp).  A kernel argument of the environment instances alone; texels null: no environment, the
+// host launches the gradient's instances and nothing reads this.
+struct DEnv {
+  const float4* texels;
+  uint32_t n, pad;
+};
+
 // Live-path state, 40 B/path in three arrays (round 5; 48 until then: a float4 of its own for the throughput, two words unused --
 // the kernels that end a bounce are HBM-bound and read and write every word of it):
 //   o4 = origin.xyz, bits(pixel | tmin_flag<<31)   tmin_flag: t_min is 1e-5 (after a dielectric) instead of 1e-4
@@ -368,7 +377,8 @@ void launch_raygen(hipStream_t s, const DCameras& cams, const DBatchInfo& bi, DB
                    DPaths paths, DeviceCounters* counters, const DObject* objects = nullptr, uint32_t filt_begin = 0u,
                    uint32_t filt_end = 0u, uint32_t* worklist = nullptr, DHits hits = DHits{nullptr, nullptr},
                    unsigned long long* tile_desc = nullptr, uint32_t tile_stride = 0u, uint32_t epoch = 0u,
-                   bool finish_misses = false, DFrame fb = DFrame{nullptr, nullptr}, bool staged = false, DLens lens = DLens{0.0f, 0.0f});
+                   bool finish_misses = false, DFrame fb = DFrame{nullptr, nullptr}, bool staged = false, DLens lens = DLens{0.0f, 0.0f},
+                   DEnv env = DEnv{nullptr, 0u, 0u});
 // variant 0: reference-order traversal (k_trace); 1: culled near-first traversal over the wide layout (k_trace_wide)
 void launch_trace(hipStream_t s, const DScene& scene, DPaths paths, DHits hits, uint32_t max_paths, int bounce,
                   DeviceCounters* counters, bool count_tests, int variant);
@@ -413,7 +423,7 @@ void launch_scan(hipStream_t s, int bounce, bool last_bounce, const uint32_t* ch
 void launch_shade(hipStream_t s, const DScene& scene, DPaths in, DPaths out, DHits hits, uint32_t max_paths,
                   bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                   const uint32_t* chunk_offsets, DFrame fb, DBand band, DeviceCounters* counters, uint8_t* octs,
-                  const DBatchInfo& bi, bool emitters = false, bool roulette = false);
+                  const DBatchInfo& bi, bool emitters = false, bool roulette = false, DEnv env = DEnv{nullptr, 0u, 0u});
 // the end of a bounce in one pass (k_shade_fused): trailing sphere run [obj_begin, obj_end) + material + stable compaction +
 // final gather.  tile_desc: shade_tiles_per_frame(max_paths) descriptors per frame of the batch (tile_stride apart), zero
 // at allocation, cleared again only when the epochs start over; epoch: a number no earlier launch of this lap has used (1 .. 2^30 - 1).
@@ -423,7 +433,21 @@ void launch_shade_fused(hipStream_t s, const DScene& scene, uint32_t obj_begin, 
                         DHits hits, uint32_t max_paths, bool staged, int bounce, bool last_bounce, const uint32_t* slot_base,
                         unsigned long long* tile_desc, uint32_t tile_stride, uint32_t epoch, DFrame fb, DBand band,
                         DeviceCounters* counters, uint8_t* octs, const DBatchInfo& bi, const uint32_t* list = nullptr,
-                        const DNextRun* next = nullptr, bool emitters = false, bool roulette = false);
+                        const DNextRun* next = nullptr, bool emitters = false, bool roulette = false, DEnv env = DEnv{nullptr, 0u, 0u});
+// The environment (ptc_set_environment; pt_env.hip).  env.texels != null: launch_raygen (where it finishes the
+// unlisted rays), launch_shade and launch_shade_fused hand over to these, the environment's instances of the same kernels, built with
+// kEmit on; launch_env_sample: the lookup on `count` directions (three floats each, device memory), three floats out each
+void launch_raygen_env(hipStream_t s, const DCameras& cams, const DBatchInfo& bi, DBand band, uint32_t pix_count, DPaths paths,
+                       DeviceCounters* counters, const DObject* objects, uint32_t filt_begin, uint32_t filt_end, uint32_t* worklist, DHits hits,
+                       unsigned long long* tile_desc, uint32_t tile_stride, uint32_t epoch, DFrame fb, bool staged, DLens lens, DEnv env);
+void launch_shade_env(hipStream_t s, const DScene& scene, DPaths in, DPaths out, DHits hits, uint32_t max_paths, bool staged, int bounce,
+                      bool last_bounce, const uint32_t* slot_base, const uint32_t* chunk_offsets, DFrame fb, DBand band, DeviceCounters* counters,
+                      uint8_t* octs, const DBatchInfo& bi, bool roulette, DEnv env);
+void launch_shade_fused_env(hipStream_t s, const DScene& scene, uint32_t obj_begin, uint32_t obj_end, bool first, DPaths in, DPaths out, DHits hits,
+                            uint32_t max_paths, bool staged, int bounce, bool last_bounce, const uint32_t* slot_base, unsigned long long* tile_desc,
+                            uint32_t tile_stride, uint32_t epoch, DFrame fb, DBand band, DeviceCounters* counters, uint8_t* octs,
+                            const DBatchInfo& bi, const uint32_t* list, const DNextRun* next, bool roulette, DEnv env);
+void launch_env_sample(hipStream_t s, DEnv env, const float* dirs, uint32_t count, float* out);
 // "prefold" at bounce 0: ray generation that also walks the sphere run in front of bounce 0's first mesh launch (next.hits: the
 // CURRENT bounce's records here) and leaves the bytes for launch_list_flags
 void launch_raygen_next(hipStream_t s, const DScene& scene, const DCameras& cams, const DBatchInfo& bi, DBand band, uint32_t pix_count, DPaths paths,
@@ -451,6 +475,12 @@ void launch_megakernel_roulette(hipStream_t s, const DScene& scene, const DCamer
 // plays (roulette: the context's parameter; 1 <= roulette < max_bounces - 1 is decided here), the roulette one, with primary_ray<true>
 void launch_megakernel_lens(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
                             int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette, DLens lens);
+// ... for a frame with an environment (env.texels != null, the caller's check): the plain loop, or (lights.records !=
+// null: a "direct_light" frame's lamp table, with `stats`) the direct-lit one; pinhole or lens, emitters or none, roulette or none
+struct DLights;
+void launch_megakernel_env(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
+                           uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
+                           DLens lens, DEnv env);
 void launch_preview(hipStream_t s, const float4* buf, uint32_t pix_count, int mode, uint32_t* rgba);
 void launch_pack(hipStream_t s, const float4* buf, uint32_t pix_count, int which, float* dst);
 // the bands of one multi-GPU gather launch (k_gather_bands): up to kGatherBands sources per launch

@@ -583,6 +583,21 @@ __device__ __forceinline__ f3 background(const f3 dir)
   return mk3(0.5f, 0.7f, 1.0f) * (1.0f - t) + mk3(1.0f, 1.0f, 1.0f) * t;  // glm::lerp = x*(1-a) + y*a
 }
 
+// What a path that leaves the scene in direction `dir` (not normalised) sees.  Without kEnv: background(), and `env` is not read --
+// the instances are what they were.  kEnv (ptc_set_environment, an extension; DESIGN section 5j): the context's octahedral map,
+// env_rules::lookup (pt_env.hpp) -- four 16-byte loads issued together, two lerps per component, nothing normalised.
+template <bool kEnv>
+__device__ __forceinline__ f3 sky(const f3 dir, const DEnv env)
+{
+  if constexpr (kEnv) {
+    f3 v;
+    env_rules::lookup(env.texels, env.n, dir.x, dir.y, dir.z, v.x, v.y, v.z);
+    return v;
+  } else {
+    return background(dir);
+  }
+}
+
 __device__ __forceinline__ f3 random_on_unit_sphere(Minstd& rng)
 {
   const float phi = 2.f * 3.14159265358979323846264338327950288f * rng.uniform();
@@ -681,11 +696,13 @@ __device__ __forceinline__ void evaluate_material(f3& ro, f3& rd, bool& tmin_fla
 // kind: 0 diffuse, 1 metal, 2 dielectric (Material::type), 3 miss, 4 emissive (kEmit instances only: material type 3, which
 // the caller maps to kKindEmit -- its material's type would read as "miss" here), anything else: nothing to do.  An emissive
 // hit makes no draw and touches neither ray nor tmin_flag: the path ends with color * emission (emit_color).
+// kEnv (DESIGN section 5j): a miss takes the environment, sky<true>(rd, env), which wants no normalised direction: kind 3 then shares
+// nothing with the other kinds but its branch.
 constexpr uint32_t kKindMiss = 3u, kKindEmit = 4u, kKindNone = 5u;  // (kKindNone: a path roulette has ended, section 5h)
-template <bool kEmit = false>
+template <bool kEmit = false, bool kEnv = false>
 __device__ __forceinline__ void shade_kinds(const uint32_t kind, f3& ro, f3& rd, bool& tmin_flag, const f3 hp, const f3 hn,
                                             const uint32_t side, const DMaterial m, const uint32_t slot, const uint32_t iteration,
-                                            const uint32_t bounce, f3& color)
+                                            const uint32_t bounce, f3& color, const DEnv env = DEnv{nullptr, 0u, 0u})
 {
   float u1 = 0.0f, u2 = 0.0f;
   if (kind <= 2u) {
@@ -697,7 +714,7 @@ __device__ __forceinline__ void shade_kinds(const uint32_t kind, f3& ro, f3& rd,
   }
   if (kind <= 1u) ro = hp - hn * (1e-4f * sign_of(dot(rd, hn)));
   f3 unit = rd;
-  if (kind == 2u || kind == 3u) unit = normalize(rd);
+  if (kind == 2u || (!kEnv && kind == 3u)) unit = normalize(rd);
   float cos_theta = 0.0f, sin_theta = 0.0f;
   if (kind <= 2u) {
     cos_theta = kind <= 1u ? 2.f * u2 - 1.f : sel_min(dot(-unit, hn), 1.0f);
@@ -744,8 +761,12 @@ __device__ __forceinline__ void shade_kinds(const uint32_t kind, f3& ro, f3& rd,
     rd = dir;
     tmin_flag = true;
   } else if (kind == 3u) {
-    const float t = 0.5f * (unit.y + 1.0f);  // background(), path_tracer.cu:29-34
-    color = color * (mk3(0.5f, 0.7f, 1.0f) * (1.0f - t) + mk3(1.0f, 1.0f, 1.0f) * t);
+    if constexpr (kEnv) {
+      color = color * sky<true>(rd, env);
+    } else {
+      const float t = 0.5f * (unit.y + 1.0f);  // background(), path_tracer.cu:29-34
+      color = color * (mk3(0.5f, 0.7f, 1.0f) * (1.0f - t) + mk3(1.0f, 1.0f, 1.0f) * t);
+    }
   } else if (kEmit && kind == kKindEmit) {
     color = emit_color(color, m);
   }

@@ -9,6 +9,7 @@
 #include "pt_feed_rules.hpp"
 #include "pt_light_sample.hpp"
 #include <float.h>
+#include <limits.h>
 
 namespace pt {
 
@@ -39,6 +40,18 @@ __global__ __launch_bounds__(kWave) void k_megakernel_direct_lens(DScene sc, DLi
                                          s_stack + threadIdx.x, lens);
 }
 
+// ... with an environment: the plain loop and the direct-lit one, each once -- emitters and roulette compiled in
+// (mega_path: the same bits without them), pinhole or lens by lens.radius
+template <bool kDirect>
+__global__ __launch_bounds__(kWave) void k_megakernel_env(DScene sc, DLights lt, DCamera cam, uint32_t iteration, DBand band, uint32_t pix_count,
+                                                          int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats,
+                                                          int roulette, DLens lens, DEnv env)
+{
+  __shared__ uint32_t s_stack[kStackDepth * kWave];
+  mega_path<true, true, kDirect, false, true>(sc, lt, cam, iteration, band, pix_count, max_bounces, fb, counters, stats, roulette,
+                                              s_stack + threadIdx.x, lens, env);
+}
+
 // the plain megakernel's instances that play roulette (the plain ones: pt_kernels.hip)
 void launch_megakernel_roulette(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
                                 int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette)
@@ -64,6 +77,22 @@ void launch_megakernel_lens(hipStream_t s, const DScene& scene, const DCamera& c
     hipLaunchKernelGGL((k_megakernel_lens<false, true>), grid, block, 0, s, scene, cam, iteration, band, pix_count, max_bounces, fb, counters, roulette, lens);
   else
     hipLaunchKernelGGL((k_megakernel_lens<false, false>), grid, block, 0, s, scene, cam, iteration, band, pix_count, max_bounces, fb, counters, 0, lens);
+}
+
+// a frame with an environment (env.texels != null, the caller's check).  lights: the lamp table of a "direct_light" frame, or null
+// (DLights::records) for the plain loop; roulette: the context's parameter -- a value that plays at no bounce becomes INT_MAX here
+void launch_megakernel_env(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
+                           uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
+                           DLens lens, DEnv env)
+{
+  const dim3 grid((pix_count + kWave - 1u) / kWave), block(kWave);
+  const int plays_from = roulette >= 1 && roulette < max_bounces - 1 ? roulette : INT_MAX;
+  if (lights.records)
+    hipLaunchKernelGGL(k_megakernel_env<true>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters, stats,
+                       plays_from, lens, env);
+  else
+    hipLaunchKernelGGL(k_megakernel_env<false>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters, stats,
+                       plays_from, lens, env);
 }
 
 void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,

@@ -20,11 +20,16 @@
 // kLens (DESIGN section 5i): the primary ray is the thin lens's, primary_ray<true> with `lens`; rng is left where the pinhole leaves it,
 // so every material draw is the pinhole render's.  The lens instances (k_megakernel_lens, k_megakernel_direct_lens) live in
 // pt_mega_direct.hip.
-template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false>
+// kEnv (ptc_set_environment, DESIGN section 5j): a miss takes the environment, sky<true>(ray.d, env), at every bounce and whatever
+// count_emission says, as the gradient does; the environment is no lamp and draws no light sample.  An environment instance serves
+// pinhole and lens alike -- lens.radius > 0 decides per launch, kLens is not read -- and is built with kEmit and kRoulette on (a scene
+// without emitters meets no emitter; `roulette` >= max_bounces plays at no bounce: the same bits): k_megakernel_env<kDirect>,
+// pt_mega_direct.hip.
+template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false, bool kEnv = false>
 __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, const DCamera& cam, const uint32_t iteration, const DBand band,
                                           const uint32_t pix_count, const int max_bounces, const DFrame fb, DeviceCounters* counters,
                                           unsigned long long* stats, const int roulette, uint32_t* stack,
-                                          const DLens lens = DLens{0.0f, 0.0f})
+                                          const DLens lens = DLens{0.0f, 0.0f}, const DEnv env = DEnv{nullptr, 0u, 0u})
 {
   static_assert(kEmit || !kDirect, "direct lighting: launched only for a scene with a lamp table, so with an emissive material");
   const uint32_t s = blockIdx.x * kWave + threadIdx.x;
@@ -34,7 +39,12 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
     const uint32_t pixel = band_pixel(band, s);
     Minstd rng;
     Ray ray;
-    primary_ray<kLens>(cam, pixel, iteration, rng, ray, lens);
+    if constexpr (kEnv) {
+      if (lens.radius > 0.0f) primary_ray<true>(cam, pixel, iteration, rng, ray, lens);
+      else primary_ray<false>(cam, pixel, iteration, rng, ray);
+    } else {
+      primary_ray<kLens>(cam, pixel, iteration, rng, ray, lens);
+    }
     f3 color = mk3(1.0f, 1.0f, 1.0f);
     f3 radiance = mk3(0.0f, 0.0f, 0.0f);
     bool count_emission = true;  // the last vertex drew no light sample (the camera, metal, glass): a lamp hit from it counts
@@ -49,7 +59,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       ++rays;
       Tally tally;
       if (!ray_scene<false>(ray, sc, rec, stack, flags, tally)) {
-        color = color * background(ray.d);
+        color = color * sky<kEnv>(ray.d, env);
         break;
       }
       if (i == 0) {

@@ -4,14 +4,29 @@
 // take a trailing DLens and call primary_ray<true>; everything behind the primary ray is the same text.  (An include and not a
 // device function both kernels call: inlined one level down the pinhole kernels came out with other instructions -- the xors of
 // path_seed associated differently -- and the pinhole instances are to stay the ones they were.)
-#if PT_RAYGEN_LENS
+// A third time by pt_env.hip, with PT_RAYGEN_LENS 2: the environment's k_raygen_env<kFilter, kFinish> (ptc_set_environment, DESIGN
+// section 5j), whose finishing miss takes sky<true>(d, env).  It takes a trailing DLens and DEnv and serves pinhole and lens alike
+// (lens.radius > 0 decides per launch: primary_ray<true> or primary_ray, each its own operations); only <true, true> touches the
+// sky, so only that instance exists, and k_raygen_next, which touches none, has no environment form.
+#if PT_RAYGEN_LENS == 2
+#define PT_RAYGEN_NAME(name) name##_env
+#define PT_RAYGEN_LENS_PARAM , DLens lens, DEnv env
+#define PT_RAYGEN_PRIMARY(cam, pixel, iteration, rng, ray)                          \
+  do {                                                                              \
+    if (lens.radius > 0.0f) primary_ray<true>(cam, pixel, iteration, rng, ray, lens); \
+    else primary_ray(cam, pixel, iteration, rng, ray);                              \
+  } while (0)
+#define PT_RAYGEN_SKY(d) sky<true>(d, env)
+#elif PT_RAYGEN_LENS
 #define PT_RAYGEN_NAME(name) name##_lens
 #define PT_RAYGEN_LENS_PARAM , DLens lens
 #define PT_RAYGEN_PRIMARY(cam, pixel, iteration, rng, ray) primary_ray<true>(cam, pixel, iteration, rng, ray, lens)
+#define PT_RAYGEN_SKY(d) background(d)
 #else
 #define PT_RAYGEN_NAME(name) name
 #define PT_RAYGEN_LENS_PARAM
 #define PT_RAYGEN_PRIMARY(cam, pixel, iteration, rng, ray) primary_ray(cam, pixel, iteration, rng, ray)
+#define PT_RAYGEN_SKY(d) background(d)
 #endif
 
 // raygen_kernel, ray_gen.cu:11-32.  Slot s of this context holds pixel band_pixel(band, s).
@@ -67,7 +82,7 @@ __global__ __launch_bounds__(256) void PT_RAYGEN_NAME(k_raygen)(DCameras cams, D
     }
     if (kFinish && !may_hit) {
       const uint32_t local_pixel = band_local(band, pixel);
-      const f3 color = mk3(1.0f, 1.0f, 1.0f) * background(d);
+      const f3 color = mk3(1.0f, 1.0f, 1.0f) * PT_RAYGEN_SKY(d);
       accumulate_nd(fb.nd4, local_pixel, acc_iteration, -d, 1e6f);
       accumulate_color(fb.color4, local_pixel, acc_iteration, color);
       continue;
@@ -85,6 +100,7 @@ __global__ __launch_bounds__(256) void PT_RAYGEN_NAME(k_raygen)(DCameras cams, D
 // primary ray is in registers: k_spheres<first, filter>'s work for it -- the run, the hit or miss record, the byte that says
 // whether it goes on the mesh launch's work list (shade_tile<.., kNext> does the same for the later bounces) -- is done here, and
 // bounce 0 starts with k_list_flags.
+#if PT_RAYGEN_LENS != 2
 __global__ __launch_bounds__(256) void PT_RAYGEN_NAME(k_raygen_next)(DScene sc, DCameras cams, DBatchInfo bi, DBand band, uint32_t pix_count, DPaths paths,
                                                      DeviceCounters* counters, DNextRun next PT_RAYGEN_LENS_PARAM)
 {
@@ -121,7 +137,9 @@ __global__ __launch_bounds__(256) void PT_RAYGEN_NAME(k_raygen_next)(DScene sc, 
     next.flags[s] = may_hit_boxes(sc.objects, next.filt_begin, next.filt_end, ray.o, ray.d, ray.tmax) ? (uint8_t)1 : (uint8_t)0;
   }
 }
+#endif
 
 #undef PT_RAYGEN_NAME
+#undef PT_RAYGEN_SKY
 #undef PT_RAYGEN_LENS_PARAM
 #undef PT_RAYGEN_PRIMARY

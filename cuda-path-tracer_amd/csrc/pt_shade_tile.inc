@@ -85,15 +85,17 @@ __device__ __forceinline__ bool goes_on(const DScene& sc, const uint32_t mat_wor
 // already divided for a roulette survivor.
 // True: the path survives with its new ray in ro, rd, tmin_flag and its throughput in color.  False: it ended and its sample is
 // in `fb` (staged: acc_iteration 0) -- miss: throughput * sky; emitter: throughput * emission, no draw; roulette: 0, no draw;
-// the last bounce: the raw throughput.
+// the last bounce: the raw throughput.  env (DESIGN section 5j): null, or the environment that is the sky of a miss, sky<true> -- the
+// caller's constant, decided where this is inlined.  (Not a template parameter: as a template this function gave k_shade's four
+// instances other instructions.)
 __device__ __forceinline__ bool bounce_outcome(const DScene& sc, const DFrame& fb, const uint32_t local_pixel, const uint32_t acc_iteration,
                                                const int bounce, const int last_bounce, const uint32_t slot, const uint32_t iteration,
                                                const bool hit, const float4 tp, const float4 nm, const bool emits, const bool ended,
-                                               f3& ro, f3& rd, bool& tmin_flag, f3& color)
+                                               f3& ro, f3& rd, bool& tmin_flag, f3& color, const DEnv* env = nullptr)
 {
   if (!hit) {
     // miss: throughput *= sky; the path ends (path_tracer.cu:304-307, 283-289)
-    color = color * background(rd);
+    color = color * (env ? sky<true>(rd, *env) : background(rd));
     if (bounce == 0) accumulate_nd(fb.nd4, local_pixel, acc_iteration, -rd, 1e6f);  // raygen defaults, ray_gen.cu:26-28
     accumulate_color(fb.color4, local_pixel, acc_iteration, color);
     return false;
@@ -141,14 +143,17 @@ __device__ __forceinline__ void pack_survivor(const f3 ro, const f3 rd, const f3
 // the throughput that came into the bounce (d4.w, t2) is loaded with the ray, the roulette stream's draw is made in phase 1 and
 // a survivor's division is applied to the registers phase 2 reads its throughput from; a path that ends is remembered for phase
 // 2, which gives it no material draw and the sample (0, 0, 0).  The count still goes out after one round trip.
-template <bool kSpheres, bool kFirst, int kGroupWaves, bool kCoherent, bool kNext = false, bool kEmit = false, bool kRoulette = false>
+// kEnv: the frame has an environment (ptc_set_environment, DESIGN section 5j; the host picks the instance): a miss multiplies the
+// throughput by the map's value in the ray's direction (`env`) where the gradient stands otherwise.  Only colour differs.
+template <bool kSpheres, bool kFirst, int kGroupWaves, bool kCoherent, bool kNext = false, bool kEmit = false, bool kRoulette = false, bool kEnv = false>
 __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_begin, const uint32_t obj_end, const DPaths in, const DPaths out,
                                            const DHits hits, const int staged, const int bounce, const int last_bounce, const uint32_t* slot_base,
                                            unsigned long long* tile_desc, const uint32_t epoch, const DFrame fb, const DBand band,
                                            DeviceCounters* counters, uint8_t* octs, const uint32_t iteration, const uint32_t* list, const size_t fo,
                                            const uint32_t tile, const uint32_t tiles, const uint32_t n, const uint32_t n_all, uint32_t* s_cnt,
-                                           uint32_t* s_excl, const DNextRun* next = nullptr)
+                                           uint32_t* s_excl, const DNextRun* next = nullptr, const DEnv env = DEnv{nullptr, 0u, 0u})
 {
+  static_assert(!kEnv || !kCoherent, "environment: the per-bounce launches (k_persist is not taught it)");
   static_assert(!kNext || (!kCoherent && !kFirst), "prefold: the per-bounce launches, behind a bounce that had a closest-hit launch");
   static_assert(!kRoulette || !kCoherent, "roulette: the per-bounce launches (k_persist is not taught it)");
   constexpr uint32_t kThreads = 64u * (uint32_t)kGroupWaves, kTile = kThreads * (uint32_t)kFuseK;
@@ -274,8 +279,8 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
         else accumulate_nd(fb.nd4, local_pixel, acc_iteration, -rd, 1e6f);           // raygen defaults, ray_gen.cu:26-28
       }
       const uint32_t slot = (slot_base ? *slot_base : 0u) + s;
-      shade_kinds<kEmit>(ended ? kKindNone : emits ? kKindEmit : (uint32_t)m.type, ro, rd, tmin_flag, mk3(tp[j].y, tp[j].z, tp[j].w), hn, ms >> 31, m, slot,
-                         iteration, (uint32_t)bounce, color);
+      shade_kinds<kEmit, kEnv>(ended ? kKindNone : emits ? kKindEmit : (uint32_t)m.type, ro, rd, tmin_flag, mk3(tp[j].y, tp[j].z, tp[j].w), hn, ms >> 31, m,
+                               slot, iteration, (uint32_t)bounce, color, env);
       if (ended) color = mk3(0.0f, 0.0f, 0.0f);
       if (!is_hit || last_bounce || emits || ended) {
         // a miss ends the path with throughput * sky (path_tracer.cu:304-307, 283-289), an emitter with throughput * emission;
@@ -291,7 +296,7 @@ __device__ __forceinline__ void shade_tile(const DScene& sc, const uint32_t obj_
       const bool is_hit = (hit_mask >> j & 1u) != 0u;  // (emits, ended: what phase 1 counted by)
       const bool emits = kEmit && is_hit && is_emitter(sc.materials[__float_as_uint(nm[j].w) & 0x7fffffffu]);
       if (bounce_outcome(sc, fb, local_pixel, acc_iteration, bounce, last_bounce, (slot_base ? *slot_base : 0u) + s, iteration, is_hit, tp[j], nm[j],
-                         emits, kRoulette && (ended_mask >> j & 1u) != 0u, ro, rd, tmin_flag, color)) {
+                         emits, kRoulette && (ended_mask >> j & 1u) != 0u, ro, rd, tmin_flag, color, kEnv ? &env : nullptr)) {
         surv_mask |= 1u << j;
         pack_survivor(ro, rd, color, pixel, tmin_flag, o4[j], d4[j], t2[j]);
       }

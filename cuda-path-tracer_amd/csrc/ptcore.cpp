@@ -463,6 +463,7 @@ void ptc_destroy(ptc_ctx* ctx)
     if (e) (void)hipEventDestroy(e);
   if (ctx->misc_counters) (void)hipFree(ctx->misc_counters);
   if (ctx->loop_stats) (void)hipFree(ctx->loop_stats);
+  if (ctx->env.texels) (void)hipFree(const_cast<float4*>(ctx->env.texels));
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -599,6 +600,95 @@ int ptc_get_lens(ptc_ctx* ctx, float* lens_radius, float* focus_distance)
   if (!ctx || !lens_radius || !focus_distance) return PTC_ERR_INVALID;
   *lens_radius = ctx->lens.radius;
   *focus_distance = ctx->lens.focus;
+  return PTC_OK;
+}
+
+// The environment.  Everything that can refuse comes before the context changes: the map that was set stays in
+// place after any refusal.  The new map is uploaded into an allocation of its own and the old one freed only then; frames in flight
+// have read the old one by the time sync_frames returns.
+int ptc_set_environment(ptc_ctx* ctx, const float* rgb, uint32_t n)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (int rc = flush_pending(ctx)) return rc;  // a batch renders under one environment
+  float4* dev = nullptr;
+  if (rgb && n != 0u) {
+    if (n < env_rules::kMinSize || n > env_rules::kMaxSize)
+      return fail(ctx, PTC_ERR_INVALID, "environment size must be in [2,4096], got " + std::to_string(n));
+    const size_t comps = 3u * (size_t)n * n;
+    for (size_t k = 0; k < comps; ++k)
+      if (!(rgb[k] >= 0.0f) || !std::isfinite(rgb[k])) {
+        const size_t texel = k / 3u;
+        return fail(ctx, PTC_ERR_INVALID, "environment texel (row " + std::to_string(texel / n) + ", column " + std::to_string(texel % n) + ") component " +
+                                              std::to_string(k % 3u) + " must be finite and not negative, got " + std::to_string(rgb[k]));
+      }
+    if (int rc = bind_device(ctx)) return rc;
+    const size_t texels = (size_t)(n + 2u) * (n + 2u);
+    std::vector<float4> host(texels);
+    env_rules::apron(rgb, n, host.data());
+    if (hipMalloc(reinterpret_cast<void**>(&dev), texels * sizeof(float4)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, PTC_ERR_OOM, "hipMalloc(environment, " + std::to_string(texels * sizeof(float4)) + " bytes) failed");
+    }
+    const hipError_t e = hipMemcpy(dev, host.data(), texels * sizeof(float4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(dev);
+      return fail(ctx, PTC_ERR_HIP, std::string("environment upload: ") + hipGetErrorString(e));
+    }
+  } else if (int rc = bind_device(ctx)) {
+    return rc;
+  }
+  if (ctx->env.texels) {  // the frames that read the old map have to be done with it
+    if (int rc = sync_frames(ctx)) {
+      if (dev) (void)hipFree(dev);
+      return rc;
+    }
+    (void)hipFree(const_cast<float4*>(ctx->env.texels));
+  }
+  ctx->env = DEnv{dev, dev ? n : 0u, 0u};
+  return PTC_OK;
+}
+
+// An equirectangular image to the octahedral map ptc_set_environment takes (host only; float64 inside, not parity-critical).  Per
+// octahedral texel centre: the direction, the image sampled bilinearly at u = atan2(d.x, -d.z) / 2 pi + 0.5 (wrapping) and v =
+// acos(d.y) / pi (clamping) -- the image's centre is the camera's default view direction -z, row 0 is up --, times scale, to binary32.
+// A point sample per texel: a map much smaller than the image skips pixels (a small sun may fall between texels).
+int ptc_environment_from_equirect(const float* rgb, uint32_t width, uint32_t height, uint32_t n, float scale, float* out)
+{
+  if (!rgb || !out || width == 0u || height == 0u || n < env_rules::kMinSize || n > env_rules::kMaxSize) return PTC_ERR_INVALID;
+  if (!std::isfinite(scale) || scale < 0.0f) return PTC_ERR_INVALID;
+  const double pi = 3.14159265358979323846;
+  for (uint32_t j = 0; j < n; ++j)
+    for (uint32_t i = 0; i < n; ++i) {
+      const double qx = 2.0 * (((double)i + 0.5) / (double)n) - 1.0, qz = 2.0 * (((double)j + 0.5) / (double)n) - 1.0;
+      double x = qx, z = qz;
+      const double y = 1.0 - std::fabs(qx) - std::fabs(qz);
+      if (y < 0.0) {  // the lower hemisphere, unfolded (the inverse of env_rules::locate's fold)
+        x = (1.0 - std::fabs(qz)) * (qx < 0.0 ? -1.0 : 1.0);
+        z = (1.0 - std::fabs(qx)) * (qz < 0.0 ? -1.0 : 1.0);
+      }
+      const double len = std::sqrt(x * x + y * y + z * z);
+      const double u = std::atan2(x / len, -z / len) / (2.0 * pi) + 0.5;
+      const double v = std::acos(std::min(1.0, std::max(-1.0, y / len))) / pi;
+      const double fx = u * (double)width - 0.5, fy = v * (double)height - 0.5;
+      const double x0f = std::floor(fx), y0f = std::floor(fy);
+      const double tx = fx - x0f, ty = fy - y0f;
+      const int64_t W = (int64_t)width, Hh = (int64_t)height;
+      const int64_t x0 = (((int64_t)x0f % W) + W) % W, x1 = (x0 + 1) % W;
+      const int64_t y0 = std::min<int64_t>(std::max<int64_t>((int64_t)y0f, 0), Hh - 1), y1 = std::min<int64_t>(std::max<int64_t>((int64_t)y0f + 1, 0), Hh - 1);
+      for (int c = 0; c < 3; ++c) {
+        const double c00 = rgb[3 * (y0 * W + x0) + c], c10 = rgb[3 * (y0 * W + x1) + c];
+        const double c01 = rgb[3 * (y1 * W + x0) + c], c11 = rgb[3 * (y1 * W + x1) + c];
+        const double top = c00 * (1.0 - tx) + c10 * tx, bot = c01 * (1.0 - tx) + c11 * tx;
+        out[3 * ((size_t)j * n + i) + c] = (float)((top * (1.0 - ty) + bot * ty) * (double)scale);
+      }
+    }
+  return PTC_OK;
+}
+
+int ptc_get_environment(ptc_ctx* ctx, uint32_t* n)
+{
+  if (!ctx || !n) return PTC_ERR_INVALID;
+  *n = ctx->env.n;
   return PTC_OK;
 }
 

@@ -502,6 +502,30 @@ int ptc_check_rng(const uint32_t* seeds, const uint32_t* discards, uint32_t n, u
   return PTC_OK;
 }
 
+// The environment's lookup and apron (pt_env.hpp) on the host, as ptc_set_environment + ptc_sample_environment run
+// them: no GPU, no context.  The same refusals as ptc_set_environment's, without a message.
+int ptc_check_environment(const float* rgb, uint32_t n, const float* dirs, uint32_t count, float* rgb_out)
+{
+  if (!rgb || n < env_rules::kMinSize || n > env_rules::kMaxSize) return PTC_ERR_INVALID;
+  if (count != 0u && (!dirs || !rgb_out)) return PTC_ERR_INVALID;
+  for (size_t k = 0; k < 3u * (size_t)n * n; ++k)
+    if (!(rgb[k] >= 0.0f) || !std::isfinite(rgb[k])) return PTC_ERR_INVALID;
+  std::vector<float4> e((size_t)(n + 2u) * (n + 2u));
+  env_rules::apron(rgb, n, e.data());
+  for (uint32_t i = 0; i < count; ++i)
+    env_rules::lookup(e.data(), n, dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u], rgb_out[3u * (size_t)i],
+                      rgb_out[3u * (size_t)i + 1u], rgb_out[3u * (size_t)i + 2u]);
+  return PTC_OK;
+}
+
+// the apron alone: E as ptc_set_environment uploads it, 4 (n + 2)^2 floats
+int ptc_check_environment_apron(const float* rgb, uint32_t n, float* texels_out)
+{
+  if (!rgb || !texels_out || n < env_rules::kMinSize || n > env_rules::kMaxSize) return PTC_ERR_INVALID;
+  env_rules::apron(rgb, n, reinterpret_cast<float4*>(texels_out));
+  return PTC_OK;
+}
+
 // ... and on the device
 int ptc_selftest_rng(ptc_ctx* ctx, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out)
 {

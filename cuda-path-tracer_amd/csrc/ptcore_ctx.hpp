@@ -271,6 +271,9 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   int roulette = 0;
   // the thin lens (ptc_set_lens): radius 0 = the pinhole; every frame of a batch renders with one lens
   DLens lens{0.0f, 1.0f};
+  // the environment (ptc_set_environment): the octahedral map with its apron on the device, or none (texels null:
+  // the gradient, the instances launched as before); the context's own allocation -- it survives ptc_upload_scene and ptc_resize
+  DEnv env{nullptr, 0u, 0u};
   unsigned long long* loop_stats = nullptr;  // device: kLightStatLines lines of kLoopStatWords words (diffuse hits, shadow rays, unoccluded)
   bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
 };

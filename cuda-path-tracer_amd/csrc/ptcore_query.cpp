@@ -496,4 +496,34 @@ int ptc_get_direct_stats(ptc_ctx* ctx, ptc_direct_stats* out)
   return PTC_OK;
 }
 
+// The environment's value in the caller's directions: the device function every miss of a frame calls (sky<true>),
+// on the context's map.  Queued frames are flushed first; no statistics move.
+int ptc_sample_environment(ptc_ctx* ctx, const float* dirs, uint32_t count, float* rgb_out)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (!ctx->env.texels) return fail(ctx, PTC_ERR_INVALID, "no environment is set (ptc_set_environment)");
+  if (count == 0u) return PTC_OK;
+  if (!dirs || !rgb_out) return fail(ctx, PTC_ERR_INVALID, "dirs or rgb_out is NULL");
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = flush_pending(ctx)) return rc;
+  std::vector<void*> pool;
+  float *d_dirs = nullptr, *d_out = nullptr;
+  int rc = dev_alloc(ctx, pool, &d_dirs, 3u * (size_t)count);
+  if (!rc) rc = dev_alloc(ctx, pool, &d_out, 3u * (size_t)count);
+  if (rc) {
+    free_pool(pool);
+    return rc;
+  }
+  hipError_t e = hipMemcpyAsync(d_dirs, dirs, 3u * (size_t)count * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    launch_env_sample(ctx->stream, ctx->env, d_dirs, count, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(rgb_out, d_out, 3u * (size_t)count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  free_pool(pool);
+  if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("sample environment: ") + hipGetErrorString(e));
+  return PTC_OK;
+}
+
 }  // extern "C"

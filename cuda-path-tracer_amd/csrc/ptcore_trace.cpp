@@ -84,6 +84,12 @@ bool lens_frame(const ptc_ctx* ctx) { return ctx->lens.radius > 0.0f; }
 // ... what the launchers of ray generation get: the context's lens, or the pinhole's "no lens"
 DLens frame_lens(const ptc_ctx* ctx) { return lens_frame(ctx) ? ctx->lens : DLens{0.0f, 0.0f}; }
 
+// The environment (ptc_set_environment): a frame rendered now meets the context's map wherever a path leaves the
+// scene -- the kernels that end a bounce, a finishing ray generation, the megakernel launch their environment instances (built with
+// emitters compiled in: the same bits without any) -- and is not eligible for the persistent launch.  Without a map: what was
+// launched before it existed.
+bool env_frame(const ptc_ctx* ctx) { return ctx->env.texels != nullptr; }
+
 // ---- the decisions of the launch plan (ptc_ctx::TraceLaunch), each in one place -------------------------------------------
 
 // What opens the object list: a traversal launch with nothing in front of it, a sphere run in front of the first traversal
@@ -213,7 +219,7 @@ int batch_begin(ptc_ctx* ctx, const ptc_ctx::Pending* items, int count)
   } else {
     launch_raygen(sl.stream, cams, sl.bi, ctx->band, ctx->pix_count, sl.paths[0], sl.counters, ctx->scene.objects, first_mesh, filt_end,
                   sl.first_listed ? sl.worklist : nullptr, sl.hits, sl.tile_desc, sl.tile_stride, next_epoch(sl), sl.primary_finished,
-                  sl.stage, ctx->staged, frame_lens(ctx));
+                  sl.stage, ctx->staged, frame_lens(ctx), ctx->env);
   }
   if (int rc = check_last(ctx, "raygen")) return rc;
   // "beam": when bounce 0 opens with a launch over ONE mesh object (k_traverse4), its primary rays start at entry points
@@ -327,7 +333,8 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
     const DNextRun next = prefold ? next_run(ctx, sl.hits_other, sl.next_flags) : DNextRun{};
     launch_shade_fused(sl.stream, scene, tail.begin, tail.end, !wrote, in, out, sl.hits, ctx->pix_count, ctx->staged, bounce, last,
                        slot_base_dev, sl.tile_desc, sl.tile_stride, sl.shade_epoch, sl.stage, ctx->band, sl.counters, octs, sl.bi,
-                       bounce == 0 && sl.primary_finished ? sl.worklist : nullptr, prefold ? &next : nullptr, ctx->has_emitters, roulette);
+                       bounce == 0 && sl.primary_finished ? sl.worklist : nullptr, prefold ? &next : nullptr, ctx->has_emitters, roulette,
+                       ctx->env);
     if (prefold) {
       std::swap(sl.hits, sl.hits_other);
       sl.prefolded = true;
@@ -337,7 +344,7 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
                       sl.bi, ctx->has_emitters, roulette, slot_base_dev);
     launch_scan(sl.stream, bounce, last, sl.chunk_counts, sl.chunk_offsets, sl.counters, sl.bi);
     launch_shade(sl.stream, scene, in, out, sl.hits, ctx->pix_count, ctx->staged, bounce, last, slot_base_dev,
-                 sl.chunk_offsets, sl.stage, ctx->band, sl.counters, octs, sl.bi, ctx->has_emitters, roulette);
+                 sl.chunk_offsets, sl.stage, ctx->band, sl.counters, octs, sl.bi, ctx->has_emitters, roulette, ctx->env);
   }
   sl.cur ^= 1;
   sl.bounces_done = bounce + 1;
@@ -349,10 +356,10 @@ int batch_bounce(ptc_ctx* ctx, int bounce, const uint32_t* slot_base_dev)
 // of it, then the kernel that ends the bounce (a sphere run may end the object list) --, the shade pass the fused one, no ray
 // sorting, staged samples, no instrumentation (the counting runs and the per-launch events keep the per-bounce launches:
 // same results), no bounce that plays roulette (k_persist is not taught it, section 5h: the per-bounce launches render such a
-// frame, with the same bits), and slots must fit the 26 bits a lane keeps them in.
+// frame, with the same bits), no environment (section 5j: the same), and slots must fit the 26 bits a lane keeps them in.
 bool persist_ok(const ptc_ctx* ctx, int count)
 {
-  if (!ctx->persist || ctx->trace_variant != 3 || !ctx->fused_shade || ctx->ray_sort || !ctx->staged || roulette_frame(ctx)) return false;
+  if (!ctx->persist || ctx->trace_variant != 3 || !ctx->fused_shade || ctx->ray_sort || !ctx->staged || roulette_frame(ctx) || env_frame(ctx)) return false;
   if (ctx->count_tests || ctx->max_bounces < 2 || count < (int)ctx->persist_min_frames) return false;
   if (ctx->launches.size() != 1u || plan_opens(ctx) != Opens::launch || launch_run(ctx, 0) != 1u) return false;
   const auto& sl = ctx->slots[(size_t)ctx->active_slot];
@@ -634,13 +641,20 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
     auto& sl = ctx->slots[0];
     ctx->cam = make_camera(*camera, ctx->width, ctx->height);
     ctx->have_cam = true;
-    if (ctx->direct_light && ctx->light_records) {  // a lamp table of total weight > 0; without one: the plain instances, the same bits
+    const bool direct = ctx->direct_light && ctx->light_records;  // a lamp table of total weight > 0; without one: the plain instances, the same bits
+    DLights lights{};
+    if (direct) {
       if (ctx->loop_stats_clear) {
         HIP_TRY(ctx, hipMemsetAsync(ctx->loop_stats, 0, kLoopStatBytes, sl.stream));
         ctx->loop_stats_clear = false;
       }
-      const DLights lights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
-                           ctx->scene.materials};
+      lights = DLights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
+                       ctx->scene.materials};
+    }
+    if (env_frame(ctx)) {  // an environment: its instance of the plain or the direct-lit loop
+      launch_megakernel_env(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,
+                            sl.counters, direct ? ctx->loop_stats : nullptr, ctx->roulette, frame_lens(ctx), ctx->env);
+    } else if (direct) {
       launch_megakernel_direct(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
                                ctx->max_bounces, ctx->fb, sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx));
     } else if (lens_frame(ctx)) {  // the thin lens: the lens instance of the plain or the roulette loop

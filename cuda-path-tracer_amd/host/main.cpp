@@ -3,7 +3,7 @@
 // following the call sequence of execute_cli_version (src/cli/cli.cpp:62-116): read scene, create_buffers,
 // max_iterations = spp, spp x path_trace, synchronize, send_to_preview, write PNG, stage timings.
 // Extra flags: --max-bounces N (the reference's cap is a compile-time 50), --denoise, --method, --gpu,
-// --lens-radius R / --focus-distance F (the thin lens), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
+// --lens-radius R / --focus-distance F (the thin lens), --environment FILE / --environment-scale S / --environment-size N (environment lighting; --dump-environment FILE: the decoded picture and the map, for tests, no GPU), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
 // (DisplayBufferType of send_to_preview, path_tracer.cu:487-520: which buffer the PNG shows), --dump-raw FILE (the
 // accumulated float framebuffers as they are: "PTRF", width, height, 7 as uint32, then colour rgb, normal xyz and
 // depth planes as float32).  Without -o the reference opens its GLFW viewer; this build is headless and says so.
@@ -52,6 +52,10 @@ struct CliConfigurations {  // configurations.hpp:11-15
   bool direct_light = false;
   int roulette = 0;
   std::optional<float> lens_radius, focus_distance;  // the thin lens (override the scene file's camera keys)
+  // environment lighting (override the scene file's "environment" key, each on its own)
+  std::optional<std::string> environment, dump_environment;
+  std::optional<float> environment_scale;
+  std::optional<int> environment_size;
   int gpu = 0;
   int gpus = 1;
   std::optional<std::string> dump_scene;
@@ -75,6 +79,10 @@ void usage()
                "      --roulette K     Russian roulette at every bounce >= K but the last, unbiased (0 = off, the default; K in [0,64])\n"
                "      --lens-radius R  thin lens: aperture radius in world units (0 = pinhole; overrides the scene's \"lens_radius\")\n"
                "      --focus-distance F  thin lens: distance of the plane in focus, > 0 (overrides the scene's \"focus_distance\")\n"
+               "      --environment FILE  environment lighting: an equirectangular Radiance .hdr (overrides the scene's \"environment\")\n"
+               "      --environment-scale S  multiply the picture by S, a finite number >= 0 (default 1)\n"
+               "      --environment-size N  size of the octahedral map made from it, in [2,4096] (default: the picture's height)\n"
+               "      --dump-environment F  test hook: write the decoded picture and the map to F and exit (no GPU needed)\n"
                "      --gpu N          HIP device ordinal\n"
                "      --gpus N         split the frame's rows over N processes / GPUs (rank r on device r %% device count)\n"
                "      --dump-scene F   write the flattened scene to F and exit (no GPU needed)\n"
@@ -129,6 +137,28 @@ CliConfigurations parse_cli_args(int argc, char** argv)
         std::exit(1);
       }
       (radius ? c.lens_radius : c.focus_distance) = x;
+    }
+    else if (a == "--environment") c.environment = need("environment");
+    else if (a == "--dump-environment") c.dump_environment = need("dump-environment");
+    else if (a == "--environment-scale") {
+      const std::string v = need("environment-scale");
+      char* end = nullptr;
+      const float x = std::strtof(v.c_str(), &end);
+      if (v.empty() || *end != '\0' || !std::isfinite(x) || x < 0.0f) {
+        std::fprintf(stderr, "Option '--environment-scale': '%s' is not a finite number >= 0\n", v.c_str());
+        std::exit(1);
+      }
+      c.environment_scale = x;
+    }
+    else if (a == "--environment-size") {
+      const std::string v = need("environment-size");
+      int n = -1;
+      if (!v.empty() && v.size() <= 4 && v.find_first_not_of("0123456789") == std::string::npos) n = std::stoi(v);
+      if (n < 2 || n > 4096) {
+        std::fprintf(stderr, "Option '--environment-size': '%s' is not a number in [2,4096]\n", v.c_str());
+        std::exit(1);
+      }
+      c.environment_size = n;
     }
     else if (a == "--gpu") c.gpu = std::stoi(need("gpu"));
     else if (a == "--gpus") c.gpus = std::stoi(need("gpus"));
@@ -291,6 +321,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   path_tracer.direct_light = configs.direct_light;
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
+  path_tracer.environment = scene_desc.environment;
 
   int shown = 0;
   std::vector<uchar4> buffer;
@@ -397,6 +428,7 @@ try {
   path_tracer.direct_light = configs.direct_light;
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
+  path_tracer.environment = scene_desc.environment;
   path_tracer.create_buffers(resolution, scene_desc);
   auto check = [&](int rc, const char* what) {
     if (rc < 0) throw std::runtime_error(std::string(what) + ": " + ptc_last_error(path_tracer.handle()));
@@ -537,7 +569,7 @@ try {
     std::fprintf(stderr, "Panic: Unsupported file extension %s!\n", path.extension().string().c_str());
     return 1;
   }
-  SceneDescription scene_desc = scene_from_json(path.string());
+  SceneDescription scene_desc = scene_from_json(path.string(), /*read_environment*/ false);  // (the picture: below, once)
   scene_desc.filename = configs.filename;
   if (configs.spp) scene_desc.spp = *configs.spp;
   // the thin lens: the command line over the scene file; a radius > 0 needs a focus distance from one of them (before any GPU is touched)
@@ -546,6 +578,32 @@ try {
   if (scene_desc.camera.lens_radius > 0.0f && !(scene_desc.camera.focus_distance > 0.0f)) {
     std::fprintf(stderr, "hip_pt: a lens radius > 0 needs a focus distance (--focus-distance F, or \"focus_distance\" in the scene's camera)\n");
     return 1;
+  }
+  // environment lighting: the command line over the scene file, value by value; the one picture that counts is read here, once
+  // (before any GPU is touched) -- a scene's own picture that the command line replaces is not opened
+  if ((configs.environment_scale || configs.environment_size) && !configs.environment && scene_desc.environment_source.file.empty()) {
+    std::fprintf(stderr, "hip_pt: --environment-scale / --environment-size need an environment (--environment FILE, or \"environment\" in the scene)\n");
+    return 1;
+  }
+  HdrImage environment_picture;
+  {
+    auto& src = scene_desc.environment_source;
+    if (configs.environment) src.file = *configs.environment;
+    if (configs.environment_scale) src.scale = *configs.environment_scale;
+    if (configs.environment_size) src.size = *configs.environment_size;
+    if (!src.file.empty()) scene_desc.environment = load_environment(src.file, src.scale, src.size, &environment_picture);
+  }
+  if (configs.dump_environment) {
+    if (!scene_desc.environment) {
+      std::fprintf(stderr, "hip_pt: --dump-environment needs an environment (--environment FILE, or \"environment\" in the scene)\n");
+      return 1;
+    }
+    std::ofstream out(*configs.dump_environment, std::ios::binary);
+    const int32_t dims[2] = {environment_picture.width, environment_picture.height};
+    out.write(reinterpret_cast<const char*>(dims), sizeof dims);
+    dump_vec(out, environment_picture.rgb);
+    dump_vec(out, scene_desc.environment->rgb);
+    return 0;
   }
   stopwatch.end_stage("Scene loading");
 
@@ -585,6 +643,7 @@ try {
   path_tracer.direct_light = configs.direct_light;
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
+  path_tracer.environment = scene_desc.environment;
   path_tracer.create_buffers(resolution, scene_desc);
   path_tracer.synchronize();
   std::printf("Start path tracing\nspp: %d\nwidth: %u, height: %u\n", spp, resolution.width, resolution.height);

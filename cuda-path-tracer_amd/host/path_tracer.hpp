@@ -6,6 +6,7 @@
 #pragma once
 
 #include <cstdint>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -46,6 +47,9 @@ public:
     float radius = 0.0f, focus_distance = 1.0f;
     bool operator!=(const Lens& o) const { return radius != o.radius || focus_distance != o.focus_distance; }
   } lens;
+  // environment lighting (ptc_set_environment): an octahedral HDR map (hdr_image.hpp: load_environment makes one
+  // from an equirectangular .hdr), or null = the reference's gradient, the default; both methods.  Pushed when the pointer changes.
+  std::shared_ptr<const EnvironmentMap> environment;
   EdgeAvoidingATrousDenoiser atrous_denoiser{};
   int max_bounces = 50;  // reference: compile-time constant, path_tracer.cu:27
 
@@ -124,6 +128,10 @@ private:
       check(ptc_set_lens(ctx_, lens.radius, lens.focus_distance), "lens");
       lens_pushed_ = lens;
     }
+    if (environment != environment_pushed_) {  // (ptc_set_environment flushes queued frames too)
+      check(ptc_set_environment(ctx_, environment ? environment->rgb.data() : nullptr, environment ? environment->size : 0u), "environment");
+      environment_pushed_ = environment;
+    }
     check(ptc_set_max_bounces(ctx_, max_bounces), "max_bounces");
     const ptc_denoiser_params p{atrous_denoiser.filter_size, atrous_denoiser.color_weight, atrous_denoiser.normal_weight,
                                 atrous_denoiser.position_weight};
@@ -137,6 +145,7 @@ private:
   bool direct_light_pushed_ = false;
   int roulette_pushed_ = 0;
   Lens lens_pushed_{};
+  std::shared_ptr<const EnvironmentMap> environment_pushed_;
 };
 
 }  // namespace hip_pt

@@ -258,7 +258,7 @@ std::string dirname_of(const std::string& path)
 
 }  // namespace
 
-SceneDescription scene_from_json(const std::string& filename)
+SceneDescription scene_from_json(const std::string& filename, bool read_environment)
 {
   std::ifstream file(filename);
   if (!file.is_open()) throw std::runtime_error("Json Parser: Cannot open file " + filename);
@@ -336,6 +336,28 @@ SceneDescription scene_from_json(const std::string& filename)
     scene.resolution[1] = (int)r->arr[1]->num;
   }
   if (const Json* sampler = root->find("sampler")) scene.spp = (int)sampler->at("samples").num;
+  // environment lighting (an extension; json_parser.py, the same rule): {"file": a Radiance .hdr, equirectangular, relative to the
+  // scene file; "scale": a finite number >= 0, default 1; "size": an integer in [2,4096], default the picture's height, at most 4096}
+  if (const Json* env = root->find("environment")) {
+    const Json* file = env->kind == Json::Object ? env->find("file") : nullptr;
+    bool ok = file && file->kind == Json::String;
+    for (size_t k = 0; ok && k < env->obj.size(); ++k) ok = env->obj[k].first == "file" || env->obj[k].first == "scale" || env->obj[k].first == "size";
+    if (!ok) throw std::runtime_error("Json Parser: \"environment\" must be an object with \"file\" (a string) and optionally \"scale\", \"size\"");
+    if (const Json* s = env->find("scale")) {
+      if (s->kind != Json::Number || !std::isfinite(s->num) || s->num < 0.0)
+        throw std::runtime_error("Json Parser: environment \"scale\" must be a finite number >= 0");
+      scene.environment_source.scale = (float)s->num;
+    }
+    if (const Json* n = env->find("size")) {
+      if (n->kind != Json::Number || n->num != std::floor(n->num) || n->num < 2.0 || n->num > 4096.0)
+        throw std::runtime_error("Json Parser: environment \"size\" must be an integer in [2,4096]");
+      scene.environment_source.size = (int)n->num;
+    }
+    // (an absolute path is taken as it is, as os.path.join does)
+    scene.environment_source.file = !file->str.empty() && file->str[0] == '/' ? file->str : dir + "/" + file->str;
+    if (read_environment)
+      scene.environment = load_environment(scene.environment_source.file, scene.environment_source.scale, scene.environment_source.size);
+  }
   return scene;
 }
 

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/ptcore.h"
+#include "hdr_image.hpp"
 
 namespace hip_pt {
 
@@ -70,6 +71,14 @@ public:
   Camera camera;
   int resolution[2] = {0, 0};
   int spp = 1;
+  // environment lighting (an extension): the octahedral map PathTracer::environment takes, or null (the
+  // reference's gradient); environment_source: the scene file's entry it came from (file: absolute; size 0: the picture's height)
+  std::shared_ptr<const EnvironmentMap> environment;
+  struct EnvironmentSource {
+    std::string file;
+    float scale = 1.0f;
+    int size = 0;
+  } environment_source;
 
   void add_material(const std::string& name, Material material);
   void add_object(Sphere sphere, const Mat4& transform, const std::string& material_name);
@@ -91,7 +100,9 @@ private:
 };
 
 // assets/json_parser.cpp:174-224 (scene_from_json) and assets/model_loader.cpp:11-44 (load_obj)
-SceneDescription scene_from_json(const std::string& filename);
+// read_environment false: the "environment" key is checked and kept in environment_source, the picture is left to the caller
+// (hip_pt, whose command line may name another picture: it reads the one that counts, once)
+SceneDescription scene_from_json(const std::string& filename, bool read_environment = true);
 Mesh load_obj(const std::string& filename);
 
 // image.cpp:9-22: RGBA8 PNG (the reference calls stbi_write_png)

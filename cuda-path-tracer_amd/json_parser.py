@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 from . import glmlite as glm
+from . import hdr
 from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, EmissiveMaterial, Mesh, MetalMaterial, SceneDescription,
                                 Sphere)
 
@@ -93,6 +94,27 @@ def _lens_value(cam, key, positive):
     return float(np.float32(v))
 
 
+def _environment(j, file_dir):
+    """The optional scene key "environment" (an extension; scene_description.cpp, the same rule):
+    {"file": a Radiance .hdr, equirectangular, relative to the scene file; "scale": a finite number >= 0, default 1; "size": the
+    octahedral map's size, an integer in [2,4096], default the image's height, at most 4096}.
+    -> (the map [n, n, 3] float32, the entry as read: file (absolute), scale, size)"""
+    if not isinstance(j, dict) or not isinstance(j.get("file"), str) or set(j) - {"file", "scale", "size"}:
+        raise ValueError("Json Parser: \"environment\" must be an object with \"file\" (a string) and optionally \"scale\", \"size\"")
+    scale = j.get("scale", 1.0)
+    if not isinstance(scale, (int, float)) or isinstance(scale, bool) or not math.isfinite(scale) or scale < 0:
+        raise ValueError(f"Json Parser: environment \"scale\" must be a finite number >= 0, got {scale!r}")
+    size = j.get("size")
+    if size is not None and (not isinstance(size, int) or isinstance(size, bool) or not 2 <= size <= 4096):
+        raise ValueError(f"Json Parser: environment \"size\" must be an integer in [2,4096], got {size!r}")
+    path = os.path.normpath(os.path.join(file_dir, j["file"]))
+    image = hdr.read_hdr(path)
+    n = size if size is not None else min(image.shape[0], 4096)
+    if n < 2:
+        raise ValueError(f"Json Parser: environment image {path} is too small for a map (height {image.shape[0]}); give \"size\"")
+    return hdr.environment_from_equirect(image, n, scale), {"file": path, "scale": float(scale), "size": int(n)}
+
+
 def scene_from_json(filename):
     with open(filename) as f:
         root = json.load(f)
@@ -134,4 +156,6 @@ def scene_from_json(filename):
     if "resolution" in cam:
         scene.resolution = (int(cam["resolution"][0]), int(cam["resolution"][1]))
     scene.spp = int(root["sampler"]["samples"]) if "sampler" in root else 1
+    if "environment" in root:
+        scene.environment, scene.environment_source = _environment(root["environment"], file_dir)
     return scene

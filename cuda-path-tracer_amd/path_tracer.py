@@ -90,6 +90,7 @@ class PathTracer:
         self._direct_light = False  # PathTracer.direct_light = True: a light sample at every diffuse hit (megakernel method only)
         self._roulette = 0  # PathTracer.roulette = k: Russian roulette at every bounce >= k but the last (0 = off)
         self._lens = (0.0, 1.0)  # PathTracer.lens = (radius, focus_distance): the thin lens (radius 0 = the pinhole)
+        self._environment = None  # PathTracer.environment = [n, n, 3] float32: an octahedral HDR sky (None = the reference's gradient)
         self.atrous_denoiser = EdgeAvoidingATrousDenoiser()
         self.max_bounces = max_bounces  # reference: compile-time 50 (path_tracer.cu:27)
         cfg = _capi.ptc_config(device=device, max_bounces=max_bounces, method=int(self.current_gpu_method), reserved=0)
@@ -101,6 +102,7 @@ class PathTracer:
         self._direct_light_pushed = False
         self._roulette_pushed = 0
         self._lens_pushed = (0.0, 1.0)
+        self._environment_pushed = None
 
     # -- lifetime -------------------------------------------------------------------------------
     def close(self):
@@ -162,6 +164,36 @@ class PathTracer:
             raise ValueError(f"focus distance must be finite, and positive under a lens radius > 0, got {focus}")
         self._lens = (radius, focus)
 
+    @property
+    def environment(self):
+        """Environment lighting (ptc_set_environment): None (the default: the reference's gradient) or an octahedral
+        HDR map, [n, n, 3] float32 with 2 <= n <= 4096, texel [j, i] = row j along z, column i along x, +y up, every component finite
+        and >= 0.  Every path that leaves the scene then takes the map's value in its direction, in both render methods.  The array
+        is copied at assignment; it is uploaded at the next trace, and only when it has been assigned since the last one."""
+        return self._environment
+
+    @environment.setter
+    def environment(self, value):
+        if value is None:
+            self._environment = None
+            return
+        m = np.array(value, dtype=np.float32, order="C")
+        if m.ndim != 3 or m.shape[0] != m.shape[1] or m.shape[2] != 3 or not 2 <= m.shape[0] <= 4096:
+            raise ValueError(f"environment must be [n, n, 3] with n in [2,4096], got shape {m.shape}")
+        if not np.all(np.isfinite(m)) or np.any(m < 0.0):
+            raise ValueError("environment components must be finite and not negative")
+        m.setflags(write=False)
+        self._environment = m
+
+    def sample_environment(self, directions):
+        """The environment's value in `directions` ([k, 3], not normalised) as the device computes it for a miss -> [k, 3] float32
+        (ptc_sample_environment).  Needs an environment."""
+        self._push_fields()
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        out = np.empty_like(d)
+        self._check(self._lib.ptc_sample_environment(self._ctx, d.ctypes.data_as(C.c_void_p), len(d), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def _push_fields(self):
         self._check(self._lib.ptc_set_max_iterations(self._ctx, int(self.max_iterations)))
         self._check(self._lib.ptc_set_method(self._ctx, int(self.current_gpu_method)))
@@ -174,6 +206,11 @@ class PathTracer:
         if self._lens != self._lens_pushed:
             self._check(self._lib.ptc_set_lens(self._ctx, self._lens[0], self._lens[1]))
             self._lens_pushed = self._lens
+        if self._environment is not self._environment_pushed:  # (a new array at every assignment: identity tells a change)
+            env = self._environment
+            self._check(self._lib.ptc_set_environment(self._ctx, env.ctypes.data_as(C.c_void_p) if env is not None else None,
+                                                      env.shape[0] if env is not None else 0))
+            self._environment_pushed = env
         self._check(self._lib.ptc_set_max_bounces(self._ctx, int(self.max_bounces)))
         d = self.atrous_denoiser
         p = _capi.ptc_denoiser_params(int(d.filter_size), float(d.color_weight), float(d.normal_weight),

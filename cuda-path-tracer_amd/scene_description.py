@@ -151,6 +151,10 @@ class SceneDescription:
         self.camera = Camera()
         self.resolution = (0, 0)
         self.spp = 1
+        # environment lighting (an extension): the octahedral map [n, n, 3] float32 PathTracer.environment takes, or
+        # None (the reference's gradient); environment_source: the scene file's entry it came from ({"file", "scale", "size"})
+        self.environment = None
+        self.environment_source = None
 
     def add_material(self, name, material):   # scene_description.cpp:150-153 (try_emplace: first one wins)
         self.material_map_.setdefault(name, material)

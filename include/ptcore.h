@@ -370,6 +370,30 @@ int ptc_set_param(ptc_ctx* ctx, const char* name, int value);
 int ptc_set_lens(ptc_ctx* ctx, float lens_radius, float focus_distance);
 int ptc_get_lens(ptc_ctx* ctx, float* lens_radius, float* focus_distance);
 
+/* Environment lighting (an extension: the reference's sky is a fixed gradient).  A context-wide octahedral HDR map:
+ * rgb = 3 n n floats in host memory, texel M[j][i] at rgb + 3 (j n + i), row j along z, column i along x, +y up, 2 <= n <= 4096, every
+ * component finite and >= 0.  With a map set, every path that leaves the scene -- in both render methods, under every parameter --
+ * ends with throughput x the map's value in its direction (a clamped bilinear fetch, continuous over the sphere; the rule, one binary32
+ * operation at a time, is DESIGN section 5j's) where the gradient stands otherwise: only colour differs from the gradient's render --
+ * normal, depth, live counts and rays_total are the same.  "direct_light" counts the environment at every miss and draws no light
+ * sample for it.  rgb == NULL or n == 0 removes the map: exactly what was launched before it existed.  The map survives
+ * ptc_upload_scene and ptc_resize.  Any time (queued frames are flushed first: a batch renders under one environment).  A frame with
+ * an environment takes the per-bounce launches under "persist" 1 (the same bits).
+ * PTC_ERR_INVALID (n out of range; a NaN, infinite or negative component: ptc_last_error names the texel and the component),
+ * PTC_ERR_OOM (the device allocation); after any refusal the environment that was set stays in place. */
+int ptc_set_environment(ptc_ctx* ctx, const float* rgb, uint32_t n);
+/* *n = the size of the map that is set, 0 without one */
+int ptc_get_environment(ptc_ctx* ctx, uint32_t* n);
+/* The device function a miss calls, on `count` directions of the caller's (host arrays: 3 floats in, 3 floats out each; a direction
+ * need not be normalised; a zero, NaN or infinite one gives 0).  PTC_ERR_INVALID without an environment.  Moves no statistics. */
+int ptc_sample_environment(ptc_ctx* ctx, const float* dirs, uint32_t count, float* rgb_out);
+/* Host only, no context: an equirectangular image (rgb: 3 width height floats, row 0 up, the image's centre the direction -z) to the
+ * octahedral map ptc_set_environment takes (out: 3 n n floats).  Per octahedral texel centre the direction d in binary64; the image
+ * sampled bilinearly, wrapping in u and clamping in v, at u = atan2(d.x, -d.z) / 2 pi + 0.5, v = acos(d.y) / pi; times scale; rounded
+ * to binary32.  A point sample per texel (no filtering).  PTC_ERR_INVALID: a NULL, a zero size, n outside [2,4096], a scale that is
+ * negative or not finite. */
+int ptc_environment_from_equirect(const float* rgb, uint32_t width, uint32_t height, uint32_t n, float scale, float* out);
+
 /* ---- the hot path ---- */
 /* PathTracer::path_trace (path_tracer.cu:389-477): one sample per pixel, accumulated as a running
  * mean; no-op once iteration() >= max_iterations.  Asynchronous on the context's stream. */
@@ -655,6 +679,11 @@ int ptc_selftest_math(ptc_ctx* ctx, const float* a, const float* b, uint32_t n, 
 int ptc_selftest_rng(ptc_ctx* ctx, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);
 /* The same header run on the host (no GPU; test hook): the same six words per element. */
 int ptc_check_rng(const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);
+/* The environment's lookup (csrc/pt_env.hpp, the header ptc_sample_environment runs on the device) on the host: the map rgb of size n
+ * (ptc_set_environment's layout and refusals) in `count` directions.  No GPU, no context; test hook. */
+int ptc_check_environment(const float* rgb, uint32_t n, const float* dirs, uint32_t count, float* rgb_out);
+/* ... and the map as ptc_set_environment uploads it: (n + 2) x (n + 2) texels of four floats {r, g, b, 0}, the apron filled in. */
+int ptc_check_environment_apron(const float* rgb, uint32_t n, float* texels_out);
 
 #ifdef __cplusplus
 }
