@@ -120,6 +120,13 @@ class ptc_direct_loop_stats(C.Structure):
     _fields_ = [("diffuse_hits", C.c_uint64), ("shadow_rays", C.c_uint64), ("unoccluded", C.c_uint64)]
 
 
+class ptc_environment_light_loop_stats(C.Structure):
+    _fields_ = [("diffuse_hits", C.c_uint64), ("shadow_rays", C.c_uint64), ("unoccluded", C.c_uint64)]
+
+
+ptc_environment_light_stats = ptc_direct_stats  # the same five fields (include/ptcore.h)
+
+
 class ptc_upload_times(C.Structure):
     _fields_ = [("bvh_build_ms", C.c_float), ("layout_ms", C.c_float), ("triangles_ms", C.c_float), ("copy_ms", C.c_float),
                 ("total_ms", C.c_float), ("bvh_on_device", C.c_uint32), ("layout_on_device", C.c_uint32)]
@@ -212,6 +219,12 @@ SIGNATURES = {
     "ptc_environment_from_equirect": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]),
     "ptc_check_environment": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptc_check_environment_apron": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ptc_environment_light": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_int]),
+    "ptc_get_environment_light_stats": (C.c_int, [_P, C.POINTER(ptc_direct_stats)]),
+    "ptc_get_environment_light_loop_stats": (C.c_int, [_P, C.POINTER(ptc_environment_light_loop_stats)]),
+    "ptc_check_environment_light_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "ptc_check_environment_light": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -524,6 +524,9 @@ constexpr uint32_t kLightSeedXor = 0x4c495445u;  // xor-ed into path_seed(point,
 constexpr uint32_t kRouletteSeedXor = 0x52524c54u;
 // the thin lens (ptc_set_lens): xor-ed into path_seed(pixel, iteration); two draws, the point on the lens disk
 constexpr uint32_t kLensSeedXor = 0x4c454e53u;
+// the environment as a light (ptc_environment_light, "environment_light"): xor-ed into path_seed(point or pixel,
+// sample_index or iteration); four draws a sample (the render loop: discard(4 * bounce))
+constexpr uint32_t kEnvLightSeedXor = 0x454e564cu;
 constexpr uint32_t kLightStatLines = 64u;        // the resolve kernel's two counters, spread over this many 128-byte lines
 //   launch_light_sample   one thread per point: the shadow ray in the path-state layout occlude_on_device takes (o4 = p, tmin_word;
 //                         d4 = w, t_max) and contrib = {unshadowed contribution rgb, 1 if sampled else 0}; a culled sample: t_max 0
@@ -543,6 +546,22 @@ constexpr uint32_t kLoopStatWords = 16u;
 void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
                               uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats,
                               int roulette = 0, DLens lens = DLens{0.0f, 0.0f});
+// The environment as a light (pt_env_light.hpp).  table: the alias table of env's map, n x n entries of 16 bytes
+// (env_light::Entry), the context's own allocation beside the map; null: no table (no map, or a map of weight 0).
+struct DEnvLight {
+  const uint4* table;
+};
+//   launch_env_light_sample  launch_light_sample's shape (pt_env.hip): one thread per point, one environment sample each; the shadow
+//                            ray is {p, tmin_word; w, FLT_MAX}, a culled sample's t_max 0.  launch_light_resolve takes it from there
+void launch_env_light_sample(hipStream_t s, DEnv env, DEnvLight el, const float* points, const float* normals, uint32_t n, uint32_t sample_index,
+                             uint32_t tmin_word, float4* o4, float4* d4, float4* contrib);
+// the megakernel's environment-light instance ("environment_light" 1 in a frame whose map has weight > 0; pt_mega_direct.hip): one
+// environment sample and one shadow ray at every diffuse hit, and the lamp's sample in front of it where lights.records != null (a
+// "direct_light" frame's lamp table); emitters, roulette (as launch_megakernel_env), pinhole or lens.  stats: the block
+// launch_megakernel_direct counts in; words 3 .. 5 of a line += diffuse hits that drew an environment sample, its shadow rays, unoccluded ones
+void launch_megakernel_env_light(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
+                                 uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
+                                 DLens lens, DEnv env, DEnvLight el);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,
                      float* out_sin, float* out_cos);
 void launch_selftest_rng(hipStream_t s, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);

@@ -1,7 +1,8 @@
 // pt_env.hip -- environment lighting in the streaming loop (ptc_set_environment): the instances of the kernels that
 // meet the sky there -- k_raygen_env<true, true> (primary rays that end in ray generation), k_shade_fused_env and k_shade_env (a miss
 // at the end of a bounce) -- compiled from the texts the gradient's instances come from (pt_raygen.inc, pt_shade_end.inc), and
-// k_env_sample, the lookup on the caller's directions (ptc_sample_environment).  The megakernel's instances: pt_mega_direct.hip.
+// k_env_sample, the lookup on the caller's directions (ptc_sample_environment), and k_env_light_sample, the environment as a light on
+// the caller's points (ptc_environment_light, section 5k).  The megakernel's instances: pt_mega_direct.hip.
 // The lookup itself: env_rules::lookup (pt_env.hpp) behind sky<true> (pt_kernels_common.inc).  Part of libptcore.so.
 //
 // The environment instances are built with kEmit on: a scene without an emissive material meets no emitter and gets the same bits, and
@@ -11,6 +12,7 @@
 #include "pt_beam_rules.hpp"
 #include "pt_feed_rules.hpp"
 #include "pt_launch_flags.hpp"
+#include "pt_env_light.hpp"
 #include <float.h>
 
 namespace pt {
@@ -40,6 +42,29 @@ __global__ __launch_bounds__(256) void k_env_sample(DEnv env, const float* dirs,
 void launch_env_sample(hipStream_t s, DEnv env, const float* dirs, uint32_t count, float* out)
 {
   hipLaunchKernelGGL(k_env_sample, dim3(div_up(count, 256u)), dim3(256), 0, s, env, dirs, count, out);
+}
+
+// ptc_environment_light's sample kernel: one thread per point, env_light::sample_point on the point's own stream;
+// out in k_light_sample's layout, for the occlusion launches and k_light_resolve (pt_light.hip).  No LDS, no cross-lane work.
+__global__ __launch_bounds__(256) void k_env_light_sample(DEnv env, DEnvLight el, const float* __restrict__ points, const float* __restrict__ normals,
+                                                          uint32_t n, uint32_t sample_index, uint32_t tmin_word, float4* __restrict__ o4,
+                                                          float4* __restrict__ d4, float4* __restrict__ contrib)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const f3 p = mk3(points[3u * (size_t)i], points[3u * (size_t)i + 1u], points[3u * (size_t)i + 2u]);
+  const f3 nrm = mk3(normals[3u * (size_t)i], normals[3u * (size_t)i + 1u], normals[3u * (size_t)i + 2u]);
+  const env_light::Sample s = env_light::sample_point(el.table, env.texels, env.n, nrm, i, sample_index, 0u);
+  o4[i] = make_float4(p.x, p.y, p.z, __uint_as_float(tmin_word));
+  d4[i] = make_float4(s.w.x, s.w.y, s.w.z, s.tmax);
+  contrib[i] = make_float4(s.contrib.x, s.contrib.y, s.contrib.z, s.sampled ? 1.0f : 0.0f);
+}
+
+void launch_env_light_sample(hipStream_t s, DEnv env, DEnvLight el, const float* points, const float* normals, uint32_t n, uint32_t sample_index,
+                             uint32_t tmin_word, float4* o4, float4* d4, float4* contrib)
+{
+  hipLaunchKernelGGL(k_env_light_sample, dim3(div_up(n, 256u)), dim3(256), 0, s, env, el, points, normals, n, sample_index, tmin_word, o4, d4,
+                     contrib);
 }
 
 // launch_raygen's finishing form (a listed first launch that walks the whole object list) under an environment

@@ -30,6 +30,7 @@
 #include "pt_beam_rules.hpp"
 #include "pt_feed_rules.hpp"
 #include "pt_light_sample.hpp"  // (mega_path names its kDirect part's types; the instances here have none of it)
+#include "pt_env_light.hpp"     // (... and its kEnvLight part's)
 static_assert(pt::beam_rules::kLeaf == pt::kLeafBit, "pt_beam_rules.hpp restates the leaf bit of the four-wide node (pt_device.hpp)");
 static_assert((uint32_t)pt::beam_rules::kEntries == pt::kBeamEntries, "pt_beam_rules.hpp restates the entries per tile (pt_device.hpp)");
 static_assert(pt::feed_rules::kBatch == (uint32_t)pt::kWave, "a feed batch is one wavefront's worth of rays");

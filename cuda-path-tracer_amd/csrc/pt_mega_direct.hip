@@ -1,5 +1,5 @@
 // pt_mega_direct.hip -- the megakernel's instances off the plain path: k_megakernel_direct (direct lighting),
-// k_megakernel<.., true> (Russian roulette, section 5h) and the thin lens's k_megakernel_lens / k_megakernel_direct_lens (section 5i),
+// k_megakernel<.., true> (Russian roulette, section 5h), k_megakernel_env_light (the environment as a light, section 5k) and the thin lens's k_megakernel_lens / k_megakernel_direct_lens (section 5i),
 // with their launchers.  The loop itself, with what kDirect and kRoulette add
 // to it, is mega_path (pt_megakernel.inc); the shadow ray's any-hit walk is scene_occluded (pt_kernels_common.inc).  Part of
 // libptcore.so.
@@ -8,6 +8,7 @@
 #include "pt_beam_rules.hpp"
 #include "pt_feed_rules.hpp"
 #include "pt_light_sample.hpp"
+#include "pt_env_light.hpp"
 #include <float.h>
 #include <limits.h>
 
@@ -52,6 +53,17 @@ __global__ __launch_bounds__(kWave) void k_megakernel_env(DScene sc, DLights lt,
                                               s_stack + threadIdx.x, lens, env);
 }
 
+// ... with the environment as a light as well ("environment_light"): one instance -- emitters and roulette compiled
+// in, pinhole or lens by lens.radius, the lamps' samples by lt.records
+__global__ __launch_bounds__(kWave) void k_megakernel_env_light(DScene sc, DLights lt, DCamera cam, uint32_t iteration, DBand band,
+                                                                uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters,
+                                                                unsigned long long* stats, int roulette, DLens lens, DEnv env, DEnvLight el)
+{
+  __shared__ uint32_t s_stack[kStackDepth * kWave];
+  mega_path<true, true, true, false, true, true>(sc, lt, cam, iteration, band, pix_count, max_bounces, fb, counters, stats, roulette,
+                                                 s_stack + threadIdx.x, lens, env, el);
+}
+
 // the plain megakernel's instances that play roulette (the plain ones: pt_kernels.hip)
 void launch_megakernel_roulette(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
                                 int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette)
@@ -93,6 +105,16 @@ void launch_megakernel_env(hipStream_t s, const DScene& scene, const DLights& li
   else
     hipLaunchKernelGGL(k_megakernel_env<false>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters, stats,
                        plays_from, lens, env);
+}
+
+void launch_megakernel_env_light(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
+                                 uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
+                                 DLens lens, DEnv env, DEnvLight el)
+{
+  const dim3 grid((pix_count + kWave - 1u) / kWave), block(kWave);
+  const int plays_from = roulette >= 1 && roulette < max_bounces - 1 ? roulette : INT_MAX;
+  hipLaunchKernelGGL(k_megakernel_env_light, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters, stats,
+                     plays_from, lens, env, el);
 }
 
 void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,

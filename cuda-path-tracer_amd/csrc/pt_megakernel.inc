@@ -25,16 +25,27 @@
 // pinhole and lens alike -- lens.radius > 0 decides per launch, kLens is not read -- and is built with kEmit and kRoulette on (a scene
 // without emitters meets no emitter; `roulette` >= max_bounces plays at no bounce: the same bits): k_megakernel_env<kDirect>,
 // pt_mega_direct.hip.
-template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false, bool kEnv = false>
+// kEnvLight (with kEnv and kDirect; ptc_set_param "environment_light", DESIGN section 5k): the environment is a light as well.  Every
+// diffuse hit draws one environment sample (env_light::sample_point, pt_env_light.hpp; the stream path_seed(pixel, iteration) ^
+// kEnvLightSeedXor, draws 4b .. 4b + 3 at bounce b) behind the lamp's, with a shadow ray of its own on the same LDS stack, and a miss
+// counts the environment only when the vertex before it drew no environment sample -- section 5g's gate in a flag of its own,
+// count_env.  The lamps are a run-time choice here: lt.records null (a wave-uniform kernel argument) is a frame without "direct_light"
+// or without a lamp table, which draws no lamp sample and counts every emitter.  stats words 3 .. 5 += diffuse hits that drew an
+// environment sample, its shadow rays, the unoccluded ones.  k_megakernel_env_light, pt_mega_direct.hip.
+template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false, bool kEnv = false, bool kEnvLight = false>
 __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, const DCamera& cam, const uint32_t iteration, const DBand band,
                                           const uint32_t pix_count, const int max_bounces, const DFrame fb, DeviceCounters* counters,
                                           unsigned long long* stats, const int roulette, uint32_t* stack,
-                                          const DLens lens = DLens{0.0f, 0.0f}, const DEnv env = DEnv{nullptr, 0u, 0u})
+                                          const DLens lens = DLens{0.0f, 0.0f}, const DEnv env = DEnv{nullptr, 0u, 0u},
+                                          const DEnvLight el = DEnvLight{nullptr})
 {
+  static_assert(!kEnvLight || (kEnv && kDirect), "the environment-light instance has an environment and a radiance sum");
   static_assert(kEmit || !kDirect, "direct lighting: launched only for a scene with a lamp table, so with an emissive material");
   const uint32_t s = blockIdx.x * kWave + threadIdx.x;
   uint32_t rays = 0u, flags = 0u;
   uint32_t n_diffuse = 0u, n_shadow = 0u, n_clear = 0u;
+  uint32_t e_diffuse = 0u, e_shadow = 0u, e_clear = 0u;
+  const bool lamps = !kEnvLight || lt.records != nullptr;
   if (s < pix_count) {
     const uint32_t pixel = band_pixel(band, s);
     Minstd rng;
@@ -48,6 +59,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
     f3 color = mk3(1.0f, 1.0f, 1.0f);
     f3 radiance = mk3(0.0f, 0.0f, 0.0f);
     bool count_emission = true;  // the last vertex drew no light sample (the camera, metal, glass): a lamp hit from it counts
+    bool count_env = true;       // (kEnvLight) ... no environment sample: a miss from it counts the environment
     f3 normal = -ray.d;
     float depth = 1e6f;
     for (int i = 0; i < max_bounces; ++i) {
@@ -59,7 +71,8 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       ++rays;
       Tally tally;
       if (!ray_scene<false>(ray, sc, rec, stack, flags, tally)) {
-        color = color * sky<kEnv>(ray.d, env);
+        if (kEnvLight && !count_env) color = mk3(0.0f, 0.0f, 0.0f);  // the environment sample of the vertex before has counted it
+        else color = color * sky<kEnv>(ray.d, env);
         break;
       }
       if (i == 0) {
@@ -79,20 +92,42 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       evaluate_material(ray.o, ray.d, tmin_flag, rec.p, rec.n, rec.side, mat, rng, color);
       ray.tmin = tmin_flag ? 1e-5f : 1e-4f;
       if constexpr (kDirect) {
-        count_emission = mat.type != 0;
+        if (lamps) count_emission = mat.type != 0;
+        if constexpr (kEnvLight) count_env = mat.type != 0;
         if (mat.type == 0) {  // diffuse: colour is throughput x albedo now; one light sample at the hit, about the unflipped normal
-          ++n_diffuse;
-          const LightSample ls = light_sample_point(lt, rec.p, rec.n, pixel, iteration, 3u * (uint32_t)i);
-          if (ls.sampled) {
-            ++n_shadow;
-            Ray shadow;
-            shadow.o = rec.p;
-            shadow.tmin = 1e-4f;
-            shadow.d = ls.w;
-            shadow.tmax = ls.tmax;
-            if (!scene_occluded(shadow, sc, stack, flags)) {
-              ++n_clear;
-              radiance = radiance + color * ls.contrib;
+          [[maybe_unused]] env_light::Sample es;  // (kEnvLight) the environment's sample: drawn first, its loads ahead of the lamp's shadow ray
+          if constexpr (kEnvLight) {
+            ++e_diffuse;
+            es = env_light::sample_point(el.table, env.texels, env.n, rec.n, pixel, iteration, 4u * (uint32_t)i);
+          }
+          if (lamps) {
+            ++n_diffuse;
+            const LightSample ls = light_sample_point(lt, rec.p, rec.n, pixel, iteration, 3u * (uint32_t)i);
+            if (ls.sampled) {
+              ++n_shadow;
+              Ray shadow;
+              shadow.o = rec.p;
+              shadow.tmin = 1e-4f;
+              shadow.d = ls.w;
+              shadow.tmax = ls.tmax;
+              if (!scene_occluded(shadow, sc, stack, flags)) {
+                ++n_clear;
+                radiance = radiance + color * ls.contrib;
+              }
+            }
+          }
+          if constexpr (kEnvLight) {
+            if (es.sampled) {  // ... and its shadow ray behind the lamp's
+              ++e_shadow;
+              Ray shadow;
+              shadow.o = rec.p;
+              shadow.tmin = 1e-4f;
+              shadow.d = es.w;
+              shadow.tmax = es.tmax;
+              if (!scene_occluded(shadow, sc, stack, flags)) {
+                ++e_clear;
+                radiance = radiance + color * es.contrib;
+              }
             }
           }
         }
@@ -103,7 +138,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
     if (flags) atomicOr(&counters->flags, flags);
   }
   // one atomic per counter and wavefront; the three loop counters spread over lines (adds to one line serialise in L2)
-  uint32_t sum = rays, sd = n_diffuse, ss = n_shadow, sv = n_clear;
+  uint32_t sum = rays, sd = n_diffuse, ss = n_shadow, sv = n_clear, ed = e_diffuse, es = e_shadow, ev = e_clear;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     sum += __shfl_down(sum, off, 64);
@@ -111,6 +146,11 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       sd += __shfl_down(sd, off, 64);
       ss += __shfl_down(ss, off, 64);
       sv += __shfl_down(sv, off, 64);
+    }
+    if constexpr (kEnvLight) {
+      ed += __shfl_down(ed, off, 64);
+      es += __shfl_down(es, off, 64);
+      ev += __shfl_down(ev, off, 64);
     }
   }
   if (threadIdx.x == 0u) {
@@ -120,6 +160,11 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       if (sd) atomicAdd(&line[0], (unsigned long long)sd);
       if (ss) atomicAdd(&line[1], (unsigned long long)ss);
       if (sv) atomicAdd(&line[2], (unsigned long long)sv);
+      if constexpr (kEnvLight) {
+        if (ed) atomicAdd(&line[3], (unsigned long long)ed);
+        if (es) atomicAdd(&line[4], (unsigned long long)es);
+        if (ev) atomicAdd(&line[5], (unsigned long long)ev);
+      }
     }
   }
 }

@@ -216,6 +216,7 @@ const ParamRow kParams[] = {
      [](ptc_ctx* c, int v) { c->scene.refill_lanes = c->refill_lanes = (uint32_t)v; }},
     {"ray_sort", 0, 1, k01, kBeforeResize, [](ptc_ctx* c, int v) { c->ray_sort = v; }},
     {"direct_light", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->direct_light = v != 0; }},
+    {"environment_light", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->environment_light = v != 0; }},
     {"roulette", 0, 64, " must be in [0,64]", kAnyTime, [](ptc_ctx* c, int v) { c->roulette = v; }},
     {"denoise_variant", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_variant = v; }},
     {"frames_in_flight", 1, 256, " must be in [1,256]", kBeforeResize, [](ptc_ctx* c, int v) { c->frames_in_flight = v; }},
@@ -464,6 +465,7 @@ void ptc_destroy(ptc_ctx* ctx)
   if (ctx->misc_counters) (void)hipFree(ctx->misc_counters);
   if (ctx->loop_stats) (void)hipFree(ctx->loop_stats);
   if (ctx->env.texels) (void)hipFree(const_cast<float4*>(ctx->env.texels));
+  if (ctx->env_table) (void)hipFree(const_cast<uint4*>(ctx->env_table));
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -643,10 +645,45 @@ int ptc_set_environment(ptc_ctx* ctx, const float* rgb, uint32_t n)
       return rc;
     }
     (void)hipFree(const_cast<float4*>(ctx->env.texels));
+    if (ctx->env_table) (void)hipFree(const_cast<uint4*>(ctx->env_table));  // the old map's alias table goes with it
   }
   ctx->env = DEnv{dev, dev ? n : 0u, 0u};
+  ctx->env_table = nullptr;
+  ctx->env_table_known = false;
   return PTC_OK;
 }
+
+}  // extern "C"
+
+// The environment's alias table, at the first call that needs it: the aproned map comes back from the device (the
+// host keeps no copy of it), env_light::build_table makes the entries, and they are uploaded into an allocation of their own.
+// Nothing reads the table before this returns, and nothing but ptc_set_environment and ptc_destroy frees it.
+int ptcd::env_light_table(ptc_ctx* ctx)
+{
+  if (ctx->env_table_known || !ctx->env.texels) return PTC_OK;
+  const uint32_t n = ctx->env.n;
+  std::vector<float4> host((size_t)(n + 2u) * (n + 2u));
+  HIP_TRY(ctx, hipMemcpy(host.data(), ctx->env.texels, host.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  std::vector<env_light::Entry> entries;
+  if (env_light::build_table(host.data(), n, entries, nullptr) > 0.0) {
+    const size_t bytes = entries.size() * sizeof(env_light::Entry);
+    void* dev = nullptr;
+    if (hipMalloc(&dev, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, PTC_ERR_OOM, "hipMalloc(environment light table, " + std::to_string(bytes) + " bytes) failed");
+    }
+    const hipError_t e = hipMemcpy(dev, entries.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(dev);
+      return fail(ctx, PTC_ERR_HIP, std::string("environment light table upload: ") + hipGetErrorString(e));
+    }
+    ctx->env_table = static_cast<const uint4*>(dev);
+  }
+  ctx->env_table_known = true;
+  return PTC_OK;
+}
+
+extern "C" {
 
 // An equirectangular image to the octahedral map ptc_set_environment takes (host only; float64 inside, not parity-critical).  Per
 // octahedral texel centre: the direction, the image sampled bilinearly at u = atan2(d.x, -d.z) / 2 pi + 0.5 (wrapping) and v =
@@ -823,6 +860,23 @@ int ptc_get_direct_loop_stats(ptc_ctx* ctx, ptc_direct_loop_stats* out)
   return PTC_OK;
 }
 
+int ptc_get_environment_light_loop_stats(ptc_ctx* ctx, ptc_environment_light_loop_stats* out)
+{
+  if (!ctx || !out) return PTC_ERR_INVALID;
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;
+  *out = ptc_environment_light_loop_stats{};
+  if (ctx->loop_stats_clear) return PTC_OK;  // nothing that counts has been launched since ptc_restart
+  std::vector<unsigned long long> host((size_t)kLightStatLines * kLoopStatWords);
+  HIP_TRY(ctx, hipMemcpy(host.data(), ctx->loop_stats, kLoopStatBytes, hipMemcpyDeviceToHost));
+  for (uint32_t l = 0; l < kLightStatLines; ++l) {
+    out->diffuse_hits += host[(size_t)kLoopStatWords * l + 3u];
+    out->shadow_rays += host[(size_t)kLoopStatWords * l + 4u];
+    out->unoccluded += host[(size_t)kLoopStatWords * l + 5u];
+  }
+  return PTC_OK;
+}
+
 static int drain_timed(ptc_ctx* ctx)
 {
   for (auto& tl : ctx->timed) {
@@ -865,6 +919,7 @@ int ptc_reset_profile(ptc_ctx* ctx)
   ctx->intersect_redone = 0;
   ctx->occlusion = ptc_occlusion_stats{};
   ctx->direct = ptc_direct_stats{};
+  ctx->env_direct = ptc_environment_light_stats{};
   const size_t off = offsetof(DeviceCounters, paths);  // the profile counters: from `paths` to the end of the head
   return each_counter_block(ctx, [&](size_t, int, DeviceCounters* dev) -> int {
     HIP_TRY(ctx, hipMemset(reinterpret_cast<char*>(dev) + off, 0, kCountersHead - off));

@@ -526,6 +526,62 @@ int ptc_check_environment_apron(const float* rgb, uint32_t n, float* texels_out)
   return PTC_OK;
 }
 
+// The environment's alias table (pt_env_light.hpp) on the host, as the first call that needs it builds it: no GPU, no
+// context.  ptc_check_environment's refusals.
+int ptc_check_environment_light_table(const float* rgb, uint32_t n, void* entries_out, double* total_weight, uint64_t* positive_squares)
+{
+  if (!rgb || !total_weight || !positive_squares || n < env_rules::kMinSize || n > env_rules::kMaxSize) return PTC_ERR_INVALID;
+  for (size_t k = 0; k < 3u * (size_t)n * n; ++k)
+    if (!(rgb[k] >= 0.0f) || !std::isfinite(rgb[k])) return PTC_ERR_INVALID;
+  std::vector<float4> e((size_t)(n + 2u) * (n + 2u));
+  env_rules::apron(rgb, n, e.data());
+  std::vector<env_light::Entry> entries;
+  *total_weight = env_light::build_table(e.data(), n, entries, positive_squares);
+  if (entries_out) {
+    if (entries.empty()) std::memset(entries_out, 0, (size_t)n * n * sizeof(env_light::Entry));
+    else std::memcpy(entries_out, entries.data(), entries.size() * sizeof(env_light::Entry));
+  }
+  return PTC_OK;
+}
+
+// ... and the sample (env_light::sample_draws) on the caller's points, normals and draws, written out as ptc_environment_light writes
+// a sample whose shadow ray is free
+int ptc_check_environment_light(const float* rgb, uint32_t n, const float* points, const float* normals, const uint32_t* v, const float* u,
+                                uint32_t count, float* radiance, float* shadow_rays, uint8_t* sampled)
+{
+  if (!rgb || n < env_rules::kMinSize || n > env_rules::kMaxSize) return PTC_ERR_INVALID;
+  if (count != 0u && (!points || !normals || !v || !u || !radiance)) return PTC_ERR_INVALID;
+  for (uint32_t i = 0; i < count; ++i)
+    if (v[i] < 1u || v[i] > 0x7ffffffeu) return PTC_ERR_INVALID;  // a raw value of the generator
+  for (size_t k = 0; k < 3u * (size_t)n * n; ++k)
+    if (!(rgb[k] >= 0.0f) || !std::isfinite(rgb[k])) return PTC_ERR_INVALID;
+  std::vector<float4> e((size_t)(n + 2u) * (n + 2u));
+  env_rules::apron(rgb, n, e.data());
+  std::vector<env_light::Entry> entries;
+  const bool table = env_light::build_table(e.data(), n, entries, nullptr) > 0.0;
+  for (uint32_t i = 0; i < count; ++i) {
+    env_light::Sample s{};
+    if (table)
+      s = env_light::sample_draws(reinterpret_cast<const uint4*>(entries.data()), e.data(), n,
+                                  mk3(normals[3u * (size_t)i], normals[3u * (size_t)i + 1u], normals[3u * (size_t)i + 2u]), v[i], u[3u * (size_t)i],
+                                  u[3u * (size_t)i + 1u], u[3u * (size_t)i + 2u]);
+    radiance[3u * (size_t)i] = s.contrib.x;
+    radiance[3u * (size_t)i + 1u] = s.contrib.y;
+    radiance[3u * (size_t)i + 2u] = s.contrib.z;
+    if (sampled) sampled[i] = s.sampled ? (uint8_t)1 : (uint8_t)0;
+    if (shadow_rays) {
+      float* r = shadow_rays + 8u * (size_t)i;
+      std::memcpy(r, points + 3u * (size_t)i, 3u * sizeof(float));
+      r[3] = 1e-4f;
+      r[4] = s.sampled ? s.w.x : 0.0f;
+      r[5] = s.sampled ? s.w.y : 0.0f;
+      r[6] = s.sampled ? s.w.z : 0.0f;
+      r[7] = s.sampled ? s.tmax : 0.0f;
+    }
+  }
+  return PTC_OK;
+}
+
 // ... and on the device
 int ptc_selftest_rng(ptc_ctx* ctx, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out)
 {

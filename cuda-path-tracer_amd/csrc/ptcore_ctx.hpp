@@ -28,6 +28,7 @@
 #include "pt_beam_rules.hpp"
 #include "pt_feed_rules.hpp"
 #include "pt_frame_rules.hpp"
+#include "pt_env_light.hpp"
 
 using namespace pt;
 
@@ -274,7 +275,16 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   // the environment (ptc_set_environment): the octahedral map with its apron on the device, or none (texels null:
   // the gradient, the instances launched as before); the context's own allocation -- it survives ptc_upload_scene and ptc_resize
   DEnv env{nullptr, 0u, 0u};
-  unsigned long long* loop_stats = nullptr;  // device: kLightStatLines lines of kLoopStatWords words (diffuse hits, shadow rays, unoccluded)
+  // the environment as a light.  "environment_light": the megakernel draws an environment sample at every diffuse
+  // hit (k_megakernel_env_light).  env_table: the alias table of env's map on the device, 16 n n bytes, the context's own allocation;
+  // built by the first call that needs it (env_light_table), freed where the map is freed.  env_table_known: that call has been made
+  // for this map -- a null table then means a map of weight 0
+  bool environment_light = false;
+  const uint4* env_table = nullptr;
+  bool env_table_known = false;
+  ptc_environment_light_stats env_direct{};  // ptc_environment_light since ptc_reset_profile
+  // device: kLightStatLines lines of kLoopStatWords words (0 .. 2 the lamps': diffuse hits, shadow rays, unoccluded; 3 .. 5 the environment's)
+  unsigned long long* loop_stats = nullptr;
   bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
 };
 
@@ -304,6 +314,9 @@ int flush_pending(ptc_ctx* ctx, bool from_trace = false);  // enqueue the iterat
 uint32_t fold_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end);  // may k_spheres take sphere_fold for this run? (ptcore_trace.cpp)
 uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end);  // ... the per-lane form, sphere_run_lanes? (ptcore_trace.cpp)
 int sync_frames(ptc_ctx* ctx);
+// The alias table of the context's environment (ptcore.cpp), built and uploaded if this map has none yet.  After
+// PTC_OK ctx->env_table is the table, or null for a map of weight 0.  PTC_ERR_OOM: the allocation failed; the environment stays.
+int env_light_table(ptc_ctx* ctx);
 // gives back everything a frame state owns and leaves it "no frame" (ptcore.cpp); its streams must be idle (sync_frames)
 void release_frame(ptc_frame_state& f);
 int frame_ready(ptc_ctx* ctx);

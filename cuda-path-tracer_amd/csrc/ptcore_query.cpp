@@ -1,5 +1,5 @@
 // ptcore_query.cpp -- the ray queries outside the render loop: ptc_intersect_rays (closest hit), ptc_occluded_rays (any hit),
-// ptc_direct_light (light sample + shadow ray + resolve) and the one host path they share: the opening checks, the fast-domain
+// ptc_direct_light and ptc_environment_light (light sample + shadow ray + resolve: light_query) and the one host path they share: the opening checks, the fast-domain
 // rule and the ray packing, the scratch of a traversal launch (WalkScratch), the exact cross-check kernel, and the device memory
 // and clean-up of one call (QueryRun).  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
@@ -197,6 +197,120 @@ void exact_closest_hit(ptc_ctx* ctx, const float4* o4, const float4* d4, uint32_
   launch_intersect(ctx->stream, ctx->scene, o4, d4, n, hits, ctx->misc_counters, reference_order ? 0 : 1);
 }
 
+// What ptc_direct_light and ptc_environment_light do behind their own checks and query_prologue: the sample kernel of the caller
+// (launch_sample: points, normals, the t_min word, and the three arrays it fills -- shadow rays in the path-state layout, unshadowed
+// contributions), the occlusion launches or, under trace variant 0 / 1, the exact closest-hit kernel, then k_light_resolve; the
+// caller's counters st.  nothing: there is nothing to sample.  what: the entry point's name, for messages.
+template <typename LaunchSample>
+int light_query(ptc_ctx* ctx, const float* points, const float* normals, uint32_t n, float* radiance, float* shadow_rays, uint8_t* visible,
+                int on_device, bool nothing, ptc_direct_stats& st, const char* what, LaunchSample launch_sample)
+{
+  int rc;
+  const size_t n3 = 3u * (size_t)n;
+  if (nothing) {
+    // no lamp, or lamps of total weight 0 (no environment table: a map of weight 0): zeros, the empty ray from every point, and no launch
+    std::vector<float> rays;
+    if (shadow_rays) {
+      std::vector<float> pts;
+      const float* src = points;
+      if (on_device) {
+        pts.resize(n3);
+        HIP_TRY(ctx, hipMemcpy(pts.data(), points, n3 * sizeof(float), hipMemcpyDeviceToHost));
+        src = pts.data();
+      }
+      rays.assign(8u * (size_t)n, 0.0f);
+      for (uint32_t i = 0; i < n; ++i) {
+        std::memcpy(&rays[8u * (size_t)i], src + 3u * (size_t)i, 3u * sizeof(float));
+        rays[8u * (size_t)i + 3u] = 1e-4f;
+      }
+    }
+    if (on_device) {
+      HIP_TRY(ctx, hipMemsetAsync(radiance, 0, n3 * sizeof(float), ctx->stream));
+      if (visible) HIP_TRY(ctx, hipMemsetAsync(visible, 0, n, ctx->stream));
+      if (shadow_rays) HIP_TRY(ctx, hipMemcpyAsync(shadow_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+      std::memset(radiance, 0, n3 * sizeof(float));
+      if (visible) std::memset(visible, 0, n);
+      if (shadow_rays) std::memcpy(shadow_rays, rays.data(), rays.size() * sizeof(float));
+    }
+    st.points += n;
+    return PTC_OK;
+  }
+  // trace variants 0 / 1 stay cross-checks: the generated rays go through the exact closest-hit kernel, as in ptc_occluded_rays
+  // (there t_min travels as a float; a generated t_max is never NaN: d * 0.999f of a finite d, or 0)
+  const bool fast = ctx->trace_variant == 3;
+  QueryRun q(ctx, true);
+  float *d_pts = nullptr, *d_nrm = nullptr, *d_rad = radiance, *d_rays = shadow_rays;
+  uint8_t *d_vis = visible, *flags = nullptr;
+  float4 *o4 = nullptr, *d4 = nullptr, *contrib = nullptr;
+  uint32_t* stats = nullptr;
+  DHits hits{};
+  WalkScratch scr{};
+  rc = q.alloc(&o4, n);
+  if (!rc) rc = q.alloc(&d4, n);
+  if (!rc) rc = q.alloc(&contrib, n);
+  if (!rc) rc = q.alloc(&stats, (size_t)kLightStatLines * 32u);
+  if (!rc && !on_device) {
+    rc = q.alloc(&d_pts, n3);
+    if (!rc) rc = q.alloc(&d_nrm, n3);
+    if (!rc) rc = q.alloc(&d_rad, n3);
+    if (!rc && shadow_rays) rc = q.alloc(&d_rays, 8u * (size_t)n);
+    if (!rc && visible) rc = q.alloc(&d_vis, n);
+  }
+  if (!rc && fast) {
+    rc = q.alloc(&flags, n);
+    if (!rc) rc = alloc_walk_scratch(ctx, q.pool, n, false, &scr);
+  } else if (!rc) {
+    rc = q.alloc(&hits.tp, n);
+    if (!rc) rc = q.alloc(&hits.nm, n);
+  }
+  if (rc) return rc;
+  uint32_t launches = 0u, dev_flags = 0u;
+  std::vector<uint32_t> host_stats((size_t)kLightStatLines * 32u, 0u);
+  auto run = [&]() -> int {
+    if (!on_device) {
+      HIP_TRY(ctx, hipMemcpyAsync(d_pts, points, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(d_nrm, normals, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(ctx, hipMemsetAsync(stats, 0, host_stats.size() * sizeof(uint32_t), ctx->stream));
+    if (int r2 = q.time_begin()) return r2;
+    const float tmin = 1e-4f;
+    uint32_t tmin_word = 0u;
+    if (!fast) std::memcpy(&tmin_word, &tmin, 4);
+    launch_sample(on_device ? points : d_pts, on_device ? normals : d_nrm, tmin_word, o4, d4, contrib);
+    ++launches;
+    if (fast) {
+      if (int r2 = occlude_on_device(ctx, ctx->stream, o4, d4, n, flags, scr, &launches)) return r2;
+    } else {
+      exact_closest_hit(ctx, o4, d4, n, hits, ctx->trace_variant == 0);
+      ++launches;
+    }
+    launch_light_resolve(ctx->stream, o4, d4, contrib, flags, hits.tp, n, d_rad, d_rays, d_vis, stats);
+    ++launches;
+    if (int r2 = check_last(ctx, what)) return r2;
+    if (int r2 = q.time_end()) return r2;
+    if (!on_device) {
+      HIP_TRY(ctx, hipMemcpyAsync(radiance, d_rad, n3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+      if (shadow_rays) HIP_TRY(ctx, hipMemcpyAsync(shadow_rays, d_rays, 8u * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+      if (visible) HIP_TRY(ctx, hipMemcpyAsync(visible, d_vis, n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(host_stats.data(), stats, host_stats.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (fast) HIP_TRY(ctx, hipMemcpyAsync(&dev_flags, &scr.counters->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return q.elapsed_ms(&st.kernel_ms);
+  };
+  if ((rc = q.finish(run())) != PTC_OK) return rc;
+  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, std::string("traversal stack overflow in ") + what);
+  for (uint32_t l = 0; l < kLightStatLines; ++l) {
+    st.sampled += host_stats[32u * l];
+    st.unoccluded += host_stats[32u * l + 1u];
+  }
+  st.points += n;
+  st.launches += launches;
+  return PTC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -383,116 +497,45 @@ int ptc_direct_light(ptc_ctx* ctx, const float* points, const float* normals, ui
   else if (n <= kMaxQuery && on_device && shadow_rays && ((uintptr_t)shadow_rays & 15u)) bad_args = "shadow_rays on the device must be 16-byte aligned";
   int rc;
   if (!query_prologue(ctx, n, "points", bad_args, &rc)) return rc;
-  const size_t n3 = 3u * (size_t)n;
-  if (!ctx->light_records) {
-    // no lamp, or lamps of total weight 0: zeros, the empty ray from every point, and no launch
-    std::vector<float> rays;
-    if (shadow_rays) {
-      std::vector<float> pts;
-      const float* src = points;
-      if (on_device) {
-        pts.resize(n3);
-        HIP_TRY(ctx, hipMemcpy(pts.data(), points, n3 * sizeof(float), hipMemcpyDeviceToHost));
-        src = pts.data();
-      }
-      rays.assign(8u * (size_t)n, 0.0f);
-      for (uint32_t i = 0; i < n; ++i) {
-        std::memcpy(&rays[8u * (size_t)i], src + 3u * (size_t)i, 3u * sizeof(float));
-        rays[8u * (size_t)i + 3u] = 1e-4f;
-      }
-    }
-    if (on_device) {
-      HIP_TRY(ctx, hipMemsetAsync(radiance, 0, n3 * sizeof(float), ctx->stream));
-      if (visible) HIP_TRY(ctx, hipMemsetAsync(visible, 0, n, ctx->stream));
-      if (shadow_rays) HIP_TRY(ctx, hipMemcpyAsync(shadow_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    } else {
-      std::memset(radiance, 0, n3 * sizeof(float));
-      if (visible) std::memset(visible, 0, n);
-      if (shadow_rays) std::memcpy(shadow_rays, rays.data(), rays.size() * sizeof(float));
-    }
-    ctx->direct.points += n;
-    return PTC_OK;
-  }
-  // trace variants 0 / 1 stay cross-checks: the generated rays go through the exact closest-hit kernel, as in ptc_occluded_rays
-  // (there t_min travels as a float; a generated t_max is never NaN: d * 0.999f of a finite d, or 0)
-  const bool fast = ctx->trace_variant == 3;
-  QueryRun q(ctx, true);
-  float *d_pts = nullptr, *d_nrm = nullptr, *d_rad = radiance, *d_rays = shadow_rays;
-  uint8_t *d_vis = visible, *flags = nullptr;
-  float4 *o4 = nullptr, *d4 = nullptr, *contrib = nullptr;
-  uint32_t* stats = nullptr;
-  DHits hits{};
-  WalkScratch scr{};
-  rc = q.alloc(&o4, n);
-  if (!rc) rc = q.alloc(&d4, n);
-  if (!rc) rc = q.alloc(&contrib, n);
-  if (!rc) rc = q.alloc(&stats, (size_t)kLightStatLines * 32u);
-  if (!rc && !on_device) {
-    rc = q.alloc(&d_pts, n3);
-    if (!rc) rc = q.alloc(&d_nrm, n3);
-    if (!rc) rc = q.alloc(&d_rad, n3);
-    if (!rc && shadow_rays) rc = q.alloc(&d_rays, 8u * (size_t)n);
-    if (!rc && visible) rc = q.alloc(&d_vis, n);
-  }
-  if (!rc && fast) {
-    rc = q.alloc(&flags, n);
-    if (!rc) rc = alloc_walk_scratch(ctx, q.pool, n, false, &scr);
-  } else if (!rc) {
-    rc = q.alloc(&hits.tp, n);
-    if (!rc) rc = q.alloc(&hits.nm, n);
-  }
-  if (rc) return rc;
-  DLights lights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres, ctx->scene.materials};
-  uint32_t launches = 0u, dev_flags = 0u;
-  std::vector<uint32_t> host_stats((size_t)kLightStatLines * 32u, 0u);
-  auto run = [&]() -> int {
-    if (!on_device) {
-      HIP_TRY(ctx, hipMemcpyAsync(d_pts, points, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(d_nrm, normals, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, hipMemsetAsync(stats, 0, host_stats.size() * sizeof(uint32_t), ctx->stream));
-    if (int r2 = q.time_begin()) return r2;
-    const float tmin = 1e-4f;
-    uint32_t tmin_word = 0u;
-    if (!fast) std::memcpy(&tmin_word, &tmin, 4);
-    launch_light_sample(ctx->stream, lights, on_device ? points : d_pts, on_device ? normals : d_nrm, n, sample_index, tmin_word, o4, d4, contrib);
-    ++launches;
-    if (fast) {
-      if (int r2 = occlude_on_device(ctx, ctx->stream, o4, d4, n, flags, scr, &launches)) return r2;
-    } else {
-      exact_closest_hit(ctx, o4, d4, n, hits, ctx->trace_variant == 0);
-      ++launches;
-    }
-    launch_light_resolve(ctx->stream, o4, d4, contrib, flags, hits.tp, n, d_rad, d_rays, d_vis, stats);
-    ++launches;
-    if (int r2 = check_last(ctx, "direct-light query")) return r2;
-    if (int r2 = q.time_end()) return r2;
-    if (!on_device) {
-      HIP_TRY(ctx, hipMemcpyAsync(radiance, d_rad, n3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-      if (shadow_rays) HIP_TRY(ctx, hipMemcpyAsync(shadow_rays, d_rays, 8u * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-      if (visible) HIP_TRY(ctx, hipMemcpyAsync(visible, d_vis, n, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(host_stats.data(), stats, host_stats.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (fast) HIP_TRY(ctx, hipMemcpyAsync(&dev_flags, &scr.counters->flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return q.elapsed_ms(&ctx->direct.kernel_ms);
-  };
-  if ((rc = q.finish(run())) != PTC_OK) return rc;
-  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, "traversal stack overflow in ptc_direct_light");
-  for (uint32_t l = 0; l < kLightStatLines; ++l) {
-    ctx->direct.sampled += host_stats[32u * l];
-    ctx->direct.unoccluded += host_stats[32u * l + 1u];
-  }
-  ctx->direct.points += n;
-  ctx->direct.launches += launches;
-  return PTC_OK;
+  const DLights lights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres, ctx->scene.materials};
+  return light_query(ctx, points, normals, n, radiance, shadow_rays, visible, on_device, !ctx->light_records, ctx->direct, "ptc_direct_light",
+                     [&](const float* pts, const float* nrm, uint32_t tmin_word, float4* o4, float4* d4, float4* contrib) {
+                       launch_light_sample(ctx->stream, lights, pts, nrm, n, sample_index, tmin_word, o4, d4, contrib);
+                     });
 }
 
 int ptc_get_direct_stats(ptc_ctx* ctx, ptc_direct_stats* out)
 {
   if (!ctx || !out) return PTC_ERR_INVALID;
   *out = ctx->direct;
+  return PTC_OK;
+}
+
+// Environment-light queries: ptc_direct_light's path with k_env_light_sample for a sample kernel.  The alias
+// table is built here if no call has needed it since the map was set.
+int ptc_environment_light(ptc_ctx* ctx, const float* points, const float* normals, uint32_t n, uint32_t sample_index, float* radiance,
+                          float* shadow_rays, uint8_t* visible, int on_device)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (!ctx->env.texels) return fail(ctx, PTC_ERR_INVALID, "no environment is set (ptc_set_environment)");
+  const char* bad_args = nullptr;
+  if (!points || !normals || !radiance) bad_args = "points, normals or radiance is NULL";
+  else if (n <= kMaxQuery && on_device && shadow_rays && ((uintptr_t)shadow_rays & 15u)) bad_args = "shadow_rays on the device must be 16-byte aligned";
+  int rc;
+  if (!query_prologue(ctx, n, "points", bad_args, &rc)) return rc;
+  if ((rc = env_light_table(ctx)) != PTC_OK) return rc;
+  const DEnv env = ctx->env;
+  const DEnvLight el{ctx->env_table};
+  return light_query(ctx, points, normals, n, radiance, shadow_rays, visible, on_device, !ctx->env_table, ctx->env_direct, "ptc_environment_light",
+                     [&](const float* pts, const float* nrm, uint32_t tmin_word, float4* o4, float4* d4, float4* contrib) {
+                       launch_env_light_sample(ctx->stream, env, el, pts, nrm, n, sample_index, tmin_word, o4, d4, contrib);
+                     });
+}
+
+int ptc_get_environment_light_stats(ptc_ctx* ctx, ptc_environment_light_stats* out)
+{
+  if (!ctx || !out) return PTC_ERR_INVALID;
+  *out = ctx->env_direct;
   return PTC_OK;
 }
 

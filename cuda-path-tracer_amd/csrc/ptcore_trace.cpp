@@ -10,6 +10,9 @@ namespace {
 // "direct_light" 1 outside the megakernel method: the refusal of ptc_trace and ptc_trace_begin
 constexpr const char* kDirectNeedsMegakernel =
     "direct_light is rendered by the megakernel method only (ptc_set_method(PTC_METHOD_MEGAKERNEL)); the streaming loop has no direct lighting";
+// ... and "environment_light" 1
+const char* const kEnvLightNeedsMegakernel =
+    "environment_light is rendered by the megakernel method only (ptc_set_method(PTC_METHOD_MEGAKERNEL)); the streaming loop has no direct lighting";
 
 // the epoch of the next look-back launch on a slot's tile descriptors (k_shade_fused, the listing k_raygen / k_spheres).  After
 // kMaxEpoch the epochs start at 1 again, and a descriptor that no launch of the finished lap has overwritten (a tile above a band
@@ -549,6 +552,7 @@ int ptc_trace_begin(ptc_ctx* ctx, const ptc_camera* camera)
   if (!camera) return fail(ctx, PTC_ERR_INVALID, "camera is NULL");
   if (ctx->active_slot >= 0) return fail(ctx, PTC_ERR_INVALID, "ptc_trace_end missing");
   if (ctx->direct_light) return fail(ctx, PTC_ERR_INVALID, kDirectNeedsMegakernel);  // (the stepwise calls are the streaming loop)
+  if (ctx->environment_light) return fail(ctx, PTC_ERR_INVALID, kEnvLightNeedsMegakernel);
   // (ptc_trace stops at max_iterations; nothing else stands between the stepwise calls and ptc_trace_end's ++iteration)
   if (ctx->iteration == INT_MAX) return fail(ctx, PTC_ERR_INVALID, "the iteration counter is at INT_MAX: ptc_restart or ptc_set_iteration first");
   if (int rc = flush_pending(ctx)) return rc;
@@ -627,6 +631,7 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
   // "direct_light" is rendered by the megakernel alone: refused before anything is queued or launched
   if (ctx->direct_light && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kDirectNeedsMegakernel);
   if (ctx->direct_light && !ctx->light_error.empty()) return fail(ctx, PTC_ERR_INVALID, ctx->light_error);  // as ptc_direct_light
+  if (ctx->environment_light && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kEnvLightNeedsMegakernel);
   if (ctx->iteration >= ctx->max_iterations) {  // path_tracer.cu:391
     ctx->result = ctx->fb.color4;
     return PTC_OK;
@@ -642,16 +647,24 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
     ctx->cam = make_camera(*camera, ctx->width, ctx->height);
     ctx->have_cam = true;
     const bool direct = ctx->direct_light && ctx->light_records;  // a lamp table of total weight > 0; without one: the plain instances, the same bits
+    // "environment_light" (DESIGN section 5k): a frame whose environment has a table, i.e. a map of weight > 0; else as with 0
+    if (ctx->environment_light && env_frame(ctx))
+      if (int rc = env_light_table(ctx)) return rc;
+    const bool env_lit = ctx->environment_light && env_frame(ctx) && ctx->env_table;
     DLights lights{};
-    if (direct) {
+    if (direct || env_lit) {
       if (ctx->loop_stats_clear) {
         HIP_TRY(ctx, hipMemsetAsync(ctx->loop_stats, 0, kLoopStatBytes, sl.stream));
         ctx->loop_stats_clear = false;
       }
+    }
+    if (direct)
       lights = DLights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
                        ctx->scene.materials};
-    }
-    if (env_frame(ctx)) {  // an environment: its instance of the plain or the direct-lit loop
+    if (env_lit) {  // the environment is a light too: its one instance, the lamps' samples by lights.records
+      launch_megakernel_env_light(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces,
+                                  ctx->fb, sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx), ctx->env, DEnvLight{ctx->env_table});
+    } else if (env_frame(ctx)) {  // an environment: its instance of the plain or the direct-lit loop
       launch_megakernel_env(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,
                             sl.counters, direct ? ctx->loop_stats : nullptr, ctx->roulette, frame_lens(ctx), ctx->env);
     } else if (direct) {

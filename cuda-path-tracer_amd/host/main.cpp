@@ -50,6 +50,7 @@ struct CliConfigurations {  // configurations.hpp:11-15
   bool denoise = false;
   bool megakernel = false;
   bool direct_light = false;
+  bool environment_light = false;
   int roulette = 0;
   std::optional<float> lens_radius, focus_distance;  // the thin lens (override the scene file's camera keys)
   // environment lighting (override the scene file's "environment" key, each on its own)
@@ -79,6 +80,8 @@ void usage()
                "      --roulette K     Russian roulette at every bounce >= K but the last, unbiased (0 = off, the default; K in [0,64])\n"
                "      --lens-radius R  thin lens: aperture radius in world units (0 = pinhole; overrides the scene's \"lens_radius\")\n"
                "      --focus-distance F  thin lens: distance of the plane in focus, > 0 (overrides the scene's \"focus_distance\")\n"
+               "      --environment-light  an environment sample with a shadow ray at every diffuse hit (needs --method megakernel;\n"
+               "                       a scene whose \"environment\" says \"light\": true asks for it under --method megakernel)\n"
                "      --environment FILE  environment lighting: an equirectangular Radiance .hdr (overrides the scene's \"environment\")\n"
                "      --environment-scale S  multiply the picture by S, a finite number >= 0 (default 1)\n"
                "      --environment-size N  size of the octahedral map made from it, in [2,4096] (default: the picture's height)\n"
@@ -115,6 +118,7 @@ CliConfigurations parse_cli_args(int argc, char** argv)
     else if (a == "--denoise") c.denoise = true;
     else if (a == "--method") c.megakernel = need("method") == "megakernel";
     else if (a == "--direct-light") c.direct_light = true;
+    else if (a == "--environment-light") c.environment_light = true;
     else if (a == "--roulette") {
       // a whole decimal number in [0, 64] (ptc_set_param's range), refused here: before the scene is read or a GPU touched
       const std::string v = need("roulette");
@@ -184,6 +188,10 @@ CliConfigurations parse_cli_args(int argc, char** argv)
   }
   if (c.direct_light && !c.megakernel) {  // before any GPU is touched: the streaming loop would render without it
     std::fprintf(stderr, "hip_pt: --direct-light needs --method megakernel (the streaming method renders no direct light)\n");
+    std::exit(1);
+  }
+  if (c.environment_light && !c.megakernel) {  // ... and no environment light
+    std::fprintf(stderr, "hip_pt: --environment-light needs --method megakernel (the streaming method renders no direct light)\n");
     std::exit(1);
   }
   if (c.filename.empty()) {
@@ -319,6 +327,8 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   DisplayBufferType display = configs.display;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
+  // (the flag, or the scene's "environment": {"light": true} where the method renders it)
+  path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.environment = scene_desc.environment;
@@ -426,6 +436,8 @@ try {
   path_tracer.max_bounces = configs.max_bounces;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
+  // (the flag, or the scene's "environment": {"light": true} where the method renders it)
+  path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.environment = scene_desc.environment;
@@ -508,9 +520,9 @@ int run_ranks(const CliConfigurations& configs, const SceneDescription& scene_de
     std::fprintf(stderr, "hip_pt: at most %d ranks\n", kMaxRanks);
     return 1;
   }
-  // (the megakernel seeds by frame pixel, so its ranks render the single-GPU image; it is let through for --direct-light, which
-  // the streaming method cannot render)
-  if (configs.denoise || (configs.megakernel && !configs.direct_light)) {
+  // (the megakernel seeds by frame pixel, so its ranks render the single-GPU image; it is let through for --direct-light and
+  // --environment-light, which the streaming method cannot render)
+  if (configs.denoise || (configs.megakernel && !configs.direct_light && !configs.environment_light)) {
     std::fprintf(stderr, "hip_pt: --gpus N renders in streaming mode without the denoiser (it needs the whole frame in one context)\n");
     return 1;
   }
@@ -641,6 +653,8 @@ try {
   path_tracer.max_bounces = configs.max_bounces;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
+  // (the flag, or the scene's "environment": {"light": true} where the method renders it)
+  path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.environment = scene_desc.environment;

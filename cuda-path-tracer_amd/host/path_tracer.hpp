@@ -40,6 +40,8 @@ public:
   int max_iterations = 1;
   GPUMethod current_gpu_method = GPUMethod::streaming;
   bool direct_light = false;  // a light sample at every diffuse hit (megakernel method only; ptc_set_param "direct_light")
+  // an environment sample at every diffuse hit (megakernel method only; ptc_set_param "environment_light")
+  bool environment_light = false;
   int roulette = 0;  // Russian roulette at every bounce >= this but the last, 0 = off (both methods; ptc_set_param "roulette", [0, 64])
   // the thin lens (ptc_set_lens): aperture radius (0 = the pinhole, the default) and the distance of the plane in
   // focus, world units; both methods
@@ -120,6 +122,10 @@ private:
       check(ptc_set_param(ctx_, "direct_light", direct_light ? 1 : 0), "direct_light");
       direct_light_pushed_ = direct_light;
     }
+    if (environment_light != environment_light_pushed_) {
+      check(ptc_set_param(ctx_, "environment_light", environment_light ? 1 : 0), "environment_light");
+      environment_light_pushed_ = environment_light;
+    }
     if (roulette != roulette_pushed_) {
       check(ptc_set_param(ctx_, "roulette", roulette), "roulette");
       roulette_pushed_ = roulette;
@@ -143,6 +149,7 @@ private:
   }
   ptc_ctx* ctx_ = nullptr;
   bool direct_light_pushed_ = false;
+  bool environment_light_pushed_ = false;
   int roulette_pushed_ = 0;
   Lens lens_pushed_{};
   std::shared_ptr<const EnvironmentMap> environment_pushed_;

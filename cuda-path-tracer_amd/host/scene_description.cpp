@@ -337,12 +337,17 @@ SceneDescription scene_from_json(const std::string& filename, bool read_environm
   }
   if (const Json* sampler = root->find("sampler")) scene.spp = (int)sampler->at("samples").num;
   // environment lighting (an extension; json_parser.py, the same rule): {"file": a Radiance .hdr, equirectangular, relative to the
-  // scene file; "scale": a finite number >= 0, default 1; "size": an integer in [2,4096], default the picture's height, at most 4096}
+  // scene file; "scale": a finite number >= 0, default 1; "size": an integer in [2,4096], default the picture's height, at most 4096;
+  // "light": a boolean, default false -- sample the environment as a light under the megakernel method}
   if (const Json* env = root->find("environment")) {
     const Json* file = env->kind == Json::Object ? env->find("file") : nullptr;
     bool ok = file && file->kind == Json::String;
-    for (size_t k = 0; ok && k < env->obj.size(); ++k) ok = env->obj[k].first == "file" || env->obj[k].first == "scale" || env->obj[k].first == "size";
-    if (!ok) throw std::runtime_error("Json Parser: \"environment\" must be an object with \"file\" (a string) and optionally \"scale\", \"size\"");
+    for (size_t k = 0; ok && k < env->obj.size(); ++k) ok = env->obj[k].first == "file" || env->obj[k].first == "scale" || env->obj[k].first == "size" || env->obj[k].first == "light";
+    if (!ok) throw std::runtime_error("Json Parser: \"environment\" must be an object with \"file\" (a string) and optionally \"scale\", \"size\", \"light\"");
+    if (const Json* l = env->find("light")) {
+      if (l->kind != Json::Bool) throw std::runtime_error("Json Parser: environment \"light\" must be true or false");
+      scene.environment_source.light = l->b;
+    }
     if (const Json* s = env->find("scale")) {
       if (s->kind != Json::Number || !std::isfinite(s->num) || s->num < 0.0)
         throw std::runtime_error("Json Parser: environment \"scale\" must be a finite number >= 0");

@@ -78,6 +78,7 @@ public:
     std::string file;
     float scale = 1.0f;
     int size = 0;
+    bool light = false;  // "light": true -- the scene asks for environment light sampling where the method renders it
   } environment_source;
 
   void add_material(const std::string& name, Material material);

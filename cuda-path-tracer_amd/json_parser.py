@@ -97,10 +97,13 @@ def _lens_value(cam, key, positive):
 def _environment(j, file_dir):
     """The optional scene key "environment" (an extension; scene_description.cpp, the same rule):
     {"file": a Radiance .hdr, equirectangular, relative to the scene file; "scale": a finite number >= 0, default 1; "size": the
-    octahedral map's size, an integer in [2,4096], default the image's height, at most 4096}.
-    -> (the map [n, n, 3] float32, the entry as read: file (absolute), scale, size)"""
-    if not isinstance(j, dict) or not isinstance(j.get("file"), str) or set(j) - {"file", "scale", "size"}:
-        raise ValueError("Json Parser: \"environment\" must be an object with \"file\" (a string) and optionally \"scale\", \"size\"")
+    octahedral map's size, an integer in [2,4096], default the image's height, at most 4096; "light": a boolean, default false --
+    sample the environment as a light under the megakernel method}.
+    -> (the map [n, n, 3] float32, the entry as read: file (absolute), scale, size, and light if the file gives it)"""
+    if not isinstance(j, dict) or not isinstance(j.get("file"), str) or set(j) - {"file", "scale", "size", "light"}:
+        raise ValueError("Json Parser: \"environment\" must be an object with \"file\" (a string) and optionally \"scale\", \"size\", \"light\"")
+    if not isinstance(j.get("light", False), bool):
+        raise ValueError(f"Json Parser: environment \"light\" must be true or false, got {j['light']!r}")
     scale = j.get("scale", 1.0)
     if not isinstance(scale, (int, float)) or isinstance(scale, bool) or not math.isfinite(scale) or scale < 0:
         raise ValueError(f"Json Parser: environment \"scale\" must be a finite number >= 0, got {scale!r}")
@@ -112,7 +115,7 @@ def _environment(j, file_dir):
     n = size if size is not None else min(image.shape[0], 4096)
     if n < 2:
         raise ValueError(f"Json Parser: environment image {path} is too small for a map (height {image.shape[0]}); give \"size\"")
-    return hdr.environment_from_equirect(image, n, scale), {"file": path, "scale": float(scale), "size": int(n)}
+    return hdr.environment_from_equirect(image, n, scale), {"file": path, "scale": float(scale), "size": int(n), **({"light": j["light"]} if "light" in j else {})}
 
 
 def scene_from_json(filename):

@@ -82,12 +82,27 @@ class _DirectLight:
         return self._tracer._direct_light_query(points, normals, sample_index, want_rays)
 
 
+class _EnvironmentLight:
+    """What PathTracer.environment_light is, in _DirectLight's manner: its truth value is the render loop's switch (ptc_set_param
+    "environment_light") -- assign True or False --, and called with points and normals it is the query (ptc_environment_light)."""
+
+    def __init__(self, tracer):
+        self._tracer = tracer
+
+    def __bool__(self):
+        return self._tracer._environment_light
+
+    def __call__(self, points, normals, sample_index=0, want_rays=False):
+        return self._tracer._environment_light_query(points, normals, sample_index, want_rays)
+
+
 class PathTracer:
     def __init__(self, device=0, max_bounces=50):
         self._lib = _capi.lib()
         self.max_iterations = 1
         self.current_gpu_method = GPUMethod.streaming
         self._direct_light = False  # PathTracer.direct_light = True: a light sample at every diffuse hit (megakernel method only)
+        self._environment_light = False  # PathTracer.environment_light = True: an environment sample at every diffuse hit (megakernel only)
         self._roulette = 0  # PathTracer.roulette = k: Russian roulette at every bounce >= k but the last (0 = off)
         self._lens = (0.0, 1.0)  # PathTracer.lens = (radius, focus_distance): the thin lens (radius 0 = the pinhole)
         self._environment = None  # PathTracer.environment = [n, n, 3] float32: an octahedral HDR sky (None = the reference's gradient)
@@ -100,6 +115,7 @@ class PathTracer:
         self._resolution = None
         self._rows = None
         self._direct_light_pushed = False
+        self._environment_light_pushed = False
         self._roulette_pushed = 0
         self._lens_pushed = (0.0, 1.0)
         self._environment_pushed = None
@@ -134,6 +150,16 @@ class PathTracer:
     @direct_light.setter
     def direct_light(self, on):
         self._direct_light = bool(on)
+
+    @property
+    def environment_light(self):
+        """The switch of environment light sampling in the megakernel (ptc_set_param "environment_light"; assign
+        True / False, read with bool()) and, called with points and normals, the environment-light query (ptc_environment_light)."""
+        return _EnvironmentLight(self)
+
+    @environment_light.setter
+    def environment_light(self, on):
+        self._environment_light = bool(on)
 
     @property
     def roulette(self):
@@ -200,6 +226,9 @@ class PathTracer:
         if self._direct_light != self._direct_light_pushed:  # (ptc_set_param flushes queued frames: only on a change)
             self._check(self._lib.ptc_set_param(self._ctx, b"direct_light", 1 if self._direct_light else 0))
             self._direct_light_pushed = self._direct_light
+        if self._environment_light != self._environment_light_pushed:
+            self._check(self._lib.ptc_set_param(self._ctx, b"environment_light", 1 if self._environment_light else 0))
+            self._environment_light_pushed = self._environment_light
         if self._roulette != self._roulette_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"roulette", self._roulette))
             self._roulette_pushed = self._roulette
@@ -529,6 +558,45 @@ class PathTracer:
         traced, shadow rays that arrived."""
         s = _capi.ptc_direct_loop_stats()
         self._check(self._lib.ptc_get_direct_loop_stats(self._ctx, C.byref(s)))
+        return {"diffuse_hits": int(s.diffuse_hits), "shadow_rays": int(s.shadow_rays), "unoccluded": int(s.unoccluded)}
+
+    def _environment_light_query(self, points, normals, sample_index=0, want_rays=False):
+        """One environment sample per surface point (ptc_environment_light), in _direct_light_query's shapes: radiance [n, 3] is what
+        the environment sends to a white Lambertian surface there by this sample.  Needs an environment."""
+        self._push_fields()
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        n = len(points)
+        if len(normals) != n:
+            raise ValueError("points and normals differ in length")
+        radiance = np.zeros((n, 3), dtype=np.float32)
+        rays = np.zeros((n, 8), dtype=np.float32) if want_rays else None
+        visible = np.zeros(n, dtype=np.uint8) if want_rays else None
+        self._check(self._lib.ptc_environment_light(
+            self._ctx, points.ctypes.data, normals.ctypes.data, n, int(sample_index), radiance.ctypes.data,
+            rays.ctypes.data if want_rays else None, visible.ctypes.data if want_rays else None, 0))
+        return (radiance, rays, visible) if want_rays else radiance
+
+    def environment_light_dev(self, points_ptr, normals_ptr, n, sample_index, radiance_ptr, rays_ptr=None, visible_ptr=None):
+        """environment_light on device memory, as direct_light_dev."""
+        self._push_fields()
+        self._check(self._lib.ptc_environment_light(
+            self._ctx, C.c_void_p(int(points_ptr)), C.c_void_p(int(normals_ptr)), int(n), int(sample_index),
+            C.c_void_p(int(radiance_ptr)), C.c_void_p(int(rays_ptr)) if rays_ptr else None,
+            C.c_void_p(int(visible_ptr)) if visible_ptr else None, 1))
+
+    def environment_light_stats(self):
+        """Counters of the environment-light query since reset_profile / creation."""
+        s = _capi.ptc_environment_light_stats()
+        self._check(self._lib.ptc_get_environment_light_stats(self._ctx, C.byref(s)))
+        return {"points": int(s.points), "sampled": int(s.sampled), "unoccluded": int(s.unoccluded),
+                "kernel_ms": float(s.kernel_ms), "launches": int(s.launches)}
+
+    def environment_light_loop_stats(self):
+        """Counters of the megakernel under environment_light = True since restart: hits on a diffuse material that drew an
+        environment sample, its shadow rays traced, those that arrived."""
+        s = _capi.ptc_environment_light_loop_stats()
+        self._check(self._lib.ptc_get_environment_light_loop_stats(self._ctx, C.byref(s)))
         return {"diffuse_hits": int(s.diffuse_hits), "shadow_rays": int(s.shadow_rays), "unoccluded": int(s.unoccluded)}
 
     def selftest_math(self, a, b):

@@ -152,7 +152,7 @@ class SceneDescription:
         self.resolution = (0, 0)
         self.spp = 1
         # environment lighting (an extension): the octahedral map [n, n, 3] float32 PathTracer.environment takes, or
-        # None (the reference's gradient); environment_source: the scene file's entry it came from ({"file", "scale", "size"})
+        # None (the reference's gradient); environment_source: the scene file's entry it came from ({"file", "scale", "size"}, and "light" if the file gives it)
         self.environment = None
         self.environment_source = None
 

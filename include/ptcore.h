@@ -336,6 +336,17 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *                      sampled (ptc_light_table) makes ptc_trace fail with PTC_ERR_INVALID, naming the object.  Under
  *                      PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is 1, before anything is
  *                      queued: the streaming loop does not render direct light.  Counters: ptc_get_direct_loop_stats.  Any time
+ *   "environment_light" RENDERING (default 0; an extension): 1 = under PTC_METHOD_MEGAKERNEL, in a frame whose
+ *                      environment (ptc_set_environment) has weight > 0, every hit on a diffuse material draws one environment sample
+ *                      (ptc_environment_light's, from path_seed(pixel, iteration) ^ 0x454e564c, draws 4 b .. 4 b + 3 at bounce b) with a
+ *                      shadow ray of its own, and a miss counts the environment only when the vertex before it drew no such sample (the
+ *                      camera, metal, glass).  Independent of "direct_light": with both, a diffuse hit draws the lamp's sample, then the
+ *                      environment's.  The expectation of every pixel is that of 0; normal, depth, rays_total, the lamps' stream and
+ *                      ptc_get_direct_loop_stats are bit for bit those of the same render with 0: only colour differs.  Without an
+ *                      environment, or under a map of weight 0, it renders bit for bit as with 0.  The alias table (16 n n bytes on the
+ *                      device) is built by the first ptc_trace that needs it: PTC_ERR_OOM from there, the environment stays.  Under
+ *                      PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is 1, before anything is
+ *                      queued.  Counters: ptc_get_environment_light_loop_stats.  Any time (queued frames are flushed first)
  *   "roulette"         RENDERING (default 0 = off; an extension): k in [1, 64] = Russian roulette at every bounce b >= k
  *                      except the last one, under both methods (and "direct_light").  A path whose closest hit exists and is no emitter
  *                      takes q = the largest component of the throughput that came into the bounce; q >= 1 changes nothing (no draw); else
@@ -578,6 +589,33 @@ typedef struct ptc_direct_loop_stats {
 } ptc_direct_loop_stats;
 int ptc_get_direct_loop_stats(ptc_ctx* ctx, ptc_direct_loop_stats* out);
 
+/* The environment as a light (an extension).  radiance[3i..] = radiance leaving a white Lambertian surface at
+ * points[i] with unit normal normals[i] by ONE sample of the context's environment (ptc_set_environment):
+ *   L(w) * cos_r * 4 f |w|_1^3 / pi if the shadow ray is free, else 0
+ * The distribution is piecewise constant over the n x n texel squares of the octahedral unit square, proportional to the largest
+ * channel of the lookup's integral over the square times |w_c|_1^3 at its centre (the solid angle: d omega = 4 |w|_1^3 ds_x ds_z);
+ * an alias table of one 16-byte entry per square, {q, alias, f, f of the alias} with f = 1 / (P n^2), built in binary64 on the host.
+ * Draws: Minstd seeded from path_seed(i, sample_index) xor 0x454e564c; a raw value v picks the entry ((v - 1) n^2) >> 31, u1 < q keeps
+ * its square (else the alias), u2, u3 the point in the square; the point is decoded to the unit direction w (the inverse of the lookup's
+ * octahedral map), cos_r = dot(n, w) (<= 0: no sample), L = the lookup a miss makes.  The binary32 operation order: DESIGN section 5k.
+ * Shadow ray: origin p, t_min 1e-4f, direction w, t_max FLT_MAX.  A culled sample: radiance 0, visible 0, ray = {p, 1e-4f, 0, 0, 0, 0}.
+ * Arrays, on_device, the trace variants and the statistics it leaves alone: as ptc_direct_light.  The table (16 n n bytes on the device)
+ * is built by the first call that needs it and kept until the map changes: PTC_ERR_OOM if it cannot be allocated (the environment
+ * stays).  PTC_ERR_INVALID without an environment; a map of weight 0 gives zeros and launches nothing. */
+int ptc_environment_light(ptc_ctx* ctx, const float* points, const float* normals, uint32_t n, uint32_t sample_index,
+                          float* radiance, float* shadow_rays, uint8_t* visible, int on_device);
+/* ptc_direct_stats' five fields for ptc_environment_light since ptc_reset_profile / create (the kernels: k_env_light_sample, the
+ * occlusion launches, k_light_resolve). */
+typedef ptc_direct_stats ptc_environment_light_stats;
+int ptc_get_environment_light_stats(ptc_ctx* ctx, ptc_environment_light_stats* out);
+/* The megakernel under "environment_light" 1 since ptc_restart: hits on a diffuse material that drew an environment sample, its shadow
+ * rays traced (the samples that were not culled) and those that arrived.  Synchronises.  Moves nothing else, ptc_get_direct_loop_stats
+ * included, and nothing moves it but ptc_trace and ptc_restart. */
+typedef struct ptc_environment_light_loop_stats {
+  uint64_t diffuse_hits, shadow_rays, unoccluded;
+} ptc_environment_light_loop_stats;
+int ptc_get_environment_light_loop_stats(ptc_ctx* ctx, ptc_environment_light_loop_stats* out);
+
 /* Where the time of the last ptc_upload_scene went (milliseconds of host wall clock; the "Initialization" stage of
  * the reference's Stopwatch, cli.cpp): */
 typedef struct ptc_upload_times {
@@ -684,6 +722,15 @@ int ptc_check_rng(const uint32_t* seeds, const uint32_t* discards, uint32_t n, u
 int ptc_check_environment(const float* rgb, uint32_t n, const float* dirs, uint32_t count, float* rgb_out);
 /* ... and the map as ptc_set_environment uploads it: (n + 2) x (n + 2) texels of four floats {r, g, b, 0}, the apron filled in. */
 int ptc_check_environment_apron(const float* rgb, uint32_t n, float* texels_out);
+/* The environment's alias table (csrc/pt_env_light.hpp) as the first call that needs it builds it, on the host: no
+ * GPU, no context; test hook.  entries_out (may be NULL): n n entries of 16 bytes {float q, uint32 alias, float f, float f of the
+ * alias}, in table order k = j n + i; zeros for a map of weight 0.  *total_weight = W, *positive_squares = the squares of weight > 0. */
+int ptc_check_environment_light_table(const float* rgb, uint32_t n, void* entries_out, double* total_weight, uint64_t* positive_squares);
+/* ... and the sample on `count` caller-given points, normals and draws (v[i]: a raw value 1 .. 2^31 - 2; u + 3 i: u1, u2, u3), written as
+ * ptc_environment_light writes a sample whose shadow ray is free: radiance 3 floats, shadow_rays 8 floats (may be NULL), sampled one
+ * byte (may be NULL) per point.  PTC_ERR_INVALID: a NULL, n out of range, a bad component, a v out of range. */
+int ptc_check_environment_light(const float* rgb, uint32_t n, const float* points, const float* normals, const uint32_t* v, const float* u,
+                                uint32_t count, float* radiance, float* shadow_rays, uint8_t* sampled);
 
 #ifdef __cplusplus
 }
