@@ -124,6 +124,10 @@ class ptc_environment_light_loop_stats(C.Structure):
     _fields_ = [("diffuse_hits", C.c_uint64), ("shadow_rays", C.c_uint64), ("unoccluded", C.c_uint64)]
 
 
+class ptc_mis_loop_stats(C.Structure):
+    _fields_ = [("weighted_emitter_hits", C.c_uint64), ("weighted_misses", C.c_uint64)]
+
+
 ptc_environment_light_stats = ptc_direct_stats  # the same five fields (include/ptcore.h)
 
 
@@ -223,6 +227,10 @@ SIGNATURES = {
     "ptc_get_environment_light_stats": (C.c_int, [_P, C.POINTER(ptc_direct_stats)]),
     "ptc_get_environment_light_loop_stats": (C.c_int, [_P, C.POINTER(ptc_environment_light_loop_stats)]),
     "ptc_check_environment_light_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "ptc_environment_light_pdf": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_int]),
+    "ptc_light_material_pdf": (C.c_int, [C.POINTER(ptc_scene_desc), _P, C.c_uint32]),
+    "ptc_get_mis_loop_stats": (C.c_int, [_P, C.POINTER(ptc_mis_loop_stats)]),
+    "ptc_check_environment_light_pdf": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptc_check_environment_light": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
 }

@@ -562,6 +562,21 @@ void launch_env_light_sample(hipStream_t s, DEnv env, DEnvLight el, const float*
 void launch_megakernel_env_light(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
                                  uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
                                  DLens lens, DEnv env, DEnvLight el);
+// Multiple importance sampling in the megakernel (ptc_set_param "mis"; pt_mis.hpp).  inv_pdf_m: per material of the
+// scene the inv_pdf every lamp record of that material carries, (float)(W / lum), 0 for a material that is no lamp or has lum 0; the
+// scene's own allocation beside the lamp table, null without one.
+struct DMis {
+  const float* inv_pdf_m;
+};
+// the megakernel's multiple-importance instance ("mis" 1 in a frame that samples lamps, the environment or both; pt_mega_mis.hip):
+// launch_megakernel_env_light's loop with the balance heuristic at diffuse vertices.  lights.records null: no lamp samples; el.table
+// null: no environment samples; env.texels null: no environment, the gradient.  stats words 6, 7 of a line += emitter hits, misses
+// behind a diffuse vertex that were weighted
+void launch_megakernel_mis(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
+                           uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
+                           DLens lens, DEnv env, DEnvLight el, DMis mis);
+// ptc_environment_light_pdf's kernel (pt_env.hip): one thread per unit direction, env_light::density
+void launch_env_light_pdf(hipStream_t s, DEnvLight el, uint32_t n, const float* dirs, uint32_t count, float* pdf);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,
                      float* out_sin, float* out_cos);
 void launch_selftest_rng(hipStream_t s, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out);

@@ -67,6 +67,21 @@ void launch_env_light_sample(hipStream_t s, DEnv env, DEnvLight el, const float*
                      contrib);
 }
 
+// ptc_environment_light_pdf's kernel: one thread per unit direction, env_light::density -- one 16-byte load of the
+// table entry the direction falls in (square_of clamps the square into the table).  No LDS, no cross-lane work.
+__global__ __launch_bounds__(256) void k_env_light_pdf(DEnvLight el, uint32_t n, const float* __restrict__ dirs, uint32_t count,
+                                                       float* __restrict__ pdf)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= count) return;
+  pdf[i] = env_light::density(el.table, n, mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]));
+}
+
+void launch_env_light_pdf(hipStream_t s, DEnvLight el, uint32_t n, const float* dirs, uint32_t count, float* pdf)
+{
+  hipLaunchKernelGGL(k_env_light_pdf, dim3(div_up(count, 256u)), dim3(256), 0, s, el, n, dirs, count, pdf);
+}
+
 // launch_raygen's finishing form (a listed first launch that walks the whole object list) under an environment
 void launch_raygen_env(hipStream_t s, const DCameras& cams, const DBatchInfo& bi, DBand band, uint32_t pix_count, DPaths paths,
                        DeviceCounters* counters, const DObject* objects, uint32_t filt_begin, uint32_t filt_end, uint32_t* worklist, DHits hits,

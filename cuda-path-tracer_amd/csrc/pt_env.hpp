@@ -45,17 +45,25 @@ PT_ENV_HD float mix(const float x, const float y, const float a) { return x * (1
 
 // Where the direction (dx, dy, dz), not normalised, falls on E.  False: the value is (0, 0, 0) and nothing is to be loaded -- a zero
 // direction, a NaN, an infinity, a sum that overflows.
-PT_ENV_HD bool locate(const float dx, const float dy, const float dz, const uint32_t n, uint32_t& i0, uint32_t& j0, float& tx, float& tz)
+// (project: its point (qx, qz) of the octahedral square [-1, 1]^2, which the environment light's density reads as well, pt_env_light.hpp)
+PT_ENV_HD bool project(const float dx, const float dy, const float dz, float& qx, float& qz)
 {
   const float a = (fabsf(dx) + fabsf(dy)) + fabsf(dz);
   if (!(a > 0.0f) || !(a <= FLT_MAX)) return false;
   const float px = dx / a;
   const float pz = dz / a;
-  float qx = px, qz = pz;
+  qx = px, qz = pz;
   if (dy < 0.0f) {  // the lower hemisphere folds outwards (dy = -0: the upper rule)
     qx = (1.0f - fabsf(pz)) * sgn(px);
     qz = (1.0f - fabsf(px)) * sgn(pz);
   }
+  return true;
+}
+
+PT_ENV_HD bool locate(const float dx, const float dy, const float dz, const uint32_t n, uint32_t& i0, uint32_t& j0, float& tx, float& tz)
+{
+  float qx, qz;
+  if (!project(dx, dy, dz, qx, qz)) return false;
   axis(qx, n, i0, tx);
   axis(qz, n, j0, tz);
   return true;

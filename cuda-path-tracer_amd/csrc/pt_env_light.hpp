@@ -9,6 +9,7 @@
 
 #include "pt_device.hpp"
 #include "pt_rng.hpp"
+#include "pt_mis.hpp"
 
 #include <float.h>
 #include <cmath>
@@ -73,10 +74,17 @@ PT_HD f3 decode(const float sx, const float sz, float& l3)
   return w;
 }
 
+// What a sample's two solid-angle densities are made of (multiple importance sampling): jac = (4 f) l^3, the
+// reciprocal of the sample's own density, and the cosine at the receiver, as the contribution takes them.
+struct Terms {
+  float jac, cos_r;
+};
+
 // One environment sample for the point with normal nrm from explicit draws: v raw, u1 .. u3 uniform.  E: the aproned map (pt_env.hpp).
+// terms: the sample's Terms.
 template <class Texel>
 PT_HD Sample sample_draws(const uint4* table, const Texel* E, const uint32_t n, const f3 nrm, const uint32_t v, const float u1, const float u2,
-                          const float u3)
+                          const float u3, Terms& terms)
 {
   uint32_t k;
   float f;
@@ -103,14 +111,23 @@ PT_HD Sample sample_draws(const uint4* table, const Texel* E, const uint32_t n, 
   out.tmax = sampled ? FLT_MAX : 0.0f;
   out.contrib = sampled ? mk3(r * gk, g * gk, b * gk) : mk3(0.0f, 0.0f, 0.0f);
   out.sampled = sampled;
+  terms = Terms{jac, cos_r};
   return out;
+}
+// ... for the callers that take the sample alone
+template <class Texel>
+PT_HD Sample sample_draws(const uint4* table, const Texel* E, const uint32_t n, const f3 nrm, const uint32_t v, const float u1, const float u2,
+                          const float u3)
+{
+  Terms terms;
+  return sample_draws(table, E, n, nrm, v, u1, u2, u3, terms);
 }
 
 // ... from the point's stream: Minstd seeded path_seed(index, sample_index) ^ kEnvLightSeedXor, four draws after `discard` (0 for a
 // query, 4 * bounce in the render loop: bounce b takes draws 4b .. 4b + 3)
 template <class Texel>
 PT_HD Sample sample_point(const uint4* table, const Texel* E, const uint32_t n, const f3 nrm, const uint32_t index, const uint32_t sample_index,
-                          const uint32_t discard)
+                          const uint32_t discard, Terms& terms)
 {
   Minstd rng;
   rng.seed(path_seed(index, sample_index) ^ kEnvLightSeedXor);
@@ -119,7 +136,49 @@ PT_HD Sample sample_point(const uint4* table, const Texel* E, const uint32_t n, 
   const float u1 = rng.uniform();
   const float u2 = rng.uniform();
   const float u3 = rng.uniform();
-  return sample_draws(table, E, n, nrm, v, u1, u2, u3);
+  return sample_draws(table, E, n, nrm, v, u1, u2, u3, terms);
+}
+template <class Texel>
+PT_HD Sample sample_point(const uint4* table, const Texel* E, const uint32_t n, const f3 nrm, const uint32_t index, const uint32_t sample_index,
+                          const uint32_t discard)
+{
+  Terms terms;
+  return sample_point(table, E, n, nrm, index, sample_index, discard, terms);
+}
+
+// ---- the sample's density (multiple importance sampling, ptc_set_param "mis") -------------------------------------
+
+// The reciprocal of jac = (4 f) l^3, the environment's solid-angle density; f == 0 (a square of weight 0): 0
+PT_HD float env_density(const float jac) { return jac > 0.0f ? 1.0f / jac : 0.0f; }
+
+// The square k = j n + i the point (qx, qz) of the octahedral square (env_rules::project) falls in
+PT_HD uint32_t square_of(const float qx, const float qz, const uint32_t n)
+{
+  const float fn = (float)n;
+  const float mx = qx * 0.5f;
+  const float sx = mx + 0.5f;
+  const float fx = floorf(sx * fn);
+  const float mz = qz * 0.5f;
+  const float sz = mz + 0.5f;
+  const float fz = floorf(sz * fn);
+  const uint32_t i = fx >= fn ? n - 1u : (fx > 0.0f ? (uint32_t)fx : 0u);
+  const uint32_t j = fz >= fn ? n - 1u : (fz > 0.0f ? (uint32_t)fz : 0u);
+  return j * n + i;
+}
+
+// The environment sample's density in the unit direction w: one 16-byte load of the square's own entry, whose f_self is f of the
+// square (build_table).  A direction env_rules::project refuses (zero, NaN, infinite) has density 0 and loads nothing.
+PT_HD float density(const uint4* table, const uint32_t n, const f3 w)
+{
+  float qx, qz;
+  if (!env_rules::project(w.x, w.y, w.z, qx, qz)) return 0.0f;
+  const uint4 t = table[square_of(qx, qz, n)];
+  const float f = __builtin_bit_cast(float, t.z);
+  const float l1 = (__builtin_fabsf(w.x) + __builtin_fabsf(w.y)) + __builtin_fabsf(w.z);
+  const float l3 = (l1 * l1) * l1;
+  const float ff = 4.0f * f;
+  const float jac = ff * l3;
+  return env_density(jac);
 }
 
 // The table of the aproned map E (host, binary64 from the binary32 texels).  Per square the filtered colour -- the

@@ -1,5 +1,5 @@
 // pt_light_sample.hpp -- one light sample for one surface point: the function k_light_sample (pt_light.hip) and
-// k_megakernel_direct (pt_mega_direct.hip) both call.  Host-callable, so that the arithmetic can be run on a CPU
+// k_megakernel_direct (pt_mega_direct.hip) both call, and k_megakernel_mis (pt_mega_mis.hip, section 5l) with the sample's terms.  Host-callable, so that the arithmetic can be run on a CPU
 // as well.
 //
 // Every line of the arithmetic is one IEEE binary32 operation of the order written down in DESIGN section 5f (-ffp-contract=off,
@@ -20,9 +20,16 @@ struct LightSample {
   f3 contrib;     // unshadowed contribution
   bool sampled;
 };
+// What a sample's two solid-angle densities are made of (multiple importance sampling): the squared distance, the
+// cosine at the lamp, the record's inv_pdf and the cosine at the receiver, as the contribution's g takes them.
+struct LightTerms {
+  float d2, cos_l, inv_pdf, cos_r;
+};
 // discard: draws of the point's light stream to skip first -- 0 for a query (k_light_sample), 3 * bounce in the render loop, whose
 // bounce b so takes draws 3b .. 3b + 2 of the stream (discard(0) leaves a generator as it is, so it is not executed)
-PT_HD LightSample light_sample_point(const DLights& lt, const f3 p, const f3 nrm, uint32_t i, uint32_t sample_index, uint32_t discard)
+// terms: the sample's LightTerms (meaningful where the sample is `sampled`)
+PT_HD LightSample light_sample_point(const DLights& lt, const f3 p, const f3 nrm, uint32_t i, uint32_t sample_index, uint32_t discard,
+                                     LightTerms& terms)
 {
   Minstd rng;
   rng.seed(path_seed(i, sample_index) ^ kLightSeedXor);
@@ -83,7 +90,14 @@ PT_HD LightSample light_sample_point(const DLights& lt, const f3 p, const f3 nrm
   out.tmax = sampled ? d * 0.999f : 0.0f;
   out.contrib = sampled ? le * g : mk3(0.0f, 0.0f, 0.0f);
   out.sampled = sampled;
+  terms = LightTerms{d2, cos_l, inv_pdf, cos_r};
   return out;
+}
+// ... for the callers that take the sample alone
+PT_HD LightSample light_sample_point(const DLights& lt, const f3 p, const f3 nrm, uint32_t i, uint32_t sample_index, uint32_t discard)
+{
+  LightTerms terms;
+  return light_sample_point(lt, p, nrm, i, sample_index, discard, terms);
 }
 
 }  // namespace pt

@@ -1,7 +1,8 @@
 // pt_megakernel.inc -- the megakernel's loop, the whole path in one thread: mega_path, and k_megakernel around it.  Included (inside
 // namespace pt, after pt_kernels_common.inc and with pt_light_sample.hpp in front) by pt_kernels.hip, which instantiates the plain
 // instances beside the closest-hit kernels as ever, and by pt_mega_direct.hip, which instantiates the kRoulette ones and
-// k_megakernel_direct: the code object that holds the traversal kernels stays the one it was (DESIGN section 5h).
+// k_megakernel_direct, and by pt_mega_mis.hip, which instantiates k_megakernel_mis (kMis, DESIGN section 5l): the code object that
+// holds the traversal kernels stays the one it was (DESIGN section 5h).
 // path_tracing_mega_kernel, path_tracer.cu:227-269: the whole path in one thread, one RNG stream per
 // pixel (a different image from streaming mode at the same seed -- a property of the reference).
 // kEmit: the scene has an emissive material (the host's choice; without one the instance is the reference's loop as it was).
@@ -32,20 +33,32 @@
 // count_env.  The lamps are a run-time choice here: lt.records null (a wave-uniform kernel argument) is a frame without "direct_light"
 // or without a lamp table, which draws no lamp sample and counts every emitter.  stats words 3 .. 5 += diffuse hits that drew an
 // environment sample, its shadow rays, the unoccluded ones.  k_megakernel_env_light, pt_mega_direct.hip.
-template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false, bool kEnv = false, bool kEnvLight = false>
+// kMis (with kEnvLight; ptc_set_param "mis", DESIGN section 5l; k_megakernel_mis, pt_mega_mis.hip): the balance heuristic between each
+// light sample and the path's own continuation ray at diffuse vertices.  One more float of path state, bsdf_pdf -- the cosine lobe's
+// density of the direction evaluate_material drew, read only while count_emission or count_env is false.  A lamp's and the
+// environment's sample are weighted against the lobe's density of their direction (not at the last bounce, which has no continuation
+// ray); an emitter hit and a miss behind a diffuse vertex count with the lobe's weight against the light sampler's density of that
+// hit instead of 0: mis.inv_pdf_m[material], loaded beside the material, and env_light::density, whose load stands in front of the
+// sky's texel loads.  Here the environment light is a run-time choice as well (el.table null: none) and so is the environment
+// (env.texels null: the gradient).  Every draw, every closest hit and shadow ray and the six counters are those of the loop without it.
+// stats words 6 and 7 += emitter hits and misses behind a diffuse vertex that were weighted.
+template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false, bool kEnv = false, bool kEnvLight = false, bool kMis = false>
 __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, const DCamera& cam, const uint32_t iteration, const DBand band,
                                           const uint32_t pix_count, const int max_bounces, const DFrame fb, DeviceCounters* counters,
                                           unsigned long long* stats, const int roulette, uint32_t* stack,
                                           const DLens lens = DLens{0.0f, 0.0f}, const DEnv env = DEnv{nullptr, 0u, 0u},
-                                          const DEnvLight el = DEnvLight{nullptr})
+                                          const DEnvLight el = DEnvLight{nullptr}, const DMis mis = DMis{nullptr})
 {
   static_assert(!kEnvLight || (kEnv && kDirect), "the environment-light instance has an environment and a radiance sum");
+  static_assert(!kMis || kEnvLight, "the multiple-importance instance samples lamps and environment by run-time choice");
   static_assert(kEmit || !kDirect, "direct lighting: launched only for a scene with a lamp table, so with an emissive material");
   const uint32_t s = blockIdx.x * kWave + threadIdx.x;
   uint32_t rays = 0u, flags = 0u;
   uint32_t n_diffuse = 0u, n_shadow = 0u, n_clear = 0u;
   uint32_t e_diffuse = 0u, e_shadow = 0u, e_clear = 0u;
+  [[maybe_unused]] uint32_t m_emit = 0u, m_miss = 0u;
   const bool lamps = !kEnvLight || lt.records != nullptr;
+  const bool env_lamp = !kMis || el.table != nullptr;  // (kEnvLight) the environment is sampled
   if (s < pix_count) {
     const uint32_t pixel = band_pixel(band, s);
     Minstd rng;
@@ -60,6 +73,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
     f3 radiance = mk3(0.0f, 0.0f, 0.0f);
     bool count_emission = true;  // the last vertex drew no light sample (the camera, metal, glass): a lamp hit from it counts
     bool count_env = true;       // (kEnvLight) ... no environment sample: a miss from it counts the environment
+    [[maybe_unused]] float bsdf_pdf = 0.0f;  // (kMis) the lobe's density of ray.d, behind a diffuse vertex
     f3 normal = -ray.d;
     float depth = 1e6f;
     for (int i = 0; i < max_bounces; ++i) {
@@ -71,6 +85,17 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       ++rays;
       Tally tally;
       if (!ray_scene<false>(ray, sc, rec, stack, flags, tally)) {
+        if constexpr (kMis) {
+          if (!count_env) {  // behind an environment sample: the lobe's share of the sky it reached (the entry's load first)
+            ++m_miss;
+            const float p_e = env_light::density(el.table, env.n, ray.d);
+            const f3 seen = color * sky<true>(ray.d, env);
+            color = seen * mis::balance(bsdf_pdf, p_e);
+          } else {
+            color = env.texels ? color * sky<true>(ray.d, env) : color * sky<false>(ray.d, env);
+          }
+          break;
+        }
         if (kEnvLight && !count_env) color = mk3(0.0f, 0.0f, 0.0f);  // the environment sample of the vertex before has counted it
         else color = color * sky<kEnv>(ray.d, env);
         break;
@@ -81,6 +106,22 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       }
       bool tmin_flag = ray.tmin != 1e-4f;
       const DMaterial& mat = sc.materials[rec.mat];
+      [[maybe_unused]] float inv_pdf_m = 0.0f;
+      if constexpr (kMis) {
+        if (lamps) inv_pdf_m = mis.inv_pdf_m[rec.mat];
+        if (is_emitter(mat)) {  // behind a diffuse vertex: the lobe's share of the lamp it reached, against the lamp sampler's density there
+          if (count_emission) {
+            color = emit_color(color, mat);
+          } else {
+            ++m_emit;
+            const float cos_l = __builtin_fabsf(dot(rec.n, ray.d));
+            const float t2 = rec.t * rec.t;
+            const float p_l = mis::lamp_density(t2, cos_l, inv_pdf_m);
+            color = emit_color(color, mat) * mis::balance(bsdf_pdf, p_l);
+          }
+          break;
+        }
+      }
       if (kEmit && is_emitter(mat)) {  // the path ends at the emitter: no draw; after a diffuse vertex its light sample has counted the lamp
         color = !kDirect || count_emission ? emit_color(color, mat) : mk3(0.0f, 0.0f, 0.0f);
         break;
@@ -93,16 +134,36 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       ray.tmin = tmin_flag ? 1e-5f : 1e-4f;
       if constexpr (kDirect) {
         if (lamps) count_emission = mat.type != 0;
-        if constexpr (kEnvLight) count_env = mat.type != 0;
+        if constexpr (kEnvLight) {
+          if (env_lamp) count_env = mat.type != 0;
+        }
         if (mat.type == 0) {  // diffuse: colour is throughput x albedo now; one light sample at the hit, about the unflipped normal
           [[maybe_unused]] env_light::Sample es;  // (kEnvLight) the environment's sample: drawn first, its loads ahead of the lamp's shadow ray
-          if constexpr (kEnvLight) {
+          [[maybe_unused]] const bool weigh = kMis && i != max_bounces - 1;  // the last bounce has no continuation ray to weigh against
+          if constexpr (kMis) bsdf_pdf = mis::lobe_density(dot(rec.n, ray.d));
+          if constexpr (kMis) {
+            es.sampled = false;
+            if (env_lamp) {
+              ++e_diffuse;
+              env_light::Terms et;
+              es = env_light::sample_point(el.table, env.texels, env.n, rec.n, pixel, iteration, 4u * (uint32_t)i, et);
+              if (weigh) es.contrib = es.contrib * mis::balance(env_light::env_density(et.jac), mis::lobe_density(et.cos_r));
+            }
+          } else if constexpr (kEnvLight) {
             ++e_diffuse;
             es = env_light::sample_point(el.table, env.texels, env.n, rec.n, pixel, iteration, 4u * (uint32_t)i);
           }
           if (lamps) {
             ++n_diffuse;
-            const LightSample ls = light_sample_point(lt, rec.p, rec.n, pixel, iteration, 3u * (uint32_t)i);
+            [[maybe_unused]] LightTerms lterms;
+            LightSample ls;
+            if constexpr (kMis) {
+              ls = light_sample_point(lt, rec.p, rec.n, pixel, iteration, 3u * (uint32_t)i, lterms);
+              if (weigh)
+                ls.contrib = ls.contrib * mis::balance(mis::lamp_density(lterms.d2, lterms.cos_l, lterms.inv_pdf), mis::lobe_density(lterms.cos_r));
+            } else {
+              ls = light_sample_point(lt, rec.p, rec.n, pixel, iteration, 3u * (uint32_t)i);
+            }
             if (ls.sampled) {
               ++n_shadow;
               Ray shadow;
@@ -139,6 +200,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
   }
   // one atomic per counter and wavefront; the three loop counters spread over lines (adds to one line serialise in L2)
   uint32_t sum = rays, sd = n_diffuse, ss = n_shadow, sv = n_clear, ed = e_diffuse, es = e_shadow, ev = e_clear;
+  [[maybe_unused]] uint32_t me = m_emit, mm = m_miss;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     sum += __shfl_down(sum, off, 64);
@@ -152,6 +214,10 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       es += __shfl_down(es, off, 64);
       ev += __shfl_down(ev, off, 64);
     }
+    if constexpr (kMis) {
+      me += __shfl_down(me, off, 64);
+      mm += __shfl_down(mm, off, 64);
+    }
   }
   if (threadIdx.x == 0u) {
     if (sum) atomicAdd(&counters->rays_total, (unsigned long long)sum);
@@ -164,6 +230,10 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
         if (ed) atomicAdd(&line[3], (unsigned long long)ed);
         if (es) atomicAdd(&line[4], (unsigned long long)es);
         if (ev) atomicAdd(&line[5], (unsigned long long)ev);
+      }
+      if constexpr (kMis) {
+        if (me) atomicAdd(&line[6], (unsigned long long)me);
+        if (mm) atomicAdd(&line[7], (unsigned long long)mm);
       }
     }
   }

@@ -582,6 +582,25 @@ int ptc_check_environment_light(const float* rgb, uint32_t n, const float* point
   return PTC_OK;
 }
 
+// ... and the sample's density (env_light::density) in `count` caller-given unit directions, as
+// ptc_environment_light_pdf returns it; a map of weight 0: zeros
+int ptc_check_environment_light_pdf(const float* rgb, uint32_t n, const float* dirs, uint32_t count, float* pdf_out)
+{
+  if (!rgb || n < env_rules::kMinSize || n > env_rules::kMaxSize) return PTC_ERR_INVALID;
+  if (count != 0u && (!dirs || !pdf_out)) return PTC_ERR_INVALID;
+  for (size_t k = 0; k < 3u * (size_t)n * n; ++k)
+    if (!(rgb[k] >= 0.0f) || !std::isfinite(rgb[k])) return PTC_ERR_INVALID;
+  std::vector<float4> e((size_t)(n + 2u) * (n + 2u));
+  env_rules::apron(rgb, n, e.data());
+  std::vector<env_light::Entry> entries;
+  const bool table = env_light::build_table(e.data(), n, entries, nullptr) > 0.0;
+  for (uint32_t i = 0; i < count; ++i)
+    pdf_out[i] = table ? env_light::density(reinterpret_cast<const uint4*>(entries.data()), n,
+                                            mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]))
+                       : 0.0f;
+  return PTC_OK;
+}
+
 // ... and on the device
 int ptc_selftest_rng(ptc_ctx* ctx, const uint32_t* seeds, const uint32_t* discards, uint32_t n, uint32_t* out)
 {

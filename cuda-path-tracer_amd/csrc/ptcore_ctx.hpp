@@ -69,6 +69,7 @@ struct ptc_scene_state {
   uint32_t light_last = 0;               // last record with a weight > 0
   const float4* light_records = nullptr; // device: 4 float4 per record (ptc_light); null while there is nothing to sample
   const float* light_cdf = nullptr;      // device: the records' cdf values, dense (the binary search)
+  const float* light_material_pdf = nullptr;  // device: per material its records' inv_pdf, 0 for no lamp ("mis"); with the table
 };
 
 // the last epoch of a lap of look-back launches on a slot's tile descriptors (30 bits: pt_shade_tile.inc; ptcore_trace.cpp, next_epoch)
@@ -280,10 +281,14 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   // built by the first call that needs it (env_light_table), freed where the map is freed.  env_table_known: that call has been made
   // for this map -- a null table then means a map of weight 0
   bool environment_light = false;
+  // "mis" (DESIGN section 5l): a frame that samples lamps or the environment combines each sample with the path's own continuation ray
+  // by the balance heuristic (k_megakernel_mis); a frame that samples neither launches what it launched before
+  bool mis = false;
   const uint4* env_table = nullptr;
   bool env_table_known = false;
   ptc_environment_light_stats env_direct{};  // ptc_environment_light since ptc_reset_profile
-  // device: kLightStatLines lines of kLoopStatWords words (0 .. 2 the lamps': diffuse hits, shadow rays, unoccluded; 3 .. 5 the environment's)
+  // device: kLightStatLines lines of kLoopStatWords words (0 .. 2 the lamps': diffuse hits, shadow rays, unoccluded; 3 .. 5 the environment's;
+  // 6, 7 "mis": weighted emitter hits, weighted misses)
   unsigned long long* loop_stats = nullptr;
   bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
 };

@@ -569,4 +569,54 @@ int ptc_sample_environment(ptc_ctx* ctx, const float* dirs, uint32_t count, floa
   return PTC_OK;
 }
 
+// The environment sample's solid-angle density in the caller's unit directions: env_light::density, the function a
+// miss behind a diffuse vertex calls under "mis", on the context's table -- built here if no call has needed it since the map was set.
+// A map of weight 0: zeros, nothing launched.  Queued frames are flushed first; no statistics move.
+int ptc_environment_light_pdf(ptc_ctx* ctx, const float* dirs, uint32_t count, float* pdf_out, int on_device)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (!ctx->env.texels) return fail(ctx, PTC_ERR_INVALID, "no environment is set (ptc_set_environment)");
+  if (count == 0u) return PTC_OK;
+  if (!dirs || !pdf_out) return fail(ctx, PTC_ERR_INVALID, "dirs or pdf_out is NULL");
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = flush_pending(ctx)) return rc;
+  if (int rc = env_light_table(ctx)) return rc;
+  const DEnvLight el{ctx->env_table};
+  const size_t in_bytes = 3u * (size_t)count * sizeof(float), out_bytes = (size_t)count * sizeof(float);
+  hipError_t e = hipSuccess;
+  if (on_device) {
+    if (!el.table) {
+      e = hipMemsetAsync(pdf_out, 0, out_bytes, ctx->stream);
+    } else {
+      launch_env_light_pdf(ctx->stream, el, ctx->env.n, dirs, count, pdf_out);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("environment light pdf: ") + hipGetErrorString(e));
+    return PTC_OK;
+  }
+  if (!el.table) {
+    std::memset(pdf_out, 0, out_bytes);
+    return PTC_OK;
+  }
+  std::vector<void*> pool;
+  float *d_dirs = nullptr, *d_out = nullptr;
+  int rc = dev_alloc(ctx, pool, &d_dirs, 3u * (size_t)count);
+  if (!rc) rc = dev_alloc(ctx, pool, &d_out, (size_t)count);
+  if (rc) {
+    free_pool(pool);
+    return rc;
+  }
+  e = hipMemcpyAsync(d_dirs, dirs, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    launch_env_light_pdf(ctx->stream, el, ctx->env.n, d_dirs, count, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(pdf_out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  free_pool(pool);
+  if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("environment light pdf: ") + hipGetErrorString(e));
+  return PTC_OK;
+}
+
 }  // extern "C"

@@ -397,6 +397,20 @@ int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_
   return PTC_OK;
 }
 
+// Per material the inv_pdf every lamp record of that material carries (multiple importance sampling): (float)(W / lum)
+// with build_light_table's lum and W = its total weight; 0 for a material that is not emissive, for lum == 0 and for a table of weight 0.
+void light_material_pdf(const ptc_scene_desc* s, double total_weight, std::vector<float>& out)
+{
+  out.assign(s->material_count, 0.0f);
+  if (!(total_weight > 0.0)) return;
+  for (uint32_t m = 0; m < s->material_count; ++m) {
+    const ptc_material& mat = s->materials[m];
+    if (mat.type != 3) continue;
+    const float lum = std::max(std::max(mat.p[0], mat.p[1]), mat.p[2]);
+    out[m] = lum == 0.0f ? 0.0f : (float)(total_weight / (double)lum);
+  }
+}
+
 }  // namespace ptcd
 
 namespace {
@@ -458,6 +472,7 @@ struct MeshWork {
 struct NewScene : ptc_scene_state {
   std::vector<ptc_light> lights;
   std::vector<float> cdf;          // the records' cdf values; empty: nothing to sample
+  std::vector<float> material_pdf; // per material the records' inv_pdf (light_material_pdf); uploaded with the lamp table
   std::vector<float4> balls;       // DScene::sphere_ball
   std::vector<uint32_t> tri_base;  // DScene::object_tri_base
   size_t tri_records = 0;          // records of DScene::tris
@@ -541,6 +556,7 @@ int stage_host(ptc_ctx* ctx, const ptc_scene_desc* s, const std::vector<MeshWork
   if (build_light_table(s, n.lights, &n.light_info, &n.light_last, &n.light_error) != PTC_OK) n.light_info = ptc_light_info{};
   if (n.light_info.total_weight > 0.0)
     for (const ptc_light& l : n.lights) n.cdf.push_back(l.cdf);
+  if (!n.cdf.empty()) light_material_pdf(s, n.light_info.total_weight, n.material_pdf);
   for (uint32_t i = 0; i < s->material_count; ++i) n.has_emitters |= s->materials[i].type == 3;
   sphere_table(s, n.balls, n.sphere_class);
   // per mesh OBJECT (instance): its mesh and the first of its world-space triangle records, which end with one all-zero
@@ -585,6 +601,7 @@ int upload_tables(ptc_ctx* ctx, const ptc_scene_desc* s, NewScene& n)
     static_assert(sizeof(ptc_light) == 4 * sizeof(float4), "a lamp record is four float4");
     if (int rc = upload(ctx, pool, &n.light_records, reinterpret_cast<const float4*>(n.lights.data()), 4u * n.lights.size())) return rc;
     if (int rc = upload(ctx, pool, &n.light_cdf, n.cdf.data(), n.cdf.size())) return rc;
+    if (int rc = upload(ctx, pool, &n.light_material_pdf, n.material_pdf.data(), n.material_pdf.size())) return rc;
   }
   const DObject* objects = nullptr;
   if (int rc = upload(ctx, pool, &objects, reinterpret_cast<const DObject*>(s->objects), s->object_count)) return rc;
@@ -825,6 +842,22 @@ int ptc_light_table(const ptc_scene_desc* scene, ptc_light* out, uint32_t capaci
   if (!lights.empty()) std::memcpy(out, lights.data(), lights.size() * sizeof(ptc_light));
   if (info) *info = li;
   return (int)lights.size();
+}
+
+int ptc_light_material_pdf(const ptc_scene_desc* scene, float* out, uint32_t capacity)
+{
+  if (!scene || !out) return fail(nullptr, PTC_ERR_INVALID, "scene or out is NULL");
+  if (int rc = validate_scene(nullptr, scene)) return rc;
+  std::vector<ptc_light> lights;
+  ptc_light_info li{};
+  std::string err;
+  if (int rc = build_light_table(scene, lights, &li, nullptr, &err)) return fail(nullptr, rc, err);
+  if (scene->material_count > capacity)
+    return fail(nullptr, PTC_ERR_INVALID, "capacity " + std::to_string(capacity) + " is too small for " + std::to_string(scene->material_count) + " materials");
+  std::vector<float> pdf;
+  light_material_pdf(scene, li.total_weight, pdf);
+  if (!pdf.empty()) std::memcpy(out, pdf.data(), pdf.size() * sizeof(float));
+  return (int)pdf.size();
 }
 
 int ptc_get_light_info(ptc_ctx* ctx, ptc_light_info* out)

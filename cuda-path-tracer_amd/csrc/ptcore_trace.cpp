@@ -13,6 +13,9 @@ constexpr const char* kDirectNeedsMegakernel =
 // ... and "environment_light" 1
 const char* const kEnvLightNeedsMegakernel =
     "environment_light is rendered by the megakernel method only (ptc_set_method(PTC_METHOD_MEGAKERNEL)); the streaming loop has no direct lighting";
+// ... and "mis" 1
+const char* const kMisNeedsMegakernel =
+    "mis is rendered by the megakernel method only (ptc_set_method(PTC_METHOD_MEGAKERNEL)); the streaming loop has no direct lighting";
 
 // the epoch of the next look-back launch on a slot's tile descriptors (k_shade_fused, the listing k_raygen / k_spheres).  After
 // kMaxEpoch the epochs start at 1 again, and a descriptor that no launch of the finished lap has overwritten (a tile above a band
@@ -553,6 +556,7 @@ int ptc_trace_begin(ptc_ctx* ctx, const ptc_camera* camera)
   if (ctx->active_slot >= 0) return fail(ctx, PTC_ERR_INVALID, "ptc_trace_end missing");
   if (ctx->direct_light) return fail(ctx, PTC_ERR_INVALID, kDirectNeedsMegakernel);  // (the stepwise calls are the streaming loop)
   if (ctx->environment_light) return fail(ctx, PTC_ERR_INVALID, kEnvLightNeedsMegakernel);
+  if (ctx->mis) return fail(ctx, PTC_ERR_INVALID, kMisNeedsMegakernel);
   // (ptc_trace stops at max_iterations; nothing else stands between the stepwise calls and ptc_trace_end's ++iteration)
   if (ctx->iteration == INT_MAX) return fail(ctx, PTC_ERR_INVALID, "the iteration counter is at INT_MAX: ptc_restart or ptc_set_iteration first");
   if (int rc = flush_pending(ctx)) return rc;
@@ -632,6 +636,7 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
   if (ctx->direct_light && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kDirectNeedsMegakernel);
   if (ctx->direct_light && !ctx->light_error.empty()) return fail(ctx, PTC_ERR_INVALID, ctx->light_error);  // as ptc_direct_light
   if (ctx->environment_light && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kEnvLightNeedsMegakernel);
+  if (ctx->mis && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kMisNeedsMegakernel);
   if (ctx->iteration >= ctx->max_iterations) {  // path_tracer.cu:391
     ctx->result = ctx->fb.color4;
     return PTC_OK;
@@ -661,7 +666,11 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
     if (direct)
       lights = DLights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
                        ctx->scene.materials};
-    if (env_lit) {  // the environment is a light too: its one instance, the lamps' samples by lights.records
+    if (ctx->mis && (direct || env_lit)) {  // "mis" (DESIGN section 5l): its one instance, whichever of the two lights the frame samples
+      launch_megakernel_mis(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,
+                            sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx), env_frame(ctx) ? ctx->env : DEnv{nullptr, 0u, 0u},
+                            DEnvLight{env_lit ? ctx->env_table : nullptr}, DMis{direct ? ctx->light_material_pdf : nullptr});
+    } else if (env_lit) {  // the environment is a light too: its one instance, the lamps' samples by lights.records
       launch_megakernel_env_light(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces,
                                   ctx->fb, sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx), ctx->env, DEnvLight{ctx->env_table});
     } else if (env_frame(ctx)) {  // an environment: its instance of the plain or the direct-lit loop

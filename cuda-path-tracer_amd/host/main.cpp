@@ -51,6 +51,7 @@ struct CliConfigurations {  // configurations.hpp:11-15
   bool megakernel = false;
   bool direct_light = false;
   bool environment_light = false;
+  bool mis = false;
   int roulette = 0;
   std::optional<float> lens_radius, focus_distance;  // the thin lens (override the scene file's camera keys)
   // environment lighting (override the scene file's "environment" key, each on its own)
@@ -82,6 +83,8 @@ void usage()
                "      --focus-distance F  thin lens: distance of the plane in focus, > 0 (overrides the scene's \"focus_distance\")\n"
                "      --environment-light  an environment sample with a shadow ray at every diffuse hit (needs --method megakernel;\n"
                "                       a scene whose \"environment\" says \"light\": true asks for it under --method megakernel)\n"
+               "      --mis            multiple importance sampling: light samples and the path's own ray combined by the balance heuristic\n"
+               "                       (needs --method megakernel and --direct-light, --environment-light or a scene that says \"light\": true)\n"
                "      --environment FILE  environment lighting: an equirectangular Radiance .hdr (overrides the scene's \"environment\")\n"
                "      --environment-scale S  multiply the picture by S, a finite number >= 0 (default 1)\n"
                "      --environment-size N  size of the octahedral map made from it, in [2,4096] (default: the picture's height)\n"
@@ -119,6 +122,7 @@ CliConfigurations parse_cli_args(int argc, char** argv)
     else if (a == "--method") c.megakernel = need("method") == "megakernel";
     else if (a == "--direct-light") c.direct_light = true;
     else if (a == "--environment-light") c.environment_light = true;
+    else if (a == "--mis") c.mis = true;
     else if (a == "--roulette") {
       // a whole decimal number in [0, 64] (ptc_set_param's range), refused here: before the scene is read or a GPU touched
       const std::string v = need("roulette");
@@ -192,6 +196,10 @@ CliConfigurations parse_cli_args(int argc, char** argv)
   }
   if (c.environment_light && !c.megakernel) {  // ... and no environment light
     std::fprintf(stderr, "hip_pt: --environment-light needs --method megakernel (the streaming method renders no direct light)\n");
+    std::exit(1);
+  }
+  if (c.mis && !c.megakernel) {  // ... and nothing to combine
+    std::fprintf(stderr, "hip_pt: --mis needs --method megakernel (the streaming method renders no direct light)\n");
     std::exit(1);
   }
   if (c.filename.empty()) {
@@ -329,6 +337,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   path_tracer.direct_light = configs.direct_light;
   // (the flag, or the scene's "environment": {"light": true} where the method renders it)
   path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
+  path_tracer.mis = configs.mis;
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.environment = scene_desc.environment;
@@ -438,6 +447,7 @@ try {
   path_tracer.direct_light = configs.direct_light;
   // (the flag, or the scene's "environment": {"light": true} where the method renders it)
   path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
+  path_tracer.mis = configs.mis;
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.environment = scene_desc.environment;
@@ -520,9 +530,9 @@ int run_ranks(const CliConfigurations& configs, const SceneDescription& scene_de
     std::fprintf(stderr, "hip_pt: at most %d ranks\n", kMaxRanks);
     return 1;
   }
-  // (the megakernel seeds by frame pixel, so its ranks render the single-GPU image; it is let through for --direct-light and
-  // --environment-light, which the streaming method cannot render)
-  if (configs.denoise || (configs.megakernel && !configs.direct_light && !configs.environment_light)) {
+  // (the megakernel seeds by frame pixel, so its ranks render the single-GPU image; it is let through for --direct-light,
+  // --environment-light and --mis, which the streaming method cannot render)
+  if (configs.denoise || (configs.megakernel && !configs.direct_light && !configs.environment_light && !configs.mis)) {
     std::fprintf(stderr, "hip_pt: --gpus N renders in streaming mode without the denoiser (it needs the whole frame in one context)\n");
     return 1;
   }
@@ -584,6 +594,11 @@ try {
   SceneDescription scene_desc = scene_from_json(path.string(), /*read_environment*/ false);  // (the picture: below, once)
   scene_desc.filename = configs.filename;
   if (configs.spp) scene_desc.spp = *configs.spp;
+  // --mis combines light samples with the path: it needs a light that is sampled (before any GPU is touched)
+  if (configs.mis && !configs.direct_light && !configs.environment_light && !scene_desc.environment_source.light) {
+    std::fprintf(stderr, "hip_pt: --mis needs --direct-light, --environment-light or a scene whose \"environment\" says \"light\": true\n");
+    return 1;
+  }
   // the thin lens: the command line over the scene file; a radius > 0 needs a focus distance from one of them (before any GPU is touched)
   if (configs.lens_radius) scene_desc.camera.lens_radius = *configs.lens_radius;
   if (configs.focus_distance) scene_desc.camera.focus_distance = *configs.focus_distance;
@@ -655,6 +670,7 @@ try {
   path_tracer.direct_light = configs.direct_light;
   // (the flag, or the scene's "environment": {"light": true} where the method renders it)
   path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
+  path_tracer.mis = configs.mis;
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.environment = scene_desc.environment;

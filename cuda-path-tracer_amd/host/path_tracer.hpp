@@ -42,6 +42,8 @@ public:
   bool direct_light = false;  // a light sample at every diffuse hit (megakernel method only; ptc_set_param "direct_light")
   // an environment sample at every diffuse hit (megakernel method only; ptc_set_param "environment_light")
   bool environment_light = false;
+  // the balance heuristic between light samples and the path's own ray (megakernel method only; ptc_set_param "mis")
+  bool mis = false;
   int roulette = 0;  // Russian roulette at every bounce >= this but the last, 0 = off (both methods; ptc_set_param "roulette", [0, 64])
   // the thin lens (ptc_set_lens): aperture radius (0 = the pinhole, the default) and the distance of the plane in
   // focus, world units; both methods
@@ -126,6 +128,10 @@ private:
       check(ptc_set_param(ctx_, "environment_light", environment_light ? 1 : 0), "environment_light");
       environment_light_pushed_ = environment_light;
     }
+    if (mis != mis_pushed_) {
+      check(ptc_set_param(ctx_, "mis", mis ? 1 : 0), "mis");
+      mis_pushed_ = mis;
+    }
     if (roulette != roulette_pushed_) {
       check(ptc_set_param(ctx_, "roulette", roulette), "roulette");
       roulette_pushed_ = roulette;
@@ -150,6 +156,7 @@ private:
   ptc_ctx* ctx_ = nullptr;
   bool direct_light_pushed_ = false;
   bool environment_light_pushed_ = false;
+  bool mis_pushed_ = false;
   int roulette_pushed_ = 0;
   Lens lens_pushed_{};
   std::shared_ptr<const EnvironmentMap> environment_pushed_;

@@ -67,6 +67,17 @@ def light_table(scene, capacity=None):
     return out[:rc].copy(), _light_info_dict(info)
 
 
+def light_material_pdf(scene, capacity=None):
+    """Per material of a scene the inv_pdf its lamp records carry (ptc_light_material_pdf; host-side, no GPU needed), 0 for a
+    material that is no lamp: what "mis" weighs a lamp hit with.  -> float32 [materials]"""
+    flat = scene.build_scene() if isinstance(scene, SceneDescription) else scene
+    desc = flat.to_c()
+    capacity = len(flat.materials) if capacity is None else int(capacity)
+    out = np.zeros(max(capacity, 1), dtype=np.float32)
+    rc = _capi.check(_capi.lib().ptc_light_material_pdf(C.byref(desc), out.ctypes.data, capacity))
+    return out[:rc].copy()
+
+
 class _DirectLight:
     """What PathTracer.direct_light is.  The name was the direct-light QUERY's (ptc_direct_light) before it became the render
     loop's switch as well (the field the C++ PathTracer has), so it is both: its truth value is the switch -- assign True or False
@@ -103,6 +114,7 @@ class PathTracer:
         self.current_gpu_method = GPUMethod.streaming
         self._direct_light = False  # PathTracer.direct_light = True: a light sample at every diffuse hit (megakernel method only)
         self._environment_light = False  # PathTracer.environment_light = True: an environment sample at every diffuse hit (megakernel only)
+        self._mis = False  # PathTracer.mis = True: the balance heuristic between light samples and the path (megakernel only)
         self._roulette = 0  # PathTracer.roulette = k: Russian roulette at every bounce >= k but the last (0 = off)
         self._lens = (0.0, 1.0)  # PathTracer.lens = (radius, focus_distance): the thin lens (radius 0 = the pinhole)
         self._environment = None  # PathTracer.environment = [n, n, 3] float32: an octahedral HDR sky (None = the reference's gradient)
@@ -116,6 +128,7 @@ class PathTracer:
         self._rows = None
         self._direct_light_pushed = False
         self._environment_light_pushed = False
+        self._mis_pushed = False
         self._roulette_pushed = 0
         self._lens_pushed = (0.0, 1.0)
         self._environment_pushed = None
@@ -160,6 +173,17 @@ class PathTracer:
     @environment_light.setter
     def environment_light(self, on):
         self._environment_light = bool(on)
+
+    @property
+    def mis(self):
+        """Multiple importance sampling in the megakernel (ptc_set_param "mis"): True = every light sample of
+        direct_light / environment_light at a diffuse hit is combined with the path's own continuation ray by the balance heuristic.
+        The same expectation, another spread; changes nothing in a frame that samples neither light."""
+        return self._mis
+
+    @mis.setter
+    def mis(self, on):
+        self._mis = bool(on)
 
     @property
     def roulette(self):
@@ -229,6 +253,9 @@ class PathTracer:
         if self._environment_light != self._environment_light_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"environment_light", 1 if self._environment_light else 0))
             self._environment_light_pushed = self._environment_light
+        if self._mis != self._mis_pushed:
+            self._check(self._lib.ptc_set_param(self._ctx, b"mis", 1 if self._mis else 0))
+            self._mis_pushed = self._mis
         if self._roulette != self._roulette_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"roulette", self._roulette))
             self._roulette_pushed = self._roulette
@@ -598,6 +625,27 @@ class PathTracer:
         s = _capi.ptc_environment_light_loop_stats()
         self._check(self._lib.ptc_get_environment_light_loop_stats(self._ctx, C.byref(s)))
         return {"diffuse_hits": int(s.diffuse_hits), "shadow_rays": int(s.shadow_rays), "unoccluded": int(s.unoccluded)}
+
+    def mis_loop_stats(self):
+        """Counters of the megakernel under mis = True since restart: emitter hits and misses behind a diffuse vertex that counted
+        with the continuation ray's weight."""
+        s = _capi.ptc_mis_loop_stats()
+        self._check(self._lib.ptc_get_mis_loop_stats(self._ctx, C.byref(s)))
+        return {"weighted_emitter_hits": int(s.weighted_emitter_hits), "weighted_misses": int(s.weighted_misses)}
+
+    def environment_light_pdf(self, dirs):
+        """The environment sample's solid-angle density (ptc_environment_light_pdf) in unit directions [n, 3] -> float32 [n].  Needs
+        an environment."""
+        self._push_fields()
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(len(dirs), dtype=np.float32)
+        self._check(self._lib.ptc_environment_light_pdf(self._ctx, dirs.ctypes.data, len(dirs), out.ctypes.data, 0))
+        return out
+
+    def environment_light_pdf_dev(self, dirs_ptr, n, pdf_ptr):
+        """environment_light_pdf on device memory."""
+        self._push_fields()
+        self._check(self._lib.ptc_environment_light_pdf(self._ctx, C.c_void_p(int(dirs_ptr)), int(n), C.c_void_p(int(pdf_ptr)), 1))
 
     def selftest_math(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)

@@ -347,6 +347,17 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *                      device) is built by the first ptc_trace that needs it: PTC_ERR_OOM from there, the environment stays.  Under
  *                      PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is 1, before anything is
  *                      queued.  Counters: ptc_get_environment_light_loop_stats.  Any time (queued frames are flushed first)
+ *   "mis"              RENDERING (default 0; an extension): 1 = under PTC_METHOD_MEGAKERNEL, in a frame that samples the
+ *                      lamps ("direct_light" with a lamp table of weight > 0), the environment ("environment_light" with a map of weight
+ *                      > 0) or both, every light sample at a diffuse hit is combined with the path's own continuation ray by the balance
+ *                      heuristic: the sample is weighted p_light / (p_light + cos_r / pi), and a lamp the continuation ray hits or a sky it
+ *                      reaches counts with cos / pi / (cos / pi + p_light) instead of 0 (p_light: the sampler's solid-angle density of
+ *                      that direction; ptc_light_material_pdf, ptc_environment_light_pdf).  Diffuse vertices only, and not at the last
+ *                      bounce, whose light samples keep weight 1: the expectation of every pixel is that of 0.  Normal, depth,
+ *                      rays_total, every stream and ptc_get_direct_loop_stats / ptc_get_environment_light_loop_stats are bit for bit
+ *                      those of the same render with 0: only colour differs.  A frame that samples neither light renders bit for bit
+ *                      as with 0.  Under PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is 1,
+ *                      before anything is queued.  Counters: ptc_get_mis_loop_stats.  Any time (queued frames are flushed first)
  *   "roulette"         RENDERING (default 0 = off; an extension): k in [1, 64] = Russian roulette at every bounce b >= k
  *                      except the last one, under both methods (and "direct_light").  A path whose closest hit exists and is no emitter
  *                      takes q = the largest component of the throughput that came into the bounce; q >= 1 changes nothing (no draw); else
@@ -616,6 +627,27 @@ typedef struct ptc_environment_light_loop_stats {
 } ptc_environment_light_loop_stats;
 int ptc_get_environment_light_loop_stats(ptc_ctx* ctx, ptc_environment_light_loop_stats* out);
 
+/* Multiple importance sampling ("mis", an extension).
+ * The environment sample's density with respect to solid angle in `count` UNIT directions dirs[3i..] (the density is that of the
+ * direction as given; nothing is normalised): 1 / (4 f |w|_1^3) with f = 1 / (P n^2) of the texel square the direction falls in
+ * (s = q 0.5 + 0.5 per axis of the lookup's octahedral point q, i = min(floor(s n), n - 1), k = j n + i), read from the square's own
+ * entry of the alias table; 0 in a square of weight 0 and for a zero, NaN or infinite direction.  For ptc_environment_light's sample in
+ * direction w it is the reciprocal of the factor 4 f |w|_1^3 of that sample.  on_device: dirs and pdf_out are device pointers.  The
+ * table is built by the first call that needs it, as ptc_environment_light does.  PTC_ERR_INVALID without an environment; a map of weight 0
+ * gives zeros and launches nothing.  Moves no statistics. */
+int ptc_environment_light_pdf(ptc_ctx* ctx, const float* dirs, uint32_t count, float* pdf_out, int on_device);
+/* Per material of `scene` the inv_pdf every lamp record (ptc_light_table) of that material carries, (float)(W / lum): the reciprocal
+ * of the lamp sampler's density per unit area on that material's surfaces.  0 for a material that is not emissive, for lum == 0 and in
+ * a scene whose lamp table has weight 0.  Host only, no GPU, no context.  -> the number of materials, or PTC_ERR_INVALID (a NULL, a
+ * capacity below material_count, ptc_light_table's refusals). */
+int ptc_light_material_pdf(const ptc_scene_desc* scene, float* out, uint32_t capacity);
+/* The megakernel under "mis" 1 since ptc_restart: emitter hits and misses behind a diffuse vertex that counted with the continuation
+ * ray's weight.  Synchronises.  Moves nothing else, and nothing moves it but ptc_trace and ptc_restart. */
+typedef struct ptc_mis_loop_stats {
+  uint64_t weighted_emitter_hits, weighted_misses;
+} ptc_mis_loop_stats;
+int ptc_get_mis_loop_stats(ptc_ctx* ctx, ptc_mis_loop_stats* out);
+
 /* Where the time of the last ptc_upload_scene went (milliseconds of host wall clock; the "Initialization" stage of
  * the reference's Stopwatch, cli.cpp): */
 typedef struct ptc_upload_times {
@@ -731,6 +763,9 @@ int ptc_check_environment_light_table(const float* rgb, uint32_t n, void* entrie
  * byte (may be NULL) per point.  PTC_ERR_INVALID: a NULL, n out of range, a bad component, a v out of range. */
 int ptc_check_environment_light(const float* rgb, uint32_t n, const float* points, const float* normals, const uint32_t* v, const float* u,
                                 uint32_t count, float* radiance, float* shadow_rays, uint8_t* sampled);
+/* ... and the sample's density in `count` caller-given unit directions, as ptc_environment_light_pdf returns it (zeros for a map of
+ * weight 0).  PTC_ERR_INVALID: a NULL, n out of range, a bad component. */
+int ptc_check_environment_light_pdf(const float* rgb, uint32_t n, const float* dirs, uint32_t count, float* pdf_out);
 
 #ifdef __cplusplus
 }
