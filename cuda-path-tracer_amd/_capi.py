@@ -26,6 +26,7 @@ METHOD_STREAMING = 1
 
 DISPLAY_FINAL, DISPLAY_COLOR, DISPLAY_NORMAL, DISPLAY_DEPTH = 0, 1, 2, 3
 BUF_COLOR, BUF_NORMAL, BUF_DEPTH, BUF_FINAL = 0, 1, 2, 3
+CURVE_CLAMP, CURVE_REINHARD, CURVE_ACES = 0, 1, 2
 
 
 class ptc_object(C.Structure):
@@ -131,6 +132,16 @@ class ptc_mis_loop_stats(C.Structure):
 ptc_environment_light_stats = ptc_direct_stats  # the same five fields (include/ptcore.h)
 
 
+class ptc_display_params(C.Structure):
+    _fields_ = [("curve", C.c_int32), ("metering", C.c_int32), ("exposure", C.c_float), ("key", C.c_float), ("white", C.c_float),
+                ("low_permille", C.c_uint32), ("high_permille", C.c_uint32)]
+
+
+class ptc_exposure_info(C.Structure):
+    _fields_ = [("pixels", C.c_uint32), ("counted", C.c_uint32), ("below", C.c_uint32), ("rejected", C.c_uint32),
+                ("level_bin", C.c_int32), ("level", C.c_float), ("scale", C.c_float), ("histogram", C.c_uint32 * 256)]
+
+
 class ptc_upload_times(C.Structure):
     _fields_ = [("bvh_build_ms", C.c_float), ("layout_ms", C.c_float), ("triangles_ms", C.c_float), ("copy_ms", C.c_float),
                 ("total_ms", C.c_float), ("bvh_on_device", C.c_uint32), ("layout_on_device", C.c_uint32)]
@@ -233,6 +244,14 @@ SIGNATURES = {
     "ptc_check_environment_light_pdf": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptc_check_environment_light": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    "ptc_set_display": (C.c_int, [_P, C.POINTER(ptc_display_params)]),
+    "ptc_get_display": (C.c_int, [_P, C.POINTER(ptc_display_params)]),
+    "ptc_get_exposure_info": (C.c_int, [_P, C.POINTER(ptc_exposure_info)]),
+    "ptc_tonemap_buffer": (C.c_int, [_P, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.POINTER(ptc_exposure_info)]),
+    "ptc_check_display_params": (C.c_int, [C.POINTER(ptc_display_params), C.c_char_p, C.c_uint32]),
+    "ptc_check_display_meter": (C.c_int, [C.POINTER(ptc_display_params), C.c_void_p, C.c_int, C.c_uint32, C.POINTER(ptc_exposure_info)]),
+    "ptc_check_display_map": (C.c_int, [C.POINTER(ptc_display_params), C.c_float, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
 }
 
 _lib = None

@@ -495,6 +495,29 @@ struct DGatherBands {
 void launch_gather_bands(hipStream_t s, const DGatherBands& bands, uint32_t count, uint32_t max_pix, int channels,
                          uint32_t frame_pixels, float* frame);
 void launch_preview_packed(hipStream_t s, const float* buf, uint32_t pix_count, int channels, int mode, uint32_t* rgba);
+// The display transform (ptc_set_display; pt_display.hip).  DMeter: the words k_meter adds into, zero between
+// calls (k_meter_level leaves them so).  DExposure: what k_meter_level makes of them -- the histogram as counted, the mean bin of
+// its trimmed middle (-1: nothing counted), that bin's lower edge and the factor k_tonemap multiplies every channel by.
+// src4 (a float4 a pixel, 16-byte aligned) or src3 (three floats a pixel): exactly one is not null.  launch_meter's grid is capped at
+// kMeterMaxBlocks workgroups of kMeterBlock threads, which stride over the rest.  launch_tonemap: metered null = `scale` as given;
+// rgba or mapped (three floats a pixel) may be null.
+constexpr int kMeterBlock = 256;
+constexpr uint32_t kMeterMaxBlocks = 2048u;
+struct DMeter {
+  uint32_t hist[256];
+  uint32_t below, rejected;
+};
+struct DExposure {
+  uint32_t hist[256];
+  uint32_t pixels, counted, below, rejected;
+  int32_t level_bin;
+  float level, scale;
+};
+void launch_meter(hipStream_t s, const float4* src4, const float* src3, uint32_t pix_count, DMeter* acc);
+void launch_meter_level(hipStream_t s, DMeter* acc, DExposure* out, uint32_t pix_count, uint32_t low_permille, uint32_t high_permille,
+                        float key, float exposure);
+void launch_tonemap(hipStream_t s, const float4* src4, const float* src3, uint32_t pix_count, const DExposure* metered, float scale,
+                    int curve, float w2, uint32_t* rgba, float* mapped);
 void launch_denoise_positions(hipStream_t s, const DCamera& cam, uint32_t pix_count, const float4* nd, float4* pos);
 void launch_denoise_pass(hipStream_t s, const DCamera& cam, uint32_t pix_count, const float4* color, const float4* nd,
                          const float4* pos, float4* out, int step_width, DDenoise params);

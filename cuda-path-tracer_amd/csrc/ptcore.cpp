@@ -467,6 +467,7 @@ void ptc_destroy(ptc_ctx* ctx)
   if (ctx->loop_stats) (void)hipFree(ctx->loop_stats);
   if (ctx->env.texels) (void)hipFree(const_cast<float4*>(ctx->env.texels));
   if (ctx->env_table) (void)hipFree(const_cast<uint4*>(ctx->env_table));
+  if (ctx->meter_dev) (void)hipFree(ctx->meter_dev);  // (exposure_dev is the same allocation)
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -782,11 +783,18 @@ int ptc_present_rgba8(ptc_ctx* ctx, void* dst, int dst_is_device, int display_ty
   if (int rc = buffer_view(ctx, show.which, &view)) return rc;
   if (int rc = sync_frames(ctx)) return rc;
   uint32_t* out = dst_is_device ? static_cast<uint32_t*>(dst) : ctx->rgba_buf;
-  launch_preview(ctx->stream, view.src, ctx->pix_count, show.mode, out);
-  if (int rc = check_last(ctx, "preview")) return rc;
+  // radiance under a display of the context's; the reference display and the other views: k_preview, as ever
+  const bool displayed = show.mode == 0 && !reference_display(ctx->display);
+  if (displayed) {
+    if (int rc = show_display(ctx, view.src, nullptr, ctx->pix_count, out, nullptr, &ctx->shown)) return rc;
+  } else {
+    launch_preview(ctx->stream, view.src, ctx->pix_count, show.mode, out);
+    if (int rc = check_last(ctx, "preview")) return rc;
+  }
   if (!dst_is_device)
     HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rgba_buf, (size_t)ctx->pix_count * 4u, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // path_tracer.cu:519
+  if (displayed) ctx->shown_known = true;
   return PTC_OK;
 }
 

@@ -184,10 +184,17 @@ int ptc_gather_present_rgba8(ptc_ctx* root, void* dst, int dst_is_device, int di
   const uint32_t P = root->width * root->height;
   if (!root->gather_rgba) HIP_TRY(root, hipMalloc(reinterpret_cast<void**>(&root->gather_rgba), (size_t)P * 4u));
   uint32_t* out = dst_is_device ? static_cast<uint32_t*>(dst) : root->gather_rgba;
-  launch_preview_packed(root->stream, root->gather_frame, P, (int)view.floats_per_pixel, show.mode, out);
-  if (int rc = check_last(root, "preview")) return rc;
+  // radiance under a display of the root's: the whole gathered frame is metered, three floats a pixel
+  const bool displayed = show.mode == 0 && !reference_display(root->display);
+  if (displayed) {
+    if (int rc = show_display(root, nullptr, root->gather_frame, P, out, nullptr, &root->shown)) return rc;
+  } else {
+    launch_preview_packed(root->stream, root->gather_frame, P, (int)view.floats_per_pixel, show.mode, out);
+    if (int rc = check_last(root, "preview")) return rc;
+  }
   if (!dst_is_device) HIP_TRY(root, hipMemcpyAsync(dst, root->gather_rgba, (size_t)P * 4u, hipMemcpyDeviceToHost, root->stream));
   HIP_TRY(root, hipStreamSynchronize(root->stream));
+  if (displayed) root->shown_known = true;
   return PTC_OK;
 }
 

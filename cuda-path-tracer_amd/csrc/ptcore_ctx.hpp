@@ -2,7 +2,7 @@
 // (ptcore.cpp: context, ptc_resize in stages -- refusals, the sizing plan, the old frame's release, a ptc_frame_state built beside the
 // context, one assignment --, the parameter table, timed launches, views; ptcore_scene.cpp: scene upload in stages -- refusals and
 // host preparation while the old scene stands, its release, device work, one assignment of ptc_scene_state; ptcore_trace.cpp: the launch plan of a
-// batch of frames; ptcore_query.cpp: the ray queries outside the render loop; ptcore_bands.cpp: several GPUs; ptcore_checks.cpp:
+// batch of frames; ptcore_query.cpp: the ray queries outside the render loop; ptcore_bands.cpp: several GPUs; ptcore_display.cpp: the display transform; ptcore_checks.cpp:
 // host-side checks of the schedule helpers).
 #pragma once
 
@@ -291,6 +291,15 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   // 6, 7 "mis": weighted emitter hits, weighted misses)
   unsigned long long* loop_stats = nullptr;
   bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
+  // the display transform (ptc_set_display; ptcore_display.cpp).  The default is the reference display: the presents
+  // launch k_preview as before and nothing below is touched.  meter_dev / exposure_dev: one allocation of the context's own, made by the
+  // first present that needs it; the accumulation words are zero between calls.  shown: the last present's DExposure, for
+  // ptc_get_exposure_info
+  ptc_display_params display{PTC_CURVE_CLAMP, 0, 1.0f, 0.18f, 4.0f, 50u, 950u};
+  DMeter* meter_dev = nullptr;
+  DExposure* exposure_dev = nullptr;
+  DExposure shown{};
+  bool shown_known = false;
 };
 
 namespace ptcd {
@@ -332,6 +341,12 @@ struct DisplayView { int which, mode; };                                       /
 int view_ready(ptc_ctx* ctx, const void* arg);
 int buffer_view(ptc_ctx* ctx, int which, BufferView* out);
 int display_view(ptc_ctx* ctx, int display_type, bool gathered, DisplayView* out);
+// The display transform (ptcore_display.cpp).  reference_display: the display under which a present launches
+// k_preview as it always did.  show_display: meter (under metering 1), level and tone-map n pixels of src4 (a float4 each) or src3
+// (three floats each) on ctx->stream, into rgba and / or mapped (device; either may be null); *shown gets the DExposure of this call
+// once the stream has been synchronised, which is the caller's to do.
+bool reference_display(const ptc_display_params& d);
+int show_display(ptc_ctx* ctx, const float4* src4, const float* src3, uint32_t n, uint32_t* rgba, float* mapped, DExposure* shown);
 // The lamp table of a validated scene (ptcore_scene.cpp; include/ptcore.h: ptc_light).  *last = last record with a weight > 0.
 // Returns PTC_OK, or PTC_ERR_INVALID with `err` naming the emissive sphere whose matrix is no similarity.
 int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err);

@@ -3,7 +3,7 @@
 // following the call sequence of execute_cli_version (src/cli/cli.cpp:62-116): read scene, create_buffers,
 // max_iterations = spp, spp x path_trace, synchronize, send_to_preview, write PNG, stage timings.
 // Extra flags: --max-bounces N (the reference's cap is a compile-time 50), --denoise, --method, --gpu,
-// --lens-radius R / --focus-distance F (the thin lens), --environment FILE / --environment-scale S / --environment-size N (environment lighting; --dump-environment FILE: the decoded picture and the map, for tests, no GPU), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
+// --lens-radius R / --focus-distance F (the thin lens), --tonemap C / --exposure EV / --auto-exposure / --key K / --white W (the display transform), --environment FILE / --environment-scale S / --environment-size N (environment lighting; --dump-environment FILE: the decoded picture and the map, for tests, no GPU), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
 // (DisplayBufferType of send_to_preview, path_tracer.cu:487-520: which buffer the PNG shows), --dump-raw FILE (the
 // accumulated float framebuffers as they are: "PTRF", width, height, 7 as uint32, then colour rgb, normal xyz and
 // depth planes as float32).  Without -o the reference opens its GLFW viewer; this build is headless and says so.
@@ -63,6 +63,9 @@ struct CliConfigurations {  // configurations.hpp:11-15
   std::optional<std::string> dump_scene;
   std::optional<std::string> dump_raw;
   DisplayBufferType display = DisplayBufferType::final;
+  // the display transform: the defaults are the reference display
+  ptc_display_params tone{PTC_CURVE_CLAMP, 0, 1.0f, 0.18f, 4.0f, 50u, 950u};
+  const char* tone_flag = nullptr;  // the first of its flags on the command line
   std::optional<std::string> replay;
   bool dry_run = false;
 };
@@ -93,6 +96,11 @@ void usage()
                "      --gpus N         split the frame's rows over N processes / GPUs (rank r on device r %% device count)\n"
                "      --dump-scene F   write the flattened scene to F and exit (no GPU needed)\n"
                "      --display D      buffer the image shows: final (default) | color | normal | depth\n"
+               "      --tonemap C      tone curve of the final / color image: clamp (default) | reinhard | aces\n"
+               "      --exposure EV    exposure in stops: every channel times 2^EV before the curve (default 0)\n"
+               "      --auto-exposure  meter the image: a log-luminance histogram's trimmed mean is brought to the key\n"
+               "      --key K          what --auto-exposure brings the metered level to, > 0 (default 0.18)\n"
+               "      --white W        white point of --tonemap reinhard, > 0 (default 4)\n"
                "      --dump-raw F     also write the accumulated float buffers (colour, normal, depth) to F\n"
                "      --replay S.json  headless viewer: replay a script of viewer events, -o PREFIX -> PREFIX_0000.png ...\n"
                "      --dry-run        with --replay: no GPU, no images; print the camera after every event\n");
@@ -168,6 +176,35 @@ CliConfigurations parse_cli_args(int argc, char** argv)
       }
       c.environment_size = n;
     }
+    else if (a == "--tonemap") {
+      // the display transform's flags are refused here: before the scene is read or a GPU touched
+      const std::string v = need("tonemap");
+      if (v == "clamp") c.tone.curve = PTC_CURVE_CLAMP;
+      else if (v == "reinhard") c.tone.curve = PTC_CURVE_REINHARD;
+      else if (v == "aces") c.tone.curve = PTC_CURVE_ACES;
+      else {
+        std::fprintf(stderr, "Option '--tonemap': unknown curve '%s' (clamp, reinhard, aces)\n", v.c_str());
+        std::exit(1);
+      }
+      if (!c.tone_flag) c.tone_flag = "--tonemap";
+    }
+    else if (a == "--auto-exposure") {
+      c.tone.metering = 1;
+      if (!c.tone_flag) c.tone_flag = "--auto-exposure";
+    }
+    else if (a == "--exposure" || a == "--white" || a == "--key") {
+      const std::string v = need(a.c_str() + 2);
+      char* end = nullptr;
+      const double x = std::strtod(v.c_str(), &end);
+      const bool stops = a == "--exposure";
+      const float f = stops ? (float)std::exp2(x) : (float)x;  // (stops so far from 0 that 2^EV is 0 or infinite in binary32 are refused too)
+      if (v.empty() || *end != '\0' || !std::isfinite(x) || !std::isfinite(f) || !(f > 0.0f)) {
+        std::fprintf(stderr, "Option '%s': '%s' is not a finite number%s\n", a.c_str(), v.c_str(), stops ? " of stops in binary32's range" : " > 0");
+        std::exit(1);
+      }
+      (stops ? c.tone.exposure : a == "--white" ? c.tone.white : c.tone.key) = f;
+      if (!c.tone_flag) c.tone_flag = stops ? "--exposure" : a == "--white" ? "--white" : "--key";
+    }
     else if (a == "--gpu") c.gpu = std::stoi(need("gpu"));
     else if (a == "--gpus") c.gpus = std::stoi(need("gpus"));
     else if (a == "--dump-scene") c.dump_scene = need("dump-scene");
@@ -200,6 +237,11 @@ CliConfigurations parse_cli_args(int argc, char** argv)
   }
   if (c.mis && !c.megakernel) {  // ... and nothing to combine
     std::fprintf(stderr, "hip_pt: --mis needs --method megakernel (the streaming method renders no direct light)\n");
+    std::exit(1);
+  }
+  if (c.tone_flag && (c.display == DisplayBufferType::normal || c.display == DisplayBufferType::depth)) {
+    std::fprintf(stderr, "hip_pt: %s applies to radiance: not with --display normal or depth (the display transform leaves those views alone)\n",
+                 c.tone_flag);
     std::exit(1);
   }
   if (c.filename.empty()) {
@@ -340,6 +382,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   path_tracer.mis = configs.mis;
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
+  path_tracer.display = configs.tone;
   path_tracer.environment = scene_desc.environment;
 
   int shown = 0;
@@ -450,6 +493,7 @@ try {
   path_tracer.mis = configs.mis;
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
+  path_tracer.display = configs.tone;
   path_tracer.environment = scene_desc.environment;
   path_tracer.create_buffers(resolution, scene_desc);
   auto check = [&](int rc, const char* what) {
@@ -479,6 +523,7 @@ try {
   stopwatch.end_stage("Path Tracing");
   if (rank == 0) {
     std::vector<uchar4> buffer((size_t)resolution.width * resolution.height);
+    check(ptc_set_display(path_tracer.handle(), &configs.tone), "display");  // the root meters the whole gathered frame
     check(ptc_gather_present_rgba8(path_tracer.handle(), buffer.data(), 0, static_cast<int>(configs.display)), "gather_present");
     const fs::path output_path{*configs.output_filename};
     if (output_path.extension() == ".png") {
@@ -673,6 +718,7 @@ try {
   path_tracer.mis = configs.mis;
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
+  path_tracer.display = configs.tone;
   path_tracer.environment = scene_desc.environment;
   path_tracer.create_buffers(resolution, scene_desc);
   path_tracer.synchronize();

@@ -54,6 +54,9 @@ public:
   // environment lighting (ptc_set_environment): an octahedral HDR map (hdr_image.hpp: load_environment makes one
   // from an equirectangular .hdr), or null = the reference's gradient, the default; both methods.  Pushed when the pointer changes.
   std::shared_ptr<const EnvironmentMap> environment;
+  // the display transform (ptc_set_display): exposure (manual or metered), a tone curve and the reference's
+  // encoding, where send_to_preview shows radiance (final, color).  The default is the reference display.  Pushed by send_to_preview.
+  ptc_display_params display{PTC_CURVE_CLAMP, 0, 1.0f, 0.18f, 4.0f, 50u, 950u};
   EdgeAvoidingATrousDenoiser atrous_denoiser{};
   int max_bounces = 50;  // reference: compile-time constant, path_tracer.cu:27
 
@@ -104,7 +107,15 @@ public:
   void send_to_preview(uchar4* dst, UResolution, DisplayBufferType type = DisplayBufferType::final,
                        bool dst_is_device = false) const
   {
+    check(ptc_set_display(ctx_, &display), "display");
     check(ptc_present_rgba8(ctx_, dst, dst_is_device ? 1 : 0, static_cast<int>(type)), "send_to_preview");
+  }
+  // of the last send_to_preview that went through the display transform (ptc_get_exposure_info)
+  [[nodiscard]] ptc_exposure_info exposure_info() const
+  {
+    ptc_exposure_info info{};
+    check(ptc_get_exposure_info(ctx_, &info), "exposure_info");
+    return info;
   }
   void synchronize() { check(ptc_synchronize(ctx_), "synchronize"); }
   [[nodiscard]] ptc_stats stats() const

@@ -78,6 +78,34 @@ def light_material_pdf(scene, capacity=None):
     return out[:rc].copy()
 
 
+class ToneCurve(IntEnum):  # ptc_curve
+    clamp = 0
+    reinhard = 1
+    aces = 2
+
+
+@dataclass(frozen=True)
+class Display:
+    """The display transform (ptc_display_params).  The default is the reference display: clamp and gamma only."""
+    curve: int = ToneCurve.clamp
+    metering: int = 0            # 0 manual, 1 histogram
+    exposure: float = 1.0        # linear factor, > 0
+    key: float = 0.18            # what the metered level is mapped to
+    white: float = 4.0           # Reinhard's white point
+    low_permille: int = 50       # the trimmed mean keeps the ranks between the two
+    high_permille: int = 950
+
+    def to_c(self):
+        return _capi.ptc_display_params(int(self.curve), int(self.metering), float(self.exposure), float(self.key), float(self.white),
+                                        int(self.low_permille), int(self.high_permille))
+
+
+def _exposure_info(info):
+    return {"pixels": int(info.pixels), "counted": int(info.counted), "below": int(info.below), "rejected": int(info.rejected),
+            "level_bin": int(info.level_bin), "level": np.float32(info.level), "scale": np.float32(info.scale),
+            "histogram": np.ctypeslib.as_array(info.histogram).astype(np.uint32)}
+
+
 class _DirectLight:
     """What PathTracer.direct_light is.  The name was the direct-light QUERY's (ptc_direct_light) before it became the render
     loop's switch as well (the field the C++ PathTracer has), so it is both: its truth value is the switch -- assign True or False
@@ -234,6 +262,52 @@ class PathTracer:
             raise ValueError("environment components must be finite and not negative")
         m.setflags(write=False)
         self._environment = m
+
+    @property
+    def display(self):
+        """The display transform (ptc_set_display): a Display.  It applies where radiance is shown -- send_to_preview and
+        gather_present of the final and colour views -- as exposure (manual, or metered from a log-luminance histogram of the shown
+        buffer), a tone curve and the reference's gamma encoding.  Assignment takes effect at once and survives create_buffers and
+        resize_image; a value the library refuses raises PtcError naming the field, and the display that was set stays."""
+        d = _capi.ptc_display_params()
+        self._check(self._lib.ptc_get_display(self._ctx, C.byref(d)))
+        return Display(ToneCurve(d.curve), int(d.metering), float(d.exposure), float(d.key), float(d.white), int(d.low_permille),
+                       int(d.high_permille))
+
+    @display.setter
+    def display(self, value):
+        d = value.to_c()
+        self._check(self._lib.ptc_set_display(self._ctx, C.byref(d)))
+
+    def exposure_info(self):
+        """Of the last send_to_preview / gather_present that went through the display transform (ptc_get_exposure_info): a dict of
+        pixels, counted, below, rejected, level_bin, level, scale and histogram ([256] uint32)."""
+        info = _capi.ptc_exposure_info()
+        self._check(self._lib.ptc_get_exposure_info(self._ctx, C.byref(info)))
+        return _exposure_info(info)
+
+    def tonemap_buffer(self, image, want_mapped=False):
+        """The display transform on an array of the caller's (ptc_tonemap_buffer): image [..., 3] or [..., 4] float32 (the fourth
+        channel is ignored) -> (rgba [..., 4] uint8, mapped [..., 3] float32 or None, the exposure info as exposure_info gives it)."""
+        a = np.ascontiguousarray(image, dtype=np.float32)
+        ch = a.shape[-1]
+        n = a.size // ch
+        rgba = np.empty((n, 4), dtype=np.uint8)
+        mapped = np.empty((n, 3), dtype=np.float32) if want_mapped else None
+        info = _capi.ptc_exposure_info()
+        self._check(self._lib.ptc_tonemap_buffer(self._ctx, a.ctypes.data_as(C.c_void_p), ch, n, 0, rgba.ctypes.data_as(C.c_void_p),
+                                                 mapped.ctypes.data_as(C.c_void_p) if want_mapped else None, 0, C.byref(info)))
+        shape = a.shape[:-1]
+        return rgba.reshape(shape + (4,)), (mapped.reshape(shape + (3,)) if want_mapped else None), _exposure_info(info)
+
+    def tonemap_buffer_dev(self, src_ptr, channels, pix_count, rgba_ptr, mapped_ptr=None):
+        """... on device pointers (a torch tensor's data_ptr()): src of `channels` (3 or 4) floats a pixel, rgba 4 bytes a pixel, mapped
+        (optional) 3 floats a pixel.  Returns the exposure info."""
+        info = _capi.ptc_exposure_info()
+        self._check(self._lib.ptc_tonemap_buffer(self._ctx, C.c_void_p(int(src_ptr)), int(channels), int(pix_count), 1,
+                                                 C.c_void_p(int(rgba_ptr)), C.c_void_p(int(mapped_ptr)) if mapped_ptr else None, 1,
+                                                 C.byref(info)))
+        return _exposure_info(info)
 
     def sample_environment(self, directions):
         """The environment's value in `directions` ([k, 3], not normalised) as the device computes it for a miss -> [k, 3] float32

@@ -495,6 +495,64 @@ int ptc_gather_present_rgba8(ptc_ctx* root, void* dst, int dst_is_device, int di
  * in row order), in microseconds.  Waits for that gather. */
 int ptc_gather_last_us(ptc_ctx* root, float* microseconds);
 
+/* ---- the display transform (an extension: the reference shows clamp + gamma only) ---- */
+/* Context-wide, applied where radiance is shown: ptc_present_rgba8 and ptc_gather_present_rgba8 under PTC_DISPLAY_FINAL and
+ * PTC_DISPLAY_COLOR (the normal and depth views are never touched).  Three steps: meter (optional) -- a 256-bin log-luminance
+ * histogram of the shown buffer, on the device, whose trimmed mean gives an exposure factor; curve -- every channel times that factor,
+ * then through the tone curve; encode -- send_to_preview's lines, unchanged (gamma 1 / 2.2, clamp, * 255.99f, alpha 255).
+ * The rule, in binary32 and integers (DESIGN section 5m states it operation by operation; tests/display_ref.py restates it):
+ *   meter   Y = (0.2126f r + 0.7152f g) + 0.0722f b.  Y negative or not finite (a NaN in any channel): `rejected`.  Y < 2^-16 (zeros,
+ *           denormals): `below`.  Else bin = min((bits(Y) >> 20) - 888, 255): eight bins an octave from 2^-16, bin 128 at 1.0.
+ *   level   N = the counted samples; the first N low_permille / 1000 and the last N (1000 - high_permille) / 1000 of them in bin order
+ *           are left out (floored); K, S = the count and the bin sum of the others; level_bin = (2 S + K) / (2 K);
+ *           level = that bin's lower edge; scale = (key / level) * exposure.  N == 0: level_bin -1, level 0, scale = exposure.
+ *           metering 0: scale = exposure, and nothing is metered.
+ *   curve   e = c * scale; x = e > 0 ? e : 0 (a NaN or a negative shows black); x = min(x, 2^20);
+ *           CLAMP y = x;  REINHARD y = (x (1 + x / white^2)) / (1 + x);  ACES y = (x (2.51 x + 0.03)) / (x (2.43 x + 0.59) + 0.14).
+ * The reference display -- curve CLAMP, metering 0, exposure 1.0f, the default -- launches exactly what was launched before the
+ * display existed (the other fields are not read). */
+typedef enum ptc_curve { PTC_CURVE_CLAMP = 0, PTC_CURVE_REINHARD = 1, PTC_CURVE_ACES = 2 } ptc_curve;
+typedef struct ptc_display_params {   /* (ptc_display is the enum of the views) */
+  int32_t curve;                      /* ptc_curve */
+  int32_t metering;                   /* 0 manual, 1 histogram */
+  float exposure;                     /* linear factor; finite and > 0; default 1 */
+  float key;                          /* what the metered level is mapped to; finite and > 0; default 0.18f */
+  float white;                        /* Reinhard's white point; finite and > 0; default 4 */
+  uint32_t low_permille, high_permille; /* the trimmed mean keeps the ranks between them; low < high <= 1000; defaults 50, 950 */
+} ptc_display_params;
+typedef struct ptc_exposure_info {
+  uint32_t pixels;                    /* pixels shown */
+  uint32_t counted, below, rejected;  /* pixels = counted + below + rejected under metering 1; all three 0 under metering 0 */
+  int32_t level_bin;                  /* -1: nothing was counted, or metering 0 */
+  float level;                        /* lower edge of level_bin; 0 where level_bin is -1 */
+  float scale;                        /* the factor every channel was multiplied by */
+  uint32_t histogram[256];
+} ptc_exposure_info;
+/* Any time; the display survives ptc_upload_scene and ptc_resize.  PTC_ERR_INVALID, with the offending field named in ptc_last_error
+ * and the display that was set left in place: a NaN, infinite or non-positive exposure, key or white; permilles out of order; an
+ * unknown curve; a metering other than 0 or 1. */
+int ptc_set_display(ptc_ctx* ctx, const ptc_display_params* display);
+int ptc_get_display(ptc_ctx* ctx, ptc_display_params* out);
+/* Of the most recent present (ptc_present_rgba8, ptc_gather_present_rgba8) that went through the display transform.
+ * ptc_present_rgba8 meters the rows of this context -- a non-root rank's own present meters only its rows --,
+ * ptc_gather_present_rgba8 the whole gathered frame on the root.  PTC_ERR_INVALID before any such present. */
+int ptc_get_exposure_info(ptc_ctx* ctx, ptc_exposure_info* out);
+/* The same kernels on a caller's buffer under the context's display (the reference display included): src = pix_count pixels of
+ * `channels` floats, 3 (packed) or 4 (the fourth is ignored; a device pointer must be 16-byte aligned), in device memory if
+ * src_on_device != 0; rgba_out (4 bytes a pixel) and mapped_out (optional: the channels after the curve, 3 floats a pixel) in
+ * device memory if out_on_device != 0; info (optional, host memory).  Needs neither a scene nor a frame, moves no render statistics
+ * and leaves ptc_get_exposure_info's answer alone.  Synchronises. */
+int ptc_tonemap_buffer(ptc_ctx* ctx, const void* src, int channels, uint32_t pix_count, int src_on_device, void* rgba_out, float* mapped_out,
+                       int out_on_device, ptc_exposure_info* info);
+/* The rule on the host, no GPU and no context (pt_display.hpp compiled for the host): the metering of count pixels of `channels`
+ * (3 or 4) floats under params, and the curve of params on every pixel under a given scale (mapped_out: 3 floats a pixel).
+ * PTC_ERR_INVALID: a NULL, channels, params ptc_set_display would refuse. */
+/* ptc_set_display's decision on params: PTC_OK, or PTC_ERR_INVALID with the refusal's text -- it names the field -- in why (may be
+ * NULL; capacity bytes, always terminated). */
+int ptc_check_display_params(const ptc_display_params* params, char* why, uint32_t capacity);
+int ptc_check_display_meter(const ptc_display_params* params, const float* rgb, int channels, uint32_t count, ptc_exposure_info* info_out);
+int ptc_check_display_map(const ptc_display_params* params, float scale, const float* rgb, int channels, uint32_t count, float* mapped_out);
+
 int ptc_synchronize(ptc_ctx* ctx);                                  /* cudaDeviceSynchronize at cli.cpp:100 */
 int ptc_get_stats(ptc_ctx* ctx, ptc_stats* out);                    /* synchronises */
 int ptc_set_profiling(ptc_ctx* ctx, int time_trace_kernel, int count_tests);
