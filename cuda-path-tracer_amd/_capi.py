@@ -129,6 +129,10 @@ class ptc_mis_loop_stats(C.Structure):
     _fields_ = [("weighted_emitter_hits", C.c_uint64), ("weighted_misses", C.c_uint64)]
 
 
+class ptc_smooth_loop_stats(C.Structure):
+    _fields_ = [("shading_normals", C.c_uint64), ("fallbacks", C.c_uint64), ("absorbed", C.c_uint64), ("culled_light_samples", C.c_uint64)]
+
+
 ptc_environment_light_stats = ptc_direct_stats  # the same five fields (include/ptcore.h)
 
 
@@ -241,6 +245,12 @@ SIGNATURES = {
     "ptc_environment_light_pdf": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_int]),
     "ptc_light_material_pdf": (C.c_int, [C.POINTER(ptc_scene_desc), _P, C.c_uint32]),
     "ptc_get_mis_loop_stats": (C.c_int, [_P, C.POINTER(ptc_mis_loop_stats)]),
+    "ptc_set_vertex_normals": (C.c_int, [_P, C.c_void_p, C.c_uint32]),
+    "ptc_get_vertex_normals": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "ptc_compute_vertex_normals": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ptc_hit_attributes": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ptc_get_smooth_loop_stats": (C.c_int, [_P, C.POINTER(ptc_smooth_loop_stats)]),
+    "ptc_check_shading_normal": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p, C.c_void_p]),
     "ptc_check_environment_light_pdf": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptc_check_environment_light": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),

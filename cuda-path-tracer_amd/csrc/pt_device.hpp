@@ -598,6 +598,28 @@ struct DMis {
 void launch_megakernel_mis(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
                            uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
                            DLens lens, DEnv env, DEnvLight el, DMis mis);
+// Smooth shading in the megakernel (ptc_set_vertex_normals, ptc_set_param "smooth_normals"; pt_smooth.hpp).
+// normals: three floats per vertex of the whole scene, object space, the scene's own allocation; mesh_first_vertex: per mesh where
+// its vertices start in it.  Kept out of DScene and DMeshView, which every other kernel takes by value.  normals null: none set.
+}  // namespace pt
+#include "pt_smooth.hpp"  // (the rule mega_path names under kSmooth)
+namespace pt {
+struct DSmooth {
+  const float* normals;
+  const uint32_t* mesh_first_vertex;
+};
+// the megakernel's smooth instances (a "smooth_normals" 1 frame of a scene with vertex normals; pt_mega_smooth.hip): mega_path with
+// kSmooth -- launch_megakernel_mis's arguments and run-time choices (lights.records null: no lamp samples; el.table null: no
+// environment samples; env.texels null: the gradient; lens.radius), the balance heuristic by `weigh` (one instance with, one without).
+// stats words 8 .. 11 of a line += shading normals formed, fall-backs to the geometric normal, absorbed continuations, culled light samples
+void launch_megakernel_smooth(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
+                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
+                              DLens lens, DEnv env, DEnvLight el, DMis mis, bool weigh, DSmooth sm);
+// ptc_hit_attributes' kernel (pt_mega_smooth.hip): one thread per ray, the reference's walk (ray_scene) on the thread's LDS stack.
+// rays: two float4 a ray, {origin, t_min} {direction, t_max}; per ray the winner's object and triangle (0xffffffff: a miss / a
+// sphere), u, v, and the shading normal (sm.normals null: the geometric one); flags |= kFlagStackOverflow
+void launch_hit_attributes(hipStream_t s, const DScene& scene, DSmooth sm, const float4* rays, uint32_t n, uint32_t* object_out,
+                           uint32_t* triangle_out, float2* uv_out, float* normal_out, uint32_t* flags);
 // ptc_environment_light_pdf's kernel (pt_env.hip): one thread per unit direction, env_light::density
 void launch_env_light_pdf(hipStream_t s, DEnvLight el, uint32_t n, const float* dirs, uint32_t count, float* pdf);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,

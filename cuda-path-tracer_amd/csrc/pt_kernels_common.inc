@@ -152,8 +152,17 @@ __device__ __forceinline__ bool ray_sphere_a(const Ray& ray, const float a, cons
   return true;
 }
 
+// What a closest hit knows besides its record (smooth shading, DESIGN section 5n; the kAttr forms of ray_triangle, ray_mesh and
+// ray_scene below): the winner's object, the offset of its triangle in the mesh's `indices` (kNoChild: a sphere) and the accepted
+// test's own u, v.  The forms without kAttr are the instructions they were.
+struct HitAttr {
+  uint32_t object, first;
+  float u, v;
+};
+
 // ray_triangle_intersection_test, intersections.cuh:49-85 (t == t_max accepted)
-__device__ __forceinline__ bool ray_triangle(const Ray& ray, const f3 p0, const f3 p1, const f3 p2, Hit& rec)
+template <bool kAttr = false>
+__device__ __forceinline__ bool ray_triangle(const Ray& ray, const f3 p0, const f3 p1, const f3 p2, Hit& rec, HitAttr* at = nullptr)
 {
   const float EPS = 0.0000001f;
   const f3 e1 = p1 - p0;
@@ -175,6 +184,10 @@ __device__ __forceinline__ bool ray_triangle(const Ray& ray, const f3 p0, const 
   const f3 outward = normalize(cross(e1, e2));
   rec.side = dot(ray.d, outward) < 0.0f ? 0u : 1u;
   rec.n = rec.side == 0u ? outward : -outward;
+  if constexpr (kAttr) {
+    at->u = u;
+    at->v = v;
+  }
   return true;
 }
 
@@ -188,9 +201,11 @@ __device__ __forceinline__ void inverse_transform_ray(const m4& inv_m, const Ray
 // ray_mesh_intersection_test, path_tracer.cu:36-76.  Depth-first, left child first, every inner box
 // the line crosses is entered (the reference has no t culling).  The stack lives in LDS, laid out
 // [depth][lane] so that a push or pop of the whole wavefront touches 64 consecutive banks.
-template <bool kCount>
+// kAttr: a hit also leaves the winner's place in `indices` and its u, v in *at (an equal t is accepted, so the triangle visited
+// last wins a tie).
+template <bool kCount, bool kAttr = false>
 __device__ __forceinline__ bool ray_mesh(Ray ray, const DMeshView& mv, const DObject* obj, Hit& rec, uint32_t* stack,
-                                         uint32_t& flags, Tally& tally, const int stack_cap = kStackDepth)
+                                         uint32_t& flags, Tally& tally, const int stack_cap = kStackDepth, HitAttr* at = nullptr)
 {
   bool hit = false;
   f3 oo, od;
@@ -213,9 +228,10 @@ __device__ __forceinline__ bool ray_mesh(Ray ray, const DMeshView& mv, const DOb
       const f3 p1 = xform_point(obj->m, ld3(mv.positions + 3u * (size_t)i1));
       const f3 p2 = xform_point(obj->m, ld3(mv.positions + 3u * (size_t)i2));
       if (kCount) ++tally.tris;
-      if (ray_triangle(ray, p0, p1, p2, rec)) {
+      if (ray_triangle<kAttr>(ray, p0, p1, p2, rec, at)) {
         hit = true;
         ray.tmax = rec.t;
+        if constexpr (kAttr) at->first = first;
       }
     } else if ((kCount ? (void)(++tally.boxes, ++tally.nodes) : (void)0), ray_aabb(oo, od, xyz(n0), xyz(n1))) {
       if (sp + 2 > stack_cap) {
@@ -231,9 +247,10 @@ __device__ __forceinline__ bool ray_mesh(Ray ray, const DMeshView& mv, const DOb
 }
 
 // ray_scene_intersection_test + ray_object_intersection_test, path_tracer.cu:78-128
-template <bool kCount>
+// kAttr: a hit also leaves the winner in *at -- its object (the later object wins a tie), HitAttr::first = kNoChild for a sphere.
+template <bool kCount, bool kAttr = false>
 __device__ __forceinline__ bool ray_scene(Ray ray, const DScene& sc, Hit& rec, uint32_t* stack, uint32_t& flags,
-                                          Tally& tally)
+                                          Tally& tally, HitAttr* at = nullptr)
 {
   bool hit = false;
   for (uint32_t i = 0; i < sc.object_count; ++i) {
@@ -251,14 +268,16 @@ __device__ __forceinline__ bool ray_scene(Ray ray, const DScene& sc, Hit& rec, u
         rec.p = xform_point(obj->m, rec.p);
         rec.t = length(rec.p - ray.o);
         rec.n = xform_normal(obj->inv_m, rec.n);
+        if constexpr (kAttr) at->first = kNoChild;
       }
     } else {
-      h = ray_mesh<kCount>(ray, sc.mesh_views[sc.object_mesh[i]], obj, rec, stack, flags, tally);
+      h = ray_mesh<kCount, kAttr>(ray, sc.mesh_views[sc.object_mesh[i]], obj, rec, stack, flags, tally, kStackDepth, at);
     }
     if (h) {
       hit = true;
       rec.mat = sc.object_material[i];
       ray.tmax = rec.t;
+      if constexpr (kAttr) at->object = i;
     }
   }
   return hit;

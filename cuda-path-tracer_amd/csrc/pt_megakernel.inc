@@ -1,8 +1,9 @@
 // pt_megakernel.inc -- the megakernel's loop, the whole path in one thread: mega_path, and k_megakernel around it.  Included (inside
 // namespace pt, after pt_kernels_common.inc and with pt_light_sample.hpp in front) by pt_kernels.hip, which instantiates the plain
 // instances beside the closest-hit kernels as ever, and by pt_mega_direct.hip, which instantiates the kRoulette ones and
-// k_megakernel_direct, and by pt_mega_mis.hip, which instantiates k_megakernel_mis (kMis, DESIGN section 5l): the code object that
-// holds the traversal kernels stays the one it was (DESIGN section 5h).
+// k_megakernel_direct, and by pt_mega_mis.hip, which instantiates k_megakernel_mis (kMis, DESIGN section 5l), and by pt_mega_smooth.hip,
+// which instantiates k_megakernel_smooth (kSmooth, section 5n): the code object that holds the traversal kernels stays the one it was
+// (DESIGN section 5h).
 // path_tracing_mega_kernel, path_tracer.cu:227-269: the whole path in one thread, one RNG stream per
 // pixel (a different image from streaming mode at the same seed -- a property of the reference).
 // kEmit: the scene has an emissive material (the host's choice; without one the instance is the reference's loop as it was).
@@ -42,13 +43,24 @@
 // sky's texel loads.  Here the environment light is a run-time choice as well (el.table null: none) and so is the environment
 // (env.texels null: the gradient).  Every draw, every closest hit and shadow ray and the six counters are those of the loop without it.
 // stats words 6 and 7 += emitter hits and misses behind a diffuse vertex that were weighted.
-template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false, bool kEnv = false, bool kEnvLight = false, bool kMis = false>
+// kSmooth (with kEnvLight; ptc_set_param "smooth_normals" in a scene with vertex normals, DESIGN section 5n; k_megakernel_smooth,
+// pt_mega_smooth.hip): at a triangle hit the shading normal hn is smooth::shading_normal's (pt_smooth.hpp) of the winner's three
+// vertex normals -- the closest hit reports the winner, ray_scene<.., true> -- and takes rec.n's place in the normal plane, in
+// evaluate_material, in the light samples and in bsdf_pdf; rec.n stays geometric (side, the lamp-side cosine of an emitter hit).  A
+// light sample whose direction lies behind the geometry (dot(w, rec.n) <= 0) counts as not sampled, and a diffuse or metal triangle
+// hit whose new direction does (dot(ray.d, rec.n) <= 0) ends the path with colour 0 behind its light samples.  Every light is a
+// run-time choice as under kMis, with or without it, and a frame that samples none deposits colour alone.  stats words 8 .. 11 +=
+// shading normals formed, fall-backs, absorbed continuations, culled light samples.
+template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false, bool kEnv = false, bool kEnvLight = false, bool kMis = false,
+          bool kSmooth = false>
 __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, const DCamera& cam, const uint32_t iteration, const DBand band,
                                           const uint32_t pix_count, const int max_bounces, const DFrame fb, DeviceCounters* counters,
                                           unsigned long long* stats, const int roulette, uint32_t* stack,
                                           const DLens lens = DLens{0.0f, 0.0f}, const DEnv env = DEnv{nullptr, 0u, 0u},
-                                          const DEnvLight el = DEnvLight{nullptr}, const DMis mis = DMis{nullptr})
+                                          const DEnvLight el = DEnvLight{nullptr}, const DMis mis = DMis{nullptr},
+                                          const DSmooth sm = DSmooth{nullptr, nullptr})
 {
+  static_assert(!kSmooth || kEnvLight, "the smooth instances sample lamps and environment by run-time choice");
   static_assert(!kEnvLight || (kEnv && kDirect), "the environment-light instance has an environment and a radiance sum");
   static_assert(!kMis || kEnvLight, "the multiple-importance instance samples lamps and environment by run-time choice");
   static_assert(kEmit || !kDirect, "direct lighting: launched only for a scene with a lamp table, so with an emissive material");
@@ -57,8 +69,9 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
   uint32_t n_diffuse = 0u, n_shadow = 0u, n_clear = 0u;
   uint32_t e_diffuse = 0u, e_shadow = 0u, e_clear = 0u;
   [[maybe_unused]] uint32_t m_emit = 0u, m_miss = 0u;
+  [[maybe_unused]] uint32_t s_formed = 0u, s_fallback = 0u, s_absorbed = 0u, s_culled = 0u;
   const bool lamps = !kEnvLight || lt.records != nullptr;
-  const bool env_lamp = !kMis || el.table != nullptr;  // (kEnvLight) the environment is sampled
+  const bool env_lamp = !(kMis || kSmooth) || el.table != nullptr;  // (kEnvLight) the environment is sampled
   if (s < pix_count) {
     const uint32_t pixel = band_pixel(band, s);
     Minstd rng;
@@ -84,7 +97,8 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       rec.side = 0u;
       ++rays;
       Tally tally;
-      if (!ray_scene<false>(ray, sc, rec, stack, flags, tally)) {
+      [[maybe_unused]] HitAttr at;
+      if (!ray_scene<false, kSmooth>(ray, sc, rec, stack, flags, tally, kSmooth ? &at : nullptr)) {
         if constexpr (kMis) {
           if (!count_env) {  // behind an environment sample: the lobe's share of the sky it reached (the entry's load first)
             ++m_miss;
@@ -96,12 +110,30 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
           }
           break;
         }
+        if constexpr (kSmooth) {  // the environment itself by env.texels
+          if (!count_env) color = mk3(0.0f, 0.0f, 0.0f);
+          else color = env.texels ? color * sky<true>(ray.d, env) : color * sky<false>(ray.d, env);
+          break;
+        }
         if (kEnvLight && !count_env) color = mk3(0.0f, 0.0f, 0.0f);  // the environment sample of the vertex before has counted it
         else color = color * sky<kEnv>(ray.d, env);
         break;
       }
+      f3 hn = rec.n;  // the shading normal: the geometric one but at a triangle hit under kSmooth
+      [[maybe_unused]] bool tri = false;
+      if constexpr (kSmooth) {
+        if (at.first != kNoChild) {
+          tri = true;
+          const uint32_t mesh = sc.object_mesh[at.object];
+          const uint32_t* idx = sc.mesh_views[mesh].indices + at.first;
+          const float* vn = sm.normals + 3u * (size_t)sm.mesh_first_vertex[mesh];
+          const f3 n0 = ld3(vn + 3u * (size_t)idx[0]), n1 = ld3(vn + 3u * (size_t)idx[1]), n2 = ld3(vn + 3u * (size_t)idx[2]);
+          if (smooth::shading_normal(n0, n1, n2, at.u, at.v, rec.n, ray.d, sc.objects[at.object].inv_m, hn)) ++s_formed;
+          else ++s_fallback;
+        }
+      }
       if (i == 0) {
-        normal = rec.n;
+        normal = hn;
         depth = rec.t;
       }
       bool tmin_flag = ray.tmin != 1e-4f;
@@ -130,7 +162,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
         color = mk3(0.0f, 0.0f, 0.0f);  // the path ends by chance: the sample is (radiance +) 0, no draw, no light sample
         break;
       }
-      evaluate_material(ray.o, ray.d, tmin_flag, rec.p, rec.n, rec.side, mat, rng, color);
+      evaluate_material(ray.o, ray.d, tmin_flag, rec.p, hn, rec.side, mat, rng, color);
       ray.tmin = tmin_flag ? 1e-5f : 1e-4f;
       if constexpr (kDirect) {
         if (lamps) count_emission = mat.type != 0;
@@ -140,29 +172,44 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
         if (mat.type == 0) {  // diffuse: colour is throughput x albedo now; one light sample at the hit, about the unflipped normal
           [[maybe_unused]] env_light::Sample es;  // (kEnvLight) the environment's sample: drawn first, its loads ahead of the lamp's shadow ray
           [[maybe_unused]] const bool weigh = kMis && i != max_bounces - 1;  // the last bounce has no continuation ray to weigh against
-          if constexpr (kMis) bsdf_pdf = mis::lobe_density(dot(rec.n, ray.d));
+          if constexpr (kMis) bsdf_pdf = mis::lobe_density(dot(hn, ray.d));
           if constexpr (kMis) {
             es.sampled = false;
             if (env_lamp) {
               ++e_diffuse;
               env_light::Terms et;
-              es = env_light::sample_point(el.table, env.texels, env.n, rec.n, pixel, iteration, 4u * (uint32_t)i, et);
+              es = env_light::sample_point(el.table, env.texels, env.n, hn, pixel, iteration, 4u * (uint32_t)i, et);
               if (weigh) es.contrib = es.contrib * mis::balance(env_light::env_density(et.jac), mis::lobe_density(et.cos_r));
             }
           } else if constexpr (kEnvLight) {
-            ++e_diffuse;
-            es = env_light::sample_point(el.table, env.texels, env.n, rec.n, pixel, iteration, 4u * (uint32_t)i);
+            if constexpr (kSmooth) es.sampled = false;
+            if (env_lamp) {
+              ++e_diffuse;
+              es = env_light::sample_point(el.table, env.texels, env.n, hn, pixel, iteration, 4u * (uint32_t)i);
+            }
+          }
+          if constexpr (kSmooth) {
+            if (tri && es.sampled && dot(es.w, rec.n) <= 0.0f) {  // behind the geometry: not sampled
+              es.sampled = false;
+              ++s_culled;
+            }
           }
           if (lamps) {
             ++n_diffuse;
             [[maybe_unused]] LightTerms lterms;
             LightSample ls;
             if constexpr (kMis) {
-              ls = light_sample_point(lt, rec.p, rec.n, pixel, iteration, 3u * (uint32_t)i, lterms);
+              ls = light_sample_point(lt, rec.p, hn, pixel, iteration, 3u * (uint32_t)i, lterms);
               if (weigh)
                 ls.contrib = ls.contrib * mis::balance(mis::lamp_density(lterms.d2, lterms.cos_l, lterms.inv_pdf), mis::lobe_density(lterms.cos_r));
             } else {
-              ls = light_sample_point(lt, rec.p, rec.n, pixel, iteration, 3u * (uint32_t)i);
+              ls = light_sample_point(lt, rec.p, hn, pixel, iteration, 3u * (uint32_t)i);
+            }
+            if constexpr (kSmooth) {
+              if (tri && ls.sampled && dot(ls.w, rec.n) <= 0.0f) {
+                ls.sampled = false;
+                ++s_culled;
+              }
             }
             if (ls.sampled) {
               ++n_shadow;
@@ -193,14 +240,23 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
           }
         }
       }
+      if constexpr (kSmooth) {
+        if (tri && mat.type != 2 && dot(ray.d, rec.n) <= 0.0f) {  // the new direction enters the geometry: absorbed
+          ++s_absorbed;
+          color = mk3(0.0f, 0.0f, 0.0f);
+          break;
+        }
+      }
     }
-    accumulate_color(fb.color4, s, iteration, kDirect ? radiance + color : color);
+    if constexpr (kSmooth) accumulate_color(fb.color4, s, iteration, lamps || env_lamp ? radiance + color : color);
+    else accumulate_color(fb.color4, s, iteration, kDirect ? radiance + color : color);
     accumulate_nd(fb.nd4, s, iteration, normal, depth);
     if (flags) atomicOr(&counters->flags, flags);
   }
   // one atomic per counter and wavefront; the three loop counters spread over lines (adds to one line serialise in L2)
   uint32_t sum = rays, sd = n_diffuse, ss = n_shadow, sv = n_clear, ed = e_diffuse, es = e_shadow, ev = e_clear;
   [[maybe_unused]] uint32_t me = m_emit, mm = m_miss;
+  [[maybe_unused]] uint32_t qf = s_formed, qb = s_fallback, qa = s_absorbed, qc = s_culled;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     sum += __shfl_down(sum, off, 64);
@@ -218,6 +274,12 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       me += __shfl_down(me, off, 64);
       mm += __shfl_down(mm, off, 64);
     }
+    if constexpr (kSmooth) {
+      qf += __shfl_down(qf, off, 64);
+      qb += __shfl_down(qb, off, 64);
+      qa += __shfl_down(qa, off, 64);
+      qc += __shfl_down(qc, off, 64);
+    }
   }
   if (threadIdx.x == 0u) {
     if (sum) atomicAdd(&counters->rays_total, (unsigned long long)sum);
@@ -234,6 +296,12 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       if constexpr (kMis) {
         if (me) atomicAdd(&line[6], (unsigned long long)me);
         if (mm) atomicAdd(&line[7], (unsigned long long)mm);
+      }
+      if constexpr (kSmooth) {
+        if (qf) atomicAdd(&line[8], (unsigned long long)qf);
+        if (qb) atomicAdd(&line[9], (unsigned long long)qb);
+        if (qa) atomicAdd(&line[10], (unsigned long long)qa);
+        if (qc) atomicAdd(&line[11], (unsigned long long)qc);
       }
     }
   }

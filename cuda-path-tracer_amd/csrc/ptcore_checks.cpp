@@ -544,6 +544,28 @@ int ptc_check_environment_light_table(const float* rgb, uint32_t n, void* entrie
   return PTC_OK;
 }
 
+// The shading normal of a triangle hit (pt_smooth.hpp) on the host: the header the megakernel's smooth instances run
+int ptc_check_shading_normal(const float* n0, const float* n1, const float* n2, const float* u, const float* v, const float* g, const float* d,
+                             const float* m16, uint32_t count, float* ns_out, uint8_t* fallback_out)
+{
+  if (!m16 || (count != 0u && (!n0 || !n1 || !n2 || !u || !v || !g || !d || !ns_out))) return PTC_ERR_INVALID;
+  m4 inv;
+  ptc_object o{};
+  const float box[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (int rc = make_object(1u, 0u, m16, nullptr, box, &o)) return rc;  // the inverse a scene's object carries
+  std::memcpy(&inv, o.inv_m, sizeof inv);
+  auto at = [](const float* p, uint32_t i) { return mk3(p[3u * (size_t)i], p[3u * (size_t)i + 1u], p[3u * (size_t)i + 2u]); };
+  for (uint32_t i = 0; i < count; ++i) {
+    f3 ns;
+    const bool formed = smooth::shading_normal(at(n0, i), at(n1, i), at(n2, i), u[i], v[i], at(g, i), at(d, i), inv, ns);
+    ns_out[3u * (size_t)i] = ns.x;
+    ns_out[3u * (size_t)i + 1u] = ns.y;
+    ns_out[3u * (size_t)i + 2u] = ns.z;
+    if (fallback_out) fallback_out[i] = formed ? (uint8_t)0 : (uint8_t)1;
+  }
+  return PTC_OK;
+}
+
 // ... and the sample (env_light::sample_draws) on the caller's points, normals and draws, written out as ptc_environment_light writes
 // a sample whose shadow ray is free
 int ptc_check_environment_light(const float* rgb, uint32_t n, const float* points, const float* normals, const uint32_t* v, const float* u,

@@ -70,6 +70,13 @@ struct ptc_scene_state {
   const float4* light_records = nullptr; // device: 4 float4 per record (ptc_light); null while there is nothing to sample
   const float* light_cdf = nullptr;      // device: the records' cdf values, dense (the binary search)
   const float* light_material_pdf = nullptr;  // device: per material its records' inv_pdf, 0 for no lamp ("mis"); with the table
+  // smooth shading (ptc_set_vertex_normals): the scene's vertex count, where each mesh's vertices start (device,
+  // uploaded with the scene), and the normals -- a device array of the scene's pool, allocated by the first call that sets any;
+  // normals_set: it holds the caller's normals now
+  uint32_t vertex_count = 0;
+  const uint32_t* mesh_first_vertex = nullptr;
+  float* vertex_normals = nullptr;
+  bool normals_set = false;
 };
 
 // the last epoch of a lap of look-back launches on a slot's tile descriptors (30 bits: pt_shade_tile.inc; ptcore_trace.cpp, next_epoch)
@@ -284,11 +291,14 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   // "mis" (DESIGN section 5l): a frame that samples lamps or the environment combines each sample with the path's own continuation ray
   // by the balance heuristic (k_megakernel_mis); a frame that samples neither launches what it launched before
   bool mis = false;
+  // "smooth_normals" (DESIGN section 5n): a frame of a scene with vertex normals shades triangle hits with the interpolated normal
+  // (k_megakernel_smooth); without normals it launches what it launched before
+  bool smooth_normals = false;
   const uint4* env_table = nullptr;
   bool env_table_known = false;
   ptc_environment_light_stats env_direct{};  // ptc_environment_light since ptc_reset_profile
   // device: kLightStatLines lines of kLoopStatWords words (0 .. 2 the lamps': diffuse hits, shadow rays, unoccluded; 3 .. 5 the environment's;
-  // 6, 7 "mis": weighted emitter hits, weighted misses)
+  // 6, 7 "mis": weighted emitter hits, weighted misses; 8 .. 11 "smooth_normals": shading normals, fall-backs, absorbed, culled)
   unsigned long long* loop_stats = nullptr;
   bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
   // the display transform (ptc_set_display; ptcore_display.cpp).  The default is the reference display: the presents

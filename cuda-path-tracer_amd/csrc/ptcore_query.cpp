@@ -405,6 +405,45 @@ int ptc_intersect_rays(ptc_ctx* ctx, const float* rays, uint32_t n, float* hit_t
   return PTC_OK;
 }
 
+// The closest hit's primitive and attributes: k_hit_attributes, one thread per ray on the reference's walk, with
+// the scene's vertex normals if any are set.  The rays go up as the caller wrote them, 8 floats each.
+int ptc_hit_attributes(ptc_ctx* ctx, const float* rays, uint32_t n, uint32_t* object_out, uint32_t* triangle_out, float* uv_out, float* normal_out)
+{
+  if (!ctx || !rays || !object_out || !triangle_out || !uv_out || !normal_out) return PTC_ERR_INVALID;
+  int rc;
+  if (!query_prologue(ctx, n, "rays", nullptr, &rc)) return rc;
+  QueryRun q(ctx, false);
+  float4* d_rays = nullptr;
+  uint32_t *d_obj = nullptr, *d_tri = nullptr, *d_flags = nullptr;
+  float2* d_uv = nullptr;
+  float* d_nrm = nullptr;
+  rc = q.alloc(&d_rays, 2u * (size_t)n);
+  if (!rc) rc = q.alloc(&d_obj, n);
+  if (!rc) rc = q.alloc(&d_tri, n);
+  if (!rc) rc = q.alloc(&d_uv, n);
+  if (!rc) rc = q.alloc(&d_nrm, 3u * (size_t)n);
+  if (!rc) rc = q.alloc(&d_flags, 1);
+  if (rc) return rc;
+  uint32_t dev_flags = 0u;
+  auto run = [&]() -> int {
+    HIP_TRY(ctx, hipMemcpyAsync(d_rays, rays, 8u * (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, sizeof(uint32_t), ctx->stream));
+    launch_hit_attributes(ctx->stream, ctx->scene, DSmooth{ctx->normals_set ? ctx->vertex_normals : nullptr, ctx->mesh_first_vertex}, d_rays, n, d_obj,
+                          d_tri, d_uv, d_nrm, d_flags);
+    if (int r2 = check_last(ctx, "hit_attributes")) return r2;
+    HIP_TRY(ctx, hipMemcpyAsync(object_out, d_obj, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(triangle_out, d_tri, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(uv_out, d_uv, n * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(normal_out, d_nrm, 3u * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&dev_flags, d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PTC_OK;
+  };
+  if ((rc = q.finish(run())) != PTC_OK) return rc;
+  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, "traversal stack overflow in ptc_hit_attributes");
+  return PTC_OK;
+}
+
 int ptc_occluded_rays(ptc_ctx* ctx, const float* rays, uint32_t n, uint8_t* occluded)
 {
   if (!ctx || !rays || !occluded) return PTC_ERR_INVALID;

@@ -475,6 +475,7 @@ struct NewScene : ptc_scene_state {
   std::vector<float> material_pdf; // per material the records' inv_pdf (light_material_pdf); uploaded with the lamp table
   std::vector<float4> balls;       // DScene::sphere_ball
   std::vector<uint32_t> tri_base;  // DScene::object_tri_base
+  std::vector<uint32_t> first_vertex;  // per mesh: where its vertices start in the scene's arrays (vertex normals, section 5n)
   size_t tri_records = 0;          // records of DScene::tris
   std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now(), last = start;
   void lap(float& into)
@@ -576,6 +577,8 @@ int stage_host(ptc_ctx* ctx, const ptc_scene_desc* s, const std::vector<MeshWork
     if (n.tri_records > 0x7fffffffull) return fail(ctx, PTC_ERR_OOM, "too many instance triangles");
   }
   n.launches = launch_table(s->objects, object_nodes, &n.tail_begin, &n.tail_end);
+  n.vertex_count = s->vertex_count;
+  for (uint32_t m = 0; m < meshes.size(); ++m) n.first_vertex.push_back(s->meshes ? s->meshes[m].first_vertex : 0u);
   for (const MeshWork& w : meshes) {
     n.bvh_nodes += w.node_count;
     n.bvh_depth = std::max(n.bvh_depth, w.depth);
@@ -732,6 +735,7 @@ int mesh_tables(ptc_ctx* ctx, const std::vector<MeshWork>& meshes, NewScene& n)
   }
   if (int rc = upload(ctx, n.scene_allocs, &d.mesh_views, n.mesh_views.data(), n.mesh_views.size())) return rc;
   if (int rc = upload(ctx, n.scene_allocs, &d.object_mesh, n.object_mesh.data(), n.object_mesh.size())) return rc;
+  if (int rc = upload(ctx, n.scene_allocs, &n.mesh_first_vertex, n.first_vertex.data(), n.first_vertex.size())) return rc;
   if (meshes.empty()) return PTC_OK;
   d.cur = n.mesh_views[0];
   const uint64_t t0 = meshes[0].triangles, n0 = meshes[0].node_count;
@@ -865,6 +869,46 @@ int ptc_get_light_info(ptc_ctx* ctx, ptc_light_info* out)
   if (!ctx || !out) return PTC_ERR_INVALID;
   if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
   *out = ctx->light_info;
+  return PTC_OK;
+}
+
+// Vertex normals beside the scene.  Every refusal comes before anything is touched; the device array joins the
+// scene's pool, so the scene's one release path (ptc_upload_scene: free_pool, then a value-initialised ptc_scene_state) takes it.
+int ptc_set_vertex_normals(ptc_ctx* ctx, const float* normals, uint32_t vertex_count)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
+  if ((normals == nullptr) != (vertex_count == 0u)) return fail(ctx, PTC_ERR_INVALID, "vertex normals: NULL and 0 go together (they remove the normals)");
+  if (normals && vertex_count != ctx->vertex_count)
+    return fail(ctx, PTC_ERR_INVALID, "vertex normals: " + std::to_string(vertex_count) + " normals for a scene of " + std::to_string(ctx->vertex_count) +
+                                          " vertices");
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;  // frames queued or in flight were asked for with what was set
+  if (!normals) {
+    ctx->normals_set = false;
+    return PTC_OK;
+  }
+  if (!ctx->vertex_normals)
+    if (int rc = dev_alloc(ctx, ctx->scene_allocs, &ctx->vertex_normals, 3u * (size_t)vertex_count)) return rc;
+  HIP_TRY(ctx, hipMemcpy(ctx->vertex_normals, normals, 3u * (size_t)vertex_count * sizeof(float), hipMemcpyHostToDevice));
+  ctx->normals_set = true;
+  return PTC_OK;
+}
+
+int ptc_get_vertex_normals(const ptc_ctx* ctx, uint32_t* vertex_count)
+{
+  const bool set = ctx && ctx->has_scene && ctx->normals_set;
+  if (vertex_count) *vertex_count = set ? ctx->vertex_count : 0u;
+  return set ? 1 : 0;
+}
+
+int ptc_compute_vertex_normals(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count, float* normals_out)
+{
+  if (!normals_out || (vertex_count && !positions) || (index_count && !indices)) return fail(nullptr, PTC_ERR_INVALID, "vertex normals: an array is NULL");
+  if (index_count % 3u != 0u) return fail(nullptr, PTC_ERR_INVALID, "vertex normals: index_count is no multiple of 3");
+  if (const int64_t i = first_index_out_of_range(indices, index_count, vertex_count); i >= 0)
+    return fail(nullptr, PTC_ERR_INVALID, "vertex normals: index " + std::to_string(i) + " names no vertex");
+  smooth::vertex_normals(positions, vertex_count, indices, index_count, normals_out);
   return PTC_OK;
 }
 

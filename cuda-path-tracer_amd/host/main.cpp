@@ -52,6 +52,7 @@ struct CliConfigurations {  // configurations.hpp:11-15
   bool direct_light = false;
   bool environment_light = false;
   bool mis = false;
+  bool smooth_normals = false;
   int roulette = 0;
   std::optional<float> lens_radius, focus_distance;  // the thin lens (override the scene file's camera keys)
   // environment lighting (override the scene file's "environment" key, each on its own)
@@ -88,6 +89,8 @@ void usage()
                "                       a scene whose \"environment\" says \"light\": true asks for it under --method megakernel)\n"
                "      --mis            multiple importance sampling: light samples and the path's own ray combined by the balance heuristic\n"
                "                       (needs --method megakernel and --direct-light, --environment-light or a scene that says \"light\": true)\n"
+               "      --smooth-normals  shade every mesh with interpolated vertex normals, area-weighted from its triangles (needs --method\n"
+               "                       megakernel; a scene that says \"smooth_normals\": true asks for it)\n"
                "      --environment FILE  environment lighting: an equirectangular Radiance .hdr (overrides the scene's \"environment\")\n"
                "      --environment-scale S  multiply the picture by S, a finite number >= 0 (default 1)\n"
                "      --environment-size N  size of the octahedral map made from it, in [2,4096] (default: the picture's height)\n"
@@ -131,6 +134,7 @@ CliConfigurations parse_cli_args(int argc, char** argv)
     else if (a == "--direct-light") c.direct_light = true;
     else if (a == "--environment-light") c.environment_light = true;
     else if (a == "--mis") c.mis = true;
+    else if (a == "--smooth-normals") c.smooth_normals = true;
     else if (a == "--roulette") {
       // a whole decimal number in [0, 64] (ptc_set_param's range), refused here: before the scene is read or a GPU touched
       const std::string v = need("roulette");
@@ -237,6 +241,10 @@ CliConfigurations parse_cli_args(int argc, char** argv)
   }
   if (c.mis && !c.megakernel) {  // ... and nothing to combine
     std::fprintf(stderr, "hip_pt: --mis needs --method megakernel (the streaming method renders no direct light)\n");
+    std::exit(1);
+  }
+  if (c.smooth_normals && !c.megakernel) {  // ... and shades with face normals
+    std::fprintf(stderr, "hip_pt: --smooth-normals needs --method megakernel (the streaming method shades with face normals)\n");
     std::exit(1);
   }
   if (c.tone_flag && (c.display == DisplayBufferType::normal || c.display == DisplayBufferType::depth)) {
@@ -372,6 +380,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   PathTracer path_tracer{configs.gpu};
   path_tracer.max_bounces = configs.max_bounces;
   path_tracer.max_iterations = scene_desc.spp;      // app.cpp:130
+  path_tracer.smooth_normals = configs.smooth_normals || scene_desc.smooth_normals;  // (before create_buffers, which computes the normals)
   path_tracer.create_buffers(resolution, scene_desc);
   bool enable_denoising = configs.denoise;
   DisplayBufferType display = configs.display;
@@ -491,6 +500,7 @@ try {
   // (the flag, or the scene's "environment": {"light": true} where the method renders it)
   path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
   path_tracer.mis = configs.mis;
+  path_tracer.smooth_normals = configs.smooth_normals || scene_desc.smooth_normals;  // (before create_buffers, which computes the normals)
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.display = configs.tone;
@@ -576,8 +586,9 @@ int run_ranks(const CliConfigurations& configs, const SceneDescription& scene_de
     return 1;
   }
   // (the megakernel seeds by frame pixel, so its ranks render the single-GPU image; it is let through for --direct-light,
-  // --environment-light and --mis, which the streaming method cannot render)
-  if (configs.denoise || (configs.megakernel && !configs.direct_light && !configs.environment_light && !configs.mis)) {
+  // --environment-light, --mis and --smooth-normals, which the streaming method cannot render)
+  if (configs.denoise ||
+      (configs.megakernel && !configs.direct_light && !configs.environment_light && !configs.mis && !configs.smooth_normals && !scene_desc.smooth_normals)) {
     std::fprintf(stderr, "hip_pt: --gpus N renders in streaming mode without the denoiser (it needs the whole frame in one context)\n");
     return 1;
   }
@@ -639,6 +650,11 @@ try {
   SceneDescription scene_desc = scene_from_json(path.string(), /*read_environment*/ false);  // (the picture: below, once)
   scene_desc.filename = configs.filename;
   if (configs.spp) scene_desc.spp = *configs.spp;
+  // a scene that asks for smooth normals needs the method that renders them (before any GPU is touched)
+  if (scene_desc.smooth_normals && !configs.megakernel) {
+    std::fprintf(stderr, "hip_pt: the scene says \"smooth_normals\": true, which needs --method megakernel (the streaming method shades with face normals)\n");
+    return 1;
+  }
   // --mis combines light samples with the path: it needs a light that is sampled (before any GPU is touched)
   if (configs.mis && !configs.direct_light && !configs.environment_light && !scene_desc.environment_source.light) {
     std::fprintf(stderr, "hip_pt: --mis needs --direct-light, --environment-light or a scene whose \"environment\" says \"light\": true\n");
@@ -716,6 +732,7 @@ try {
   // (the flag, or the scene's "environment": {"light": true} where the method renders it)
   path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
   path_tracer.mis = configs.mis;
+  path_tracer.smooth_normals = configs.smooth_normals || scene_desc.smooth_normals;  // (before create_buffers, which computes the normals)
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.display = configs.tone;

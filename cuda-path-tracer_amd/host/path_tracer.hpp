@@ -44,6 +44,10 @@ public:
   bool environment_light = false;
   // the balance heuristic between light samples and the path's own ray (megakernel method only; ptc_set_param "mis")
   bool mis = false;
+  // smooth shading (megakernel method only; ptc_set_param "smooth_normals"): triangle hits are shaded with the
+  // interpolated vertex normal.  Set before create_buffers it also makes create_buffers compute and set the scene's vertex normals
+  // (compute_vertex_normals); vertex normals of the caller's own go through set_vertex_normals after create_buffers.
+  bool smooth_normals = false;
   int roulette = 0;  // Russian roulette at every bounce >= this but the last, 0 = off (both methods; ptc_set_param "roulette", [0, 64])
   // the thin lens (ptc_set_lens): aperture radius (0 = the pinhole, the default) and the distance of the plane in
   // focus, world units; both methods
@@ -89,7 +93,42 @@ public:
     d.indices = flat.indices.data();
     d.index_count = (uint32_t)flat.indices.size();
     check(ptc_upload_scene(ctx_, &d), "create_buffers");
+    if (smooth_normals && !flat.indices.empty()) set_vertex_normals(compute_vertex_normals(flat));  // (a new scene starts without normals)
     resize_image(r);
+  }
+
+  // area-weighted vertex normals of the scene's mesh (ptc_compute_vertex_normals; host only): three floats per vertex
+  [[nodiscard]] static std::vector<float> compute_vertex_normals(const FlatScene& flat)
+  {
+    std::vector<float> normals(flat.positions.size(), 0.0f);
+    if (ptc_compute_vertex_normals(flat.positions.data(), (uint32_t)(flat.positions.size() / 3), flat.indices.data(), (uint32_t)flat.indices.size(),
+                                   normals.data()) < 0)
+      throw std::runtime_error(std::string("compute_vertex_normals: ") + ptc_last_error(nullptr));
+    return normals;
+  }
+  // the uploaded scene's vertex normals (ptc_set_vertex_normals): three floats per vertex of the scene; an empty vector removes them
+  void set_vertex_normals(const std::vector<float>& normals)
+  {
+    check(ptc_set_vertex_normals(ctx_, normals.empty() ? nullptr : normals.data(), (uint32_t)(normals.size() / 3)), "vertex_normals");
+  }
+  [[nodiscard]] ptc_smooth_loop_stats smooth_loop_stats() const
+  {
+    ptc_smooth_loop_stats s{};
+    check(ptc_get_smooth_loop_stats(ctx_, &s), "smooth_loop_stats");
+    return s;
+  }
+  // the closest hit's primitive and attributes (ptc_hit_attributes): rays 8 floats each; per ray object, triangle, (u, v), normal
+  struct HitAttributes {
+    std::vector<uint32_t> object, triangle;
+    std::vector<float> uv, normal;
+  };
+  [[nodiscard]] HitAttributes hit_attributes(const std::vector<float>& rays)
+  {
+    push_fields();
+    const uint32_t n = (uint32_t)(rays.size() / 8);
+    HitAttributes out{std::vector<uint32_t>(n), std::vector<uint32_t>(n), std::vector<float>(2u * (size_t)n), std::vector<float>(3u * (size_t)n)};
+    check(ptc_hit_attributes(ctx_, rays.data(), n, out.object.data(), out.triangle.data(), out.uv.data(), out.normal.data()), "hit_attributes");
+    return out;
   }
 
   void path_trace(const Camera& camera, UResolution)
@@ -143,6 +182,10 @@ private:
       check(ptc_set_param(ctx_, "mis", mis ? 1 : 0), "mis");
       mis_pushed_ = mis;
     }
+    if (smooth_normals != smooth_normals_pushed_) {
+      check(ptc_set_param(ctx_, "smooth_normals", smooth_normals ? 1 : 0), "smooth_normals");
+      smooth_normals_pushed_ = smooth_normals;
+    }
     if (roulette != roulette_pushed_) {
       check(ptc_set_param(ctx_, "roulette", roulette), "roulette");
       roulette_pushed_ = roulette;
@@ -168,6 +211,7 @@ private:
   bool direct_light_pushed_ = false;
   bool environment_light_pushed_ = false;
   bool mis_pushed_ = false;
+  bool smooth_normals_pushed_ = false;
   int roulette_pushed_ = 0;
   Lens lens_pushed_{};
   std::shared_ptr<const EnvironmentMap> environment_pushed_;

@@ -336,6 +336,11 @@ SceneDescription scene_from_json(const std::string& filename, bool read_environm
     scene.resolution[1] = (int)r->arr[1]->num;
   }
   if (const Json* sampler = root->find("sampler")) scene.spp = (int)sampler->at("samples").num;
+  // smooth shading (an extension; json_parser.py, the same rule): the top-level key "smooth_normals", a boolean
+  if (const Json* sm = root->find("smooth_normals")) {
+    if (sm->kind != Json::Bool) throw std::runtime_error("Json Parser: \"smooth_normals\" must be true or false");
+    scene.smooth_normals = sm->b;
+  }
   // environment lighting (an extension; json_parser.py, the same rule): {"file": a Radiance .hdr, equirectangular, relative to the
   // scene file; "scale": a finite number >= 0, default 1; "size": an integer in [2,4096], default the picture's height, at most 4096;
   // "light": a boolean, default false -- sample the environment as a light under the megakernel method}

@@ -80,6 +80,9 @@ public:
     int size = 0;
     bool light = false;  // "light": true -- the scene asks for environment light sampling where the method renders it
   } environment_source;
+  // smooth shading (an extension): the scene file's "smooth_normals": true -- shade every mesh with interpolated
+  // vertex normals, computed from its triangles (the megakernel method renders them)
+  bool smooth_normals = false;
 
   void add_material(const std::string& name, Material material);
   void add_object(Sphere sphere, const Mat4& transform, const std::string& material_name);

@@ -159,6 +159,10 @@ def scene_from_json(filename):
     if "resolution" in cam:
         scene.resolution = (int(cam["resolution"][0]), int(cam["resolution"][1]))
     scene.spp = int(root["sampler"]["samples"]) if "sampler" in root else 1
+    if "smooth_normals" in root:  # (an extension; scene_description.cpp, the same rule)
+        if not isinstance(root["smooth_normals"], bool):
+            raise ValueError('Json Parser: "smooth_normals" must be true or false')
+        scene.smooth_normals = root["smooth_normals"]
     if "environment" in root:
         scene.environment, scene.environment_source = _environment(root["environment"], file_dir)
     return scene

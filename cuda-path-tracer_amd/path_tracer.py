@@ -78,6 +78,27 @@ def light_material_pdf(scene, capacity=None):
     return out[:rc].copy()
 
 
+def compute_vertex_normals(positions, indices=None, mesh_ranges=None):
+    """Area-weighted vertex normals (ptc_compute_vertex_normals; host-side, no GPU needed).  positions [v, 3] and
+    indices [t * 3] of one mesh, or -- with mesh_ranges, a mesh table's rows (first_vertex, vertex_count, first_index, index_count, ...)
+    -- of a whole scene, mesh by mesh.  A FlatScene or SceneDescription in place of positions brings all three.  -> float32 [v, 3], a
+    zero vector for a vertex no triangle uses or whose sum has no direction."""
+    if isinstance(positions, SceneDescription):
+        positions = positions.build_scene()
+    if isinstance(positions, FlatScene):
+        positions, indices, mesh_ranges = positions.positions, positions.indices, getattr(positions, "mesh_ranges", None)
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    out = np.zeros_like(pos)
+    rows = [(0, len(pos), 0, len(idx))] if mesh_ranges is None else [tuple(int(x) for x in r[:4]) for r in np.asarray(mesh_ranges).reshape(-1, 6)]
+    for fv, nv, fi, ni in rows:
+        p, i, o = np.ascontiguousarray(pos[fv:fv + nv]), np.ascontiguousarray(idx[fi:fi + ni]), np.zeros((nv, 3), dtype=np.float32)
+        _capi.check(_capi.lib().ptc_compute_vertex_normals(p.ctypes.data_as(C.c_void_p), nv, i.ctypes.data_as(C.c_void_p), ni,
+                                                          o.ctypes.data_as(C.c_void_p)))
+        out[fv:fv + nv] = o
+    return out
+
+
 class ToneCurve(IntEnum):  # ptc_curve
     clamp = 0
     reinhard = 1
@@ -143,6 +164,8 @@ class PathTracer:
         self._direct_light = False  # PathTracer.direct_light = True: a light sample at every diffuse hit (megakernel method only)
         self._environment_light = False  # PathTracer.environment_light = True: an environment sample at every diffuse hit (megakernel only)
         self._mis = False  # PathTracer.mis = True: the balance heuristic between light samples and the path (megakernel only)
+        self._smooth_normals = False  # PathTracer.smooth_normals = True: interpolated vertex normals at triangle hits (megakernel only)
+        self._vertex_normals = None  # PathTracer.vertex_normals = [v, 3] float32, parallel to the uploaded scene's positions (None: none)
         self._roulette = 0  # PathTracer.roulette = k: Russian roulette at every bounce >= k but the last (0 = off)
         self._lens = (0.0, 1.0)  # PathTracer.lens = (radius, focus_distance): the thin lens (radius 0 = the pinhole)
         self._environment = None  # PathTracer.environment = [n, n, 3] float32: an octahedral HDR sky (None = the reference's gradient)
@@ -157,6 +180,7 @@ class PathTracer:
         self._direct_light_pushed = False
         self._environment_light_pushed = False
         self._mis_pushed = False
+        self._smooth_normals_pushed = False
         self._roulette_pushed = 0
         self._lens_pushed = (0.0, 1.0)
         self._environment_pushed = None
@@ -212,6 +236,34 @@ class PathTracer:
     @mis.setter
     def mis(self, on):
         self._mis = bool(on)
+
+    @property
+    def smooth_normals(self):
+        """Smooth shading in the megakernel (ptc_set_param "smooth_normals"): True = a triangle hit is shaded with
+        the normal interpolated from vertex_normals.  Changes nothing while no vertex normals are set."""
+        return self._smooth_normals
+
+    @smooth_normals.setter
+    def smooth_normals(self, on):
+        self._smooth_normals = bool(on)
+
+    @property
+    def vertex_normals(self):
+        """The scene's vertex normals (ptc_set_vertex_normals): [v, 3] float32 parallel to the uploaded scene's positions, object space,
+        any length; None removes them.  Assignment uploads at once -- after create_buffers, which starts every scene without normals --
+        and a refusal (no scene, another vertex count) raises PtcError and leaves what was set."""
+        return self._vertex_normals
+
+    @vertex_normals.setter
+    def vertex_normals(self, value):
+        if value is None:
+            self._check(self._lib.ptc_set_vertex_normals(self._ctx, None, 0))
+            self._vertex_normals = None
+            return
+        n = np.array(value, dtype=np.float32, order="C").reshape(-1, 3)
+        self._check(self._lib.ptc_set_vertex_normals(self._ctx, n.ctypes.data_as(C.c_void_p), len(n)))
+        n.setflags(write=False)
+        self._vertex_normals = n
 
     @property
     def roulette(self):
@@ -330,6 +382,9 @@ class PathTracer:
         if self._mis != self._mis_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"mis", 1 if self._mis else 0))
             self._mis_pushed = self._mis
+        if self._smooth_normals != self._smooth_normals_pushed:
+            self._check(self._lib.ptc_set_param(self._ctx, b"smooth_normals", 1 if self._smooth_normals else 0))
+            self._smooth_normals_pushed = self._smooth_normals
         if self._roulette != self._roulette_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"roulette", self._roulette))
             self._roulette_pushed = self._roulette
@@ -366,6 +421,7 @@ class PathTracer:
         assert isinstance(flat, FlatScene)
         desc = flat.to_c()
         self._check(self._lib.ptc_upload_scene(self._ctx, C.byref(desc)))
+        self._vertex_normals = None  # (a new scene starts without normals)
         self.resize_image(resolution)
 
     def path_trace(self, camera, resolution=None):
@@ -706,6 +762,28 @@ class PathTracer:
         s = _capi.ptc_mis_loop_stats()
         self._check(self._lib.ptc_get_mis_loop_stats(self._ctx, C.byref(s)))
         return {"weighted_emitter_hits": int(s.weighted_emitter_hits), "weighted_misses": int(s.weighted_misses)}
+
+    def smooth_loop_stats(self):
+        """Counters of the megakernel under smooth_normals = True with vertex normals set, since restart: triangle hits shaded with the
+        interpolated normal, those that fell back to the geometric one, paths whose new direction entered the geometry, light samples
+        culled because theirs did."""
+        s = _capi.ptc_smooth_loop_stats()
+        self._check(self._lib.ptc_get_smooth_loop_stats(self._ctx, C.byref(s)))
+        return {"shading_normals": int(s.shading_normals), "fallbacks": int(s.fallbacks), "absorbed": int(s.absorbed),
+                "culled_light_samples": int(s.culled_light_samples)}
+
+    def hit_attributes(self, rays):
+        """The closest hit's primitive and attributes (ptc_hit_attributes) of rays [n, 8] (origin, t_min, direction, t_max) ->
+        dict(object uint32 [n] (0xffffffff: a miss), triangle uint32 [n] (0xffffffff: a sphere or a miss), uv float32 [n, 2],
+        normal float32 [n, 3]: the shading normal where vertex normals are set, else the geometric one)."""
+        self._push_fields()
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(r)
+        obj, tri = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        uv, nrm = np.zeros((n, 2), dtype=np.float32), np.zeros((n, 3), dtype=np.float32)
+        self._check(self._lib.ptc_hit_attributes(self._ctx, r.ctypes.data_as(C.c_void_p), n, obj.ctypes.data_as(C.c_void_p),
+                                                 tri.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p)))
+        return {"object": obj, "triangle": tri, "uv": uv, "normal": nrm}
 
     def environment_light_pdf(self, dirs):
         """The environment sample's solid-angle density (ptc_environment_light_pdf) in unit directions [n, 3] -> float32 [n].  Needs

@@ -155,6 +155,9 @@ class SceneDescription:
         # None (the reference's gradient); environment_source: the scene file's entry it came from ({"file", "scale", "size"}, and "light" if the file gives it)
         self.environment = None
         self.environment_source = None
+        # smooth shading (an extension): the scene file's "smooth_normals": true -- PathTracer.smooth_normals with
+        # compute_vertex_normals' normals is what renders it (the megakernel method)
+        self.smooth_normals = False
 
     def add_material(self, name, material):   # scene_description.cpp:150-153 (try_emplace: first one wins)
         self.material_map_.setdefault(name, material)

@@ -358,6 +358,13 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *                      those of the same render with 0: only colour differs.  A frame that samples neither light renders bit for bit
  *                      as with 0.  Under PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is 1,
  *                      before anything is queued.  Counters: ptc_get_mis_loop_stats.  Any time (queued frames are flushed first)
+ *   "smooth_normals"   RENDERING (default 0; an extension): 1 = under PTC_METHOD_MEGAKERNEL, in a scene with vertex normals
+ *                      (ptc_set_vertex_normals), a triangle hit is shaded with the interpolated vertex normal: the normal plane, the
+ *                      material's lobes and the light samples take it, the geometric normal keeps `side` and the lamp-side terms.  A
+ *                      light sample or a diffuse / metal continuation that lies behind the geometry counts as 0.  Every other
+ *                      parameter combines with it.  Without vertex normals a frame launches what it launched with 0.  Under
+ *                      PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is 1, before anything is
+ *                      queued.  Counters: ptc_get_smooth_loop_stats.  Any time (queued frames are flushed first)
  *   "roulette"         RENDERING (default 0 = off; an extension): k in [1, 64] = Russian roulette at every bounce b >= k
  *                      except the last one, under both methods (and "direct_light").  A path whose closest hit exists and is no emitter
  *                      takes q = the largest component of the throughput that came into the bounce; q >= 1 changes nothing (no draw); else
@@ -706,6 +713,39 @@ typedef struct ptc_mis_loop_stats {
 } ptc_mis_loop_stats;
 int ptc_get_mis_loop_stats(ptc_ctx* ctx, ptc_mis_loop_stats* out);
 
+/* Smooth shading ("smooth_normals", an extension: the reference shades every triangle with its face normal).
+ *
+ * ptc_set_vertex_normals: three floats per vertex, parallel to the uploaded scene's `positions` and covering the whole scene -- a mesh
+ * of a mesh table finds its normals at first_vertex, as its positions do.  Object space; they need not be unit length.  NULL / 0
+ * removes them.  PTC_ERR_NO_SCENE without a scene, PTC_ERR_INVALID (with a message) when vertex_count differs from the scene's or
+ * exactly one of the two arguments is NULL / 0; a refusal leaves what was set in place.  The device copy belongs to the scene:
+ * ptc_upload_scene releases it with the scene, and a new scene starts without normals; ptc_resize and the context's settings do not
+ * touch it.  Queued frames are traced first. */
+int ptc_set_vertex_normals(ptc_ctx* ctx, const float* normals, uint32_t vertex_count);
+/* 1 and *vertex_count (may be NULL) = the scene's vertex count while normals are set; 0 and *vertex_count = 0 when none are. */
+int ptc_get_vertex_normals(const ptc_ctx* ctx, uint32_t* vertex_count);
+/* Area-weighted vertex normals of ONE mesh, on the host (no GPU, no context): triangles in index order, c = cross(p1 - p0, p2 - p0)
+ * added to the sums of corners 0, 1, 2 in that order, binary32, nothing contracted; then every sum s with 0 < dot(s, s) <= FLT_MAX
+ * becomes normalize(s) and every other one -- zero, not finite, a vertex no triangle uses -- (0, 0, 0).  The order is serial and
+ * fixed (tests/smooth_ref.py restates it bit for bit); there is no device version, whose float atomics would make the sums depend on
+ * scheduling.  normals_out: 3 vertex_count floats.  PTC_ERR_INVALID: a NULL, index_count no multiple of 3, an index out of range. */
+int ptc_compute_vertex_normals(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count, float* normals_out);
+/* The closest hit's primitive and its attributes, for callers that interpolate attributes of their own.  rays: 8 floats a ray, as for
+ * ptc_intersect_rays.  Per ray: object_out = the object's index, 0xffffffff on a miss; triangle_out = the triangle of its mesh (the
+ * offset of its first index / 3), 0xffffffff for a sphere and on a miss; uv_out = the accepted triangle test's u, v (vertex 1's and
+ * vertex 2's weights; 0, 0 otherwise); normal_out (3 floats) = the shading normal of section 5n where vertex normals are set and a
+ * triangle was hit, else the geometric normal facing the ray, zeros on a miss.  Host pointers.  One thread per ray walks the
+ * reference's tree in the reference's order (an equal t is accepted: within a mesh the triangle visited last wins, across objects the
+ * later one): it names the winner the render loops' own walks find, and makes no claim about speed. */
+int ptc_hit_attributes(ptc_ctx* ctx, const float* rays, uint32_t n, uint32_t* object_out, uint32_t* triangle_out, float* uv_out, float* normal_out);
+/* The megakernel under "smooth_normals" 1 with vertex normals set, since ptc_restart: triangle hits whose shading normal was the
+ * interpolated one, those that fell back to the geometric normal, paths ended because the new direction entered the geometry, light
+ * samples culled because theirs did.  Synchronises.  Moves nothing else, and nothing moves it but ptc_trace and ptc_restart. */
+typedef struct ptc_smooth_loop_stats {
+  uint64_t shading_normals, fallbacks, absorbed, culled_light_samples;
+} ptc_smooth_loop_stats;
+int ptc_get_smooth_loop_stats(ptc_ctx* ctx, ptc_smooth_loop_stats* out);
+
 /* Where the time of the last ptc_upload_scene went (milliseconds of host wall clock; the "Initialization" stage of
  * the reference's Stopwatch, cli.cpp): */
 typedef struct ptc_upload_times {
@@ -816,6 +856,12 @@ int ptc_check_environment_apron(const float* rgb, uint32_t n, float* texels_out)
  * GPU, no context; test hook.  entries_out (may be NULL): n n entries of 16 bytes {float q, uint32 alias, float f, float f of the
  * alias}, in table order k = j n + i; zeros for a map of weight 0.  *total_weight = W, *positive_squares = the squares of weight > 0. */
 int ptc_check_environment_light_table(const float* rgb, uint32_t n, void* entries_out, double* total_weight, uint64_t* positive_squares);
+/* The shading normal of section 5n (csrc/pt_smooth.hpp, the header the megakernel's smooth instances run on the device) on the host: no
+ * GPU, no context; test hook.  Per case i the vertex normals n0, n1, n2 (3 floats each), the barycentrics u, v, the geometric normal g
+ * facing the ray and the ray direction d (3 floats each), all under the object matrix m16 (column-major; its inverse as ptc_make_object
+ * computes it).  ns_out: 3 floats a case; fallback_out (may be NULL): 1 where the rule fell back to g. */
+int ptc_check_shading_normal(const float* n0, const float* n1, const float* n2, const float* u, const float* v, const float* g, const float* d,
+                             const float* m16, uint32_t count, float* ns_out, uint8_t* fallback_out);
 /* ... and the sample on `count` caller-given points, normals and draws (v[i]: a raw value 1 .. 2^31 - 2; u + 3 i: u1, u2, u3), written as
  * ptc_environment_light writes a sample whose shadow ray is free: radiance 3 floats, shadow_rays 8 floats (may be NULL), sampled one
  * byte (may be NULL) per point.  PTC_ERR_INVALID: a NULL, n out of range, a bad component, a v out of range. */
