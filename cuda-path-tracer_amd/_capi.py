@@ -254,6 +254,8 @@ SIGNATURES = {
     "ptc_check_environment_light_pdf": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptc_check_environment_light": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    "ptc_check_light_sample": (C.c_int, [C.POINTER(ptc_scene_desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptc_set_display": (C.c_int, [_P, C.POINTER(ptc_display_params)]),
     "ptc_get_display": (C.c_int, [_P, C.POINTER(ptc_display_params)]),
     "ptc_get_exposure_info": (C.c_int, [_P, C.POINTER(ptc_exposure_info)]),

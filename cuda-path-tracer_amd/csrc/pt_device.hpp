@@ -533,10 +533,11 @@ void launch_occlude_spheres(hipStream_t s, const DScene& scene, uint32_t obj_beg
 void launch_occlude(hipStream_t s, const DScene& scene, uint32_t obj_index, const float4* rays_o, const float4* rays_d,
                     uint8_t* occluded, int work_slot, DeviceCounters* counters, uint32_t waves, uint32_t* slow_list, const DBatchInfo& bi);
 // direct-light queries (pt_light.hip).  The lamp table lives outside DScene (which every other kernel takes
-// by value): records = 4 float4 per lamp primitive (ptc_light), cdf = the records' cdf values as a dense array.
+// by value): records = 4 float4 per lamp primitive (ptc_light), thresholds = per record the first of the generator's 2^31 - 2 states
+// that belongs to a later record (build_light_table), as a dense array.
 struct DLights {
   const float4* records;
-  const float* cdf;
+  const uint32_t* thresholds;
   uint32_t count, last;        // records; last record with a weight > 0
   const DObject* objects;      // DScene's arrays: a sphere lamp reads its object's matrix and its sphere, every lamp its material
   const float4* spheres;

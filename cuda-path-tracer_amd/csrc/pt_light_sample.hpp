@@ -1,6 +1,6 @@
 // pt_light_sample.hpp -- one light sample for one surface point: the function k_light_sample (pt_light.hip) and
 // k_megakernel_direct (pt_mega_direct.hip) both call, and k_megakernel_mis (pt_mega_mis.hip, section 5l) with the sample's terms.  Host-callable, so that the arithmetic can be run on a CPU
-// as well.
+// as well (ptc_check_light_sample, ptcore_checks.cpp: light_pick and light_sample_draws on the caller's draws).
 //
 // Every line of the arithmetic is one IEEE binary32 operation of the order written down in DESIGN section 5f (-ffp-contract=off,
 // correctly rounded divide and sqrt); tests/direct_ref.py restates it in numpy, operation for operation.
@@ -25,26 +25,26 @@ struct LightSample {
 struct LightTerms {
   float d2, cos_l, inv_pdf, cos_r;
 };
-// discard: draws of the point's light stream to skip first -- 0 for a query (k_light_sample), 3 * bounce in the render loop, whose
-// bounce b so takes draws 3b .. 3b + 2 of the stream (discard(0) leaves a generator as it is, so it is not executed)
-// terms: the sample's LightTerms (meaningful where the sample is `sampled`)
-PT_HD LightSample light_sample_point(const DLights& lt, const f3 p, const f3 nrm, uint32_t i, uint32_t sample_index, uint32_t discard,
-                                     LightTerms& terms)
+// The lamp of the raw first draw v (Minstd::next, 1 .. 2^31 - 2): k = min(#{j : T_j <= v - 1}, last) over the table's integer thresholds
+// (build_light_table), 4 bytes a step (count and last are kernel arguments: wave-uniform).  Exact: lamp k owns T_k - T_(k-1) of the
+// generator's 2^31 - 2 states (a binary32 cdf has a step of 2^-24 near 1, and the lamps below it were never picked).
+PT_HD uint32_t light_pick(const DLights& lt, const uint32_t v)
 {
-  Minstd rng;
-  rng.seed(path_seed(i, sample_index) ^ kLightSeedXor);
-  if (discard != 0u) rng.discard(discard);
-  const float u0 = rng.uniform();
-  const float u1 = rng.uniform();
-  const float u2 = rng.uniform();
-  // k = min(#{j : cdf_j <= u0}, last): the dense cdf array, 4 bytes a step (count and last are kernel arguments: wave-uniform)
+  const uint32_t n = v - 1u;
   uint32_t lo = 0u, hi = lt.count;
   while (lo < hi) {
     const uint32_t mid = (lo + hi) >> 1;
-    if (lt.cdf[mid] <= u0) lo = mid + 1u;
+    if (lt.thresholds[mid] <= n) lo = mid + 1u;
     else hi = mid;
   }
-  const uint32_t k = lo < lt.last ? lo : lt.last;
+  return lo < lt.last ? lo : lt.last;
+}
+// One light sample for the point p with normal nrm from explicit draws: raw = a Minstd::next (it picks the lamp), u1, u2 uniform (the point on it).
+// terms: the sample's LightTerms (meaningful where the sample is `sampled`)
+PT_HD LightSample light_sample_draws(const DLights& lt, const f3 p, const f3 nrm, const uint32_t raw, const float u1, const float u2,
+                                     LightTerms& terms)
+{
+  const uint32_t k = light_pick(lt, raw);
   const float4* rec = lt.records + 4u * (size_t)k;
   const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
   const f3 p0 = mk3(r0.x, r0.y, r0.z);
@@ -92,6 +92,19 @@ PT_HD LightSample light_sample_point(const DLights& lt, const f3 p, const f3 nrm
   out.sampled = sampled;
   terms = LightTerms{d2, cos_l, inv_pdf, cos_r};
   return out;
+}
+// ... with the draws of the point's light stream.  discard: draws to skip first -- 0 for a query (k_light_sample), 3 * bounce in the
+// render loop, whose bounce b so takes draws 3b .. 3b + 2 of the stream (discard(0) leaves a generator as it is, so it is not executed)
+PT_HD LightSample light_sample_point(const DLights& lt, const f3 p, const f3 nrm, uint32_t i, uint32_t sample_index, uint32_t discard,
+                                     LightTerms& terms)
+{
+  Minstd rng;
+  rng.seed(path_seed(i, sample_index) ^ kLightSeedXor);
+  if (discard != 0u) rng.discard(discard);
+  const uint32_t v = rng.next();
+  const float u1 = rng.uniform();
+  const float u2 = rng.uniform();
+  return light_sample_draws(lt, p, nrm, v, u1, u2, terms);
 }
 // ... for the callers that take the sample alone
 PT_HD LightSample light_sample_point(const DLights& lt, const f3 p, const f3 nrm, uint32_t i, uint32_t sample_index, uint32_t discard)

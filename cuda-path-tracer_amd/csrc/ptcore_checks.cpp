@@ -1,8 +1,9 @@
 // ptcore_checks.cpp -- host-side checks of the rules the kernels share with the host (ptc_check_beam, ptc_check_beam_frustum, ptc_check_feed,
-// ptc_check_traversal_layout, ptc_check_rng), ptc_debug_beam_entries, ptc_debug_sphere_lanes, ptc_selftest_math, ptc_selftest_rng, and
+// ptc_check_traversal_layout, ptc_check_rng, ptc_check_light_sample), ptc_debug_beam_entries, ptc_debug_sphere_lanes, ptc_selftest_math, ptc_selftest_rng, and
 // ptc_generate_rays (the frame's primary rays as ray generation builds them).  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
 #include "pt_rng.hpp"
+#include "pt_light_sample.hpp"
 
 using namespace pt;
 using namespace ptcd;
@@ -620,6 +621,55 @@ int ptc_check_environment_light_pdf(const float* rgb, uint32_t n, const float* d
     pdf_out[i] = table ? env_light::density(reinterpret_cast<const uint4*>(entries.data()), n,
                                             mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]))
                        : 0.0f;
+  return PTC_OK;
+}
+
+// The light sample of section 5f (pt_light_sample.hpp: the header k_light_sample and the megakernel's lit instances run) on the host, against
+// the lamp table of `scene` and the caller's draws: no GPU, no context.  Written out as ptc_direct_light writes a sample whose shadow
+// ray is free; a scene without lamps or of total weight 0: zeros.
+int ptc_check_light_sample(const ptc_scene_desc* scene, const float* points, const float* normals, const uint32_t* v, const float* u,
+                           uint32_t count, uint32_t* lamp, float* shadow_rays, float* contribution, uint8_t* sampled)
+{
+  if (!scene) return fail(nullptr, PTC_ERR_INVALID, "scene is NULL");
+  if (count != 0u && (!points || !normals || !v || !u)) return fail(nullptr, PTC_ERR_INVALID, "points, normals or draws are NULL");
+  for (uint32_t i = 0; i < count; ++i)
+    if (v[i] < 1u || v[i] > 0x7ffffffeu) return fail(nullptr, PTC_ERR_INVALID, "a raw draw is 1 .. 2^31 - 2");
+  std::vector<ptc_light> lights;
+  std::vector<uint32_t> thresholds;
+  ptc_light_info li{};
+  uint32_t last = 0u;
+  if (int rc = checked_light_table(scene, lights, &li, &last, &thresholds)) return rc;
+  static_assert(sizeof(ptc_light) == 4 * sizeof(float4), "a lamp record is four float4");
+  const DLights lt{reinterpret_cast<const float4*>(lights.data()), thresholds.data(), li.lights, last,
+                   reinterpret_cast<const DObject*>(scene->objects), reinterpret_cast<const float4*>(scene->spheres),
+                   reinterpret_cast<const DMaterial*>(scene->materials)};
+  for (uint32_t i = 0; i < count; ++i) {
+    LightSample s{};
+    uint32_t k = 0u;
+    if (!thresholds.empty()) {
+      LightTerms terms;
+      k = light_pick(lt, v[i]);
+      s = light_sample_draws(lt, mk3(points[3u * (size_t)i], points[3u * (size_t)i + 1u], points[3u * (size_t)i + 2u]),
+                             mk3(normals[3u * (size_t)i], normals[3u * (size_t)i + 1u], normals[3u * (size_t)i + 2u]), v[i], u[2u * (size_t)i],
+                             u[2u * (size_t)i + 1u], terms);
+    }
+    if (lamp) lamp[i] = k;
+    if (sampled) sampled[i] = s.sampled ? (uint8_t)1 : (uint8_t)0;
+    if (contribution) {
+      contribution[3u * (size_t)i] = s.contrib.x;
+      contribution[3u * (size_t)i + 1u] = s.contrib.y;
+      contribution[3u * (size_t)i + 2u] = s.contrib.z;
+    }
+    if (shadow_rays) {
+      float* r = shadow_rays + 8u * (size_t)i;
+      std::memcpy(r, points + 3u * (size_t)i, 3u * sizeof(float));
+      r[3] = 1e-4f;
+      r[4] = s.sampled ? s.w.x : 0.0f;
+      r[5] = s.sampled ? s.w.y : 0.0f;
+      r[6] = s.sampled ? s.w.z : 0.0f;
+      r[7] = s.sampled ? s.tmax : 0.0f;
+    }
+  }
   return PTC_OK;
 }
 

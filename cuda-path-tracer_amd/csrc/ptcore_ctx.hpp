@@ -68,7 +68,7 @@ struct ptc_scene_state {
   std::string light_error;               // not empty: an emissive sphere of the scene cannot be sampled (the query's refusal)
   uint32_t light_last = 0;               // last record with a weight > 0
   const float4* light_records = nullptr; // device: 4 float4 per record (ptc_light); null while there is nothing to sample
-  const float* light_cdf = nullptr;      // device: the records' cdf values, dense (the binary search)
+  const uint32_t* light_thresholds = nullptr;  // device: the records' selection thresholds, dense (the binary search)
   const float* light_material_pdf = nullptr;  // device: per material its records' inv_pdf, 0 for no lamp ("mis"); with the table
   // smooth shading (ptc_set_vertex_normals): the scene's vertex count, where each mesh's vertices start (device,
   // uploaded with the scene), and the normals -- a device array of the scene's pool, allocated by the first call that sets any;
@@ -358,8 +358,13 @@ int display_view(ptc_ctx* ctx, int display_type, bool gathered, DisplayView* out
 bool reference_display(const ptc_display_params& d);
 int show_display(ptc_ctx* ctx, const float4* src4, const float* src3, uint32_t n, uint32_t* rgba, float* mapped, DExposure* shown);
 // The lamp table of a validated scene (ptcore_scene.cpp; include/ptcore.h: ptc_light).  *last = last record with a weight > 0.
+// thresholds (may be null): per record what light_pick searches (pt_light_sample.hpp), empty for a table of weight 0.
 // Returns PTC_OK, or PTC_ERR_INVALID with `err` naming the emissive sphere whose matrix is no similarity.
-int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err);
+int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err,
+                      std::vector<uint32_t>* thresholds);
+// ... of a scene as the caller hands it over: validate_scene's and build_light_table's refusals, with their message (ptc_last_error(NULL))
+int checked_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last,
+                        std::vector<uint32_t>* thresholds);
 
 // What a traversal launch over n rays needs besides its rays, outside a frame slot (ptcore_query.cpp).  The queries allocate it per
 // call (alloc_walk_scratch, into the call's pool); a bounce loop would fill it with its slot's buffers instead.

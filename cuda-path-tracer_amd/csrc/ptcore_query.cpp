@@ -536,7 +536,7 @@ int ptc_direct_light(ptc_ctx* ctx, const float* points, const float* normals, ui
   else if (n <= kMaxQuery && on_device && shadow_rays && ((uintptr_t)shadow_rays & 15u)) bad_args = "shadow_rays on the device must be 16-byte aligned";
   int rc;
   if (!query_prologue(ctx, n, "points", bad_args, &rc)) return rc;
-  const DLights lights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres, ctx->scene.materials};
+  const DLights lights{ctx->light_records, ctx->light_thresholds, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres, ctx->scene.materials};
   return light_query(ctx, points, normals, n, radiance, shadow_rays, visible, on_device, !ctx->light_records, ctx->direct, "ptc_direct_light",
                      [&](const float* pts, const float* nrm, uint32_t tmin_word, float4* o4, float4* d4, float4* contrib) {
                        launch_light_sample(ctx->stream, lights, pts, nrm, n, sample_index, tmin_word, o4, d4, contrib);

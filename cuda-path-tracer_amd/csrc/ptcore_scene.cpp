@@ -299,9 +299,17 @@ namespace ptcd {
 // The lamp table (include/ptcore.h: ptc_light) from the caller's arrays -- not from DScene::tris, which is in
 // tree order and may exist only on the device.  Records in binary32 with the operations of the instance triangles
 // (layout_rules::instance_triangle); weights, their running sum and the cdf in binary64, from the records' own fields.
-int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err)
+// thresholds (may be null): what a sample picks its lamp by (light_pick, pt_light_sample.hpp) -- per record T_k, the first of the
+// generator's N = 2^31 - 2 states n = v - 1 that belongs to a later record: round(run_k / W * N) from the same running sums, raised so
+// that every record of weight > 0 owns a state, capped so that the live records behind it still get one each; a record of weight 0
+// repeats its predecessor's (it owns nothing), the last live record and everything behind it get N.  Record k so owns
+// T_k - T_(k-1) states, within 1 + m of its share w_k / W * N (m = the live records whose share is below one state).  Empty for a
+// table of weight 0.
+int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err,
+                      std::vector<uint32_t>* thresholds)
 {
   out.clear();
+  if (thresholds) thresholds->clear();
   ptc_light_info li{};
   std::vector<double> weight;
   std::vector<float> lum_of;
@@ -374,6 +382,7 @@ int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_
   li.lights = (uint32_t)out.size();
   double W = 0.0;
   uint32_t last_live = 0u;
+  uint64_t live = 0u;
   for (size_t k = 0; k < out.size(); ++k) {
     if (!std::isfinite(weight[k])) {
       *err = "lamp primitive " + std::to_string(k) + " (object " + std::to_string(out[k].object) + ") has no finite area";
@@ -381,15 +390,31 @@ int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_
       return PTC_ERR_INVALID;
     }
     W += weight[k];
-    if (weight[k] > 0.0) last_live = (uint32_t)k;
+    if (weight[k] > 0.0) last_live = (uint32_t)k, ++live;
+  }
+  constexpr uint64_t kStates = 0x7ffffffeull;  // N: the values v - 1 of a raw draw
+  if (live > kStates) {
+    *err = "more than 2^31 - 2 lamp primitives of weight > 0: a sample's draw has no state for each";
+    out.clear();
+    return PTC_ERR_INVALID;
   }
   li.total_weight = W;
   if (W > 0.0) {
+    if (thresholds) thresholds->resize(out.size());
     double run = 0.0;
+    uint64_t prev = 0u, behind = live;  // T_(k-1); live records from k on
     for (size_t k = 0; k < out.size(); ++k) {
       run += weight[k];
       out[k].cdf = k >= last_live ? 1.0f : (float)(run / W);
       out[k].inv_pdf = lum_of[k] == 0.0f ? 0.0f : (float)(W / (double)lum_of[k]);
+      if (k >= last_live) {
+        prev = kStates;
+      } else if (weight[k] > 0.0) {
+        --behind;
+        const uint64_t ideal = (uint64_t)std::floor(run / W * (double)kStates + 0.5);
+        prev = std::min(std::max(ideal, prev + 1u), kStates - behind);
+      }
+      if (thresholds) (*thresholds)[k] = (uint32_t)prev;
     }
   }
   if (info) *info = li;
@@ -409,6 +434,15 @@ void light_material_pdf(const ptc_scene_desc* s, double total_weight, std::vecto
     const float lum = std::max(std::max(mat.p[0], mat.p[1]), mat.p[2]);
     out[m] = lum == 0.0f ? 0.0f : (float)(total_weight / (double)lum);
   }
+}
+
+int checked_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last,
+                        std::vector<uint32_t>* thresholds)
+{
+  if (int rc = validate_scene(nullptr, s)) return rc;
+  std::string err;
+  if (int rc = build_light_table(s, out, info, last, &err, thresholds)) return fail(nullptr, rc, err);
+  return PTC_OK;
 }
 
 }  // namespace ptcd
@@ -471,7 +505,7 @@ struct MeshWork {
 // (stage_host), and the clock behind upload_times: lap(field) charges the time since the last lap to that field.
 struct NewScene : ptc_scene_state {
   std::vector<ptc_light> lights;
-  std::vector<float> cdf;          // the records' cdf values; empty: nothing to sample
+  std::vector<uint32_t> thresholds;  // the records' selection thresholds (build_light_table); empty: nothing to sample
   std::vector<float> material_pdf; // per material the records' inv_pdf (light_material_pdf); uploaded with the lamp table
   std::vector<float4> balls;       // DScene::sphere_ball
   std::vector<uint32_t> tri_base;  // DScene::object_tri_base
@@ -554,10 +588,11 @@ int stage_host(ptc_ctx* ctx, const ptc_scene_desc* s, const std::vector<MeshWork
 {
   // the lamp table (direct-light queries).  An emissive sphere that cannot be sampled is no reason to
   // refuse the scene: it renders as ever, only ptc_direct_light refuses
-  if (build_light_table(s, n.lights, &n.light_info, &n.light_last, &n.light_error) != PTC_OK) n.light_info = ptc_light_info{};
-  if (n.light_info.total_weight > 0.0)
-    for (const ptc_light& l : n.lights) n.cdf.push_back(l.cdf);
-  if (!n.cdf.empty()) light_material_pdf(s, n.light_info.total_weight, n.material_pdf);
+  if (build_light_table(s, n.lights, &n.light_info, &n.light_last, &n.light_error, &n.thresholds) != PTC_OK) {
+    n.light_info = ptc_light_info{};
+    n.thresholds.clear();
+  }
+  if (!n.thresholds.empty()) light_material_pdf(s, n.light_info.total_weight, n.material_pdf);
   for (uint32_t i = 0; i < s->material_count; ++i) n.has_emitters |= s->materials[i].type == 3;
   sphere_table(s, n.balls, n.sphere_class);
   // per mesh OBJECT (instance): its mesh and the first of its world-space triangle records, which end with one all-zero
@@ -600,10 +635,10 @@ int upload_tables(ptc_ctx* ctx, const ptc_scene_desc* s, NewScene& n)
 {
   std::vector<void*>& pool = n.scene_allocs;
   DScene& d = n.scene;
-  if (!n.cdf.empty()) {
+  if (!n.thresholds.empty()) {
     static_assert(sizeof(ptc_light) == 4 * sizeof(float4), "a lamp record is four float4");
     if (int rc = upload(ctx, pool, &n.light_records, reinterpret_cast<const float4*>(n.lights.data()), 4u * n.lights.size())) return rc;
-    if (int rc = upload(ctx, pool, &n.light_cdf, n.cdf.data(), n.cdf.size())) return rc;
+    if (int rc = upload(ctx, pool, &n.light_thresholds, n.thresholds.data(), n.thresholds.size())) return rc;
     if (int rc = upload(ctx, pool, &n.light_material_pdf, n.material_pdf.data(), n.material_pdf.size())) return rc;
   }
   const DObject* objects = nullptr;
@@ -840,7 +875,7 @@ int ptc_light_table(const ptc_scene_desc* scene, ptc_light* out, uint32_t capaci
   std::vector<ptc_light> lights;
   ptc_light_info li{};
   std::string err;
-  if (int rc = build_light_table(scene, lights, &li, nullptr, &err)) return fail(nullptr, rc, err);
+  if (int rc = build_light_table(scene, lights, &li, nullptr, &err, nullptr)) return fail(nullptr, rc, err);
   if (lights.size() > capacity)
     return fail(nullptr, PTC_ERR_INVALID, "capacity " + std::to_string(capacity) + " is too small for " + std::to_string(lights.size()) + " lamp primitives");
   if (!lights.empty()) std::memcpy(out, lights.data(), lights.size() * sizeof(ptc_light));
@@ -855,7 +890,7 @@ int ptc_light_material_pdf(const ptc_scene_desc* scene, float* out, uint32_t cap
   std::vector<ptc_light> lights;
   ptc_light_info li{};
   std::string err;
-  if (int rc = build_light_table(scene, lights, &li, nullptr, &err)) return fail(nullptr, rc, err);
+  if (int rc = build_light_table(scene, lights, &li, nullptr, &err, nullptr)) return fail(nullptr, rc, err);
   if (scene->material_count > capacity)
     return fail(nullptr, PTC_ERR_INVALID, "capacity " + std::to_string(capacity) + " is too small for " + std::to_string(scene->material_count) + " materials");
   std::vector<float> pdf;

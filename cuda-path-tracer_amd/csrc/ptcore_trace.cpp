@@ -671,7 +671,7 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
       }
     }
     if (direct)
-      lights = DLights{ctx->light_records, ctx->light_cdf, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
+      lights = DLights{ctx->light_records, ctx->light_thresholds, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
                        ctx->scene.materials};
     if (smooth) {  // its two instances, with the balance heuristic and without; every light and the environment by run-time choice
       launch_megakernel_smooth(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,

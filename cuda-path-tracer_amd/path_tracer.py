@@ -78,6 +78,29 @@ def light_material_pdf(scene, capacity=None):
     return out[:rc].copy()
 
 
+def check_light_sample(scene, points, normals, v, u):
+    """One light sample per point from explicit draws (ptc_check_light_sample; host-side, no GPU needed): the header the device runs,
+    against the lamp table of `scene` (a SceneDescription or a FlatScene).  points, normals [n, 3]; v uint32 [n], the raw first draw
+    (1 .. 2^31 - 2: it picks the lamp); u [n, 2]: u1, u2.  -> dict(lamp uint32 [n], rays [n, 8], contribution [n, 3], sampled bool [n])"""
+    flat = scene.build_scene() if isinstance(scene, SceneDescription) else scene
+    desc = flat.to_c()
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    v = np.ascontiguousarray(v, dtype=np.uint32).reshape(-1)
+    u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+    n = len(p)
+    if not (len(nrm) == n and len(v) == n and len(u) == n):
+        raise ValueError("points, normals, v and u must have one row per point")
+    lamp = np.zeros(n, dtype=np.uint32)
+    rays = np.zeros((n, 8), dtype=np.float32)
+    contribution = np.zeros((n, 3), dtype=np.float32)
+    sampled = np.zeros(n, dtype=np.uint8)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    _capi.check(_capi.lib().ptc_check_light_sample(C.byref(desc), ptr(p), ptr(nrm), ptr(v), ptr(u), n, ptr(lamp), ptr(rays), ptr(contribution),
+                                                   ptr(sampled)))
+    return {"lamp": lamp, "rays": rays, "contribution": contribution, "sampled": sampled.astype(bool)}
+
+
 def compute_vertex_normals(positions, indices=None, mesh_ranges=None):
     """Area-weighted vertex normals (ptc_compute_vertex_normals; host-side, no GPU needed).  positions [v, 3] and
     indices [t * 3] of one mesh, or -- with mesh_ranges, a mesh table's rows (first_vertex, vertex_count, first_index, index_count, ...)

@@ -606,14 +606,21 @@ typedef struct ptc_light {           /* one lamp primitive, 64 bytes, world spac
                                         DScene::tris;  sphere: p0 = transform_point(M, centre), e1[0] = world radius = length of M's
                                         column 0 (binary32, glm order) * radius, the rest 0 */
   float cdf;                         /* (float)(sum of the weights up to and including this record / W); the last record with a
-                                        weight > 0 and every record behind it: exactly 1.0f */
+                                        weight > 0 and every record behind it: exactly 1.0f.  Informational: no sample reads it */
   float inv_pdf;                     /* 1 / (area density of a sample on this primitive) = (float)(W / lum), 0 when lum == 0 */
   uint32_t object;                   /* index into ptc_scene_desc::objects */
   uint32_t kind_material;            /* material index | kind << 31  (kind 0 triangle, 1 sphere) */
 } ptc_light;
 /* weight of a record = area * lum in binary64 from the record's own binary32 fields: area = 0.5 |e1 x e2| or 4 pi R^2,
- * lum = max(r, g, b) of the material's emission; W = the weights summed in table order.  A sample picks record
- * k = min(#{j : cdf_j <= u0}, last record with a weight > 0) for u0 in [0, 1]: a record of weight 0 is never picked. */
+ * lum = max(r, g, b) of the material's emission; W = the weights summed in table order.  A sample picks its record from the RAW
+ * first draw v of its stream (1 .. 2^31 - 2), in integers: with n = v - 1 in [0, N), N = 2^31 - 2,
+ *   k = min(#{j : T_j <= n}, last record with a weight > 0),
+ * T_k = round(run_k / W * N) in binary64 from the same running sums, then raised to at least T_(k-1) + 1 for a record of weight > 0 and
+ * capped so that the records of weight > 0 behind it keep a state each; a record of weight 0 has T_k = T_(k-1), the last record with
+ * a weight > 0 and every record behind it N.  Record k so owns T_k - T_(k-1) of the N states: none for a weight of 0, at least one for
+ * any weight > 0, and within 1 + m of its share w_k / W * N (m = the records of weight > 0 whose share is below one state).  More than N
+ * records of weight > 0: PTC_ERR_INVALID.  (The binary32 cdf is no part of this: near 1 it has a step of 2^-24, under which a small
+ * lamp beside a large one was never picked, or many times too often.) */
 typedef struct ptc_light_info {
   uint32_t lights, sphere_lights, triangle_lights, emissive_objects;
   double total_area, total_weight;
@@ -632,7 +639,7 @@ int ptc_get_light_info(ptc_ctx* ctx, ptc_light_info* out);    /* of the uploaded
  * with w = (q - p) / d, cos_r = dot(n, w) (<= 0: no sample), cos_l = |dot(n_l, w)| (lamps are two-sided, as in the path
  * tracer; a sphere lamp's far side is hidden by the lamp itself -- the shadow ray decides, not a special case).
  * Shadow ray: origin p, t_min 1e-4f, direction w, t_max = d * 0.999f (the any-hit walk's fast domain).
- * Draws: Minstd seeded from path_seed(i, sample_index) xor 0x4c495445 (no render path xors its seed); u0 picks the lamp, u1, u2
+ * Draws: Minstd seeded from path_seed(i, sample_index) xor 0x4c495445 (no render path xors its seed); the raw first draw picks the lamp, u1, u2
  * the point (triangle: b1 = 1 - sqrt(u1), b2 = u2 * sqrt(u1), q = p0 + b1 e1 + b2 e2; sphere: z = 1 - 2 u1,
  * r = sqrt(max(0, 1 - z^2)), phi = 2 pi u2 through det_sincos, q = transform_point(M, c + R * dir), n_l = normalize(q - world
  * centre)).  The binary32 operation order: DESIGN section 5f.
@@ -870,6 +877,14 @@ int ptc_check_environment_light(const float* rgb, uint32_t n, const float* point
 /* ... and the sample's density in `count` caller-given unit directions, as ptc_environment_light_pdf returns it (zeros for a map of
  * weight 0).  PTC_ERR_INVALID: a NULL, n out of range, a bad component. */
 int ptc_check_environment_light_pdf(const float* rgb, uint32_t n, const float* dirs, uint32_t count, float* pdf_out);
+/* The light sample of ptc_direct_light (csrc/pt_light_sample.hpp, the header k_light_sample and the megakernel's lit instances run on the
+ * device) on the host, against the lamp table of `scene` (ptc_light_table's refusals): no GPU, no context; test hook.  Per point i the
+ * point and its unit normal (3 floats each) and the three draws given explicitly: v[i] raw (1 .. 2^31 - 2; it picks the lamp), u + 2 i:
+ * u1, u2.  Out, each may be NULL: lamp (the record picked), shadow_rays (8 floats, as ptc_direct_light returns them), contribution (3
+ * floats, unshadowed), sampled (one byte).  A scene without lamps or of total weight 0: zeros.  PTC_ERR_INVALID: a NULL input, a v out of
+ * range. */
+int ptc_check_light_sample(const ptc_scene_desc* scene, const float* points, const float* normals, const uint32_t* v, const float* u,
+                           uint32_t count, uint32_t* lamp, float* shadow_rays, float* contribution, uint8_t* sampled);
 
 #ifdef __cplusplus
 }

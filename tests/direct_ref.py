@@ -2,10 +2,11 @@
 manner of lit_ref.py.  Three things, none of them the thing under test:
 
   (a) light_table: the lamp table in numpy -- the records in binary32 with the operations of the library's instance triangles
-      (transform_point, edge differences, normalize(cross)), weights / running sum / cdf in binary64 from the records' fields;
+      (transform_point, edge differences, normalize(cross)), weights / running sum / cdf in binary64 from the records' fields; and
+      thresholds / select: the integer thresholds a sample picks its lamp by, from the raw first draw;
   (b) light_sample / sample / query: one light sample per point in numpy binary32, one numpy operation per source operation of
       light_sample_point in the order DESIGN section 5f writes down (numpy does not contract into FMA); its pinned pieces are the
-      oracle's orc_path_seed, orc_rng_seed / orc_rng_uniform (the draws: ref_f32.stream_draws), orc_sincos and intersect_rays (the
+      oracle's orc_path_seed, orc_rng_seed / orc_rng_uniform (the draws: light_draws), orc_sincos and intersect_rays (the
       shadow rays).  light_sample takes its draws from the caller: the query (sample) and the render loop (lit_ref.render_megakernel,
       section 5g) key their light streams differently and share everything else;
   (c) estimate_f64 and the truths: a float64 Monte-Carlo estimator written from the formula
@@ -16,7 +17,7 @@ manner of lit_ref.py.  Three things, none of them the thing under test:
 Also the scenes and seeded points the CPU and GPU tests share."""
 import numpy as np
 
-from ref_f32 import PI, PI2, F, _cross, _dot, _normalize, _sincos, _xform_point, stream_draws
+from ref_f32 import PI, PI2, Draws, F, _cross, _dot, _normalize, _sincos, _xform_point, stream_states
 
 SEED_XOR = 0x4C495445                            # kLightSeedXor (pt_device.hpp)
 T_MIN = F(1e-4)
@@ -95,25 +96,62 @@ def light_table(flat):
     return recs, info, weights, last
 
 
-def select(cdf, last, u0):
-    """k = min(#{j : cdf_j <= u0}, last)."""
-    return np.minimum(np.searchsorted(np.asarray(cdf, dtype=np.float32), np.asarray(u0, dtype=np.float32), side="right"), last)
+STATES = 2 ** 31 - 2                             # N: the values n = v - 1 of a raw draw v (minstd_rand: 1 .. 2^31 - 2)
+M31 = 2 ** 31 - 1
+
+
+def thresholds(weights):
+    """T_k of include/ptcore.h, in closed form where build_light_table runs a loop: the live records' ideal thresholds
+    R_j = floor(run / W * N + 0.5) (j = 0 .. L - 1 in table order; run, W: the sequential binary64 sums), raised
+    T_j = j + max_{i <= j}(R_i - i) (each at least its predecessor + 1), capped at N - (L - 1 - j) (the live records behind keep a
+    state each), the last live one N; a record of weight 0 repeats its predecessor (0 in front of the first live one), everything
+    behind the last live one gets N.  -> uint32[len(weights)]; zeros for a table of weight 0."""
+    w = np.asarray(weights, dtype=np.float64)
+    out = np.zeros(len(w), dtype=np.uint32)
+    live = np.nonzero(w > 0.0)[0]
+    if len(live) == 0:
+        return out
+    run = np.cumsum(w)                 # add.accumulate: sequential, as the library's loop
+    j = np.arange(len(live), dtype=np.int64)
+    ideal = np.floor(run[live] / run[-1] * float(STATES) + 0.5).astype(np.int64)
+    t = np.minimum(j + np.maximum.accumulate(ideal - j), STATES - (len(live) - 1 - j))
+    t[-1] = STATES
+    owner = np.searchsorted(live, np.arange(len(w)), side="right") - 1   # the live record at or in front of k; -1: none yet
+    out[owner >= 0] = t[owner[owner >= 0]]
+    return out
+
+
+def select(weights, last, v):
+    """k = min(#{j : T_j <= v - 1}, last) for raw draws v."""
+    n = np.asarray(v, dtype=np.int64) - 1
+    return np.minimum(np.searchsorted(thresholds(weights), n, side="right"), last)
+
+
+def light_draws(orc, indices, iteration, discard):
+    """The three draws of a sample: per index a generator seeded path_seed(index, iteration) ^ SEED_XOR, discard(discard); the raw value
+    v = next(), then u1, u2 = uniform() -> (v uint32[n], u float32[n, 2]).  (The query: discard 0; the render loop: 3 * bounce.)"""
+    states = stream_states(orc, indices, iteration, SEED_XOR, discard)
+    v = ((states.astype(np.uint64) * np.uint64(48271)) % np.uint64(M31)).astype(np.uint32)   # minstd_rand's step
+    draws = Draws(orc, v)
+    every = np.arange(len(v))
+    return v, np.stack([draws.uniform(every) for _ in range(2)], axis=-1).reshape(-1, 2)
 
 
 # ---- (b) the sample, binary32 ---------------------------------------------------------------------------------------------
-def light_sample(orc, flat, table, p, nrm, u):
-    """light_sample_point for points p [n, 3] with normals nrm and draws u [n, 3] (item 1: whose they
-    are is the caller's business): -> dict(rays [n, 8] as ptc_direct_light returns them, contribution [n, 3] (unshadowed), sampled
+def light_sample(orc, flat, table, p, nrm, draws):
+    """light_sample_draws for points p [n, 3] with normals nrm and draws = (v uint32[n] raw, u [n, 2]: u1,
+    u2), as light_draws returns them (item 1: whose they are is the caller's business): -> dict(rays [n, 8] as ptc_direct_light returns them, contribution [n, 3] (unshadowed), sampled
     bool[n], lamp int[n]).  table = light_table(flat), total weight > 0."""
-    recs, _, _, last = table
+    recs, _, weights, last = table
     n = len(p)
     rays = np.zeros((n, 8), dtype=np.float32)
     rays[:, 0:3], rays[:, 3] = p, T_MIN
     contribution = np.zeros((n, 3), dtype=np.float32)
     if n == 0:
         return {"rays": rays, "contribution": contribution, "sampled": np.zeros(0, dtype=bool), "lamp": np.zeros(0, dtype=np.int64)}
-    u0, u1, u2 = u[:, 0], u[:, 1], u[:, 2]
-    k = select(recs["cdf"], last, u0)
+    raw, u = draws
+    u1, u2 = u[:, 0], u[:, 1]
+    k = select(weights, last, raw)
     r = recs[k]
     p0 = r["p0"]
     q = np.zeros((n, 3), dtype=np.float32)
@@ -173,7 +211,7 @@ def sample(orc, flat, points, normals, sample_index, table=None):
         rays[:, 0:3], rays[:, 3] = p, T_MIN
         return {"rays": rays, "contribution": np.zeros((n, 3), dtype=np.float32), "sampled": np.zeros(n, dtype=bool),
                 "lamp": np.zeros(n, dtype=np.int64)}
-    return light_sample(orc, flat, table, p, nrm, stream_draws(orc, range(n), sample_index, SEED_XOR, 0, 3))
+    return light_sample(orc, flat, table, p, nrm, light_draws(orc, range(n), sample_index, 0))
 
 
 def query(orc, flat, points, normals, sample_index, table=None, scene_handle=None):

@@ -181,7 +181,7 @@ def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounc
                 if lit:
                     count_emission[sc] = typ != 0
                     diffuse_hits += len(df)
-                    smp = direct_ref.light_sample(orc, flat, lamps, pts, nrm, lit_ref.stream_draws(orc, df, iteration, direct_ref.SEED_XOR, 3 * b, 3))
+                    smp = direct_ref.light_sample(orc, flat, lamps, pts, nrm, direct_ref.light_draws(orc, df, iteration, 3 * b))
                     got, traced = _arrived(orc, flat, sh, smp["sampled"], smp["rays"])
                     shadow_rays += traced
                     unoccluded += int(got.sum())

@@ -345,7 +345,7 @@ def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounc
                 diffuse_hits += len(df)
                 pts = recs["point"][df].astype(np.float32)
                 nrm = recs["normal"][df].astype(np.float32)
-                u = stream_draws(orc, df, iteration, direct_ref.SEED_XOR, 3 * b, 3)
+                u = direct_ref.light_draws(orc, df, iteration, 3 * b)
                 smp = direct_ref.light_sample(orc, flat, lamps, pts, nrm, u)
                 sel = np.nonzero(smp["sampled"])[0]
                 shadow_rays += len(sel)

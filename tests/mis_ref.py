@@ -125,14 +125,15 @@ def material_pdf(flat, table=None):
     return out
 
 
-def light_terms(orc, flat, table, p, nrm, u):
+def light_terms(orc, flat, table, p, nrm, draws):
     """(d2, cos_l, inv_pdf, cos_r) of direct_ref.light_sample's sample for the same points and draws, by direct_ref's own lines"""
-    recs, _, _, last = table
+    recs, _, weights, last = table
     n = len(p)
     if n == 0:
         return (np.zeros(0, dtype=np.float32),) * 4
-    u0, u1, u2 = u[:, 0], u[:, 1], u[:, 2]
-    r = recs[direct_ref.select(recs["cdf"], last, u0)]
+    raw, u = draws
+    u1, u2 = u[:, 0], u[:, 1]
+    r = recs[direct_ref.select(weights, last, raw)]
     p0 = r["p0"]
     q = np.zeros((n, 3), dtype=np.float32)
     nl = np.zeros((n, 3), dtype=np.float32)
@@ -242,7 +243,7 @@ def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounc
                 if lit:
                     count_emission[sc] = typ != 0
                     diffuse_hits += len(df)
-                    u = lit_ref.stream_draws(orc, df, iteration, direct_ref.SEED_XOR, 3 * b, 3)
+                    u = direct_ref.light_draws(orc, df, iteration, 3 * b)
                     smp = direct_ref.light_sample(orc, flat, lamps, pts, nrm, u)
                     contribution = smp["contribution"]
                     if weigh and len(df):

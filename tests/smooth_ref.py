@@ -337,7 +337,7 @@ def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounc
                 if lit:
                     count_emission[sc] = typ != 0
                     diffuse_hits += len(df)
-                    u = lit_ref.stream_draws(orc, df, iteration, direct_ref.SEED_XOR, 3 * b, 3)
+                    u = direct_ref.light_draws(orc, df, iteration, 3 * b)
                     smp = direct_ref.light_sample(orc, flat, lamps, pts, nrm, u)
                     contribution = smp["contribution"]
                     if weigh and len(df):

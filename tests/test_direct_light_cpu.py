@@ -70,12 +70,17 @@ def test_table_against_the_restatement_and_float64(pkg, name):
                 assert rec_area <= 1e-6   # a triangle of area 0
             k += 1
     assert k == len(got)
-    # selection: an entry of weight 0 is never picked
-    u0 = np.concatenate([[0.0, 1.0], cdf, np.nextafter(cdf, np.float32(0)), np.nextafter(cdf, np.float32(2))]).astype(np.float32)
-    u0 = u0[(u0 >= 0) & (u0 <= 1)]
-    picked = D.select(cdf, last, u0)
-    assert np.all(weights[picked] > 0.0), (name, u0[weights[picked] <= 0.0])
-    assert set(picked) == set(np.nonzero(np.diff(np.concatenate([[0.0], cdf.astype(np.float64)])) > 0)[0]) | {last}
+    # selection, from the raw first draw in integers: every record of weight > 0 is picked, none of weight 0 -- by the restatement
+    # and by the library's own header (ptc_check_light_sample), at both ends of the generator's range and around every threshold
+    t = D.thresholds(weights).astype(np.int64)
+    v = np.concatenate([[1, D.STATES], t, t + 1, t + 2])
+    v = np.unique(v[(v >= 1) & (v <= D.STATES)]).astype(np.uint32)
+    picked = D.select(weights, last, v)
+    assert np.all(weights[picked] > 0.0), (name, v[weights[picked] <= 0.0])
+    assert set(picked) == set(np.nonzero(weights > 0.0)[0])
+    lib = pkg.check_light_sample(flat, np.zeros((len(v), 3)), np.tile(np.float32([0, 1, 0]), (len(v), 1)), v, np.full((len(v), 2), 0.5))
+    assert np.array_equal(lib["lamp"], picked)
+    assert picked[0] == np.nonzero(weights > 0.0)[0][0] and picked[-1] == last
 
 
 def test_a_scene_without_lamps_has_an_empty_table(pkg):
