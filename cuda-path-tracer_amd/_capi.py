@@ -133,6 +133,15 @@ class ptc_smooth_loop_stats(C.Structure):
     _fields_ = [("shading_normals", C.c_uint64), ("fallbacks", C.c_uint64), ("absorbed", C.c_uint64), ("culled_light_samples", C.c_uint64)]
 
 
+class ptc_texture_loop_stats(C.Structure):
+    _fields_ = [("lookups", C.c_uint64), ("fallbacks", C.c_uint64)]
+
+
+class ptc_texture_desc(C.Structure):
+    _fields_ = [("rgba8", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("encoding", C.c_uint32), ("filter", C.c_uint32),
+                ("wrap", C.c_uint32)]
+
+
 ptc_environment_light_stats = ptc_direct_stats  # the same five fields (include/ptcore.h)
 
 
@@ -250,6 +259,15 @@ SIGNATURES = {
     "ptc_compute_vertex_normals": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptc_hit_attributes": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptc_get_smooth_loop_stats": (C.c_int, [_P, C.POINTER(ptc_smooth_loop_stats)]),
+    "ptc_set_textures": (C.c_int, [_P, C.POINTER(ptc_texture_desc), C.c_uint32, C.c_void_p, C.c_uint32]),
+    "ptc_get_textures": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "ptc_set_texcoords": (C.c_int, [_P, C.c_void_p, C.c_uint32]),
+    "ptc_get_texcoords": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "ptc_texture_decode_table": (C.c_int, [C.c_uint32, C.c_void_p]),
+    "ptc_sample_texture": (C.c_int, [_P, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ptc_hit_surface": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ptc_get_texture_loop_stats": (C.c_int, [_P, C.POINTER(ptc_texture_loop_stats)]),
+    "ptc_check_texture_lookup": (C.c_int, [C.POINTER(ptc_texture_desc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "ptc_check_shading_normal": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p, C.c_void_p]),
     "ptc_check_environment_light_pdf": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptc_check_environment_light": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,

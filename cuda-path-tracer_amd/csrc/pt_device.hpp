@@ -10,6 +10,7 @@
 #include "../../include/ptcore.h"
 #include "pt_math.hpp"
 #include "pt_env.hpp"
+#include "pt_texture.hpp"
 
 namespace pt {
 
@@ -621,6 +622,31 @@ void launch_megakernel_smooth(hipStream_t s, const DScene& scene, const DLights&
 // sphere), u, v, and the shading normal (sm.normals null: the geometric one); flags |= kFlagStackOverflow
 void launch_hit_attributes(hipStream_t s, const DScene& scene, DSmooth sm, const float4* rays, uint32_t n, uint32_t* object_out,
                            uint32_t* triangle_out, float2* uv_out, float* normal_out, uint32_t* flags);
+// Image textures in the megakernel (ptc_set_textures, ptc_set_texcoords, ptc_set_param "textures"; pt_texture.hpp).
+// texels: every texture's texels back to back, one allocation of the scene's pool; records: one per texture; material_texture: per
+// material -1 or a texture; table: the two decode tables; st: two floats per triangle corner of the whole scene, parallel to its
+// indices; mesh_first_index: per mesh where its corners start in it.  Kept out of DScene, as DSmooth is.  A null member: not set.
+struct DTex {
+  const uint32_t* texels;
+  const texmap::Record* records;
+  const int32_t* material_texture;
+  const float* table;
+  const float* st;
+  const uint32_t* mesh_first_index;
+};
+// the megakernel's textured instances (a "textures" 1 frame of a scene with textures and texture coordinates; pt_mega_tex.hip):
+// mega_path with kTex -- launch_megakernel_smooth's arguments and run-time choices, the balance heuristic by `weigh`, the shading
+// normal by sm.normals (null: the geometric one; an instance each).  stats words 12, 13 of a line += texture lookups, fall-backs
+void launch_megakernel_tex(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
+                           uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
+                           DLens lens, DEnv env, DEnvLight el, DMis mis, bool weigh, DSmooth sm, DTex tx);
+// ptc_sample_texture's kernel (pt_mega_tex.hip): one thread per coordinate pair, texmap::lookup on one record of the pool; rgb 3
+// floats a pair (zeros where the rule refuses the pair), rejected (may be null) one byte a pair
+void launch_texture_sample(hipStream_t s, DTex tx, uint32_t texture, const float* st, uint32_t n, float* rgb, uint8_t* rejected);
+// ptc_hit_surface's kernel (pt_mega_tex.hip): k_hit_attributes' walk; per ray the interpolated s, t (tx.st null, a sphere, a miss:
+// zeros) and the albedo the loop would use at the hit (a miss: zeros); flags |= kFlagStackOverflow
+void launch_hit_surface(hipStream_t s, const DScene& scene, DTex tx, const float4* rays, uint32_t n, float2* st_out, float* albedo_out,
+                        uint32_t* flags);
 // ptc_environment_light_pdf's kernel (pt_env.hip): one thread per unit direction, env_light::density
 void launch_env_light_pdf(hipStream_t s, DEnvLight el, uint32_t n, const float* dirs, uint32_t count, float* pdf);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,

@@ -2,8 +2,8 @@
 // namespace pt, after pt_kernels_common.inc and with pt_light_sample.hpp in front) by pt_kernels.hip, which instantiates the plain
 // instances beside the closest-hit kernels as ever, and by pt_mega_direct.hip, which instantiates the kRoulette ones and
 // k_megakernel_direct, and by pt_mega_mis.hip, which instantiates k_megakernel_mis (kMis, DESIGN section 5l), and by pt_mega_smooth.hip,
-// which instantiates k_megakernel_smooth (kSmooth, section 5n): the code object that holds the traversal kernels stays the one it was
-// (DESIGN section 5h).
+// which instantiates k_megakernel_smooth (kSmooth, section 5n), and by pt_mega_tex.hip, which instantiates k_megakernel_tex (kTex,
+// section 5o): the code object that holds the traversal kernels stays the one it was (DESIGN section 5h).
 // path_tracing_mega_kernel, path_tracer.cu:227-269: the whole path in one thread, one RNG stream per
 // pixel (a different image from streaming mode at the same seed -- a property of the reference).
 // kEmit: the scene has an emissive material (the host's choice; without one the instance is the reference's loop as it was).
@@ -51,15 +51,23 @@
 // hit whose new direction does (dot(ray.d, rec.n) <= 0) ends the path with colour 0 behind its light samples.  Every light is a
 // run-time choice as under kMis, with or without it, and a frame that samples none deposits colour alone.  stats words 8 .. 11 +=
 // shading normals formed, fall-backs, absorbed continuations, culled light samples.
+// kTex (with kEnvLight; ptc_set_param "textures" in a scene with textures and texture coordinates, DESIGN section 5o; k_megakernel_tex,
+// pt_mega_tex.hip): at a triangle hit on a diffuse or metal material with a texture bound, after the emitter check and roulette and
+// immediately before evaluate_material, the material is copied and texmap::albedo's (pt_texture.hpp) colour -- the texel at the
+// winner's interpolated corner coordinates times p[0..2] -- replaces p[0..2] in the copy; everything downstream takes it from there.
+// Every light is a run-time choice as under kSmooth, with kSmooth or without.  stats words 12, 13 += lookups, fall-backs.
 template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false, bool kEnv = false, bool kEnvLight = false, bool kMis = false,
-          bool kSmooth = false>
+          bool kSmooth = false, bool kTex = false>
 __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, const DCamera& cam, const uint32_t iteration, const DBand band,
                                           const uint32_t pix_count, const int max_bounces, const DFrame fb, DeviceCounters* counters,
                                           unsigned long long* stats, const int roulette, uint32_t* stack,
                                           const DLens lens = DLens{0.0f, 0.0f}, const DEnv env = DEnv{nullptr, 0u, 0u},
                                           const DEnvLight el = DEnvLight{nullptr}, const DMis mis = DMis{nullptr},
-                                          const DSmooth sm = DSmooth{nullptr, nullptr})
+                                          const DSmooth sm = DSmooth{nullptr, nullptr},
+                                          const DTex tx = DTex{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr})
 {
+  constexpr bool kDyn = kSmooth || kTex;  // every light and the environment are run-time choices
+  static_assert(!kTex || kEnvLight, "the textured instances sample lamps and environment by run-time choice");
   static_assert(!kSmooth || kEnvLight, "the smooth instances sample lamps and environment by run-time choice");
   static_assert(!kEnvLight || (kEnv && kDirect), "the environment-light instance has an environment and a radiance sum");
   static_assert(!kMis || kEnvLight, "the multiple-importance instance samples lamps and environment by run-time choice");
@@ -70,8 +78,9 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
   uint32_t e_diffuse = 0u, e_shadow = 0u, e_clear = 0u;
   [[maybe_unused]] uint32_t m_emit = 0u, m_miss = 0u;
   [[maybe_unused]] uint32_t s_formed = 0u, s_fallback = 0u, s_absorbed = 0u, s_culled = 0u;
+  [[maybe_unused]] uint32_t t_lookup = 0u, t_fallback = 0u;
   const bool lamps = !kEnvLight || lt.records != nullptr;
-  const bool env_lamp = !(kMis || kSmooth) || el.table != nullptr;  // (kEnvLight) the environment is sampled
+  const bool env_lamp = !(kMis || kDyn) || el.table != nullptr;  // (kEnvLight) the environment is sampled
   if (s < pix_count) {
     const uint32_t pixel = band_pixel(band, s);
     Minstd rng;
@@ -98,7 +107,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       ++rays;
       Tally tally;
       [[maybe_unused]] HitAttr at;
-      if (!ray_scene<false, kSmooth>(ray, sc, rec, stack, flags, tally, kSmooth ? &at : nullptr)) {
+      if (!ray_scene<false, kDyn>(ray, sc, rec, stack, flags, tally, kDyn ? &at : nullptr)) {
         if constexpr (kMis) {
           if (!count_env) {  // behind an environment sample: the lobe's share of the sky it reached (the entry's load first)
             ++m_miss;
@@ -110,7 +119,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
           }
           break;
         }
-        if constexpr (kSmooth) {  // the environment itself by env.texels
+        if constexpr (kDyn) {  // the environment itself by env.texels
           if (!count_env) color = mk3(0.0f, 0.0f, 0.0f);
           else color = env.texels ? color * sky<true>(ray.d, env) : color * sky<false>(ray.d, env);
           break;
@@ -162,7 +171,25 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
         color = mk3(0.0f, 0.0f, 0.0f);  // the path ends by chance: the sample is (radiance +) 0, no draw, no light sample
         break;
       }
-      evaluate_material(ray.o, ray.d, tmin_flag, rec.p, hn, rec.side, mat, rng, color);
+      if constexpr (kTex) {
+        DMaterial tmat = mat;
+        if (at.first != kNoChild && mat.type <= 1) {
+          const int32_t ti = tx.material_texture[rec.mat];
+          if (ti >= 0) {
+            const uint32_t mesh = sc.object_mesh[at.object];
+            const float* st = tx.st + 2u * ((size_t)tx.mesh_first_index[mesh] + at.first);
+            f3 alb;
+            if (texmap::albedo(tx.texels, tx.records[ti], tx.table, st, st + 2, st + 4, at.u, at.v, mk3(mat.p[0], mat.p[1], mat.p[2]), alb)) ++t_lookup;
+            else ++t_fallback;
+            tmat.p[0] = alb.x;
+            tmat.p[1] = alb.y;
+            tmat.p[2] = alb.z;
+          }
+        }
+        evaluate_material(ray.o, ray.d, tmin_flag, rec.p, hn, rec.side, tmat, rng, color);
+      } else {
+        evaluate_material(ray.o, ray.d, tmin_flag, rec.p, hn, rec.side, mat, rng, color);
+      }
       ray.tmin = tmin_flag ? 1e-5f : 1e-4f;
       if constexpr (kDirect) {
         if (lamps) count_emission = mat.type != 0;
@@ -182,7 +209,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
               if (weigh) es.contrib = es.contrib * mis::balance(env_light::env_density(et.jac), mis::lobe_density(et.cos_r));
             }
           } else if constexpr (kEnvLight) {
-            if constexpr (kSmooth) es.sampled = false;
+            if constexpr (kDyn) es.sampled = false;
             if (env_lamp) {
               ++e_diffuse;
               es = env_light::sample_point(el.table, env.texels, env.n, hn, pixel, iteration, 4u * (uint32_t)i);
@@ -248,7 +275,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
         }
       }
     }
-    if constexpr (kSmooth) accumulate_color(fb.color4, s, iteration, lamps || env_lamp ? radiance + color : color);
+    if constexpr (kDyn) accumulate_color(fb.color4, s, iteration, lamps || env_lamp ? radiance + color : color);
     else accumulate_color(fb.color4, s, iteration, kDirect ? radiance + color : color);
     accumulate_nd(fb.nd4, s, iteration, normal, depth);
     if (flags) atomicOr(&counters->flags, flags);
@@ -257,6 +284,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
   uint32_t sum = rays, sd = n_diffuse, ss = n_shadow, sv = n_clear, ed = e_diffuse, es = e_shadow, ev = e_clear;
   [[maybe_unused]] uint32_t me = m_emit, mm = m_miss;
   [[maybe_unused]] uint32_t qf = s_formed, qb = s_fallback, qa = s_absorbed, qc = s_culled;
+  [[maybe_unused]] uint32_t tl = t_lookup, tf = t_fallback;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     sum += __shfl_down(sum, off, 64);
@@ -280,6 +308,10 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       qa += __shfl_down(qa, off, 64);
       qc += __shfl_down(qc, off, 64);
     }
+    if constexpr (kTex) {
+      tl += __shfl_down(tl, off, 64);
+      tf += __shfl_down(tf, off, 64);
+    }
   }
   if (threadIdx.x == 0u) {
     if (sum) atomicAdd(&counters->rays_total, (unsigned long long)sum);
@@ -302,6 +334,10 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
         if (qb) atomicAdd(&line[9], (unsigned long long)qb);
         if (qa) atomicAdd(&line[10], (unsigned long long)qa);
         if (qc) atomicAdd(&line[11], (unsigned long long)qc);
+      }
+      if constexpr (kTex) {
+        if (tl) atomicAdd(&line[12], (unsigned long long)tl);
+        if (tf) atomicAdd(&line[13], (unsigned long long)tf);
       }
     }
   }

@@ -567,6 +567,33 @@ int ptc_check_shading_normal(const float* n0, const float* n1, const float* n2, 
   return PTC_OK;
 }
 
+// The texture lookup (pt_texture.hpp) on the host: the header the textured kernels run on the device, on the
+// caller's own texels (a byte quadruple is the word the pool holds, r in the low byte)
+int ptc_check_texture_lookup(const ptc_texture_desc* desc, const float* st, uint32_t n, float* rgb_out, uint8_t* rejected_out)
+{
+  if (!desc || (n != 0u && (!st || !rgb_out))) return fail(nullptr, PTC_ERR_INVALID, "texture lookup: an array is NULL");
+  const std::string why = texture_refusal(*desc);
+  if (!why.empty()) return fail(nullptr, PTC_ERR_INVALID, "the texture " + why);
+  const size_t count = (size_t)desc->width * desc->height;
+  std::vector<uint32_t> words(count);
+  for (size_t i = 0; i < count; ++i)
+    words[i] = (uint32_t)desc->rgba8[4u * i] | ((uint32_t)desc->rgba8[4u * i + 1u] << 8) | ((uint32_t)desc->rgba8[4u * i + 2u] << 16) |
+               ((uint32_t)desc->rgba8[4u * i + 3u] << 24);
+  float table[2u * texmap::kTableEntries];
+  texmap::decode_table(texmap::kLinear, table);
+  texmap::decode_table(texmap::kSrgb, table + texmap::kTableEntries);
+  const texmap::Record rec{0u, desc->width, desc->height, texmap::pack_flags(desc->encoding, desc->filter, desc->wrap)};
+  for (uint32_t i = 0; i < n; ++i) {
+    f3 c;
+    const bool ok = texmap::lookup(words.data(), rec, table, st[2u * (size_t)i], st[2u * (size_t)i + 1u], c);
+    rgb_out[3u * (size_t)i] = c.x;
+    rgb_out[3u * (size_t)i + 1u] = c.y;
+    rgb_out[3u * (size_t)i + 2u] = c.z;
+    if (rejected_out) rejected_out[i] = ok ? (uint8_t)0 : (uint8_t)1;
+  }
+  return PTC_OK;
+}
+
 // ... and the sample (env_light::sample_draws) on the caller's points, normals and draws, written out as ptc_environment_light writes
 // a sample whose shadow ray is free
 int ptc_check_environment_light(const float* rgb, uint32_t n, const float* points, const float* normals, const uint32_t* v, const float* u,

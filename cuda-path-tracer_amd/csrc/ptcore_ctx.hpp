@@ -77,6 +77,21 @@ struct ptc_scene_state {
   const uint32_t* mesh_first_vertex = nullptr;
   float* vertex_normals = nullptr;
   bool normals_set = false;
+  // image textures (ptc_set_textures, ptc_set_texcoords): the scene's index and material counts and where each
+  // mesh's corners start (device, uploaded with the scene); the coordinates, allocated by the first call that sets any; the texel
+  // pool, the records, the per-material binding (replaced as a whole by every call that sets textures) and the two decode tables
+  // (allocated by the first) -- all of the scene's pool
+  uint32_t index_count = 0, material_count = 0;
+  const uint32_t* mesh_first_index = nullptr;
+  float* texcoords = nullptr;
+  bool texcoords_set = false;
+  uint32_t* tex_texels = nullptr;
+  texmap::Record* tex_records = nullptr;
+  int32_t* tex_material = nullptr;
+  float* tex_table = nullptr;
+  uint32_t texture_count = 0;
+  uint64_t texel_count = 0;
+  bool textures_set = false;
 };
 
 // the last epoch of a lap of look-back launches on a slot's tile descriptors (30 bits: pt_shade_tile.inc; ptcore_trace.cpp, next_epoch)
@@ -294,11 +309,15 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   // "smooth_normals" (DESIGN section 5n): a frame of a scene with vertex normals shades triangle hits with the interpolated normal
   // (k_megakernel_smooth); without normals it launches what it launched before
   bool smooth_normals = false;
+  // "textures" (DESIGN section 5o): a frame of a scene with textures and texture coordinates takes the colour of a bound diffuse or
+  // metal triangle hit from its texture (k_megakernel_tex); without either it launches what it launched before
+  bool textures = false;
   const uint4* env_table = nullptr;
   bool env_table_known = false;
   ptc_environment_light_stats env_direct{};  // ptc_environment_light since ptc_reset_profile
   // device: kLightStatLines lines of kLoopStatWords words (0 .. 2 the lamps': diffuse hits, shadow rays, unoccluded; 3 .. 5 the environment's;
-  // 6, 7 "mis": weighted emitter hits, weighted misses; 8 .. 11 "smooth_normals": shading normals, fall-backs, absorbed, culled)
+  // 6, 7 "mis": weighted emitter hits, weighted misses; 8 .. 11 "smooth_normals": shading normals, fall-backs, absorbed, culled;
+  // 12, 13 "textures": lookups, fall-backs)
   unsigned long long* loop_stats = nullptr;
   bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
   // the display transform (ptc_set_display; ptcore_display.cpp).  The default is the reference display: the presents
@@ -363,6 +382,9 @@ int show_display(ptc_ctx* ctx, const float4* src4, const float* src3, uint32_t n
 int build_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last, std::string* err,
                       std::vector<uint32_t>* thresholds);
 // ... of a scene as the caller hands it over: validate_scene's and build_light_table's refusals, with their message (ptc_last_error(NULL))
+// What ptc_set_textures and ptc_check_texture_lookup refuse in one texture (ptcore_scene.cpp): the rest of the sentence "texture i
+// ...", or "" for a texture they take
+std::string texture_refusal(const ptc_texture_desc& t);
 int checked_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, ptc_light_info* info, uint32_t* last,
                         std::vector<uint32_t>* thresholds);
 

@@ -444,6 +444,74 @@ int ptc_hit_attributes(ptc_ctx* ctx, const float* rays, uint32_t n, uint32_t* ob
   return PTC_OK;
 }
 
+// what the textured kernels take, from what is set now (a null member: not set)
+static DTex textures_of(const ptc_ctx* ctx)
+{
+  const bool tex = ctx->textures_set;
+  return DTex{tex ? ctx->tex_texels : nullptr, tex ? ctx->tex_records : nullptr, tex ? ctx->tex_material : nullptr, ctx->tex_table,
+              ctx->texcoords_set ? ctx->texcoords : nullptr, ctx->mesh_first_index};
+}
+
+// The interpolated texture coordinate and the albedo at the closest hit: k_hit_surface, ptc_hit_attributes' walk
+int ptc_hit_surface(ptc_ctx* ctx, const float* rays, uint32_t n, float* st_out, float* albedo_out)
+{
+  if (!ctx || !rays || !st_out || !albedo_out) return PTC_ERR_INVALID;
+  int rc;
+  if (!query_prologue(ctx, n, "rays", nullptr, &rc)) return rc;
+  QueryRun q(ctx, false);
+  float4* d_rays = nullptr;
+  float2* d_st = nullptr;
+  float* d_alb = nullptr;
+  uint32_t* d_flags = nullptr;
+  rc = q.alloc(&d_rays, 2u * (size_t)n);
+  if (!rc) rc = q.alloc(&d_st, n);
+  if (!rc) rc = q.alloc(&d_alb, 3u * (size_t)n);
+  if (!rc) rc = q.alloc(&d_flags, 1);
+  if (rc) return rc;
+  uint32_t dev_flags = 0u;
+  auto run = [&]() -> int {
+    HIP_TRY(ctx, hipMemcpyAsync(d_rays, rays, 8u * (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, sizeof(uint32_t), ctx->stream));
+    launch_hit_surface(ctx->stream, ctx->scene, textures_of(ctx), d_rays, n, d_st, d_alb, d_flags);
+    if (int r2 = check_last(ctx, "hit_surface")) return r2;
+    HIP_TRY(ctx, hipMemcpyAsync(st_out, d_st, n * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(albedo_out, d_alb, 3u * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&dev_flags, d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PTC_OK;
+  };
+  if ((rc = q.finish(run())) != PTC_OK) return rc;
+  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, "traversal stack overflow in ptc_hit_surface");
+  return PTC_OK;
+}
+
+// The lookup of one texture of the pool on the device: k_texture_sample, one thread per coordinate pair
+int ptc_sample_texture(ptc_ctx* ctx, uint32_t texture, const float* st, uint32_t n, float* rgb_out, uint8_t* rejected_out)
+{
+  if (!ctx || !st || !rgb_out) return PTC_ERR_INVALID;
+  int rc;
+  const bool known = ctx->has_scene && ctx->textures_set && texture < ctx->texture_count;
+  const char* bad = known || !ctx->has_scene ? nullptr : (ctx->textures_set ? "ptc_sample_texture: no such texture" : "ptc_sample_texture: no textures are set");
+  if (!query_prologue(ctx, n, "coordinates", bad, &rc)) return rc;
+  QueryRun q(ctx, false);
+  float *d_st = nullptr, *d_rgb = nullptr;
+  uint8_t* d_rej = nullptr;
+  rc = q.alloc(&d_st, 2u * (size_t)n);
+  if (!rc) rc = q.alloc(&d_rgb, 3u * (size_t)n);
+  if (!rc) rc = q.alloc(&d_rej, n);
+  if (rc) return rc;
+  auto run = [&]() -> int {
+    HIP_TRY(ctx, hipMemcpyAsync(d_st, st, 2u * (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    launch_texture_sample(ctx->stream, textures_of(ctx), texture, d_st, n, d_rgb, d_rej);
+    if (int r2 = check_last(ctx, "texture_sample")) return r2;
+    HIP_TRY(ctx, hipMemcpyAsync(rgb_out, d_rgb, 3u * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (rejected_out) HIP_TRY(ctx, hipMemcpyAsync(rejected_out, d_rej, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PTC_OK;
+  };
+  return q.finish(run());
+}
+
 int ptc_occluded_rays(ptc_ctx* ctx, const float* rays, uint32_t n, uint8_t* occluded)
 {
   if (!ctx || !rays || !occluded) return PTC_ERR_INVALID;

@@ -445,6 +445,18 @@ int checked_light_table(const ptc_scene_desc* s, std::vector<ptc_light>& out, pt
   return PTC_OK;
 }
 
+// What ptc_set_textures and ptc_check_texture_lookup refuse in one texture ("" : nothing)
+std::string texture_refusal(const ptc_texture_desc& t)
+{
+  if (t.width < 1u || t.width > texmap::kMaxSide || t.height < 1u || t.height > texmap::kMaxSide)
+    return "is " + std::to_string(t.width) + " x " + std::to_string(t.height) + ": each side must be in [1,4096]";
+  if (!t.rgba8) return "has a NULL texel pointer";
+  if (t.encoding > PTC_TEXTURE_SRGB) return "has encoding " + std::to_string(t.encoding) + ": 0 (linear) or 1 (sRGB)";
+  if (t.filter > PTC_TEXTURE_BILINEAR) return "has filter " + std::to_string(t.filter) + ": 0 (nearest) or 1 (bilinear)";
+  if (t.wrap > PTC_TEXTURE_CLAMP) return "has wrap " + std::to_string(t.wrap) + ": 0 (repeat) or 1 (clamp)";
+  return "";
+}
+
 }  // namespace ptcd
 
 namespace {
@@ -510,6 +522,7 @@ struct NewScene : ptc_scene_state {
   std::vector<float4> balls;       // DScene::sphere_ball
   std::vector<uint32_t> tri_base;  // DScene::object_tri_base
   std::vector<uint32_t> first_vertex;  // per mesh: where its vertices start in the scene's arrays (vertex normals, section 5n)
+  std::vector<uint32_t> first_index;   // per mesh: where its corners start in the scene's indices (texture coordinates, section 5o)
   size_t tri_records = 0;          // records of DScene::tris
   std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now(), last = start;
   void lap(float& into)
@@ -614,6 +627,9 @@ int stage_host(ptc_ctx* ctx, const ptc_scene_desc* s, const std::vector<MeshWork
   n.launches = launch_table(s->objects, object_nodes, &n.tail_begin, &n.tail_end);
   n.vertex_count = s->vertex_count;
   for (uint32_t m = 0; m < meshes.size(); ++m) n.first_vertex.push_back(s->meshes ? s->meshes[m].first_vertex : 0u);
+  n.index_count = s->index_count;
+  n.material_count = s->material_count;
+  for (uint32_t m = 0; m < meshes.size(); ++m) n.first_index.push_back(s->meshes ? s->meshes[m].first_index : 0u);
   for (const MeshWork& w : meshes) {
     n.bvh_nodes += w.node_count;
     n.bvh_depth = std::max(n.bvh_depth, w.depth);
@@ -771,6 +787,7 @@ int mesh_tables(ptc_ctx* ctx, const std::vector<MeshWork>& meshes, NewScene& n)
   if (int rc = upload(ctx, n.scene_allocs, &d.mesh_views, n.mesh_views.data(), n.mesh_views.size())) return rc;
   if (int rc = upload(ctx, n.scene_allocs, &d.object_mesh, n.object_mesh.data(), n.object_mesh.size())) return rc;
   if (int rc = upload(ctx, n.scene_allocs, &n.mesh_first_vertex, n.first_vertex.data(), n.first_vertex.size())) return rc;
+  if (int rc = upload(ctx, n.scene_allocs, &n.mesh_first_index, n.first_index.data(), n.first_index.size())) return rc;
   if (meshes.empty()) return PTC_OK;
   d.cur = n.mesh_views[0];
   const uint64_t t0 = meshes[0].triangles, n0 = meshes[0].node_count;
@@ -935,6 +952,136 @@ int ptc_get_vertex_normals(const ptc_ctx* ctx, uint32_t* vertex_count)
   const bool set = ctx && ctx->has_scene && ctx->normals_set;
   if (vertex_count) *vertex_count = set ? ctx->vertex_count : 0u;
   return set ? 1 : 0;
+}
+
+// Texture coordinates beside the scene: ptc_set_vertex_normals' shape, two floats per corner.
+int ptc_set_texcoords(ptc_ctx* ctx, const float* st, uint32_t index_count)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
+  if ((st == nullptr) != (index_count == 0u)) return fail(ctx, PTC_ERR_INVALID, "texture coordinates: NULL and 0 go together (they remove the coordinates)");
+  if (st && index_count != ctx->index_count)
+    return fail(ctx, PTC_ERR_INVALID, "texture coordinates: " + std::to_string(index_count) + " corners for a scene of " +
+                                          std::to_string(ctx->index_count) + " indices");
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;  // frames queued or in flight were asked for with what was set
+  if (!st) {
+    ctx->texcoords_set = false;
+    return PTC_OK;
+  }
+  if (!ctx->texcoords)
+    if (int rc = dev_alloc(ctx, ctx->scene_allocs, &ctx->texcoords, 2u * (size_t)index_count)) return rc;
+  HIP_TRY(ctx, hipMemcpy(ctx->texcoords, st, 2u * (size_t)index_count * sizeof(float), hipMemcpyHostToDevice));
+  ctx->texcoords_set = true;
+  return PTC_OK;
+}
+
+int ptc_get_texcoords(const ptc_ctx* ctx, uint32_t* index_count)
+{
+  const bool set = ctx && ctx->has_scene && ctx->texcoords_set;
+  if (index_count) *index_count = set ? ctx->index_count : 0u;
+  return set ? 1 : 0;
+}
+
+// Textures beside the scene.  Every refusal comes before anything is touched; the new pool, records and binding
+// are uploaded beside the old ones and take their place in the scene's pool only when nothing can fail any more.
+int ptc_set_textures(ptc_ctx* ctx, const ptc_texture_desc* textures, uint32_t texture_count, const int32_t* material_texture, uint32_t material_count)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
+  if ((textures == nullptr) != (texture_count == 0u)) return fail(ctx, PTC_ERR_INVALID, "textures: NULL and 0 go together (they remove the textures)");
+  std::vector<texmap::Record> records;
+  uint64_t texels = 0;
+  if (textures) {
+    if (material_count != ctx->material_count)
+      return fail(ctx, PTC_ERR_INVALID, "textures: " + std::to_string(material_count) + " bindings for a scene of " + std::to_string(ctx->material_count) +
+                                            " materials");
+    if (material_count && !material_texture) return fail(ctx, PTC_ERR_INVALID, "textures: material_texture is NULL");
+    for (uint32_t i = 0; i < texture_count; ++i) {
+      const std::string why = texture_refusal(textures[i]);
+      if (!why.empty()) return fail(ctx, PTC_ERR_INVALID, "texture " + std::to_string(i) + " " + why);
+      records.push_back(texmap::Record{(uint32_t)texels, textures[i].width, textures[i].height,
+                                        texmap::pack_flags(textures[i].encoding, textures[i].filter, textures[i].wrap)});
+      texels += (uint64_t)textures[i].width * textures[i].height;
+      if (texels * 4u > (1ull << 30)) return fail(ctx, PTC_ERR_INVALID, "textures: the pool exceeds 1 GiB at texture " + std::to_string(i));
+    }
+    for (uint32_t m = 0; m < material_count; ++m)
+      if (material_texture[m] < -1 || material_texture[m] >= (int64_t)texture_count)
+        return fail(ctx, PTC_ERR_INVALID, "textures: material " + std::to_string(m) + " is bound to texture " + std::to_string(material_texture[m]) +
+                                              " of " + std::to_string(texture_count));
+  }
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;  // frames queued or in flight were asked for with what was set
+  auto drop = [&](auto*& p) {  // gives one array of the scene's pool back
+    if (!p) return;
+    auto& pool = ctx->scene_allocs;
+    pool.erase(std::remove(pool.begin(), pool.end(), (void*)p), pool.end());
+    (void)hipFree(p);
+    p = nullptr;
+  };
+  if (!textures) {
+    drop(ctx->tex_texels);
+    drop(ctx->tex_records);
+    drop(ctx->tex_material);
+    ctx->texture_count = 0;
+    ctx->texel_count = 0;
+    ctx->textures_set = false;
+    return PTC_OK;
+  }
+  std::vector<void*> fresh;
+  struct Guard {
+    std::vector<void*>& p;
+    ~Guard() { free_pool(p); }
+  } guard{fresh};
+  uint32_t* d_texels = nullptr;
+  texmap::Record* d_records = nullptr;
+  int32_t* d_material = nullptr;
+  float* d_table = nullptr;
+  if (int rc = dev_alloc(ctx, fresh, &d_texels, (size_t)texels)) return rc;
+  if (int rc = dev_alloc(ctx, fresh, &d_records, records.size())) return rc;
+  if (int rc = dev_alloc(ctx, fresh, &d_material, std::max<size_t>(material_count, 1u))) return rc;
+  if (!ctx->tex_table)
+    if (int rc = dev_alloc(ctx, fresh, &d_table, 2u * (size_t)texmap::kTableEntries)) return rc;
+  for (uint32_t i = 0; i < texture_count; ++i)
+    HIP_TRY(ctx, hipMemcpy(d_texels + records[i].offset, textures[i].rgba8, (size_t)records[i].width * records[i].height * 4u, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(d_records, records.data(), records.size() * sizeof(texmap::Record), hipMemcpyHostToDevice));
+  if (material_count) HIP_TRY(ctx, hipMemcpy(d_material, material_texture, material_count * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (d_table) {
+    float table[2u * texmap::kTableEntries];
+    texmap::decode_table(texmap::kLinear, table);
+    texmap::decode_table(texmap::kSrgb, table + texmap::kTableEntries);
+    HIP_TRY(ctx, hipMemcpy(d_table, table, sizeof table, hipMemcpyHostToDevice));
+  }
+  // the commit: nothing below can fail
+  drop(ctx->tex_texels);
+  drop(ctx->tex_records);
+  drop(ctx->tex_material);
+  ctx->scene_allocs.insert(ctx->scene_allocs.end(), fresh.begin(), fresh.end());
+  fresh.clear();
+  ctx->tex_texels = d_texels;
+  ctx->tex_records = d_records;
+  ctx->tex_material = d_material;
+  if (d_table) ctx->tex_table = d_table;
+  ctx->texture_count = texture_count;
+  ctx->texel_count = texels;
+  ctx->textures_set = true;
+  return PTC_OK;
+}
+
+int ptc_get_textures(const ptc_ctx* ctx, uint32_t* texture_count, uint64_t* texel_count)
+{
+  const bool set = ctx && ctx->has_scene && ctx->textures_set;
+  if (texture_count) *texture_count = set ? ctx->texture_count : 0u;
+  if (texel_count) *texel_count = set ? ctx->texel_count : 0u;
+  return set ? 1 : 0;
+}
+
+int ptc_texture_decode_table(uint32_t encoding, float* out256)
+{
+  if (!out256) return fail(nullptr, PTC_ERR_INVALID, "texture decode table: out is NULL");
+  if (encoding > PTC_TEXTURE_SRGB) return fail(nullptr, PTC_ERR_INVALID, "texture decode table: encoding " + std::to_string(encoding) + " is neither 0 nor 1");
+  texmap::decode_table(encoding, out256);
+  return PTC_OK;
 }
 
 int ptc_compute_vertex_normals(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count, float* normals_out)

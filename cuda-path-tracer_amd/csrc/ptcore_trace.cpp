@@ -19,6 +19,9 @@ const char* const kMisNeedsMegakernel =
 // ... and "smooth_normals" 1
 const char* const kSmoothNeedsMegakernel =
     "smooth_normals is rendered by the megakernel method only (ptc_set_method(PTC_METHOD_MEGAKERNEL)); the streaming loop shades with face normals";
+// ... and "textures" 1
+const char* const kTexturesNeedMegakernel =
+    "textures are rendered by the megakernel method only (ptc_set_method(PTC_METHOD_MEGAKERNEL)); the streaming loop's hit records carry no primitive";
 
 // the epoch of the next look-back launch on a slot's tile descriptors (k_shade_fused, the listing k_raygen / k_spheres).  After
 // kMaxEpoch the epochs start at 1 again, and a descriptor that no launch of the finished lap has overwritten (a tile above a band
@@ -561,6 +564,7 @@ int ptc_trace_begin(ptc_ctx* ctx, const ptc_camera* camera)
   if (ctx->environment_light) return fail(ctx, PTC_ERR_INVALID, kEnvLightNeedsMegakernel);
   if (ctx->mis) return fail(ctx, PTC_ERR_INVALID, kMisNeedsMegakernel);
   if (ctx->smooth_normals) return fail(ctx, PTC_ERR_INVALID, kSmoothNeedsMegakernel);
+  if (ctx->textures) return fail(ctx, PTC_ERR_INVALID, kTexturesNeedMegakernel);
   // (ptc_trace stops at max_iterations; nothing else stands between the stepwise calls and ptc_trace_end's ++iteration)
   if (ctx->iteration == INT_MAX) return fail(ctx, PTC_ERR_INVALID, "the iteration counter is at INT_MAX: ptc_restart or ptc_set_iteration first");
   if (int rc = flush_pending(ctx)) return rc;
@@ -642,6 +646,7 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
   if (ctx->environment_light && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kEnvLightNeedsMegakernel);
   if (ctx->mis && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kMisNeedsMegakernel);
   if (ctx->smooth_normals && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kSmoothNeedsMegakernel);
+  if (ctx->textures && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kTexturesNeedMegakernel);
   if (ctx->iteration >= ctx->max_iterations) {  // path_tracer.cu:391
     ctx->result = ctx->fb.color4;
     return PTC_OK;
@@ -663,8 +668,10 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
     const bool env_lit = ctx->environment_light && env_frame(ctx) && ctx->env_table;
     // "smooth_normals" (DESIGN section 5n): a frame of a scene with vertex normals; without them as with 0
     const bool smooth = ctx->smooth_normals && ctx->normals_set;
+    // "textures" (DESIGN section 5o): a frame of a scene with textures and texture coordinates; without either as with 0
+    const bool textured = ctx->textures && ctx->textures_set && ctx->texcoords_set;
     DLights lights{};
-    if (direct || env_lit || smooth) {  // the frames that count in the loop-counter lines
+    if (direct || env_lit || smooth || textured) {  // the frames that count in the loop-counter lines
       if (ctx->loop_stats_clear) {
         HIP_TRY(ctx, hipMemsetAsync(ctx->loop_stats, 0, kLoopStatBytes, sl.stream));
         ctx->loop_stats_clear = false;
@@ -673,7 +680,13 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
     if (direct)
       lights = DLights{ctx->light_records, ctx->light_thresholds, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
                        ctx->scene.materials};
-    if (smooth) {  // its two instances, with the balance heuristic and without; every light and the environment by run-time choice
+    if (textured) {  // its four instances: the balance heuristic and the shading normal, each with and without
+      launch_megakernel_tex(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,
+                            sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx), env_frame(ctx) ? ctx->env : DEnv{nullptr, 0u, 0u},
+                            DEnvLight{env_lit ? ctx->env_table : nullptr}, DMis{direct ? ctx->light_material_pdf : nullptr},
+                            ctx->mis && (direct || env_lit), DSmooth{smooth ? ctx->vertex_normals : nullptr, ctx->mesh_first_vertex},
+                            DTex{ctx->tex_texels, ctx->tex_records, ctx->tex_material, ctx->tex_table, ctx->texcoords, ctx->mesh_first_index});
+    } else if (smooth) {  // its two instances, with the balance heuristic and without; every light and the environment by run-time choice
       launch_megakernel_smooth(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,
                                sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx), env_frame(ctx) ? ctx->env : DEnv{nullptr, 0u, 0u},
                                DEnvLight{env_lit ? ctx->env_table : nullptr}, DMis{direct ? ctx->light_material_pdf : nullptr},

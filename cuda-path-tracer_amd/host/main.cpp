@@ -3,7 +3,7 @@
 // following the call sequence of execute_cli_version (src/cli/cli.cpp:62-116): read scene, create_buffers,
 // max_iterations = spp, spp x path_trace, synchronize, send_to_preview, write PNG, stage timings.
 // Extra flags: --max-bounces N (the reference's cap is a compile-time 50), --denoise, --method, --gpu,
-// --lens-radius R / --focus-distance F (the thin lens), --tonemap C / --exposure EV / --auto-exposure / --key K / --white W (the display transform), --environment FILE / --environment-scale S / --environment-size N (environment lighting; --dump-environment FILE: the decoded picture and the map, for tests, no GPU), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
+// --lens-radius R / --focus-distance F (the thin lens), --tonemap C / --exposure EV / --auto-exposure / --key K / --white W (the display transform), --environment FILE / --environment-scale S / --environment-size N (environment lighting; --dump-environment FILE: the decoded picture and the map, for tests, no GPU), --textures (image textures), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
 // (DisplayBufferType of send_to_preview, path_tracer.cu:487-520: which buffer the PNG shows), --dump-raw FILE (the
 // accumulated float framebuffers as they are: "PTRF", width, height, 7 as uint32, then colour rgb, normal xyz and
 // depth planes as float32).  Without -o the reference opens its GLFW viewer; this build is headless and says so.
@@ -53,6 +53,7 @@ struct CliConfigurations {  // configurations.hpp:11-15
   bool environment_light = false;
   bool mis = false;
   bool smooth_normals = false;
+  bool textures = false;
   int roulette = 0;
   std::optional<float> lens_radius, focus_distance;  // the thin lens (override the scene file's camera keys)
   // environment lighting (override the scene file's "environment" key, each on its own)
@@ -91,6 +92,8 @@ void usage()
                "                       (needs --method megakernel and --direct-light, --environment-light or a scene that says \"light\": true)\n"
                "      --smooth-normals  shade every mesh with interpolated vertex normals, area-weighted from its triangles (needs --method\n"
                "                       megakernel; a scene that says \"smooth_normals\": true asks for it)\n"
+               "      --textures       take the colour of a material that carries a \"texture\" from its picture, at the mesh's `vt` coordinates (needs\n"
+               "                       --method megakernel; a scene that says \"textures\": true asks for it)\n"
                "      --environment FILE  environment lighting: an equirectangular Radiance .hdr (overrides the scene's \"environment\")\n"
                "      --environment-scale S  multiply the picture by S, a finite number >= 0 (default 1)\n"
                "      --environment-size N  size of the octahedral map made from it, in [2,4096] (default: the picture's height)\n"
@@ -135,6 +138,7 @@ CliConfigurations parse_cli_args(int argc, char** argv)
     else if (a == "--environment-light") c.environment_light = true;
     else if (a == "--mis") c.mis = true;
     else if (a == "--smooth-normals") c.smooth_normals = true;
+    else if (a == "--textures") c.textures = true;
     else if (a == "--roulette") {
       // a whole decimal number in [0, 64] (ptc_set_param's range), refused here: before the scene is read or a GPU touched
       const std::string v = need("roulette");
@@ -245,6 +249,10 @@ CliConfigurations parse_cli_args(int argc, char** argv)
   }
   if (c.smooth_normals && !c.megakernel) {  // ... and shades with face normals
     std::fprintf(stderr, "hip_pt: --smooth-normals needs --method megakernel (the streaming method shades with face normals)\n");
+    std::exit(1);
+  }
+  if (c.textures && !c.megakernel) {  // ... and its hit records carry no primitive
+    std::fprintf(stderr, "hip_pt: --textures needs --method megakernel (the streaming method's hit records carry no primitive)\n");
     std::exit(1);
   }
   if (c.tone_flag && (c.display == DisplayBufferType::normal || c.display == DisplayBufferType::depth)) {
@@ -381,6 +389,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   path_tracer.max_bounces = configs.max_bounces;
   path_tracer.max_iterations = scene_desc.spp;      // app.cpp:130
   path_tracer.smooth_normals = configs.smooth_normals || scene_desc.smooth_normals;  // (before create_buffers, which computes the normals)
+  path_tracer.textures = configs.textures || scene_desc.textures;  // (create_buffers sets the scene's textures and coordinates)
   path_tracer.create_buffers(resolution, scene_desc);
   bool enable_denoising = configs.denoise;
   DisplayBufferType display = configs.display;
@@ -501,6 +510,7 @@ try {
   path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
   path_tracer.mis = configs.mis;
   path_tracer.smooth_normals = configs.smooth_normals || scene_desc.smooth_normals;  // (before create_buffers, which computes the normals)
+  path_tracer.textures = configs.textures || scene_desc.textures;  // (create_buffers sets the scene's textures and coordinates)
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.display = configs.tone;
@@ -586,9 +596,10 @@ int run_ranks(const CliConfigurations& configs, const SceneDescription& scene_de
     return 1;
   }
   // (the megakernel seeds by frame pixel, so its ranks render the single-GPU image; it is let through for --direct-light,
-  // --environment-light, --mis and --smooth-normals, which the streaming method cannot render)
+  // --environment-light, --mis, --smooth-normals and --textures, which the streaming method cannot render)
   if (configs.denoise ||
-      (configs.megakernel && !configs.direct_light && !configs.environment_light && !configs.mis && !configs.smooth_normals && !scene_desc.smooth_normals)) {
+      (configs.megakernel && !configs.direct_light && !configs.environment_light && !configs.mis && !configs.smooth_normals && !scene_desc.smooth_normals &&
+       !configs.textures && !scene_desc.textures)) {
     std::fprintf(stderr, "hip_pt: --gpus N renders in streaming mode without the denoiser (it needs the whole frame in one context)\n");
     return 1;
   }
@@ -655,6 +666,12 @@ try {
     std::fprintf(stderr, "hip_pt: the scene says \"smooth_normals\": true, which needs --method megakernel (the streaming method shades with face normals)\n");
     return 1;
   }
+  // ... and so does a scene that asks for textures, or whose materials carry one
+  if ((scene_desc.textures || scene_desc.has_textures()) && !configs.megakernel) {
+    std::fprintf(stderr, "hip_pt: the scene %s, which needs --method megakernel (the streaming method's hit records carry no primitive)\n",
+                 scene_desc.textures ? "says \"textures\": true" : "has a material with a \"texture\"");
+    return 1;
+  }
   // --mis combines light samples with the path: it needs a light that is sampled (before any GPU is touched)
   if (configs.mis && !configs.direct_light && !configs.environment_light && !scene_desc.environment_source.light) {
     std::fprintf(stderr, "hip_pt: --mis needs --direct-light, --environment-light or a scene whose \"environment\" says \"light\": true\n");
@@ -712,6 +729,20 @@ try {
       const float lens[2] = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
       out.write(reinterpret_cast<const char*>(lens), sizeof lens);
     }
+    if (!flat.texcoords.empty() || !flat.textures.empty()) {  // (a scene without textures: the dump as ever)
+      const char tag[4] = {'T', 'E', 'X', '0'};
+      out.write(tag, sizeof tag);
+      dump_vec(out, flat.texcoords);
+      dump_vec(out, flat.material_texture);
+      const uint64_t count = flat.textures.size();
+      out.write(reinterpret_cast<const char*>(&count), sizeof count);
+      for (const TextureSource& t : flat.textures) {
+        const PngImage img = read_png(t.file);
+        const uint32_t head[5] = {(uint32_t)img.width, (uint32_t)img.height, t.encoding, t.filter, t.wrap};
+        out.write(reinterpret_cast<const char*>(head), sizeof head);
+        dump_vec(out, img.rgba);
+      }
+    }
     return 0;
   }
   if (configs.replay && configs.dry_run) return run_replay(configs, scene_desc);
@@ -733,6 +764,7 @@ try {
   path_tracer.environment_light = configs.environment_light || (configs.megakernel && scene_desc.environment_source.light);
   path_tracer.mis = configs.mis;
   path_tracer.smooth_normals = configs.smooth_normals || scene_desc.smooth_normals;  // (before create_buffers, which computes the normals)
+  path_tracer.textures = configs.textures || scene_desc.textures;  // (create_buffers sets the scene's textures and coordinates)
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.display = configs.tone;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/ptcore.h"
+#include "png_image.hpp"
 #include "scene_description.hpp"
 
 namespace hip_pt {
@@ -48,6 +49,10 @@ public:
   // interpolated vertex normal.  Set before create_buffers it also makes create_buffers compute and set the scene's vertex normals
   // (compute_vertex_normals); vertex normals of the caller's own go through set_vertex_normals after create_buffers.
   bool smooth_normals = false;
+  // image textures (megakernel method only; ptc_set_param "textures"): a triangle hit on a diffuse or metal material
+  // with a texture bound takes its colour from the texel at the interpolated coordinate.  Textures and coordinates go through
+  // set_textures and set_texcoords after create_buffers; without either the flag changes nothing.
+  bool textures = false;
   int roulette = 0;  // Russian roulette at every bounce >= this but the last, 0 = off (both methods; ptc_set_param "roulette", [0, 64])
   // the thin lens (ptc_set_lens): aperture radius (0 = the pinhole, the default) and the distance of the plane in
   // focus, world units; both methods
@@ -94,6 +99,18 @@ public:
     d.index_count = (uint32_t)flat.indices.size();
     check(ptc_upload_scene(ctx_, &d), "create_buffers");
     if (smooth_normals && !flat.indices.empty()) set_vertex_normals(compute_vertex_normals(flat));  // (a new scene starts without normals)
+    // what the scene file says about textures (a new scene starts without): the materials' pictures, read here (png_image.hpp flips
+    // the rows), and the mesh's per-corner coordinates
+    if (!flat.textures.empty()) {
+      std::vector<PngImage> pictures;
+      std::vector<ptc_texture_desc> descs;
+      for (const TextureSource& src : flat.textures) pictures.push_back(read_png(src.file));
+      for (size_t i = 0; i < pictures.size(); ++i)
+        descs.push_back(ptc_texture_desc{pictures[i].rgba.data(), (uint32_t)pictures[i].width, (uint32_t)pictures[i].height, flat.textures[i].encoding,
+                                         flat.textures[i].filter, flat.textures[i].wrap});
+      set_textures(descs, flat.material_texture);
+    }
+    if (!flat.texcoords.empty()) set_texcoords(flat.texcoords);
     resize_image(r);
   }
 
@@ -116,6 +133,45 @@ public:
     ptc_smooth_loop_stats s{};
     check(ptc_get_smooth_loop_stats(ctx_, &s), "smooth_loop_stats");
     return s;
+  }
+  // the uploaded scene's textures and, per material, -1 or the texture bound to it (ptc_set_textures); no textures removes them
+  void set_textures(const std::vector<ptc_texture_desc>& textures_in, const std::vector<int32_t>& material_texture)
+  {
+    check(ptc_set_textures(ctx_, textures_in.empty() ? nullptr : textures_in.data(), (uint32_t)textures_in.size(), material_texture.data(),
+                           (uint32_t)material_texture.size()),
+          "textures");
+  }
+  // the uploaded scene's texture coordinates (ptc_set_texcoords): two floats per triangle corner, parallel to the scene's indices; an
+  // empty vector removes them
+  void set_texcoords(const std::vector<float>& st)
+  {
+    check(ptc_set_texcoords(ctx_, st.empty() ? nullptr : st.data(), (uint32_t)(st.size() / 2)), "texcoords");
+  }
+  [[nodiscard]] ptc_texture_loop_stats texture_loop_stats() const
+  {
+    ptc_texture_loop_stats s{};
+    check(ptc_get_texture_loop_stats(ctx_, &s), "texture_loop_stats");
+    return s;
+  }
+  // the lookup of one of the scene's textures on the device (ptc_sample_texture): st two floats a pair -> three floats a pair
+  [[nodiscard]] std::vector<float> sample_texture(uint32_t texture, const std::vector<float>& st)
+  {
+    push_fields();
+    std::vector<float> rgb(3u * (st.size() / 2));
+    check(ptc_sample_texture(ctx_, texture, st.data(), (uint32_t)(st.size() / 2), rgb.data(), nullptr), "sample_texture");
+    return rgb;
+  }
+  // the closest hit's texture coordinate and albedo (ptc_hit_surface): rays 8 floats each; per ray (s, t) and three floats
+  struct HitSurface {
+    std::vector<float> st, albedo;
+  };
+  [[nodiscard]] HitSurface hit_surface(const std::vector<float>& rays)
+  {
+    push_fields();
+    const uint32_t n = (uint32_t)(rays.size() / 8);
+    HitSurface out{std::vector<float>(2u * (size_t)n), std::vector<float>(3u * (size_t)n)};
+    check(ptc_hit_surface(ctx_, rays.data(), n, out.st.data(), out.albedo.data()), "hit_surface");
+    return out;
   }
   // the closest hit's primitive and attributes (ptc_hit_attributes): rays 8 floats each; per ray object, triangle, (u, v), normal
   struct HitAttributes {
@@ -186,6 +242,10 @@ private:
       check(ptc_set_param(ctx_, "smooth_normals", smooth_normals ? 1 : 0), "smooth_normals");
       smooth_normals_pushed_ = smooth_normals;
     }
+    if (textures != textures_pushed_) {
+      check(ptc_set_param(ctx_, "textures", textures ? 1 : 0), "textures");
+      textures_pushed_ = textures;
+    }
     if (roulette != roulette_pushed_) {
       check(ptc_set_param(ctx_, "roulette", roulette), "roulette");
       roulette_pushed_ = roulette;
@@ -212,6 +272,7 @@ private:
   bool environment_light_pushed_ = false;
   bool mis_pushed_ = false;
   bool smooth_normals_pushed_ = false;
+  bool textures_pushed_ = false;
   int roulette_pushed_ = 0;
   Lens lens_pushed_{};
   std::shared_ptr<const EnvironmentMap> environment_pushed_;

@@ -200,8 +200,32 @@ FlatScene SceneDescription::build_scene() const
   if (mesh) {
     flat.positions = mesh->positions;
     flat.indices = mesh->indices;
+    flat.texcoords = mesh->texcoords;
+  }
+  if (has_textures()) {  // (the materials in the table's order: std::map iterates by name)
+    for (const auto& [name, material] : material_map_) {
+      const auto* d = std::get_if<DiffuseMateral>(&material);
+      const auto* mt = std::get_if<MetalMaterial>(&material);
+      const TextureSource* src = d ? &d->texture : (mt ? &mt->texture : nullptr);
+      int32_t bound = -1;
+      if (src && !src->file.empty()) {
+        const auto it = std::find(flat.textures.begin(), flat.textures.end(), *src);
+        bound = (int32_t)(it - flat.textures.begin());
+        if (it == flat.textures.end()) flat.textures.push_back(*src);
+      }
+      flat.material_texture.push_back(bound);
+    }
   }
   return flat;
+}
+
+bool SceneDescription::has_textures() const
+{
+  for (const auto& [name, material] : material_map_) {
+    if (const auto* d = std::get_if<DiffuseMateral>(&material); d && !d->texture.file.empty()) return true;
+    if (const auto* mt = std::get_if<MetalMaterial>(&material); mt && !mt->texture.file.empty()) return true;
+  }
+  return false;
 }
 
 // ---------------------------------------------------------------- JSON (just enough for the scene grammar)
@@ -269,11 +293,40 @@ SceneDescription scene_from_json(const std::string& filename, bool read_environm
 
   SceneDescription scene;
   scene.filename = filename;
+  // a diffuse or metal material's optional "texture" (an extension; json_parser.py, the same rule): {"file": a PNG,
+  // relative to the scene file; "encoding": "srgb" | "linear"; "filter": "bilinear" | "nearest"; "wrap": "repeat" | "clamp"}
+  auto texture_of = [&](const Json& m, const std::string& name) {
+    TextureSource src;
+    const Json* t = m.find("texture");
+    if (!t) return src;
+    const Json* file = t->kind == Json::Object ? t->find("file") : nullptr;
+    bool ok = file && file->kind == Json::String;
+    if (ok)
+      for (const auto& [key, value] : t->obj)
+        ok = ok && (key == "file" || key == "encoding" || key == "filter" || key == "wrap");
+    if (!ok)
+      throw std::runtime_error("Json Parser: material " + name + ": \"texture\" must be an object with \"file\" (a string) and optionally \"encoding\", \"filter\", \"wrap\"");
+    auto choice = [&](const char* key, const char* first, const char* second, uint32_t* out) {
+      const Json* j = t->find(key);
+      if (!j) return;
+      if (j->kind == Json::String && j->str == first) *out = 0u;
+      else if (j->kind == Json::String && j->str == second) *out = 1u;
+      else throw std::runtime_error("Json Parser: material " + name + ": texture \"" + key + "\" must be \"" + first + "\" or \"" + second + "\"");
+    };
+    choice("encoding", "linear", "srgb", &src.encoding);
+    choice("filter", "nearest", "bilinear", &src.filter);
+    choice("wrap", "repeat", "clamp", &src.wrap);
+    src.file = !file->str.empty() && file->str[0] == '/' ? file->str : dir + "/" + file->str;
+    return src;
+  };
   for (const auto& m : root->at("materials").arr) {  // read_materials, json_parser.cpp:101-122
     const std::string name = m->at("name").str, type = m->at("type").str;
+    if (m->find("texture") && type != "lambertian" && type != "metal")
+      throw std::runtime_error("Json Parser: material " + name + ": only a lambertian or a metal material may carry a \"texture\"");
     if (type == "lambertian") {
       DiffuseMateral d{};
       vec3_from(m->at("albedo"), d.albedo);
+      d.texture = texture_of(*m, name);
       scene.add_material(name, d);
     } else if (type == "dielectric") {
       scene.add_material(name, DielectricMaterial{m->at("refraction_index").f()});
@@ -281,6 +334,7 @@ SceneDescription scene_from_json(const std::string& filename, bool read_environm
       MetalMaterial mt{};
       vec3_from(m->at("albedo"), mt.albedo);
       mt.fuzz = m->at("fuzz").f();
+      mt.texture = texture_of(*m, name);
       scene.add_material(name, mt);
     } else if (type == "emissive") {  // an extension: the reference's grammar has no emitters
       // "emission": three finite numbers >= 0 (json_parser.py, the same rule)
@@ -341,6 +395,11 @@ SceneDescription scene_from_json(const std::string& filename, bool read_environm
     if (sm->kind != Json::Bool) throw std::runtime_error("Json Parser: \"smooth_normals\" must be true or false");
     scene.smooth_normals = sm->b;
   }
+  // image textures (an extension; json_parser.py, the same rule): the top-level key "textures", a boolean
+  if (const Json* tx = root->find("textures")) {
+    if (tx->kind != Json::Bool) throw std::runtime_error("Json Parser: \"textures\" must be true or false");
+    scene.textures = tx->b;
+  }
   // environment lighting (an extension; json_parser.py, the same rule): {"file": a Radiance .hdr, equirectangular, relative to the
   // scene file; "scale": a finite number >= 0, default 1; "size": an integer in [2,4096], default the picture's height, at most 4096;
   // "light": a boolean, default false -- sample the environment as a light under the megakernel method}
@@ -385,6 +444,10 @@ Mesh load_obj(const std::string& filename)
   Mesh mesh;
   std::vector<float> all;          // every `v` of the file
   std::vector<uint32_t> faces;     // the first mesh's triangles, indices into `all`
+  // texture coordinates (an extension; json_parser.py, the same rule): every `vt` of the file, and per corner of
+  // `faces` the pair its token's second field names -- negative indices count from the last `vt` read, a corner without one (or with
+  // one the file does not hold) gets (0, 0)
+  std::vector<float> vts, corners;
   std::string line, cur_o, cur_g, cur_m;
   bool closed = false;             // the first mesh is complete: a later chunk has begun
   auto name_of = [](const std::string& l, size_t from) {
@@ -400,6 +463,11 @@ Mesh load_obj(const std::string& filename)
         all.push_back(y);
         all.push_back(z);
       }
+    } else if (line[0] == 'v' && line[1] == 't' && line.size() > 2 && line[2] == ' ') {
+      float s = 0.0f, t = 0.0f;
+      (void)std::sscanf(line.c_str() + 3, "%f %f", &s, &t);
+      vts.push_back(s);
+      vts.push_back(t);
     } else if ((line[0] == 'o' || line[0] == 'g') && (line[1] == ' ' || line[1] == '\t')) {
       std::string& cur = line[0] == 'o' ? cur_o : cur_g;
       const std::string name = name_of(line, 1);
@@ -411,17 +479,29 @@ Mesh load_obj(const std::string& filename)
       cur_m = name;
     } else if (line[0] == 'f' && line[1] == ' ' && !closed) {
       std::vector<uint32_t> face;
+      std::vector<float> st;
       std::istringstream ss(line.substr(2));
       std::string tok;
       while (ss >> tok) {
         const long idx = std::strtol(tok.c_str(), nullptr, 10);  // "a", "a/b", "a/b/c", "a//c"
         const long count = (long)(all.size() / 3);
         face.push_back((uint32_t)(idx < 0 ? count + idx : idx - 1));
+        const size_t slash = tok.find('/');
+        long t = slash == std::string::npos ? 0 : std::strtol(tok.c_str() + slash + 1, nullptr, 10);  // ("a//c": 0, no `vt`)
+        const long vt_count = (long)(vts.size() / 2);
+        t = t < 0 ? vt_count + t : t - 1;
+        const bool known = t >= 0 && t < vt_count;
+        st.push_back(known ? vts[2 * (size_t)t] : 0.0f);
+        st.push_back(known ? vts[2 * (size_t)t + 1] : 0.0f);
       }
       for (size_t k = 1; k + 1 < face.size(); ++k) {
         faces.push_back(face[0]);
         faces.push_back(face[k]);
         faces.push_back(face[k + 1]);
+        for (const size_t c : {(size_t)0, k, k + 1}) {
+          corners.push_back(st[2 * c]);
+          corners.push_back(st[2 * c + 1]);
+        }
       }
     }
   }
@@ -441,6 +521,7 @@ Mesh load_obj(const std::string& filename)
     }
   mesh.indices.reserve(faces.size());
   for (uint32_t v : faces) mesh.indices.push_back(remap[v]);
+  if (!vts.empty()) mesh.texcoords = corners;
   for (int a = 0; a < 3; ++a) mesh.aabb_min[a] = mesh.aabb_max[a] = mesh.positions[(size_t)a];
   for (size_t v = 0; v < mesh.positions.size() / 3; ++v)
     for (int a = 0; a < 3; ++a) {

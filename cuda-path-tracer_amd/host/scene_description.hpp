@@ -25,8 +25,15 @@ Mat4 rotate(float angle_rad, float ax, float ay, float az);        // glm::rotat
 Mat4 look_at(const float from[3], const float at[3], const float up[3]);  // json_parser.cpp:57-70
 Mat4 multiply(const Mat4& a, const Mat4& b);                       // glm mat4 * mat4
 
-struct DiffuseMateral { float albedo[3]; };                 // (sic) material.hpp:6-8
-struct MetalMaterial { float albedo[3]; float fuzz; };      // material.hpp:10-13
+// a material's "texture" in a scene file (an extension): the picture (a PNG; file empty: none) and how it is looked
+// up, ptc_texture_desc's enum values
+struct TextureSource {
+  std::string file;
+  uint32_t encoding = PTC_TEXTURE_SRGB, filter = PTC_TEXTURE_BILINEAR, wrap = PTC_TEXTURE_REPEAT;
+  bool operator==(const TextureSource& o) const { return file == o.file && encoding == o.encoding && filter == o.filter && wrap == o.wrap; }
+};
+struct DiffuseMateral { float albedo[3]; TextureSource texture{}; };                 // (sic) material.hpp:6-8
+struct MetalMaterial { float albedo[3]; float fuzz; TextureSource texture{}; };      // material.hpp:10-13
 struct DielectricMaterial { float refraction_index; };      // material.hpp:15-17
 struct EmissiveMaterial { float emission[3]; };             // an extension (the reference has no emitters): ptc_material type 3
 using Material = std::variant<DiffuseMateral, MetalMaterial, DielectricMaterial, EmissiveMaterial>;
@@ -36,6 +43,9 @@ struct Sphere { float center[3] = {0, 0, 0}; float radius = 0; };  // sphere.hpp
 struct Mesh {  // mesh.hpp:9-18
   std::vector<float> positions;    // xyz per vertex
   std::vector<uint32_t> indices;
+  // texture coordinates (an extension): one (s, t) pair per triangle CORNER, parallel to indices (a corner without
+  // a `vt` has (0, 0)); empty: the file has no `vt` record
+  std::vector<float> texcoords;
   float aabb_min[3] = {0, 0, 0}, aabb_max[3] = {0, 0, 0};
   [[nodiscard]] size_t triangle_count() const { return indices.size() / 3; }
 };
@@ -63,6 +73,12 @@ struct FlatScene {
   std::vector<ptc_material> materials;
   std::vector<float> positions;
   std::vector<uint32_t> indices;
+  // image textures (an extension; PathTracer::create_buffers sets them): texcoords two floats per corner, parallel to
+  // indices (empty: the mesh has none); textures: the distinct TextureSource of the materials; material_texture: per material -1 or
+  // an index into it (empty: no material has one)
+  std::vector<float> texcoords;
+  std::vector<TextureSource> textures;
+  std::vector<int32_t> material_texture;
 };
 
 class SceneDescription {  // scene_description.hpp:27-49
@@ -83,6 +99,9 @@ public:
   // smooth shading (an extension): the scene file's "smooth_normals": true -- shade every mesh with interpolated
   // vertex normals, computed from its triangles (the megakernel method renders them)
   bool smooth_normals = false;
+  // image textures (an extension): the scene file's "textures": true; has_textures: a material carries a "texture"
+  bool textures = false;
+  [[nodiscard]] bool has_textures() const;
 
   void add_material(const std::string& name, Material material);
   void add_object(Sphere sphere, const Mat4& transform, const std::string& material_name);

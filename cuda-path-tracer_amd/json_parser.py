@@ -10,21 +10,29 @@ import numpy as np
 from . import glmlite as glm
 from . import hdr
 from .scene_description import (Camera, DielectricMaterial, DiffuseMateral, EmissiveMaterial, Mesh, MetalMaterial, SceneDescription,
-                                Sphere)
+                                Sphere, TextureSource)
 
 
 def load_obj(filename):
     """model_loader.cpp:11-44 keeps assimp's mMeshes[0] only.  assimp's OBJ importer opens a new mesh at every `o` / `g` that
     names another object or group and at every `usemtl` that names another material, and drops meshes without faces: the
     first chunk that holds a face is kept, with the vertices its faces use (file order); fan triangulation.  The same rule
-    as host/scene_description.cpp (tests/test_cli_frontend.py compares the two)."""
+    as host/scene_description.cpp (tests/test_cli_frontend.py compares the two).
+    Texture coordinates (an extension): `vt` records and the second field of an `f a/b/c` token are collected into
+    Mesh.texcoords, one (s, t) pair per triangle corner, fan-triangulated with the faces; negative indices count from the last `vt`
+    read, a corner without a `vt` (or with one the file does not hold) gets (0, 0); a file without `vt` records gives None."""
     positions, faces = [], []
+    vts, corners = [], []
     cur = {"o": "", "g": "", "usemtl": ""}
     closed = False
     with open(filename) as f:
         for line in f:
             if line.startswith("v "):
                 positions.append([float(x) for x in line.split()[1:4]])
+                continue
+            if line.startswith("vt "):
+                vals = [float(x) for x in line.split()[1:3]]
+                vts.append((vals + [0.0, 0.0])[:2])
                 continue
             key = line.split(None, 1)[0] if line.strip() else ""
             if key in cur and line[len(key):len(key) + 1] in (" ", "\t"):
@@ -33,12 +41,17 @@ def load_obj(filename):
                     closed = True
                 cur[key] = name
             elif line.startswith("f ") and not closed:
-                face = []
+                face, st = [], []
                 for tok in line.split()[1:]:
-                    idx = int(tok.split("/")[0])
+                    fields = tok.split("/")
+                    idx = int(fields[0])
                     face.append(len(positions) + idx if idx < 0 else idx - 1)
+                    t = int(fields[1]) if len(fields) > 1 and fields[1] else 0
+                    t = len(vts) + t if t < 0 else t - 1
+                    st.append(vts[t] if 0 <= t < len(vts) else [0.0, 0.0])
                 for k in range(1, len(face) - 1):
                     faces += [face[0], face[k], face[k + 1]]
+                    corners += [st[0], st[k], st[k + 1]]
     if not positions or not faces:
         raise ValueError(f"Unable to load {filename}")
     positions = np.array(positions, dtype=np.float32)
@@ -48,7 +61,7 @@ def load_obj(filename):
     used = np.zeros(len(positions), dtype=bool)
     used[faces] = True
     remap = np.cumsum(used) - 1
-    return Mesh(positions[used], remap[faces].astype(np.uint32))
+    return Mesh(positions[used], remap[faces].astype(np.uint32), texcoords=np.array(corners, dtype=np.float32) if vts else None)
 
 
 def _command(j):
@@ -81,6 +94,24 @@ def _emission(m):
             not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v >= 0 for v in e)):
         raise ValueError(f"Json Parser: emissive material {m.get('name')!r} needs \"emission\": three finite numbers >= 0")
     return tuple(e)
+
+
+def _texture(m, file_dir):
+    """A diffuse or metal material's optional "texture" (an extension; scene_description.cpp, the same rule):
+    {"file": a PNG, relative to the scene file; "encoding": "srgb" | "linear"; "filter": "bilinear" | "nearest"; "wrap": "repeat" |
+    "clamp"}, defaults srgb, bilinear, repeat.  -> a TextureSource, or None without the key"""
+    if "texture" not in m:
+        return None
+    j = m["texture"]
+    choices = {"encoding": ("srgb", "linear"), "filter": ("bilinear", "nearest"), "wrap": ("repeat", "clamp")}
+    if not isinstance(j, dict) or not isinstance(j.get("file"), str) or set(j) - {"file", *choices}:
+        raise ValueError(f"Json Parser: material {m.get('name')!r}: \"texture\" must be an object with \"file\" (a string) and optionally "
+                         "\"encoding\", \"filter\", \"wrap\"")
+    for key, allowed in choices.items():
+        if j.get(key, allowed[0]) not in allowed:
+            raise ValueError(f"Json Parser: material {m.get('name')!r}: texture \"{key}\" must be \"{allowed[0]}\" or \"{allowed[1]}\"")
+    return TextureSource(os.path.normpath(os.path.join(file_dir, j["file"])), j.get("encoding", "srgb"), j.get("filter", "bilinear"),
+                         j.get("wrap", "repeat"))
 
 
 def _lens_value(cam, key, positive):
@@ -127,15 +158,17 @@ def scene_from_json(filename):
     for m in root["materials"]:
         t = m["type"]
         if t == "lambertian":
-            scene.add_material(m["name"], DiffuseMateral(tuple(m["albedo"])))
+            scene.add_material(m["name"], DiffuseMateral(tuple(m["albedo"]), _texture(m, file_dir)))
         elif t == "dielectric":
             scene.add_material(m["name"], DielectricMaterial(m["refraction_index"]))
         elif t == "metal":
-            scene.add_material(m["name"], MetalMaterial(tuple(m["albedo"]), m["fuzz"]))
+            scene.add_material(m["name"], MetalMaterial(tuple(m["albedo"]), m["fuzz"], _texture(m, file_dir)))
         elif t == "emissive":  # an extension: the reference's grammar has no emitters
             scene.add_material(m["name"], EmissiveMaterial(_emission(m)))
         else:
             raise ValueError(f"Json Parser: Unsupported material type {t}")
+        if "texture" in m and t not in ("lambertian", "metal"):
+            raise ValueError(f"Json Parser: material {m['name']!r}: only a lambertian or a metal material may carry a \"texture\"")
     for s in root["surfaces"]:
         transform = _transform(s["transform"])
         if s["type"] == "sphere":
@@ -163,6 +196,10 @@ def scene_from_json(filename):
         if not isinstance(root["smooth_normals"], bool):
             raise ValueError('Json Parser: "smooth_normals" must be true or false')
         scene.smooth_normals = root["smooth_normals"]
+    if "textures" in root:  # (an extension; scene_description.cpp, the same rule)
+        if not isinstance(root["textures"], bool):
+            raise ValueError('Json Parser: "textures" must be true or false')
+        scene.textures = root["textures"]
     if "environment" in root:
         scene.environment, scene.environment_source = _environment(root["environment"], file_dir)
     return scene

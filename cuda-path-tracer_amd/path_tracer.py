@@ -101,6 +101,56 @@ def check_light_sample(scene, points, normals, v, u):
     return {"lamp": lamp, "rays": rays, "contribution": contribution, "sampled": sampled.astype(bool)}
 
 
+_ENCODINGS = {"linear": 0, "srgb": 1}
+_FILTERS = {"nearest": 0, "bilinear": 1}
+_WRAPS = {"repeat": 0, "clamp": 1}
+
+
+class Texture:
+    """One image texture (ptc_texture_desc): rgba8 [height, width, 4] uint8 with row 0 at t = 0 -- the BOTTOM of the
+    picture in OBJ's convention (a file reader flips rows) --, encoding "srgb" | "linear", filter "bilinear" | "nearest", wrap "repeat" |
+    "clamp" (or their numbers, which are passed on unchecked: the library refuses)."""
+
+    def __init__(self, rgba8, encoding="srgb", filter="bilinear", wrap="repeat"):
+        a = np.array(rgba8, dtype=np.uint8, order="C")
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("a texture is [height, width, 4] uint8, got shape %r" % (a.shape,))
+        a.setflags(write=False)
+        self.rgba8 = a
+        self.encoding = _ENCODINGS.get(encoding, encoding)
+        self.filter = _FILTERS.get(filter, filter)
+        self.wrap = _WRAPS.get(wrap, wrap)
+
+    @property
+    def height(self):
+        return self.rgba8.shape[0]
+
+    @property
+    def width(self):
+        return self.rgba8.shape[1]
+
+    def _desc(self):
+        return _capi.ptc_texture_desc(self.rgba8.ctypes.data, self.width, self.height, int(self.encoding), int(self.filter), int(self.wrap))
+
+
+def texture_decode_table(encoding):
+    """The 256-entry decode table of an encoding ("linear" | "srgb" or 0 | 1; ptc_texture_decode_table; host-side, no GPU needed)"""
+    out = np.zeros(256, dtype=np.float32)
+    _capi.check(_capi.lib().ptc_texture_decode_table(int(_ENCODINGS.get(encoding, encoding)), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def check_texture_lookup(texture, st):
+    """The texture lookup of DESIGN section 5o on the host (ptc_check_texture_lookup; no GPU needed): st [n, 2] ->
+    (rgb float32 [n, 3], rejected bool [n])"""
+    st = np.ascontiguousarray(st, dtype=np.float32).reshape(-1, 2)
+    rgb, rej = np.zeros((len(st), 3), dtype=np.float32), np.zeros(len(st), dtype=np.uint8)
+    d = texture._desc()
+    _capi.check(_capi.lib().ptc_check_texture_lookup(C.byref(d), st.ctypes.data_as(C.c_void_p), len(st), rgb.ctypes.data_as(C.c_void_p),
+                                                     rej.ctypes.data_as(C.c_void_p)))
+    return rgb, rej.astype(bool)
+
+
 def compute_vertex_normals(positions, indices=None, mesh_ranges=None):
     """Area-weighted vertex normals (ptc_compute_vertex_normals; host-side, no GPU needed).  positions [v, 3] and
     indices [t * 3] of one mesh, or -- with mesh_ranges, a mesh table's rows (first_vertex, vertex_count, first_index, index_count, ...)
@@ -204,6 +254,10 @@ class PathTracer:
         self._environment_light_pushed = False
         self._mis_pushed = False
         self._smooth_normals_pushed = False
+        self._textures = False  # PathTracer.textures = True: bound materials take their colour from their texture (megakernel only)
+        self._textures_pushed = False
+        self._texture_table = None  # PathTracer.texture_table = (textures, material_texture) (None: none)
+        self._texcoords = None  # PathTracer.texcoords = [index_count, 2] float32, parallel to the uploaded scene's indices (None: none)
         self._roulette_pushed = 0
         self._lens_pushed = (0.0, 1.0)
         self._environment_pushed = None
@@ -269,6 +323,64 @@ class PathTracer:
     @smooth_normals.setter
     def smooth_normals(self, on):
         self._smooth_normals = bool(on)
+
+    @property
+    def textures(self):
+        """Image textures in the megakernel (ptc_set_param "textures"): True = a triangle hit on a diffuse or metal
+        material with a texture bound takes its colour from the texel at the interpolated coordinate.  Changes nothing while
+        texture_table or texcoords is not set."""
+        return self._textures
+
+    @textures.setter
+    def textures(self, on):
+        self._textures = bool(on)
+
+    @property
+    def texture_table(self):
+        """The scene's textures and their bindings (ptc_set_textures): a pair (list of Texture, material_texture) with
+        material_texture[m] = -1 or the texture of material m of the uploaded scene; None removes them.  Assignment uploads at once --
+        after create_buffers, which starts every scene without textures -- and a refusal raises PtcError and leaves what was set."""
+        return self._texture_table
+
+    @texture_table.setter
+    def texture_table(self, value):
+        if value is None:
+            self._check(self._lib.ptc_set_textures(self._ctx, None, 0, None, 0))
+            self._texture_table = None
+            return
+        textures, binding = value
+        textures = list(textures)
+        b = np.array(binding, dtype=np.int32, order="C").reshape(-1)
+        descs = (_capi.ptc_texture_desc * max(len(textures), 1))(*[t._desc() for t in textures])
+        self._check(self._lib.ptc_set_textures(self._ctx, descs if textures else None, len(textures), b.ctypes.data_as(C.c_void_p), len(b)))
+        b.setflags(write=False)
+        self._texture_table = (tuple(textures), b)
+
+    def load_scene_textures(self, flat):
+        """What a scene file says about textures, after create_buffers: reads the pictures of flat.texture_sources (png.read_png, which
+        flips rows) and sets texture_table and texcoords from them and from flat.texcoords.  A scene without either sets nothing."""
+        from . import png
+        if flat.texture_sources:
+            self.texture_table = ([Texture(png.read_png(s.file), s.encoding, s.filter, s.wrap) for s in flat.texture_sources], flat.material_texture)
+        if flat.texcoords is not None:
+            self.texcoords = flat.texcoords
+
+    @property
+    def texcoords(self):
+        """The scene's texture coordinates (ptc_set_texcoords): [index_count, 2] float32 (s, t), one pair per triangle corner, parallel
+        to the uploaded scene's indices; None removes them.  Assignment uploads at once, as vertex_normals does."""
+        return self._texcoords
+
+    @texcoords.setter
+    def texcoords(self, value):
+        if value is None:
+            self._check(self._lib.ptc_set_texcoords(self._ctx, None, 0))
+            self._texcoords = None
+            return
+        st = np.array(value, dtype=np.float32, order="C").reshape(-1, 2)
+        self._check(self._lib.ptc_set_texcoords(self._ctx, st.ctypes.data_as(C.c_void_p), len(st)))
+        st.setflags(write=False)
+        self._texcoords = st
 
     @property
     def vertex_normals(self):
@@ -408,6 +520,9 @@ class PathTracer:
         if self._smooth_normals != self._smooth_normals_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"smooth_normals", 1 if self._smooth_normals else 0))
             self._smooth_normals_pushed = self._smooth_normals
+        if self._textures != self._textures_pushed:
+            self._check(self._lib.ptc_set_param(self._ctx, b"textures", 1 if self._textures else 0))
+            self._textures_pushed = self._textures
         if self._roulette != self._roulette_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"roulette", self._roulette))
             self._roulette_pushed = self._roulette
@@ -445,6 +560,7 @@ class PathTracer:
         desc = flat.to_c()
         self._check(self._lib.ptc_upload_scene(self._ctx, C.byref(desc)))
         self._vertex_normals = None  # (a new scene starts without normals)
+        self._texture_table = self._texcoords = None  # (... and without textures and coordinates)
         self.resize_image(resolution)
 
     def path_trace(self, camera, resolution=None):
@@ -794,6 +910,33 @@ class PathTracer:
         self._check(self._lib.ptc_get_smooth_loop_stats(self._ctx, C.byref(s)))
         return {"shading_normals": int(s.shading_normals), "fallbacks": int(s.fallbacks), "absorbed": int(s.absorbed),
                 "culled_light_samples": int(s.culled_light_samples)}
+
+    def texture_loop_stats(self):
+        """Counters of the megakernel under textures = True with textures and coordinates set, since restart: texel lookups, and hits
+        that kept the material's colour because their interpolated coordinate was not finite."""
+        s = _capi.ptc_texture_loop_stats()
+        self._check(self._lib.ptc_get_texture_loop_stats(self._ctx, C.byref(s)))
+        return {"lookups": int(s.lookups), "fallbacks": int(s.fallbacks)}
+
+    def sample_texture(self, texture, st):
+        """The lookup of texture `texture` of texture_table on the device, without rendering (ptc_sample_texture): st [n, 2] ->
+        (rgb float32 [n, 3], zeros where the rule refuses the pair; rejected bool [n])"""
+        self._push_fields()
+        st = np.ascontiguousarray(st, dtype=np.float32).reshape(-1, 2)
+        rgb, rej = np.zeros((len(st), 3), dtype=np.float32), np.zeros(len(st), dtype=np.uint8)
+        self._check(self._lib.ptc_sample_texture(self._ctx, int(texture), st.ctypes.data_as(C.c_void_p), len(st), rgb.ctypes.data_as(C.c_void_p),
+                                                 rej.ctypes.data_as(C.c_void_p)))
+        return rgb, rej.astype(bool)
+
+    def hit_surface(self, rays):
+        """The closest hit's texture coordinate and albedo (ptc_hit_surface) of rays [n, 8] -> dict(st float32 [n, 2], albedo float32
+        [n, 3]: texel x colour where a texture applies, else the material's colour; zeros on a miss)"""
+        self._push_fields()
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        st, alb = np.zeros((len(r), 2), dtype=np.float32), np.zeros((len(r), 3), dtype=np.float32)
+        self._check(self._lib.ptc_hit_surface(self._ctx, r.ctypes.data_as(C.c_void_p), len(r), st.ctypes.data_as(C.c_void_p),
+                                              alb.ctypes.data_as(C.c_void_p)))
+        return {"st": st, "albedo": alb}
 
     def hit_attributes(self, rays):
         """The closest hit's primitive and attributes (ptc_hit_attributes) of rays [n, 8] (origin, t_min, direction, t_max) ->

@@ -12,15 +12,26 @@ from . import _capi
 from . import glmlite as glm
 
 
+@dataclass(frozen=True)
+class TextureSource:
+    """A material's "texture" in a scene file (an extension): the picture (a PNG; absolute path) and how it is looked up"""
+    file: str
+    encoding: str = "srgb"     # "srgb" | "linear"
+    filter: str = "bilinear"   # "bilinear" | "nearest"
+    wrap: str = "repeat"       # "repeat" | "clamp"
+
+
 @dataclass
 class DiffuseMateral:  # (sic) material.hpp:6-8
     albedo: tuple
+    texture: TextureSource = None  # (an extension; DESIGN section 5o)
 
 
 @dataclass
 class MetalMaterial:  # material.hpp:10-13
     albedo: tuple
     fuzz: float = 0.0
+    texture: TextureSource = None  # (an extension; DESIGN section 5o)
 
 
 @dataclass
@@ -44,8 +55,13 @@ class Mesh:  # mesh.hpp:9-18
     positions: np.ndarray  # [V,3] float32
     indices: np.ndarray    # [3T] uint32
     aabb: tuple = None     # (min xyz, max xyz); the OBJ loader takes assimp's bounding box
+    # texture coordinates (an extension): [3T, 2] float32, one (s, t) pair per triangle CORNER, parallel to indices
+    # (a corner without a `vt` has (0, 0)); None: the file has no `vt` record
+    texcoords: np.ndarray = None
 
     def __post_init__(self):
+        if self.texcoords is not None:
+            self.texcoords = np.ascontiguousarray(self.texcoords, dtype=np.float32).reshape(-1, 2)
         self.positions = np.ascontiguousarray(self.positions, dtype=np.float32).reshape(-1, 3)
         self.indices = np.ascontiguousarray(self.indices, dtype=np.uint32).reshape(-1)
         if self.aabb is None and len(self.positions):
@@ -84,6 +100,12 @@ class FlatScene:
     indices: np.ndarray            # [3T] uint32
     bvh: np.ndarray = None         # optional [2T-1] structured, 32 B each
     mesh_ranges: np.ndarray = None  # optional [M,6] uint32 (ptc_mesh_range): several distinct meshes, objects[i].index = mesh
+    # image textures (an extension; PathTracer.load_scene_textures sets them): texcoords [3T, 2] float32 parallel to
+    # indices (zeros for a mesh without any; None: no mesh has any); texture_sources: the distinct TextureSource of the materials, and
+    # material_texture [M] int32, -1 or an index into it (None: no material has one)
+    texcoords: np.ndarray = None
+    texture_sources: list = None
+    material_texture: np.ndarray = None
     keepalive: list = field(default_factory=list)
 
     def to_c(self):
@@ -158,6 +180,9 @@ class SceneDescription:
         # smooth shading (an extension): the scene file's "smooth_normals": true -- PathTracer.smooth_normals with
         # compute_vertex_normals' normals is what renders it (the megakernel method)
         self.smooth_normals = False
+        # image textures (an extension): the scene file's "textures": true -- PathTracer.textures with
+        # load_scene_textures is what renders the materials' "texture" entries (the megakernel method)
+        self.textures = False
 
     def add_material(self, name, material):   # scene_description.cpp:150-153 (try_emplace: first one wins)
         self.material_map_.setdefault(name, material)
@@ -185,6 +210,20 @@ class SceneDescription:
         names = sorted(self.material_map_, key=lambda s: s.encode())
         index_of = {n: i for i, n in enumerate(names)}
         materials = np.array([material_record(self.material_map_[n]) for n in names], dtype=MATERIAL_DTYPE)
+        sources, material_texture = [], np.full(len(names), -1, dtype=np.int32)
+        for k, n in enumerate(names):
+            src = getattr(self.material_map_[n], "texture", None)
+            if src is not None:
+                if src not in sources:
+                    sources.append(src)
+                material_texture[k] = sources.index(src)
+        tex = dict(texture_sources=sources, material_texture=material_texture) if sources else {}
+
+        def corners(meshes):  # the scene's per-corner coordinates: zeros for a mesh without any, None when no mesh has any
+            if not any(m.texcoords is not None for m in meshes):
+                return None
+            return np.ascontiguousarray(np.concatenate([m.texcoords if m.texcoords is not None else np.zeros((len(m.indices), 2), np.float32)
+                                                        for m in meshes]), dtype=np.float32)
 
         mesh = None
         if self.mesh_map_:
@@ -230,7 +269,7 @@ class SceneDescription:
                 materials=materials,
                 positions=np.ascontiguousarray(np.concatenate([m.positions for m in distinct]), dtype=np.float32),
                 indices=np.ascontiguousarray(np.concatenate([m.indices for m in distinct]), dtype=np.uint32),
-                mesh_ranges=np.array(ranges, dtype=np.uint32))
+                mesh_ranges=np.array(ranges, dtype=np.uint32), texcoords=corners(distinct), **tex)
         return FlatScene(
             objects=objects,
             object_material_indices=np.array([index_of[n] for n in self.objects_material_mapping_], dtype=np.uint32),
@@ -238,7 +277,7 @@ class SceneDescription:
             materials=materials,
             positions=mesh.positions if mesh is not None else np.zeros((0, 3), dtype=np.float32),
             indices=mesh.indices if mesh is not None else np.zeros((0,), dtype=np.uint32),
-            bvh=prebuilt_bvh)
+            bvh=prebuilt_bvh, texcoords=corners([mesh]) if mesh is not None else None, **tex)
 
 
 def bvh_from_mesh(mesh):

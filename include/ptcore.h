@@ -365,6 +365,14 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *                      parameter combines with it.  Without vertex normals a frame launches what it launched with 0.  Under
  *                      PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is 1, before anything is
  *                      queued.  Counters: ptc_get_smooth_loop_stats.  Any time (queued frames are flushed first)
+ *   "textures"         RENDERING (default 0; an extension): 1 = under PTC_METHOD_MEGAKERNEL, in a scene with textures
+ *                      (ptc_set_textures) and texture coordinates (ptc_set_texcoords), a triangle hit on a diffuse or metal material
+ *                      with a texture bound takes its colour from the texel at the interpolated coordinate, times the material's
+ *                      p[0..2].  Glass and emissive materials and spheres keep p.  Normal, depth and the ray count are those of the
+ *                      same render with 0.  Every other parameter combines with it.  Without textures or without coordinates a
+ *                      frame launches what it launched with 0.  Under PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with
+ *                      PTC_ERR_INVALID while it is 1, before anything is queued.  Counters: ptc_get_texture_loop_stats.  Any time
+ *                      (queued frames are flushed first)
  *   "roulette"         RENDERING (default 0 = off; an extension): k in [1, 64] = Russian roulette at every bounce b >= k
  *                      except the last one, under both methods (and "direct_light").  A path whose closest hit exists and is no emitter
  *                      takes q = the largest component of the throughput that came into the bounce; q >= 1 changes nothing (no draw); else
@@ -753,6 +761,64 @@ typedef struct ptc_smooth_loop_stats {
 } ptc_smooth_loop_stats;
 int ptc_get_smooth_loop_stats(ptc_ctx* ctx, ptc_smooth_loop_stats* out);
 
+/* Image textures ("textures", an extension: the reference's materials have one constant colour).
+ *
+ * A texture: width x height texels of four bytes, r g b a (alpha is carried and ignored), row 0 first, and row 0 is t = 0 -- the
+ * BOTTOM of the picture in OBJ's convention: a file reader flips rows, the core never does.  Each side 1 .. 4096.  encoding: how a
+ * byte becomes a float (ptc_texture_decode_table); filter and wrap: the lookup's (section 5o), wrap on both axes. */
+enum { PTC_TEXTURE_LINEAR = 0, PTC_TEXTURE_SRGB = 1 };
+enum { PTC_TEXTURE_NEAREST = 0, PTC_TEXTURE_BILINEAR = 1 };
+enum { PTC_TEXTURE_REPEAT = 0, PTC_TEXTURE_CLAMP = 1 };
+typedef struct ptc_texture_desc {
+  const uint8_t* rgba8;
+  uint32_t width, height;
+  uint32_t encoding;
+  uint32_t filter;
+  uint32_t wrap;
+} ptc_texture_desc;
+/* ptc_set_textures: the scene's textures and, per material of the uploaded scene, -1 or the texture bound to it
+ * (material_texture[m], material_count entries).  textures NULL / texture_count 0 removes everything (material_texture is not read).
+ * PTC_ERR_NO_SCENE without a scene; PTC_ERR_INVALID (with a message) for a material_count other than the scene's, a binding out of
+ * range, a side outside 1 .. 4096, a NULL texel pointer, an enum value out of range, a pool above 1 GiB; a refusal leaves what was
+ * set in place.  The texels are copied: one device allocation of the scene's holds every texture back to back.  The copy belongs
+ * to the scene: ptc_upload_scene releases it with the scene, and a new scene starts without textures; ptc_resize and the
+ * context's settings do not touch it.  A binding on a glass or an emissive material is accepted and ignored.  Queued frames are
+ * traced first. */
+int ptc_set_textures(ptc_ctx* ctx, const ptc_texture_desc* textures, uint32_t texture_count, const int32_t* material_texture,
+                     uint32_t material_count);
+/* 1, *texture_count and *texel_count (the pool's texels; either may be NULL) while textures are set; 0 and zeros when none are. */
+int ptc_get_textures(const ptc_ctx* ctx, uint32_t* texture_count, uint64_t* texel_count);
+/* ptc_set_texcoords: two floats (s, t) per triangle CORNER, parallel to the uploaded scene's `indices` and covering the whole scene --
+ * a mesh of a mesh table finds its corners at first_index, as its indices do.  Per corner and not per vertex: a seam needs no split
+ * vertices, and positions, indices and BVH stay the caller's.  Any float is accepted (a hit whose interpolated coordinate is not
+ * finite keeps the material's colour).  NULL / 0 removes them.  Refusals and lifetime as ptc_set_vertex_normals', with index_count
+ * in vertex_count's place. */
+int ptc_set_texcoords(ptc_ctx* ctx, const float* st, uint32_t index_count);
+/* 1 and *index_count (may be NULL) = the scene's index count while coordinates are set; 0 and *index_count = 0 when none are. */
+int ptc_get_texcoords(const ptc_ctx* ctx, uint32_t* index_count);
+/* The decode table of an encoding, on the host (no GPU, no context): out[k] for a byte k.  Linear: (float)k / 255.0f, one binary32
+ * division.  sRGB: the piecewise sRGB curve (c / 12.92 up to 0.04045, ((c + 0.055) / 1.055)^2.4 above) evaluated in double and
+ * rounded once.  The device decodes by loading from a copy of these tables.  PTC_ERR_INVALID: a NULL, an unknown encoding. */
+int ptc_texture_decode_table(uint32_t encoding, float* out256);
+/* The lookup of section 5o (steps 2 .. 7) on the device, without rendering: k_texture_sample, one thread per pair.  texture: an index
+ * into what ptc_set_textures set; st: 2 n floats; rgb_out: 3 n floats, zeros where the rule refuses the pair (a NaN or an infinity);
+ * rejected_out (may be NULL): one byte a pair, 1 where it did.  Host pointers.  PTC_ERR_INVALID without textures or for an index
+ * out of range. */
+int ptc_sample_texture(ptc_ctx* ctx, uint32_t texture, const float* st, uint32_t n, float* rgb_out, uint8_t* rejected_out);
+/* Per ray (8 floats, as for ptc_intersect_rays) at the closest hit: st_out (2 floats) = the interpolated texture coordinate of a
+ * triangle hit while coordinates are set (zeros for a sphere, on a miss and without coordinates); albedo_out (3 floats) = the colour
+ * the megakernel's loop would shade with there under "textures" 1 -- texel x p[0..2] where the rule applies (textures and coordinates
+ * set, a triangle, a diffuse or metal material with a binding, a finite coordinate), else the material's p[0..2]; zeros on a miss.
+ * ptc_hit_attributes' walk, one thread per ray; host pointers. */
+int ptc_hit_surface(ptc_ctx* ctx, const float* rays, uint32_t n, float* st_out, float* albedo_out);
+/* The megakernel under "textures" 1 with textures and coordinates set, since ptc_restart: texel lookups made (one per textured hit
+ * that reached evaluate_material, whatever the filter), and hits that fell back to the material's colour because the interpolated
+ * coordinate was not finite.  Synchronises.  Moves nothing else, and nothing moves it but ptc_trace and ptc_restart. */
+typedef struct ptc_texture_loop_stats {
+  uint64_t lookups, fallbacks;
+} ptc_texture_loop_stats;
+int ptc_get_texture_loop_stats(ptc_ctx* ctx, ptc_texture_loop_stats* out);
+
 /* Where the time of the last ptc_upload_scene went (milliseconds of host wall clock; the "Initialization" stage of
  * the reference's Stopwatch, cli.cpp): */
 typedef struct ptc_upload_times {
@@ -869,6 +935,10 @@ int ptc_check_environment_light_table(const float* rgb, uint32_t n, void* entrie
  * computes it).  ns_out: 3 floats a case; fallback_out (may be NULL): 1 where the rule fell back to g. */
 int ptc_check_shading_normal(const float* n0, const float* n1, const float* n2, const float* u, const float* v, const float* g, const float* d,
                              const float* m16, uint32_t count, float* ns_out, uint8_t* fallback_out);
+/* The texture lookup of section 5o (csrc/pt_texture.hpp, the header the textured kernels run on the device; steps 2 .. 7) on the
+ * host: no GPU, no context; the host twin of ptc_sample_texture.  desc: one texture; st: 2 n floats; rgb_out: 3 n floats;
+ * rejected_out (may be NULL): one byte a pair.  PTC_ERR_INVALID: a NULL, a texture ptc_set_textures would refuse. */
+int ptc_check_texture_lookup(const ptc_texture_desc* desc, const float* st, uint32_t n, float* rgb_out, uint8_t* rejected_out);
 /* ... and the sample on `count` caller-given points, normals and draws (v[i]: a raw value 1 .. 2^31 - 2; u + 3 i: u1, u2, u3), written as
  * ptc_environment_light writes a sample whose shadow ray is free: radiance 3 floats, shadow_rays 8 floats (may be NULL), sampled one
  * byte (may be NULL) per point.  PTC_ERR_INVALID: a NULL, n out of range, a bad component, a v out of range. */

@@ -1,0 +1,539 @@
+"""Image textures on the GPU (ptc_set_textures, ptc_set_texcoords, ptc_set_param "textures", ptc_sample_texture, ptc_hit_surface; DESIGN
+section 5o): the lookup query, the surface query and the megakernel's textured instances against the numpy restatement
+tests/texture_ref.py, bit for bit; two anchors that need no restatement; what textures and coordinates are tied to (the scene) and what
+they must leave alone; the cases in which the parameter must change nothing."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import env_light_ref
+import smooth_ref
+import texture_ref
+
+pytestmark = pytest.mark.gpu
+
+PLANES = ("color", "normal", "depth")
+OLD = ("diffuse_hits", "shadow_rays", "unoccluded", "env_diffuse_hits", "env_shadow_rays", "env_unoccluded", "mis_emitter_hits", "mis_misses")
+EVERYTHING = PLANES + ("rays",) + OLD + smooth_ref.COUNTERS + texture_ref.COUNTERS
+W, H, ITERS = 33, 17, 2
+LENS = (0.25, 3.5)
+ENV = smooth_ref.ENV
+FLT_MAX = np.float32(np.finfo(np.float32).max)
+_cache = {}
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _entries(pkg):
+    if "entries" not in _cache:
+        _cache["entries"] = env_light_ref.table_of(pkg, ENV)[0]
+    return _cache["entries"]
+
+
+# name -> (the scene, {material: texture of texture_ref.pool})
+SCENES = {
+    "room": (lambda pkg: smooth_ref.room_scene(pkg), {"ball": 0, "ball2": 2, "walls": 1}),
+    "sheet": (lambda pkg: smooth_ref.sheet_scene(pkg), {"sheet": 0, "diffuse": 2, "floor": 1}),  # (the floor is a sphere: no coordinates)
+    "lamp": (lambda pkg: smooth_ref.sheet_scene(pkg, ("lamp", "diffuse")), {"sheet": 0, "diffuse": 1, "lamp": 2}),
+    "metal": (lambda pkg: smooth_ref.sheet_scene(pkg, ("metal", "diffuse")), {"metal": 2, "diffuse": 0}),
+    "ignored": (lambda pkg: smooth_ref.sheet_scene(pkg, ("glass", "lamp")), {"glass": 0, "lamp": 1, "sheet": 2}),
+}
+
+
+def _scene(pkg, name):
+    """name -> dict(scene, flat, textures, binding, st, nrm), built once"""
+    if name not in _cache:
+        scene = SCENES[name][0](pkg)
+        flat = scene.build_scene(distinct_meshes=True)
+        _cache[name] = dict(scene=scene, flat=flat, textures=texture_ref.pool(pkg), binding=texture_ref.bind(scene, flat, SCENES[name][1]),
+                            st=texture_ref.random_texcoords(flat), nrm=pkg.compute_vertex_normals(flat))
+    return _cache[name]
+
+
+def _tracer(pkg, flat, w=W, h=H, mb=8, mega=True, textured=True, table=None, st=None, smooth=False, normals=None, mis=False, env_light=False,
+            direct=False, roulette=0, lens=None, interleave=None):
+    pt = pkg.PathTracer(device=0, max_bounces=mb)
+    if mega:
+        pt.current_gpu_method = pkg.GPUMethod.megakernel
+    pt.textures = textured
+    pt.smooth_normals = smooth
+    pt.mis = mis
+    pt.environment_light = env_light
+    pt.direct_light = direct
+    pt.roulette = roulette
+    if lens is not None:
+        pt.lens = lens
+    pt.create_buffers((w, h), flat)
+    if table is not None:
+        pt.texture_table = table
+    if st is not None:
+        pt.texcoords = st
+    if normals is not None:
+        pt.vertex_normals = normals
+    if interleave is not None:
+        pt.set_interleave(*interleave)
+    return pt
+
+
+def _result(pt):
+    out = {p: pt.download(p) for p in PLANES}
+    out["rays"] = pt.stats()["rays_total"]
+    out.update(pt.direct_loop_stats())
+    out.update({"env_" + k: v for k, v in pt.environment_light_loop_stats().items()})
+    st = pt.mis_loop_stats()
+    out.update({"mis_emitter_hits": st["weighted_emitter_hits"], "mis_misses": st["weighted_misses"]})
+    out.update(pt.smooth_loop_stats())
+    st = pt.texture_loop_stats()
+    out.update({"lookups": st["lookups"], "tex_fallbacks": st["fallbacks"]})
+    return out
+
+
+def _run(pt, camera, env, iters=ITERS, iter_begin=0):
+    pt.environment = env
+    pt.restart()
+    if iter_begin:
+        pt.set_iteration(iter_begin)
+    pt.max_iterations = iter_begin + iters
+    rays0 = pt.stats()["rays_total"]
+    for _ in range(iters):
+        pt.path_trace(camera)
+    out = _result(pt)
+    out["rays"] -= rays0
+    return out
+
+
+def _same(got, ref, keys, what):
+    for k in keys:
+        if k in PLANES:
+            a, b = _bits(got[k]), _bits(np.asarray(ref[k], dtype=np.float32).reshape(got[k].shape))
+            assert np.array_equal(a, b), (what, k, int(np.sum(a != b)), np.argwhere(a != b)[:4].tolist())
+        else:
+            assert got[k] == ref[k], (what, k, got[k], ref[k])
+
+
+def _against_the_loop(pkg, orc, scene_name, w=W, h=H, mb=8, env=None, iters=ITERS, iter_begin=0, st=None, smooth=False, **kw):
+    s = _scene(pkg, scene_name)
+    st = s["st"] if st is None else st
+    entries = _entries(pkg) if env is not None else None
+    ref = texture_ref.render_megakernel(pkg, orc, s["flat"], s["scene"].camera, w, h, iter_begin, iters, mb, textures=s["textures"],
+                                        binding=s["binding"], texcoords=st, textured=True, normals=s["nrm"] if smooth else None, smooth=smooth,
+                                        env=env, entries=entries, env_light=kw.get("env_light", False), direct=kw.get("direct", False),
+                                        mis=kw.get("mis", False), roulette=kw.get("roulette", 0), lens=kw.get("lens"))
+    with _tracer(pkg, s["flat"], w, h, mb, table=(s["textures"], s["binding"]), st=st, smooth=smooth, normals=s["nrm"] if smooth else None, **kw) as pt:
+        got = _run(pt, s["scene"].camera, env, iters, iter_begin)
+    _same(got, ref, EVERYTHING, (scene_name, w, h, mb, kw, iter_begin))
+    return got
+
+
+# ---- 1. the lookup query ---------------------------------------------------------------------------------------------------------------
+def test_sample_texture_over_a_pool_of_three(pkg):
+    """each texture of a pool of three sizes on the CPU test's coordinate set: an offset bug shows on the second and third"""
+    s = _scene(pkg, "sheet")
+    with _tracer(pkg, s["flat"], table=(s["textures"], s["binding"])) as pt:
+        for ti, tex in enumerate(s["textures"]):
+            st = texture_ref.coordinate_set(tex.width, tex.height)
+            got, rej = pt.sample_texture(ti, st)
+            want, wrej = texture_ref.lookup(pkg, tex, st)
+            bad = np.argwhere(_bits(got) != _bits(want))
+            assert len(bad) == 0, (ti, st[bad[:4, 0]].tolist(), got[bad[:4, 0]].tolist(), want[bad[:4, 0]].tolist())
+            assert np.array_equal(rej, wrej) and rej.sum() > 0 and not got[rej].any()
+            host, hrej = pkg.check_texture_lookup(tex, st)
+            assert np.array_equal(_bits(got), _bits(host)) and np.array_equal(rej, hrej)
+        with pytest.raises(pkg.PtcError):
+            pt.sample_texture(3, np.zeros((1, 2), np.float32))
+        pt.texture_table = None
+        with pytest.raises(pkg.PtcError):
+            pt.sample_texture(0, np.zeros((1, 2), np.float32))
+
+
+@pytest.mark.parametrize("width,height", [(4096, 2), (2, 4096), (1, 1)])
+def test_sample_texture_at_the_size_limits(pkg, width, height):
+    s = _scene(pkg, "sheet")
+    st = texture_ref.coordinate_set(width, height)
+    for k, (filt, wrap, enc) in enumerate((f, w, e) for f in ("nearest", "bilinear") for w in ("repeat", "clamp") for e in ("linear", "srgb")):
+        tex = texture_ref.random_texture(pkg, width, height, 100 + k, encoding=enc, filter=filt, wrap=wrap)
+        with _tracer(pkg, s["flat"], table=([s["textures"][0], tex], s["binding"] * 0 - 1)) as pt:
+            got, rej = pt.sample_texture(1, st)
+        want, wrej = texture_ref.lookup(pkg, tex, st)
+        assert np.array_equal(_bits(got), _bits(want)) and np.array_equal(rej, wrej), (filt, wrap, enc)
+
+
+# ---- 2. the surface query ----------------------------------------------------------------------------------------------------------------
+def _rays(o, d, tmin=1e-4, tmax=FLT_MAX):
+    o, d = np.asarray(o, dtype=np.float32).reshape(-1, 3), np.asarray(d, dtype=np.float32).reshape(-1, 3)
+    r = np.zeros((len(o), 8), dtype=np.float32)
+    r[:, 0:3], r[:, 3], r[:, 4:7], r[:, 7] = o, tmin, d, tmax
+    return r
+
+
+def _surface(pkg, orc, flat, rays, textures, binding, st):
+    want = texture_ref.hit_surface(pkg, orc, flat, rays, textures, binding, st)
+    with _tracer(pkg, flat, mega=False, textured=False, table=None if textures is None else (textures, binding), st=st) as pt:
+        got = pt.hit_surface(rays)
+    for k in ("st", "albedo"):
+        assert np.array_equal(_bits(got[k]), _bits(want[k])), (k, np.argwhere(_bits(got[k]) != _bits(want[k]))[:4].tolist())
+    return got
+
+
+@pytest.mark.parametrize("what", ["everything", "coordinates_alone", "nothing"])
+def test_hit_surface_random_rays(pkg, orc, what):
+    """4099 rays (no multiple of 64) from around a two-mesh table whose second mesh starts at first_index > 0, with a sphere object: hits
+    on both meshes and both instances, on the sphere (no coordinates: the material's colour), and misses (zeros)"""
+    s = _scene(pkg, "sheet")
+    flat = s["flat"]
+    assert smooth_ref.mesh_rows(flat)[1][2] > 0
+    rng = np.random.default_rng(3)
+    k = 4099
+    o = (rng.standard_normal((k, 3)) * 0.2 + [0.0, 1.5, 2.5]).astype(np.float32)
+    at = rng.uniform([-1.4, -0.8, -1.5], [1.4, 0.8, 1.0], (k, 3))
+    d = at - o
+    d = (d / np.linalg.norm(d, axis=1)[:, None]).astype(np.float32)
+    d[::9] = -d[::9]  # away from everything
+    rays = _rays(o, d)
+    rays[5::11, 7] = 2.0  # a t_max of the caller's that cuts some hits off
+    got = _surface(pkg, orc, flat, rays, s["textures"] if what == "everything" else None, s["binding"],
+                   None if what == "nothing" else s["st"])
+    plain = np.asarray(flat.materials)["p"][:, :3]
+    is_plain = (got["albedo"][:, None, :] == plain[None, :, :]).all(axis=2).any(axis=1)
+    miss = ~got["albedo"].any(axis=1)
+    assert miss.sum() > 400 and not got["st"][miss].any()
+    if what == "everything":
+        assert (~is_plain & ~miss).sum() > 300 and (is_plain & ~miss).sum() > 100  # textured triangles; the floor sphere keeps its colour
+    else:
+        assert (is_plain | miss).all() and got["st"].any() == (what == "coordinates_alone")
+
+
+def test_hit_surface_on_a_seam(pkg, orc):
+    """rays aimed at the shared edges and the shared vertices of a 2 x 2-quad sheet whose two triangles per quad carry different corner
+    coordinates: the winner's corners are the ones interpolated (ties: the triangle the walk visits last)"""
+    glm = pkg.glmlite
+    s = pkg.SceneDescription()
+    s.add_material("a", pkg.DiffuseMateral((0.5, 0.75, 0.25)))
+    pos, idx = smooth_ref.sheet(2, 2, size=2.0)
+    s.add_object(s.add_mesh("sheet.obj", pkg.Mesh(pos, idx)), glm.identity(), "a")
+    flat = s.build_scene(distinct_meshes=True)
+    st = np.zeros((len(idx), 2), np.float32)
+    tri = np.arange(len(idx)) // 3
+    st[:, 0] = tri * 0.125 + (np.arange(len(idx)) % 3) * 0.03125  # every triangle a band of s of its own: dyadic, no two corners alike
+    st[:, 1] = np.where(tri % 2 == 0, 0.25, 0.75) + (np.arange(len(idx)) % 3) * 0.0625
+    targets = [(x, 0.0, z) for x in (-1.0, -0.5, 0.0, 0.5, 1.0) for z in (-1.0, -0.5, 0.0, 0.5, 1.0)]  # vertices, edge midpoints, diagonals
+    targets += [(0.25, 0.0, -0.25), (-0.25, 0.0, 0.25), (0.3, 0.0, 0.1), (3.0, 0.0, 3.0)]
+    d = np.float32([0.5, -1.0, 0.25])  # dyadic numbers throughout: two triangles that share the target give the same t
+    o = np.float32([(x - 1.0, y + 2.0, z - 0.5) for x, y, z in targets])
+    tex = [texture_ref.random_texture(pkg, 8, 8, 21, encoding="linear", filter="nearest", wrap="repeat")]
+    got = _surface(pkg, orc, flat, _rays(o, np.tile(d, (len(o), 1))), tex, np.zeros(1, np.int32), st)
+    bands = np.floor(got["st"][:-1, 0] / 0.125).astype(int)
+    assert len(set(bands.tolist())) == 8 and not got["st"][-1].any() and not got["albedo"][-1].any()  # all eight triangles win somewhere
+
+
+# ---- 3. frames against the restatement ------------------------------------------------------------------------------------------------
+SIZES = [(w, h, mb) for w, h in ((33, 17), (65, 33)) for mb in (1, 2, 8)]
+
+
+@pytest.mark.parametrize("w,h,mb", SIZES)
+def test_the_lamp_lit_room(pkg, orc, w, h, mb):
+    """a textured diffuse mesh and its scaled, rotated instance (and the room's walls) under "direct_light" """
+    got = _against_the_loop(pkg, orc, "room", w, h, mb, direct=True)
+    assert got["lookups"] > 0 and got["shadow_rays"] > 0
+
+
+@pytest.mark.parametrize("w,h,mb", SIZES)
+def test_a_sheet_under_the_sky(pkg, orc, w, h, mb):
+    got = _against_the_loop(pkg, orc, "sheet", w, h, mb, env=ENV, env_light=True)
+    assert got["lookups"] > 0 and got["env_shadow_rays"] > 0
+
+
+@pytest.mark.parametrize("w,h,mb", SIZES)
+@pytest.mark.parametrize("smooth", [False, True])
+def test_both_lights_with_mis(pkg, orc, w, h, mb, smooth):
+    got = _against_the_loop(pkg, orc, "lamp", w, h, mb, env=ENV, env_light=True, direct=True, mis=True, smooth=smooth)
+    assert got["lookups"] > 0 and (got["shading_normals"] > 0) == smooth and (got["mis_misses"] > 0 or mb == 1)
+
+
+@pytest.mark.parametrize("w,h,mb", SIZES)
+@pytest.mark.parametrize("smooth", [False, True])
+def test_a_metal_mesh(pkg, orc, w, h, mb, smooth):
+    got = _against_the_loop(pkg, orc, "metal", w, h, mb, env=ENV, smooth=smooth)
+    assert got["lookups"] > 0
+
+
+@pytest.mark.parametrize("w,h,mb", SIZES)
+def test_a_binding_on_glass_and_on_an_emitter_is_ignored(pkg, orc, w, h, mb):
+    got = _against_the_loop(pkg, orc, "ignored", w, h, mb, env=ENV, direct=True)
+    s = _scene(pkg, "ignored")
+    with _tracer(pkg, s["flat"], w, h, mb, table=(s["textures"], texture_ref.bind(s["scene"], s["flat"], {"sheet": 2})), st=s["st"], direct=True) as pt:
+        unbound = _run(pt, s["scene"].camera, ENV)
+    _same(got, unbound, EVERYTHING, "ignored")
+
+
+@pytest.mark.parametrize("w,h,mb", SIZES)
+def test_nan_and_infinite_coordinates_fall_back(pkg, orc, w, h, mb):
+    bad = _scene(pkg, "sheet")["st"].copy()
+    bad[::7, 0] = np.nan
+    bad[3::11, 1] = np.inf
+    bad[5::13, 0] = -np.inf
+    got = _against_the_loop(pkg, orc, "sheet", w, h, mb, env=ENV, env_light=True, st=bad)
+    assert got["tex_fallbacks"] > 0 and got["lookups"] > 0
+
+
+@pytest.mark.parametrize("w,h,mb", SIZES)
+def test_roulette_under_the_lens(pkg, orc, w, h, mb):
+    _against_the_loop(pkg, orc, "room", w, h, mb, direct=True, roulette=1, lens=LENS)
+
+
+@pytest.mark.parametrize("w,h,mb", SIZES)
+def test_iteration_2_31_minus_5(pkg, orc, w, h, mb):
+    _against_the_loop(pkg, orc, "sheet", w, h, mb, iters=2, iter_begin=2 ** 31 - 5, env=ENV, env_light=True)
+
+
+def test_plain_without_any_light(pkg, orc):
+    _against_the_loop(pkg, orc, "sheet", mb=4)
+
+
+@pytest.mark.parametrize("w,h,mb", SIZES)
+def test_two_interleaved_ranks_against_the_one_context_frame(pkg, w, h, mb):
+    s = _scene(pkg, "sheet")
+    kw = dict(table=(s["textures"], s["binding"]), st=s["st"], env_light=True)
+    with _tracer(pkg, s["flat"], w, h, mb, **kw) as pt:
+        one = _run(pt, s["scene"].camera, ENV)
+    parts = []
+    for rank in (0, 1):
+        with _tracer(pkg, s["flat"], w, h, mb, interleave=(rank, 2, 8), **kw) as pt:
+            parts.append(_run(pt, s["scene"].camera, ENV))
+        rows = [r for first in range(rank * 8, h, 16) for r in range(first, min(first + 8, h))]
+        for p in PLANES:
+            assert np.array_equal(_bits(parts[-1][p].reshape(len(rows), w, -1)), _bits(one[p].reshape(h, w, -1)[rows])), (rank, p)
+    for k in ("rays",) + OLD + smooth_ref.COUNTERS + texture_ref.COUNTERS:
+        assert parts[0][k] + parts[1][k] == one[k], k
+    assert one["lookups"] > 0
+
+
+# ---- 4. anchors that need no restatement -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mis,smooth", [(False, False), (True, True)])
+def test_white_texels_give_the_bits_of_textures_0(pkg, mis, smooth):
+    """nearest, linear, every texel (255, 255, 255, .): the factor is 1.0f"""
+    s = _scene(pkg, "lamp")
+    texels = np.full((3, 5, 4), 255, np.uint8)
+    texels[..., 3] = np.arange(15).reshape(3, 5)  # alpha is carried and ignored
+    white = [pkg.Texture(texels, "linear", "nearest", "repeat")] * 3
+    kw = dict(table=(white, s["binding"]), st=s["st"], env_light=True, direct=True, mis=mis, smooth=smooth, normals=s["nrm"])
+    with _tracer(pkg, s["flat"], textured=False, **kw) as pt:
+        want = _run(pt, s["scene"].camera, ENV)
+    with _tracer(pkg, s["flat"], textured=True, **kw) as pt:
+        got = _run(pt, s["scene"].camera, ENV)
+    _same(got, want, PLANES + ("rays",) + OLD + smooth_ref.COUNTERS, "white")
+    assert got["lookups"] > 0 and want["lookups"] == 0
+
+
+@pytest.mark.parametrize("encoding", ["linear", "srgb"])
+def test_constant_texels_give_the_bits_of_a_darker_material(pkg, encoding):
+    """nearest, every texel the byte c: the frame of the untextured scene whose bound materials' colours are p table[c], in binary32"""
+    c = 173
+    s = _scene(pkg, "metal")
+    tex = [pkg.Texture(np.full((2, 3, 4), c, np.uint8), encoding, "nearest", "clamp")] * 3
+    with _tracer(pkg, s["flat"], table=(tex, s["binding"]), st=s["st"], env_light=True) as pt:
+        got = _run(pt, s["scene"].camera, ENV)
+    darker = s["scene"].build_scene(distinct_meshes=True)
+    factor = pkg.texture_decode_table(encoding)[c]
+    for m in np.nonzero(s["binding"] >= 0)[0]:
+        darker.materials["p"][m, :3] = darker.materials["p"][m, :3].astype(np.float32) * factor
+    with _tracer(pkg, darker, textured=False, env_light=True) as pt:
+        want = _run(pt, s["scene"].camera, ENV)
+    _same(got, want, PLANES + ("rays",) + OLD, encoding)
+    assert got["lookups"] > 0
+
+
+# ---- 5. the cases that must render the parent's bits -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("mis", [False, True])
+@pytest.mark.parametrize("smooth", [False, True])
+def test_the_bits_of_the_parent(pkg, mis, smooth):
+    """ "textures" 1 with every material unbound, "textures" 1 without coordinates and "textures" 0 with everything set render what a
+    context that never heard of textures renders"""
+    s = _scene(pkg, "lamp")
+    kw = dict(env_light=True, direct=True, mis=mis, smooth=smooth, normals=s["nrm"], roulette=2)
+    with _tracer(pkg, s["flat"], textured=False, **kw) as pt:
+        want = _run(pt, s["scene"].camera, ENV)
+    unbound = np.full(len(s["binding"]), -1, np.int32)
+    cases = {"unbound": dict(textured=True, table=(s["textures"], unbound), st=s["st"]),
+             "no_coordinates": dict(textured=True, table=(s["textures"], s["binding"])),
+             "no_textures": dict(textured=True, st=s["st"]),
+             "off": dict(textured=False, table=(s["textures"], s["binding"]), st=s["st"])}
+    for name, tx in cases.items():
+        with _tracer(pkg, s["flat"], **tx, **kw) as pt:
+            got = _run(pt, s["scene"].camera, ENV)
+        _same(got, want, EVERYTHING, (name, mis, smooth))
+        assert got["lookups"] == 0 and got["tex_fallbacks"] == 0
+
+
+# ---- 6. what textures and coordinates are tied to --------------------------------------------------------------------------------------
+def test_textures_set_changed_and_removed(pkg, orc):
+    """set, trace 2; another pool and binding, trace 2; none, trace 2; other coordinates with the first pool, trace 2: the restatement
+    continued with prev="""
+    s = _scene(pkg, "sheet")
+    flat, cam = s["flat"], s["scene"].camera
+    other = [s["textures"][2], s["textures"][0]]
+    other_binding = texture_ref.bind(s["scene"], flat, {"sheet": 1, "diffuse": 0})
+    other_st = np.ascontiguousarray(s["st"][::-1])
+    steps = [((s["textures"], s["binding"]), s["st"]), ((other, other_binding), s["st"]), (None, s["st"]), ((s["textures"], s["binding"]), other_st)]
+    ref = None
+    for k, (table, st) in enumerate(steps):
+        ref = texture_ref.render_megakernel(pkg, orc, flat, cam, W, H, 2 * k, 2, 4, textures=table[0] if table else None,
+                                            binding=table[1] if table else None, texcoords=st, textured=True, prev=ref)
+    with _tracer(pkg, flat, mb=4) as pt:
+        pt.max_iterations = 8
+        for table, st in steps:
+            pt.texture_table = table
+            pt.texcoords = st
+            count, texels = C.c_uint32(9), C.c_uint64(9)
+            assert pt._lib.ptc_get_textures(pt._ctx, C.byref(count), C.byref(texels)) == (1 if table else 0)
+            assert count.value == (len(table[0]) if table else 0) and texels.value == (sum(t.width * t.height for t in table[0]) if table else 0)
+            pt.path_trace(cam)
+            pt.path_trace(cam)
+        _same(_result(pt), ref, PLANES, "changed")
+
+
+def test_an_upload_drops_them_and_a_resize_and_refusals_keep_them(pkg):
+    s = _scene(pkg, "sheet")
+    flat, textures, binding, st = s["flat"], s["textures"], s["binding"], s["st"]
+    with _tracer(pkg, flat, mb=4, table=(textures, binding), st=st) as pt:
+        lib, ctx = pt._lib, pt._ctx
+        count = C.c_uint32(0)
+        assert lib.ptc_get_textures(ctx, C.byref(count), None) == 1 and count.value == 3
+        assert lib.ptc_get_texcoords(ctx, C.byref(count)) == 1 and count.value == len(flat.indices)
+        refusals = [(textures, binding[:-1], "materials"),  # a material_count other than the scene's
+                    (textures, np.where(binding == 2, 3, binding), "bound to texture 3"),
+                    (textures, np.where(binding == 2, -2, binding), "bound to texture -2"),
+                    ([pkg.Texture(np.zeros((1, 1, 4), np.uint8), encoding=2)], binding * 0 - 1, "encoding"),
+                    ([pkg.Texture(np.zeros((1, 1, 4), np.uint8), filter=2)], binding * 0 - 1, "filter"),
+                    ([pkg.Texture(np.zeros((1, 1, 4), np.uint8), wrap=2)], binding * 0 - 1, "wrap"),
+                    ([pkg.Texture(np.zeros((1, 4097, 4), np.uint8))], binding * 0 - 1, "4097")]
+        for tex, b, word in refusals:
+            with pytest.raises(pkg.PtcError) as e:
+                pt.texture_table = (tex, b)
+            assert e.value.code == pkg._capi.PTC_ERR_INVALID and word in str(e.value), (word, str(e.value))
+        d = textures[0]._desc()
+        d.rgba8 = None
+        b = np.ascontiguousarray(binding * 0 - 1, dtype=np.int32)
+        assert lib.ptc_set_textures(ctx, C.byref(d), 1, b.ctypes.data_as(C.c_void_p), len(b)) == pkg._capi.PTC_ERR_INVALID
+        d = textures[0]._desc()
+        assert lib.ptc_set_textures(ctx, C.byref(d), 0, b.ctypes.data_as(C.c_void_p), len(b)) == pkg._capi.PTC_ERR_INVALID  # not NULL with 0
+        with pytest.raises(pkg.PtcError) as e:
+            pt.texcoords = st[:-1]
+        assert "corners" in str(e.value)
+        assert lib.ptc_get_textures(ctx, C.byref(count), None) == 1 and count.value == 3 and pt.texture_table is not None
+        assert lib.ptc_get_texcoords(ctx, None) == 1 and pt.texcoords is not None
+        before = _run(pt, s["scene"].camera, None)  # ... and what was set still renders
+        assert before["lookups"] > 0
+        pt.resize_image((W + 2, H))  # a resize does not touch them
+        assert lib.ptc_get_textures(ctx, None, None) == 1 and lib.ptc_get_texcoords(ctx, None) == 1
+        pt.create_buffers((W, H), flat)
+        assert lib.ptc_get_textures(ctx, C.byref(count), None) == 0 and count.value == 0 and pt.texture_table is None
+        assert lib.ptc_get_texcoords(ctx, C.byref(count)) == 0 and count.value == 0 and pt.texcoords is None
+        after = _run(pt, s["scene"].camera, None)
+        assert after["lookups"] == 0
+    with pkg.PathTracer(device=0) as pt:
+        for assign in (lambda: setattr(pt, "texture_table", (textures, binding)), lambda: setattr(pt, "texcoords", st)):
+            with pytest.raises(pkg.PtcError) as e:
+                assign()
+            assert e.value.code == pkg._capi.PTC_ERR_NO_SCENE
+
+
+def test_a_pool_above_one_gib_is_refused(pkg):
+    """65 textures of 4096 x 4096 texels are 1 GiB + 64 MiB: refused from the sizes alone, before a texel is read (they share one
+    read-only 64 MiB array here, of which nothing is copied)"""
+    s = _scene(pkg, "sheet")
+    big = pkg.Texture(np.broadcast_to(np.zeros((1, 1, 4), np.uint8), (4096, 4096, 4)))
+    with _tracer(pkg, s["flat"], table=(s["textures"], s["binding"])) as pt:
+        with pytest.raises(pkg.PtcError) as e:
+            pt.texture_table = ([big] * 65, s["binding"] * 0 - 1)
+        assert "1 GiB" in str(e.value) and pt._lib.ptc_get_textures(pt._ctx, None, None) == 1
+
+
+def test_the_streaming_loop_refuses_and_queues_nothing(pkg):
+    s = _scene(pkg, "sheet")
+    with _tracer(pkg, s["flat"], mega=False, table=(s["textures"], s["binding"]), st=s["st"]) as pt:
+        pt.max_iterations = 4
+        for _ in range(2):
+            with pytest.raises(pkg._capi.PtcError) as e:
+                pt.path_trace(s["scene"].camera)
+            assert e.value.code == pkg._capi.PTC_ERR_INVALID and "textures are rendered by the megakernel" in str(e.value)
+        cam = pkg._capi.ptc_camera()
+        assert pt._lib.ptc_trace_begin(pt._ctx, C.byref(cam)) == pkg._capi.PTC_ERR_INVALID
+        assert pt.iteration() == 0 and pt.stats()["rays_total"] == 0 and pt.stats()["frames"] == 0
+        pt.textures = False  # and without it the context renders as ever
+        pt.path_trace(s["scene"].camera)
+        assert pt.iteration() == 1 and pt.stats()["rays_total"] > 0
+    with pkg.PathTracer(device=0) as pt:
+        for bad in (-1, 2):
+            with pytest.raises(pkg._capi.PtcError) as e:
+                pt.set_param("textures", bad)
+            assert "textures must be 0 or 1" in str(e.value)
+
+
+# ---- 7. the command line ----------------------------------------------------------------------------------------------------------------
+import json  # noqa: E402
+import os  # noqa: E402
+import struct  # noqa: E402
+import subprocess  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIP_PT = os.path.join(ROOT, "cuda-path-tracer_amd", "host", "hip_pt")
+ASSET = os.path.join(ROOT, "assets", "scenes", "cornell_textured.json")
+
+
+def _read_raw(path):
+    data = open(path, "rb").read()
+    assert data[:4] == b"PTRF"
+    w, h, ch = struct.unpack_from("<III", data, 4)
+    assert ch == 7 and len(data) == 16 + 4 * 7 * w * h
+    f = np.frombuffer(data, dtype="<f4", offset=16)
+    P = w * h
+    return {"color": f[:3 * P].reshape(h, w, 3), "normal": f[3 * P:6 * P].reshape(h, w, 3), "depth": f[6 * P:].reshape(h, w)}
+
+
+def _asset_reference(pkg, orc):
+    """the restatement of assets/scenes/cornell_textured.json with the Python reader's textures and coordinates, once for the three runs"""
+    if "asset" not in _cache:
+        scene = pkg.json_parser.scene_from_json(ASSET)
+        assert scene.textures is True
+        flat = scene.build_scene()
+        w, h = scene.resolution
+        textures = [pkg.Texture(pkg.png.read_png(s.file), s.encoding, s.filter, s.wrap) for s in flat.texture_sources]
+        _cache["asset"] = texture_ref.render_megakernel(pkg, orc, flat, scene.camera, w, h, 0, 1, 2, textures=textures, binding=flat.material_texture,
+                                                        texcoords=flat.texcoords, textured=True)
+        assert _cache["asset"]["lookups"] > 1000  # (what a run that ignored the option would not reproduce)
+    return _cache["asset"]
+
+
+@pytest.mark.parametrize("how", ["flag", "scene_key", "two_ranks"])
+def test_hip_pt_textures_against_the_restatement(pkg, orc, tmp_path, how):
+    """hip_pt --method megakernel with --textures (on the asset without its "textures" key), with the scene key, and over two ranks: the
+    float framebuffers the run dumps are the restatement's"""
+    if not os.path.exists(HIP_PT):
+        subprocess.run(["make"], cwd=os.path.dirname(HIP_PT), check=True, stdout=subprocess.DEVNULL)
+    want = _asset_reference(pkg, orc)
+    scene_file, extra = ASSET, []
+    if how == "flag":  # the same scene beside the asset's folder tree, its files named from there, without the key
+        with open(ASSET) as f:
+            j = json.load(f)
+        del j["textures"]
+        for s in j["surfaces"]:
+            if "filename" in s:
+                s["filename"] = os.path.relpath(os.path.join(os.path.dirname(ASSET), s["filename"]), str(tmp_path))
+        for m in j["materials"]:
+            if "texture" in m:
+                m["texture"]["file"] = os.path.relpath(os.path.join(os.path.dirname(ASSET), m["texture"]["file"]), str(tmp_path))
+        scene_file = str(tmp_path / "no_key.json")
+        with open(scene_file, "w") as f:
+            json.dump(j, f)
+        extra = ["--textures"]
+    if how == "two_ranks":
+        extra = ["--gpus", "2"]
+    raw = tmp_path / "out.raw"
+    cmd = [HIP_PT, scene_file, "-o", str(tmp_path / "out.png"), "--spp", "1", "--max-bounces", "2", "--dump-raw", str(raw), "--method", "megakernel"] + extra
+    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout + r.stderr
+    _same(_read_raw(raw), want, PLANES, how)
