@@ -237,6 +237,7 @@ SIGNATURES = {
     "ptc_debug_persist": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint64]),
     "ptc_check_feed": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "ptc_check_frame_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ptc_frame_plan)]),
+    "ptc_check_megakernel_instance": (C.c_int, [C.c_int] * 11 + [C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]),
     "ptc_selftest_math": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ptc_selftest_rng": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -10,6 +10,7 @@
 #include "../../include/ptcore.h"
 #include "pt_math.hpp"
 #include "pt_env.hpp"
+#include "pt_smooth.hpp"
 #include "pt_texture.hpp"
 
 namespace pt {
@@ -467,21 +468,78 @@ void launch_accumulate(hipStream_t s, DFrame stage, DFrame fb, uint32_t pix_coun
 void launch_persist(hipStream_t s, const DScene& scene, uint32_t obj_index, DHits hits, DeviceCounters* counters, const DBatchInfo& bi,
                     const DPersistArgs& pa, uint32_t waves, bool spheres, bool listed0, bool emitters = false);
 uint32_t persist_tiles_per_frame(uint32_t max_paths);
-void launch_megakernel(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band,
-                       uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters = false);
-// ... for a frame with a bounce that plays Russian roulette (1 <= roulette < max_bounces - 1, the caller's check)
-void launch_megakernel_roulette(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
-                                int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette);
-// ... for a frame under a thin lens (lens.radius > 0, the caller's check): the plain loop or, when some bounce
-// plays (roulette: the context's parameter; 1 <= roulette < max_bounces - 1 is decided here), the roulette one, with primary_ray<true>
-void launch_megakernel_lens(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band, uint32_t pix_count,
-                            int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters, int roulette, DLens lens);
-// ... for a frame with an environment (env.texels != null, the caller's check): the plain loop, or (lights.records !=
-// null: a "direct_light" frame's lamp table, with `stats`) the direct-lit one; pinhole or lens, emitters or none, roulette or none
-struct DLights;
-void launch_megakernel_env(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                           uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
-                           DLens lens, DEnv env);
+// ---- the megakernel's launch (DESIGN sections 5g .. 5o) ----------------------------------------------------------------------
+// What the options of the loop (mega_path, pt_megakernel.inc) read beside the scene.  Each is a kernel argument of the instances
+// that know the option alone, kept out of DScene and DMeshView, which every other kernel takes by value; each has an "off" value
+// -- a null first member, radius 0 -- and an instance that takes run-time choices reads the option from it.
+// The lamp table (section 5f): records = 4 float4 per lamp primitive (ptc_light), thresholds = per record the first of the
+// generator's 2^31 - 2 states that belongs to a later record (build_light_table), as a dense array.  records null: no lamp samples.
+struct DLights {
+  const float4* records;
+  const uint32_t* thresholds;
+  uint32_t count, last;        // records; last record with a weight > 0
+  const DObject* objects;      // DScene's arrays: a sphere lamp reads its object's matrix and its sphere, every lamp its material
+  const float4* spheres;
+  const DMaterial* materials;
+};
+// The environment as a light (section 5k; pt_env_light.hpp).  table: the alias table of DEnv's map, n x n entries of 16 bytes
+// (env_light::Entry), the context's own allocation beside the map; null: no environment samples (no map, or a map of weight 0).
+struct DEnvLight {
+  const uint4* table;
+};
+// Multiple importance sampling (section 5l; pt_mis.hpp).  inv_pdf_m: per material of the scene the inv_pdf every lamp record of that
+// material carries, (float)(W / lum), 0 for a material that is no lamp or has lum 0; the scene's allocation beside the lamp table,
+// null without one.
+struct DMis {
+  const float* inv_pdf_m;
+};
+// Smooth shading (section 5n; pt_smooth.hpp).  normals: three floats per vertex of the whole scene, object space, the scene's own
+// allocation; mesh_first_vertex: per mesh where its vertices start in it.  normals null: the geometric normal.
+struct DSmooth {
+  const float* normals;
+  const uint32_t* mesh_first_vertex;
+};
+// Image textures (section 5o; pt_texture.hpp).  texels: every texture's texels back to back, one allocation of the scene's pool;
+// records: one per texture; material_texture: per material -1 or a texture; table: the two decode tables; st: two floats per
+// triangle corner of the whole scene, parallel to its indices; mesh_first_index: per mesh where its corners start in it.  A null
+// member: not set.
+struct DTex {
+  const uint32_t* texels;
+  const texmap::Record* records;
+  const int32_t* material_texture;
+  const float* table;
+  const float* st;
+  const uint32_t* mesh_first_index;
+};
+// The loop counters: kLightStatLines lines of kLoopStatWords 64-bit words (a 128-byte line each), one add per wavefront and word
+// (the words: mega_path's table).  Not part of DeviceCounters, whose layout the feed depends on.
+constexpr uint32_t kLoopStatWords = 16u;
+// One frame of the megakernel: everything a launch takes.  ptc_trace builds it in one place (mega_frame, ptcore_trace.cpp), where
+// every "off" value is written once; launch_megakernel (pt_kernels.hip) reads the frame's facts back from those values, asks the
+// instance rule (pt_mega_rules.hpp) for the kernel, and the unit that holds that kernel launches it.  roulette: the kernel's argument
+// as the rule decides it (mega_rules::roulette_argument); stats: the loop counters, null for a frame that counts nothing; emitters,
+// weigh: the two facts no member carries (the scene has an emissive material; the balance heuristic applies).
+struct MegaFrame {
+  DScene scene;
+  DLights lights;
+  DCamera cam;
+  uint32_t iteration;
+  DBand band;
+  uint32_t pix_count;
+  int max_bounces;
+  DFrame fb;
+  DeviceCounters* counters;
+  unsigned long long* stats;
+  int roulette;
+  DLens lens;
+  DEnv env;
+  DEnvLight el;
+  DMis mis;
+  DSmooth sm;
+  DTex tx;
+  bool emitters, weigh;
+};
+void launch_megakernel(hipStream_t s, const MegaFrame& f);
 void launch_preview(hipStream_t s, const float4* buf, uint32_t pix_count, int mode, uint32_t* rgba);
 void launch_pack(hipStream_t s, const float4* buf, uint32_t pix_count, int which, float* dst);
 // the bands of one multi-GPU gather launch (k_gather_bands): up to kGatherBands sources per launch
@@ -533,17 +591,7 @@ void launch_occlude_spheres(hipStream_t s, const DScene& scene, uint32_t obj_beg
                             const float4* rays_d, uint32_t n, uint8_t* occluded);
 void launch_occlude(hipStream_t s, const DScene& scene, uint32_t obj_index, const float4* rays_o, const float4* rays_d,
                     uint8_t* occluded, int work_slot, DeviceCounters* counters, uint32_t waves, uint32_t* slow_list, const DBatchInfo& bi);
-// direct-light queries (pt_light.hip).  The lamp table lives outside DScene (which every other kernel takes
-// by value): records = 4 float4 per lamp primitive (ptc_light), thresholds = per record the first of the generator's 2^31 - 2 states
-// that belongs to a later record (build_light_table), as a dense array.
-struct DLights {
-  const float4* records;
-  const uint32_t* thresholds;
-  uint32_t count, last;        // records; last record with a weight > 0
-  const DObject* objects;      // DScene's arrays: a sphere lamp reads its object's matrix and its sphere, every lamp its material
-  const float4* spheres;
-  const DMaterial* materials;
-};
+// direct-light queries (pt_light.hip) on the lamp table, DLights
 constexpr uint32_t kLightSeedXor = 0x4c495445u;  // xor-ed into path_seed(point, sample_index): no render path xors its seed
 // Russian roulette (ptc_set_param "roulette"): xor-ed into path_seed(slot or pixel, iteration); discard(bounce), one draw
 constexpr uint32_t kRouletteSeedXor = 0x52524c54u;
@@ -563,83 +611,15 @@ void launch_light_sample(hipStream_t s, const DLights& lights, const float* poin
                          uint32_t tmin_word, float4* o4, float4* d4, float4* contrib);
 void launch_light_resolve(hipStream_t s, const float4* o4, const float4* d4, const float4* contrib, const uint8_t* occluded,
                           const float4* closest_tp, uint32_t n, float* radiance, float* rays, uint8_t* visible, uint32_t* stats);
-// direct lighting in the megakernel: k_megakernel_direct (pt_mega_direct.hip) wraps the one loop, mega_path with
-// kDirect (pt_megakernel.inc) -- a light sample and a shadow ray (scene_occluded, pt_kernels_common.inc) at every diffuse hit.  stats: kLightStatLines lines of kLoopStatWords 64-bit words (a 128-byte line each), word 0 += diffuse
-// hits, word 1 += shadow rays traced, word 2 += unoccluded ones; one add per wavefront.  Not part of DeviceCounters, whose layout the
-// feed depends on.
-constexpr uint32_t kLoopStatWords = 16u;
-void launch_megakernel_direct(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats,
-                              int roulette = 0, DLens lens = DLens{0.0f, 0.0f});
-// The environment as a light (pt_env_light.hpp).  table: the alias table of env's map, n x n entries of 16 bytes
-// (env_light::Entry), the context's own allocation beside the map; null: no table (no map, or a map of weight 0).
-struct DEnvLight {
-  const uint4* table;
-};
 //   launch_env_light_sample  launch_light_sample's shape (pt_env.hip): one thread per point, one environment sample each; the shadow
 //                            ray is {p, tmin_word; w, FLT_MAX}, a culled sample's t_max 0.  launch_light_resolve takes it from there
 void launch_env_light_sample(hipStream_t s, DEnv env, DEnvLight el, const float* points, const float* normals, uint32_t n, uint32_t sample_index,
                              uint32_t tmin_word, float4* o4, float4* d4, float4* contrib);
-// the megakernel's environment-light instance ("environment_light" 1 in a frame whose map has weight > 0; pt_mega_direct.hip): one
-// environment sample and one shadow ray at every diffuse hit, and the lamp's sample in front of it where lights.records != null (a
-// "direct_light" frame's lamp table); emitters, roulette (as launch_megakernel_env), pinhole or lens.  stats: the block
-// launch_megakernel_direct counts in; words 3 .. 5 of a line += diffuse hits that drew an environment sample, its shadow rays, unoccluded ones
-void launch_megakernel_env_light(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                                 uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
-                                 DLens lens, DEnv env, DEnvLight el);
-// Multiple importance sampling in the megakernel (ptc_set_param "mis"; pt_mis.hpp).  inv_pdf_m: per material of the
-// scene the inv_pdf every lamp record of that material carries, (float)(W / lum), 0 for a material that is no lamp or has lum 0; the
-// scene's own allocation beside the lamp table, null without one.
-struct DMis {
-  const float* inv_pdf_m;
-};
-// the megakernel's multiple-importance instance ("mis" 1 in a frame that samples lamps, the environment or both; pt_mega_mis.hip):
-// launch_megakernel_env_light's loop with the balance heuristic at diffuse vertices.  lights.records null: no lamp samples; el.table
-// null: no environment samples; env.texels null: no environment, the gradient.  stats words 6, 7 of a line += emitter hits, misses
-// behind a diffuse vertex that were weighted
-void launch_megakernel_mis(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                           uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
-                           DLens lens, DEnv env, DEnvLight el, DMis mis);
-// Smooth shading in the megakernel (ptc_set_vertex_normals, ptc_set_param "smooth_normals"; pt_smooth.hpp).
-// normals: three floats per vertex of the whole scene, object space, the scene's own allocation; mesh_first_vertex: per mesh where
-// its vertices start in it.  Kept out of DScene and DMeshView, which every other kernel takes by value.  normals null: none set.
-}  // namespace pt
-#include "pt_smooth.hpp"  // (the rule mega_path names under kSmooth)
-namespace pt {
-struct DSmooth {
-  const float* normals;
-  const uint32_t* mesh_first_vertex;
-};
-// the megakernel's smooth instances (a "smooth_normals" 1 frame of a scene with vertex normals; pt_mega_smooth.hip): mega_path with
-// kSmooth -- launch_megakernel_mis's arguments and run-time choices (lights.records null: no lamp samples; el.table null: no
-// environment samples; env.texels null: the gradient; lens.radius), the balance heuristic by `weigh` (one instance with, one without).
-// stats words 8 .. 11 of a line += shading normals formed, fall-backs to the geometric normal, absorbed continuations, culled light samples
-void launch_megakernel_smooth(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
-                              DLens lens, DEnv env, DEnvLight el, DMis mis, bool weigh, DSmooth sm);
 // ptc_hit_attributes' kernel (pt_mega_smooth.hip): one thread per ray, the reference's walk (ray_scene) on the thread's LDS stack.
 // rays: two float4 a ray, {origin, t_min} {direction, t_max}; per ray the winner's object and triangle (0xffffffff: a miss / a
 // sphere), u, v, and the shading normal (sm.normals null: the geometric one); flags |= kFlagStackOverflow
 void launch_hit_attributes(hipStream_t s, const DScene& scene, DSmooth sm, const float4* rays, uint32_t n, uint32_t* object_out,
                            uint32_t* triangle_out, float2* uv_out, float* normal_out, uint32_t* flags);
-// Image textures in the megakernel (ptc_set_textures, ptc_set_texcoords, ptc_set_param "textures"; pt_texture.hpp).
-// texels: every texture's texels back to back, one allocation of the scene's pool; records: one per texture; material_texture: per
-// material -1 or a texture; table: the two decode tables; st: two floats per triangle corner of the whole scene, parallel to its
-// indices; mesh_first_index: per mesh where its corners start in it.  Kept out of DScene, as DSmooth is.  A null member: not set.
-struct DTex {
-  const uint32_t* texels;
-  const texmap::Record* records;
-  const int32_t* material_texture;
-  const float* table;
-  const float* st;
-  const uint32_t* mesh_first_index;
-};
-// the megakernel's textured instances (a "textures" 1 frame of a scene with textures and texture coordinates; pt_mega_tex.hip):
-// mega_path with kTex -- launch_megakernel_smooth's arguments and run-time choices, the balance heuristic by `weigh`, the shading
-// normal by sm.normals (null: the geometric one; an instance each).  stats words 12, 13 of a line += texture lookups, fall-backs
-void launch_megakernel_tex(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                           uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
-                           DLens lens, DEnv env, DEnvLight el, DMis mis, bool weigh, DSmooth sm, DTex tx);
 // ptc_sample_texture's kernel (pt_mega_tex.hip): one thread per coordinate pair, texmap::lookup on one record of the pool; rgb 3
 // floats a pair (zeros where the rule refuses the pair), rejected (may be null) one byte a pair
 void launch_texture_sample(hipStream_t s, DTex tx, uint32_t texture, const float* st, uint32_t n, float* rgb, uint8_t* rejected);

@@ -31,6 +31,7 @@
 #include "pt_feed_rules.hpp"
 #include "pt_light_sample.hpp"  // (mega_path names its kDirect part's types; the instances here have none of it)
 #include "pt_env_light.hpp"     // (... and its kEnvLight part's)
+#include "pt_mega_rules.hpp"
 static_assert(pt::beam_rules::kLeaf == pt::kLeafBit, "pt_beam_rules.hpp restates the leaf bit of the four-wide node (pt_device.hpp)");
 static_assert((uint32_t)pt::beam_rules::kEntries == pt::kBeamEntries, "pt_beam_rules.hpp restates the entries per tile (pt_device.hpp)");
 static_assert(pt::feed_rules::kBatch == (uint32_t)pt::kWave, "a feed batch is one wavefront's worth of rays");
@@ -176,7 +177,8 @@ void k_traverse4(DScene sc, uint32_t obj_index, DPaths paths, DHits hits, int bo
 }
 
 
-// k_megakernel<kEmit, kRoulette>: pt_megakernel.inc (its kRoulette instances live in pt_mega_direct.hip)
+// k_megakernel<kEmit, kRoulette>: pt_megakernel.inc (its kRoulette instances live in pt_mega_direct.hip); launch_megakernel, the one way
+// a frame reaches any of the megakernel's instances, is below
 #include "pt_megakernel.inc"
 
 // intersection_kernel on caller-supplied rays (parity tests): rays_o = origin.xyz,t_min ; rays_d = direction.xyz,t_max
@@ -253,16 +255,36 @@ void launch_traverse(hipStream_t s, const DScene& scene, uint32_t obj_index, boo
     else hipLaunchKernelGGL((k_traverse4<false, false>), grid, block, 0, s, scene, obj_index, paths, hits, bounce, work_slot, counters, slow_list, order, bi, listed ? 1 : 0);
   }
 }
-void launch_megakernel(hipStream_t s, const DScene& scene, const DCamera& cam, uint32_t iteration, DBand band,
-                       uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, bool emitters)
+// this unit's instances of the megakernel: the plain loop without roulette
+void launch_mega_plain(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in)
 {
-  // (the plain instances; a frame with a bounce that plays roulette: launch_megakernel_roulette, pt_mega_direct.hip)
-  if (emitters)
-    hipLaunchKernelGGL((k_megakernel<true, false>), dim3(div_up(pix_count, kWave)), dim3(kWave), 0, s, scene, cam, iteration, band,
-                       pix_count, max_bounces, fb, counters, 0);
-  else
-    hipLaunchKernelGGL((k_megakernel<false, false>), dim3(div_up(pix_count, kWave)), dim3(kWave), 0, s, scene, cam, iteration, band,
-                       pix_count, max_bounces, fb, counters, 0);
+  mega_go_plain(in.a ? k_megakernel<true, false> : k_megakernel<false, false>, s, f);
+}
+// One frame of the megakernel: the frame's facts, read back from its "off" values; the instance the rule names for them
+// (pt_mega_rules.hpp); the unit that holds it.  Nothing behind this decides anything again.
+void launch_megakernel(hipStream_t s, const MegaFrame& f)
+{
+  using mega_rules::Kernel;
+  mega_rules::Facts facts;
+  facts.direct = f.lights.records != nullptr;
+  facts.env = f.env.texels != nullptr;
+  facts.env_lit = f.el.table != nullptr;
+  facts.smooth = f.sm.normals != nullptr;
+  facts.textured = f.tx.texels != nullptr;
+  facts.weigh = f.weigh;
+  facts.lens = f.lens.radius > 0.0f;
+  facts.plays = f.roulette != mega_rules::kNoRoulette;
+  facts.emitters = f.emitters;
+  const mega_rules::Instance in = mega_rules::instance(facts);
+  switch (in.kernel) {
+    case Kernel::tex: return launch_mega_tex(s, f, in);
+    case Kernel::smooth: return launch_mega_smooth(s, f, in);
+    case Kernel::mis: return launch_mega_mis(s, f, in);
+    case Kernel::plain:
+      if (!in.b) return launch_mega_plain(s, f, in);  // (<.., true>: pt_mega_direct.hip)
+      [[fallthrough]];
+    default: return launch_mega_direct(s, f, in);
+  }
 }
 void launch_intersect(hipStream_t s, const DScene& scene, const float4* rays_o, const float4* rays_d, uint32_t n,
                       DHits hits, DeviceCounters* counters, int variant)

@@ -1,13 +1,14 @@
-// pt_mega_mis.hip -- the megakernel's multiple-importance instance (ptc_set_param "mis"): k_megakernel_mis with its
-// launcher, in a translation unit of its own so that pt_mega_direct.hip stays the code object it was.  The loop itself, with what kMis
-// adds to it, is mega_path (pt_megakernel.inc); the densities and the weight are pt_mis.hpp's and pt_env_light.hpp's.  Part of
-// libptcore.so.
+// pt_mega_mis.hip -- the megakernel's multiple-importance instance (ptc_set_param "mis"): k_megakernel_mis and
+// launch_mega_mis (the rule that names it: pt_mega_rules.hpp), in a translation unit of its own so that pt_mega_direct.hip stays the
+// code object it was.  The loop itself, with what kMegaMis adds to it, is mega_path (pt_megakernel.inc); the densities and the weight
+// are pt_mis.hpp's and pt_env_light.hpp's.  Part of libptcore.so.
 #include "pt_device.hpp"
 #include "pt_rng.hpp"
 #include "pt_beam_rules.hpp"
 #include "pt_feed_rules.hpp"
 #include "pt_light_sample.hpp"
 #include "pt_env_light.hpp"
+#include "pt_mega_rules.hpp"
 #include <float.h>
 #include <limits.h>
 
@@ -24,17 +25,12 @@ __global__ __launch_bounds__(kWave) void k_megakernel_mis(DScene sc, DLights lt,
                                                           int roulette, DLens lens, DEnv env, DEnvLight el, DMis mis)
 {
   __shared__ uint32_t s_stack[kStackDepth * kWave];
-  mega_path<true, true, true, false, true, true, true>(sc, lt, cam, iteration, band, pix_count, max_bounces, fb, counters, stats, roulette,
-                                                       s_stack + threadIdx.x, lens, env, el, mis);
+  mega_path<kMegaEnvLit | kMegaMis>(sc, lt, cam, iteration, band, pix_count, max_bounces, fb, counters, stats, roulette, s_stack + threadIdx.x, lens,
+                                    env, el, mis);
 }
 
-void launch_megakernel_mis(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                           uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
-                           DLens lens, DEnv env, DEnvLight el, DMis mis)
+void launch_mega_mis(hipStream_t s, const MegaFrame& f, const mega_rules::Instance&)
 {
-  const dim3 grid((pix_count + kWave - 1u) / kWave), block(kWave);
-  const int plays_from = roulette >= 1 && roulette < max_bounces - 1 ? roulette : INT_MAX;
-  hipLaunchKernelGGL(k_megakernel_mis, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters, stats,
-                     plays_from, lens, env, el, mis);
+  mega_go_lit(k_megakernel_mis, s, f, f.lens, f.env, f.el, f.mis);
 }
 }  // namespace pt

@@ -1,8 +1,8 @@
 // pt_mega_smooth.hip -- smooth shading (ptc_set_vertex_normals, ptc_set_param "smooth_normals"): the megakernel's
-// two smooth instances, k_megakernel_smooth<kMis>, and the primitive query's kernel, k_hit_attributes, with their launchers -- in a
-// translation unit of its own so that every other code object stays what it was.  The loop itself, with what kSmooth adds to it, is
-// mega_path (pt_megakernel.inc); the rule is pt_smooth.hpp's; the closest hit that reports its winner is ray_scene<.., true>
-// (pt_kernels_common.inc).  Part of libptcore.so.
+// two smooth instances, k_megakernel_smooth<kMis>, and the primitive query's kernel, k_hit_attributes, with launch_mega_smooth (the
+// rule that names an instance: pt_mega_rules.hpp) and the query's launcher -- in a translation unit of its own so that every other
+// code object stays what it was.  The loop itself, with what kMegaSmooth adds to it, is mega_path (pt_megakernel.inc); the rule is
+// pt_smooth.hpp's; the closest hit that reports its winner is ray_scene<.., true> (pt_kernels_common.inc).  Part of libptcore.so.
 #include "pt_device.hpp"
 #include "pt_rng.hpp"
 #include "pt_beam_rules.hpp"
@@ -10,6 +10,7 @@
 #include "pt_light_sample.hpp"
 #include "pt_env_light.hpp"
 #include "pt_smooth.hpp"
+#include "pt_mega_rules.hpp"
 #include <float.h>
 #include <limits.h>
 
@@ -28,8 +29,8 @@ __global__ __launch_bounds__(kWave) void k_megakernel_smooth(DScene sc, DLights 
                                                              int roulette, DLens lens, DEnv env, DEnvLight el, DMis mis, DSmooth sm)
 {
   __shared__ uint32_t s_stack[kStackDepth * kWave];
-  mega_path<true, true, true, false, true, true, kMis, true>(sc, lt, cam, iteration, band, pix_count, max_bounces, fb, counters, stats, roulette,
-                                                             s_stack + threadIdx.x, lens, env, el, mis, sm);
+  mega_path<kMegaEnvLit | kMegaSmooth | (kMis ? kMegaMis : 0u)>(sc, lt, cam, iteration, band, pix_count, max_bounces, fb, counters, stats, roulette,
+                                                                s_stack + threadIdx.x, lens, env, el, mis, sm);
 }
 
 // ptc_hit_attributes: one thread per ray, the reference's walk in the reference's order on the thread's column of the LDS stack (no
@@ -81,18 +82,9 @@ __global__ __launch_bounds__(kWave) void k_hit_attributes(DScene sc, DSmooth sm,
   if (flags) atomicOr(flags_out, flags);
 }
 
-void launch_megakernel_smooth(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                              uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
-                              DLens lens, DEnv env, DEnvLight el, DMis mis, bool weigh, DSmooth sm)
+void launch_mega_smooth(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in)
 {
-  const dim3 grid((pix_count + kWave - 1u) / kWave), block(kWave);
-  const int plays_from = roulette >= 1 && roulette < max_bounces - 1 ? roulette : INT_MAX;
-  if (weigh)
-    hipLaunchKernelGGL(k_megakernel_smooth<true>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters,
-                       stats, plays_from, lens, env, el, mis, sm);
-  else
-    hipLaunchKernelGGL(k_megakernel_smooth<false>, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters,
-                       stats, plays_from, lens, env, el, mis, sm);
+  mega_go_lit(in.a ? k_megakernel_smooth<true> : k_megakernel_smooth<false>, s, f, f.lens, f.env, f.el, f.mis, f.sm);
 }
 
 void launch_hit_attributes(hipStream_t s, const DScene& scene, DSmooth sm, const float4* rays, uint32_t n, uint32_t* object_out,

@@ -1,8 +1,9 @@
 // pt_mega_tex.hip -- image textures (ptc_set_textures, ptc_set_texcoords, ptc_set_param "textures"): the
 // megakernel's four textured instances, k_megakernel_tex<kMis, kSmooth>, the lookup query's kernel, k_texture_sample, and the surface
-// query's, k_hit_surface, with their launchers -- in a translation unit of its own so that every other code object stays what it was.
-// The loop itself, with what kTex adds to it, is mega_path (pt_megakernel.inc); the rule is pt_texture.hpp's; the closest hit that
-// reports its winner is ray_scene<.., true> (pt_kernels_common.inc).  Part of libptcore.so.
+// query's, k_hit_surface, with launch_mega_tex (the rule that names an instance: pt_mega_rules.hpp) and the queries' launchers -- in a
+// translation unit of its own so that every other code object stays what it was.  The loop itself, with what kMegaTex adds to it, is
+// mega_path (pt_megakernel.inc); the rule is pt_texture.hpp's; the closest hit that reports its winner is ray_scene<.., true>
+// (pt_kernels_common.inc).  Part of libptcore.so.
 #include "pt_device.hpp"
 #include "pt_rng.hpp"
 #include "pt_beam_rules.hpp"
@@ -11,6 +12,7 @@
 #include "pt_env_light.hpp"
 #include "pt_smooth.hpp"
 #include "pt_texture.hpp"
+#include "pt_mega_rules.hpp"
 #include <float.h>
 #include <limits.h>
 
@@ -29,8 +31,9 @@ __global__ __launch_bounds__(kWave) void k_megakernel_tex(DScene sc, DLights lt,
                                                           int roulette, DLens lens, DEnv env, DEnvLight el, DMis mis, DSmooth sm, DTex tx)
 {
   __shared__ uint32_t s_stack[kStackDepth * kWave];
-  mega_path<true, true, true, false, true, true, kMis, kSmooth, true>(sc, lt, cam, iteration, band, pix_count, max_bounces, fb, counters, stats,
-                                                                      roulette, s_stack + threadIdx.x, lens, env, el, mis, sm, tx);
+  mega_path<kMegaEnvLit | kMegaTex | (kMis ? kMegaMis : 0u) | (kSmooth ? kMegaSmooth : 0u)>(sc, lt, cam, iteration, band, pix_count, max_bounces, fb,
+                                                                                            counters, stats, roulette, s_stack + threadIdx.x, lens,
+                                                                                            env, el, mis, sm, tx);
 }
 
 // ptc_sample_texture: one thread per coordinate pair, steps 2 .. 7 of the rule on one texture of the pool
@@ -90,23 +93,11 @@ __global__ __launch_bounds__(kWave) void k_hit_surface(DScene sc, DTex tx, const
   if (flags) atomicOr(flags_out, flags);
 }
 
-void launch_megakernel_tex(hipStream_t s, const DScene& scene, const DLights& lights, const DCamera& cam, uint32_t iteration, DBand band,
-                           uint32_t pix_count, int max_bounces, DFrame fb, DeviceCounters* counters, unsigned long long* stats, int roulette,
-                           DLens lens, DEnv env, DEnvLight el, DMis mis, bool weigh, DSmooth sm, DTex tx)
+void launch_mega_tex(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in)
 {
-  const dim3 grid((pix_count + kWave - 1u) / kWave), block(kWave);
-  const int plays_from = roulette >= 1 && roulette < max_bounces - 1 ? roulette : INT_MAX;
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, scene, lights, cam, iteration, band, pix_count, max_bounces, fb, counters, stats, plays_from, lens,
-                       env, el, mis, sm, tx);
-  };
-  if (sm.normals) {
-    if (weigh) go(k_megakernel_tex<true, true>);
-    else go(k_megakernel_tex<false, true>);
-  } else {
-    if (weigh) go(k_megakernel_tex<true, false>);
-    else go(k_megakernel_tex<false, false>);
-  }
+  mega_go_lit(in.b ? (in.a ? k_megakernel_tex<true, true> : k_megakernel_tex<false, true>)
+                   : (in.a ? k_megakernel_tex<true, false> : k_megakernel_tex<false, false>),
+              s, f, f.lens, f.env, f.el, f.mis, f.sm, f.tx);
 }
 
 void launch_texture_sample(hipStream_t s, DTex tx, uint32_t tex, const float* st, uint32_t n, float* rgb, uint8_t* rejected)

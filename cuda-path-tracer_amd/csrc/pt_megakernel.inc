@@ -1,63 +1,64 @@
-// pt_megakernel.inc -- the megakernel's loop, the whole path in one thread: mega_path, and k_megakernel around it.  Included (inside
-// namespace pt, after pt_kernels_common.inc and with pt_light_sample.hpp in front) by pt_kernels.hip, which instantiates the plain
-// instances beside the closest-hit kernels as ever, and by pt_mega_direct.hip, which instantiates the kRoulette ones and
-// k_megakernel_direct, and by pt_mega_mis.hip, which instantiates k_megakernel_mis (kMis, DESIGN section 5l), and by pt_mega_smooth.hip,
-// which instantiates k_megakernel_smooth (kSmooth, section 5n), and by pt_mega_tex.hip, which instantiates k_megakernel_tex (kTex,
-// section 5o): the code object that holds the traversal kernels stays the one it was (DESIGN section 5h).
-// path_tracing_mega_kernel, path_tracer.cu:227-269: the whole path in one thread, one RNG stream per
-// pixel (a different image from streaming mode at the same seed -- a property of the reference).
-// kEmit: the scene has an emissive material (the host's choice; without one the instance is the reference's loop as it was).
-// kRoulette: Russian roulette from bounce `roulette` on, the last bounce excepted (DESIGN section 5h; the host picks the instance
-// when some bounce plays): after the emitter check and before evaluate_material, on the roulette stream of the pixel.  A path that
-// ends there leaves colour 0 and makes no draw.
-// kDirect (with kEmit; DESIGN section 5g): one light sample (section 5f, pt_light_sample.hpp) and one shadow ray at every diffuse
-// hit, a per-path radiance sum and the emission gate that keeps a lamp from being counted twice -- and nothing else.  The shadow
-// ray takes the per-thread any-hit walk (scene_occluded) on the thread's own LDS stack, which is free while it runs.  The light
-// samples draw from a stream of their own (path_seed(pixel, iteration) ^ kLightSeedXor, draws 3b .. 3b + 2 at bounce b), so every
-// material draw, every closest hit, the normal and depth planes and rays_total are those of the plain loop at the same iteration:
-// only the colour differs.  A path roulette ends takes no light sample at that hit and adds nothing to the three loop counters; a
-// survivor's light sample is weighted with the divided colour.  tests/direct_loop_ref.py restates the loop in numpy.
-// stats (kDirect): kLightStatLines lines of kLoopStatWords 64-bit words; word 0 += diffuse hits, word 1 += shadow rays traced,
-// word 2 += unoccluded ones.  stack: the calling thread's column of the workgroup's LDS stack.
-// kLens (DESIGN section 5i): the primary ray is the thin lens's, primary_ray<true> with `lens`; rng is left where the pinhole leaves it,
-// so every material draw is the pinhole render's.  The lens instances (k_megakernel_lens, k_megakernel_direct_lens) live in
-// pt_mega_direct.hip.
-// kEnv (ptc_set_environment, DESIGN section 5j): a miss takes the environment, sky<true>(ray.d, env), at every bounce and whatever
-// count_emission says, as the gradient does; the environment is no lamp and draws no light sample.  An environment instance serves
-// pinhole and lens alike -- lens.radius > 0 decides per launch, kLens is not read -- and is built with kEmit and kRoulette on (a scene
-// without emitters meets no emitter; `roulette` >= max_bounces plays at no bounce: the same bits): k_megakernel_env<kDirect>,
-// pt_mega_direct.hip.
-// kEnvLight (with kEnv and kDirect; ptc_set_param "environment_light", DESIGN section 5k): the environment is a light as well.  Every
-// diffuse hit draws one environment sample (env_light::sample_point, pt_env_light.hpp; the stream path_seed(pixel, iteration) ^
-// kEnvLightSeedXor, draws 4b .. 4b + 3 at bounce b) behind the lamp's, with a shadow ray of its own on the same LDS stack, and a miss
-// counts the environment only when the vertex before it drew no environment sample -- section 5g's gate in a flag of its own,
-// count_env.  The lamps are a run-time choice here: lt.records null (a wave-uniform kernel argument) is a frame without "direct_light"
-// or without a lamp table, which draws no lamp sample and counts every emitter.  stats words 3 .. 5 += diffuse hits that drew an
-// environment sample, its shadow rays, the unoccluded ones.  k_megakernel_env_light, pt_mega_direct.hip.
-// kMis (with kEnvLight; ptc_set_param "mis", DESIGN section 5l; k_megakernel_mis, pt_mega_mis.hip): the balance heuristic between each
-// light sample and the path's own continuation ray at diffuse vertices.  One more float of path state, bsdf_pdf -- the cosine lobe's
-// density of the direction evaluate_material drew, read only while count_emission or count_env is false.  A lamp's and the
-// environment's sample are weighted against the lobe's density of their direction (not at the last bounce, which has no continuation
-// ray); an emitter hit and a miss behind a diffuse vertex count with the lobe's weight against the light sampler's density of that
-// hit instead of 0: mis.inv_pdf_m[material], loaded beside the material, and env_light::density, whose load stands in front of the
-// sky's texel loads.  Here the environment light is a run-time choice as well (el.table null: none) and so is the environment
-// (env.texels null: the gradient).  Every draw, every closest hit and shadow ray and the six counters are those of the loop without it.
-// stats words 6 and 7 += emitter hits and misses behind a diffuse vertex that were weighted.
-// kSmooth (with kEnvLight; ptc_set_param "smooth_normals" in a scene with vertex normals, DESIGN section 5n; k_megakernel_smooth,
-// pt_mega_smooth.hip): at a triangle hit the shading normal hn is smooth::shading_normal's (pt_smooth.hpp) of the winner's three
-// vertex normals -- the closest hit reports the winner, ray_scene<.., true> -- and takes rec.n's place in the normal plane, in
-// evaluate_material, in the light samples and in bsdf_pdf; rec.n stays geometric (side, the lamp-side cosine of an emitter hit).  A
-// light sample whose direction lies behind the geometry (dot(w, rec.n) <= 0) counts as not sampled, and a diffuse or metal triangle
-// hit whose new direction does (dot(ray.d, rec.n) <= 0) ends the path with colour 0 behind its light samples.  Every light is a
-// run-time choice as under kMis, with or without it, and a frame that samples none deposits colour alone.  stats words 8 .. 11 +=
-// shading normals formed, fall-backs, absorbed continuations, culled light samples.
-// kTex (with kEnvLight; ptc_set_param "textures" in a scene with textures and texture coordinates, DESIGN section 5o; k_megakernel_tex,
-// pt_mega_tex.hip): at a triangle hit on a diffuse or metal material with a texture bound, after the emitter check and roulette and
-// immediately before evaluate_material, the material is copied and texmap::albedo's (pt_texture.hpp) colour -- the texel at the
-// winner's interpolated corner coordinates times p[0..2] -- replaces p[0..2] in the copy; everything downstream takes it from there.
-// Every light is a run-time choice as under kSmooth, with kSmooth or without.  stats words 12, 13 += lookups, fall-backs.
-template <bool kEmit, bool kRoulette, bool kDirect, bool kLens = false, bool kEnv = false, bool kEnvLight = false, bool kMis = false,
-          bool kSmooth = false, bool kTex = false>
+// pt_megakernel.inc -- the megakernel's loop, the whole path in one thread (path_tracing_mega_kernel, path_tracer.cu:227-269; one RNG
+// stream per pixel: a different image from streaming mode at the same seed, a property of the reference): mega_path, the two plain
+// kernels around it, and what every unit's launcher shares.  Included inside namespace pt, after pt_kernels_common.inc and with
+// pt_light_sample.hpp and pt_env_light.hpp in front, by the five units that hold its 22 instances: pt_kernels.hip (the plain loop
+// without roulette, beside the closest-hit kernels as ever), pt_mega_direct.hip, pt_mega_mis.hip, pt_mega_smooth.hip and
+// pt_mega_tex.hip -- a unit per feature, so that the code objects of the features before it stay the ones they were (DESIGN section
+// 5h).  Which instance a frame launches: pt_mega_rules.hpp.
+//
+// The options of the loop, one bit of kF each: what the option adds; its DESIGN section, where the reasons are; the 64-bit words of a
+// loop-counter line it adds to (`stats`: kLightStatLines lines of kLoopStatWords words, one add per wavefront); the kernels built with it.
+//   kMegaEmit      a path ends at an emissive material and takes its colour, without a draw; off, the loop is the reference's.
+//                  5d; -; k_megakernel<true, ..>, k_megakernel_lens<true, ..> and every kernel below (no emitter: the same bits)
+//   kMegaRoulette  Russian roulette from bounce `roulette` on, the last bounce excepted: behind the emitter check, before
+//                  evaluate_material, on the pixel's roulette stream.  A path it ends leaves colour 0, draws, samples and counts nothing.
+//                  5h; -; k_megakernel<.., true>, k_megakernel_lens<.., true>, k_megakernel_direct<true>, k_megakernel_direct_lens<true>
+//                  and every kernel from kMegaEnv on (`roulette` INT_MAX plays at no bounce: the same bits)
+//   kMegaDirect    (with kMegaEmit) at every diffuse hit one light sample (5f, pt_light_sample.hpp; stream path_seed(pixel, iteration) ^
+//                  kLightSeedXor, draws 3b .. 3b + 2 at bounce b) and one shadow ray (scene_occluded on the thread's own LDS stack, free
+//                  while it runs), a per-path radiance sum, and the gate count_emission that keeps a lamp from counting twice.  Draws,
+//                  closest hits, normal, depth and rays_total stay the plain loop's; tests/direct_loop_ref.py restates it in numpy.
+//                  5g; words 0 .. 2 diffuse hits, shadow rays, unoccluded ones; k_megakernel_direct<..>, k_megakernel_direct_lens<..>,
+//                  k_megakernel_env<true> and every kernel from kMegaEnvLight on
+//   kMegaLens      the primary ray is the thin lens's, primary_ray<true> with `lens`; rng is left where the pinhole leaves it.
+//                  5i; -; k_megakernel_lens<..>, k_megakernel_direct_lens<..>
+//   kMegaEnv       a miss takes the environment, sky<true>(ray.d, env), at every bounce, as the gradient does: the environment is no
+//                  lamp.  Pinhole or lens by lens.radius > 0 per launch; kMegaLens is not read.
+//                  5j; -; k_megakernel_env<..> and every kernel below
+//   kMegaEnvLight  (with kMegaEnv and kMegaDirect) the environment is a light too: behind the lamp's sample one environment sample
+//                  (env_light::sample_point, pt_env_light.hpp; stream ^ kEnvLightSeedXor, draws 4b .. 4b + 3) with a shadow ray of its
+//                  own, and 5g's gate in a flag of its own, count_env, for the miss behind it.  The lamps become a run-time choice:
+//                  lt.records null (wave-uniform) draws no lamp sample and counts every emitter.
+//                  5k; words 3 .. 5 hits that drew an environment sample, its shadow rays, unoccluded ones; k_megakernel_env_light and
+//                  every kernel below
+//   kMegaMis       (with kMegaEnvLight) the balance heuristic at diffuse vertices (pt_mis.hpp).  One more float of path state,
+//                  bsdf_pdf, the lobe's density of the direction drawn, read only while a gate is closed.  A light sample is weighed
+//                  against the lobe's density of its direction (not at the last bounce: no continuation ray); an emitter hit or a miss
+//                  behind a diffuse vertex counts with the lobe's weight against the sampler's density there -- mis.inv_pdf_m[material],
+//                  loaded beside the material, and env_light::density, loaded ahead of the sky's texels -- instead of 0.  The
+//                  environment light (el.table) and the environment (env.texels) become run-time choices as well.  Draws, hits,
+//                  shadow rays and words 0 .. 5 stay those of the loop without it.
+//                  5l; words 6, 7 emitter hits, misses that were weighed; k_megakernel_mis, k_megakernel_smooth<true>, k_megakernel_tex<true, ..>
+//   kMegaSmooth    (with kMegaEnvLight) at a triangle hit -- ray_scene<.., true> reports the winner -- the shading normal hn is
+//                  smooth::shading_normal's (pt_smooth.hpp) and takes rec.n's place in the normal plane, evaluate_material, the light
+//                  samples and bsdf_pdf; rec.n stays geometric (side, an emitter's cosine).  A light sample that points behind the
+//                  geometry counts as not sampled; a diffuse or metal hit whose new direction does ends the path with colour 0 behind
+//                  its light samples.  Every light is a run-time choice as under kMegaMis, with it or without.
+//                  5n; words 8 .. 11 normals formed, fall-backs, absorbed continuations, culled light samples; k_megakernel_smooth<..>,
+//                  k_megakernel_tex<.., true>
+//   kMegaTex       (with kMegaEnvLight) at a triangle hit on a diffuse or metal material with a texture bound, immediately before
+//                  evaluate_material, texmap::albedo's colour (pt_texture.hpp: the texel at the interpolated corner coordinates times
+//                  p[0..2]) replaces p[0..2] in a copy of the material.  Every light is a run-time choice as under kMegaSmooth.
+//                  5o; words 12, 13 lookups, fall-backs; k_megakernel_tex<..>
+constexpr uint32_t kMegaEmit = 1u, kMegaRoulette = 2u, kMegaDirect = 4u, kMegaLens = 8u, kMegaEnv = 16u, kMegaEnvLight = 32u, kMegaMis = 64u,
+                   kMegaSmooth = 128u, kMegaTex = 256u;
+// what every instance with an environment is built with: emitters and roulette compiled in, pinhole or lens by lens.radius
+constexpr uint32_t kMegaEnvBase = kMegaEmit | kMegaRoulette | kMegaEnv;
+// ... and every instance that samples the environment: the lamps' samples by lt.records
+constexpr uint32_t kMegaEnvLit = kMegaEnvBase | kMegaDirect | kMegaEnvLight;
+
+// stack: the calling thread's column of the workgroup's LDS stack
+template <uint32_t kF>
 __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, const DCamera& cam, const uint32_t iteration, const DBand band,
                                           const uint32_t pix_count, const int max_bounces, const DFrame fb, DeviceCounters* counters,
                                           unsigned long long* stats, const int roulette, uint32_t* stack,
@@ -66,6 +67,8 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
                                           const DSmooth sm = DSmooth{nullptr, nullptr},
                                           const DTex tx = DTex{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr})
 {
+  constexpr bool kEmit = kF & kMegaEmit, kRoulette = kF & kMegaRoulette, kDirect = kF & kMegaDirect, kLens = kF & kMegaLens, kEnv = kF & kMegaEnv,
+                 kEnvLight = kF & kMegaEnvLight, kMis = kF & kMegaMis, kSmooth = kF & kMegaSmooth, kTex = kF & kMegaTex;
   constexpr bool kDyn = kSmooth || kTex;  // every light and the environment are run-time choices
   static_assert(!kTex || kEnvLight, "the textured instances sample lamps and environment by run-time choice");
   static_assert(!kSmooth || kEnvLight, "the smooth instances sample lamps and environment by run-time choice");
@@ -343,15 +346,15 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
   }
 }
 
-// the plain loop (instances: pt_kernels.hip; the ones that play roulette: pt_mega_direct.hip)
+// the plain loop (instances: <.., false> pt_kernels.hip; the ones that play roulette: pt_mega_direct.hip)
 template <bool kEmit, bool kRoulette = false>
 __global__ __launch_bounds__(kWave) void k_megakernel(DScene sc, DCamera cam, uint32_t iteration, DBand band,
                                                       uint32_t pix_count, int max_bounces, DFrame fb,
                                                       DeviceCounters* counters, int roulette)
 {
   __shared__ uint32_t s_stack[kStackDepth * kWave];
-  mega_path<kEmit, kRoulette, false>(sc, DLights{}, cam, iteration, band, pix_count, max_bounces, fb, counters, nullptr, roulette,
-                                     s_stack + threadIdx.x);
+  mega_path<(kEmit ? kMegaEmit : 0u) | (kRoulette ? kMegaRoulette : 0u)>(sc, DLights{}, cam, iteration, band, pix_count, max_bounces, fb, counters,
+                                                                         nullptr, roulette, s_stack + threadIdx.x);
 }
 
 // ... under a thin lens (DESIGN section 5i; instances: pt_mega_direct.hip)
@@ -361,6 +364,32 @@ __global__ __launch_bounds__(kWave) void k_megakernel_lens(DScene sc, DCamera ca
                                                            DeviceCounters* counters, int roulette, DLens lens)
 {
   __shared__ uint32_t s_stack[kStackDepth * kWave];
-  mega_path<kEmit, kRoulette, false, true>(sc, DLights{}, cam, iteration, band, pix_count, max_bounces, fb, counters, nullptr, roulette,
-                                           s_stack + threadIdx.x, lens);
+  mega_path<(kEmit ? kMegaEmit : 0u) | (kRoulette ? kMegaRoulette : 0u) | kMegaLens>(sc, DLights{}, cam, iteration, band, pix_count, max_bounces, fb,
+                                                                                     counters, nullptr, roulette, s_stack + threadIdx.x, lens);
+}
+
+// ---- the host's side: what the five units' launchers share.  A unit's launcher (launch_mega_*, below launch_megakernel in
+// pt_kernels.hip) gets the frame and the instance the rule chose, picks that kernel among its own by the instance's template
+// arguments and launches it through one of these: one thread per pixel of the band, a wavefront per workgroup.
+void launch_mega_plain(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);   // pt_kernels.hip
+void launch_mega_direct(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);  // pt_mega_direct.hip
+void launch_mega_mis(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);     // pt_mega_mis.hip
+void launch_mega_smooth(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);  // pt_mega_smooth.hip
+void launch_mega_tex(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);     // pt_mega_tex.hip
+template <typename K, typename... A>
+void mega_go(K kernel, hipStream_t s, const MegaFrame& f, const A&... args)
+{
+  hipLaunchKernelGGL(kernel, dim3((f.pix_count + kWave - 1u) / kWave), dim3(kWave), 0, s, args...);
+}
+// the parameters of the two plain kernels (no lamp table, no loop counters), then `more`
+template <typename K, typename... A>
+void mega_go_plain(K kernel, hipStream_t s, const MegaFrame& f, const A&... more)
+{
+  mega_go(kernel, s, f, f.scene, f.cam, f.iteration, f.band, f.pix_count, f.max_bounces, f.fb, f.counters, f.roulette, more...);
+}
+// ... of every other kernel, then `more`
+template <typename K, typename... A>
+void mega_go_lit(K kernel, hipStream_t s, const MegaFrame& f, const A&... more)
+{
+  mega_go(kernel, s, f, f.scene, f.lights, f.cam, f.iteration, f.band, f.pix_count, f.max_bounces, f.fb, f.counters, f.stats, f.roulette, more...);
 }

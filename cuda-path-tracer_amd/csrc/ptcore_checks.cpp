@@ -2,6 +2,7 @@
 // ptc_check_traversal_layout, ptc_check_rng, ptc_check_light_sample), ptc_debug_beam_entries, ptc_debug_sphere_lanes, ptc_selftest_math, ptc_selftest_rng, and
 // ptc_generate_rays (the frame's primary rays as ray generation builds them).  Part of libptcore.so (ptcore_ctx.hpp).
 #include "ptcore_ctx.hpp"
+#include "pt_mega_rules.hpp"
 #include "pt_rng.hpp"
 #include "pt_light_sample.hpp"
 
@@ -232,6 +233,26 @@ int ptc_check_frame_plan(uint32_t width, uint32_t height, int frames_in_flight, 
 {
   if (!out || width < 2u || height < 2u || (uint64_t)width * height > 0x7fffffffull) return PTC_ERR_INVALID;
   *out = frame_plan(width, height, frames_in_flight, frames_auto != 0, batch_frames, prefold != 0);
+  return PTC_OK;
+}
+
+// mega_rules::instance (pt_mega_rules.hpp), the rule launch_megakernel follows, with roulette_frame's reading of `plays`.
+int ptc_check_megakernel_instance(int direct, int env, int env_lit, int smooth, int textured, int weigh, int lens, int plays, int emitters,
+                                  int roulette, int max_bounces, char* name_out, uint32_t name_capacity, int* roulette_out)
+{
+  if (!name_out || !roulette_out) return PTC_ERR_INVALID;
+  mega_rules::Facts f;
+  f.direct = direct != 0;
+  f.env = env != 0;
+  f.env_lit = env_lit != 0;
+  f.smooth = smooth != 0;
+  f.textured = textured != 0;
+  f.weigh = weigh != 0;
+  f.lens = lens != 0;
+  f.plays = plays < 0 ? roulette_frame(roulette, max_bounces) : plays != 0;
+  f.emitters = emitters != 0;
+  if (!mega_rules::instance_name(mega_rules::instance(f), name_out, name_capacity)) return PTC_ERR_INVALID;
+  *roulette_out = mega_rules::roulette_argument(f.plays, roulette);
   return PTC_OK;
 }
 

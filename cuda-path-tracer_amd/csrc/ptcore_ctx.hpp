@@ -289,6 +289,8 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
 
   ptc_direct_stats direct{};             // ptc_direct_light since ptc_reset_profile
 
+  // The megakernel's options.  What they come to in a frame: mega_frame (ptcore_trace.cpp); which kernel that frame launches -- the one
+  // named below only while no later option is on as well: the instance rule (pt_mega_rules.hpp).
   // "direct_light" (DESIGN section 5g): the megakernel draws a light sample at every diffuse hit (k_megakernel_direct)
   bool direct_light = false;
   // "roulette" (DESIGN section 5h): Russian roulette at every bounce >= this, the last bounce excepted; 0 = off
@@ -357,6 +359,8 @@ int flush_pending(ptc_ctx* ctx, bool from_trace = false);  // enqueue the iterat
 uint32_t fold_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end);  // may k_spheres take sphere_fold for this run? (ptcore_trace.cpp)
 uint32_t lanes_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end);  // ... the per-lane form, sphere_run_lanes? (ptcore_trace.cpp)
 int sync_frames(ptc_ctx* ctx);
+// "roulette" (DESIGN section 5h): does any bounce of a frame play?  (ptcore_trace.cpp: the one statement of it)
+bool roulette_frame(int roulette, int max_bounces);
 // The alias table of the context's environment (ptcore.cpp), built and uploaded if this map has none yet.  After
 // PTC_OK ctx->env_table is the table, or null for a map of weight 0.  PTC_ERR_OOM: the allocation failed; the environment stays.
 int env_light_table(ptc_ctx* ctx);

@@ -1,6 +1,7 @@
 // ptcore_trace.cpp -- the launch plan of a batch of frames (batch_begin / batch_bounce / batch_end), ptc_trace and its stepwise
 // form, the live counts.  Part of libptcore.so (ptcore_ctx.hpp).  The ray queries outside the render loop: ptcore_query.cpp.
 #include "ptcore_ctx.hpp"
+#include "pt_mega_rules.hpp"
 
 using namespace pt;
 using namespace ptcd;
@@ -86,7 +87,7 @@ size_t launch_run(const ptc_ctx* ctx, size_t k)
 // every other bounce launches what it launched before the parameter existed.
 bool roulette_bounce(const ptc_ctx* ctx, int bounce) { return ctx->roulette >= 1 && bounce >= ctx->roulette && bounce < ctx->max_bounces - 1; }
 // ... does any bounce of a frame?
-bool roulette_frame(const ptc_ctx* ctx) { return ctx->roulette >= 1 && ctx->roulette < ctx->max_bounces - 1; }
+bool roulette_frame(const ptc_ctx* ctx) { return ptcd::roulette_frame(ctx->roulette, ctx->max_bounces); }
 
 // The thin lens (ptc_set_lens): is a frame rendered now a lens frame?  Such a frame launches the lens instances of
 // ray generation (of the megakernel), and gets no entry points ("beam"): k_beam builds a tile's frustum from the pinhole origin, and
@@ -453,9 +454,47 @@ int batch_end(ptc_ctx* ctx)
 // frames per batch ptc_trace may use right now (only the default traversal kernel reads DBatchInfo)
 int batch_limit(const ptc_ctx* ctx) { return ctx->staged && ctx->trace_variant == 3 ? ctx->batch : 1; }
 
+// One frame of the megakernel (MegaFrame, pt_device.hpp) from the context, for the slot whose counters it adds to: what the frame's
+// options come to in this scene, and for each one what the launch gets -- its data, or the "off" value, written here and nowhere
+// else.  launch_megakernel reads the kernel off these values (pt_mega_rules.hpp), so an option that is off must be off here.
+// (ctx->env_table: after env_light_table, which an "environment_light" frame with an environment has called.)
+MegaFrame mega_frame(const ptc_ctx* ctx, DeviceCounters* counters)
+{
+  const bool direct = ctx->direct_light && ctx->light_records;  // a lamp table of total weight > 0; without one as with 0
+  const bool env = env_frame(ctx);
+  const bool env_lit = ctx->environment_light && env && ctx->env_table;  // (section 5k) a map of weight > 0; else as with 0
+  const bool smooth = ctx->smooth_normals && ctx->normals_set;           // (section 5n) a scene with vertex normals; else as with 0
+  const bool textured = ctx->textures && ctx->textures_set && ctx->texcoords_set;  // (section 5o) textures and coordinates; else as with 0
+  MegaFrame f{};
+  f.scene = ctx->scene;
+  f.lights = direct ? DLights{ctx->light_records, ctx->light_thresholds, ctx->light_info.lights, ctx->light_last, ctx->scene.objects,
+                              ctx->scene.spheres, ctx->scene.materials}
+                    : DLights{};
+  f.cam = ctx->cam;
+  f.iteration = (uint32_t)ctx->iteration;
+  f.band = ctx->band;
+  f.pix_count = ctx->pix_count;
+  f.max_bounces = ctx->max_bounces;
+  f.fb = ctx->fb;
+  f.counters = counters;
+  f.stats = direct || env_lit || smooth || textured ? ctx->loop_stats : nullptr;  // the frames that count in the loop-counter lines
+  f.roulette = mega_rules::roulette_argument(roulette_frame(ctx), ctx->roulette);
+  f.lens = frame_lens(ctx);
+  f.env = env ? ctx->env : DEnv{nullptr, 0u, 0u};
+  f.el = DEnvLight{env_lit ? ctx->env_table : nullptr};
+  f.mis = DMis{direct ? ctx->light_material_pdf : nullptr};
+  f.sm = DSmooth{smooth ? ctx->vertex_normals : nullptr, ctx->mesh_first_vertex};
+  f.tx = textured ? DTex{ctx->tex_texels, ctx->tex_records, ctx->tex_material, ctx->tex_table, ctx->texcoords, ctx->mesh_first_index} : DTex{};
+  f.emitters = ctx->has_emitters;
+  f.weigh = ctx->mis && (direct || env_lit);  // (section 5l) a frame that samples neither light weighs nothing
+  return f;
+}
+
 }  // namespace
 
 namespace ptcd {
+bool roulette_frame(int roulette, int max_bounces) { return roulette >= 1 && roulette < max_bounces - 1; }
+
 // may k_spheres take sphere_fold for the run [begin, end)?  Every object a "simple" sphere (sphere_ball_of)
 uint32_t fold_run_of(const ptc_ctx* ctx, uint32_t begin, uint32_t end)
 {
@@ -661,59 +700,15 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
     auto& sl = ctx->slots[0];
     ctx->cam = make_camera(*camera, ctx->width, ctx->height);
     ctx->have_cam = true;
-    const bool direct = ctx->direct_light && ctx->light_records;  // a lamp table of total weight > 0; without one: the plain instances, the same bits
     // "environment_light" (DESIGN section 5k): a frame whose environment has a table, i.e. a map of weight > 0; else as with 0
     if (ctx->environment_light && env_frame(ctx))
       if (int rc = env_light_table(ctx)) return rc;
-    const bool env_lit = ctx->environment_light && env_frame(ctx) && ctx->env_table;
-    // "smooth_normals" (DESIGN section 5n): a frame of a scene with vertex normals; without them as with 0
-    const bool smooth = ctx->smooth_normals && ctx->normals_set;
-    // "textures" (DESIGN section 5o): a frame of a scene with textures and texture coordinates; without either as with 0
-    const bool textured = ctx->textures && ctx->textures_set && ctx->texcoords_set;
-    DLights lights{};
-    if (direct || env_lit || smooth || textured) {  // the frames that count in the loop-counter lines
-      if (ctx->loop_stats_clear) {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->loop_stats, 0, kLoopStatBytes, sl.stream));
-        ctx->loop_stats_clear = false;
-      }
+    const MegaFrame frame = mega_frame(ctx, sl.counters);
+    if (frame.stats && ctx->loop_stats_clear) {
+      HIP_TRY(ctx, hipMemsetAsync(ctx->loop_stats, 0, kLoopStatBytes, sl.stream));
+      ctx->loop_stats_clear = false;
     }
-    if (direct)
-      lights = DLights{ctx->light_records, ctx->light_thresholds, ctx->light_info.lights, ctx->light_last, ctx->scene.objects, ctx->scene.spheres,
-                       ctx->scene.materials};
-    if (textured) {  // its four instances: the balance heuristic and the shading normal, each with and without
-      launch_megakernel_tex(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,
-                            sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx), env_frame(ctx) ? ctx->env : DEnv{nullptr, 0u, 0u},
-                            DEnvLight{env_lit ? ctx->env_table : nullptr}, DMis{direct ? ctx->light_material_pdf : nullptr},
-                            ctx->mis && (direct || env_lit), DSmooth{smooth ? ctx->vertex_normals : nullptr, ctx->mesh_first_vertex},
-                            DTex{ctx->tex_texels, ctx->tex_records, ctx->tex_material, ctx->tex_table, ctx->texcoords, ctx->mesh_first_index});
-    } else if (smooth) {  // its two instances, with the balance heuristic and without; every light and the environment by run-time choice
-      launch_megakernel_smooth(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,
-                               sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx), env_frame(ctx) ? ctx->env : DEnv{nullptr, 0u, 0u},
-                               DEnvLight{env_lit ? ctx->env_table : nullptr}, DMis{direct ? ctx->light_material_pdf : nullptr},
-                               ctx->mis && (direct || env_lit), DSmooth{ctx->vertex_normals, ctx->mesh_first_vertex});
-    } else if (ctx->mis && (direct || env_lit)) {  // "mis" (DESIGN section 5l): its one instance, whichever of the two lights the frame samples
-      launch_megakernel_mis(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,
-                            sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx), env_frame(ctx) ? ctx->env : DEnv{nullptr, 0u, 0u},
-                            DEnvLight{env_lit ? ctx->env_table : nullptr}, DMis{direct ? ctx->light_material_pdf : nullptr});
-    } else if (env_lit) {  // the environment is a light too: its one instance, the lamps' samples by lights.records
-      launch_megakernel_env_light(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces,
-                                  ctx->fb, sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx), ctx->env, DEnvLight{ctx->env_table});
-    } else if (env_frame(ctx)) {  // an environment: its instance of the plain or the direct-lit loop
-      launch_megakernel_env(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces, ctx->fb,
-                            sl.counters, direct ? ctx->loop_stats : nullptr, ctx->roulette, frame_lens(ctx), ctx->env);
-    } else if (direct) {
-      launch_megakernel_direct(sl.stream, ctx->scene, lights, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
-                               ctx->max_bounces, ctx->fb, sl.counters, ctx->loop_stats, ctx->roulette, frame_lens(ctx));
-    } else if (lens_frame(ctx)) {  // the thin lens: the lens instance of the plain or the roulette loop
-      launch_megakernel_lens(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces,
-                             ctx->fb, sl.counters, ctx->has_emitters, ctx->roulette, ctx->lens);
-    } else if (roulette_frame(ctx)) {  // some bounce plays roulette
-      launch_megakernel_roulette(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count, ctx->max_bounces,
-                                 ctx->fb, sl.counters, ctx->has_emitters, ctx->roulette);
-    } else {
-      launch_megakernel(sl.stream, ctx->scene, ctx->cam, (uint32_t)ctx->iteration, ctx->band, ctx->pix_count,
-                        ctx->max_bounces, ctx->fb, sl.counters, ctx->has_emitters);
-    }
+    launch_megakernel(sl.stream, frame);
     if (int rc = check_last(ctx, "megakernel")) return rc;
     HIP_TRY(ctx, hipEventRecord(sl.done, sl.stream));
     if (ctx->staged) {

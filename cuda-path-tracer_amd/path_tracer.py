@@ -151,6 +151,17 @@ def check_texture_lookup(texture, st):
     return rgb, rej.astype(bool)
 
 
+def check_megakernel_instance(direct=False, env=False, env_lit=False, smooth=False, textured=False, weigh=False, lens=False, plays=None,
+                              emitters=False, roulette=0, max_bounces=50):
+    """The megakernel's instance rule on the host (ptc_check_megakernel_instance; no GPU): the nine facts of a frame -> (the kernel's
+    name as a profile prints it, its roulette argument).  plays None: the library's own reading of roulette under max_bounces."""
+    name, arg = C.create_string_buffer(64), C.c_int(0)
+    _capi.check(_capi.lib().ptc_check_megakernel_instance(int(direct), int(env), int(env_lit), int(smooth), int(textured), int(weigh), int(lens),
+                                                          -1 if plays is None else int(plays), int(emitters), int(roulette), int(max_bounces),
+                                                          name, len(name), C.byref(arg)))
+    return name.value.decode(), arg.value
+
+
 def compute_vertex_normals(positions, indices=None, mesh_ranges=None):
     """Area-weighted vertex normals (ptc_compute_vertex_normals; host-side, no GPU needed).  positions [v, 3] and
     indices [t * 3] of one mesh, or -- with mesh_ranges, a mesh table's rows (first_vertex, vertex_count, first_index, index_count, ...)

@@ -877,6 +877,16 @@ typedef struct ptc_frame_plan {
 } ptc_frame_plan;
 int ptc_check_frame_plan(uint32_t width, uint32_t height, int frames_in_flight, int frames_auto, int batch_frames, int prefold,
                          ptc_frame_plan* out);
+/* The instance rule of the megakernel, on the host (no GPU, no context; test hook; csrc/pt_mega_rules.hpp): which of its 22
+ * kernels ptc_trace launches for a frame with these nine facts (0 or not 0 each) -- direct: "direct_light" and a lamp table of
+ * weight > 0; env: an environment; env_lit: "environment_light", an environment and a table of weight > 0; smooth:
+ * "smooth_normals" and vertex normals; textured: "textures", textures and texture coordinates; weigh: "mis" and (direct or
+ * env_lit); lens: a lens radius > 0; plays: some bounce plays roulette, or < 0 for ptc_trace's own reading of `roulette` under
+ * `max_bounces`; emitters: the scene has an emissive material -- and the roulette argument the kernel gets: `roulette` where a
+ * bounce plays, else INT_MAX.  name_out: the kernel as a profile prints it, e.g. "k_megakernel_tex<true, false>".
+ * PTC_ERR_INVALID for a NULL out and for a name_capacity the name does not fit in (40 bytes hold every name). */
+int ptc_check_megakernel_instance(int direct, int env, int env_lit, int smooth, int textured, int weigh, int lens, int plays, int emitters,
+                                  int roulette, int max_bounces, char* name_out, uint32_t name_capacity, int* roulette_out);
 /* Entry points for primary rays ("beam"), checked on the host (no GPU): for every 8 x 8-pixel tile of a width x height
  * frame of `camera`, the entries k_beam computes for the mesh under the object matrix object_m16 (NULL: identity;
  * column-major), and for sample rays of the tile (corners and centre of the jitter range of every stride-th pixel) the
