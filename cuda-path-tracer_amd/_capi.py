@@ -137,6 +137,10 @@ class ptc_texture_loop_stats(C.Structure):
     _fields_ = [("lookups", C.c_uint64), ("fallbacks", C.c_uint64)]
 
 
+class ptc_normal_map_loop_stats(C.Structure):
+    _fields_ = [("bent", C.c_uint64), ("kept", C.c_uint64)]
+
+
 class ptc_texture_desc(C.Structure):
     _fields_ = [("rgba8", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("encoding", C.c_uint32), ("filter", C.c_uint32),
                 ("wrap", C.c_uint32)]
@@ -238,6 +242,7 @@ SIGNATURES = {
     "ptc_check_feed": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "ptc_check_frame_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ptc_frame_plan)]),
     "ptc_check_megakernel_instance": (C.c_int, [C.c_int] * 11 + [C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]),
+    "ptc_check_megakernel_instance2": (C.c_int, [C.c_int] * 12 + [C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]),
     "ptc_selftest_math": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ptc_selftest_rng": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
@@ -269,6 +274,12 @@ SIGNATURES = {
     "ptc_hit_surface": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "ptc_get_texture_loop_stats": (C.c_int, [_P, C.POINTER(ptc_texture_loop_stats)]),
     "ptc_check_texture_lookup": (C.c_int, [C.POINTER(ptc_texture_desc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ptc_set_normal_maps": (C.c_int, [_P, C.c_void_p, C.c_uint32]),
+    "ptc_get_normal_maps": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "ptc_normal_map_decode_table": (C.c_int, [C.c_void_p]),
+    "ptc_hit_shading_normal": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ptc_get_normal_map_loop_stats": (C.c_int, [_P, C.POINTER(ptc_normal_map_loop_stats)]),
+    "ptc_check_normal_map": (C.c_int, [C.POINTER(ptc_texture_desc)] + [C.c_void_p] * 12 + [C.c_uint32, C.c_void_p, C.c_void_p]),
     "ptc_check_shading_normal": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p, C.c_void_p]),
     "ptc_check_environment_light_pdf": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ptc_check_environment_light": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,

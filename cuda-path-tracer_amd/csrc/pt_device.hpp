@@ -12,6 +12,7 @@
 #include "pt_env.hpp"
 #include "pt_smooth.hpp"
 #include "pt_texture.hpp"
+#include "pt_normal_map.hpp"
 
 namespace pt {
 
@@ -511,6 +512,12 @@ struct DTex {
   const float* st;
   const uint32_t* mesh_first_index;
 };
+// Normal maps (section 5q; pt_normal_map.hpp).  material_normal_map: per material -1 or a texture of DTex's pool; table: the normal
+// maps' decode table, 256 floats.  They read DTex's texels, records, st and mesh_first_index.  material_normal_map null: no maps.
+struct DNmap {
+  const int32_t* material_normal_map;
+  const float* table;
+};
 // The loop counters: kLightStatLines lines of kLoopStatWords 64-bit words (a 128-byte line each), one add per wavefront and word
 // (the words: mega_path's table).  Not part of DeviceCounters, whose layout the feed depends on.
 constexpr uint32_t kLoopStatWords = 16u;
@@ -537,6 +544,7 @@ struct MegaFrame {
   DMis mis;
   DSmooth sm;
   DTex tx;
+  DNmap nm;
   bool emitters, weigh;
 };
 void launch_megakernel(hipStream_t s, const MegaFrame& f);
@@ -627,6 +635,11 @@ void launch_texture_sample(hipStream_t s, DTex tx, uint32_t texture, const float
 // zeros) and the albedo the loop would use at the hit (a miss: zeros); flags |= kFlagStackOverflow
 void launch_hit_surface(hipStream_t s, const DScene& scene, DTex tx, const float4* rays, uint32_t n, float2* st_out, float* albedo_out,
                         uint32_t* flags);
+// ptc_hit_shading_normal's kernel (pt_mega_nmap.hip): k_hit_surface's walk; per ray the normal the loop would hand evaluate_material
+// at the closest hit from what is set (sm.normals, nm.material_normal_map; either may be null) and what the rule did there
+// (nmap::kMiss .. kKept); flags |= kFlagStackOverflow
+void launch_hit_shading_normal(hipStream_t s, const DScene& scene, DSmooth sm, DTex tx, DNmap nm, const float4* rays, uint32_t n,
+                               float* normal_out, uint8_t* outcome_out, uint32_t* flags);
 // ptc_environment_light_pdf's kernel (pt_env.hip): one thread per unit direction, env_light::density
 void launch_env_light_pdf(hipStream_t s, DEnvLight el, uint32_t n, const float* dirs, uint32_t count, float* pdf);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,

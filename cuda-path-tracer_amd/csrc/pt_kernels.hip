@@ -275,8 +275,10 @@ void launch_megakernel(hipStream_t s, const MegaFrame& f)
   facts.lens = f.lens.radius > 0.0f;
   facts.plays = f.roulette != mega_rules::kNoRoulette;
   facts.emitters = f.emitters;
+  facts.bent = f.nm.material_normal_map != nullptr;
   const mega_rules::Instance in = mega_rules::instance(facts);
   switch (in.kernel) {
+    case Kernel::nmap: return launch_mega_nmap(s, f, in);
     case Kernel::tex: return launch_mega_tex(s, f, in);
     case Kernel::smooth: return launch_mega_smooth(s, f, in);
     case Kernel::mis: return launch_mega_mis(s, f, in);

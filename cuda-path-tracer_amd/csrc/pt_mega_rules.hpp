@@ -1,4 +1,4 @@
-// pt_mega_rules.hpp -- the instance rule of the megakernel: which of its 22 kernels a frame launches, and the roulette argument it
+// pt_mega_rules.hpp -- the instance rule of the megakernel: which of its 26 kernels a frame launches, and the roulette argument it
 // gets.  Shared by launch_megakernel (pt_kernels.hip) and the host's check (ptc_check_megakernel_instance,
 // tests/test_mega_instance_cpu.py); pure, host only, the only place the rule lives.
 #pragma once
@@ -14,18 +14,20 @@ namespace mega_rules {
 //   env_lit   "environment_light", env and a table of weight > 0     smooth    "smooth_normals" and vertex normals
 //   textured  "textures", textures and texture coordinates           weigh     "mis" and (direct or env_lit)
 //   lens      a lens radius > 0                                       plays     some bounce plays roulette (roulette_frame)
-//   emitters  the scene has an emissive material
+//   emitters  the scene has an emissive material                      bent      "normal_maps", textures, coordinates and a binding
 // The rule is total: it assumes no implication between them (env_lit without env, weigh without a light).
 struct Facts {
   bool direct, env, env_lit, smooth, textured, weigh, lens, plays, emitters;
+  bool bent = false;
 };
 
-// The kernels by family, in the rule's order; the units that hold them (the megakernel's five code objects):
-//   tex pt_mega_tex.hip; smooth pt_mega_smooth.hip; mis pt_mega_mis.hip; plain<.., false> pt_kernels.hip; the rest pt_mega_direct.hip
-enum class Kernel { tex, smooth, mis, env_light, env, direct_lens, direct, lens, plain };
+// The kernels by family, in the rule's order; the units that hold them (the megakernel's six code objects):
+//   nmap pt_mega_nmap.hip; tex pt_mega_tex.hip; smooth pt_mega_smooth.hip; mis pt_mega_mis.hip; plain<.., false> pt_kernels.hip; the rest pt_mega_direct.hip
+enum class Kernel { tex, smooth, mis, env_light, env, direct_lens, direct, lens, plain, nmap };
 constexpr const char* kKernelNames[] = {"k_megakernel_tex",         "k_megakernel_smooth", "k_megakernel_mis",
                                         "k_megakernel_env_light",   "k_megakernel_env",    "k_megakernel_direct_lens",
-                                        "k_megakernel_direct",      "k_megakernel_lens",   "k_megakernel"};
+                                        "k_megakernel_direct",      "k_megakernel_lens",   "k_megakernel",
+                                        "k_megakernel_nmap"};
 
 // a, b: the kernel's template arguments in its own order (`args` of them count)
 struct Instance {
@@ -42,12 +44,14 @@ constexpr int kNoRoulette = INT_MAX;
 inline int roulette_argument(bool plays, int roulette) { return plays ? roulette : kNoRoulette; }
 
 // The rule: the first row that matches.
+//   0 bent      k_megakernel_nmap<weigh, smooth>
 //   1 textured  k_megakernel_tex<weigh, smooth>      5 env     k_megakernel_env<direct>
 //   2 smooth    k_megakernel_smooth<weigh>           6 direct  k_megakernel_direct_lens<plays> under a lens, else k_megakernel_direct<plays>
 //   3 weigh     k_megakernel_mis                     7 lens    k_megakernel_lens<emitters, plays>
 //   4 env_lit   k_megakernel_env_light               8 else    k_megakernel<emitters, plays>
 inline Instance instance(const Facts& f)
 {
+  if (f.bent) return {Kernel::nmap, 2, f.weigh, f.smooth};
   if (f.textured) return {Kernel::tex, 2, f.weigh, f.smooth};
   if (f.smooth) return {Kernel::smooth, 1, f.weigh, false};
   if (f.weigh) return {Kernel::mis, 0, false, false};

@@ -1,10 +1,10 @@
 // pt_megakernel.inc -- the megakernel's loop, the whole path in one thread (path_tracing_mega_kernel, path_tracer.cu:227-269; one RNG
 // stream per pixel: a different image from streaming mode at the same seed, a property of the reference): mega_path, the two plain
 // kernels around it, and what every unit's launcher shares.  Included inside namespace pt, after pt_kernels_common.inc and with
-// pt_light_sample.hpp and pt_env_light.hpp in front, by the five units that hold its 22 instances: pt_kernels.hip (the plain loop
-// without roulette, beside the closest-hit kernels as ever), pt_mega_direct.hip, pt_mega_mis.hip, pt_mega_smooth.hip and
-// pt_mega_tex.hip -- a unit per feature, so that the code objects of the features before it stay the ones they were (DESIGN section
-// 5h).  Which instance a frame launches: pt_mega_rules.hpp.
+// pt_light_sample.hpp and pt_env_light.hpp in front, by the six units that hold its 26 instances: pt_kernels.hip (the plain loop
+// without roulette, beside the closest-hit kernels as ever), pt_mega_direct.hip, pt_mega_mis.hip, pt_mega_smooth.hip,
+// pt_mega_tex.hip and pt_mega_nmap.hip -- a unit per feature, so that the code objects of the features before it stay the ones they
+// were (DESIGN section 5h).  Which instance a frame launches: pt_mega_rules.hpp.
 //
 // The options of the loop, one bit of kF each: what the option adds; its DESIGN section, where the reasons are; the 64-bit words of a
 // loop-counter line it adds to (`stats`: kLightStatLines lines of kLoopStatWords words, one add per wavefront); the kernels built with it.
@@ -49,9 +49,15 @@
 //   kMegaTex       (with kMegaEnvLight) at a triangle hit on a diffuse or metal material with a texture bound, immediately before
 //                  evaluate_material, texmap::albedo's colour (pt_texture.hpp: the texel at the interpolated corner coordinates times
 //                  p[0..2]) replaces p[0..2] in a copy of the material.  Every light is a run-time choice as under kMegaSmooth.
-//                  5o; words 12, 13 lookups, fall-backs; k_megakernel_tex<..>
+//                  5o; words 12, 13 lookups, fall-backs; k_megakernel_tex<..>, k_megakernel_nmap<..>
+//   kMegaNmap      (with kMegaTex) at the same place and on the same hits, for a material with a normal map bound (nm.material_normal_map),
+//                  nmap::shade's normal (pt_normal_map.hpp: the map's texel in the tangent frame of the corners' coordinates, about hn)
+//                  replaces hn from there on -- evaluate_material, the light samples, bsdf_pdf; the normal plane has hn as it was.  Where
+//                  it bent the normal, kMegaSmooth's culls and its absorption apply as at a triangle under kMegaSmooth.  The albedo fetch
+//                  becomes a run-time choice, tx.material_texture.
+//                  5q; words 14, 15 bent normals, fall-backs (a flat texel counts in neither); k_megakernel_nmap<..>
 constexpr uint32_t kMegaEmit = 1u, kMegaRoulette = 2u, kMegaDirect = 4u, kMegaLens = 8u, kMegaEnv = 16u, kMegaEnvLight = 32u, kMegaMis = 64u,
-                   kMegaSmooth = 128u, kMegaTex = 256u;
+                   kMegaSmooth = 128u, kMegaTex = 256u, kMegaNmap = 512u;
 // what every instance with an environment is built with: emitters and roulette compiled in, pinhole or lens by lens.radius
 constexpr uint32_t kMegaEnvBase = kMegaEmit | kMegaRoulette | kMegaEnv;
 // ... and every instance that samples the environment: the lamps' samples by lt.records
@@ -65,11 +71,13 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
                                           const DLens lens = DLens{0.0f, 0.0f}, const DEnv env = DEnv{nullptr, 0u, 0u},
                                           const DEnvLight el = DEnvLight{nullptr}, const DMis mis = DMis{nullptr},
                                           const DSmooth sm = DSmooth{nullptr, nullptr},
-                                          const DTex tx = DTex{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr})
+                                          const DTex tx = DTex{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+                                          const DNmap nm = DNmap{nullptr, nullptr})
 {
   constexpr bool kEmit = kF & kMegaEmit, kRoulette = kF & kMegaRoulette, kDirect = kF & kMegaDirect, kLens = kF & kMegaLens, kEnv = kF & kMegaEnv,
-                 kEnvLight = kF & kMegaEnvLight, kMis = kF & kMegaMis, kSmooth = kF & kMegaSmooth, kTex = kF & kMegaTex;
+                 kEnvLight = kF & kMegaEnvLight, kMis = kF & kMegaMis, kSmooth = kF & kMegaSmooth, kTex = kF & kMegaTex, kNmap = kF & kMegaNmap;
   constexpr bool kDyn = kSmooth || kTex;  // every light and the environment are run-time choices
+  static_assert(!kNmap || kTex, "the normal-mapped instances read the textured instances' pool and coordinates");
   static_assert(!kTex || kEnvLight, "the textured instances sample lamps and environment by run-time choice");
   static_assert(!kSmooth || kEnvLight, "the smooth instances sample lamps and environment by run-time choice");
   static_assert(!kEnvLight || (kEnv && kDirect), "the environment-light instance has an environment and a radiance sum");
@@ -82,6 +90,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
   [[maybe_unused]] uint32_t m_emit = 0u, m_miss = 0u;
   [[maybe_unused]] uint32_t s_formed = 0u, s_fallback = 0u, s_absorbed = 0u, s_culled = 0u;
   [[maybe_unused]] uint32_t t_lookup = 0u, t_fallback = 0u;
+  [[maybe_unused]] uint32_t b_bent = 0u, b_kept = 0u;
   const bool lamps = !kEnvLight || lt.records != nullptr;
   const bool env_lamp = !(kMis || kDyn) || el.table != nullptr;  // (kEnvLight) the environment is sampled
   if (s < pix_count) {
@@ -131,8 +140,9 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
         else color = color * sky<kEnv>(ray.d, env);
         break;
       }
-      f3 hn = rec.n;  // the shading normal: the geometric one but at a triangle hit under kSmooth
+      f3 hn = rec.n;  // the shading normal: the geometric one but at a triangle hit under kSmooth, and behind a bent hit under kNmap
       [[maybe_unused]] bool tri = false;
+      [[maybe_unused]] bool bent = false;  // (kNmap) the normal map replaced hn at this hit
       if constexpr (kSmooth) {
         if (at.first != kNoChild) {
           tri = true;
@@ -177,7 +187,32 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       if constexpr (kTex) {
         DMaterial tmat = mat;
         if (at.first != kNoChild && mat.type <= 1) {
-          const int32_t ti = tx.material_texture[rec.mat];
+          int32_t ti;
+          if constexpr (kNmap) {  // the map first: every load of the hit ahead of the first use, the flat test ahead of the tangents
+            ti = tx.material_texture ? tx.material_texture[rec.mat] : -1;
+            const int32_t ni = nm.material_normal_map[rec.mat];
+            if (ni >= 0) {
+              const uint32_t mesh = sc.object_mesh[at.object];
+              const float* stp = tx.st + 2u * ((size_t)tx.mesh_first_index[mesh] + at.first);
+              const uint32_t* idx = sc.mesh_views[mesh].indices + at.first;
+              const float* pos = sc.mesh_views[mesh].positions;
+              const texmap::Record nrec = tx.records[ni];
+              const float stc[6] = {stp[0], stp[1], stp[2], stp[3], stp[4], stp[5]};
+              const f3 p0 = ld3(pos + 3u * (size_t)idx[0]), p1 = ld3(pos + 3u * (size_t)idx[1]), p2 = ld3(pos + 3u * (size_t)idx[2]);
+              f3 nn;
+              const uint32_t how = nmap::shade(tx.texels, nrec, nm.table, p0, p1, p2, stc, stc + 2, stc + 4, at.u, at.v, sc.objects[at.object].m, hn,
+                                               rec.n, ray.d, nn);
+              if (how == nmap::kBent) {
+                bent = true;
+                hn = nn;
+                ++b_bent;
+              } else if (how == nmap::kKept) {
+                ++b_kept;
+              }
+            }
+          } else {
+            ti = tx.material_texture[rec.mat];
+          }
           if (ti >= 0) {
             const uint32_t mesh = sc.object_mesh[at.object];
             const float* st = tx.st + 2u * ((size_t)tx.mesh_first_index[mesh] + at.first);
@@ -218,8 +253,8 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
               es = env_light::sample_point(el.table, env.texels, env.n, hn, pixel, iteration, 4u * (uint32_t)i);
             }
           }
-          if constexpr (kSmooth) {
-            if (tri && es.sampled && dot(es.w, rec.n) <= 0.0f) {  // behind the geometry: not sampled
+          if constexpr (kSmooth || kNmap) {
+            if ((kSmooth ? tri : bent) && es.sampled && dot(es.w, rec.n) <= 0.0f) {  // behind the geometry: not sampled
               es.sampled = false;
               ++s_culled;
             }
@@ -235,8 +270,8 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
             } else {
               ls = light_sample_point(lt, rec.p, hn, pixel, iteration, 3u * (uint32_t)i);
             }
-            if constexpr (kSmooth) {
-              if (tri && ls.sampled && dot(ls.w, rec.n) <= 0.0f) {
+            if constexpr (kSmooth || kNmap) {
+              if ((kSmooth ? tri : bent) && ls.sampled && dot(ls.w, rec.n) <= 0.0f) {
                 ls.sampled = false;
                 ++s_culled;
               }
@@ -270,8 +305,8 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
           }
         }
       }
-      if constexpr (kSmooth) {
-        if (tri && mat.type != 2 && dot(ray.d, rec.n) <= 0.0f) {  // the new direction enters the geometry: absorbed
+      if constexpr (kSmooth || kNmap) {
+        if ((kSmooth ? tri : bent) && mat.type != 2 && dot(ray.d, rec.n) <= 0.0f) {  // the new direction enters the geometry: absorbed
           ++s_absorbed;
           color = mk3(0.0f, 0.0f, 0.0f);
           break;
@@ -288,6 +323,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
   [[maybe_unused]] uint32_t me = m_emit, mm = m_miss;
   [[maybe_unused]] uint32_t qf = s_formed, qb = s_fallback, qa = s_absorbed, qc = s_culled;
   [[maybe_unused]] uint32_t tl = t_lookup, tf = t_fallback;
+  [[maybe_unused]] uint32_t bb = b_bent, bk = b_kept;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     sum += __shfl_down(sum, off, 64);
@@ -305,7 +341,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       me += __shfl_down(me, off, 64);
       mm += __shfl_down(mm, off, 64);
     }
-    if constexpr (kSmooth) {
+    if constexpr (kSmooth || kNmap) {
       qf += __shfl_down(qf, off, 64);
       qb += __shfl_down(qb, off, 64);
       qa += __shfl_down(qa, off, 64);
@@ -314,6 +350,10 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
     if constexpr (kTex) {
       tl += __shfl_down(tl, off, 64);
       tf += __shfl_down(tf, off, 64);
+    }
+    if constexpr (kNmap) {
+      bb += __shfl_down(bb, off, 64);
+      bk += __shfl_down(bk, off, 64);
     }
   }
   if (threadIdx.x == 0u) {
@@ -332,7 +372,7 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
         if (me) atomicAdd(&line[6], (unsigned long long)me);
         if (mm) atomicAdd(&line[7], (unsigned long long)mm);
       }
-      if constexpr (kSmooth) {
+      if constexpr (kSmooth || kNmap) {
         if (qf) atomicAdd(&line[8], (unsigned long long)qf);
         if (qb) atomicAdd(&line[9], (unsigned long long)qb);
         if (qa) atomicAdd(&line[10], (unsigned long long)qa);
@@ -341,6 +381,10 @@ __device__ __forceinline__ void mega_path(const DScene& sc, const DLights& lt, c
       if constexpr (kTex) {
         if (tl) atomicAdd(&line[12], (unsigned long long)tl);
         if (tf) atomicAdd(&line[13], (unsigned long long)tf);
+      }
+      if constexpr (kNmap) {
+        if (bb) atomicAdd(&line[14], (unsigned long long)bb);
+        if (bk) atomicAdd(&line[15], (unsigned long long)bk);
       }
     }
   }
@@ -368,7 +412,7 @@ __global__ __launch_bounds__(kWave) void k_megakernel_lens(DScene sc, DCamera ca
                                                                                      counters, nullptr, roulette, s_stack + threadIdx.x, lens);
 }
 
-// ---- the host's side: what the five units' launchers share.  A unit's launcher (launch_mega_*, below launch_megakernel in
+// ---- the host's side: what the six units' launchers share.  A unit's launcher (launch_mega_*, below launch_megakernel in
 // pt_kernels.hip) gets the frame and the instance the rule chose, picks that kernel among its own by the instance's template
 // arguments and launches it through one of these: one thread per pixel of the band, a wavefront per workgroup.
 void launch_mega_plain(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);   // pt_kernels.hip
@@ -376,6 +420,7 @@ void launch_mega_direct(hipStream_t s, const MegaFrame& f, const mega_rules::Ins
 void launch_mega_mis(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);     // pt_mega_mis.hip
 void launch_mega_smooth(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);  // pt_mega_smooth.hip
 void launch_mega_tex(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);     // pt_mega_tex.hip
+void launch_mega_nmap(hipStream_t s, const MegaFrame& f, const mega_rules::Instance& in);    // pt_mega_nmap.hip
 template <typename K, typename... A>
 void mega_go(K kernel, hipStream_t s, const MegaFrame& f, const A&... args)
 {

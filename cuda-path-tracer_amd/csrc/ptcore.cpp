@@ -220,6 +220,7 @@ const ParamRow kParams[] = {
     {"mis", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->mis = v != 0; }},
     {"smooth_normals", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->smooth_normals = v != 0; }},
     {"textures", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->textures = v != 0; }},
+    {"normal_maps", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->normal_maps = v != 0; }},
     {"roulette", 0, 64, " must be in [0,64]", kAnyTime, [](ptc_ctx* c, int v) { c->roulette = v; }},
     {"denoise_variant", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_variant = v; }},
     {"frames_in_flight", 1, 256, " must be in [1,256]", kBeforeResize, [](ptc_ctx* c, int v) { c->frames_in_flight = v; }},
@@ -934,6 +935,22 @@ int ptc_get_texture_loop_stats(ptc_ctx* ctx, ptc_texture_loop_stats* out)
   for (uint32_t l = 0; l < kLightStatLines; ++l) {
     out->lookups += host[(size_t)kLoopStatWords * l + 12u];
     out->fallbacks += host[(size_t)kLoopStatWords * l + 13u];
+  }
+  return PTC_OK;
+}
+
+int ptc_get_normal_map_loop_stats(ptc_ctx* ctx, ptc_normal_map_loop_stats* out)
+{
+  if (!ctx || !out) return PTC_ERR_INVALID;
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;
+  *out = ptc_normal_map_loop_stats{};
+  if (ctx->loop_stats_clear) return PTC_OK;  // nothing that counts has been launched since ptc_restart
+  std::vector<unsigned long long> host((size_t)kLightStatLines * kLoopStatWords);
+  HIP_TRY(ctx, hipMemcpy(host.data(), ctx->loop_stats, kLoopStatBytes, hipMemcpyDeviceToHost));
+  for (uint32_t l = 0; l < kLightStatLines; ++l) {
+    out->bent += host[(size_t)kLoopStatWords * l + 14u];
+    out->kept += host[(size_t)kLoopStatWords * l + 15u];
   }
   return PTC_OK;
 }

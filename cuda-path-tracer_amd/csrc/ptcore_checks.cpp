@@ -240,8 +240,17 @@ int ptc_check_frame_plan(uint32_t width, uint32_t height, int frames_in_flight, 
 int ptc_check_megakernel_instance(int direct, int env, int env_lit, int smooth, int textured, int weigh, int lens, int plays, int emitters,
                                   int roulette, int max_bounces, char* name_out, uint32_t name_capacity, int* roulette_out)
 {
+  return ptc_check_megakernel_instance2(direct, env, env_lit, smooth, textured, weigh, lens, plays, emitters, 0, roulette, max_bounces, name_out,
+                                        name_capacity, roulette_out);
+}
+
+// ... with the tenth fact
+int ptc_check_megakernel_instance2(int direct, int env, int env_lit, int smooth, int textured, int weigh, int lens, int plays, int emitters,
+                                   int bent, int roulette, int max_bounces, char* name_out, uint32_t name_capacity, int* roulette_out)
+{
   if (!name_out || !roulette_out) return PTC_ERR_INVALID;
   mega_rules::Facts f;
+  f.bent = bent != 0;
   f.direct = direct != 0;
   f.env = env != 0;
   f.env_lit = env_lit != 0;
@@ -611,6 +620,39 @@ int ptc_check_texture_lookup(const ptc_texture_desc* desc, const float* st, uint
     rgb_out[3u * (size_t)i + 1u] = c.y;
     rgb_out[3u * (size_t)i + 2u] = c.z;
     if (rejected_out) rejected_out[i] = ok ? (uint8_t)0 : (uint8_t)1;
+  }
+  return PTC_OK;
+}
+
+// The normal map's rule (pt_normal_map.hpp) on the host: steps 1 .. 8 on the caller's own texels
+int ptc_check_normal_map(const ptc_texture_desc* desc, const float* p0, const float* p1, const float* p2, const float* st0, const float* st1,
+                         const float* st2, const float* u, const float* v, const float* m16, const float* b, const float* g, const float* d,
+                         uint32_t count, float* normal_out, uint8_t* outcome_out)
+{
+  if (!desc || !m16 || (count != 0u && (!p0 || !p1 || !p2 || !st0 || !st1 || !st2 || !u || !v || !b || !g || !d || !normal_out || !outcome_out)))
+    return fail(nullptr, PTC_ERR_INVALID, "normal map: an array is NULL");
+  const std::string why = texture_refusal(*desc);
+  if (!why.empty()) return fail(nullptr, PTC_ERR_INVALID, "the texture " + why);
+  const size_t texels = (size_t)desc->width * desc->height;
+  std::vector<uint32_t> words(texels);
+  for (size_t i = 0; i < texels; ++i)
+    words[i] = (uint32_t)desc->rgba8[4u * i] | ((uint32_t)desc->rgba8[4u * i + 1u] << 8) | ((uint32_t)desc->rgba8[4u * i + 2u] << 16) |
+               ((uint32_t)desc->rgba8[4u * i + 3u] << 24);
+  float table[texmap::kTableEntries];
+  nmap::decode_table(table);
+  const texmap::Record rec{0u, desc->width, desc->height, texmap::pack_flags(desc->encoding, desc->filter, desc->wrap)};
+  m4 m;
+  for (int c = 0; c < 4; ++c)
+    for (int r = 0; r < 4; ++r) m.c[c][r] = m16[4 * c + r];
+  auto at3 = [](const float* a, uint32_t i) { return mk3(a[3u * (size_t)i], a[3u * (size_t)i + 1u], a[3u * (size_t)i + 2u]); };
+  for (uint32_t i = 0; i < count; ++i) {
+    f3 n;
+    const uint32_t how = nmap::shade(words.data(), rec, table, at3(p0, i), at3(p1, i), at3(p2, i), st0 + 2u * (size_t)i, st1 + 2u * (size_t)i,
+                                     st2 + 2u * (size_t)i, u[i], v[i], m, at3(b, i), at3(g, i), at3(d, i), n);
+    normal_out[3u * (size_t)i] = n.x;
+    normal_out[3u * (size_t)i + 1u] = n.y;
+    normal_out[3u * (size_t)i + 2u] = n.z;
+    outcome_out[i] = (uint8_t)how;
   }
   return PTC_OK;
 }

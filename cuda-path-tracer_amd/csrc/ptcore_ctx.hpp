@@ -92,6 +92,13 @@ struct ptc_scene_state {
   uint32_t texture_count = 0;
   uint64_t texel_count = 0;
   bool textures_set = false;
+  // normal maps (ptc_set_normal_maps): per material -1 or a texture of the pool above (replaced as a whole by every
+  // call that sets any; dropped by every ptc_set_textures, whose pool its indices name) and the decode table (allocated by the
+  // first) -- of the scene's pool; nmap_bound: the materials with a map
+  int32_t* nmap_material = nullptr;
+  float* nmap_table = nullptr;
+  uint32_t nmap_bound = 0;
+  bool nmaps_set = false;
 };
 
 // the last epoch of a lap of look-back launches on a slot's tile descriptors (30 bits: pt_shade_tile.inc; ptcore_trace.cpp, next_epoch)
@@ -314,12 +321,15 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   // "textures" (DESIGN section 5o): a frame of a scene with textures and texture coordinates takes the colour of a bound diffuse or
   // metal triangle hit from its texture (k_megakernel_tex); without either it launches what it launched before
   bool textures = false;
+  // "normal_maps" (DESIGN section 5q): a frame of a scene with textures, texture coordinates and a normal-map binding bends the normal
+  // of a bound diffuse or metal triangle hit by its map (k_megakernel_nmap); without any of them it launches what it launched before
+  bool normal_maps = false;
   const uint4* env_table = nullptr;
   bool env_table_known = false;
   ptc_environment_light_stats env_direct{};  // ptc_environment_light since ptc_reset_profile
   // device: kLightStatLines lines of kLoopStatWords words (0 .. 2 the lamps': diffuse hits, shadow rays, unoccluded; 3 .. 5 the environment's;
   // 6, 7 "mis": weighted emitter hits, weighted misses; 8 .. 11 "smooth_normals": shading normals, fall-backs, absorbed, culled;
-  // 12, 13 "textures": lookups, fall-backs)
+  // 12, 13 "textures": lookups, fall-backs; 14, 15 "normal_maps": bent normals, fall-backs)
   unsigned long long* loop_stats = nullptr;
   bool loop_stats_clear = true;              // ptc_restart has run since the last direct-lit launch: that launch's stream zeroes the block first
   // the display transform (ptc_set_display; ptcore_display.cpp).  The default is the reference display: the presents

@@ -485,6 +485,41 @@ int ptc_hit_surface(ptc_ctx* ctx, const float* rays, uint32_t n, float* st_out, 
   return PTC_OK;
 }
 
+// The normal the loop would shade with at the closest hit, from what is set: k_hit_shading_normal, ptc_hit_surface's walk
+int ptc_hit_shading_normal(ptc_ctx* ctx, const float* rays, uint32_t n, float* normal_out, uint8_t* outcome_out)
+{
+  if (!ctx || !rays || !normal_out || !outcome_out) return PTC_ERR_INVALID;
+  int rc;
+  if (!query_prologue(ctx, n, "rays", nullptr, &rc)) return rc;
+  QueryRun q(ctx, false);
+  float4* d_rays = nullptr;
+  float* d_normal = nullptr;
+  uint8_t* d_outcome = nullptr;
+  uint32_t* d_flags = nullptr;
+  rc = q.alloc(&d_rays, 2u * (size_t)n);
+  if (!rc) rc = q.alloc(&d_normal, 3u * (size_t)n);
+  if (!rc) rc = q.alloc(&d_outcome, n);
+  if (!rc) rc = q.alloc(&d_flags, 1);
+  if (rc) return rc;
+  uint32_t dev_flags = 0u;
+  const DSmooth sm{ctx->normals_set ? ctx->vertex_normals : nullptr, ctx->mesh_first_vertex};
+  const DNmap nm{ctx->nmaps_set ? ctx->nmap_material : nullptr, ctx->nmap_table};
+  auto run = [&]() -> int {
+    HIP_TRY(ctx, hipMemcpyAsync(d_rays, rays, 8u * (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, sizeof(uint32_t), ctx->stream));
+    launch_hit_shading_normal(ctx->stream, ctx->scene, sm, textures_of(ctx), nm, d_rays, n, d_normal, d_outcome, d_flags);
+    if (int r2 = check_last(ctx, "hit_shading_normal")) return r2;
+    HIP_TRY(ctx, hipMemcpyAsync(normal_out, d_normal, 3u * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(outcome_out, d_outcome, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&dev_flags, d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PTC_OK;
+  };
+  if ((rc = q.finish(run())) != PTC_OK) return rc;
+  if (dev_flags & kFlagStackOverflow) return fail(ctx, PTC_ERR_STACK, "traversal stack overflow in ptc_hit_shading_normal");
+  return PTC_OK;
+}
+
 // The lookup of one texture of the pool on the device: k_texture_sample, one thread per coordinate pair
 int ptc_sample_texture(ptc_ctx* ctx, uint32_t texture, const float* st, uint32_t n, float* rgb_out, uint8_t* rejected_out)
 {

@@ -800,6 +800,17 @@ int mesh_tables(ptc_ctx* ctx, const std::vector<MeshWork>& meshes, NewScene& n)
 
 }  // namespace
 
+// gives one array of the scene's pool back (the textures' and the normal maps' replaced arrays)
+template <typename T>
+static void drop_scene_array(ptc_ctx* ctx, T*& p)
+{
+  if (!p) return;
+  auto& pool = ctx->scene_allocs;
+  pool.erase(std::remove(pool.begin(), pool.end(), (void*)p), pool.end());
+  (void)hipFree(p);
+  p = nullptr;
+}
+
 extern "C" {
 
 int ptc_upload_scene(ptc_ctx* ctx, const ptc_scene_desc* s)
@@ -1012,17 +1023,14 @@ int ptc_set_textures(ptc_ctx* ctx, const ptc_texture_desc* textures, uint32_t te
   }
   if (int rc = bind_device(ctx)) return rc;
   if (int rc = sync_frames(ctx)) return rc;  // frames queued or in flight were asked for with what was set
-  auto drop = [&](auto*& p) {  // gives one array of the scene's pool back
-    if (!p) return;
-    auto& pool = ctx->scene_allocs;
-    pool.erase(std::remove(pool.begin(), pool.end(), (void*)p), pool.end());
-    (void)hipFree(p);
-    p = nullptr;
-  };
+  auto drop = [&](auto*& p) { drop_scene_array(ctx, p); };
   if (!textures) {
     drop(ctx->tex_texels);
     drop(ctx->tex_records);
     drop(ctx->tex_material);
+    drop(ctx->nmap_material);  // its indices named this pool
+    ctx->nmap_bound = 0;
+    ctx->nmaps_set = false;
     ctx->texture_count = 0;
     ctx->texel_count = 0;
     ctx->textures_set = false;
@@ -1056,6 +1064,9 @@ int ptc_set_textures(ptc_ctx* ctx, const ptc_texture_desc* textures, uint32_t te
   drop(ctx->tex_texels);
   drop(ctx->tex_records);
   drop(ctx->tex_material);
+  drop(ctx->nmap_material);  // its indices named the old pool
+  ctx->nmap_bound = 0;
+  ctx->nmaps_set = false;
   ctx->scene_allocs.insert(ctx->scene_allocs.end(), fresh.begin(), fresh.end());
   fresh.clear();
   ctx->tex_texels = d_texels;
@@ -1074,6 +1085,77 @@ int ptc_get_textures(const ptc_ctx* ctx, uint32_t* texture_count, uint64_t* texe
   if (texture_count) *texture_count = set ? ctx->texture_count : 0u;
   if (texel_count) *texel_count = set ? ctx->texel_count : 0u;
   return set ? 1 : 0;
+}
+
+// The normal-map binding beside the textures: ptc_set_textures' shape -- every refusal before anything is touched,
+// the new binding uploaded beside the old one
+int ptc_set_normal_maps(ptc_ctx* ctx, const int32_t* material_normal_map, uint32_t material_count)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (!ctx->has_scene) return fail(ctx, PTC_ERR_NO_SCENE, "no scene uploaded");
+  if ((material_normal_map == nullptr) != (material_count == 0u))
+    return fail(ctx, PTC_ERR_INVALID, "normal maps: NULL and 0 go together (they remove the binding)");
+  uint32_t bound = 0;
+  if (material_normal_map) {
+    if (!ctx->textures_set) return fail(ctx, PTC_ERR_INVALID, "normal maps: no textures are set (ptc_set_textures first)");
+    if (material_count != ctx->material_count)
+      return fail(ctx, PTC_ERR_INVALID, "normal maps: " + std::to_string(material_count) + " bindings for a scene of " +
+                                            std::to_string(ctx->material_count) + " materials");
+    for (uint32_t m = 0; m < material_count; ++m) {
+      if (material_normal_map[m] < -1 || material_normal_map[m] >= (int64_t)ctx->texture_count)
+        return fail(ctx, PTC_ERR_INVALID, "normal maps: material " + std::to_string(m) + " is bound to texture " +
+                                              std::to_string(material_normal_map[m]) + " of " + std::to_string(ctx->texture_count));
+      if (material_normal_map[m] >= 0) ++bound;
+    }
+  }
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;  // frames queued or in flight were asked for with what was set
+  auto drop = [&](auto*& p) { drop_scene_array(ctx, p); };
+  if (!material_normal_map) {
+    drop(ctx->nmap_material);
+    ctx->nmap_bound = 0;
+    ctx->nmaps_set = false;
+    return PTC_OK;
+  }
+  std::vector<void*> fresh;
+  struct Guard {
+    std::vector<void*>& p;
+    ~Guard() { free_pool(p); }
+  } guard{fresh};
+  int32_t* d_material = nullptr;
+  float* d_table = nullptr;
+  if (int rc = dev_alloc(ctx, fresh, &d_material, (size_t)material_count)) return rc;
+  if (!ctx->nmap_table)
+    if (int rc = dev_alloc(ctx, fresh, &d_table, (size_t)texmap::kTableEntries)) return rc;
+  HIP_TRY(ctx, hipMemcpy(d_material, material_normal_map, material_count * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (d_table) {
+    float table[texmap::kTableEntries];
+    nmap::decode_table(table);
+    HIP_TRY(ctx, hipMemcpy(d_table, table, sizeof table, hipMemcpyHostToDevice));
+  }
+  // the commit: nothing below can fail
+  drop(ctx->nmap_material);
+  ctx->scene_allocs.insert(ctx->scene_allocs.end(), fresh.begin(), fresh.end());
+  fresh.clear();
+  ctx->nmap_material = d_material;
+  if (d_table) ctx->nmap_table = d_table;
+  ctx->nmap_bound = bound;
+  ctx->nmaps_set = true;
+  return PTC_OK;
+}
+
+int ptc_get_normal_maps(const ptc_ctx* ctx, uint32_t* bound_materials)
+{
+  const bool set = ctx && ctx->has_scene && ctx->nmaps_set;
+  if (bound_materials) *bound_materials = set ? ctx->nmap_bound : 0u;
+  return set ? 1 : 0;
+}
+
+int ptc_normal_map_decode_table(float* out256)
+{
+  if (!out256) return fail(nullptr, PTC_ERR_INVALID, "normal map decode table: out is NULL");
+  nmap::decode_table(out256);
+  return PTC_OK;
 }
 
 int ptc_texture_decode_table(uint32_t encoding, float* out256)

@@ -23,6 +23,9 @@ const char* const kSmoothNeedsMegakernel =
 // ... and "textures" 1
 const char* const kTexturesNeedMegakernel =
     "textures are rendered by the megakernel method only (ptc_set_method(PTC_METHOD_MEGAKERNEL)); the streaming loop's hit records carry no primitive";
+// ... and "normal_maps" 1
+const char* const kNormalMapsNeedMegakernel =
+    "normal_maps are rendered by the megakernel method only (ptc_set_method(PTC_METHOD_MEGAKERNEL)); the streaming loop's hit records carry no primitive";
 
 // the epoch of the next look-back launch on a slot's tile descriptors (k_shade_fused, the listing k_raygen / k_spheres).  After
 // kMaxEpoch the epochs start at 1 again, and a descriptor that no launch of the finished lap has overwritten (a tile above a band
@@ -465,6 +468,8 @@ MegaFrame mega_frame(const ptc_ctx* ctx, DeviceCounters* counters)
   const bool env_lit = ctx->environment_light && env && ctx->env_table;  // (section 5k) a map of weight > 0; else as with 0
   const bool smooth = ctx->smooth_normals && ctx->normals_set;           // (section 5n) a scene with vertex normals; else as with 0
   const bool textured = ctx->textures && ctx->textures_set && ctx->texcoords_set;  // (section 5o) textures and coordinates; else as with 0
+  // (section 5q) a pool, coordinates and a binding that names a map; else as with 0
+  const bool bent = ctx->normal_maps && ctx->textures_set && ctx->texcoords_set && ctx->nmaps_set && ctx->nmap_bound > 0u;
   MegaFrame f{};
   f.scene = ctx->scene;
   f.lights = direct ? DLights{ctx->light_records, ctx->light_thresholds, ctx->light_info.lights, ctx->light_last, ctx->scene.objects,
@@ -477,14 +482,18 @@ MegaFrame mega_frame(const ptc_ctx* ctx, DeviceCounters* counters)
   f.max_bounces = ctx->max_bounces;
   f.fb = ctx->fb;
   f.counters = counters;
-  f.stats = direct || env_lit || smooth || textured ? ctx->loop_stats : nullptr;  // the frames that count in the loop-counter lines
+  f.stats = direct || env_lit || smooth || textured || bent ? ctx->loop_stats : nullptr;  // the frames that count in the loop-counter lines
   f.roulette = mega_rules::roulette_argument(roulette_frame(ctx), ctx->roulette);
   f.lens = frame_lens(ctx);
   f.env = env ? ctx->env : DEnv{nullptr, 0u, 0u};
   f.el = DEnvLight{env_lit ? ctx->env_table : nullptr};
   f.mis = DMis{direct ? ctx->light_material_pdf : nullptr};
   f.sm = DSmooth{smooth ? ctx->vertex_normals : nullptr, ctx->mesh_first_vertex};
-  f.tx = textured ? DTex{ctx->tex_texels, ctx->tex_records, ctx->tex_material, ctx->tex_table, ctx->texcoords, ctx->mesh_first_index} : DTex{};
+  // under a normal map alone the pool and the coordinates without the colour binding: the albedo fetch reads material_texture
+  f.tx = textured || bent ? DTex{ctx->tex_texels, ctx->tex_records, textured ? ctx->tex_material : nullptr, ctx->tex_table, ctx->texcoords,
+                                 ctx->mesh_first_index}
+                          : DTex{};
+  f.nm = bent ? DNmap{ctx->nmap_material, ctx->nmap_table} : DNmap{nullptr, nullptr};
   f.emitters = ctx->has_emitters;
   f.weigh = ctx->mis && (direct || env_lit);  // (section 5l) a frame that samples neither light weighs nothing
   return f;
@@ -604,6 +613,7 @@ int ptc_trace_begin(ptc_ctx* ctx, const ptc_camera* camera)
   if (ctx->mis) return fail(ctx, PTC_ERR_INVALID, kMisNeedsMegakernel);
   if (ctx->smooth_normals) return fail(ctx, PTC_ERR_INVALID, kSmoothNeedsMegakernel);
   if (ctx->textures) return fail(ctx, PTC_ERR_INVALID, kTexturesNeedMegakernel);
+  if (ctx->normal_maps) return fail(ctx, PTC_ERR_INVALID, kNormalMapsNeedMegakernel);
   // (ptc_trace stops at max_iterations; nothing else stands between the stepwise calls and ptc_trace_end's ++iteration)
   if (ctx->iteration == INT_MAX) return fail(ctx, PTC_ERR_INVALID, "the iteration counter is at INT_MAX: ptc_restart or ptc_set_iteration first");
   if (int rc = flush_pending(ctx)) return rc;
@@ -686,6 +696,7 @@ int ptc_trace(ptc_ctx* ctx, const ptc_camera* camera)
   if (ctx->mis && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kMisNeedsMegakernel);
   if (ctx->smooth_normals && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kSmoothNeedsMegakernel);
   if (ctx->textures && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kTexturesNeedMegakernel);
+  if (ctx->normal_maps && ctx->method != PTC_METHOD_MEGAKERNEL) return fail(ctx, PTC_ERR_INVALID, kNormalMapsNeedMegakernel);
   if (ctx->iteration >= ctx->max_iterations) {  // path_tracer.cu:391
     ctx->result = ctx->fb.color4;
     return PTC_OK;

@@ -3,7 +3,7 @@
 // following the call sequence of execute_cli_version (src/cli/cli.cpp:62-116): read scene, create_buffers,
 // max_iterations = spp, spp x path_trace, synchronize, send_to_preview, write PNG, stage timings.
 // Extra flags: --max-bounces N (the reference's cap is a compile-time 50), --denoise, --method, --gpu,
-// --lens-radius R / --focus-distance F (the thin lens), --tonemap C / --exposure EV / --auto-exposure / --key K / --white W (the display transform), --environment FILE / --environment-scale S / --environment-size N (environment lighting; --dump-environment FILE: the decoded picture and the map, for tests, no GPU), --textures (image textures), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
+// --lens-radius R / --focus-distance F (the thin lens), --tonemap C / --exposure EV / --auto-exposure / --key K / --white W (the display transform), --environment FILE / --environment-scale S / --environment-size N (environment lighting; --dump-environment FILE: the decoded picture and the map, for tests, no GPU), --textures (image textures), --normal-maps (normal maps), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
 // (DisplayBufferType of send_to_preview, path_tracer.cu:487-520: which buffer the PNG shows), --dump-raw FILE (the
 // accumulated float framebuffers as they are: "PTRF", width, height, 7 as uint32, then colour rgb, normal xyz and
 // depth planes as float32).  Without -o the reference opens its GLFW viewer; this build is headless and says so.
@@ -54,6 +54,7 @@ struct CliConfigurations {  // configurations.hpp:11-15
   bool mis = false;
   bool smooth_normals = false;
   bool textures = false;
+  bool normal_maps = false;
   int roulette = 0;
   std::optional<float> lens_radius, focus_distance;  // the thin lens (override the scene file's camera keys)
   // environment lighting (override the scene file's "environment" key, each on its own)
@@ -94,6 +95,8 @@ void usage()
                "                       megakernel; a scene that says \"smooth_normals\": true asks for it)\n"
                "      --textures       take the colour of a material that carries a \"texture\" from its picture, at the mesh's `vt` coordinates (needs\n"
                "                       --method megakernel; a scene that says \"textures\": true asks for it)\n"
+               "      --normal-maps    shade a material that carries a \"normal_map\" with its picture's normals, at the mesh's `vt` coordinates (needs\n"
+               "                       --method megakernel; a scene that says \"normal_maps\": true asks for it)\n"
                "      --environment FILE  environment lighting: an equirectangular Radiance .hdr (overrides the scene's \"environment\")\n"
                "      --environment-scale S  multiply the picture by S, a finite number >= 0 (default 1)\n"
                "      --environment-size N  size of the octahedral map made from it, in [2,4096] (default: the picture's height)\n"
@@ -139,6 +142,7 @@ CliConfigurations parse_cli_args(int argc, char** argv)
     else if (a == "--mis") c.mis = true;
     else if (a == "--smooth-normals") c.smooth_normals = true;
     else if (a == "--textures") c.textures = true;
+    else if (a == "--normal-maps") c.normal_maps = true;
     else if (a == "--roulette") {
       // a whole decimal number in [0, 64] (ptc_set_param's range), refused here: before the scene is read or a GPU touched
       const std::string v = need("roulette");
@@ -253,6 +257,10 @@ CliConfigurations parse_cli_args(int argc, char** argv)
   }
   if (c.textures && !c.megakernel) {  // ... and its hit records carry no primitive
     std::fprintf(stderr, "hip_pt: --textures needs --method megakernel (the streaming method's hit records carry no primitive)\n");
+    std::exit(1);
+  }
+  if (c.normal_maps && !c.megakernel) {
+    std::fprintf(stderr, "hip_pt: --normal-maps needs --method megakernel (the streaming method's hit records carry no primitive)\n");
     std::exit(1);
   }
   if (c.tone_flag && (c.display == DisplayBufferType::normal || c.display == DisplayBufferType::depth)) {
@@ -390,6 +398,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   path_tracer.max_iterations = scene_desc.spp;      // app.cpp:130
   path_tracer.smooth_normals = configs.smooth_normals || scene_desc.smooth_normals;  // (before create_buffers, which computes the normals)
   path_tracer.textures = configs.textures || scene_desc.textures;  // (create_buffers sets the scene's textures and coordinates)
+  path_tracer.normal_maps = configs.normal_maps || scene_desc.normal_maps;  // (... and its normal-map binding)
   path_tracer.create_buffers(resolution, scene_desc);
   bool enable_denoising = configs.denoise;
   DisplayBufferType display = configs.display;
@@ -511,6 +520,7 @@ try {
   path_tracer.mis = configs.mis;
   path_tracer.smooth_normals = configs.smooth_normals || scene_desc.smooth_normals;  // (before create_buffers, which computes the normals)
   path_tracer.textures = configs.textures || scene_desc.textures;  // (create_buffers sets the scene's textures and coordinates)
+  path_tracer.normal_maps = configs.normal_maps || scene_desc.normal_maps;  // (... and its normal-map binding)
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.display = configs.tone;
@@ -596,10 +606,10 @@ int run_ranks(const CliConfigurations& configs, const SceneDescription& scene_de
     return 1;
   }
   // (the megakernel seeds by frame pixel, so its ranks render the single-GPU image; it is let through for --direct-light,
-  // --environment-light, --mis, --smooth-normals and --textures, which the streaming method cannot render)
+  // --environment-light, --mis, --smooth-normals, --textures and --normal-maps, which the streaming method cannot render)
   if (configs.denoise ||
       (configs.megakernel && !configs.direct_light && !configs.environment_light && !configs.mis && !configs.smooth_normals && !scene_desc.smooth_normals &&
-       !configs.textures && !scene_desc.textures)) {
+       !configs.textures && !scene_desc.textures && !configs.normal_maps && !scene_desc.normal_maps)) {
     std::fprintf(stderr, "hip_pt: --gpus N renders in streaming mode without the denoiser (it needs the whole frame in one context)\n");
     return 1;
   }
@@ -672,6 +682,11 @@ try {
                  scene_desc.textures ? "says \"textures\": true" : "has a material with a \"texture\"");
     return 1;
   }
+  if ((scene_desc.normal_maps || scene_desc.has_normal_maps()) && !configs.megakernel) {
+    std::fprintf(stderr, "hip_pt: the scene %s, which needs --method megakernel (the streaming method's hit records carry no primitive)\n",
+                 scene_desc.normal_maps ? "says \"normal_maps\": true" : "has a material with a \"normal_map\"");
+    return 1;
+  }
   // --mis combines light samples with the path: it needs a light that is sampled (before any GPU is touched)
   if (configs.mis && !configs.direct_light && !configs.environment_light && !scene_desc.environment_source.light) {
     std::fprintf(stderr, "hip_pt: --mis needs --direct-light, --environment-light or a scene whose \"environment\" says \"light\": true\n");
@@ -742,6 +757,11 @@ try {
         out.write(reinterpret_cast<const char*>(head), sizeof head);
         dump_vec(out, img.rgba);
       }
+      if (!flat.material_normal_map.empty()) {  // (a scene without normal maps: the dump as ever)
+        const char maps[4] = {'N', 'M', 'P', '0'};
+        out.write(maps, sizeof maps);
+        dump_vec(out, flat.material_normal_map);
+      }
     }
     return 0;
   }
@@ -765,6 +785,7 @@ try {
   path_tracer.mis = configs.mis;
   path_tracer.smooth_normals = configs.smooth_normals || scene_desc.smooth_normals;  // (before create_buffers, which computes the normals)
   path_tracer.textures = configs.textures || scene_desc.textures;  // (create_buffers sets the scene's textures and coordinates)
+  path_tracer.normal_maps = configs.normal_maps || scene_desc.normal_maps;  // (... and its normal-map binding)
   path_tracer.roulette = configs.roulette;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.display = configs.tone;

@@ -53,6 +53,10 @@ public:
   // with a texture bound takes its colour from the texel at the interpolated coordinate.  Textures and coordinates go through
   // set_textures and set_texcoords after create_buffers; without either the flag changes nothing.
   bool textures = false;
+  // normal maps (megakernel method only; ptc_set_param "normal_maps"): a triangle hit on a diffuse or metal material
+  // with a normal map bound shades with the map's normal.  The binding goes through set_normal_maps after set_textures; without
+  // textures, coordinates or a binding the flag changes nothing.  Independent of `textures`.
+  bool normal_maps = false;
   int roulette = 0;  // Russian roulette at every bounce >= this but the last, 0 = off (both methods; ptc_set_param "roulette", [0, 64])
   // the thin lens (ptc_set_lens): aperture radius (0 = the pinhole, the default) and the distance of the plane in
   // focus, world units; both methods
@@ -109,6 +113,7 @@ public:
         descs.push_back(ptc_texture_desc{pictures[i].rgba.data(), (uint32_t)pictures[i].width, (uint32_t)pictures[i].height, flat.textures[i].encoding,
                                          flat.textures[i].filter, flat.textures[i].wrap});
       set_textures(descs, flat.material_texture);
+      if (!flat.material_normal_map.empty()) set_normal_maps(flat.material_normal_map);
     }
     if (!flat.texcoords.empty()) set_texcoords(flat.texcoords);
     resize_image(r);
@@ -146,6 +151,40 @@ public:
   void set_texcoords(const std::vector<float>& st)
   {
     check(ptc_set_texcoords(ctx_, st.empty() ? nullptr : st.data(), (uint32_t)(st.size() / 2)), "texcoords");
+  }
+  // per material of the uploaded scene -1 or the texture that is its normal map (ptc_set_normal_maps), after set_textures, which drops
+  // the binding; an empty vector removes it
+  void set_normal_maps(const std::vector<int32_t>& material_normal_map)
+  {
+    check(ptc_set_normal_maps(ctx_, material_normal_map.empty() ? nullptr : material_normal_map.data(), (uint32_t)material_normal_map.size()),
+          "normal_maps");
+  }
+  [[nodiscard]] ptc_normal_map_loop_stats normal_map_loop_stats() const
+  {
+    ptc_normal_map_loop_stats s{};
+    check(ptc_get_normal_map_loop_stats(ctx_, &s), "normal_map_loop_stats");
+    return s;
+  }
+  // the normal the loop would shade with at the closest hit, from what is set (ptc_hit_shading_normal): rays 8 floats each; per ray
+  // three floats and an outcome byte (0 miss, 1 no map applied, 2 bent, 3 flat, 4 kept)
+  struct HitShadingNormal {
+    std::vector<float> normal;
+    std::vector<uint8_t> outcome;
+  };
+  [[nodiscard]] HitShadingNormal hit_shading_normal(const std::vector<float>& rays)
+  {
+    push_fields();
+    const uint32_t n = (uint32_t)(rays.size() / 8);
+    HitShadingNormal out{std::vector<float>(3u * (size_t)n), std::vector<uint8_t>(n)};
+    check(ptc_hit_shading_normal(ctx_, rays.data(), n, out.normal.data(), out.outcome.data()), "hit_shading_normal");
+    return out;
+  }
+  // host only: the normal maps' decode table (ptc_normal_map_decode_table), 256 floats
+  [[nodiscard]] static std::vector<float> normal_map_decode_table()
+  {
+    std::vector<float> table(256);
+    if (ptc_normal_map_decode_table(table.data()) < 0) throw std::runtime_error(std::string("normal_map_decode_table: ") + ptc_last_error(nullptr));
+    return table;
   }
   [[nodiscard]] ptc_texture_loop_stats texture_loop_stats() const
   {
@@ -246,6 +285,10 @@ private:
       check(ptc_set_param(ctx_, "textures", textures ? 1 : 0), "textures");
       textures_pushed_ = textures;
     }
+    if (normal_maps != normal_maps_pushed_) {
+      check(ptc_set_param(ctx_, "normal_maps", normal_maps ? 1 : 0), "normal_maps");
+      normal_maps_pushed_ = normal_maps;
+    }
     if (roulette != roulette_pushed_) {
       check(ptc_set_param(ctx_, "roulette", roulette), "roulette");
       roulette_pushed_ = roulette;
@@ -273,6 +316,7 @@ private:
   bool mis_pushed_ = false;
   bool smooth_normals_pushed_ = false;
   bool textures_pushed_ = false;
+  bool normal_maps_pushed_ = false;
   int roulette_pushed_ = 0;
   Lens lens_pushed_{};
   std::shared_ptr<const EnvironmentMap> environment_pushed_;

@@ -202,7 +202,7 @@ FlatScene SceneDescription::build_scene() const
     flat.indices = mesh->indices;
     flat.texcoords = mesh->texcoords;
   }
-  if (has_textures()) {  // (the materials in the table's order: std::map iterates by name)
+  if (has_textures() || has_normal_maps()) {  // (the materials in the table's order: std::map iterates by name)
     for (const auto& [name, material] : material_map_) {
       const auto* d = std::get_if<DiffuseMateral>(&material);
       const auto* mt = std::get_if<MetalMaterial>(&material);
@@ -216,7 +216,32 @@ FlatScene SceneDescription::build_scene() const
       flat.material_texture.push_back(bound);
     }
   }
+  if (has_normal_maps()) {  // behind the colour textures: a picture joins the pool once per (file, filter, wrap)
+    for (const auto& [name, material] : material_map_) {
+      const auto* d = std::get_if<DiffuseMateral>(&material);
+      const auto* mt = std::get_if<MetalMaterial>(&material);
+      const TextureSource* src = d ? &d->normal_map : (mt ? &mt->normal_map : nullptr);
+      int32_t bound = -1;
+      if (src && !src->file.empty()) {
+        const auto it = std::find_if(flat.textures.begin(), flat.textures.end(), [&](const TextureSource& t) {
+          return t.file == src->file && t.filter == src->filter && t.wrap == src->wrap;
+        });
+        bound = (int32_t)(it - flat.textures.begin());
+        if (it == flat.textures.end()) flat.textures.push_back(*src);
+      }
+      flat.material_normal_map.push_back(bound);
+    }
+  }
   return flat;
+}
+
+bool SceneDescription::has_normal_maps() const
+{
+  for (const auto& [name, material] : material_map_) {
+    if (const auto* d = std::get_if<DiffuseMateral>(&material); d && !d->normal_map.file.empty()) return true;
+    if (const auto* mt = std::get_if<MetalMaterial>(&material); mt && !mt->normal_map.file.empty()) return true;
+  }
+  return false;
 }
 
 bool SceneDescription::has_textures() const
@@ -295,23 +320,27 @@ SceneDescription scene_from_json(const std::string& filename, bool read_environm
   scene.filename = filename;
   // a diffuse or metal material's optional "texture" (an extension; json_parser.py, the same rule): {"file": a PNG,
   // relative to the scene file; "encoding": "srgb" | "linear"; "filter": "bilinear" | "nearest"; "wrap": "repeat" | "clamp"}
-  auto texture_of = [&](const Json& m, const std::string& name) {
+  // ... or its "normal_map" (section 5q): the same without "encoding", which a normal map does not have
+  auto texture_of = [&](const Json& m, const std::string& name, const std::string& what = "texture") {
     TextureSource src;
-    const Json* t = m.find("texture");
+    const bool map = what == "normal_map";
+    if (map) src.encoding = PTC_TEXTURE_LINEAR;
+    const Json* t = m.find(what);
     if (!t) return src;
     const Json* file = t->kind == Json::Object ? t->find("file") : nullptr;
     bool ok = file && file->kind == Json::String;
     if (ok)
       for (const auto& [key, value] : t->obj)
-        ok = ok && (key == "file" || key == "encoding" || key == "filter" || key == "wrap");
+        ok = ok && (key == "file" || (key == "encoding" && !map) || key == "filter" || key == "wrap");
     if (!ok)
-      throw std::runtime_error("Json Parser: material " + name + ": \"texture\" must be an object with \"file\" (a string) and optionally \"encoding\", \"filter\", \"wrap\"");
+      throw std::runtime_error("Json Parser: material " + name + ": \"" + what + "\" must be an object with \"file\" (a string) and optionally " +
+                               (map ? "" : "\"encoding\", ") + "\"filter\", \"wrap\"");
     auto choice = [&](const char* key, const char* first, const char* second, uint32_t* out) {
       const Json* j = t->find(key);
       if (!j) return;
       if (j->kind == Json::String && j->str == first) *out = 0u;
       else if (j->kind == Json::String && j->str == second) *out = 1u;
-      else throw std::runtime_error("Json Parser: material " + name + ": texture \"" + key + "\" must be \"" + first + "\" or \"" + second + "\"");
+      else throw std::runtime_error("Json Parser: material " + name + ": " + what + " \"" + key + "\" must be \"" + first + "\" or \"" + second + "\"");
     };
     choice("encoding", "linear", "srgb", &src.encoding);
     choice("filter", "nearest", "bilinear", &src.filter);
@@ -321,12 +350,14 @@ SceneDescription scene_from_json(const std::string& filename, bool read_environm
   };
   for (const auto& m : root->at("materials").arr) {  // read_materials, json_parser.cpp:101-122
     const std::string name = m->at("name").str, type = m->at("type").str;
-    if (m->find("texture") && type != "lambertian" && type != "metal")
-      throw std::runtime_error("Json Parser: material " + name + ": only a lambertian or a metal material may carry a \"texture\"");
+    for (const char* what : {"texture", "normal_map"})
+      if (m->find(what) && type != "lambertian" && type != "metal")
+        throw std::runtime_error("Json Parser: material " + name + ": only a lambertian or a metal material may carry a \"" + what + "\"");
     if (type == "lambertian") {
       DiffuseMateral d{};
       vec3_from(m->at("albedo"), d.albedo);
       d.texture = texture_of(*m, name);
+      d.normal_map = texture_of(*m, name, "normal_map");
       scene.add_material(name, d);
     } else if (type == "dielectric") {
       scene.add_material(name, DielectricMaterial{m->at("refraction_index").f()});
@@ -335,6 +366,7 @@ SceneDescription scene_from_json(const std::string& filename, bool read_environm
       vec3_from(m->at("albedo"), mt.albedo);
       mt.fuzz = m->at("fuzz").f();
       mt.texture = texture_of(*m, name);
+      mt.normal_map = texture_of(*m, name, "normal_map");
       scene.add_material(name, mt);
     } else if (type == "emissive") {  // an extension: the reference's grammar has no emitters
       // "emission": three finite numbers >= 0 (json_parser.py, the same rule)
@@ -399,6 +431,11 @@ SceneDescription scene_from_json(const std::string& filename, bool read_environm
   if (const Json* tx = root->find("textures")) {
     if (tx->kind != Json::Bool) throw std::runtime_error("Json Parser: \"textures\" must be true or false");
     scene.textures = tx->b;
+  }
+  // normal maps (an extension; json_parser.py, the same rule): the top-level key "normal_maps", a boolean
+  if (const Json* nm = root->find("normal_maps")) {
+    if (nm->kind != Json::Bool) throw std::runtime_error("Json Parser: \"normal_maps\" must be true or false");
+    scene.normal_maps = nm->b;
   }
   // environment lighting (an extension; json_parser.py, the same rule): {"file": a Radiance .hdr, equirectangular, relative to the
   // scene file; "scale": a finite number >= 0, default 1; "size": an integer in [2,4096], default the picture's height, at most 4096;

@@ -32,8 +32,9 @@ struct TextureSource {
   uint32_t encoding = PTC_TEXTURE_SRGB, filter = PTC_TEXTURE_BILINEAR, wrap = PTC_TEXTURE_REPEAT;
   bool operator==(const TextureSource& o) const { return file == o.file && encoding == o.encoding && filter == o.filter && wrap == o.wrap; }
 };
-struct DiffuseMateral { float albedo[3]; TextureSource texture{}; };                 // (sic) material.hpp:6-8
-struct MetalMaterial { float albedo[3]; float fuzz; TextureSource texture{}; };      // material.hpp:10-13
+// (normal_map: a material's "normal_map"; its encoding is not read)
+struct DiffuseMateral { float albedo[3]; TextureSource texture{}; TextureSource normal_map{}; };                 // (sic) material.hpp:6-8
+struct MetalMaterial { float albedo[3]; float fuzz; TextureSource texture{}; TextureSource normal_map{}; };      // material.hpp:10-13
 struct DielectricMaterial { float refraction_index; };      // material.hpp:15-17
 struct EmissiveMaterial { float emission[3]; };             // an extension (the reference has no emitters): ptc_material type 3
 using Material = std::variant<DiffuseMateral, MetalMaterial, DielectricMaterial, EmissiveMaterial>;
@@ -79,6 +80,9 @@ struct FlatScene {
   std::vector<float> texcoords;
   std::vector<TextureSource> textures;
   std::vector<int32_t> material_texture;
+  // normal maps (an extension): per material -1 or an index into `textures` (empty: no material has one); a map's
+  // picture stands in `textures` once per (file, filter, wrap), also where it is some material's colour texture
+  std::vector<int32_t> material_normal_map;
 };
 
 class SceneDescription {  // scene_description.hpp:27-49
@@ -102,6 +106,9 @@ public:
   // image textures (an extension): the scene file's "textures": true; has_textures: a material carries a "texture"
   bool textures = false;
   [[nodiscard]] bool has_textures() const;
+  // normal maps (an extension): the scene file's "normal_maps": true; has_normal_maps: a material carries a "normal_map"
+  bool normal_maps = false;
+  [[nodiscard]] bool has_normal_maps() const;
 
   void add_material(const std::string& name, Material material);
   void add_object(Sphere sphere, const Mat4& transform, const std::string& material_name);

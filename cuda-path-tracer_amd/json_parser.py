@@ -96,22 +96,25 @@ def _emission(m):
     return tuple(e)
 
 
-def _texture(m, file_dir):
+def _texture(m, file_dir, key="texture"):
     """A diffuse or metal material's optional "texture" (an extension; scene_description.cpp, the same rule):
     {"file": a PNG, relative to the scene file; "encoding": "srgb" | "linear"; "filter": "bilinear" | "nearest"; "wrap": "repeat" |
-    "clamp"}, defaults srgb, bilinear, repeat.  -> a TextureSource, or None without the key"""
-    if "texture" not in m:
+    "clamp"}, defaults srgb, bilinear, repeat -- or its "normal_map" (section 5q): the same without "encoding", which a normal map does
+    not have.  -> a TextureSource, or None without the key"""
+    if key not in m:
         return None
-    j = m["texture"]
+    j = m[key]
     choices = {"encoding": ("srgb", "linear"), "filter": ("bilinear", "nearest"), "wrap": ("repeat", "clamp")}
+    if key == "normal_map":
+        del choices["encoding"]
     if not isinstance(j, dict) or not isinstance(j.get("file"), str) or set(j) - {"file", *choices}:
-        raise ValueError(f"Json Parser: material {m.get('name')!r}: \"texture\" must be an object with \"file\" (a string) and optionally "
-                         "\"encoding\", \"filter\", \"wrap\"")
-    for key, allowed in choices.items():
-        if j.get(key, allowed[0]) not in allowed:
-            raise ValueError(f"Json Parser: material {m.get('name')!r}: texture \"{key}\" must be \"{allowed[0]}\" or \"{allowed[1]}\"")
-    return TextureSource(os.path.normpath(os.path.join(file_dir, j["file"])), j.get("encoding", "srgb"), j.get("filter", "bilinear"),
-                         j.get("wrap", "repeat"))
+        raise ValueError(f"Json Parser: material {m.get('name')!r}: \"{key}\" must be an object with \"file\" (a string) and optionally "
+                         + ", ".join(f'"{c}"' for c in choices))
+    for c, allowed in choices.items():
+        if j.get(c, allowed[0]) not in allowed:
+            raise ValueError(f"Json Parser: material {m.get('name')!r}: {key} \"{c}\" must be \"{allowed[0]}\" or \"{allowed[1]}\"")
+    return TextureSource(os.path.normpath(os.path.join(file_dir, j["file"])), j.get("encoding", "srgb" if key == "texture" else "linear"),
+                         j.get("filter", "bilinear"), j.get("wrap", "repeat"))
 
 
 def _lens_value(cam, key, positive):
@@ -158,17 +161,18 @@ def scene_from_json(filename):
     for m in root["materials"]:
         t = m["type"]
         if t == "lambertian":
-            scene.add_material(m["name"], DiffuseMateral(tuple(m["albedo"]), _texture(m, file_dir)))
+            scene.add_material(m["name"], DiffuseMateral(tuple(m["albedo"]), _texture(m, file_dir), _texture(m, file_dir, "normal_map")))
         elif t == "dielectric":
             scene.add_material(m["name"], DielectricMaterial(m["refraction_index"]))
         elif t == "metal":
-            scene.add_material(m["name"], MetalMaterial(tuple(m["albedo"]), m["fuzz"], _texture(m, file_dir)))
+            scene.add_material(m["name"], MetalMaterial(tuple(m["albedo"]), m["fuzz"], _texture(m, file_dir), _texture(m, file_dir, "normal_map")))
         elif t == "emissive":  # an extension: the reference's grammar has no emitters
             scene.add_material(m["name"], EmissiveMaterial(_emission(m)))
         else:
             raise ValueError(f"Json Parser: Unsupported material type {t}")
-        if "texture" in m and t not in ("lambertian", "metal"):
-            raise ValueError(f"Json Parser: material {m['name']!r}: only a lambertian or a metal material may carry a \"texture\"")
+        for key in ("texture", "normal_map"):
+            if key in m and t not in ("lambertian", "metal"):
+                raise ValueError(f"Json Parser: material {m['name']!r}: only a lambertian or a metal material may carry a \"{key}\"")
     for s in root["surfaces"]:
         transform = _transform(s["transform"])
         if s["type"] == "sphere":
@@ -200,6 +204,10 @@ def scene_from_json(filename):
         if not isinstance(root["textures"], bool):
             raise ValueError('Json Parser: "textures" must be true or false')
         scene.textures = root["textures"]
+    if "normal_maps" in root:  # (an extension; scene_description.cpp, the same rule)
+        if not isinstance(root["normal_maps"], bool):
+            raise ValueError('Json Parser: "normal_maps" must be true or false')
+        scene.normal_maps = root["normal_maps"]
     if "environment" in root:
         scene.environment, scene.environment_source = _environment(root["environment"], file_dir)
     return scene

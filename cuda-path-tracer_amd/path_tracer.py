@@ -151,6 +151,42 @@ def check_texture_lookup(texture, st):
     return rgb, rej.astype(bool)
 
 
+def normal_map_decode_table():
+    """The 256-entry decode table of a normal map (ptc_normal_map_decode_table; host-side, no GPU needed)"""
+    out = np.zeros(256, dtype=np.float32)
+    _capi.check(_capi.lib().ptc_normal_map_decode_table(out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def check_normal_map(texture, p0, p1, p2, st0, st1, st2, u, v, m16, b, g, d):
+    """The normal map's rule of DESIGN section 5q on the host (ptc_check_normal_map; no GPU needed).  Per case the corners' object-space
+    positions [n, 3], their coordinate pairs [n, 2], the hit's u, v [n], the base normal, the geometric normal and the ray direction
+    [n, 3]; m16 the object matrix, column-major -> (normal float32 [n, 3], outcome uint8 [n]: 2 bent, 3 flat, 4 kept)"""
+    a3 = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3) for a in (p0, p1, p2, b, g, d)]
+    a2 = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 2) for a in (st0, st1, st2)]
+    a1 = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (u, v)]
+    n = len(a1[0])
+    if any(len(a) != n for a in a3 + a2 + a1):
+        raise ValueError("check_normal_map: the arrays differ in length")
+    m = np.ascontiguousarray(m16, dtype=np.float32).reshape(16)
+    out, how = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.uint8)
+    desc = texture._desc()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    _capi.check(_capi.lib().ptc_check_normal_map(C.byref(desc), ptr(a3[0]), ptr(a3[1]), ptr(a3[2]), ptr(a2[0]), ptr(a2[1]), ptr(a2[2]), ptr(a1[0]),
+                                                 ptr(a1[1]), ptr(m), ptr(a3[3]), ptr(a3[4]), ptr(a3[5]), n, ptr(out), ptr(how)))
+    return out, how
+
+
+def check_megakernel_instance2(direct=False, env=False, env_lit=False, smooth=False, textured=False, weigh=False, lens=False, plays=None,
+                               emitters=False, bent=False, roulette=0, max_bounces=50):
+    """check_megakernel_instance with the tenth fact, bent (ptc_check_megakernel_instance2)"""
+    name, arg = C.create_string_buffer(64), C.c_int(0)
+    _capi.check(_capi.lib().ptc_check_megakernel_instance2(int(direct), int(env), int(env_lit), int(smooth), int(textured), int(weigh), int(lens),
+                                                           -1 if plays is None else int(plays), int(emitters), int(bent), int(roulette),
+                                                           int(max_bounces), name, len(name), C.byref(arg)))
+    return name.value.decode(), arg.value
+
+
 def check_megakernel_instance(direct=False, env=False, env_lit=False, smooth=False, textured=False, weigh=False, lens=False, plays=None,
                               emitters=False, roulette=0, max_bounces=50):
     """The megakernel's instance rule on the host (ptc_check_megakernel_instance; no GPU): the nine facts of a frame -> (the kernel's
@@ -268,6 +304,9 @@ class PathTracer:
         self._textures = False  # PathTracer.textures = True: bound materials take their colour from their texture (megakernel only)
         self._textures_pushed = False
         self._texture_table = None  # PathTracer.texture_table = (textures, material_texture) (None: none)
+        self._normal_maps = False  # PathTracer.normal_maps = True: bound materials take their normal from their map (megakernel only)
+        self._normal_maps_pushed = False
+        self._normal_map_table = None  # PathTracer.normal_map_table = material_normal_map (None: none)
         self._texcoords = None  # PathTracer.texcoords = [index_count, 2] float32, parallel to the uploaded scene's indices (None: none)
         self._roulette_pushed = 0
         self._lens_pushed = (0.0, 1.0)
@@ -357,7 +396,7 @@ class PathTracer:
     def texture_table(self, value):
         if value is None:
             self._check(self._lib.ptc_set_textures(self._ctx, None, 0, None, 0))
-            self._texture_table = None
+            self._texture_table = self._normal_map_table = None
             return
         textures, binding = value
         textures = list(textures)
@@ -366,13 +405,46 @@ class PathTracer:
         self._check(self._lib.ptc_set_textures(self._ctx, descs if textures else None, len(textures), b.ctypes.data_as(C.c_void_p), len(b)))
         b.setflags(write=False)
         self._texture_table = (tuple(textures), b)
+        self._normal_map_table = None  # (its indices named the old pool: the library dropped it)
+
+    @property
+    def normal_maps(self):
+        """Normal maps in the megakernel (ptc_set_param "normal_maps"): True = a triangle hit on a diffuse or metal
+        material with a normal map bound shades with the map's normal.  Independent of `textures`.  Changes nothing while
+        texture_table, texcoords or normal_map_table is not set."""
+        return self._normal_maps
+
+    @normal_maps.setter
+    def normal_maps(self, on):
+        self._normal_maps = bool(on)
+
+    @property
+    def normal_map_table(self):
+        """The scene's normal-map binding (ptc_set_normal_maps): material_normal_map[m] = -1 or the texture of texture_table that is
+        material m's normal map; None removes it.  Assignment uploads at once, after texture_table -- every assignment to texture_table
+        drops it -- and a refusal raises PtcError and leaves what was set."""
+        return self._normal_map_table
+
+    @normal_map_table.setter
+    def normal_map_table(self, value):
+        if value is None:
+            self._check(self._lib.ptc_set_normal_maps(self._ctx, None, 0))
+            self._normal_map_table = None
+            return
+        b = np.array(value, dtype=np.int32, order="C").reshape(-1)
+        self._check(self._lib.ptc_set_normal_maps(self._ctx, b.ctypes.data_as(C.c_void_p), len(b)))
+        b.setflags(write=False)
+        self._normal_map_table = b
 
     def load_scene_textures(self, flat):
         """What a scene file says about textures, after create_buffers: reads the pictures of flat.texture_sources (png.read_png, which
-        flips rows) and sets texture_table and texcoords from them and from flat.texcoords.  A scene without either sets nothing."""
+        flips rows) and sets texture_table, normal_map_table (flat.material_normal_map) and texcoords from them and from flat.texcoords.
+        A scene without any sets nothing."""
         from . import png
         if flat.texture_sources:
             self.texture_table = ([Texture(png.read_png(s.file), s.encoding, s.filter, s.wrap) for s in flat.texture_sources], flat.material_texture)
+            if flat.material_normal_map is not None:
+                self.normal_map_table = flat.material_normal_map
         if flat.texcoords is not None:
             self.texcoords = flat.texcoords
 
@@ -534,6 +606,9 @@ class PathTracer:
         if self._textures != self._textures_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"textures", 1 if self._textures else 0))
             self._textures_pushed = self._textures
+        if self._normal_maps != self._normal_maps_pushed:
+            self._check(self._lib.ptc_set_param(self._ctx, b"normal_maps", 1 if self._normal_maps else 0))
+            self._normal_maps_pushed = self._normal_maps
         if self._roulette != self._roulette_pushed:
             self._check(self._lib.ptc_set_param(self._ctx, b"roulette", self._roulette))
             self._roulette_pushed = self._roulette
@@ -571,7 +646,7 @@ class PathTracer:
         desc = flat.to_c()
         self._check(self._lib.ptc_upload_scene(self._ctx, C.byref(desc)))
         self._vertex_normals = None  # (a new scene starts without normals)
-        self._texture_table = self._texcoords = None  # (... and without textures and coordinates)
+        self._texture_table = self._texcoords = self._normal_map_table = None  # (... and without textures, coordinates and normal maps)
         self.resize_image(resolution)
 
     def path_trace(self, camera, resolution=None):
@@ -928,6 +1003,23 @@ class PathTracer:
         s = _capi.ptc_texture_loop_stats()
         self._check(self._lib.ptc_get_texture_loop_stats(self._ctx, C.byref(s)))
         return {"lookups": int(s.lookups), "fallbacks": int(s.fallbacks)}
+
+    def normal_map_loop_stats(self):
+        """Counters of the megakernel under normal_maps = True with a binding, textures and coordinates set, since restart: hits whose
+        normal the map replaced, and hits where the rule fell back to the base normal (a flat texel counts in neither)."""
+        s = _capi.ptc_normal_map_loop_stats()
+        self._check(self._lib.ptc_get_normal_map_loop_stats(self._ctx, C.byref(s)))
+        return {"bent": int(s.bent), "kept": int(s.kept)}
+
+    def hit_shading_normal(self, rays):
+        """The normal the megakernel's loop would shade with at the closest hit (ptc_hit_shading_normal) of rays [n, 8], from what is
+        set -> dict(normal float32 [n, 3], zeros on a miss; outcome uint8 [n]: 0 miss, 1 no map applied, 2 bent, 3 flat, 4 kept)"""
+        self._push_fields()
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        nrm, how = np.zeros((len(r), 3), dtype=np.float32), np.zeros(len(r), dtype=np.uint8)
+        self._check(self._lib.ptc_hit_shading_normal(self._ctx, r.ctypes.data_as(C.c_void_p), len(r), nrm.ctypes.data_as(C.c_void_p),
+                                                     how.ctypes.data_as(C.c_void_p)))
+        return {"normal": nrm, "outcome": how}
 
     def sample_texture(self, texture, st):
         """The lookup of texture `texture` of texture_table on the device, without rendering (ptc_sample_texture): st [n, 2] ->

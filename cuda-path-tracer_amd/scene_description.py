@@ -25,6 +25,7 @@ class TextureSource:
 class DiffuseMateral:  # (sic) material.hpp:6-8
     albedo: tuple
     texture: TextureSource = None  # (an extension)
+    normal_map: TextureSource = None  # (an extension; its encoding is not read)
 
 
 @dataclass
@@ -32,6 +33,7 @@ class MetalMaterial:  # material.hpp:10-13
     albedo: tuple
     fuzz: float = 0.0
     texture: TextureSource = None  # (an extension)
+    normal_map: TextureSource = None  # (an extension; its encoding is not read)
 
 
 @dataclass
@@ -106,6 +108,9 @@ class FlatScene:
     texcoords: np.ndarray = None
     texture_sources: list = None
     material_texture: np.ndarray = None
+    # normal maps (an extension): material_normal_map [M] int32, -1 or an index into texture_sources (None: no
+    # material has one); a map's picture stands in texture_sources once, also where it is some material's colour texture
+    material_normal_map: np.ndarray = None
     keepalive: list = field(default_factory=list)
 
     def to_c(self):
@@ -183,6 +188,9 @@ class SceneDescription:
         # image textures (an extension): the scene file's "textures": true -- PathTracer.textures with
         # load_scene_textures is what renders the materials' "texture" entries (the megakernel method)
         self.textures = False
+        # normal maps (an extension): the scene file's "normal_maps": true -- PathTracer.normal_maps with
+        # load_scene_textures is what renders the materials' "normal_map" entries (the megakernel method)
+        self.normal_maps = False
 
     def add_material(self, name, material):   # scene_description.cpp:150-153 (try_emplace: first one wins)
         self.material_map_.setdefault(name, material)
@@ -217,7 +225,18 @@ class SceneDescription:
                 if src not in sources:
                     sources.append(src)
                 material_texture[k] = sources.index(src)
+        # the normal maps behind the colour textures: a picture joins the pool once per (file, filter, wrap) -- a map's encoding is not read
+        material_normal_map = np.full(len(names), -1, dtype=np.int32)
+        for k, n in enumerate(names):
+            src = getattr(self.material_map_[n], "normal_map", None)
+            if src is not None:
+                same = [i for i, s in enumerate(sources) if (s.file, s.filter, s.wrap) == (src.file, src.filter, src.wrap)]
+                if not same:
+                    sources.append(src)
+                material_normal_map[k] = same[0] if same else len(sources) - 1
         tex = dict(texture_sources=sources, material_texture=material_texture) if sources else {}
+        if (material_normal_map >= 0).any():
+            tex["material_normal_map"] = material_normal_map
 
         def corners(meshes):  # the scene's per-corner coordinates: zeros for a mesh without any, None when no mesh has any
             if not any(m.texcoords is not None for m in meshes):

@@ -373,6 +373,13 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *                      frame launches what it launched with 0.  Under PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with
  *                      PTC_ERR_INVALID while it is 1, before anything is queued.  Counters: ptc_get_texture_loop_stats.  Any time
  *                      (queued frames are flushed first)
+ *   "normal_maps"      RENDERING (default 0; an extension): 1 = under PTC_METHOD_MEGAKERNEL, in a scene with textures,
+ *                      texture coordinates and a normal-map binding (ptc_set_normal_maps), a triangle hit on a diffuse or metal material
+ *                      with a map bound is shaded with the map's normal -- its material, its light samples and "mis" see it; the normal
+ *                      and depth planes are those of the same render with 0 (the paths behind the hit differ).  Independent of "textures";
+ *                      every other parameter combines with it.  Without textures, coordinates or a bound map a frame launches what it
+ *                      launched with 0.  Under PTC_METHOD_STREAMING ptc_trace and ptc_trace_begin fail with PTC_ERR_INVALID while it is
+ *                      1, before anything is queued.  Counters: ptc_get_normal_map_loop_stats.  Any time (queued frames are flushed first)
  *   "roulette"         RENDERING (default 0 = off; an extension): k in [1, 64] = Russian roulette at every bounce b >= k
  *                      except the last one, under both methods (and "direct_light").  A path whose closest hit exists and is no emitter
  *                      takes q = the largest component of the throughput that came into the bounce; q >= 1 changes nothing (no draw); else
@@ -819,6 +826,35 @@ typedef struct ptc_texture_loop_stats {
 } ptc_texture_loop_stats;
 int ptc_get_texture_loop_stats(ptc_ctx* ctx, ptc_texture_loop_stats* out);
 
+/* Normal maps ("normal_maps", an extension): a texture of the pool read as a tangent-space normal at a triangle hit
+ * on a diffuse or metal material, in the frame the corners' texture coordinates span, about the hit's base normal (the interpolated
+ * vertex normal under "smooth_normals", else the geometric one).
+ *
+ * ptc_set_normal_maps: per material of the uploaded scene -1 or an index into the pool ptc_set_textures set (material_count
+ * entries).  NULL / 0 removes the binding.  PTC_ERR_NO_SCENE without a scene; PTC_ERR_INVALID (with a message) without textures, for a
+ * material_count other than the scene's, for an index out of range; a refusal leaves what was set.  The binding belongs to the scene
+ * as the textures do, and a successful ptc_set_textures removes it: its indices named the old pool.  A texture bound as a normal map
+ * is decoded with ptc_normal_map_decode_table's table whatever its encoding says; its filter and wrap hold.  A binding on a glass or
+ * an emissive material is accepted and ignored.  Queued frames are traced first. */
+int ptc_set_normal_maps(ptc_ctx* ctx, const int32_t* material_normal_map, uint32_t material_count);
+/* 1 and *bound_materials (may be NULL) = the materials with a map while a binding is set; 0 and 0 when none is. */
+int ptc_get_normal_maps(const ptc_ctx* ctx, uint32_t* bound_materials);
+/* The normal maps' decode table, on the host (no GPU, no context): out[k] = max(((float)k - 128.0f) / 127.0f, -1.0f) -- byte 128 is
+ * exactly 0, byte 255 exactly 1, bytes 0 and 1 are -1.  PTC_ERR_INVALID: a NULL. */
+int ptc_normal_map_decode_table(float* out256);
+/* Per ray (8 floats, as for ptc_intersect_rays) at the closest hit: normal_out (3 floats) = the normal the megakernel's loop would hand
+ * its material there from what is SET (vertex normals if set, the normal map if bound, textures and coordinates set), whatever the
+ * parameters say -- as ptc_hit_surface reports; outcome_out (one byte): 0 a miss (normal zeros), 1 no map applied (a sphere, an unbound
+ * material, glass, an emitter, nothing set), 2 bent, 3 flat (the texel is (0, 0, > 0): the base normal's bits), 4 kept (the rule fell
+ * back to the base normal).  ptc_hit_attributes' walk, one thread per ray; host pointers. */
+int ptc_hit_shading_normal(ptc_ctx* ctx, const float* rays, uint32_t n, float* normal_out, uint8_t* outcome_out);
+/* The megakernel under "normal_maps" 1 with a binding, textures and coordinates set, since ptc_restart: hits whose normal the map
+ * replaced, and hits where the rule fell back to the base normal; a flat texel counts in neither.  Synchronises. */
+typedef struct ptc_normal_map_loop_stats {
+  uint64_t bent, kept;
+} ptc_normal_map_loop_stats;
+int ptc_get_normal_map_loop_stats(ptc_ctx* ctx, ptc_normal_map_loop_stats* out);
+
 /* Where the time of the last ptc_upload_scene went (milliseconds of host wall clock; the "Initialization" stage of
  * the reference's Stopwatch, cli.cpp): */
 typedef struct ptc_upload_times {
@@ -887,6 +923,10 @@ int ptc_check_frame_plan(uint32_t width, uint32_t height, int frames_in_flight, 
  * PTC_ERR_INVALID for a NULL out and for a name_capacity the name does not fit in (40 bytes hold every name). */
 int ptc_check_megakernel_instance(int direct, int env, int env_lit, int smooth, int textured, int weigh, int lens, int plays, int emitters,
                                   int roulette, int max_bounces, char* name_out, uint32_t name_capacity, int* roulette_out);
+/* ... with the tenth fact, bent: "normal_maps", textures, texture coordinates and a normal-map binding (section 5q) -- the rule over
+ * all 26 kernels; with bent 0 it answers as ptc_check_megakernel_instance does. */
+int ptc_check_megakernel_instance2(int direct, int env, int env_lit, int smooth, int textured, int weigh, int lens, int plays, int emitters,
+                                   int bent, int roulette, int max_bounces, char* name_out, uint32_t name_capacity, int* roulette_out);
 /* Entry points for primary rays ("beam"), checked on the host (no GPU): for every 8 x 8-pixel tile of a width x height
  * frame of `camera`, the entries k_beam computes for the mesh under the object matrix object_m16 (NULL: identity;
  * column-major), and for sample rays of the tile (corners and centre of the jitter range of every stride-th pixel) the
@@ -949,6 +989,14 @@ int ptc_check_shading_normal(const float* n0, const float* n1, const float* n2, 
  * host: no GPU, no context; the host twin of ptc_sample_texture.  desc: one texture; st: 2 n floats; rgb_out: 3 n floats;
  * rejected_out (may be NULL): one byte a pair.  PTC_ERR_INVALID: a NULL, a texture ptc_set_textures would refuse. */
 int ptc_check_texture_lookup(const ptc_texture_desc* desc, const float* st, uint32_t n, float* rgb_out, uint8_t* rejected_out);
+/* The normal map's rule of section 5q (csrc/pt_normal_map.hpp, the header the normal-mapped kernels run on the device) on the host: no
+ * GPU, no context.  desc: the map (its encoding is not read).  Per case i: the corners' object-space positions p0, p1, p2 (3 floats
+ * each), their coordinate pairs st0, st1, st2 (2 floats each), the hit's u, v, the base normal b, the geometric normal g facing the ray
+ * and the ray direction d (3 floats each), all under the object matrix m16 (column-major).  normal_out: 3 floats a case; outcome_out:
+ * one byte a case, 2 bent, 3 flat, 4 kept.  PTC_ERR_INVALID: a NULL, a texture ptc_set_textures would refuse. */
+int ptc_check_normal_map(const ptc_texture_desc* desc, const float* p0, const float* p1, const float* p2, const float* st0, const float* st1,
+                         const float* st2, const float* u, const float* v, const float* m16, const float* b, const float* g, const float* d,
+                         uint32_t count, float* normal_out, uint8_t* outcome_out);
 /* ... and the sample on `count` caller-given points, normals and draws (v[i]: a raw value 1 .. 2^31 - 2; u + 3 i: u1, u2, u3), written as
  * ptc_environment_light writes a sample whose shadow ray is free: radiance 3 floats, shadow_rays 8 floats (may be NULL), sampled one
  * byte (may be NULL) per point.  PTC_ERR_INVALID: a NULL, n out of range, a bad component, a v out of range. */
