@@ -7,7 +7,7 @@ manner of lit_ref.py.  Three things, none of them the thing under test:
   (b) light_sample / sample / query: one light sample per point in numpy binary32, one numpy operation per source operation of
       light_sample_point in the order DESIGN section 5f writes down (numpy does not contract into FMA); its pinned pieces are the
       oracle's orc_path_seed, orc_rng_seed / orc_rng_uniform (the draws: light_draws), orc_sincos and intersect_rays (the
-      shadow rays).  light_sample takes its draws from the caller: the query (sample) and the render loop (lit_ref.render_megakernel,
+      shadow rays).  light_sample takes its draws from the caller: the query (sample) and the render loop (loop_ref.render_megakernel,
       section 5g) key their light streams differently and share everything else;
   (c) estimate_f64 and the truths: a float64 Monte-Carlo estimator written from the formula
           Le cos_r cos_l / (pi d^2 pdf_area) * visibility

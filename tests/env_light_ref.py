@@ -3,19 +3,15 @@ binary32 -- TEST INFRASTRUCTURE: the checker of tests/test_environment_light_cpu
 thing under test.
 
 What stands here: the sample of section 5k, every numpy operation one binary32 operation of the rule in its order (numpy does not
-contract into FMA); the stream it draws from; the megakernel's loop with the environment for a light, built from the pinned pieces of
-lit_ref / env_ref / direct_ref / lens_ref (_primary, _closest_hits, shade, play, _deposit, lookup, light_sample, stream_draws) with the
-loop itself stated here; and a binary64 quadrature of what a sample estimates.  The alias TABLE is data to this file: it is built in
+contract into FMA); the stream it draws from; and a binary64 quadrature of what a sample estimates.  The megakernel's loop with the
+environment for a light is loop_ref.render_megakernel's under `env_light`.  The alias TABLE is data to this file: it is built in
 binary64 by the library's host code (ptc_check_environment_light_table), its properties are what test_environment_light_cpu.py checks,
 and the sample below reads it as the device does."""
 import ctypes as C
 
 import numpy as np
 
-import direct_ref
 import env_ref
-import lens_ref
-import lit_ref
 from ref_f32 import PI, Draws, F, _dot, stream_states
 
 SEED_XOR = 0x454E564C  # kEnvLightSeedXor (pt_device.hpp)
@@ -123,93 +119,6 @@ def query(orc, flat, entries, texels, points, normals, sample_index, scene_handl
         visible[sel] = blocked == 0
     radiance = np.where(visible[:, None], s["contribution"], F(0.0)).astype(np.float32)
     return radiance, s["rays"], visible.astype(np.uint8), s["sampled"]
-
-
-def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, env=None, entries=None, env_light=False, direct=False,
-                      roulette=0, lens=None, prev=None, scene_handle=None):
-    """The megakernel's loop (lit_ref.render_megakernel's, stated again with one more option) under the environment `env` with its table
-    `entries` (table_of's).  env_light with an environment of weight > 0 is the rule of section 5k: at every hit on a diffuse material,
-    after evaluate_material and after the lamp's sample where `direct` has lamps to sample, one environment sample at the hit point
-    about the hit's normal from stream(pixel, iteration, 4 * bounce); a sampled one traces its shadow ray and, if the oracle reports no
-    hit, radiance += colour * contribution.  A miss takes colour * environment only when the vertex before it drew no environment
-    sample (the camera, metal, glass), else 0 -- the emission gate of section 5g in a flag of its own; the lamps' gate moves only where
-    lamps are sampled.  Radiance + colour is deposited where either light is sampled.  Without env_light, without an environment or under
-    a map of weight 0 every result is env_ref.render_megakernel's.
-    -> lit_ref's dict (the tables left out) and env_diffuse_hits, env_shadow_rays, env_unoccluded."""
-    sh = scene_handle or orc.SceneHandle(flat)
-    materials = np.asarray(flat.materials)
-    lit = False
-    if direct:
-        lamps = direct_ref.light_table(flat)
-        lit = len(lamps[0]) > 0 and float(lamps[1]["total_weight"]) > 0.0
-    lit_env = bool(env_light) and env is not None and entries is not None
-    texels = env_ref.apron(env) if lit_env else None
-    P = w * h
-    frame = lit_ref._frame(prev, P)
-    rays = diffuse_hits = shadow_rays = unoccluded = 0
-    env_diffuse_hits = env_shadow_rays = env_unoccluded = 0
-    with env_ref._sky_in_place(env), lens_ref._primary_in_place(lens):
-        for it in range(iter_count):
-            iteration = iter_begin + it
-            o, d, tmin, states = lit_ref._primary(orc, camera, w, h, np.arange(P), iteration)
-            draws = Draws(orc, states)
-            color = np.ones((P, 3), dtype=np.float32)
-            radiance = np.zeros((P, 3), dtype=np.float32)
-            count_emission = np.ones(P, dtype=bool)
-            count_env = np.ones(P, dtype=bool)
-            normal = -d
-            depth = np.full(P, F(1e6), dtype=np.float32)
-            active = np.arange(P)
-            for b in range(max_bounces):
-                if len(active) == 0:
-                    break
-                rays += len(active)
-                recs, em, emission, sc, typ = lit_ref._closest_hits(orc, flat, sh, materials, o, d, tmin, active, b, color, normal, depth)
-                if lit_env:  # a miss behind an environment sample: that sample has counted the environment
-                    hit = np.zeros(P, dtype=bool)
-                    hit[em] = hit[sc] = True
-                    miss = active[~hit[active]]
-                    color[miss[~count_env[miss]]] = F(0.0)
-                color[em] = np.where(count_emission[em][:, None], color[em] * emission, F(0.0))
-                if lit_ref.plays_at(roulette, b, max_bounces):
-                    ended, _ = lit_ref.play(orc, color, sc, sc, iteration, b)
-                    sc, typ = sc[~ended], typ[~ended]
-                lit_ref.shade(orc, materials, o, d, tmin, recs, sc, draws, color)
-                df = sc[typ == 0]
-                pts = recs["point"][df].astype(np.float32)
-                nrm = recs["normal"][df].astype(np.float32)
-                if lit:
-                    count_emission[sc] = typ != 0
-                    diffuse_hits += len(df)
-                    smp = direct_ref.light_sample(orc, flat, lamps, pts, nrm, direct_ref.light_draws(orc, df, iteration, 3 * b))
-                    got, traced = _arrived(orc, flat, sh, smp["sampled"], smp["rays"])
-                    shadow_rays += traced
-                    unoccluded += int(got.sum())
-                    radiance[df[got]] = radiance[df[got]] + color[df[got]] * smp["contribution"][got]
-                if lit_env:
-                    count_env[sc] = typ != 0
-                    env_diffuse_hits += len(df)
-                    v, u = stream(orc, df, iteration, 4 * b)
-                    smp = sample(entries, texels, pts, nrm, v, u)
-                    got, traced = _arrived(orc, flat, sh, smp["sampled"], smp["rays"])
-                    env_shadow_rays += traced
-                    env_unoccluded += int(got.sum())
-                    radiance[df[got]] = radiance[df[got]] + color[df[got]] * smp["contribution"][got]
-                active = sc
-            total = radiance + color if (lit or lit_env) else color
-            lit_ref._deposit(frame, np.arange(P), iteration, total, normal, depth)
-    return {**lit_ref._planes(frame, h, w), "rays": rays, "diffuse_hits": diffuse_hits, "shadow_rays": shadow_rays, "unoccluded": unoccluded,
-            "env_diffuse_hits": env_diffuse_hits, "env_shadow_rays": env_shadow_rays, "env_unoccluded": env_unoccluded}
-
-
-def _arrived(orc, flat, sh, sampled, shadow):
-    """-> (bool[n]: the sample's shadow ray is free, the number of shadow rays traced)"""
-    clear = np.zeros(len(sampled), dtype=bool)
-    sel = np.nonzero(sampled)[0]
-    if len(sel):
-        _, blocked = orc.intersect_rays(flat, shadow[sel], scene_handle=sh)
-        clear[sel] = blocked == 0
-    return clear, len(sel)
 
 
 def irradiance_f64(env, normal, grid):

@@ -3,15 +3,10 @@ checker of tests/test_environment_cpu.py and tests/test_gpu_environment.py, not 
 
 The reference's sky is a fixed gradient, so the oracle (oracle/oracle.c) cannot check an environment and stays as it is.  This file
 restates the apron and the lookup of section 5j -- every numpy operation below is one binary32 operation of the rule, in its order
-(numpy does not contract into FMA) -- and nothing else: the render loops are lit_ref's (or, under a lens, lens_ref's) own.
-render_streaming and render_megakernel here call them with this module's lookup in lit_ref.sky's place for the length of the call, the
-way lens_ref swaps lit_ref._primary.  env None is no environment: lit_ref's results themselves."""
-import contextlib
-
+(numpy does not contract into FMA) -- and nothing else: the render loops are loop_ref's, which take `env` as an option and hand this
+module's lookup to their misses in lit_ref.sky's place.  env None is no environment: the gradient."""
 import numpy as np
 
-import lens_ref
-import lit_ref
 from ref_f32 import F
 
 FLT_MAX = F(np.finfo(np.float32).max)
@@ -98,32 +93,6 @@ def lookup(env, d, texels=None):
     bot = _lerp(c01, c11, tx[:, None])
     value = _lerp(top, bot, tz[:, None])
     return np.where(ok[:, None], value, F(0.0)).astype(np.float32)
-
-
-@contextlib.contextmanager
-def _sky_in_place(env):
-    if env is None:
-        yield
-        return
-    texels = apron(env)
-    saved = lit_ref.sky
-    lit_ref.sky = lambda d: lookup(None, d, texels)
-    try:
-        yield
-    finally:
-        lit_ref.sky = saved
-
-
-def render_streaming(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, env=None, lens=None, **kw):
-    """lens_ref.render_streaming (lit_ref's, under the lens if any) with the environment for a sky; keywords: lit_ref's"""
-    with _sky_in_place(env):
-        return lens_ref.render_streaming(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, lens=lens, **kw)
-
-
-def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, env=None, lens=None, **kw):
-    """lens_ref.render_megakernel with the environment for a sky; keywords: lit_ref's"""
-    with _sky_in_place(env):
-        return lens_ref.render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, lens=lens, **kw)
 
 
 def direction_set(rng, n, count=4096):

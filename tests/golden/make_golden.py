@@ -131,7 +131,7 @@ LOOP_REF_MEGAKERNEL = ("color", "normal", "depth", "rays", "diffuse_hits", "shad
 
 
 def loop_ref_cases():
-    """The arrays of tests/golden/loop_ref.npz: what the numpy restatements of the render loops (tests/lit_ref.py) and of the
+    """The arrays of tests/golden/loop_ref.npz: what the numpy restatements of the render loops (tests/loop_ref.py) and of the
     light sample (tests/direct_ref.py) return, at the CPU tests' shape -- every option of either loop, a rank of an interleaved
     pair, a continuation from a frame, a far iteration, scenes with metal and glass, a lamp behind glass and no lamp.  The file
     was written by the restatements as they stood when each loop still had a copy per feature; it pins the CHECKER's bits (the
@@ -139,18 +139,19 @@ def loop_ref_cases():
     import direct_loop_scenes as scenes
     import direct_ref as dr
     import lit_ref as lr
+    import loop_ref
     c = LOOP_REF
     w, h, n, mb = c["w"], c["h"], c["iterations"], c["max_bounces"]
     out = {}
 
     def streaming(name, scene, flat, sh, roulette, iter_begin=0, iter_count=n, **kw):
-        r = lr.render_streaming(orc, flat, scene.camera, w, h, iter_begin, iter_count, mb, roulette=roulette, scene_handle=sh, **kw)
+        r = loop_ref.render_streaming(orc, flat, scene.camera, w, h, iter_begin, iter_count, mb, roulette=roulette, scene_handle=sh, **kw)
         assert roulette == 0 or r["ended"].sum() > 0, name
         out.update({f"{name}_{k}": np.asarray(r[k]) for k in LOOP_REF_STREAMING})
         return r
 
     def megakernel(name, scene, flat, sh, direct, roulette, iter_begin=0, iter_count=n, **kw):
-        r = lr.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iter_count, mb, direct=direct, roulette=roulette,
+        r = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iter_count, mb, direct=direct, roulette=roulette,
                                  scene_handle=sh, **kw)
         assert roulette == 0 or r["ended"].sum() > 0, name
         out.update({f"{name}_{k}": np.asarray(r[k]) for k in LOOP_REF_MEGAKERNEL})
@@ -197,9 +198,84 @@ def loop_ref_cases():
     return out
 
 
+LOOP_REF_COUNTERS = ("rays", "diffuse_hits", "shadow_rays", "unoccluded", "env_diffuse_hits", "env_shadow_rays", "env_unoccluded",
+                     "mis_emitter_hits", "mis_misses", "shading_normals", "fallbacks", "absorbed", "culled_light_samples", "lookups",
+                     "tex_fallbacks", "bent", "kept")
+LOOP_REF_OPTIONS = ("color", "normal", "depth") + LOOP_REF_COUNTERS + ("played", "ended", "skipped")
+LOOP_REF_PAIRS = {"dm": ("diffuse", "metal"), "lg": ("lamp", "glass")}
+
+
+def loop_ref_option_cases():
+    """The arrays of tests/golden/loop_ref_options.npz: what tests/loop_ref.py's loops return under the options loop_ref.npz does not
+    reach -- environment light, MIS, smooth shading, textures, normal maps, the lens --, at LOOP_REF's shape on smooth_ref.sheet_scene in
+    two material pairs: everything on (at once, at a far iteration, under a lens, continued from a frame, with a refused coordinate),
+    everything but smooth shading, MIS and roulette, and each of the five alone; and the streaming loop under an environment and a lens.
+    The file was written while the megakernel's loop still had a copy per feature, by the last of those copies (and lit_ref's tally of
+    play for the tables); it pins the CHECKER's bits, and tests/test_loop_ref_golden_cpu.py holds today's loop to it."""
+    import env_light_ref
+    import loop_ref
+    import normal_map_ref
+    import smooth_ref
+    import texture_ref
+    c = LOOP_REF
+    w, h, n, mb = c["w"], c["h"], c["iterations"], c["max_bounces"]
+    env = smooth_ref.ENV
+    entries = env_light_ref.table_of(pkg, env)[0]
+    out, cases = {}, []
+    for tag, pair in LOOP_REF_PAIRS.items():
+        scene = smooth_ref.sheet_scene(pkg, pair)
+        flat = scene.build_scene(distinct_meshes=True)
+        sh = orc.SceneHandle(flat)
+        textures = texture_ref.pool(pkg) + [normal_map_ref.bumpy_map(pkg), normal_map_ref.flat_map(pkg)]
+        names = ("sheet", "floor") + tuple(m for m in pair if m in ("diffuse", "metal"))
+        binding = texture_ref.bind(scene, flat, {m: k % 3 for k, m in enumerate(names)})
+        nbinding = texture_ref.bind(scene, flat, {m: 3 for m in names})
+        st = texture_ref.random_texcoords(flat)
+        sky = dict(env=env, entries=entries)
+        tex = dict(textures=textures, binding=binding, texcoords=st)
+        on = dict(direct=True, env_light=True, mis=True, normals=smooth_ref.scene_vertex_normals(flat), smooth=True, textured=True,
+                  nbinding=nbinding, normal_maps=True, roulette=1, **sky, **tex)
+
+        def megakernel(name, iter_begin=0, iter_count=n, **kw):
+            r = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iter_count, mb, pkg=pkg, scene_handle=sh, **kw)
+            assert (r["ended"].sum() > 0) == (kw.get("roulette", 0) >= 1), name
+            if "lamp" in pair and kw.get("direct"):
+                assert r["shadow_rays"] > r["unoccluded"] > 0, name
+                assert not kw.get("mis") or r["mis_emitter_hits"] > 0, name
+            out.update({f"{tag}_{name}_{k}": np.asarray(r[k]) for k in LOOP_REF_OPTIONS})
+            cases.append(f"{tag}_{name}")
+            return r
+
+        first = megakernel("all", **on)
+        megakernel("all_far", iter_begin=c["far_iteration"], **on)
+        megakernel("all_lens", lens=(0.05, 3.0), **on)
+        megakernel("all_continued", iter_begin=n, iter_count=1, prev=first, **on)
+        megakernel("all_but_smooth_mis_roulette", **{**on, "smooth": False, "mis": False, "roulette": 0})
+        megakernel("map_alone", nbinding=nbinding, normal_maps=True, **sky, **tex)
+        megakernel("texture_alone", textured=True, **sky, **tex)
+        megakernel("smooth_alone", normals=on["normals"], smooth=True, **sky)
+        megakernel("mis_alone", direct=True, env_light=True, mis=True, **sky)
+        megakernel("env_light_alone", env_light=True, **sky)
+        if tag == "dm":
+            bad = st.copy()
+            bad[::7, 0] = np.nan
+            megakernel("all_nan", **{**on, "texcoords": bad})
+        r = loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, n, mb, roulette=1, env=env, lens=(0.05, 3.0), scene_handle=sh)
+        assert r["ended"].sum() > 0, tag
+        out.update({f"{tag}_streaming_{k}": np.asarray(r[k]) for k in LOOP_REF_STREAMING})
+    for k in LOOP_REF_COUNTERS:
+        assert any(out[f"{name}_{k}"] > 0 for name in cases), k
+    return out
+
+
 def main_loop_ref():
     np.savez_compressed(os.path.join(HERE, "loop_ref.npz"), **loop_ref_cases())
     print("wrote", os.path.join(HERE, "loop_ref.npz"))
+
+
+def main_loop_ref_options():
+    np.savez_compressed(os.path.join(HERE, "loop_ref_options.npz"), **loop_ref_option_cases())
+    print("wrote", os.path.join(HERE, "loop_ref_options.npz"))
 
 
 def main():
@@ -264,8 +340,11 @@ if __name__ == "__main__":
         main_interleaved()
     elif sys.argv[1:] == ["loop_ref"]:
         main_loop_ref()
+    elif sys.argv[1:] == ["loop_ref_options"]:
+        main_loop_ref_options()
     else:
         main()
         main_multimesh()
         main_interleaved()
         main_loop_ref()
+        main_loop_ref_options()

@@ -4,11 +4,9 @@ tests/test_lens_cpu.py and tests/test_gpu_lens.py, not the thing under test.
 The reference's camera is a pinhole, so the oracle (oracle/oracle.c) cannot check a lens and stays as it is.  This file restates the
 primary ray under a lens from the oracle's pinned pieces -- orc_to_gpu_camera (the camera matrix), orc_path_seed / orc_rng_* (every
 draw, through ref_f32.stream_draws), orc_sincos -- and, operation by operation, orc_generate_ray's u, v and direction (oracle.c:
-290-293) and glm's mat4 * vec4 (ref_f32._xform_point's order).  The render loops are lit_ref's own: render_streaming and
-render_megakernel here call lit_ref's with this module's primary generator in lit_ref._primary's place for the length of the call.
-lens None, or a radius of 0, is the pinhole: lit_ref's results themselves.  Every numpy operation below is one binary32 operation of
-section 5i's list, in its order (numpy does not contract into FMA)."""
-import contextlib
+290-293) and glm's mat4 * vec4 (ref_f32._xform_point's order).  The render loops are loop_ref's, which take `lens` as an option and
+draw their primary rays from `primary` below.  lens None, or a radius of 0, is the pinhole: lit_ref._primary's rays themselves.
+Every numpy operation below is one binary32 operation of section 5i's list, in its order (numpy does not contract into FMA)."""
 import ctypes as C
 import ctypes.util
 
@@ -116,28 +114,3 @@ def primary(orc, camera, w, h, pixels, iteration, lens):
     lx, ly, _ = lens_points(orc, pixels, iteration, lens[0])
     o, d = rays_from_parts(m, dx, dy, lx, ly, lens[1])
     return o, d, np.full(len(dx), F(1e-4), dtype=np.float32), states
-
-
-@contextlib.contextmanager
-def _primary_in_place(lens):
-    if not is_on(lens):
-        yield
-        return
-    saved = lit_ref._primary
-    lit_ref._primary = lambda orc, camera, w, h, pixels, iteration: primary(orc, camera, w, h, pixels, iteration, lens)
-    try:
-        yield
-    finally:
-        lit_ref._primary = saved
-
-
-def render_streaming(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, lens=None, **kw):
-    """lit_ref.render_streaming under the lens (its keywords: roulette, prev, pixels, slot_offset, scene_handle, record)"""
-    with _primary_in_place(lens):
-        return lit_ref.render_streaming(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, **kw)
-
-
-def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, lens=None, **kw):
-    """lit_ref.render_megakernel under the lens (its keywords: direct, roulette, prev, scene_handle, record)"""
-    with _primary_in_place(lens):
-        return lit_ref.render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, **kw)

@@ -1,28 +1,27 @@
-"""CPU restatement of the render loops WITH the library's extensions -- emissive materials (ptc_material type 3), direct lighting in
-the megakernel (ptc_set_param "direct_light") and Russian roulette (ptc_set_param "roulette", section 5h) -- in
-numpy binary32.  TEST INFRASTRUCTURE: the checker of tests/test_gpu_emissive.py, test_gpu_direct_loop.py and test_gpu_roulette.py,
-not the thing under test.  Each loop and each rule stands here once; a feature is an option of its loop.
+"""CPU restatement of what the render loops are built from, WITH the library's extensions -- emissive materials (ptc_material type 3)
+and Russian roulette (ptc_set_param "roulette") -- in numpy binary32.  TEST INFRASTRUCTURE: the pieces of
+tests/loop_ref.py, the checker of tests/test_gpu_emissive.py, test_gpu_direct_loop.py and test_gpu_roulette.py, not the thing under
+test.  Each rule stands here once; the loops that apply them stand in loop_ref.
 
-The reference has none of the three, so the oracle (oracle/oracle.c) cannot check them and stays as it is.  This file restates
-the oracle's streaming loop (oracle.c:1055-1125, and its interleaved-rows variant) and its megakernel loop (oracle.c:
-1283-1305) with the rules added, built from the oracle's pinned pieces:
+The reference has neither, so the oracle (oracle/oracle.c) cannot check them and stays as it is.  loop_ref restates the oracle's
+streaming loop (oracle.c:1055-1125, and its interleaved-rows variant) and its megakernel loop (oracle.c:1283-1305) with the rules
+added, built from the oracle's pinned pieces:
   - orc_generate_ray (primary rays), orc_intersect_rays (closest hits, each bounce; the HIT FLAG of the shadow rays),
     orc_path_seed / orc_rng_* (every draw), orc_sincos (random_in_unit_sphere);
-  - restated operation by operation: evaluate_material and random_in_unit_sphere (oracle.c:825-916), the sky, the stable
-    partition on bounces_left, the cap (paths alive after the last bounce keep the colour the last bounce left) and the
-    running-mean gather; direct_ref.light_table / light_sample (the lamp table and section 5f's light sample).
+  - restated operation by operation, here: evaluate_material and random_in_unit_sphere (oracle.c:825-916), the sky, the primary
+    rays; there: the stable partition on bounces_left, the cap (paths alive after the last bounce keep the colour the last bounce
+    left) and the running-mean gather.
 The emissive rule: a path whose closest hit has an emissive material ends at that bounce with colour * emission (a
 binary32 multiply per component, like the miss's colour * sky), makes no draw there, and drops out of the partition like a
-miss; at bounce 0 it records the hit's normal and t.  The direct-light rule stands at render_megakernel, the roulette rule at
-play.  On scenes without emitters, with both options off, every result equals the oracle's bit for bit
-(tests/test_lit_ref_cpu.py); tests/golden/loop_ref.npz pins the bits of every option (tests/test_loop_ref_golden_cpu.py).
+miss; at bounce 0 it records the hit's normal and t.  The roulette rule stands at play.  On scenes without emitters, with every
+option off, every result of the loops equals the oracle's bit for bit (tests/test_lit_ref_cpu.py); tests/golden/loop_ref.npz and
+loop_ref_options.npz pin the bits of every option (tests/test_loop_ref_golden_cpu.py).
 Every numpy operation below is one binary32 operation of the C source, in its order (numpy does not contract into FMA)."""
 import ctypes as C
 
 import numpy as np
 
-import direct_ref
-from ref_f32 import PI2, Draws, F, _dot, _normalize, _sign, _sincos, stream_draws, stream_states
+from ref_f32 import PI2, Draws, F, _dot, _normalize, _sign, _sincos, stream_draws  # noqa: F401  (Draws: for this module's users)
 
 FLT_MAX = F(np.finfo(np.float32).max)
 SKY_X = np.array([0.5, 0.7, 1.0], dtype=np.float32)
@@ -141,58 +140,12 @@ def _primary(orc, camera, w, h, pixels, iteration):
     return o, d, tmin, states
 
 
-def _fold(fb, local, iteration, value):
-    """temporal_accumulate (oracle.c:920-924) into fb[local]."""
-    if iteration == 0:
-        fb[local] = value
-    else:
-        sc = F(iteration + 1)
-        fb[local] = (fb[local] * (sc - F(1.0)) + value) / sc
-
-
-def _frame(prev, P):
-    """The running means a render folds its samples into, (colour [P, 3], normal [P, 3], depth [P]): zeros, or an earlier
-    result's planes (copied: the result handed in stays as it is)."""
-    if prev is None:
-        return np.zeros((P, 3), np.float32), np.zeros((P, 3), np.float32), np.zeros(P, np.float32)
-    return tuple(np.array(prev[k], dtype=np.float32).reshape(shape) for k, shape in (("color", (P, 3)), ("normal", (P, 3)), ("depth", P)))
-
-
-def _deposit(frame, local, iteration, color, normal, depth):
-    """One iteration's samples into the three planes; path i belongs to the frame's place local[i]."""
-    for fb, value in zip(frame, (color, normal, depth)):
-        _fold(fb, local, iteration, value)
-
-
-def _planes(frame, rows, w):
-    return {"color": frame[0].reshape(rows, w, 3), "normal": frame[1].reshape(rows, w, 3), "depth": frame[2].reshape(rows, w)}
-
-
 def interleaved_pixels(w, h, rank, nranks, block_rows):
     """The rank's slots -> frame pixels (band_slot_to_pixel, oracle.c:996-1004), in the rank's order."""
     rows = []
     for first in range(rank * block_rows, h, nranks * block_rows):
         rows.extend(range(first, min(first + block_rows, h)))
     return (np.asarray(rows, dtype=np.int64)[:, None] * w + np.arange(w)[None, :]).reshape(-1)
-
-
-def _closest_hits(orc, flat, sh, materials, o, d, tmin, at, bounce, color, normal, depth):
-    """The bounce's closest hits of the paths in rows `at`, and what a bounce does before any draw: a miss takes colour * sky,
-    a hit at bounce 0 records its normal and t, an emitter is told from the rest.
-    -> (records [len(o)], rows on an emitter, their emission [.., 3], rows on another material, those materials' types)."""
-    recs_at, hit_at = orc.intersect_rays(flat, _rays(o[at], tmin[at], d[at]), scene_handle=sh)
-    recs = np.zeros(len(o), dtype=recs_at.dtype)
-    recs[at] = recs_at
-    hit_at = hit_at.astype(bool)
-    miss, hi = at[~hit_at], at[hit_at]
-    color[miss] = color[miss] * sky(d[miss])
-    if bounce == 0:
-        depth[hi] = recs["t"][hi]
-        normal[hi] = recs["normal"][hi]
-    mat = recs["material_id"][hi].astype(np.int64)
-    typ = materials["type"][mat]
-    lamp = typ == EMISSIVE
-    return recs, hi[lamp], materials["p"][mat[lamp], :3].astype(np.float32), hi[~lamp], typ[~lamp]
 
 
 def plays_at(roulette, bounce, max_bounces):
@@ -203,7 +156,7 @@ def plays_at(roulette, bounce, max_bounces):
 def play(orc, color, idx, indices, iteration, bounce, record=None):
     """The roulette rule, one binary32 operation per line item.  With k = roulette >= 1, a path plays at
     bounce b iff plays_at(k, b, max_bounces) -- b >= k and b is not the last bounce --, its closest hit exists and the hit's
-    material is not emissive; both loops play after the emitter check and before evaluate_material.  c = the throughput that
+    material is not emissive; both loops (loop_ref) play after the emitter check and before evaluate_material.  c = the throughput that
     came into the bounce:
       1. q = max(max(c.r, c.g), c.b), by compare and select ((a < b) ? b : a);
       2. q >= 1: nothing happens (no draw, no division);
@@ -231,136 +184,3 @@ def play(orc, color, idx, indices, iteration, bounce, record=None):
         record.append({"kind": "roulette", "iteration": iteration, "bounce": bounce, "q": q, "skipped": skip, "ended": ended,
                        "after": c[div].copy(), "indices": np.asarray(indices).copy()})
     return ended, skip
-
-
-def _tally(tables, it, bounce, ended, skip):
-    tables["played"][it, bounce], tables["ended"][it, bounce], tables["skipped"][it, bounce] = len(ended), ended.sum(), skip.sum()
-
-
-def render_streaming(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, roulette=0, prev=None, pixels=None,
-                     slot_offset=None, scene_handle=None, record=None):
-    """orc_render_streaming (pixels None) or orc_render_streaming_interleaved (pixels = interleaved_pixels(..),
-    slot_offset = the rank's first global slot, added at every bounce) with emitters and, with roulette >= 1, the rule of
-    play on the stream of slot_base + slot.  Returns the oracle's dict -- color / normal / depth over the frame's (or the
-    rank's) pixels in order, live [iter, bounce], rays -- and played / ended / skipped, each [iter, bounce] (0 where no bounce
-    plays).  record: a list that gets play's entries."""
-    sh = scene_handle or orc.SceneHandle(flat)
-    materials = np.asarray(flat.materials)
-    if pixels is None:
-        pixels = np.arange(w * h, dtype=np.int64)
-        slot_base = 0
-    else:
-        slot_base = int(slot_offset)
-    P = len(pixels)
-    frame = _frame(prev, P)
-    live = np.zeros((iter_count, max_bounces), dtype=np.uint32)
-    tables = {k: np.zeros((iter_count, max_bounces), dtype=np.int64) for k in TABLES}
-    rays = 0
-    for it in range(iter_count):
-        iteration = iter_begin + it
-        o, d, tmin, _ = _primary(orc, camera, w, h, pixels, iteration)
-        color = np.ones((P, 3), dtype=np.float32)
-        normal = -d
-        depth = np.full(P, F(1e6), dtype=np.float32)
-        local = np.arange(P)  # slot -> the pixel's place in the frame (or in the rank's rows)
-        n = P
-        for b in range(max_bounces):
-            if n == 0:
-                break
-            live[it, b] = n
-            rays += n
-            recs, em, emission, sc, _ = _closest_hits(orc, flat, sh, materials, o, d, tmin, np.arange(n), b, color, normal, depth)
-            color[em] = color[em] * emission  # the emissive rule: colour * emission, no draw, the path ends
-            if plays_at(roulette, b, max_bounces):  # before any material draw of the bounce
-                ended, skip = play(orc, color, sc, slot_base + sc, iteration, b, record)
-                _tally(tables, it, b, ended, skip)
-                sc = sc[~ended]
-            states = np.zeros(P, dtype=np.uint32)
-            states[sc] = stream_states(orc, slot_base + sc, iteration, 0, b)  # the material stream: keyed on the SLOT, per bounce
-            shade(orc, materials, o, d, tmin, recs, sc, Draws(orc, states), color)
-            # stable partition on bounces_left > 0 (oracle.c:1082-1104): live first, then the rest, both in order
-            goes_on = np.zeros(n, dtype=bool)
-            goes_on[sc] = True
-            order = np.concatenate([np.nonzero(goes_on)[0], np.nonzero(~goes_on)[0], np.arange(n, P)])
-            o, d, tmin, color, normal, depth, local = (a[order] for a in (o, d, tmin, color, normal, depth, local))
-            n = len(sc)
-        _deposit(frame, local, iteration, color, normal, depth)
-    return {**_planes(frame, P // w, w), "live": live, "rays": rays, **tables}
-
-
-def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, direct=False, roulette=0, prev=None,
-                      scene_handle=None, record=None):
-    """orc_render_megakernel (oracle.c:1280-1330) with emitters: one generator per pixel for the whole path; an emissive
-    hit records normal / depth if it is the first hit, then colour *= emission and the path ends, with no draw.
-
-    direct: the rule of DESIGN section 5g (ptc_set_param "direct_light" 1).  A per-path radiance sum, deposited as radiance +
-    colour; at every hit on a diffuse material, after evaluate_material (colour = throughput x albedo), one light sample
-    (direct_ref.light_sample: section 5f, items 2-5) at the hit point about the hit's normal from the stream
-    seed(path_seed(pixel, iteration) ^ kLightSeedXor), discard(3 * bounce); a sampled sample traces {p, 1e-4, w, d * 0.999} and,
-    if the oracle reports no hit, radiance += colour * contribution; an emissive hit ends the path with colour * emission if
-    the vertex before drew no light sample (the camera, metal, glass), else with 0.  A scene whose lamp table is empty or has no
-    weight renders as without the option.
-
-    roulette >= 1: the rule of play, on the roulette stream of the PIXEL.  A path that ends leaves colour 0, draws nothing, takes
-    no light sample and adds nothing to the three loop counters; a survivor's light sample is weighted with the divided colour.
-
-    -> dict(color, normal, depth, rays, diffuse_hits, shadow_rays, unoccluded, played, ended, skipped); the counters are 0
-    without direct, the tables ([iter, bounce]) where no bounce plays.  record: a list that gets play's entries and, per
-    (iteration, bounce) with light samples, a "kind": "light" entry with the diffuse hits' pixels, points, normals, the sample
-    drawn there and which shadow rays came through."""
-    sh = scene_handle or orc.SceneHandle(flat)
-    materials = np.asarray(flat.materials)
-    lit = False
-    if direct:
-        lamps = direct_ref.light_table(flat)
-        lit = len(lamps[0]) > 0 and float(lamps[1]["total_weight"]) > 0.0
-    P = w * h
-    frame = _frame(prev, P)
-    tables = {k: np.zeros((iter_count, max_bounces), dtype=np.int64) for k in TABLES}
-    rays = diffuse_hits = shadow_rays = unoccluded = 0
-    for it in range(iter_count):
-        iteration = iter_begin + it
-        o, d, tmin, states = _primary(orc, camera, w, h, np.arange(P), iteration)
-        draws = Draws(orc, states)
-        color = np.ones((P, 3), dtype=np.float32)
-        radiance = np.zeros((P, 3), dtype=np.float32)
-        count_emission = np.ones(P, dtype=bool)  # (stays all True unless lit)
-        normal = -d
-        depth = np.full(P, F(1e6), dtype=np.float32)
-        active = np.arange(P)
-        for b in range(max_bounces):
-            if len(active) == 0:
-                break
-            rays += len(active)
-            recs, em, emission, sc, typ = _closest_hits(orc, flat, sh, materials, o, d, tmin, active, b, color, normal, depth)
-            color[em] = np.where(count_emission[em][:, None], color[em] * emission, F(0.0))
-            if plays_at(roulette, b, max_bounces):
-                ended, skip = play(orc, color, sc, sc, iteration, b, record)
-                _tally(tables, it, b, ended, skip)
-                sc, typ = sc[~ended], typ[~ended]
-            shade(orc, materials, o, d, tmin, recs, sc, draws, color)
-            if lit:
-                count_emission[sc] = typ != 0
-                df = sc[typ == 0]
-                diffuse_hits += len(df)
-                pts = recs["point"][df].astype(np.float32)
-                nrm = recs["normal"][df].astype(np.float32)
-                u = direct_ref.light_draws(orc, df, iteration, 3 * b)
-                smp = direct_ref.light_sample(orc, flat, lamps, pts, nrm, u)
-                sel = np.nonzero(smp["sampled"])[0]
-                shadow_rays += len(sel)
-                clear = np.zeros(len(df), dtype=bool)
-                if len(sel):
-                    _, blocked = orc.intersect_rays(flat, smp["rays"][sel], scene_handle=sh)
-                    clear[sel] = blocked == 0
-                unoccluded += int(clear.sum())
-                got = df[clear]
-                radiance[got] = radiance[got] + color[got] * smp["contribution"][clear]
-                if record is not None:
-                    record.append({"kind": "light", "iteration": iteration, "bounce": b, "pixels": df, "points": pts, "normals": nrm,
-                                   "sample": smp, "clear": clear})
-            active = sc
-        total = radiance + color if lit else color   # (no lamp table: the plain kernel deposits colour itself)
-        _deposit(frame, np.arange(P), iteration, total, normal, depth)
-    return {**_planes(frame, h, w), "rays": rays, "diffuse_hits": diffuse_hits, "shadow_rays": shadow_rays,
-            "unoccluded": unoccluded, **tables}

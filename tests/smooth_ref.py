@@ -5,17 +5,10 @@ What stands here: the host's area-weighted vertex normals and the shading normal
 operation of the rule in its order (numpy does not contract into FMA); the winner of a closest hit -- the oracle's closest hit, and among
 the triangles the one whose own binary32 ray_triangle lines reproduce the oracle's t bit for bit, ties resolved by the depth-first leaf
 order of the oracle's tree within a mesh and by object order across objects (the reference accepts an equal t, so the one visited last
-wins); and mis_ref.render_megakernel's loop stated again with one more option, `smooth`, from the pinned pieces of lit_ref / direct_ref /
-env_ref / env_light_ref / mis_ref / lens_ref."""
+wins).  The loop that applies them is loop_ref.render_megakernel's under `smooth`."""
 import numpy as np
 
-import direct_ref
-import env_light_ref
-import env_ref
-import lens_ref
-import lit_ref
-import mis_ref
-from ref_f32 import Draws, F, _cross, _dot, _normalize, _xform_point
+from ref_f32 import F, _cross, _dot, _normalize, _xform_point
 
 FLT_MAX = F(np.finfo(np.float32).max)
 EPS = F(0.0000001)
@@ -231,153 +224,6 @@ def _shade_rows(flat, normals, obj, first, u, v, g, d):
         corner[k] = fv + idx[fi + int(f):fi + int(f) + 3]
     inv = np.asarray(flat.objects["inv_m"], dtype=np.float32)[obj]
     return shading_normal(normals[corner[:, 0]], normals[corner[:, 1]], normals[corner[:, 2]], u, v, g, d, inv)
-
-
-# ---- the loop ----------------------------------------------------------------------------------------------------------------------------
-def render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, normals=None, smooth=False, env=None, entries=None,
-                      env_light=False, direct=False, mis=False, roulette=0, lens=None, prev=None, scene_handle=None):
-    """mis_ref.render_megakernel's loop with one more option.  smooth with vertex normals is the rule of section 5n: at every closest hit
-    on a triangle the shading normal n_s (shading_normal; counted as formed or as a fall-back) takes the geometric normal's place in the
-    normal plane at bounce 0, in evaluate_material, in the light samples and in bsdf_pdf; the geometric normal keeps `side` and the
-    lamp-side cosine of an emitter hit.  A lamp's or the environment's sample at a triangle hit whose direction has dot(w, g) <= 0 counts
-    as not sampled (counted as culled); after evaluate_material and the light samples a diffuse or metal triangle hit whose new direction
-    has dot(d, g) <= 0 ends the path with colour 0 (counted as absorbed).  Without smooth or without normals every result is mis_ref's.
-    -> mis_ref's dict and the four counters of COUNTERS."""
-    if not smooth or normals is None:
-        out = mis_ref.render_megakernel(orc, flat, camera, w, h, iter_begin, iter_count, max_bounces, env=env, entries=entries, env_light=env_light,
-                                        direct=direct, mis=mis, roulette=roulette, lens=lens, prev=prev, scene_handle=scene_handle)
-        return {**out, **{k: 0 for k in COUNTERS}}
-    sh = scene_handle or orc.SceneHandle(flat)
-    materials = np.asarray(flat.materials)
-    lit = False
-    if direct:
-        lamps = direct_ref.light_table(flat)
-        lit = len(lamps[0]) > 0 and float(lamps[1]["total_weight"]) > 0.0
-    lit_env = bool(env_light) and env is not None and entries is not None
-    mis = bool(mis) and (lit or lit_env)
-    texels = env_ref.apron(env) if lit_env else None
-    n_map = texels.shape[0] - 2 if lit_env else 0
-    inv_pdf_m = mis_ref.material_pdf(flat, lamps) if (mis and lit) else None
-    P = w * h
-    frame = lit_ref._frame(prev, P)
-    rays = diffuse_hits = shadow_rays = unoccluded = 0
-    env_diffuse_hits = env_shadow_rays = env_unoccluded = 0
-    mis_emitter_hits = mis_misses = 0
-    formed = fallbacks = absorbed = culled = 0
-    with env_ref._sky_in_place(env), lens_ref._primary_in_place(lens):
-        for it in range(iter_count):
-            iteration = iter_begin + it
-            o, d, tmin, states = lit_ref._primary(orc, camera, w, h, np.arange(P), iteration)
-            draws = Draws(orc, states)
-            color = np.ones((P, 3), dtype=np.float32)
-            radiance = np.zeros((P, 3), dtype=np.float32)
-            count_emission = np.ones(P, dtype=bool)
-            count_env = np.ones(P, dtype=bool)
-            bsdf_pdf = np.zeros(P, dtype=np.float32)
-            normal = -d
-            depth = np.full(P, F(1e6), dtype=np.float32)
-            active = np.arange(P)
-            for b in range(max_bounces):
-                if len(active) == 0:
-                    break
-                rays += len(active)
-                d_in = d.copy()
-                bounce_rays = lit_ref._rays(o[active], tmin[active], d[active])
-                recs, em, emission, sc, typ = lit_ref._closest_hits(orc, flat, sh, materials, o, d, tmin, active, b, color, normal, depth)
-                # the shading normal of every triangle hit of the bounce, an emitter's and a path's that roulette will end among them
-                hit_at = np.zeros(len(active), dtype=bool)
-                at_of = np.full(P, -1, dtype=np.int64)
-                at_of[active] = np.arange(len(active))
-                hit_at[at_of[em]] = hit_at[at_of[sc]] = True
-                w_obj, w_first, w_u, w_v = winners(orc, flat, sh, bounce_rays, recs[active], hit_at)
-                tri = np.zeros(P, dtype=bool)
-                tri[active] = w_first >= 0
-                shaded = recs.copy()
-                trows = active[w_first >= 0]
-                if len(trows):
-                    k = at_of[trows]
-                    ns, fell = _shade_rows(flat, normals, w_obj[k], w_first[k], w_u[k], w_v[k], recs["normal"][trows].astype(np.float32), d_in[trows])
-                    shaded["normal"][trows] = ns
-                    formed += int((~fell).sum())
-                    fallbacks += int(fell.sum())
-                    if b == 0:
-                        normal[trows] = ns
-                if lit_env:  # a miss behind an environment sample (colour is colour * sky here)
-                    hit = np.zeros(P, dtype=bool)
-                    hit[em] = hit[sc] = True
-                    miss = active[~hit[active]]
-                    gated = miss[~count_env[miss]]
-                    if mis:
-                        mis_misses += len(gated)
-                        color[gated] = color[gated] * mis_ref.balance(bsdf_pdf[gated], mis_ref.pdf(entries, n_map, d[gated]))[:, None]
-                    else:
-                        color[gated] = F(0.0)
-                if mis:
-                    seen = color[em] * emission
-                    gated = ~count_emission[em]
-                    mis_emitter_hits += int(gated.sum())
-                    t = recs["t"][em].astype(np.float32)
-                    cos_l = np.abs(_dot(recs["normal"][em].astype(np.float32), d[em]))  # the geometric normal
-                    m_of = recs["material_id"][em].astype(np.int64)
-                    p_l = mis_ref.lamp_density(t * t, cos_l, inv_pdf_m[m_of] if inv_pdf_m is not None else np.zeros(len(em), np.float32))
-                    color[em] = np.where(gated[:, None], seen * mis_ref.balance(bsdf_pdf[em], p_l)[:, None], seen)
-                else:
-                    color[em] = np.where(count_emission[em][:, None], color[em] * emission, F(0.0))
-                if lit_ref.plays_at(roulette, b, max_bounces):
-                    ended, _ = lit_ref.play(orc, color, sc, sc, iteration, b)
-                    sc, typ = sc[~ended], typ[~ended]
-                lit_ref.shade(orc, materials, o, d, tmin, shaded, sc, draws, color)
-                df = sc[typ == 0]
-                pts = recs["point"][df].astype(np.float32)
-                nrm = shaded["normal"][df].astype(np.float32)
-                geo = recs["normal"][df].astype(np.float32)
-                weigh = mis and b != max_bounces - 1
-                if mis:
-                    bsdf_pdf[df] = mis_ref.lobe_density(_dot(nrm, d[df]))
-                if lit:
-                    count_emission[sc] = typ != 0
-                    diffuse_hits += len(df)
-                    u = direct_ref.light_draws(orc, df, iteration, 3 * b)
-                    smp = direct_ref.light_sample(orc, flat, lamps, pts, nrm, u)
-                    contribution = smp["contribution"]
-                    if weigh and len(df):
-                        d2, cos_l, inv_pdf, cos_r = mis_ref.light_terms(orc, flat, lamps, pts, nrm, u)
-                        contribution = contribution * mis_ref.balance(mis_ref.lamp_density(d2, cos_l, inv_pdf), mis_ref.lobe_density(cos_r))[:, None]
-                    with np.errstate(invalid="ignore"):
-                        behind = smp["sampled"] & tri[df] & (_dot(smp["rays"][:, 4:7].astype(np.float32), geo) <= F(0.0))
-                    culled += int(behind.sum())
-                    got, traced = env_light_ref._arrived(orc, flat, sh, smp["sampled"] & ~behind, smp["rays"])
-                    shadow_rays += traced
-                    unoccluded += int(got.sum())
-                    radiance[df[got]] = radiance[df[got]] + color[df[got]] * contribution[got]
-                if lit_env:
-                    count_env[sc] = typ != 0
-                    env_diffuse_hits += len(df)
-                    v, u = env_light_ref.stream(orc, df, iteration, 4 * b)
-                    smp = env_light_ref.sample(entries, texels, pts, nrm, v, u)
-                    contribution = smp["contribution"]
-                    if weigh and len(df):
-                        jac, cos_r = mis_ref.env_terms(entries, n_map, nrm, smp["square"], u)
-                        contribution = contribution * mis_ref.balance(mis_ref.env_density(jac), mis_ref.lobe_density(cos_r))[:, None]
-                    with np.errstate(invalid="ignore"):
-                        behind = smp["sampled"] & tri[df] & (_dot(smp["w"].astype(np.float32), geo) <= F(0.0))
-                    culled += int(behind.sum())
-                    got, traced = env_light_ref._arrived(orc, flat, sh, smp["sampled"] & ~behind, smp["rays"])
-                    env_shadow_rays += traced
-                    env_unoccluded += int(got.sum())
-                    radiance[df[got]] = radiance[df[got]] + color[df[got]] * contribution[got]
-                # the absorbed continuation: behind the light samples, glass exempt
-                with np.errstate(invalid="ignore"):
-                    gone = tri[sc] & (typ != 2) & (_dot(d[sc], recs["normal"][sc].astype(np.float32)) <= F(0.0))
-                absorbed += int(gone.sum())
-                color[sc[gone]] = F(0.0)
-                active = sc[~gone]
-            total = radiance + color if (lit or lit_env) else color
-            lit_ref._deposit(frame, np.arange(P), iteration, total, normal, depth)
-    return {**lit_ref._planes(frame, h, w), "rays": rays, "diffuse_hits": diffuse_hits, "shadow_rays": shadow_rays, "unoccluded": unoccluded,
-            "env_diffuse_hits": env_diffuse_hits, "env_shadow_rays": env_shadow_rays, "env_unoccluded": env_unoccluded,
-            "mis_emitter_hits": mis_emitter_hits, "mis_misses": mis_misses, "shading_normals": formed, "fallbacks": fallbacks,
-            "absorbed": absorbed, "culled_light_samples": culled}
 
 
 # ---- the meshes and scenes the CPU and GPU tests share ----------------------------------------------------------------------------------

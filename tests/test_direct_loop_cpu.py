@@ -1,5 +1,5 @@
 """Direct lighting in the megakernel without a GPU: the binding, and the CPU restatement
-(lit_ref.render_megakernel with direct=True) against the same loop without the option for everything but the colour, on the
+(loop_ref.render_megakernel with direct=True) against the same loop without the option for everything but the colour, on the
 no-lamp and glass-fronted-lamp scenes for the emission gate, and against direct_ref's sample for the light stream at bounce 0."""
 import ctypes as C
 import os
@@ -10,7 +10,7 @@ import pytest
 
 import direct_loop_scenes as scenes
 import direct_ref as dr
-import lit_ref as lr
+import loop_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,8 +24,8 @@ def _both(orc, key, scene, mb, iters=2):
         flat = scene.build_scene()
         sh = orc.SceneHandle(flat)
         record = []
-        lit = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, iters, mb, direct=True, scene_handle=sh, record=record)
-        plain = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, iters, mb, scene_handle=sh)
+        lit = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, iters, mb, direct=True, scene_handle=sh, record=record)
+        plain = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, iters, mb, scene_handle=sh)
         _cache[(key, mb)] = (flat, lit, plain, record)
     return _cache[(key, mb)]
 

@@ -1,8 +1,8 @@
 """Environment lighting (ptc_set_environment) without a GPU: the library's host build of csrc/pt_env.hpp
 (ptc_check_environment, ptc_check_environment_apron) against the numpy restatement tests/env_ref.py -- the checker of
 tests/test_gpu_environment.py -- bit for bit; the apron against the table; the properties the rule promises (index range, weights in
-[0, 1), zeros for the bad directions, continuity across the fold, convergence on a smooth sky); the refusals; env_ref's loops with no
-environment are lit_ref's own; the Python field's checks."""
+[0, 1), zeros for the bad directions, continuity across the fold, convergence on a smooth sky); the refusals; loop_ref's loops with env=None
+are the loops without the option; the Python field's checks."""
 import ctypes as C
 import json
 import os
@@ -14,6 +14,7 @@ import pytest
 
 import env_ref
 import lit_ref
+import loop_ref
 
 SIZES = (2, 5, 64)
 
@@ -181,13 +182,13 @@ def test_the_refusals(pkg):
 
 
 def test_no_environment_is_lit_ref_s_own_render(pkg, orc):
-    """env None: env_ref's loops return lit_ref's results and leave lit_ref.sky alone; with a map they put it back afterwards"""
+    """env None given is env not given, in both loops; with a map or without, lit_ref.sky is left alone (the sky is an argument)"""
     w, h = 16, 12
     scene = pkg.scenes.cornell_spheres((w, h))
     flat = scene.build_scene()
     sky = lit_ref.sky
-    for mine, theirs in ((env_ref.render_streaming, lit_ref.render_streaming), (env_ref.render_megakernel, lit_ref.render_megakernel)):
-        a, b = mine(orc, flat, scene.camera, w, h, 0, 2, 3), theirs(orc, flat, scene.camera, w, h, 0, 2, 3)
+    for mine in (loop_ref.render_streaming, loop_ref.render_megakernel):
+        a, b = mine(orc, flat, scene.camera, w, h, 0, 2, 3, env=None), mine(orc, flat, scene.camera, w, h, 0, 2, 3)
         for k in ("color", "normal", "depth"):
             assert np.array_equal(_bits(a[k]), _bits(b[k])), k
         assert a["rays"] == b["rays"]

@@ -13,6 +13,7 @@ import pytest
 
 import env_light_ref
 import env_ref
+import loop_ref
 
 SIZES = (2, 5, 64)
 T_BOUND = 4.073  # the two-sided 0.1 % point of Student's t, 15 degrees of freedom (test_gpu_direct_loop.test_same_expectation_lower_spread)
@@ -263,8 +264,8 @@ def test_unbiased_against_the_quadrature(pkg):
 
 
 def test_the_loop_with_the_option_off_is_env_ref_s(pkg, orc):
-    """env_light_ref.render_megakernel without env_light, and with it under no environment or a map of weight 0, is
-    env_ref.render_megakernel bit for bit; with it under a map with weight only colour differs"""
+    """loop_ref.render_megakernel with env_light given but inert -- off, or on under no environment or a map of weight 0 -- is the loop
+    without the option bit for bit; with it under a map with weight only colour differs"""
     w, h = 12, 8
     scene = pkg.scenes.cornell_spheres((w, h))
     flat = scene.build_scene()
@@ -272,14 +273,14 @@ def test_the_loop_with_the_option_off_is_env_ref_s(pkg, orc):
     entries, _, _ = env_light_ref.table_of(pkg, env)
     zeros = np.zeros((2, 2, 3), dtype=np.float32)
     for e, ent, on in ((env, entries, False), (None, None, True), (zeros, None, True)):
-        want = env_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 2, 4, env=e, direct=True, roulette=1)
-        got = env_light_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 2, 4, env=e, entries=ent, env_light=on, direct=True, roulette=1)
+        want = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 2, 4, env=e, direct=True, roulette=1)
+        got = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 2, 4, env=e, entries=ent, env_light=on, direct=True, roulette=1)
         for k in ("color", "normal", "depth"):
             assert np.array_equal(_bits(got[k]), _bits(want[k])), k
         assert all(got[k] == want[k] for k in ("rays", "diffuse_hits", "shadow_rays", "unoccluded"))
         assert got["env_diffuse_hits"] == 0
-    lit = env_light_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 2, 4, env=env, entries=entries, env_light=True, direct=True, roulette=1)
-    off = env_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 2, 4, env=env, direct=True, roulette=1)
+    lit = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 2, 4, env=env, entries=entries, env_light=True, direct=True, roulette=1)
+    off = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 2, 4, env=env, direct=True, roulette=1)
     assert all(np.array_equal(_bits(lit[k]), _bits(off[k])) for k in ("normal", "depth"))
     assert all(lit[k] == off[k] for k in ("rays", "diffuse_hits", "shadow_rays", "unoccluded"))
     assert lit["env_diffuse_hits"] > 0 and lit["env_diffuse_hits"] >= lit["env_shadow_rays"] >= lit["env_unoccluded"]

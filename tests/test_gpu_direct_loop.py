@@ -1,5 +1,5 @@
 """Direct lighting in the megakernel (ptc_set_param "direct_light" 1) on the GPU against its CPU restatement
-(tests/lit_ref.py, render_megakernel with direct=True), bit for bit: colour, first-hit normal and depth, ptc_stats.rays_total and the three loop counters
+(tests/loop_ref.py, render_megakernel with direct=True), bit for bit: colour, first-hit normal and depth, ptc_stats.rays_total and the three loop counters
 (diffuse hits, shadow rays traced, unoccluded).  Then what the rule promises beside the bits: normal / depth / rays_total equal to
 the plain megakernel's, a lamp-less scene untouched, interleaved ranks assembling to the one-context frame, the refusals, and a
 paired statistical test of the estimator (same expectation as the plain render, lower spread)."""
@@ -10,7 +10,7 @@ import pytest
 
 import direct_loop_scenes as scenes
 import direct_ref as D
-import lit_ref as lr
+import loop_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +49,7 @@ def _same(got, ref, what, planes=PLANES, counters=COUNTERS):
 
 def _against_restatement(pkg, orc, scene, w, h, mb, iters, what, iter_begin=0):
     flat = scene.build_scene()
-    ref = lr.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iters, mb, direct=True)
+    ref = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iters, mb, direct=True)
     got = _render(pkg, scene, flat, w, h, mb, iters, True, iter_begin)
     _same(got, ref, what)
     return flat, got, ref

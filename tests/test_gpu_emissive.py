@@ -1,4 +1,4 @@
-"""Emissive materials (ptc_material type 3, an extension: the reference has no emitters) on the GPU against tests/lit_ref.py,
+"""Emissive materials (ptc_material type 3, an extension: the reference has no emitters) on the GPU against tests/loop_ref.py,
 bit for bit: colour, first-hit normal and depth, ray totals and the live counts of the last frame.  A path whose closest hit
 is an emitter ends there with colour * emission and no draw, and leaves the stable partition like a miss -- so every later
 survivor's slot, and with it its random numbers, moves.  The scenes put the emitter in each place a closest hit can come
@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import lit_ref as lr
+import loop_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -29,9 +30,9 @@ def _reference(orc, key, flat, camera, mb, method="streaming"):
     k = (key, mb, method)
     if k not in _cache:
         if method == "streaming":
-            _cache[k] = lr.render_streaming(orc, flat, camera, W, H, 0, ITERS, mb)
+            _cache[k] = loop_ref.render_streaming(orc, flat, camera, W, H, 0, ITERS, mb)
         else:
-            _cache[k] = lr.render_megakernel(orc, flat, camera, W, H, 0, ITERS, mb)
+            _cache[k] = loop_ref.render_megakernel(orc, flat, camera, W, H, 0, ITERS, mb)
     return _cache[k]
 
 
@@ -121,7 +122,7 @@ def test_interleaved_ranks_with_emitters(pkg, orc):
     sh = orc.SceneHandle(flat)
     for rank in (0, 1):
         pixels = lr.interleaved_pixels(W, H, rank, 2, 8)
-        ref = lr.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, 6, pixels=pixels, slot_offset=rank * W * H,
+        ref = loop_ref.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, 6, pixels=pixels, slot_offset=rank * W * H,
                                   scene_handle=sh)
         got = _render(pkg, scene, flat, 6, interleave=(rank, 2, 8))
         _same(got, ref, ("interleaved", rank))
@@ -200,7 +201,7 @@ def test_random_object_lists_with_emitters(pkg, orc, seed):
     scene, kinds = _random_lit(pkg, seed)
     flat = scene.build_scene(distinct_meshes=True)
     assert 3 in flat.materials["type"].tolist()
-    ref = lr.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, 6)
+    ref = loop_ref.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, 6)
     for params in ((), KNOBS[seed % len(KNOBS)]):
         _same(_render(pkg, scene, flat, 6, params=params), ref, (seed, kinds, params))
 
@@ -239,7 +240,7 @@ def test_hip_pt_renders_the_lit_scene_file(pkg, orc, tmp_path):
     got = np.array(Image.open(out)).astype(np.int32)
     scene = pkg.json_parser.scene_from_json(path)
     w, h = scene.resolution
-    ref = lr.render_streaming(orc, scene.build_scene(), scene.camera, w, h, 0, 2, 6)
+    ref = loop_ref.render_streaming(orc, scene.build_scene(), scene.camera, w, h, 0, 2, 6)
     want = orc.preview(ref["color"], w, h, 0).astype(np.int32)
     assert got.shape == want.shape
     assert (ref["color"] > 1.0).any()

@@ -1,5 +1,5 @@
-"""Environment lighting (ptc_set_environment) on the GPU against its CPU restatement (tests/env_ref.py: lit_ref's loops
-with the lookup for a sky), bit for bit.  An environment changes only colour: every render here is compared in colour with the
+"""Environment lighting (ptc_set_environment) on the GPU against its CPU restatement (tests/loop_ref.py's loops
+with tests/env_ref.py's lookup for a sky), bit for bit.  An environment changes only colour: every render here is compared in colour with the
 restatement, and in normal, depth, the last frame's live counts and rays_total with the SAME context's render without an environment.
 The lookup itself through ptc_sample_environment; every schedule of the streaming loop, the megakernel, emitters, roulette, a lens,
 "direct_light", interleaved ranks, a late iteration; a map of zeros; a change of map between frames; removal; the refusals; denoise
@@ -15,6 +15,7 @@ import pytest
 
 import env_ref
 import lit_ref
+import loop_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -125,7 +126,7 @@ def _only_colour_differs(base, got, what, counters=()):
 def _ref_streaming(orc, flat, camera, w, h, mb, env=ENV, iters=ITERS, iter_begin=0, **kw):
     key = ("stream", id(flat), w, h, mb, id(env), iters, iter_begin, tuple(sorted((k, str(v)) for k, v in kw.items())))
     if key not in _cache:
-        _cache[key] = env_ref.render_streaming(orc, flat, camera, w, h, iter_begin, iters, mb, env=env, **kw)
+        _cache[key] = loop_ref.render_streaming(orc, flat, camera, w, h, iter_begin, iters, mb, env=env, **kw)
     return _cache[key]
 
 
@@ -181,7 +182,7 @@ def test_sizes_and_bounces(pkg, orc, w, h, mb, method):
     mega = method == "megakernel"
     base, got = _both(pkg, flat, scene.camera, w=w, h=h, mb=mb, method=pkg.GPUMethod.megakernel if mega else None)
     if mega:
-        ref = env_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, ITERS, mb, env=ENV)
+        ref = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, ITERS, mb, env=ENV)
     else:
         ref = _ref_streaming(orc, flat, scene.camera, w, h, mb)
     _colour_is(got, ref, (method, w, h, mb))
@@ -206,7 +207,7 @@ def test_prefold_on_the_open_room(pkg, orc):
 def test_emitters_roulette_and_lens(pkg, orc, method, scene_name, roulette, lens):
     scene, flat = _scene(pkg, scene_name)
     mega = method == "megakernel"
-    render = env_ref.render_megakernel if mega else env_ref.render_streaming
+    render = loop_ref.render_megakernel if mega else loop_ref.render_streaming
     ref = render(orc, flat, scene.camera, W, H, 0, ITERS, 8, env=ENV, lens=lens, roulette=roulette)
     what = (method, scene_name, roulette, lens)
     schedules = ({},) if mega else ({}, {"params": (("fused_shade", 0),)})
@@ -223,7 +224,7 @@ def test_emitters_roulette_and_lens(pkg, orc, method, scene_name, roulette, lens
 def test_direct_light_in_the_megakernel(pkg, orc, roulette, lens):
     """the environment counts at every miss whatever the light sample before it did; it is no lamp: the three loop counters stay"""
     scene, flat = _scene(pkg, "lit_open")
-    ref = env_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, 8, env=ENV, lens=lens, direct=True, roulette=roulette)
+    ref = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, 8, env=ENV, lens=lens, direct=True, roulette=roulette)
     assert ref["shadow_rays"] > 0
     base, got = _both(pkg, flat, scene.camera, method=pkg.GPUMethod.megakernel, direct=True, roulette=roulette, lens=lens)
     _colour_is(got, ref, ("direct", roulette, lens))
@@ -244,7 +245,7 @@ def test_two_interleaved_ranks_against_the_one_context_frame(pkg, orc):
     assert 50 < sky.sum() < W * H - 50
     for rank in (0, 1):
         pixels = lit_ref.interleaved_pixels(W, H, rank, 2, 8)
-        ref = env_ref.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, 8, env=ENV, pixels=pixels, slot_offset=rank * W * H, scene_handle=sh)
+        ref = loop_ref.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, 8, env=ENV, pixels=pixels, slot_offset=rank * W * H, scene_handle=sh)
         base, got = _both(pkg, flat, scene.camera, interleave=(rank, 2, 8))
         _colour_is(got, ref, ("interleaved", rank))
         _only_colour_differs(base, got, ("interleaved", rank))
@@ -258,7 +259,7 @@ def test_iteration_2_31_minus_5(pkg, orc, method):
     scene, flat = _scene(pkg, "open")
     mega = method == "megakernel"
     first = 2 ** 31 - 5
-    render = env_ref.render_megakernel if mega else env_ref.render_streaming
+    render = loop_ref.render_megakernel if mega else loop_ref.render_streaming
     ref = render(orc, flat, scene.camera, W, H, first, 2, 4, env=ENV)
     base, got = _both(pkg, flat, scene.camera, mb=4, iters=2, iter_begin=first, method=pkg.GPUMethod.megakernel if mega else None)
     _colour_is(got, ref, (method, first))
@@ -274,7 +275,7 @@ def test_a_map_of_zeros_on_the_open_room(pkg, orc, method):
     scene, flat = _scene(pkg, "lit_open")
     mega = method == "megakernel"
     zeros = np.zeros((4, 4, 3), dtype=np.float32)
-    render = env_ref.render_megakernel if mega else env_ref.render_streaming
+    render = loop_ref.render_megakernel if mega else loop_ref.render_streaming
     ref = render(orc, flat, scene.camera, W, H, 0, 1, 8, env=zeros)
     base, got = _both(pkg, flat, scene.camera, env=zeros, iters=1, method=pkg.GPUMethod.megakernel if mega else None)
     _colour_is(got, ref, method)
@@ -290,7 +291,7 @@ def test_another_map_between_frames(pkg, orc, method):
     """set, trace 2, set another (another size), trace 2: the restatement continued with prev="""
     scene, flat = _scene(pkg, "open")
     mega = method == "megakernel"
-    render = env_ref.render_megakernel if mega else env_ref.render_streaming
+    render = loop_ref.render_megakernel if mega else loop_ref.render_streaming
     other = _env(n=12, seed=9, top=1.0)
     ref = render(orc, flat, scene.camera, W, H, 0, 2, 4, env=ENV)
     ref = render(orc, flat, scene.camera, W, H, 2, 2, 4, env=other, prev=ref)
@@ -316,7 +317,7 @@ def test_removal_equals_a_context_that_never_had_one(pkg, orc):
     for p in PLANES:
         assert np.array_equal(_bits(never[p]), _bits(after[p])), p
     assert never["rays"] == after["rays"] and never["last_live"] == after["last_live"]
-    ref = lit_ref.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, 8)
+    ref = loop_ref.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, 8)
     _colour_is(after, ref, "removed")
 
 

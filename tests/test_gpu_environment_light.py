@@ -12,6 +12,7 @@ import pytest
 import direct_ref
 import env_light_ref
 import env_ref
+import loop_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -117,7 +118,7 @@ EVERYTHING = PLANES + ("rays",) + LAMP_COUNTERS + ENV_COUNTERS
 def _against_the_loop(pkg, orc, scene_name, w=W, h=H, mb=8, env=ENV, iters=ITERS, iter_begin=0, direct=False, roulette=0, lens=None):
     scene, flat = _scene(pkg, scene_name)
     entries, _ = _table(pkg, env)
-    ref = env_light_ref.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iters, mb, env=env, entries=entries, env_light=True,
+    ref = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iters, mb, env=env, entries=entries, env_light=True,
                                           direct=direct, roulette=roulette, lens=lens)
     with _tracer(pkg, flat, w, h, mb, direct=direct, roulette=roulette, lens=lens) as pt:
         got = _run(pt, scene.camera, env, iters, iter_begin)
@@ -269,7 +270,7 @@ def test_another_map_between_frames_and_its_removal(pkg, orc):
     ref = None
     for k, env in enumerate((ENV, other, None, ENV)):
         entries = _table(pkg, env)[0] if env is not None else None
-        ref = env_light_ref.render_megakernel(orc, flat, scene.camera, W, H, 2 * k, 2, 4, env=env, entries=entries, env_light=True, prev=ref)
+        ref = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 2 * k, 2, 4, env=env, entries=entries, env_light=True, prev=ref)
     with _tracer(pkg, flat, mb=4) as pt:
         pt.max_iterations = 8
         for env in (ENV, other, None, ENV):

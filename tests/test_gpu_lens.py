@@ -1,4 +1,4 @@
-"""The thin lens (ptc_set_lens) on the GPU against its CPU restatement (tests/lens_ref.py: lit_ref's loops with the lens's
+"""The thin lens (ptc_set_lens) on the GPU against its CPU restatement (tests/loop_ref.py's loops with tests/lens_ref.py's
 primary rays), bit for bit: colour, first-hit normal and depth, ptc_stats.rays_total and the per-bounce live counts.  The primary
 rays themselves through ptc_generate_rays; one streaming frame per ray-generation instance the host can pick; the megakernel (plain,
 "roulette", "direct_light": the three loop counters too); interleaved ranks; lens changes between calls; the refusals; denoise and
@@ -10,6 +10,7 @@ import pytest
 
 import lens_ref
 import lit_ref
+import loop_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -94,7 +95,7 @@ def _ref_streaming(orc, flat, cameras, lens, iters=ITERS, w=W, h=H, mb=MB, **kw)
     lenses = lens if isinstance(lens, list) else [lens] * iters
     prev, rays = None, 0
     for i in range(iters):
-        prev = lens_ref.render_streaming(orc, flat, cameras[i % len(cameras)], w, h, i, 1, mb, lens=lenses[i], prev=prev, **kw)
+        prev = loop_ref.render_streaming(orc, flat, cameras[i % len(cameras)], w, h, i, 1, mb, lens=lenses[i], prev=prev, **kw)
         rays += prev["rays"]
     return {**prev, "rays": rays}
 
@@ -237,14 +238,14 @@ def test_megakernel_against_the_restatement(pkg, orc, name, direct, roulette):
     """cornell_lit (emitters: the kEmit instances) and, plain, the room without lamps; with "direct_light" the three loop counters too"""
     for scene_name in ("lit",) + (("room",) if not direct else ()):
         scene, flat = _scene(pkg, scene_name)
-        ref = lens_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, lens=LENS, direct=direct, roulette=roulette)
+        ref = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, lens=LENS, direct=direct, roulette=roulette)
         got = _render(pkg, flat, [scene.camera], LENS, method=pkg.GPUMethod.megakernel, direct=direct, roulette=roulette)
         _same(got, ref, (name, scene_name), live=False, counters=COUNTERS)
         if roulette:
             assert ref["played"].sum() > 0 and ref["ended"].sum() > 0
         if direct:
             assert ref["shadow_rays"] > 0
-        pin = lit_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, roulette=roulette)
+        pin = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, roulette=roulette)
         assert not np.array_equal(ref["depth"], pin["depth"])
 
 
@@ -276,7 +277,7 @@ def test_lens_changes_between_calls(pkg, orc, method):
     scene, flat = _scene(pkg, "room")
     lenses = [(0.0, 1.0), LENS, (0.05, 6.0), (0.0, 3.0)]
     mega = method == "megakernel"
-    render = lens_ref.render_megakernel if mega else lens_ref.render_streaming
+    render = loop_ref.render_megakernel if mega else loop_ref.render_streaming
     with _tracer(pkg, flat, method=pkg.GPUMethod.megakernel if mega else None) as pt:
         pt.max_iterations = len(lenses)
         prev, rays = None, 0

@@ -10,6 +10,7 @@ import pytest
 import direct_ref as D
 import light_census as LC
 import light_f64 as L64
+import loop_ref
 import seed_cases as sc
 import smooth_ref
 
@@ -205,7 +206,7 @@ def test_megakernel_units(pkg, orc, unit):
     if env is not None:
         import env_light_ref
         entries = env_light_ref.table_of(pkg, env)[0]
-    ref = smooth_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, iters, mb, normals=normals if opt.get("smooth") else None,
+    ref = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, iters, mb, normals=normals if opt.get("smooth") else None,
                                        smooth=opt.get("smooth", False), env=env, entries=entries, env_light=opt.get("env_light", False), direct=True,
                                        mis=opt.get("mis", False))
     with pkg.PathTracer(device=0, max_bounces=mb) as pt:

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import lit_ref as lr
+import loop_ref
 import material_cases as mc
 import material_f64 as f64
 
@@ -87,9 +88,9 @@ def test_walls_through_every_way_to_the_material_code(pkg, orc, name, mb):
     lit = name == "wall_lit"
     with np.errstate(all="ignore"):
         if lit:   # the oracle has no emitters: tests/lit_ref.py is the checker (pinned to the oracle on the other walls)
-            ref = lr.render_streaming(orc, flat, scene.camera, w, h, 0, ITERS, mb, scene_handle=sh)
-            mk = lr.render_megakernel(orc, flat, scene.camera, w, h, 0, ITERS, mb, scene_handle=sh)
-            rank = lr.render_streaming(orc, flat, scene.camera, w, h, 0, ITERS, mb, scene_handle=sh,
+            ref = loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, ITERS, mb, scene_handle=sh)
+            mk = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, ITERS, mb, scene_handle=sh)
+            rank = loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, ITERS, mb, scene_handle=sh,
                                        pixels=lr.interleaved_pixels(w, h, 1, 2, 8), slot_offset=w * h)
         else:
             ref = orc.render_streaming(flat, scene.camera, w, h, 0, ITERS, mb, scene_handle=sh)

@@ -12,6 +12,7 @@ import pytest
 import direct_loop_scenes
 import direct_ref
 import env_light_ref
+import loop_ref
 import mis_ref
 
 pytestmark = pytest.mark.gpu
@@ -127,7 +128,7 @@ def _against_the_loop(pkg, orc, scene_name, w=W, h=H, mb=8, env=None, iters=ITER
                       lens=None):
     scene, flat = _scene(pkg, scene_name)
     entries = _table(pkg, env) if env is not None else None
-    ref = mis_ref.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iters, mb, env=env, entries=entries, env_light=env_light,
+    ref = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iters, mb, env=env, entries=entries, env_light=env_light,
                                     direct=direct, mis=True, roulette=roulette, lens=lens)
     with _tracer(pkg, flat, w, h, mb, env_light=env_light, direct=direct, roulette=roulette, lens=lens) as pt:
         got = _run(pt, scene.camera, env, iters, iter_begin)
@@ -282,7 +283,7 @@ def test_another_map_between_frames_and_its_removal(pkg, orc):
     ref = None
     for k, env in enumerate((ENV, other, None, ENV)):
         entries = _table(pkg, env) if env is not None else None
-        ref = mis_ref.render_megakernel(orc, flat, scene.camera, W, H, 2 * k, 2, 4, env=env, entries=entries, env_light=True, mis=True, prev=ref)
+        ref = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 2 * k, 2, 4, env=env, entries=entries, env_light=True, mis=True, prev=ref)
     with _tracer(pkg, flat, mb=4, env_light=True) as pt:
         pt.max_iterations = 8
         for env in (ENV, other, None, ENV):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import env_light_ref
+import loop_ref
 import normal_map_ref
 import smooth_ref
 import texture_ref
@@ -126,11 +127,11 @@ def _against_the_loop(pkg, orc, scene_name, w=W, h=H, mb=8, env=None, iters=ITER
     s = _scene(pkg, scene_name)
     st = s["st"] if st is None else st
     entries = _entries(pkg) if env is not None else None
-    ref = normal_map_ref.render_megakernel(pkg, orc, s["flat"], s["scene"].camera, w, h, iter_begin, iters, mb, textures=s["textures"],
+    ref = loop_ref.render_megakernel(orc, s["flat"], s["scene"].camera, w, h, iter_begin, iters, mb, textures=s["textures"],
                                            binding=s["binding"], texcoords=st, textured=textured, nbinding=s["nbinding"], normal_maps=True,
                                            normals=s["nrm"] if smooth else None, smooth=smooth, env=env, entries=entries,
                                            env_light=kw.get("env_light", False), direct=kw.get("direct", False), mis=kw.get("mis", False),
-                                           roulette=kw.get("roulette", 0), lens=kw.get("lens"))
+                                           roulette=kw.get("roulette", 0), lens=kw.get("lens"), pkg=pkg)
     with _tracer(pkg, s["flat"], w, h, mb, textured=textured, table=(s["textures"], s["binding"]), maps=s["nbinding"], st=st, smooth=smooth,
                  normals=s["nrm"] if smooth else None, **kw) as pt:
         got = _run(pt, s["scene"].camera, env, iters, iter_begin)
@@ -350,8 +351,8 @@ def test_normal_maps_set_changed_and_removed(pkg, orc):
     steps = [s["nbinding"], other, None, s["nbinding"]]
     ref = None
     for k, maps in enumerate(steps):
-        ref = normal_map_ref.render_megakernel(pkg, orc, flat, cam, W, H, 2 * k, 2, 4, textures=s["textures"], binding=s["binding"], texcoords=s["st"],
-                                               textured=True, nbinding=maps, normal_maps=True, prev=ref)
+        ref = loop_ref.render_megakernel(orc, flat, cam, W, H, 2 * k, 2, 4, textures=s["textures"], binding=s["binding"], texcoords=s["st"],
+                                               textured=True, nbinding=maps, normal_maps=True, prev=ref, pkg=pkg)
     with _tracer(pkg, flat, mb=4, textured=True, table=(s["textures"], s["binding"]), st=s["st"]) as pt:
         pt.max_iterations = 8
         for maps in steps:
@@ -457,9 +458,9 @@ def _asset_reference(pkg, orc):
         flat = scene.build_scene()
         w, h = scene.resolution
         textures = [pkg.Texture(pkg.png.read_png(s.file), s.encoding, s.filter, s.wrap) for s in flat.texture_sources]
-        _cache["asset"] = normal_map_ref.render_megakernel(pkg, orc, flat, scene.camera, w, h, 0, 1, 2, textures=textures, binding=flat.material_texture,
+        _cache["asset"] = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 1, 2, textures=textures, binding=flat.material_texture,
                                                            texcoords=flat.texcoords, textured=True, nbinding=flat.material_normal_map,
-                                                           normal_maps=True)
+                                                           normal_maps=True, pkg=pkg)
         assert _cache["asset"]["bent"] > 1000  # (what a run that ignored the option would not reproduce)
     return _cache["asset"]
 

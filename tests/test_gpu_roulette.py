@@ -1,4 +1,4 @@
-"""Russian roulette (ptc_set_param "roulette") on the GPU against its CPU restatement (tests/lit_ref.py with roulette >= 1), bit
+"""Russian roulette (ptc_set_param "roulette") on the GPU against its CPU restatement (tests/loop_ref.py with roulette >= 1), bit
 for bit: colour, first-hit normal and depth, ptc_stats.rays_total and the per-bounce live counts, under the streaming method (every
 schedule that ends a bounce differently, interleaved ranks, the stepwise calls, high sample indices) and under the megakernel (plain
 and with "direct_light" 1: the three loop counters too).  Then what the rule promises beside the bits: a parameter that lets no
@@ -10,6 +10,7 @@ import pytest
 
 import direct_loop_scenes as scenes
 import lit_ref as lr
+import loop_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +30,7 @@ def _lit(pkg):
 def _ref_streaming(orc, key, flat, camera, w, h, mb, iters, k, **kw):
     key = ("s", key, w, h, mb, iters, k, tuple(sorted((a, str(b)[:40]) for a, b in kw.items() if a != "pixels")))
     if key not in _cache:
-        _cache[key] = lr.render_streaming(orc, flat, camera, w, h, kw.pop("iter_begin", 0), iters, mb, roulette=k, **kw)
+        _cache[key] = loop_ref.render_streaming(orc, flat, camera, w, h, kw.pop("iter_begin", 0), iters, mb, roulette=k, **kw)
     return _cache[key]
 
 
@@ -188,7 +189,7 @@ def test_every_class_of_path(pkg, orc, name):
         assert ended > 0 and divided > 0 and skipped > 0, (name, k, ended, divided, skipped)
         _same(_render(pkg, scene, flat, w, h, MB, iters, k), ref, (name, k))
         _same(_render(pkg, scene, flat, w, h, MB, iters, k, params=(("fused_shade", 0),)), ref, (name, k, "three kernels"))
-    mk = lr.render_megakernel(orc, flat, scene.camera, w, h, 0, iters, MB, roulette=1)
+    mk = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, iters, MB, roulette=1)
     assert all(n > 0 for n in _classes(mk)), _classes(mk)
     _same(_render(pkg, scene, flat, w, h, MB, iters, 1, method=pkg.GPUMethod.megakernel), mk, (name, "megakernel"), live=False)
 
@@ -200,7 +201,7 @@ def test_a_parameter_that_lets_no_bounce_play_renders_as_0(pkg, orc, k):
     if "gpu0" not in _cache:
         _cache["gpu0"] = {m: _render(pkg, scene, flat, W, H, MB, ITERS, 0, method=m) for m in (pkg.GPUMethod.streaming, pkg.GPUMethod.megakernel)}
     zero = _cache["gpu0"]
-    _same(zero[pkg.GPUMethod.streaming], plain, "roulette 0 against lit_ref")
+    _same(zero[pkg.GPUMethod.streaming], plain, "roulette 0 against loop_ref")
     for m in zero:
         _same(_render(pkg, scene, flat, W, H, MB, ITERS, k, method=m), zero[m], (k, m), live=m == pkg.GPUMethod.streaming)
     direct0 = _render(pkg, scene, flat, W, H, MB, ITERS, 0, method=pkg.GPUMethod.megakernel, direct=True)
@@ -213,10 +214,10 @@ def test_high_sample_indices(pkg, orc):
     scene = pkg.scenes.cornell_lit(resolution=(32, 24), with_mesh=True)
     flat = scene.build_scene()
     begin = 2 ** 31 - 6
-    ref = lr.render_streaming(orc, flat, scene.camera, 32, 24, begin, 3, 6, roulette=1)
+    ref = loop_ref.render_streaming(orc, flat, scene.camera, 32, 24, begin, 3, 6, roulette=1)
     assert all(n > 0 for n in _classes(ref))
     _same(_render(pkg, scene, flat, 32, 24, 6, 3, 1, iter_begin=begin), ref, "2^31 - 6")
-    mk = lr.render_megakernel(orc, flat, scene.camera, 32, 24, begin, 3, 6, direct=True, roulette=1)
+    mk = loop_ref.render_megakernel(orc, flat, scene.camera, 32, 24, begin, 3, 6, direct=True, roulette=1)
     _same(_render(pkg, scene, flat, 32, 24, 6, 3, 1, iter_begin=begin, method=pkg.GPUMethod.megakernel, direct=True), mk, "2^31 - 6, direct",
           live=False, counters=COUNTERS)
 
@@ -230,7 +231,7 @@ def test_two_interleaved_ranks(pkg, orc):
     sh = orc.SceneHandle(flat)
     for rank in (0, 1):
         pixels = lr.interleaved_pixels(w, h, rank, 2, block)
-        ref = lr.render_streaming(orc, flat, scene.camera, w, h, 0, ITERS, mb, roulette=1, pixels=pixels, slot_offset=rank * w * h,
+        ref = loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, ITERS, mb, roulette=1, pixels=pixels, slot_offset=rank * w * h,
                                   scene_handle=sh)
         assert all(n > 0 for n in _classes(ref))
         _same(_render(pkg, scene, flat, w, h, mb, ITERS, 1, interleave=(rank, 2, block)), ref, ("interleaved", rank))
@@ -242,7 +243,7 @@ def test_megakernel_against_the_restatement(pkg, orc, mb, direct):
     """Plain and with "direct_light" 1.  At 2 bounces bounce 1 is the last one: nothing plays."""
     scene, flat = _lit(pkg)
     k = 1
-    ref = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, mb, direct=direct, roulette=k)
+    ref = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, mb, direct=direct, roulette=k)
     got = _render(pkg, scene, flat, W, H, mb, ITERS, k, method=pkg.GPUMethod.megakernel, direct=direct)
     _same(got, ref, ("megakernel", mb, direct), live=False, counters=COUNTERS)
     off = _render(pkg, scene, flat, W, H, mb, ITERS, 0, method=pkg.GPUMethod.megakernel, direct=direct)
@@ -266,14 +267,14 @@ def test_the_forms_of_the_end_of_a_bounce_agree(pkg, orc):
     w, h, mb, iters, k = 64, 48, 6, 2, 1
     scene = pkg.scenes.cornell_lit(resolution=(w, h), with_mesh=True)
     flat = scene.build_scene()
-    ref = lr.render_streaming(orc, flat, scene.camera, w, h, 0, iters, mb, roulette=k)
+    ref = loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, iters, mb, roulette=k)
     assert all(n > 0 for n in _classes(ref)), _classes(ref)
     forms = {name: _render(pkg, scene, flat, w, h, mb, iters, k, params=params)
              for name, params in (("fused", ()), ("three_kernels", (("fused_shade", 0),)), ("persist", (("persist", 1),)))}
     for name, got in forms.items():
         assert got["color"].tobytes() == forms["fused"]["color"].tobytes(), name
         _same(got, ref, name)
-    mk = lr.render_megakernel(orc, flat, scene.camera, w, h, 0, iters, mb, direct=True, roulette=k)
+    mk = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, iters, mb, direct=True, roulette=k)
     _same(_render(pkg, scene, flat, w, h, mb, iters, k, method=pkg.GPUMethod.megakernel, direct=True), mk, "megakernel, direct", live=False,
           counters=COUNTERS)
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import env_light_ref
+import loop_ref
 import smooth_ref
 
 pytestmark = pytest.mark.gpu
@@ -109,7 +110,7 @@ def _against_the_loop(pkg, orc, scene_name, w=W, h=H, mb=8, env=None, iters=ITER
     scene, flat, nrm = _scene(pkg, scene_name)
     nrm = nrm if normals is None else normals
     entries = _entries(pkg) if env is not None else None
-    ref = smooth_ref.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iters, mb, normals=nrm, smooth=True, env=env, entries=entries,
+    ref = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, iter_begin, iters, mb, normals=nrm, smooth=True, env=env, entries=entries,
                                        env_light=kw.get("env_light", False), direct=kw.get("direct", False), mis=kw.get("mis", False),
                                        roulette=kw.get("roulette", 0), lens=kw.get("lens"))
     with _tracer(pkg, flat, w, h, mb, normals=nrm, **kw) as pt:
@@ -266,7 +267,7 @@ def test_normals_set_changed_and_removed(pkg, orc):
     other = np.roll(nrm, 1, axis=1)
     ref = None
     for k, n in enumerate((nrm, other, None, nrm)):
-        ref = smooth_ref.render_megakernel(orc, flat, scene.camera, W, H, 2 * k, 2, 4, normals=n, smooth=True, prev=ref)
+        ref = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 2 * k, 2, 4, normals=n, smooth=True, prev=ref)
     with _tracer(pkg, flat, mb=4) as pt:
         pt.max_iterations = 8
         for n in (nrm, other, None, nrm):
@@ -360,7 +361,7 @@ def _asset_reference(pkg, orc):
         flat = scene.build_scene()
         w, h = scene.resolution
         nrm = smooth_ref.scene_vertex_normals(flat)
-        _cache["asset"] = smooth_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 1, 1, normals=nrm, smooth=True)
+        _cache["asset"] = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 1, 1, normals=nrm, smooth=True)
         assert _cache["asset"]["shading_normals"] > 1000  # (what a run that ignored the option would not reproduce)
     return _cache["asset"]
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import env_light_ref
+import loop_ref
 import smooth_ref
 import texture_ref
 
@@ -118,10 +119,10 @@ def _against_the_loop(pkg, orc, scene_name, w=W, h=H, mb=8, env=None, iters=ITER
     s = _scene(pkg, scene_name)
     st = s["st"] if st is None else st
     entries = _entries(pkg) if env is not None else None
-    ref = texture_ref.render_megakernel(pkg, orc, s["flat"], s["scene"].camera, w, h, iter_begin, iters, mb, textures=s["textures"],
+    ref = loop_ref.render_megakernel(orc, s["flat"], s["scene"].camera, w, h, iter_begin, iters, mb, textures=s["textures"],
                                         binding=s["binding"], texcoords=st, textured=True, normals=s["nrm"] if smooth else None, smooth=smooth,
                                         env=env, entries=entries, env_light=kw.get("env_light", False), direct=kw.get("direct", False),
-                                        mis=kw.get("mis", False), roulette=kw.get("roulette", 0), lens=kw.get("lens"))
+                                        mis=kw.get("mis", False), roulette=kw.get("roulette", 0), lens=kw.get("lens"), pkg=pkg)
     with _tracer(pkg, s["flat"], w, h, mb, table=(s["textures"], s["binding"]), st=st, smooth=smooth, normals=s["nrm"] if smooth else None, **kw) as pt:
         got = _run(pt, s["scene"].camera, env, iters, iter_begin)
     _same(got, ref, EVERYTHING, (scene_name, w, h, mb, kw, iter_begin))
@@ -380,8 +381,8 @@ def test_textures_set_changed_and_removed(pkg, orc):
     steps = [((s["textures"], s["binding"]), s["st"]), ((other, other_binding), s["st"]), (None, s["st"]), ((s["textures"], s["binding"]), other_st)]
     ref = None
     for k, (table, st) in enumerate(steps):
-        ref = texture_ref.render_megakernel(pkg, orc, flat, cam, W, H, 2 * k, 2, 4, textures=table[0] if table else None,
-                                            binding=table[1] if table else None, texcoords=st, textured=True, prev=ref)
+        ref = loop_ref.render_megakernel(orc, flat, cam, W, H, 2 * k, 2, 4, textures=table[0] if table else None,
+                                            binding=table[1] if table else None, texcoords=st, textured=True, prev=ref, pkg=pkg)
     with _tracer(pkg, flat, mb=4) as pt:
         pt.max_iterations = 8
         for table, st in steps:
@@ -502,8 +503,8 @@ def _asset_reference(pkg, orc):
         flat = scene.build_scene()
         w, h = scene.resolution
         textures = [pkg.Texture(pkg.png.read_png(s.file), s.encoding, s.filter, s.wrap) for s in flat.texture_sources]
-        _cache["asset"] = texture_ref.render_megakernel(pkg, orc, flat, scene.camera, w, h, 0, 1, 2, textures=textures, binding=flat.material_texture,
-                                                        texcoords=flat.texcoords, textured=True)
+        _cache["asset"] = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 1, 2, textures=textures, binding=flat.material_texture,
+                                                        texcoords=flat.texcoords, textured=True, pkg=pkg)
         assert _cache["asset"]["lookups"] > 1000  # (what a run that ignored the option would not reproduce)
     return _cache["asset"]
 

@@ -1,5 +1,5 @@
-"""tests/lit_ref.py -- the CPU restatement of the render loops with emissive materials -- pinned to the oracle where the oracle
-can speak (scenes without emitters: every bit of colour, normal, depth, live counts and ray totals, streaming, megakernel and
+"""tests/loop_ref.py -- the CPU restatement of the render loops, here with emissive materials (tests/lit_ref.py) --
+pinned to the oracle where the oracle can speak (scenes without emitters: every bit of colour, normal, depth, live counts and ray totals, streaming, megakernel and
 interleaved rows), the emissive rule's own properties where it cannot, and the "emissive" entry of the scene grammar in both
 readers (json_parser.py and hip_pt --dump-scene).  Emitters are an extension: the reference has none, so what is checked
 here is the rule of include/ptcore.h, not the reference."""
@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import lit_ref as lr
+import loop_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIP_PT = os.path.join(ROOT, "cuda-path-tracer_amd", "host", "hip_pt")
@@ -56,18 +57,18 @@ def test_restatement_equals_the_oracle_without_emitters(pkg, orc, name, mb):
     flat = scene.build_scene()
     sh = orc.SceneHandle(flat)
     # streaming: three iterations, and two more folded into the first two's frame (the running mean's later steps)
-    got = lr.render_streaming(orc, flat, scene.camera, w, h, 0, 3, mb, scene_handle=sh)
+    got = loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, 3, mb, scene_handle=sh)
     want = orc.render_streaming(flat, scene.camera, w, h, 0, 3, mb, scene_handle=sh)
     _same(got, want, (name, mb, "streaming"))
-    got2 = lr.render_streaming(orc, flat, scene.camera, w, h, 3, 2, mb, prev=got, scene_handle=sh)
+    got2 = loop_ref.render_streaming(orc, flat, scene.camera, w, h, 3, 2, mb, prev=got, scene_handle=sh)
     want2 = orc.render_streaming(flat, scene.camera, w, h, 3, 2, mb, prev=want, scene_handle=sh)
     _same(got2, want2, (name, mb, "streaming, iterations 3-4"))
-    got = lr.render_megakernel(orc, flat, scene.camera, w, h, 0, 3, mb, scene_handle=sh)
+    got = loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, 3, mb, scene_handle=sh)
     want = orc.render_megakernel(flat, scene.camera, w, h, 0, 3, mb, scene_handle=sh)
     _same(got, want, (name, mb, "megakernel"))
     for rank, world, block in ((0, 2, 8), (1, 2, 8), (2, 3, 4)):
         pixels = lr.interleaved_pixels(w, h, rank, world, block)
-        got = lr.render_streaming(orc, flat, scene.camera, w, h, 0, 3, mb, pixels=pixels, slot_offset=rank * w * h, scene_handle=sh)
+        got = loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, 3, mb, pixels=pixels, slot_offset=rank * w * h, scene_handle=sh)
         want = orc.render_interleaved(flat, scene.camera, w, h, rank, world, block, rank * w * h, 0, 3, mb, scene_handle=sh)
         _same(got, want, (name, mb, "interleaved", rank, world))
 
@@ -89,7 +90,7 @@ def test_an_emitter_that_fills_the_view_gives_its_emission(pkg, orc, mode):
     e = (0.25, 3.0, 7.5)
     scene = _one_ball(pkg, pkg.EmissiveMaterial(e), radius=50.0)  # the camera sits inside the lamp: every ray hits it
     flat = scene.build_scene()
-    render = lr.render_streaming if mode == "streaming" else lr.render_megakernel
+    render = loop_ref.render_streaming if mode == "streaming" else loop_ref.render_megakernel
     out = render(orc, flat, scene.camera, 24, 16, 0, 3, 6)
     assert np.array_equal(out["color"], np.broadcast_to(np.array(e, dtype=np.float32), (16, 24, 3)))
     assert out["rays"] == 3 * 24 * 16  # every path ends at its first hit
@@ -106,10 +107,10 @@ def test_an_unreachable_emitter_changes_nothing(pkg, orc):
     fb, fl = base.build_scene(), lit.build_scene()
     for mb in (2, 6):
         want = orc.render_streaming(fb, base.camera, 40, 30, 0, 3, mb)
-        got = lr.render_streaming(orc, fl, lit.camera, 40, 30, 0, 3, mb)
+        got = loop_ref.render_streaming(orc, fl, lit.camera, 40, 30, 0, 3, mb)
         _same(got, want, ("streaming", mb))
         want = orc.render_megakernel(fb, base.camera, 40, 30, 0, 3, mb)
-        got = lr.render_megakernel(orc, fl, lit.camera, 40, 30, 0, 3, mb)
+        got = loop_ref.render_megakernel(orc, fl, lit.camera, 40, 30, 0, 3, mb)
         _same(got, want, ("megakernel", mb))
 
 
@@ -119,8 +120,8 @@ def test_a_black_emitter_ends_the_path(pkg, orc):
     dark = _one_ball(pkg, pkg.EmissiveMaterial((0.0, 0.0, 0.0)), radius=0.8, at=(0.0, 0.0, -2.0), extra=extra)
     grey = _one_ball(pkg, pkg.DiffuseMateral((0.5, 0.5, 0.5)), radius=0.8, at=(0.0, 0.0, -2.0), extra=extra)
     fd, fg = dark.build_scene(), grey.build_scene()
-    a = lr.render_streaming(orc, fd, dark.camera, 32, 24, 0, 1, 6)
-    b = lr.render_streaming(orc, fg, grey.camera, 32, 24, 0, 1, 6)
+    a = loop_ref.render_streaming(orc, fd, dark.camera, 32, 24, 0, 1, 6)
+    b = loop_ref.render_streaming(orc, fg, grey.camera, 32, 24, 0, 1, 6)
     assert np.array_equal(a["depth"], b["depth"])
     on_ball = a["depth"] < 3.0  # the ball's front face lies at t 1.2 ... 2, the wall at 4 and beyond
     assert on_ball.sum() > 20
@@ -128,7 +129,7 @@ def test_a_black_emitter_ends_the_path(pkg, orc):
     assert b["color"][on_ball].any()
     assert a["live"][0, 1] == b["live"][0, 1] - int(on_ball.sum())
     assert a["rays"] < b["rays"]
-    m = lr.render_megakernel(orc, fd, dark.camera, 32, 24, 0, 1, 6)
+    m = loop_ref.render_megakernel(orc, fd, dark.camera, 32, 24, 0, 1, 6)
     assert not m["color"][on_ball].any()
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import lit_ref as lr
+import loop_ref
 import material_cases as mc
 import material_f64 as f64
 
@@ -43,10 +44,10 @@ def test_the_two_restatements_agree_on_the_walls(pkg, orc, name):
     with np.errstate(all="ignore"):   # the 1e12 albedos overflow to inf, and inf * 0 is NaN, in both restatements
         for mb in (2, 8):
             want = orc.render_streaming(flat, scene.camera, w, h, 0, mc.WALL_ITERS, mb, scene_handle=sh)
-            _same(lr.render_streaming(orc, flat, scene.camera, w, h, 0, mc.WALL_ITERS, mb, scene_handle=sh), want,
+            _same(loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, mc.WALL_ITERS, mb, scene_handle=sh), want,
                   (name, mb, "streaming"))
         want = orc.render_megakernel(flat, scene.camera, w, h, 0, mc.WALL_ITERS, 8, scene_handle=sh)
-        _same(lr.render_megakernel(orc, flat, scene.camera, w, h, 0, mc.WALL_ITERS, 8, scene_handle=sh), want,
+        _same(loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, mc.WALL_ITERS, 8, scene_handle=sh), want,
               (name, "megakernel"))
 
 
@@ -57,7 +58,7 @@ def test_the_two_restatements_agree_on_records_out_of_range(pkg, orc):
     w, h = scene.resolution
     with np.errstate(all="ignore"):
         want = orc.render_streaming(flat, scene.camera, w, h, 0, mc.WALL_ITERS, 8)
-        _same(lr.render_streaming(orc, flat, scene.camera, w, h, 0, mc.WALL_ITERS, 8), want, "streaming")
+        _same(loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, mc.WALL_ITERS, 8), want, "streaming")
     nan = np.isnan(want["color"]).any(axis=2)
     assert 100 < nan.sum() < 0.05 * w * h, int(nan.sum())
 
@@ -68,9 +69,9 @@ def test_the_two_restatements_agree_on_the_critical_frames(pkg, orc):
         for name, kind, index, scene, flat in _critical(pkg):
             sh = orc.SceneHandle(flat)
             want = orc.render_streaming(flat, scene.camera, w, h, 0, n, mb, scene_handle=sh)
-            _same(lr.render_streaming(orc, flat, scene.camera, w, h, 0, n, mb, scene_handle=sh), want, (name, "streaming"))
+            _same(loop_ref.render_streaming(orc, flat, scene.camera, w, h, 0, n, mb, scene_handle=sh), want, (name, "streaming"))
             want = orc.render_megakernel(flat, scene.camera, w, h, 0, n, mb, scene_handle=sh)
-            _same(lr.render_megakernel(orc, flat, scene.camera, w, h, 0, n, mb, scene_handle=sh), want, (name, "megakernel"))
+            _same(loop_ref.render_megakernel(orc, flat, scene.camera, w, h, 0, n, mb, scene_handle=sh), want, (name, "megakernel"))
 
 
 def test_branch_census_of_the_critical_frames(pkg, orc):

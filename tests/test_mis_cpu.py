@@ -13,6 +13,7 @@ import pytest
 import direct_loop_scenes
 import env_light_ref
 import env_ref
+import loop_ref
 import mis_ref
 
 SIZES = (2, 5, 64)
@@ -282,8 +283,8 @@ def test_the_loop_with_the_option_off_is_env_light_ref_s(pkg, orc):
     scene, flat, env, entries = _room(pkg)
     for kw in (dict(env=env, entries=entries, env_light=True, direct=True, roulette=1), dict(env=env, entries=entries, env_light=True),
                dict(direct=True), dict(env=env, entries=entries, direct=True, lens=(0.25, 3.5))):
-        want = env_light_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 2, 4, **kw)
-        got = mis_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 2, 4, mis=False, **kw)
+        want = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 2, 4, **kw)
+        got = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 2, 4, mis=False, **kw)
         for k in ("color", "normal", "depth"):
             assert np.array_equal(_bits(got[k]), _bits(want[k])), (k, sorted(kw))
         assert all(got[k] == want[k] for k in ("rays",) + SIX)
@@ -298,8 +299,8 @@ def test_the_parameter_with_neither_light_in_effect_changes_nothing(pkg, orc):
     cases = ((scene, flat, dict(env=env, entries=entries)), (scene, flat, dict(env=np.zeros((4, 4, 3), np.float32), entries=None, env_light=True)),
              (bare, bare.build_scene(), dict(direct=True)))
     for sc, fl, kw in cases:
-        off = mis_ref.render_megakernel(orc, fl, sc.camera, W, H, 0, 2, 4, mis=False, **kw)
-        on = mis_ref.render_megakernel(orc, fl, sc.camera, W, H, 0, 2, 4, mis=True, **kw)
+        off = loop_ref.render_megakernel(orc, fl, sc.camera, W, H, 0, 2, 4, mis=False, **kw)
+        on = loop_ref.render_megakernel(orc, fl, sc.camera, W, H, 0, 2, 4, mis=True, **kw)
         assert all(np.array_equal(_bits(on[k]), _bits(off[k])) for k in ("color", "normal", "depth"))
         assert all(on[k] == off[k] for k in ("rays", "mis_emitter_hits", "mis_misses") + SIX)
 
@@ -310,8 +311,8 @@ def test_the_loop_with_the_option_on_changes_colour_alone(pkg, orc, mb):
     last bounce and keeps weight 1: the same colour too"""
     scene, flat, env, entries = _room(pkg)
     kw = dict(env=env, entries=entries, env_light=True, direct=True)
-    off = mis_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 3, mb, mis=False, **kw)
-    on = mis_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 3, mb, mis=True, **kw)
+    off = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 3, mb, mis=False, **kw)
+    on = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 3, mb, mis=True, **kw)
     assert all(np.array_equal(_bits(on[k]), _bits(off[k])) for k in ("normal", "depth"))
     assert all(on[k] == off[k] for k in ("rays",) + SIX)
     assert np.isfinite(on["color"]).all() and (on["color"] >= 0.0).all()

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import env_light_ref
+import loop_ref
 import normal_map_ref
 import smooth_ref
 import texture_ref
@@ -318,10 +319,10 @@ def _lights(pkg, lights):
 def test_loop_off_is_the_loop_it_extends(pkg, orc):
     s = _sheet(pkg)
     kw = dict(textures=s["textures"], binding=s["binding"], texcoords=s["st"], textured=True, normals=s["nrm"], smooth=True, **_lights(pkg, "env"))
-    want = texture_ref.render_megakernel(pkg, orc, s["flat"], s["scene"].camera, W, H, 0, 1, 4, **kw)
+    want = loop_ref.render_megakernel(orc, s["flat"], s["scene"].camera, W, H, 0, 1, 4, pkg=pkg, **kw)
     unbound = np.full(len(s["bumpy"]), -1, np.int32)
     for nm in (dict(nbinding=s["bumpy"], normal_maps=False), dict(nbinding=None, normal_maps=True), dict(nbinding=unbound, normal_maps=True)):
-        got = normal_map_ref.render_megakernel(pkg, orc, s["flat"], s["scene"].camera, W, H, 0, 1, 4, **nm, **kw)
+        got = loop_ref.render_megakernel(orc, s["flat"], s["scene"].camera, W, H, 0, 1, 4, pkg=pkg, **nm, **kw)
         for k in want:
             assert np.array_equal(got[k], want[k]), k
         assert all(got[k] == 0 for k in normal_map_ref.COUNTERS)
@@ -330,12 +331,12 @@ def test_loop_off_is_the_loop_it_extends(pkg, orc):
 @pytest.mark.parametrize("smooth", [False, True])
 @pytest.mark.parametrize("lights", ["none", "env_mis"])
 def test_an_all_flat_map_gives_the_bits_of_the_loop_it_extends(pkg, orc, smooth, lights):
-    """every texel (128, 128, 255): the statement with the option on walks every line of texture_ref's loop to the same bits -- the
-    check of this file's own restating"""
+    """every texel (128, 128, 255): the loop with the option on walks to the bits of the loop without it -- a flat texel leaves the
+    normal, the culls and the absorption where they were"""
     s = _sheet(pkg)
     kw = dict(textures=s["textures"], binding=s["binding"], texcoords=s["st"], textured=True, normals=s["nrm"], smooth=smooth, **_lights(pkg, lights))
-    want = texture_ref.render_megakernel(pkg, orc, s["flat"], s["scene"].camera, W, H, 0, 1, 4, **kw)
-    got = normal_map_ref.render_megakernel(pkg, orc, s["flat"], s["scene"].camera, W, H, 0, 1, 4, nbinding=s["flat_binding"], normal_maps=True, **kw)
+    want = loop_ref.render_megakernel(orc, s["flat"], s["scene"].camera, W, H, 0, 1, 4, pkg=pkg, **kw)
+    got = loop_ref.render_megakernel(orc, s["flat"], s["scene"].camera, W, H, 0, 1, 4, nbinding=s["flat_binding"], normal_maps=True, pkg=pkg, **kw)
     for k in want:
         assert np.array_equal(got[k], want[k]), k
     assert got["bent"] == 0 and got["kept"] == 0 and got["lookups"] > 0
@@ -346,8 +347,8 @@ def test_a_bumpy_map_changes_the_colour_alone_and_both_counters_move(pkg, orc):
     bad = s["st"].copy()
     bad[::7, 0] = np.nan
     kw = dict(textures=s["textures"], binding=s["binding"], texcoords=bad, textured=False, **_lights(pkg, "env"))
-    off = texture_ref.render_megakernel(pkg, orc, s["flat"], s["scene"].camera, 65, 33, 0, 1, 8, **kw)
-    on = normal_map_ref.render_megakernel(pkg, orc, s["flat"], s["scene"].camera, 65, 33, 0, 1, 8, nbinding=s["bumpy"], normal_maps=True, **kw)
+    off = loop_ref.render_megakernel(orc, s["flat"], s["scene"].camera, 65, 33, 0, 1, 8, pkg=pkg, **kw)
+    on = loop_ref.render_megakernel(orc, s["flat"], s["scene"].camera, 65, 33, 0, 1, 8, nbinding=s["bumpy"], normal_maps=True, pkg=pkg, **kw)
     assert (on["color"] != off["color"]).any()
     assert np.array_equal(on["normal"], off["normal"]) and np.array_equal(on["depth"], off["depth"])
     assert on["bent"] > 0 and on["kept"] > 0 and on["lookups"] == 0, {k: on[k] for k in normal_map_ref.COUNTERS}

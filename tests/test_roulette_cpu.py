@@ -1,5 +1,5 @@
 """Russian roulette (ptc_set_param "roulette") without a GPU: the binding and hip_pt's argument handling, and the
-CPU restatement (lit_ref's loops with roulette >= 1) against the same loops without the option wherever no bounce plays, and the
+CPU restatement (loop_ref's loops with roulette >= 1) against the same loops without the option wherever no bounce plays, and the
 properties the rule promises where one does.  The bits of either are pinned by tests/test_loop_ref_golden_cpu.py."""
 import os
 import subprocess
@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import lit_ref as lr
+import loop_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -28,9 +28,9 @@ def _scene(pkg, orc):
 def _streaming(pkg, orc, k, record=None):
     scene, flat, sh = _scene(pkg, orc)
     if record is not None:
-        return lr.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, MB, roulette=k, scene_handle=sh, record=record)
+        return loop_ref.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, MB, roulette=k, scene_handle=sh, record=record)
     if ("s", k) not in _cache:
-        _cache[("s", k)] = lr.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, MB, roulette=k, scene_handle=sh)
+        _cache[("s", k)] = loop_ref.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, MB, roulette=k, scene_handle=sh)
     return _cache[("s", k)]
 
 
@@ -70,7 +70,7 @@ def test_binding_and_hip_pt_arguments(pkg):
 def test_no_bounce_plays_streaming(pkg, orc, k):
     scene, flat, sh = _scene(pkg, orc)
     if "plain_s" not in _cache:
-        _cache["plain_s"] = lr.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, MB, scene_handle=sh)
+        _cache["plain_s"] = loop_ref.render_streaming(orc, flat, scene.camera, W, H, 0, ITERS, MB, scene_handle=sh)
     plain, got = _cache["plain_s"], _streaming(pkg, orc, k)
     for p in PLANES:
         assert np.array_equal(got[p].view(np.uint32), plain[p].view(np.uint32)), p
@@ -84,9 +84,9 @@ def test_no_bounce_plays_megakernel(pkg, orc, k, direct):
     scene, flat, sh = _scene(pkg, orc)
     key = ("plain_m", direct)
     if key not in _cache:
-        _cache[key] = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, scene_handle=sh)
+        _cache[key] = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, scene_handle=sh)
     plain = _cache[key]
-    got = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, roulette=k, scene_handle=sh)
+    got = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, roulette=k, scene_handle=sh)
     for p in PLANES:
         assert np.array_equal(got[p].view(np.uint32), plain[p].view(np.uint32)), p
     assert got["rays"] == plain["rays"] and got["played"].sum() == 0
@@ -120,9 +120,9 @@ def test_k_1_streaming(pkg, orc):
 def test_k_1_megakernel(pkg, orc):
     scene, flat, sh = _scene(pkg, orc)
     for direct in (False, True):
-        plain = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, scene_handle=sh)
+        plain = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, scene_handle=sh)
         record = []
-        got = lr.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, roulette=1, scene_handle=sh, record=record)
+        got = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, ITERS, MB, direct=direct, roulette=1, scene_handle=sh, record=record)
         record = [r for r in record if r["kind"] == "roulette"]
         assert np.array_equal(got["normal"], plain["normal"]) and np.array_equal(got["depth"], plain["depth"])
         assert got["rays"] < plain["rays"] and not np.array_equal(got["color"], plain["color"])
@@ -144,13 +144,13 @@ def test_a_black_wall_ends_every_path_that_leaves_it(pkg, orc):
     s.camera = pkg.scenes._camera_from_look_at((0.0, 0.6, 3.0), (0.0, -0.3, -1.0), vfov_deg=50.0)
     flat = s.build_scene()
     record = []
-    got = lr.render_streaming(orc, flat, s.camera, W, H, 0, ITERS, MB, roulette=1, record=record)
+    got = loop_ref.render_streaming(orc, flat, s.camera, W, H, 0, ITERS, MB, roulette=1, record=record)
     zero = sum(int((r["q"] == 0).sum()) for r in record)
     assert zero > 0
     for r in record:
         assert r["ended"][r["q"] == 0].all()
     # ... so no path with throughput 0 is ever shaded twice: every path alive behind a play has a positive throughput
-    plain = lr.render_streaming(orc, flat, s.camera, W, H, 0, ITERS, MB)
+    plain = loop_ref.render_streaming(orc, flat, s.camera, W, H, 0, ITERS, MB)
     assert got["rays"] < plain["rays"]
     # the image is the plain one wherever no divided path arrives: a dead path deposits 0 either way (0 * sky == 0)
     assert np.isfinite(got["color"]).all()

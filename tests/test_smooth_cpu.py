@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import env_light_ref
+import loop_ref
 import smooth_ref
 
 ENV = smooth_ref.ENV
@@ -194,9 +195,9 @@ def _scene(pkg, name):
 def test_loop_off_is_the_loop_it_extends(pkg, orc):
     scene, flat, nrm = _scene(pkg, "sheet")
     entries = env_light_ref.table_of(pkg, ENV)[0]
-    want = env_light_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 2, 4, env=ENV, entries=entries, env_light=True)
+    want = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 2, 4, env=ENV, entries=entries, env_light=True)
     for kw in ({"normals": nrm, "smooth": False}, {"normals": None, "smooth": True}):
-        got = smooth_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 2, 4, env=ENV, entries=entries, env_light=True, **kw)
+        got = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 2, 4, env=ENV, entries=entries, env_light=True, **kw)
         for k in want:
             assert np.array_equal(got[k], want[k]), k
         assert all(got[k] == 0 for k in smooth_ref.COUNTERS)
@@ -215,8 +216,8 @@ def test_face_normals_make_the_same_draws(pkg, orc):
     s.add_object(s.add_mesh("m.obj", pkg.Mesh(p, i)), glm.translate((0.0, -0.4, 0.0)), "ball")
     s.camera = pkg.scenes._camera_from_look_at((0.0, 0.5, 3.0), (0.0, -0.3, 0.0), vfov_deg=40.0)
     flat = s.build_scene(distinct_meshes=True)
-    off = smooth_ref.render_megakernel(orc, flat, s.camera, W, H, 0, 1, 3)
-    on = smooth_ref.render_megakernel(orc, flat, s.camera, W, H, 0, 1, 3, normals=n, smooth=True)
+    off = loop_ref.render_megakernel(orc, flat, s.camera, W, H, 0, 1, 3)
+    on = loop_ref.render_megakernel(orc, flat, s.camera, W, H, 0, 1, 3, normals=n, smooth=True)
     assert on["rays"] == off["rays"] and np.array_equal(on["depth"], off["depth"])
     assert on["shading_normals"] > 50 and on["fallbacks"] == 0
     assert np.abs(on["normal"] - off["normal"]).max() < 1e-6
@@ -225,8 +226,8 @@ def test_face_normals_make_the_same_draws(pkg, orc):
 
 def test_loop_on_changes_normal_and_colour(pkg, orc):
     scene, flat, nrm = _scene(pkg, "sheet")
-    off = smooth_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4)
-    on = smooth_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4, normals=nrm, smooth=True)
+    off = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4)
+    on = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4, normals=nrm, smooth=True)
     assert (on["normal"] != off["normal"]).any() and (on["color"] != off["color"]).any()
     assert np.array_equal(on["depth"], off["depth"])  # the geometry is what it was
 
@@ -235,10 +236,10 @@ def test_the_counters_move_on_the_gpu_tests_scenes(pkg, orc):
     """what test_gpu_smooth.py compares on these scenes is not a row of zeros"""
     entries = env_light_ref.table_of(pkg, ENV)[0]
     scene, flat, nrm = _scene(pkg, "sheet")
-    out = smooth_ref.render_megakernel(orc, flat, scene.camera, 65, 33, 0, 2, 8, normals=nrm, smooth=True, env=ENV, entries=entries, env_light=True)
+    out = loop_ref.render_megakernel(orc, flat, scene.camera, 65, 33, 0, 2, 8, normals=nrm, smooth=True, env=ENV, entries=entries, env_light=True)
     assert all(out[k] > 0 for k in smooth_ref.COUNTERS), {k: out[k] for k in smooth_ref.COUNTERS}
     scene, flat, nrm = _scene(pkg, "room")
-    out = smooth_ref.render_megakernel(orc, flat, scene.camera, 65, 33, 0, 2, 8, normals=nrm, smooth=True, direct=True)
+    out = loop_ref.render_megakernel(orc, flat, scene.camera, 65, 33, 0, 2, 8, normals=nrm, smooth=True, direct=True)
     assert all(out[k] > 0 for k in smooth_ref.COUNTERS), {k: out[k] for k in smooth_ref.COUNTERS}
 
 
@@ -252,7 +253,7 @@ def convergence(pkg, orc, w=48, h=48):
     """-> per n_lat in (8, 16, 32) the mean angle (degrees) between the normal plane of the UV sphere mesh and that of the analytic sphere
     object, over pixels that hit in both frames: (flat, smooth)"""
     ball = smooth_ref.sphere_scene(pkg)
-    ref = smooth_ref.render_megakernel(orc, ball.build_scene(), ball.camera, w, h, 0, 1, 1)
+    ref = loop_ref.render_megakernel(orc, ball.build_scene(), ball.camera, w, h, 0, 1, 1)
     out = []
     for n_lat in (8, 16, 32):
         s = smooth_ref.sphere_scene(pkg, n_lat, 2 * n_lat)
@@ -260,7 +261,7 @@ def convergence(pkg, orc, w=48, h=48):
         radial = smooth_ref.uv_sphere(n_lat, 2 * n_lat)[2]
         row = []
         for kw in ({}, {"normals": radial, "smooth": True}):
-            got = smooth_ref.render_megakernel(orc, flat, s.camera, w, h, 0, 1, 1, **kw)
+            got = loop_ref.render_megakernel(orc, flat, s.camera, w, h, 0, 1, 1, **kw)
             both = (got["depth"] < 1e5) & (ref["depth"] < 1e5)
             row.append(_mean_angle(got["normal"], ref["normal"], both))
         out.append(tuple(row))

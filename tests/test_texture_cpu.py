@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import env_light_ref
+import loop_ref
 import smooth_ref
 import texture_ref
 
@@ -136,10 +137,10 @@ def test_loop_off_is_the_loop_it_extends(pkg, orc):
     scene, flat, textures, binding, st, nrm = _sheet(pkg)
     entries = env_light_ref.table_of(pkg, ENV)[0]
     kw = dict(env=ENV, entries=entries, env_light=True, normals=nrm, smooth=True)
-    want = smooth_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4, **kw)
+    want = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4, **kw)
     for tx in (dict(textures=textures, binding=binding, texcoords=st, textured=False), dict(textures=None, texcoords=st, textured=True),
                dict(textures=textures, binding=binding, texcoords=None, textured=True)):
-        got = texture_ref.render_megakernel(pkg, orc, flat, scene.camera, W, H, 0, 1, 4, **tx, **kw)
+        got = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4, pkg=pkg, **tx, **kw)
         for k in want:
             assert np.array_equal(got[k], want[k]), k
         assert all(got[k] == 0 for k in texture_ref.COUNTERS)
@@ -148,25 +149,25 @@ def test_loop_off_is_the_loop_it_extends(pkg, orc):
 @pytest.mark.parametrize("smooth", [False, True])
 @pytest.mark.parametrize("lights", ["none", "env", "env_mis"])
 def test_white_textures_give_the_bits_of_the_loop_it_extends(pkg, orc, smooth, lights):
-    """every texel 255 under the linear table is the factor 1.0f: the statement with the option on, and with smooth shading as its
-    switch, walks every line of smooth_ref's loop to the same bits -- the check of this file's own restating"""
+    """every texel 255 under the linear table is the factor 1.0f: the loop with the option on, under smooth shading or not, walks to the
+    bits of the loop without it -- the winners, the lookup and the material copies change nothing but the albedo"""
     scene, flat, _, binding, st, nrm = _sheet(pkg)
     white = [pkg.Texture(np.full((2, 3, 4), 255, np.uint8), "linear", "nearest", "repeat")] * 3
     entries = env_light_ref.table_of(pkg, ENV)[0]
     kw = dict(normals=nrm, smooth=smooth)
     if lights != "none":
         kw.update(env=ENV, entries=entries, env_light=True, mis=lights == "env_mis")
-    want = smooth_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4, **kw)
-    got = texture_ref.render_megakernel(pkg, orc, flat, scene.camera, W, H, 0, 1, 4, textures=white, binding=binding, texcoords=st, textured=True, **kw)
-    for k in want:
+    want = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4, **kw)
+    got = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4, textures=white, binding=binding, texcoords=st, textured=True, pkg=pkg, **kw)
+    for k in set(want) - set(texture_ref.COUNTERS):  # everything but the texture's own two counters
         assert np.array_equal(got[k], want[k]), k
     assert got["lookups"] > 0
 
 
 def test_loop_on_changes_the_colour_alone(pkg, orc):
     scene, flat, textures, binding, st, _ = _sheet(pkg)
-    off = smooth_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4)
-    on = texture_ref.render_megakernel(pkg, orc, flat, scene.camera, W, H, 0, 1, 4, textures=textures, binding=binding, texcoords=st, textured=True)
+    off = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4)
+    on = loop_ref.render_megakernel(orc, flat, scene.camera, W, H, 0, 1, 4, textures=textures, binding=binding, texcoords=st, textured=True, pkg=pkg)
     assert (on["color"] != off["color"]).any()
     assert np.array_equal(on["normal"], off["normal"]) and np.array_equal(on["depth"], off["depth"]) and on["rays"] == off["rays"]
 
@@ -177,7 +178,7 @@ def test_the_counters_move_on_the_gpu_tests_scenes(pkg, orc):
     bad = st.copy()
     bad[::7, 0] = np.nan
     bad[3::11, 1] = np.inf
-    out = texture_ref.render_megakernel(pkg, orc, flat, scene.camera, 65, 33, 0, 1, 8, textures=textures, binding=binding, texcoords=bad, textured=True)
+    out = loop_ref.render_megakernel(orc, flat, scene.camera, 65, 33, 0, 1, 8, textures=textures, binding=binding, texcoords=bad, textured=True, pkg=pkg)
     assert all(out[k] > 0 for k in texture_ref.COUNTERS), {k: out[k] for k in texture_ref.COUNTERS}
 
 

@@ -108,13 +108,13 @@ def self_shadow(pkg, orc):
     import numpy as np
 
     import direct_loop_scenes as scenes
-    import lit_ref
+    import loop_ref
     for room in (scenes.small_lamp_room, scenes.small_lamp_sphere_room):
         scene = room(pkg)
         flat = scene.build_scene()
         sh = orc.SceneHandle(flat)
         record = []
-        lit_ref.render_megakernel(orc, flat, scene.camera, 32, 24, 0, 4, scenes.STAT_BOUNCES, direct=True, scene_handle=sh, record=record)
+        loop_ref.render_megakernel(orc, flat, scene.camera, 32, 24, 0, 4, scenes.STAT_BOUNCES, direct=True, scene_handle=sh, record=record)
         rays = near = 0
         light = lost = 0.0
         for e in (e for e in record if e["kind"] == "light"):

@@ -129,14 +129,14 @@ def variance(pkg, name, scene, size, env, direct, env_light, ratio, blocks=16, p
 
 def cpu(pkg, orc):
     """the restatement's block means on low_panel_scene, 24 x 16, 16 blocks of 8 iterations per mode: the ratio of spreads"""
-    import mis_ref
+    import loop_ref
     scene = low_panel_scene(pkg)
     flat = scene.build_scene(distinct_meshes=True)
     sh = orc.SceneHandle(flat)
     means = np.zeros((2, 16, 3))
     for mode in (0, 1):
         for b in range(16):
-            r = mis_ref.render_megakernel(orc, flat, scene.camera, 24, 16, 8 * b, 8, 8, direct=True, mis=bool(mode), scene_handle=sh)
+            r = loop_ref.render_megakernel(orc, flat, scene.camera, 24, 16, 8 * b, 8, 8, direct=True, mis=bool(mode), scene_handle=sh)
             means[mode, b] = r["color"].astype(np.float64).reshape(-1, 3).mean(axis=0) * (b + 1)
     sd = means.std(axis=1, ddof=1)
     print("low_panel_scene on the restatement, 24 x 16, 8 bounces, 16 blocks of 8 iterations: image mean", means.mean(axis=1)[0], "/",
