@@ -137,6 +137,11 @@ class ptc_texture_loop_stats(C.Structure):
     _fields_ = [("lookups", C.c_uint64), ("fallbacks", C.c_uint64)]
 
 
+class ptc_denoise_albedo_stats(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("surface_hits", C.c_uint64), ("texel_lookups", C.c_uint64), ("floored", C.c_uint64),
+                ("stage_ms", C.c_double)]
+
+
 class ptc_normal_map_loop_stats(C.Structure):
     _fields_ = [("bent", C.c_uint64), ("kept", C.c_uint64)]
 
@@ -202,6 +207,9 @@ SIGNATURES = {
     "ptc_copy_live_count": (C.c_int, [_P, C.c_int, _P]),
     "ptc_read_live_count": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint32)]),
     "ptc_denoise": (C.c_int, [_P]),
+    "ptc_denoise_albedo": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ptc_get_denoise_albedo_stats": (C.c_int, [_P, C.POINTER(ptc_denoise_albedo_stats)]),
+    "ptc_check_demodulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "ptc_present_rgba8": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "ptc_download": (C.c_int, [_P, C.c_int, _P, C.c_int]),
     "ptc_band_export": (C.c_int, [_P, C.POINTER(ptc_band_handle)]),

@@ -640,6 +640,14 @@ void launch_hit_surface(hipStream_t s, const DScene& scene, DTex tx, const float
 // (nmap::kMiss .. kKept); flags |= kFlagStackOverflow
 void launch_hit_shading_normal(hipStream_t s, const DScene& scene, DSmooth sm, DTex tx, DNmap nm, const float4* rays, uint32_t n,
                                float* normal_out, uint8_t* outcome_out, uint32_t* flags);
+// "denoise_albedo" (pt_denoise_albedo.hip).  launch_denoise_albedo: one wavefront per 8 x 8 pixel tile of cam's frame;
+// per pixel the first-hit albedo under tx (k_hit_surface's at a diffuse or metal hit, else ones) and the colour demodulated by it, a
+// float4 each; rays (may be null) 2 float4 a pixel: the pixel-centre ray it walked; stats: kLightStatLines lines of kLoopStatWords
+// words, 0 .. 3 += pixels, surface hits, texel lookups, floored channels; flags |= kFlagStackOverflow.  launch_remodulate: front =
+// front x the effective albedo of that plane, in place
+void launch_denoise_albedo(hipStream_t s, const DScene& scene, DTex tx, const DCamera& cam, const float4* color, float4* albedo,
+                           float4* irradiance, float4* rays, unsigned long long* stats, uint32_t* flags);
+void launch_remodulate(hipStream_t s, uint32_t pix_count, const float4* albedo, float4* front);
 // ptc_environment_light_pdf's kernel (pt_env.hip): one thread per unit direction, env_light::density
 void launch_env_light_pdf(hipStream_t s, DEnvLight el, uint32_t n, const float* dirs, uint32_t count, float* pdf);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,

@@ -42,4 +42,10 @@ inline ptc_frame_plan frame_plan(uint32_t width, uint32_t height, int frames_in_
   return plan;
 }
 
+// "denoise_albedo" (DESIGN section 5r): the planes the stage adds to a frame -- the first-hit albedo and the irradiance, a float4 per
+// pixel each -- and the float4 elements of one.  Not part of ptc_frame_plan: they are allocated by the first call that runs the
+// stage at a frame size (ptcore.cpp, albedo_planes), not by ptc_resize, and released with the frame.
+constexpr int kDenoiseAlbedoPlanes = 2;
+inline uint64_t denoise_albedo_floats4(uint32_t width, uint32_t height) { return (uint64_t)width * height; }
+
 }  // namespace pt

@@ -223,6 +223,7 @@ const ParamRow kParams[] = {
     {"normal_maps", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->normal_maps = v != 0; }},
     {"roulette", 0, 64, " must be in [0,64]", kAnyTime, [](ptc_ctx* c, int v) { c->roulette = v; }},
     {"denoise_variant", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_variant = v; }},
+    {"denoise_albedo", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_albedo = v != 0; }},
     {"frames_in_flight", 1, 256, " must be in [1,256]", kBeforeResize, [](ptc_ctx* c, int v) { c->frames_in_flight = v; }},
 };
 #undef PT_STR
@@ -440,6 +441,9 @@ int ptc_create(const ptc_config* config, ptc_ctx** out)
   if (hipMemset(ctx->slot_offset_dev, 0, 256) != hipSuccess) return bail(fail(ctx, PTC_ERR_HIP, "hipMemset failed"));
   if (hipMalloc(&p, kLoopStatBytes) != hipSuccess) return bail(fail(ctx, PTC_ERR_OOM, "hipMalloc(direct-light loop counters) failed"));
   ctx->loop_stats = static_cast<unsigned long long*>(p);
+  if (hipMalloc(&p, kLoopStatBytes) != hipSuccess) return bail(fail(ctx, PTC_ERR_OOM, "hipMalloc(denoise albedo counters) failed"));
+  ctx->albedo_stats = static_cast<unsigned long long*>(p);
+  if (hipMemset(ctx->albedo_stats, 0, kLoopStatBytes) != hipSuccess) return bail(fail(ctx, PTC_ERR_HIP, "hipMemset failed"));
   *out = ctx;
   return PTC_OK;
 }
@@ -468,6 +472,7 @@ void ptc_destroy(ptc_ctx* ctx)
     if (e) (void)hipEventDestroy(e);
   if (ctx->misc_counters) (void)hipFree(ctx->misc_counters);
   if (ctx->loop_stats) (void)hipFree(ctx->loop_stats);
+  if (ctx->albedo_stats) (void)hipFree(ctx->albedo_stats);
   if (ctx->env.texels) (void)hipFree(const_cast<float4*>(ctx->env.texels));
   if (ctx->env_table) (void)hipFree(const_cast<uint4*>(ctx->env_table));
   if (ctx->meter_dev) (void)hipFree(ctx->meter_dev);  // (exposure_dev is the same allocation)
@@ -515,6 +520,8 @@ int ptc_restart(ptc_ctx* ctx)
     if (int rc = flush_pending(ctx)) return rc;
   ctx->iteration = 0;
   ctx->loop_stats_clear = true;  // ptc_get_direct_loop_stats counts from here
+  ctx->albedo_stage_ms = 0.0;    // ptc_get_denoise_albedo_stats' stage_ms too: launches timed before this carry the old epoch
+  ctx->albedo_epoch += 1u;
   return PTC_OK;
 }
 
@@ -741,12 +748,52 @@ int ptc_set_denoiser_params(ptc_ctx* ctx, const ptc_denoiser_params* p)
   return PTC_OK;
 }
 
-int ptc_denoise(ptc_ctx* ctx)
+// what ptc_denoise and ptc_denoise_albedo refuse, in the one order they share
+static int denoise_ready(ptc_ctx* ctx)
 {
   if (int rc = frame_ready(ctx)) return rc;
   if (!ctx->have_cam) return fail(ctx, PTC_ERR_INVALID, "denoise needs a traced frame (it reuses the last camera)");
   if (ctx->pix_count != ctx->width * ctx->height) return fail(ctx, PTC_ERR_INVALID, "denoise needs the full frame in one context");
+  return PTC_OK;
+}
+
+// "denoise_albedo" (DESIGN section 5r): the two planes of this frame size, allocated by the first call that gets here and released
+// with the frame (release_frame: they are of frame_allocs)
+static int albedo_planes(ptc_ctx* ctx)
+{
+  static_assert(kDenoiseAlbedoPlanes == 2, "the albedo and the irradiance plane");
+  const size_t elems = (size_t)denoise_albedo_floats4(ctx->width, ctx->height);
+  if (!ctx->den_albedo)
+    if (int rc = dev_alloc(ctx, ctx->frame_allocs, &ctx->den_albedo, elems)) return rc;
+  if (!ctx->den_irradiance)
+    if (int rc = dev_alloc(ctx, ctx->frame_allocs, &ctx->den_irradiance, elems)) return rc;
+  return PTC_OK;
+}
+
+// Stages 1 and 2 on ctx->stream: the counter block zeroed, then k_denoise_albedo over the accumulated colour under the textures the
+// megakernel would use now (`textured` of mega_frame, ptcore_trace.cpp: "textures" with textures and coordinates set; else none).
+// rays: null, or 2 float4 a pixel on the device.  Timed as one launch of the stage.
+static int albedo_stage(ptc_ctx* ctx, float4* rays)
+{
+  const bool textured = ctx->textures && ctx->textures_set && ctx->texcoords_set;
+  const DTex tx = textured ? DTex{ctx->tex_texels, ctx->tex_records, ctx->tex_material, ctx->tex_table, ctx->texcoords, ctx->mesh_first_index} : DTex{};
+  HIP_TRY(ctx, hipMemsetAsync(ctx->albedo_stats, 0, kLoopStatBytes, ctx->stream));
+  ptc_ctx::TimedLaunch tl;
+  if (int rc = timed_begin(ctx, ctx->stream, -2, &tl)) return rc;
+  tl.tag = ctx->albedo_epoch;
+  launch_denoise_albedo(ctx->stream, ctx->scene, tx, ctx->cam, ctx->fb.color4, ctx->den_albedo, ctx->den_irradiance, rays, ctx->albedo_stats,
+                        &ctx->misc_counters->flags);
+  return timed_end(ctx, ctx->stream, tl);
+}
+
+int ptc_denoise(ptc_ctx* ctx)
+{
+  if (int rc = denoise_ready(ctx)) return rc;
   if (int rc = flush_pending(ctx)) return rc;
+  // "denoise_albedo": the passes filter the irradiance plane and their result is multiplied back (no pass, no stage)
+  const bool albedo = ctx->denoise_albedo && ctx->den.filter_size >= 1;
+  if (albedo)
+    if (int rc = albedo_planes(ctx)) return rc;
   // every sample must be folded in before the framebuffers are read (stream order, no host sync)
   if (ctx->order_valid) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->order_event, 0));
   else if (!ctx->slots.empty() && ctx->slots[(size_t)ctx->last_slot].stream != ctx->stream)
@@ -757,6 +804,10 @@ int ptc_denoise(ptc_ctx* ctx)
   float4* back = ctx->den_a;
   float4* front = ctx->den_b;
   if (ctx->den.filter_size >= 1) launch_denoise_positions(ctx->stream, ctx->cam, ctx->pix_count, ctx->fb.nd4, ctx->den_pos);
+  if (albedo) {
+    if (int rc = albedo_stage(ctx, nullptr)) return rc;
+    color = ctx->den_irradiance;
+  }
   for (int step = 1; step <= ctx->den.filter_size; step *= 2) {
     ptc_ctx::TimedLaunch tl;
     if (int rc = timed_begin(ctx, ctx->stream, -1, &tl)) return rc;
@@ -768,6 +819,13 @@ int ptc_denoise(ptc_ctx* ctx)
     color = new_color;
     back = new_back;
     front = new_front;
+  }
+  if (albedo) {  // (filter_size >= 1: front is the last pass's output)
+    ptc_ctx::TimedLaunch tl;
+    if (int rc = timed_begin(ctx, ctx->stream, -2, &tl)) return rc;
+    tl.tag = ctx->albedo_epoch;
+    launch_remodulate(ctx->stream, ctx->pix_count, ctx->den_albedo, front);
+    if (int rc = timed_end(ctx, ctx->stream, tl)) return rc;
   }
   ctx->result = front;
   if (int rc = check_last(ctx, "denoise")) return rc;
@@ -961,7 +1019,9 @@ static int drain_timed(ptc_ctx* ctx)
     float ms = 0.0f;
     HIP_TRY(ctx, hipEventSynchronize(tl.stop));
     HIP_TRY(ctx, hipEventElapsedTime(&ms, tl.start, tl.stop));
-    if (tl.bounce < 0) {
+    if (tl.bounce == -2) {
+      if (tl.tag == ctx->albedo_epoch) ctx->albedo_stage_ms += ms;
+    } else if (tl.bounce < 0) {
       ctx->denoise_ms += ms;
       ctx->denoise_passes += 1u;
     } else {
@@ -1032,6 +1092,58 @@ int ptc_get_profile(ptc_ctx* ctx, ptc_profile* out)
   out->denoise_ms = ctx->denoise_ms;
   out->denoise_passes = ctx->denoise_passes;
   out->persist_launches = ctx->persist_launches;
+  return PTC_OK;
+}
+
+// Stages 1 and 2 of "denoise_albedo" alone, whatever the parameter says: the planes and the rays the kernel built,
+// packed to the caller's host arrays.  The frames in flight are folded in first (host-side, as ptc_download does).
+int ptc_denoise_albedo(ptc_ctx* ctx, float* albedo_out, float* irradiance_out, float* rays_out)
+{
+  if (int rc = denoise_ready(ctx)) return rc;
+  if (int rc = flush_pending(ctx)) return rc;
+  if (int rc = albedo_planes(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;
+  const size_t P = ctx->pix_count;
+  std::vector<void*> pool;
+  float4* d_rays = nullptr;
+  auto run = [&]() -> int {
+    if (rays_out)
+      if (int rc = dev_alloc(ctx, pool, &d_rays, 2u * P)) return rc;
+    if (int rc = albedo_stage(ctx, d_rays)) return rc;
+    if (int rc = check_last(ctx, "denoise_albedo")) return rc;
+    for (const auto& plane : {std::make_pair((const float4*)ctx->den_albedo, albedo_out), std::make_pair((const float4*)ctx->den_irradiance, irradiance_out)}) {
+      if (!plane.second) continue;
+      launch_pack(ctx->stream, plane.first, ctx->pix_count, 0, ctx->pack_buf);  // (stream order: the copy below is done before the next pack)
+      if (int rc = check_last(ctx, "pack")) return rc;
+      HIP_TRY(ctx, hipMemcpyAsync(plane.second, ctx->pack_buf, 3u * P * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (rays_out) HIP_TRY(ctx, hipMemcpyAsync(rays_out, d_rays, 2u * P * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    return PTC_OK;
+  };
+  const int rc = run();
+  const hipError_t e = hipStreamSynchronize(ctx->stream);  // nothing may still use the pool; the caller's arrays are complete
+  free_pool(pool);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("denoise_albedo: ") + hipGetErrorString(e));
+  return PTC_OK;
+}
+
+int ptc_get_denoise_albedo_stats(ptc_ctx* ctx, ptc_denoise_albedo_stats* out)
+{
+  if (!ctx || !out) return PTC_ERR_INVALID;
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;
+  if (int rc = drain_timed(ctx)) return rc;
+  *out = ptc_denoise_albedo_stats{};
+  std::vector<unsigned long long> host((size_t)kLightStatLines * kLoopStatWords);
+  HIP_TRY(ctx, hipMemcpy(host.data(), ctx->albedo_stats, kLoopStatBytes, hipMemcpyDeviceToHost));
+  for (uint32_t l = 0; l < kLightStatLines; ++l) {
+    out->pixels += host[(size_t)kLoopStatWords * l];
+    out->surface_hits += host[(size_t)kLoopStatWords * l + 1u];
+    out->texel_lookups += host[(size_t)kLoopStatWords * l + 2u];
+    out->floored += host[(size_t)kLoopStatWords * l + 3u];
+  }
+  out->stage_ms = ctx->albedo_stage_ms;
   return PTC_OK;
 }
 

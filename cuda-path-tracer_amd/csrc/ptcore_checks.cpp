@@ -5,6 +5,7 @@
 #include "pt_mega_rules.hpp"
 #include "pt_rng.hpp"
 #include "pt_light_sample.hpp"
+#include "pt_demodulate.hpp"
 
 using namespace pt;
 using namespace ptcd;
@@ -620,6 +621,19 @@ int ptc_check_texture_lookup(const ptc_texture_desc* desc, const float* st, uint
     rgb_out[3u * (size_t)i + 1u] = c.y;
     rgb_out[3u * (size_t)i + 2u] = c.z;
     if (rejected_out) rejected_out[i] = ok ? (uint8_t)0 : (uint8_t)1;
+  }
+  return PTC_OK;
+}
+
+// The denoiser's albedo rule (pt_demodulate.hpp) on the host, a channel at a time: the header k_denoise_albedo and
+// k_remodulate run on the device
+int ptc_check_demodulate(const float* colour, const float* albedo, uint32_t n, float* irradiance_out, float* effective_out)
+{
+  if (n != 0u && (!colour || !albedo || !irradiance_out || !effective_out)) return fail(nullptr, PTC_ERR_INVALID, "demodulate: an array is NULL");
+  for (uint32_t i = 0; i < n; ++i) {
+    const float e = demod::effective_albedo(albedo[i]);
+    effective_out[i] = e;
+    irradiance_out[i] = demod::demodulate(colour[i], e);
   }
   return PTC_OK;
 }

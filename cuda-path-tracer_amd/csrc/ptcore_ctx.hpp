@@ -180,6 +180,10 @@ struct ptc_frame_state {
   float4* den_a = nullptr;
   float4* den_b = nullptr;
   float4* den_pos = nullptr;     // per-pixel view-space hit position of the accumulated depth (denoiser)
+  // "denoise_albedo" (DESIGN section 5r): the first-hit albedo plane and the irradiance plane, denoise_albedo_floats4 each
+  // (pt_frame_rules.hpp); of frame_allocs, allocated by the first call that runs the stage at this frame size (albedo_planes)
+  float4* den_albedo = nullptr;
+  float4* den_irradiance = nullptr;
   const float4* result = nullptr;
   float* pack_buf = nullptr;     // 3 floats / pixel staging for downloads
   uint32_t* rgba_buf = nullptr;  // staging for host presents
@@ -274,6 +278,14 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   bool fused_shade = true;    // "fused_shade": the end of a bounce in one pass (k_shade_fused); 0: k_tail_count -> k_scan -> k_shade
   int ray_sort = 0;           // "ray_sort": 1 = traversal lanes pick their rays up grouped by direction octant (bounces >= 1)
   int denoise_variant = 0;    // "denoise_variant": 0 = taps staged in LDS (default), 1 = taps through L1 / L2
+  // "denoise_albedo" (DESIGN section 5r): ptc_denoise filters the colour divided by the first-hit albedo and multiplies it back.
+  // albedo_stats: k_denoise_albedo's counter block on the device (kLoopStatBytes, the context's own; zeroed ahead of every launch, so
+  // it holds the last launch's counts).  albedo_stage_ms: the stage's launches since ptc_restart (TimedLaunch::bounce == -2, counted
+  // while their tag is albedo_epoch, which ptc_restart moves)
+  bool denoise_albedo = false;
+  unsigned long long* albedo_stats = nullptr;
+  double albedo_stage_ms = 0.0;
+  uint32_t albedo_epoch = 0;
   uint32_t lds_entries = kLds4;  // the kernels' LDS stack (pt_device.hpp); fewer only through "debug_lds_entries"
   int force_slow = 0;
 
@@ -283,6 +295,7 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   struct TimedLaunch {
     hipEvent_t start, stop;
     int bounce;
+    uint32_t tag = 0;  // (bounce -2) albedo_epoch when it was enqueued
   };
   std::vector<TimedLaunch> timed;        // recorded, not yet read
   std::vector<hipEvent_t> free_events;
@@ -359,7 +372,7 @@ int fail(ptc_ctx* ctx, int code, const std::string& msg);
 
 int check_last(ptc_ctx* ctx, const char* what);
 // HIP events around one launch of a timed kernel, on the stream it runs on (ptcore.cpp; a closest-hit launch of `bounce`, an
-// A-Trous pass with bounce -1).  Nothing while ctx->time_trace is off.
+// A-Trous pass with bounce -1, a launch of the "denoise_albedo" stage with bounce -2).  Nothing while ctx->time_trace is off.
 int timed_begin(ptc_ctx* ctx, hipStream_t stream, int bounce, ptc_ctx::TimedLaunch* tl);
 int timed_end(ptc_ctx* ctx, hipStream_t stream, const ptc_ctx::TimedLaunch& tl);
 int bind_device(ptc_ctx* ctx);

@@ -2,7 +2,7 @@
 //   cuda_pt [--spp N] [-o out.png] <scene.json>          (reference: src/main.cpp:9-25, src/lib/configurations.cpp:7-45)
 // following the call sequence of execute_cli_version (src/cli/cli.cpp:62-116): read scene, create_buffers,
 // max_iterations = spp, spp x path_trace, synchronize, send_to_preview, write PNG, stage timings.
-// Extra flags: --max-bounces N (the reference's cap is a compile-time 50), --denoise, --method, --gpu,
+// Extra flags: --max-bounces N (the reference's cap is a compile-time 50), --denoise, --denoise-albedo, --method, --gpu,
 // --lens-radius R / --focus-distance F (the thin lens), --tonemap C / --exposure EV / --auto-exposure / --key K / --white W (the display transform), --environment FILE / --environment-scale S / --environment-size N (environment lighting; --dump-environment FILE: the decoded picture and the map, for tests, no GPU), --textures (image textures), --normal-maps (normal maps), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
 // (DisplayBufferType of send_to_preview, path_tracer.cu:487-520: which buffer the PNG shows), --dump-raw FILE (the
 // accumulated float framebuffers as they are: "PTRF", width, height, 7 as uint32, then colour rgb, normal xyz and
@@ -48,6 +48,7 @@ struct CliConfigurations {  // configurations.hpp:11-15
   std::optional<std::string> output_filename;
   int max_bounces = 50;
   bool denoise = false;
+  bool denoise_albedo = false;  // (implies denoise)
   bool megakernel = false;
   bool direct_light = false;
   bool environment_light = false;
@@ -82,6 +83,8 @@ void usage()
                "      --spp arg        Sample per pixel (overrides the setting in the scene file)\n"
                "      --max-bounces N  bounce cap (default 50)\n"
                "      --denoise        run the A-Trous denoiser before writing the image\n"
+               "      --denoise-albedo  denoise irradiance, not colour: the first-hit albedo is divided out before the filter and multiplied\n"
+               "                       back after it, so that a texture's detail passes the filter (implies --denoise)\n"
                "      --method M       streaming (default) | megakernel\n"
                "      --direct-light   a light sample with a shadow ray at every diffuse hit (needs --method megakernel)\n"
                "      --roulette K     Russian roulette at every bounce >= K but the last, unbiased (0 = off, the default; K in [0,64])\n"
@@ -136,6 +139,7 @@ CliConfigurations parse_cli_args(int argc, char** argv)
     else if (a.rfind("--spp=", 0) == 0) c.spp = std::stoi(a.substr(6));
     else if (a == "--max-bounces") c.max_bounces = std::stoi(need("max-bounces"));
     else if (a == "--denoise") c.denoise = true;
+    else if (a == "--denoise-albedo") c.denoise = c.denoise_albedo = true;
     else if (a == "--method") c.megakernel = need("method") == "megakernel";
     else if (a == "--direct-light") c.direct_light = true;
     else if (a == "--environment-light") c.environment_light = true;
@@ -343,7 +347,7 @@ bool write_raw(const std::string& path, uint32_t width, uint32_t height, Fetch f
 //   {"window": [w, h], "iterations_per_frame": 2, "events": [
 //      {"frames": 3},                      loop turns: run_cuda + one PNG each
 //      {"key": "W", "count": 5},           GLFW_REPEAT of W/A/S/D/R/F            {"mouse": [dx, dy]}   right-drag, pixels
-//      {"space": true}  {"resize": [w, h]}  {"denoise": true}  {"display": "normal"}  {"method": "megakernel"}
+//      {"space": true}  {"resize": [w, h]}  {"denoise": true}  {"denoise_albedo": true}  {"display": "normal"}  {"method": "megakernel"}
 //      {"max_iterations": 64}  {"filter_size": 10}  {"speed": 0.5}  {"position": [x, y, z]}  {"reset": true} ]}
 // A turn runs "iterations_per_frame" iterations (default 1) instead of as many as fit into 16 ms, so that a replay
 // gives the same frames every time; "budget_ms": 16 restores the reference's clock.
@@ -401,6 +405,7 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   path_tracer.normal_maps = configs.normal_maps || scene_desc.normal_maps;  // (... and its normal-map binding)
   path_tracer.create_buffers(resolution, scene_desc);
   bool enable_denoising = configs.denoise;
+  path_tracer.denoise_albedo = configs.denoise_albedo;
   DisplayBufferType display = configs.display;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
@@ -448,6 +453,8 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
       path_tracer.resize_image(resolution);  // app.cpp:45
     } else if (const Json* j = ev->find("denoise")) {
       enable_denoising = j->b;
+    } else if (const Json* j = ev->find("denoise_albedo")) {  // (no reference equivalent: the denoiser's albedo factorisation)
+      path_tracer.denoise_albedo = j->b;
     } else if (const Json* j = ev->find("display")) {
       display = j->str == "color" ? DisplayBufferType::color : j->str == "normal" ? DisplayBufferType::normal
                 : j->str == "depth" ? DisplayBufferType::depth : DisplayBufferType::final;
@@ -787,6 +794,7 @@ try {
   path_tracer.textures = configs.textures || scene_desc.textures;  // (create_buffers sets the scene's textures and coordinates)
   path_tracer.normal_maps = configs.normal_maps || scene_desc.normal_maps;  // (... and its normal-map binding)
   path_tracer.roulette = configs.roulette;
+  path_tracer.denoise_albedo = configs.denoise_albedo;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.display = configs.tone;
   path_tracer.environment = scene_desc.environment;

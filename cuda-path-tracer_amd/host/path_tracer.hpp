@@ -57,6 +57,9 @@ public:
   // with a normal map bound shades with the map's normal.  The binding goes through set_normal_maps after set_textures; without
   // textures, coordinates or a binding the flag changes nothing.  Independent of `textures`.
   bool normal_maps = false;
+  // the denoiser's albedo factorisation (ptc_set_param "denoise_albedo"): denoise filters the colour divided by the
+  // first-hit albedo and multiplies it back, so that a texture's detail passes the filter.  Both methods.
+  bool denoise_albedo = false;
   int roulette = 0;  // Russian roulette at every bounce >= this but the last, 0 = off (both methods; ptc_set_param "roulette", [0, 64])
   // the thin lens (ptc_set_lens): aperture radius (0 = the pinhole, the default) and the distance of the plane in
   // focus, world units; both methods
@@ -237,6 +240,25 @@ public:
     push_fields();
     check(ptc_denoise(ctx_), "denoise");
   }
+  // the albedo stage alone (ptc_denoise_albedo), whatever denoise_albedo says: per pixel three floats of albedo, three of irradiance and
+  // the eight of the pixel-centre ray the kernel walked
+  struct DenoiseAlbedo {
+    std::vector<float> albedo, irradiance, rays;
+  };
+  [[nodiscard]] DenoiseAlbedo denoise_albedo_planes(UResolution resolution)
+  {
+    push_fields();
+    const size_t n = (size_t)resolution.width * resolution.height;
+    DenoiseAlbedo out{std::vector<float>(3u * n), std::vector<float>(3u * n), std::vector<float>(8u * n)};
+    check(ptc_denoise_albedo(ctx_, out.albedo.data(), out.irradiance.data(), out.rays.data()), "denoise_albedo");
+    return out;
+  }
+  [[nodiscard]] ptc_denoise_albedo_stats denoise_albedo_stats() const
+  {
+    ptc_denoise_albedo_stats s{};
+    check(ptc_get_denoise_albedo_stats(ctx_, &s), "denoise_albedo_stats");
+    return s;
+  }
   // dst: device (or managed) pointer like the reference's PBO when dst_is_device, else host memory
   void send_to_preview(uchar4* dst, UResolution, DisplayBufferType type = DisplayBufferType::final,
                        bool dst_is_device = false) const
@@ -289,6 +311,10 @@ private:
       check(ptc_set_param(ctx_, "normal_maps", normal_maps ? 1 : 0), "normal_maps");
       normal_maps_pushed_ = normal_maps;
     }
+    if (denoise_albedo != denoise_albedo_pushed_) {
+      check(ptc_set_param(ctx_, "denoise_albedo", denoise_albedo ? 1 : 0), "denoise_albedo");
+      denoise_albedo_pushed_ = denoise_albedo;
+    }
     if (roulette != roulette_pushed_) {
       check(ptc_set_param(ctx_, "roulette", roulette), "roulette");
       roulette_pushed_ = roulette;
@@ -317,6 +343,7 @@ private:
   bool smooth_normals_pushed_ = false;
   bool textures_pushed_ = false;
   bool normal_maps_pushed_ = false;
+  bool denoise_albedo_pushed_ = false;
   int roulette_pushed_ = 0;
   Lens lens_pushed_{};
   std::shared_ptr<const EnvironmentMap> environment_pushed_;

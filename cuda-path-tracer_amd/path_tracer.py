@@ -151,6 +151,19 @@ def check_texture_lookup(texture, st):
     return rgb, rej.astype(bool)
 
 
+def check_demodulate(colour, albedo):
+    """The denoiser's albedo rule of DESIGN section 5r on the host (ptc_check_demodulate; no GPU needed), elementwise on two float32
+    arrays of one shape -> (irradiance, effective albedo), float32 of that shape"""
+    c = np.ascontiguousarray(colour, dtype=np.float32)
+    a = np.ascontiguousarray(albedo, dtype=np.float32)
+    if c.shape != a.shape:
+        raise ValueError("check_demodulate: the arrays differ in shape")
+    irr, eff = np.zeros_like(c), np.zeros_like(c)
+    _capi.check(_capi.lib().ptc_check_demodulate(c.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), c.size,
+                                                 irr.ctypes.data_as(C.c_void_p), eff.ctypes.data_as(C.c_void_p)))
+    return irr, eff
+
+
 def normal_map_decode_table():
     """The 256-entry decode table of a normal map (ptc_normal_map_decode_table; host-side, no GPU needed)"""
     out = np.zeros(256, dtype=np.float32)
@@ -659,6 +672,28 @@ class PathTracer:
     def denoise(self, resolution=None):
         self._push_fields()
         self._check(self._lib.ptc_denoise(self._ctx))
+
+    def denoise_albedo(self):
+        """The albedo stage of set_param("denoise_albedo", 1) alone (ptc_denoise_albedo), whatever the parameter
+        says -> dict(albedo float32 [h, w, 3]: the first-hit albedo of the pixel-centre ray, ones at glass, an emitter and on a miss;
+        irradiance float32 [h, w, 3]: the accumulated colour over the effective albedo; rays float32 [h * w, 8]: the rays the kernel
+        walked, hit_surface's layout).  Needs a traced frame and the whole frame in this context."""
+        self._push_fields()
+        w, h = self._resolution
+        alb, irr = np.zeros((h, w, 3), dtype=np.float32), np.zeros((h, w, 3), dtype=np.float32)
+        rays = np.zeros((h * w, 8), dtype=np.float32)
+        self._check(self._lib.ptc_denoise_albedo(self._ctx, alb.ctypes.data_as(C.c_void_p), irr.ctypes.data_as(C.c_void_p),
+                                                 rays.ctypes.data_as(C.c_void_p)))
+        return {"albedo": alb, "irradiance": irr, "rays": rays}
+
+    def denoise_albedo_stats(self):
+        """Counters of the last call that ran the albedo stage (denoise under "denoise_albedo" 1, or denoise_albedo): pixels, those whose
+        first hit is diffuse or metal, those that took a texel, channels on the albedo floor; stage_ms: the stage's launches since
+        restart, while events are enabled."""
+        s = _capi.ptc_denoise_albedo_stats()
+        self._check(self._lib.ptc_get_denoise_albedo_stats(self._ctx, C.byref(s)))
+        return {"pixels": int(s.pixels), "surface_hits": int(s.surface_hits), "texel_lookups": int(s.texel_lookups),
+                "floored": int(s.floored), "stage_ms": float(s.stage_ms)}
 
     def send_to_preview(self, dev_pbo=None, resolution=None, display_type=DisplayBufferType.final):
         """With dev_pbo=None returns an [h, w, 4] uint8 array; otherwise writes RGBA8 to the device pointer."""

@@ -286,7 +286,16 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *   "denoise_variant"  0 (default): the A-Trous passes stage their taps in LDS, one sub-lattice of the dilated filter per
  *                      workgroup; 1: taps through L1 / L2 (round-1 kernel, kept as a cross-check).  Same results up to
  *                      summation order (both within 1e-5 of the oracle)
- *   "slot_offset"      added to every compacted slot index before the material RNG is seeded (path_tracer.cu:300).  A
+ *   "denoise_albedo"   DENOISING (default 0; an extension): 1 = ptc_denoise filters irradiance, not colour.  Per
+ *                      pixel the first-hit albedo of the pixel-centre view ray (k_denoise_albedo: at a diffuse or metal hit what
+ *                      ptc_hit_surface reports there -- with the texel only while "textures" is 1 and textures and coordinates
+ *                      are set --, at glass, an emitter and on a miss (1, 1, 1)); per channel e = albedo > 1/64 ? albedo : 1/64 (a NaN
+ *                      takes 1/64); the passes run on colour / e with the same normals, positions, weights and "denoise_variant",
+ *                      and their result x e is the final buffer (k_remodulate).  ptc_profile's denoise_passes and denoise_ms count
+ *                      the passes as before; the stage's own time and counters: ptc_get_denoise_albedo_stats.  A filter_size < 1
+ *                      runs no stage.  Two float4 planes per pixel, allocated by the first call that needs them and released with
+ *                      the frame.  0 launches exactly what was launched before the parameter existed.  Any time
+ *   "slot_offset"     added to every compacted slot index before the material RNG is seeded (path_tracer.cu:300).  A
  *                      rank of a multi-GPU run that numbers its paths locally (ptc_set_interleave) sets rank * (pixels of
  *                      the largest share) so that no two ranks draw the same random streams; 0 (default) = the reference
  *   "beam"             1 (default): when a bounce-0 traversal launch walks one mesh object, a small kernel first computes, per
@@ -469,6 +478,27 @@ int ptc_read_live_count(ptc_ctx* ctx, int bounce, uint32_t* host_out);
 
 /* PathTracer::denoise (path_tracer.cu:479-485) */
 int ptc_denoise(ptc_ctx* ctx);
+
+/* The albedo stage of "denoise_albedo" alone, whatever the parameter says: k_denoise_albedo on the accumulated
+ * colour and the last traced camera, returned to host arrays, each of which may be NULL -- albedo_out 3 floats per pixel (the plane
+ * as the parameter's text describes it), irradiance_out 3 floats per pixel (colour / e per channel), rays_out 8 floats per pixel (the
+ * pixel-centre rays the kernel walked, in ptc_intersect_rays' layout: origin, t_min 1e-4, direction, t_max infinity; pinhole rays under
+ * a lens too).  Pixels in row order.  The final buffer is not touched.  ptc_denoise's refusals: PTC_ERR_INVALID without a traced frame
+ * and for a context that does not own the whole frame (ptc_set_rows, ptc_set_interleave).  Synchronises. */
+int ptc_denoise_albedo(ptc_ctx* ctx, float* albedo_out, float* irradiance_out, float* rays_out);
+/* pixels, surface_hits (pixels whose first hit is diffuse or metal), texel_lookups (those that took a texel) and floored (channels
+ * whose albedo took the floor 1/64) of the last call that ran k_denoise_albedo -- ptc_denoise under "denoise_albedo" 1 with a
+ * filter_size >= 1, or ptc_denoise_albedo; zeros before the first.  stage_ms: the summed duration of the stage's launches
+ * (k_denoise_albedo and k_remodulate) since ptc_restart, while events are enabled (ptc_set_profiling).  Synchronises. */
+typedef struct ptc_denoise_albedo_stats {
+  uint64_t pixels, surface_hits, texel_lookups, floored;
+  double stage_ms;
+} ptc_denoise_albedo_stats;
+int ptc_get_denoise_albedo_stats(ptc_ctx* ctx, ptc_denoise_albedo_stats* out);
+/* The rule of section 5r on the host (no GPU, no context), a channel at a time: effective_out[i] = albedo[i] > 1/64 ? albedo[i] : 1/64
+ * and irradiance_out[i] = colour[i] / effective_out[i], one binary32 operation each -- the header the kernels run.  n values in every
+ * array.  PTC_ERR_INVALID: a NULL with n > 0. */
+int ptc_check_demodulate(const float* colour, const float* albedo, uint32_t n, float* irradiance_out, float* effective_out);
 
 /* PathTracer::send_to_preview (path_tracer.cu:487-520): tonemap to RGBA8 (4 bytes/pixel, rows of
  * this context only).  dst is a device pointer if dst_is_device != 0 (the reference always writes a
