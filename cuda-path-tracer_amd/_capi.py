@@ -142,6 +142,10 @@ class ptc_denoise_albedo_stats(C.Structure):
                 ("stage_ms", C.c_double)]
 
 
+class ptc_denoise_variance_stats(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("floored", C.c_uint64), ("stage_ms", C.c_double)]
+
+
 class ptc_normal_map_loop_stats(C.Structure):
     _fields_ = [("bent", C.c_uint64), ("kept", C.c_uint64)]
 
@@ -210,6 +214,12 @@ SIGNATURES = {
     "ptc_denoise_albedo": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptc_get_denoise_albedo_stats": (C.c_int, [_P, C.POINTER(ptc_denoise_albedo_stats)]),
     "ptc_check_demodulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ptc_set_denoise_variance": (C.c_int, [_P, C.c_float]),
+    "ptc_get_denoise_variance": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "ptc_denoise_variance": (C.c_int, [_P, C.c_void_p, C.c_void_p]),
+    "ptc_get_denoise_variance_stats": (C.c_int, [_P, C.POINTER(ptc_denoise_variance_stats)]),
+    "ptc_check_denoise_variance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float,
+                                             C.c_void_p, C.c_void_p]),
     "ptc_present_rgba8": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "ptc_download": (C.c_int, [_P, C.c_int, _P, C.c_int]),
     "ptc_band_export": (C.c_int, [_P, C.POINTER(ptc_band_handle)]),

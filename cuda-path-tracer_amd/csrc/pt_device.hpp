@@ -343,6 +343,12 @@ struct DDenoise {
   int variant;  // 0: taps staged in LDS per sub-lattice (k_denoise_lds, default); 1: taps through L1 / L2 (k_denoise)
 };
 
+// a guided pass of "denoise_variance" (DESIGN section 5s): no colour weight -- sigma x the prefiltered variance takes its place
+struct DDenoiseVar {
+  float n_phi, p_phi, sigma;
+  int variant;  // as DDenoise's: 0 k_denoise_var_lds, 1 k_denoise_var
+};
+
 // The reference BVH built on the device (pt_bvh_gpu.hip): the same tree as build_bvh (pt_bvh.cpp), node for node.
 // d_packed: 2 * (2T-1) float4 ({min, first}, {max, count}: DScene::bvh); d_nodes (may be null): the same nodes in the
 // reference's 32-byte layout; level_base (may be null): first node of every depth, plus the node count at the end.
@@ -648,6 +654,17 @@ void launch_hit_shading_normal(hipStream_t s, const DScene& scene, DSmooth sm, D
 void launch_denoise_albedo(hipStream_t s, const DScene& scene, DTex tx, const DCamera& cam, const float4* color, float4* albedo,
                            float4* irradiance, float4* rays, unsigned long long* stats, uint32_t* flags);
 void launch_remodulate(hipStream_t s, uint32_t pix_count, const float4* albedo, float4* front);
+// "denoise_variance" (pt_denoise_variance.hip).  launch_variance_estimate: per pixel the weighted variance of `color`
+// over its 7 x 7 window (normal and position weights, centred form), one float a pixel.  launch_variance_prefilter: the 3 x 3
+// Gaussian of a variance plane (prefiltered may be null: the counters alone); stats: kLightStatLines lines of kLoopStatWords words, 0 and 1 += pixels, pixels below the floor.  launch_denoise_var_pass: one guided pass at
+// step_width -- colour and variance in, colour and variance out (neither pair may alias); the LDS kernel for the steps 1 .. 32 that are
+// powers of two under variant 0, else the through-cache kernel.
+void launch_variance_estimate(hipStream_t s, uint32_t width, uint32_t height, const float4* color, const float4* nd, const float4* pos,
+                              float* variance, float n_phi, float p_phi);
+void launch_variance_prefilter(hipStream_t s, uint32_t width, uint32_t height, const float* variance, float* prefiltered,
+                               unsigned long long* stats);
+void launch_denoise_var_pass(hipStream_t s, const DCamera& cam, uint32_t pix_count, const float4* color, const float* variance,
+                             const float4* nd, const float4* pos, float4* out, float* variance_out, int step_width, DDenoiseVar params);
 // ptc_environment_light_pdf's kernel (pt_env.hip): one thread per unit direction, env_light::density
 void launch_env_light_pdf(hipStream_t s, DEnvLight el, uint32_t n, const float* dirs, uint32_t count, float* pdf);
 void launch_selftest(hipStream_t s, const float* a, const float* b, uint32_t n, float* out_div, float* out_sqrt,

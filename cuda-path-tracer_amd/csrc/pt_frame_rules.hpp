@@ -48,4 +48,10 @@ inline ptc_frame_plan frame_plan(uint32_t width, uint32_t height, int frames_in_
 constexpr int kDenoiseAlbedoPlanes = 2;
 inline uint64_t denoise_albedo_floats4(uint32_t width, uint32_t height) { return (uint64_t)width * height; }
 
+// "denoise_variance" (DESIGN section 5s): the planes the mode adds to a frame -- the two scalar variance planes that ping-pong beside
+// den_a and den_b (the estimate writes the first; ptc_denoise_variance's prefiltered plane borrows the second), a float per pixel each
+// -- and the floats of one.  Allocated and released as the albedo planes are (ptcore.cpp, variance_planes).
+constexpr int kDenoiseVariancePlanes = 2;
+inline uint64_t denoise_variance_floats(uint32_t width, uint32_t height) { return (uint64_t)width * height; }
+
 }  // namespace pt

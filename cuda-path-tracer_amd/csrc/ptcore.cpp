@@ -224,6 +224,7 @@ const ParamRow kParams[] = {
     {"roulette", 0, 64, " must be in [0,64]", kAnyTime, [](ptc_ctx* c, int v) { c->roulette = v; }},
     {"denoise_variant", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_variant = v; }},
     {"denoise_albedo", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_albedo = v != 0; }},
+    {"denoise_variance", 0, 1, k01, kAnyTime, [](ptc_ctx* c, int v) { c->denoise_variance = v != 0; }},
     {"frames_in_flight", 1, 256, " must be in [1,256]", kBeforeResize, [](ptc_ctx* c, int v) { c->frames_in_flight = v; }},
 };
 #undef PT_STR
@@ -444,6 +445,9 @@ int ptc_create(const ptc_config* config, ptc_ctx** out)
   if (hipMalloc(&p, kLoopStatBytes) != hipSuccess) return bail(fail(ctx, PTC_ERR_OOM, "hipMalloc(denoise albedo counters) failed"));
   ctx->albedo_stats = static_cast<unsigned long long*>(p);
   if (hipMemset(ctx->albedo_stats, 0, kLoopStatBytes) != hipSuccess) return bail(fail(ctx, PTC_ERR_HIP, "hipMemset failed"));
+  if (hipMalloc(&p, kVarianceStatBytes) != hipSuccess) return bail(fail(ctx, PTC_ERR_OOM, "hipMalloc(denoise variance counters) failed"));
+  ctx->variance_stats = static_cast<unsigned long long*>(p);
+  if (hipMemset(ctx->variance_stats, 0, kVarianceStatBytes) != hipSuccess) return bail(fail(ctx, PTC_ERR_HIP, "hipMemset failed"));
   *out = ctx;
   return PTC_OK;
 }
@@ -473,6 +477,7 @@ void ptc_destroy(ptc_ctx* ctx)
   if (ctx->misc_counters) (void)hipFree(ctx->misc_counters);
   if (ctx->loop_stats) (void)hipFree(ctx->loop_stats);
   if (ctx->albedo_stats) (void)hipFree(ctx->albedo_stats);
+  if (ctx->variance_stats) (void)hipFree(ctx->variance_stats);
   if (ctx->env.texels) (void)hipFree(const_cast<float4*>(ctx->env.texels));
   if (ctx->env_table) (void)hipFree(const_cast<uint4*>(ctx->env_table));
   if (ctx->meter_dev) (void)hipFree(ctx->meter_dev);  // (exposure_dev is the same allocation)
@@ -522,6 +527,7 @@ int ptc_restart(ptc_ctx* ctx)
   ctx->loop_stats_clear = true;  // ptc_get_direct_loop_stats counts from here
   ctx->albedo_stage_ms = 0.0;    // ptc_get_denoise_albedo_stats' stage_ms too: launches timed before this carry the old epoch
   ctx->albedo_epoch += 1u;
+  ctx->variance_stage_ms = 0.0;  // ptc_get_denoise_variance_stats' stage_ms: its launches carry the same epoch
   return PTC_OK;
 }
 
@@ -786,6 +792,36 @@ static int albedo_stage(ptc_ctx* ctx, float4* rays)
   return timed_end(ctx, ctx->stream, tl);
 }
 
+// "denoise_variance" (DESIGN section 5s): the two variance planes of this frame size, allocated by the first call that gets here and
+// released with the frame (release_frame: they are of frame_allocs)
+static int variance_planes(ptc_ctx* ctx)
+{
+  static_assert(kDenoiseVariancePlanes == 2, "the variance planes that ping-pong beside den_a and den_b");
+  const size_t elems = (size_t)denoise_variance_floats(ctx->width, ctx->height);
+  if (!ctx->den_var_a)
+    if (int rc = dev_alloc(ctx, ctx->frame_allocs, &ctx->den_var_a, elems)) return rc;
+  if (!ctx->den_var_b)
+    if (int rc = dev_alloc(ctx, ctx->frame_allocs, &ctx->den_var_b, elems)) return rc;
+  return PTC_OK;
+}
+
+// The estimate stage on ctx->stream: the counters zeroed, k_variance_estimate of `plane` (under the normals and den_pos, which the
+// caller has made) into den_var_a, then k_variance_prefilter of that, which counts the pixels on the floor and, for
+// ptc_denoise_variance (keep_prefiltered), writes the prefiltered plane into den_var_b; under ptc_denoise it writes nothing -- the
+// passes prefilter for themselves.  Timed as one launch of the stage.
+static int variance_stage(ptc_ctx* ctx, const float4* plane, bool keep_prefiltered)
+{
+  HIP_TRY(ctx, hipMemsetAsync(ctx->variance_stats, 0, kVarianceStatBytes, ctx->stream));
+  ptc_ctx::TimedLaunch tl;
+  if (int rc = timed_begin(ctx, ctx->stream, -3, &tl)) return rc;
+  tl.tag = ctx->albedo_epoch;
+  launch_variance_estimate(ctx->stream, ctx->width, ctx->height, plane, ctx->fb.nd4, ctx->den_pos, ctx->den_var_a, ctx->den.normal_weight,
+                           ctx->den.position_weight);
+  launch_variance_prefilter(ctx->stream, ctx->width, ctx->height, ctx->den_var_a, keep_prefiltered ? ctx->den_var_b : nullptr,
+                            ctx->variance_stats);
+  return timed_end(ctx, ctx->stream, tl);
+}
+
 int ptc_denoise(ptc_ctx* ctx)
 {
   if (int rc = denoise_ready(ctx)) return rc;
@@ -794,6 +830,10 @@ int ptc_denoise(ptc_ctx* ctx)
   const bool albedo = ctx->denoise_albedo && ctx->den.filter_size >= 1;
   if (albedo)
     if (int rc = albedo_planes(ctx)) return rc;
+  // "denoise_variance": an estimate stage ahead of the passes, and the guided passes in the plain ones' place (no pass, no stage)
+  const bool guided = ctx->denoise_variance && ctx->den.filter_size >= 1;
+  if (guided)
+    if (int rc = variance_planes(ctx)) return rc;
   // every sample must be folded in before the framebuffers are read (stream order, no host sync)
   if (ctx->order_valid) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->order_event, 0));
   else if (!ctx->slots.empty() && ctx->slots[(size_t)ctx->last_slot].stream != ctx->stream)
@@ -808,10 +848,27 @@ int ptc_denoise(ptc_ctx* ctx)
     if (int rc = albedo_stage(ctx, nullptr)) return rc;
     color = ctx->den_irradiance;
   }
+  // (guided only) the variance travels beside the colour: (var, var_back) swap as (color, back) do
+  DDenoiseVar vprm{};
+  const float* var = nullptr;
+  float* var_back = nullptr;
+  if (guided) {
+    vprm = DDenoiseVar{ctx->den.normal_weight, ctx->den.position_weight, ctx->variance_sigma, ctx->denoise_variant};
+    var = ctx->den_var_a;
+    var_back = ctx->den_var_b;
+    if (int rc = variance_stage(ctx, color, false)) return rc;
+  }
   for (int step = 1; step <= ctx->den.filter_size; step *= 2) {
     ptc_ctx::TimedLaunch tl;
     if (int rc = timed_begin(ctx, ctx->stream, -1, &tl)) return rc;
-    launch_denoise_pass(ctx->stream, ctx->cam, ctx->pix_count, color, ctx->fb.nd4, ctx->den_pos, back, step, prm);
+    if (guided) {
+      launch_denoise_var_pass(ctx->stream, ctx->cam, ctx->pix_count, color, var, ctx->fb.nd4, ctx->den_pos, back, var_back, step, vprm);
+      float* const written = var_back;
+      var_back = const_cast<float*>(var);
+      var = written;
+    } else {
+      launch_denoise_pass(ctx->stream, ctx->cam, ctx->pix_count, color, ctx->fb.nd4, ctx->den_pos, back, step, prm);
+    }
     if (int rc = timed_end(ctx, ctx->stream, tl)) return rc;
     const float4* new_color = back;
     float4* new_back = front;
@@ -1021,6 +1078,8 @@ static int drain_timed(ptc_ctx* ctx)
     HIP_TRY(ctx, hipEventElapsedTime(&ms, tl.start, tl.stop));
     if (tl.bounce == -2) {
       if (tl.tag == ctx->albedo_epoch) ctx->albedo_stage_ms += ms;
+    } else if (tl.bounce == -3) {
+      if (tl.tag == ctx->albedo_epoch) ctx->variance_stage_ms += ms;
     } else if (tl.bounce < 0) {
       ctx->denoise_ms += ms;
       ctx->denoise_passes += 1u;
@@ -1144,6 +1203,70 @@ int ptc_get_denoise_albedo_stats(ptc_ctx* ctx, ptc_denoise_albedo_stats* out)
     out->floored += host[(size_t)kLoopStatWords * l + 3u];
   }
   out->stage_ms = ctx->albedo_stage_ms;
+  return PTC_OK;
+}
+
+int ptc_set_denoise_variance(ptc_ctx* ctx, float sigma)
+{
+  if (!ctx) return PTC_ERR_INVALID;
+  if (!std::isfinite(sigma) || !(sigma > 0.0f)) return fail(ctx, PTC_ERR_INVALID, "denoise_variance: sigma must be finite and > 0");
+  ctx->variance_sigma = sigma;
+  return PTC_OK;
+}
+
+int ptc_get_denoise_variance(ptc_ctx* ctx, float* sigma)
+{
+  if (!ctx || !sigma) return PTC_ERR_INVALID;
+  *sigma = ctx->variance_sigma;
+  return PTC_OK;
+}
+
+// The estimate stage of "denoise_variance" alone, whatever the parameter says, on the plane ptc_denoise would
+// filter now: the irradiance under "denoise_albedo" 1 (the albedo stage runs first), else the accumulated colour.  The frames in
+// flight are folded in first (host-side, as ptc_download does).
+int ptc_denoise_variance(ptc_ctx* ctx, float* variance_out, float* prefiltered_out)
+{
+  if (int rc = denoise_ready(ctx)) return rc;
+  if (int rc = flush_pending(ctx)) return rc;
+  if (ctx->denoise_albedo)
+    if (int rc = albedo_planes(ctx)) return rc;
+  if (int rc = variance_planes(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;
+  const size_t P = ctx->pix_count;
+  auto run = [&]() -> int {
+    launch_denoise_positions(ctx->stream, ctx->cam, ctx->pix_count, ctx->fb.nd4, ctx->den_pos);
+    const float4* plane = ctx->fb.color4;
+    if (ctx->denoise_albedo) {
+      if (int rc = albedo_stage(ctx, nullptr)) return rc;
+      plane = ctx->den_irradiance;
+    }
+    if (int rc = variance_stage(ctx, plane, true)) return rc;
+    if (int rc = check_last(ctx, "denoise_variance")) return rc;
+    if (variance_out) HIP_TRY(ctx, hipMemcpyAsync(variance_out, ctx->den_var_a, P * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (prefiltered_out) HIP_TRY(ctx, hipMemcpyAsync(prefiltered_out, ctx->den_var_b, P * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return PTC_OK;
+  };
+  const int rc = run();
+  const hipError_t e = hipStreamSynchronize(ctx->stream);  // the caller's arrays are complete
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(ctx, PTC_ERR_HIP, std::string("denoise_variance: ") + hipGetErrorString(e));
+  return PTC_OK;
+}
+
+int ptc_get_denoise_variance_stats(ptc_ctx* ctx, ptc_denoise_variance_stats* out)
+{
+  if (!ctx || !out) return PTC_ERR_INVALID;
+  if (int rc = bind_device(ctx)) return rc;
+  if (int rc = sync_frames(ctx)) return rc;
+  if (int rc = drain_timed(ctx)) return rc;
+  *out = ptc_denoise_variance_stats{};
+  std::vector<unsigned long long> host((size_t)kLightStatLines * kLoopStatWords);
+  HIP_TRY(ctx, hipMemcpy(host.data(), ctx->variance_stats, kVarianceStatBytes, hipMemcpyDeviceToHost));
+  for (uint32_t l = 0; l < kLightStatLines; ++l) {
+    out->pixels += host[(size_t)kLoopStatWords * l];
+    out->floored += host[(size_t)kLoopStatWords * l + 1u];
+  }
+  out->stage_ms = ctx->variance_stage_ms;
   return PTC_OK;
 }
 

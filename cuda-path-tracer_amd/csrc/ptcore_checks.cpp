@@ -6,6 +6,7 @@
 #include "pt_rng.hpp"
 #include "pt_light_sample.hpp"
 #include "pt_demodulate.hpp"
+#include "pt_denoise_variance.hpp"
 
 using namespace pt;
 using namespace ptcd;
@@ -635,6 +636,97 @@ int ptc_check_demodulate(const float* colour, const float* albedo, uint32_t n, f
     effective_out[i] = e;
     irradiance_out[i] = demod::demodulate(colour[i], e);
   }
+  return PTC_OK;
+}
+
+// The whole "denoise_variance" mode on the host from the caller's planes: tap positions as k_denoise_positions and
+// the off-by-one taps make them, the estimate, then the guided passes with their ping-pong -- every per-tap number from
+// pt_denoise_variance.hpp, the header the kernels compile.  colour, normal: 3 floats a pixel; depth: one; variance_out (may be NULL):
+// the estimate, one float a pixel; result_out (may be NULL): 3 floats a pixel, untouched when filter_size < 1 (no pass, no result).
+int ptc_check_denoise_variance(const float* colour, const float* normal, const float* depth, const ptc_camera* camera, uint32_t width,
+                               uint32_t height, const ptc_denoiser_params* weights, float sigma, float* variance_out, float* result_out)
+{
+  if (!colour || !normal || !depth || !camera || !weights) return fail(nullptr, PTC_ERR_INVALID, "denoise_variance: an array is NULL");
+  if (width < 2u || height < 2u || (uint64_t)width * height > 0x7fffffffull) return fail(nullptr, PTC_ERR_INVALID, "denoise_variance: bad size");
+  if (!std::isfinite(sigma) || !(sigma > 0.0f)) return fail(nullptr, PTC_ERR_INVALID, "denoise_variance: sigma must be finite and > 0");
+  const int W = (int)width, H = (int)height;
+  const uint32_t P = width * height;
+  const DCamera cam = make_camera(*camera, width, height);
+  auto view_point = [&](int u, int v, float d) {  // generate_ray (pt_kernels_common.inc) at the pixel centre, the same operations
+    const float fu = ((float)u + 0.5f) / (float)(cam.width - 1u);
+    const float fv = ((float)cam.height - ((float)v + 0.5f)) / (float)(cam.height - 1u);
+    const f3 dir = normalize(xform_vector(cam.cam, mk3(cam.llx + cam.vw * fu, cam.lly + cam.vh * fv, -1.0f)));
+    return cam.origin + dir * d;
+  };
+  auto at3 = [](const std::vector<float>& a, uint32_t i) { return mk3(a[3u * i], a[3u * i + 1u], a[3u * i + 2u]); };
+  const std::vector<float> nrm(normal, normal + 3u * (size_t)P);
+  std::vector<float> pos(3u * (size_t)P);
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const uint32_t i = (uint32_t)x + (uint32_t)y * width;
+      const f3 p = view_point(x, y, depth[i]);
+      pos[3u * i] = p.x, pos[3u * i + 1u] = p.y, pos[3u * i + 2u] = p.z;
+    }
+  std::vector<float> c(colour, colour + 3u * (size_t)P), c2(3u * (size_t)P), var(P), var2(P);
+  // ---- the estimate
+  {
+    const float kn = dvar::term_scale(weights->normal_weight), kp = dvar::term_scale(weights->position_weight);
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        const uint32_t i = (uint32_t)x + (uint32_t)y * width;
+        const f3 cp = at3(c, i), np = at3(nrm, i), xp = at3(pos, i);
+        dvar::MeanSum ms{mk3(0.f, 0.f, 0.f), 0.0f};
+        auto window = [&](auto&& tap) {
+          for (int dy = -dvar::kVarRadius; dy <= dvar::kVarRadius; ++dy)
+            for (int dx = -dvar::kVarRadius; dx <= dvar::kVarRadius; ++dx) {
+              const uint32_t q = (uint32_t)std::clamp(x + dx, 0, W - 1) + (uint32_t)std::clamp(y + dy, 0, H - 1) * width;
+              tap(dvar::estimate_weight(np, at3(nrm, q), xp, at3(pos, q), kn, kp), at3(c, q));
+            }
+        };
+        window([&](float g, f3 cq) { dvar::mean_tap(ms, g, cp, cq); });
+        const f3 m = dvar::mean_of(ms, cp);
+        float acc = 0.0f;
+        window([&](float g, f3 cq) { dvar::variance_tap(acc, g, cq, m); });
+        var[i] = dvar::variance_of(acc, ms.g);
+      }
+  }
+  if (variance_out) std::copy(var.begin(), var.end(), variance_out);
+  // ---- the passes: (colour, variance) ping-pong; the last pass's output is the result
+  const float kp = dvar::term_scale(weights->position_weight);
+  int passes = 0;
+  for (int64_t step = 1; step <= (int64_t)weights->filter_size; step *= 2, ++passes) {
+    const float kn = dvar::term_scale((float)(step * step) * weights->normal_weight);
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        const uint32_t i = (uint32_t)x + (uint32_t)y * width;
+        float v9[9];
+        for (int dy = -1; dy <= 1; ++dy)
+          for (int dx = -1; dx <= 1; ++dx)
+            v9[3 * (dy + 1) + dx + 1] = var[(uint32_t)std::clamp(x + dx, 0, W - 1) + (uint32_t)std::clamp(y + dy, 0, H - 1) * width];
+        const float kc = dvar::colour_scale(sigma, dvar::prefilter(v9));
+        const f3 cp = at3(c, i), np = at3(nrm, i), xp = at3(pos, i);
+        dvar::PassSum ps{mk3(0.f, 0.f, 0.f), 0.0f, 0.0f};
+        for (int dy = -2; dy <= 2; ++dy)
+          for (int dx = -2; dx <= 2; ++dx) {
+            // the passes' tap-coordinate contract (k_denoise_lds): inclusive clamp, the last element past the end, own view ray
+            const int u = (int)std::clamp<int64_t>(x + dx * step, 0, W), v = (int)std::clamp<int64_t>(y + dy * step, 0, H);
+            const uint32_t ti = std::min((uint32_t)u + (uint32_t)v * width, P - 1u);
+            const f3 xq = (u == W || v == H) ? view_point(u, v, depth[ti]) : at3(pos, ti);
+            const f3 diff = cp - at3(c, ti);
+            const float dc = dvar::dist2(cp, at3(c, ti));
+            const float w = dvar::pass_weight(dc, dvar::dist2(np, at3(nrm, ti)), dvar::dist2(xp, xq), kc, kn, kp);
+            dvar::pass_tap(ps, w * dvar::kernel_weight(dx, dy), diff, var[ti]);
+          }
+        f3 co;
+        float vo;
+        dvar::pass_result(ps, cp, co, vo);
+        c2[3u * i] = co.x, c2[3u * i + 1u] = co.y, c2[3u * i + 2u] = co.z;
+        var2[i] = vo;
+      }
+    c.swap(c2);
+    var.swap(var2);
+  }
+  if (result_out && passes > 0) std::copy(c.begin(), c.end(), result_out);
   return PTC_OK;
 }
 

@@ -105,6 +105,7 @@ struct ptc_scene_state {
 constexpr uint32_t kMaxEpoch = 0x3fffffffu;
 // the counter block of the direct-lit megakernel (ptc_ctx::loop_stats)
 constexpr size_t kLoopStatBytes = (size_t)kLightStatLines * kLoopStatWords * sizeof(unsigned long long);
+constexpr size_t kVarianceStatBytes = kLoopStatBytes;  // k_variance_prefilter's counters, in lines as the albedo stage's: words 0, 1
 
 // Everything of a context that a ptc_resize decides or that dies with it.  ptc_resize (ptcore.cpp) builds one of these beside the
 // context and assigns it as a whole, after the last step that can fail; a value-initialised one is the state "no frame"
@@ -184,6 +185,10 @@ struct ptc_frame_state {
   // (pt_frame_rules.hpp); of frame_allocs, allocated by the first call that runs the stage at this frame size (albedo_planes)
   float4* den_albedo = nullptr;
   float4* den_irradiance = nullptr;
+  // "denoise_variance" (DESIGN section 5s): the two variance planes, denoise_variance_floats each (pt_frame_rules.hpp); of
+  // frame_allocs, allocated by the first call that runs the mode at this frame size (variance_planes)
+  float* den_var_a = nullptr;
+  float* den_var_b = nullptr;
   const float4* result = nullptr;
   float* pack_buf = nullptr;     // 3 floats / pixel staging for downloads
   uint32_t* rgba_buf = nullptr;  // staging for host presents
@@ -286,6 +291,14 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   unsigned long long* albedo_stats = nullptr;
   double albedo_stage_ms = 0.0;
   uint32_t albedo_epoch = 0;
+  // "denoise_variance" (DESIGN section 5s): ptc_denoise estimates a per-pixel variance and lets it steer the passes' colour weight.
+  // variance_sigma: ptc_set_denoise_variance.  variance_stats: k_variance_prefilter's counter block on the device (kLoopStatBytes; pixels, pixels on the
+  // floor; zeroed ahead of every launch of the stage).  variance_stage_ms: the stage's launches since ptc_restart (TimedLaunch::bounce
+  // == -3, counted while their tag is albedo_epoch, the one epoch ptc_restart moves)
+  bool denoise_variance = false;
+  float variance_sigma = 16.0f;
+  unsigned long long* variance_stats = nullptr;
+  double variance_stage_ms = 0.0;
   uint32_t lds_entries = kLds4;  // the kernels' LDS stack (pt_device.hpp); fewer only through "debug_lds_entries"
   int force_slow = 0;
 
@@ -295,7 +308,7 @@ struct ptc_ctx : ptc_scene_state, ptc_frame_state {
   struct TimedLaunch {
     hipEvent_t start, stop;
     int bounce;
-    uint32_t tag = 0;  // (bounce -2) albedo_epoch when it was enqueued
+    uint32_t tag = 0;  // (bounce -2, -3) albedo_epoch when it was enqueued
   };
   std::vector<TimedLaunch> timed;        // recorded, not yet read
   std::vector<hipEvent_t> free_events;
@@ -372,7 +385,7 @@ int fail(ptc_ctx* ctx, int code, const std::string& msg);
 
 int check_last(ptc_ctx* ctx, const char* what);
 // HIP events around one launch of a timed kernel, on the stream it runs on (ptcore.cpp; a closest-hit launch of `bounce`, an
-// A-Trous pass with bounce -1, a launch of the "denoise_albedo" stage with bounce -2).  Nothing while ctx->time_trace is off.
+// A-Trous pass with bounce -1, a launch of the "denoise_albedo" stage with bounce -2, of the "denoise_variance" estimate stage with -3).  Nothing while ctx->time_trace is off.
 int timed_begin(ptc_ctx* ctx, hipStream_t stream, int bounce, ptc_ctx::TimedLaunch* tl);
 int timed_end(ptc_ctx* ctx, hipStream_t stream, const ptc_ctx::TimedLaunch& tl);
 int bind_device(ptc_ctx* ctx);

@@ -2,7 +2,7 @@
 //   cuda_pt [--spp N] [-o out.png] <scene.json>          (reference: src/main.cpp:9-25, src/lib/configurations.cpp:7-45)
 // following the call sequence of execute_cli_version (src/cli/cli.cpp:62-116): read scene, create_buffers,
 // max_iterations = spp, spp x path_trace, synchronize, send_to_preview, write PNG, stage timings.
-// Extra flags: --max-bounces N (the reference's cap is a compile-time 50), --denoise, --denoise-albedo, --method, --gpu,
+// Extra flags: --max-bounces N (the reference's cap is a compile-time 50), --denoise, --denoise-albedo, --denoise-variance [--variance-sigma S] (5s), --method, --gpu,
 // --lens-radius R / --focus-distance F (the thin lens), --tonemap C / --exposure EV / --auto-exposure / --key K / --white W (the display transform), --environment FILE / --environment-scale S / --environment-size N (environment lighting; --dump-environment FILE: the decoded picture and the map, for tests, no GPU), --textures (image textures), --normal-maps (normal maps), --dump-scene FILE (flattened scene arrays, for tests; needs no GPU), --gpus N, --display final|color|normal|depth
 // (DisplayBufferType of send_to_preview, path_tracer.cu:487-520: which buffer the PNG shows), --dump-raw FILE (the
 // accumulated float framebuffers as they are: "PTRF", width, height, 7 as uint32, then colour rgb, normal xyz and
@@ -49,6 +49,8 @@ struct CliConfigurations {  // configurations.hpp:11-15
   int max_bounces = 50;
   bool denoise = false;
   bool denoise_albedo = false;  // (implies denoise)
+  bool denoise_variance = false;  // (implies denoise)
+  float variance_sigma = 16.0f;
   bool megakernel = false;
   bool direct_light = false;
   bool environment_light = false;
@@ -85,6 +87,9 @@ void usage()
                "      --denoise        run the A-Trous denoiser before writing the image\n"
                "      --denoise-albedo  denoise irradiance, not colour: the first-hit albedo is divided out before the filter and multiplied\n"
                "                       back after it, so that a texture's detail passes the filter (implies --denoise)\n"
+               "      --denoise-variance  steer the filter's colour weight by a per-pixel variance estimate, not by one constant: low-contrast\n"
+               "                       edges stay and fireflies go (implies --denoise)\n"
+               "      --variance-sigma S  how many variances of colour distance that weight tolerates (default 16; finite, > 0)\n"
                "      --method M       streaming (default) | megakernel\n"
                "      --direct-light   a light sample with a shadow ray at every diffuse hit (needs --method megakernel)\n"
                "      --roulette K     Russian roulette at every bounce >= K but the last, unbiased (0 = off, the default; K in [0,64])\n"
@@ -140,6 +145,8 @@ CliConfigurations parse_cli_args(int argc, char** argv)
     else if (a == "--max-bounces") c.max_bounces = std::stoi(need("max-bounces"));
     else if (a == "--denoise") c.denoise = true;
     else if (a == "--denoise-albedo") c.denoise = c.denoise_albedo = true;
+    else if (a == "--denoise-variance") c.denoise = c.denoise_variance = true;
+    else if (a == "--variance-sigma") c.variance_sigma = std::stof(need("variance-sigma"));
     else if (a == "--method") c.megakernel = need("method") == "megakernel";
     else if (a == "--direct-light") c.direct_light = true;
     else if (a == "--environment-light") c.environment_light = true;
@@ -347,7 +354,7 @@ bool write_raw(const std::string& path, uint32_t width, uint32_t height, Fetch f
 //   {"window": [w, h], "iterations_per_frame": 2, "events": [
 //      {"frames": 3},                      loop turns: run_cuda + one PNG each
 //      {"key": "W", "count": 5},           GLFW_REPEAT of W/A/S/D/R/F            {"mouse": [dx, dy]}   right-drag, pixels
-//      {"space": true}  {"resize": [w, h]}  {"denoise": true}  {"denoise_albedo": true}  {"display": "normal"}  {"method": "megakernel"}
+//      {"space": true}  {"resize": [w, h]}  {"denoise": true}  {"denoise_albedo": true}  {"denoise_variance": true}  {"display": "normal"}  {"method": "megakernel"}
 //      {"max_iterations": 64}  {"filter_size": 10}  {"speed": 0.5}  {"position": [x, y, z]}  {"reset": true} ]}
 // A turn runs "iterations_per_frame" iterations (default 1) instead of as many as fit into 16 ms, so that a replay
 // gives the same frames every time; "budget_ms": 16 restores the reference's clock.
@@ -406,6 +413,8 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
   path_tracer.create_buffers(resolution, scene_desc);
   bool enable_denoising = configs.denoise;
   path_tracer.denoise_albedo = configs.denoise_albedo;
+  path_tracer.denoise_variance = configs.denoise_variance;
+  path_tracer.denoise_variance_sigma = configs.variance_sigma;
   DisplayBufferType display = configs.display;
   if (configs.megakernel) path_tracer.current_gpu_method = GPUMethod::megakernel;
   path_tracer.direct_light = configs.direct_light;
@@ -455,6 +464,8 @@ int run_replay(const CliConfigurations& configs, SceneDescription& scene_desc)
       enable_denoising = j->b;
     } else if (const Json* j = ev->find("denoise_albedo")) {  // (no reference equivalent: the denoiser's albedo factorisation)
       path_tracer.denoise_albedo = j->b;
+    } else if (const Json* j = ev->find("denoise_variance")) {  // (no reference equivalent: the variance-guided passes)
+      path_tracer.denoise_variance = j->b;
     } else if (const Json* j = ev->find("display")) {
       display = j->str == "color" ? DisplayBufferType::color : j->str == "normal" ? DisplayBufferType::normal
                 : j->str == "depth" ? DisplayBufferType::depth : DisplayBufferType::final;
@@ -795,6 +806,8 @@ try {
   path_tracer.normal_maps = configs.normal_maps || scene_desc.normal_maps;  // (... and its normal-map binding)
   path_tracer.roulette = configs.roulette;
   path_tracer.denoise_albedo = configs.denoise_albedo;
+  path_tracer.denoise_variance = configs.denoise_variance;
+  path_tracer.denoise_variance_sigma = configs.variance_sigma;
   if (scene_desc.camera.lens_radius > 0.0f) path_tracer.lens = {scene_desc.camera.lens_radius, scene_desc.camera.focus_distance};
   path_tracer.display = configs.tone;
   path_tracer.environment = scene_desc.environment;

@@ -60,6 +60,10 @@ public:
   // the denoiser's albedo factorisation (ptc_set_param "denoise_albedo"): denoise filters the colour divided by the
   // first-hit albedo and multiplies it back, so that a texture's detail passes the filter.  Both methods.
   bool denoise_albedo = false;
+  // the variance-guided passes (ptc_set_param "denoise_variance"): denoise estimates a per-pixel variance of the plane
+  // it filters and divides the colour distance by denoise_variance_sigma x that, not by the constant color_weight.  Both methods.
+  bool denoise_variance = false;
+  float denoise_variance_sigma = 16.0f;  // finite and > 0 (ptc_set_denoise_variance)
   int roulette = 0;  // Russian roulette at every bounce >= this but the last, 0 = off (both methods; ptc_set_param "roulette", [0, 64])
   // the thin lens (ptc_set_lens): aperture radius (0 = the pinhole, the default) and the distance of the plane in
   // focus, world units; both methods
@@ -253,6 +257,37 @@ public:
     check(ptc_denoise_albedo(ctx_, out.albedo.data(), out.irradiance.data(), out.rays.data()), "denoise_albedo");
     return out;
   }
+  // the estimate stage alone (ptc_denoise_variance), whatever denoise_variance says: per pixel the variance and its 3 x 3 Gaussian
+  struct DenoiseVariance {
+    std::vector<float> variance, prefiltered;
+  };
+  [[nodiscard]] DenoiseVariance denoise_variance_planes(UResolution resolution)
+  {
+    push_fields();
+    const size_t n = (size_t)resolution.width * resolution.height;
+    DenoiseVariance out{std::vector<float>(n), std::vector<float>(n)};
+    check(ptc_denoise_variance(ctx_, out.variance.data(), out.prefiltered.data()), "denoise_variance");
+    return out;
+  }
+  [[nodiscard]] ptc_denoise_variance_stats denoise_variance_stats() const
+  {
+    ptc_denoise_variance_stats s{};
+    check(ptc_get_denoise_variance_stats(ctx_, &s), "denoise_variance_stats");
+    return s;
+  }
+  // the whole mode on the host from caller planes (ptc_check_denoise_variance; no GPU): colour and normal 3 floats a pixel, depth one
+  static void check_denoise_variance(const std::vector<float>& colour, const std::vector<float>& normal, const std::vector<float>& depth,
+                                     const ptc_camera& camera, UResolution resolution, const ptc_denoiser_params& weights, float sigma,
+                                     std::vector<float>& variance_out, std::vector<float>& result_out)
+  {
+    const size_t n = (size_t)resolution.width * resolution.height;
+    if (colour.size() != 3u * n || normal.size() != 3u * n || depth.size() != n) throw std::runtime_error("check_denoise_variance: plane sizes");
+    variance_out.assign(n, 0.0f);
+    result_out.assign(3u * n, 0.0f);
+    if (ptc_check_denoise_variance(colour.data(), normal.data(), depth.data(), &camera, resolution.width, resolution.height, &weights, sigma,
+                                   variance_out.data(), result_out.data()) != PTC_OK)
+      throw std::runtime_error("check_denoise_variance: refused");
+  }
   [[nodiscard]] ptc_denoise_albedo_stats denoise_albedo_stats() const
   {
     ptc_denoise_albedo_stats s{};
@@ -315,6 +350,14 @@ private:
       check(ptc_set_param(ctx_, "denoise_albedo", denoise_albedo ? 1 : 0), "denoise_albedo");
       denoise_albedo_pushed_ = denoise_albedo;
     }
+    if (denoise_variance != denoise_variance_pushed_) {
+      check(ptc_set_param(ctx_, "denoise_variance", denoise_variance ? 1 : 0), "denoise_variance");
+      denoise_variance_pushed_ = denoise_variance;
+    }
+    if (denoise_variance_sigma != denoise_variance_sigma_pushed_) {
+      check(ptc_set_denoise_variance(ctx_, denoise_variance_sigma), "denoise_variance_sigma");
+      denoise_variance_sigma_pushed_ = denoise_variance_sigma;
+    }
     if (roulette != roulette_pushed_) {
       check(ptc_set_param(ctx_, "roulette", roulette), "roulette");
       roulette_pushed_ = roulette;
@@ -344,6 +387,8 @@ private:
   bool textures_pushed_ = false;
   bool normal_maps_pushed_ = false;
   bool denoise_albedo_pushed_ = false;
+  bool denoise_variance_pushed_ = false;
+  float denoise_variance_sigma_pushed_ = 16.0f;
   int roulette_pushed_ = 0;
   Lens lens_pushed_{};
   std::shared_ptr<const EnvironmentMap> environment_pushed_;

@@ -164,6 +164,25 @@ def check_demodulate(colour, albedo):
     return irr, eff
 
 
+def check_denoise_variance(colour, normal, depth, camera, filter_size=10, normal_weight=0.30, position_weight=0.25, sigma=16.0):
+    """The whole "denoise_variance" mode of DESIGN section 5s on the host (ptc_check_denoise_variance; no GPU needed) from caller
+    planes: colour and normal float32 [h, w, 3], depth float32 [h, w], camera a Camera -> (variance float32 [h, w]: the estimate,
+    result float32 [h, w, 3]: the last guided pass's colour, or None when filter_size < 1)"""
+    c = np.ascontiguousarray(colour, dtype=np.float32)
+    n = np.ascontiguousarray(normal, dtype=np.float32)
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3 or n.shape != c.shape or d.shape != c.shape[:2]:
+        raise ValueError("check_denoise_variance: colour and normal are [h, w, 3], depth is [h, w]")
+    h, w = d.shape
+    cam = camera.to_c()
+    prm = _capi.ptc_denoiser_params(int(filter_size), 0.0, float(normal_weight), float(position_weight))
+    var, out = np.zeros((h, w), dtype=np.float32), np.zeros((h, w, 3), dtype=np.float32)
+    _capi.check(_capi.lib().ptc_check_denoise_variance(c.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
+                                                       C.cast(C.byref(cam), C.c_void_p), w, h, C.cast(C.byref(prm), C.c_void_p), float(sigma),
+                                                       var.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return var, (out if int(filter_size) >= 1 else None)
+
+
 def normal_map_decode_table():
     """The 256-entry decode table of a normal map (ptc_normal_map_decode_table; host-side, no GPU needed)"""
     out = np.zeros(256, dtype=np.float32)
@@ -685,6 +704,36 @@ class PathTracer:
         self._check(self._lib.ptc_denoise_albedo(self._ctx, alb.ctypes.data_as(C.c_void_p), irr.ctypes.data_as(C.c_void_p),
                                                  rays.ctypes.data_as(C.c_void_p)))
         return {"albedo": alb, "irradiance": irr, "rays": rays}
+
+    @property
+    def denoise_variance_sigma(self):
+        """sigma of set_param("denoise_variance", 1) (ptc_set_denoise_variance): the prefiltered variance is
+        multiplied by it under the colour distance.  Finite and > 0; default 16."""
+        s = C.c_float(0.0)
+        self._check(self._lib.ptc_get_denoise_variance(self._ctx, C.byref(s)))
+        return float(s.value)
+
+    @denoise_variance_sigma.setter
+    def denoise_variance_sigma(self, sigma):
+        self._check(self._lib.ptc_set_denoise_variance(self._ctx, float(sigma)))
+
+    def denoise_variance(self):
+        """The estimate stage of set_param("denoise_variance", 1) alone (ptc_denoise_variance), whatever the parameter
+        says, on the plane denoise() would filter now -> dict(variance float32 [h, w]: the 7 x 7 weighted variance of that plane;
+        prefiltered float32 [h, w]: its 3 x 3 Gaussian, what the first pass divides by).  Needs a traced frame and the whole frame in
+        this context."""
+        self._push_fields()
+        w, h = self._resolution
+        var, pre = np.zeros((h, w), dtype=np.float32), np.zeros((h, w), dtype=np.float32)
+        self._check(self._lib.ptc_denoise_variance(self._ctx, var.ctypes.data_as(C.c_void_p), pre.ctypes.data_as(C.c_void_p)))
+        return {"variance": var, "prefiltered": pre}
+
+    def denoise_variance_stats(self):
+        """Counters of the last call that ran the estimate stage (denoise under "denoise_variance" 1, or denoise_variance): pixels, those
+        whose first prefiltered variance is below the floor; stage_ms: the stage's launches since restart, while events are enabled."""
+        s = _capi.ptc_denoise_variance_stats()
+        self._check(self._lib.ptc_get_denoise_variance_stats(self._ctx, C.byref(s)))
+        return {"pixels": int(s.pixels), "floored": int(s.floored), "stage_ms": float(s.stage_ms)}
 
     def denoise_albedo_stats(self):
         """Counters of the last call that ran the albedo stage (denoise under "denoise_albedo" 1, or denoise_albedo): pixels, those whose

@@ -58,6 +58,8 @@ def replay(scene, script, device=0, max_bounces=50):
                 state["denoise"] = bool(ev["denoise"])
             elif "denoise_albedo" in ev:                                         # (no reference equivalent)
                 pt.set_param("denoise_albedo", 1 if ev["denoise_albedo"] else 0)
+            elif "denoise_variance" in ev:                                       # (no reference equivalent)
+                pt.set_param("denoise_variance", 1 if ev["denoise_variance"] else 0)
             elif "display" in ev:
                 state["display"] = getattr(DisplayBufferType, ev["display"], DisplayBufferType.final)
             elif "method" in ev:

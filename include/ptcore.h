@@ -295,6 +295,20 @@ int ptc_set_trace_variant(ptc_ctx* ctx, int variant);
  *                      the passes as before; the stage's own time and counters: ptc_get_denoise_albedo_stats.  A filter_size < 1
  *                      runs no stage.  Two float4 planes per pixel, allocated by the first call that needs them and released with
  *                      the frame.  0 launches exactly what was launched before the parameter existed.  Any time
+ *   "denoise_variance" DENOISING (default 0; an extension): 1 = ptc_denoise steers the colour weight by a per-pixel
+ *                      variance instead of the constant color_weight.  An estimate stage (k_variance_estimate) takes, per pixel, the
+ *                      variance of the plane the passes filter -- the accumulated colour, or the irradiance under "denoise_albedo" 1
+ *                      -- over its 7 x 7 window (coordinates clamped to the image; tap weights exp(-(|dn|^2 / normal_weight +
+ *                      |dx|^2 / position_weight)); centred: the weighted mean first, then the weighted squared distance from it, summed
+ *                      over the channels).  A pass at step s keeps the 5 x 5 taps, their kernel weights, their coordinate contract and
+ *                      the normal and position terms of the plain pass; its colour term is |dc|^2 / (sigma x v + 2^-53), v the 3 x 3
+ *                      Gaussian (1 2 1; 2 4 2; 1 2 1) / 16 of the current variance plane around the centre pixel at one-pixel spacing;
+ *                      it writes c' = sum w c / sum w and v' = sum w^2 v / (sum w)^2, and v' travels with c' through the ping-pong.
+ *                      color_weight is not read.  sigma: ptc_set_denoise_variance.  The passes count into ptc_profile's
+ *                      denoise_passes and denoise_ms as the plain ones do; the stage's own time and counters:
+ *                      ptc_get_denoise_variance_stats.  "denoise_variant" picks the passes' kernel as before.  A filter_size < 1 runs
+ *                      no stage.  Two float planes per pixel, allocated by the first call that needs them and released with the
+ *                      frame.  0 launches exactly what was launched before the parameter existed.  Any time
  *   "slot_offset"     added to every compacted slot index before the material RNG is seeded (path_tracer.cu:300).  A
  *                      rank of a multi-GPU run that numbers its paths locally (ptc_set_interleave) sets rank * (pixels of
  *                      the largest share) so that no two ranks draw the same random streams; 0 (default) = the reference
@@ -499,6 +513,34 @@ int ptc_get_denoise_albedo_stats(ptc_ctx* ctx, ptc_denoise_albedo_stats* out);
  * and irradiance_out[i] = colour[i] / effective_out[i], one binary32 operation each -- the header the kernels run.  n values in every
  * array.  PTC_ERR_INVALID: a NULL with n > 0. */
 int ptc_check_demodulate(const float* colour, const float* albedo, uint32_t n, float* irradiance_out, float* effective_out);
+
+/* sigma of "denoise_variance" (default 16, the choice of its sweep): the prefiltered variance is multiplied by it under the colour distance,
+ * so two pixels of equal variance under pure noise have a mean exponent of -2 / sigma.  PTC_ERR_INVALID for a value that is not
+ * finite or is <= 0; the value set before stays.  Any time. */
+int ptc_set_denoise_variance(ptc_ctx* ctx, float sigma);
+int ptc_get_denoise_variance(ptc_ctx* ctx, float* sigma);
+/* The estimate stage of "denoise_variance" alone, whatever that parameter says, on the plane ptc_denoise would filter now (the
+ * irradiance while "denoise_albedo" is 1, else the accumulated colour) with the weights set now, returned to host arrays, each of
+ * which may be NULL -- variance_out one float per pixel (the estimate), prefiltered_out one float per pixel (its 3 x 3 Gaussian, what
+ * the first pass divides by).  Pixels in row order.  The final buffer is not touched.  ptc_denoise's refusals: PTC_ERR_INVALID without
+ * a traced frame and for a context that does not own the whole frame (ptc_set_rows, ptc_set_interleave).  Synchronises. */
+int ptc_denoise_variance(ptc_ctx* ctx, float* variance_out, float* prefiltered_out);
+/* pixels and floored (pixels whose first prefiltered variance is below the floor 2^-53) of the last call that ran the estimate stage
+ * -- ptc_denoise under "denoise_variance" 1 with a filter_size >= 1, or ptc_denoise_variance; zeros before the first.  stage_ms: the
+ * summed duration of the stage's launches (k_variance_estimate and k_variance_prefilter) since ptc_restart, while events are enabled
+ * (ptc_set_profiling).  Synchronises. */
+typedef struct ptc_denoise_variance_stats {
+  uint64_t pixels, floored;
+  double stage_ms;
+} ptc_denoise_variance_stats;
+int ptc_get_denoise_variance_stats(ptc_ctx* ctx, ptc_denoise_variance_stats* out);
+/* The whole mode on the host (no GPU, no context) from the caller's planes, with the per-tap functions of the header the kernels
+ * compile: colour and normal 3 floats per pixel, depth one, pixels in row order; the view rays of `camera` at width x height (both
+ * >= 2); weights: filter_size, normal_weight and position_weight are read, color_weight is not.  variance_out (may be NULL): the
+ * estimate, one float per pixel.  result_out (may be NULL): the last pass's colour, 3 floats per pixel; untouched when filter_size < 1.
+ * PTC_ERR_INVALID: a NULL input, a bad size, a sigma that ptc_set_denoise_variance would refuse. */
+int ptc_check_denoise_variance(const float* colour, const float* normal, const float* depth, const ptc_camera* camera, uint32_t width,
+                               uint32_t height, const ptc_denoiser_params* weights, float sigma, float* variance_out, float* result_out);
 
 /* PathTracer::send_to_preview (path_tracer.cu:487-520): tonemap to RGBA8 (4 bytes/pixel, rows of
  * this context only).  dst is a device pointer if dst_is_device != 0 (the reference always writes a
